@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- Mpixels/s of the baseline-JPEG decode hot path on 4K 4:2:0 batches (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N > 1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run does what the headline needs: it builds the batch, warms up, times K steps, checks that every timed step did
+the whole work (unconverged_chunk_runs, picture statuses), writes --dump-outputs and prints the JSON line with the kernels'
+HIP-event times of the timed region and the roofline objects computed from them (traffic from the committed collection under
+profiles/).  --full adds everything else below: the parity gate, one_pass_latency_ms, host_side, the rocprofv3 traffic
+passes, the one-stream pass, extra_configs, e2e_from_bytes(_pool) and cpu_baseline (--no-* switch single legs off again).
+
+--dump-outputs DIR writes what the timed path computed in its last step (rank 0's batch): the decoded RGB of every picture
+is W*H*3 bytes (51 GB at the headline size), so DIR/rgb.npy holds a fixed, seeded sample of it, float32 [pictures, pixels, 3]
+(dump_outputs()).  The inputs are synthetic pictures from fixed seeds, so equal arguments give equal inputs.
 
 A *step* = one pass of the whole hot path (entropy decode -> dequant -> IDCT -> upsample -> RGB) over the rank's batch:
 `--images-per-gpu` synthetic 3840x2160 4:2:0 q75 baseline JPEGs (BASELINE.json configs[4] is 16384 images over 8 GPUs
@@ -10,34 +20,36 @@ HBM before the timed region; outputs stay in HBM.  Images are independent, so ra
 global batch goes to rank i mod N.  The harness needs one barrier and one MAX-reduce of the elapsed time; both go over
 gloo (host TCP) -- the north star says "no RCCL", and that holds for the harness as well as for the data path.
 
-The JSON line carries, besides the contract fields:
+The JSON line carries, besides the contract fields ([full] = with --full only):
   roofline      what SURVEY.md s8(d) defines.  stages=all (the default, the headline): achieved = sum over the images of
                 B_e2e = S + 3*W*H (compressed bytes in, packed RGB out) per step / wall time per step of the timed region, frac =
                 that / the 8 TB/s HBM3E peak; `kernel` = the kernel class with the largest HIP-event time in the timed region,
                 whose own per-launch figures (algorithmic bytes, average launch duration, fraction of peak) are in
                 `dominant_kernel`; `traffic` = HBM bytes per step from rocprofv3 PMC passes (FETCH_SIZE x 2 + WRITE_SIZE, separate
-                passes, /opt/skills/guides/MI355X_MICROARCH.md) -- observed in this run when rocprofv3 is on the box
-                (`traffic_source`: "observed ..."), else scaled from the committed collection under profiles/.
+                passes, as the MI355X microarchitecture guide prescribes) -- observed in this run with --full when rocprofv3 is on
+                the box (`traffic_source`: "observed ..."), else scaled from the committed collection under profiles/.
                 stages=pixels (the config-4 stage-B sweep): the pixel kernel on B_idct = 128*n_blocks + 3*W*H.
   kernel_rooflines  every kernel class on its own algorithmic bytes, from the timed region's event times
                 (the library overlaps the entropy stages of two chunks and stage B on three streams: these durations include
                 the contention); idct_color also with the bytes it physically moves (frac_physical)
-  roofline_isolated / kernel_rooflines_isolated  the same from a one-stream pass over the same batch: stand-alone durations
+  roofline_isolated / kernel_rooflines_isolated  [full] the same from a one-stream pass over the same batch: stand-alone durations
   upload_side   GPU work of the upload, outside the timed region (HIP-event time for the unique pictures scaled to the batch): 0
                 since round 5 -- the host writes the lane-interleaved scan pool while it packs the scans for the transfer; with
                 --device-destuff the de-stuffing kernels and k_scan_interleave
-  one_pass_latency_ms  ms_per_step is the pipelined rate (the steps are enqueued back to back, one wait); this is ONE pass of the same
-                batch on its own, enqueue to the end of its last kernel (this rank)
+  one_pass_latency_ms  [full] ms_per_step is the pipelined rate (the steps are enqueued back to back, one wait); this is ONE pass of
+                the same batch on its own, enqueue to the end of its last kernel (this rank); null in a plain run
   kernels       per kernel class: launches, total ms
-  parity        the gate behind `value`: every picture of the timed batch compared on the device with its
+  host_side     [full] parse and batch-creation times of the unique pictures, and the parser on one thread
+  parity        [full] the gate behind `value`: every picture of the timed batch compared on the device with its
                 unique original (bit-equal), pictures of the batch compared with the CPU oracle (coefficients equal, RGB
                 within 1), and the pictures the cpu_baseline leg decodes compared with a REF_COMPAT decode on the GPU.
                 The run fails if any check fails.
-  extra_configs the other measurement rows of SURVEY s8(d): BASELINE config 4 (4096 x 1080p) whole path and stage B alone
+  extra_configs [full] the other measurement rows of SURVEY s8(d): BASELINE config 4 (4096 x 1080p) whole path and stage B alone
                 (the ">= 60 % of HBM on B_idct" sweep), 4K at quality 50 and 90; each with Mpixels/s, Gbit/s of entropy-coded
                 data and the dominant kernel's roofline fraction
-  e2e_from_bytes  mjx_decode_batch from JPEG file bytes in host memory to RGB in HBM (parse + H2D + decode), Mpixels/s
-  cpu_baseline  the oracle (C restatement of the reference's algorithm, kind "port") on all host cores and on one core
+  e2e_from_bytes  [full] mjx_decode_batch from JPEG file bytes in host memory to RGB in HBM (parse + H2D + decode), Mpixels/s;
+                e2e_from_bytes_pool the same through the library's multi-GPU pool
+  cpu_baseline  [full] the oracle (C restatement of the reference's algorithm, kind "port") on all host cores and on one core
 """
 import argparse
 import json
@@ -69,14 +81,20 @@ def parse_args():
     ap.add_argument("--device-destuff", action="store_true", help="upload stuffed scans; FF00 compaction on the GPU at upload")
     ap.add_argument("--streams", type=int, default=0, choices=[0, 1, 2, 3], help="HIP streams of the context (0 = library default); with 2, "
                     "stage B of one chunk overlaps stage A of the next and per-kernel times include the contention")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the headline: parity gate, traffic passes, one-stream pass, extra configs, "
+                    "from-bytes legs, CPU baseline (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a fixed, seeded sample of the last timed step's RGB to DIR/rgb.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the all-core CPU baseline (0 = every core the job may use: affinity mask capped by the cgroup quota)")
-    ap.add_argument("--no-extra", action="store_true", help="skip extra_configs, e2e_from_bytes and the traffic passes (main line only)")
-    ap.add_argument("--no-traffic", action="store_true", help="do not run the rocprofv3 PMC passes that observe HBM traffic (roofline.traffic then comes from profiles/)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip extra_configs, e2e_from_bytes and the traffic passes (main line only)")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: do not run the rocprofv3 PMC passes that observe HBM traffic (roofline.traffic then comes from profiles/)")
     ap.add_argument("--traffic-images", type=int, default=256, help="pictures per launch in the PMC passes")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle legs of the parity gate (the on-device check stays)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the oracle legs of the parity gate (the on-device check stays)")
     ap.add_argument("--parity-images", type=int, default=16, help="pictures of the timed batch checked against the CPU oracle (decoded in parallel on the host cores)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def algorithmic_bytes(kind, by, nsub_total, nblk):
@@ -373,10 +391,40 @@ def cpu_baseline(datas, width, height, threads, keep_rgb):
     return out, [rgbs[i] for i in range(min(keep_rgb, len(rgbs))) if st[i] == 0], sample[:keep_rgb]
 
 
+def host_threads():
+    """Threads of the host-side pools (synthesis, parsing): the cores the job may use, at most 32."""
+    return min(32, usable_cores()[0])
+
+
 def make_inputs(mjx, width, height, subsampling, quality, seeds):
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(min(32, os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(host_threads()) as ex:
         return list(ex.map(lambda s: mjx.synth_jpeg(width, height, subsampling, quality, s), seeds))
+
+
+DUMP_SEED, DUMP_PICTURES, DUMP_PIXELS = 1234, 16, 1 << 18
+
+
+def dump_sample(n_pictures, pixels_per_picture):
+    """The sample --dump-outputs writes: sorted picture indices of the batch and sorted row-major pixel indices within a
+    picture (every pixel of pictures of at most DUMP_PIXELS), drawn from DUMP_SEED -- the same for the same arguments."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    pics = np.sort(rng.choice(n_pictures, size=min(n_pictures, DUMP_PICTURES), replace=False))
+    if pixels_per_picture <= DUMP_PIXELS:
+        return pics, np.arange(pixels_per_picture)
+    return pics, np.sort(rng.choice(pixels_per_picture, size=DUMP_PIXELS, replace=False))
+
+
+def dump_outputs(batch, directory):
+    """--dump-outputs: DIR/rgb.npy = float32 [pictures, pixels, 3], the decoded RGB of the pictures and pixels dump_sample()
+    picks (the pictures of a bench batch share one geometry): at most 16 x 2^18 x 3 x 4 B = 50 MB."""
+    import numpy as np
+    inf = batch.info(0)
+    pics, px = dump_sample(len(batch), inf["width"] * inf["height"])
+    rgb = np.stack([batch.rgb(int(i)).reshape(-1, 3)[px] for i in pics]).astype(np.float32)
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "rgb.npy"), rgb)
 
 
 def _any_rank(value):
@@ -394,15 +442,16 @@ def _any_rank(value):
 
 
 def run_config(mjx, ctx, datas, per_gpu, stages, steps, warmup, chunk_images=0, device_destuff=False, sync_all=None,
-               parity_images=0, host_side=None, latency_pass=False):
-    """Builds the device-resident batch (unique pictures uploaded once, tiled on the device), times `steps` passes, and runs
-    the on-device half of the parity gate.  Returns (record, batch, period) -- the caller closes the batch."""
+               parity_images=0, host_side=None, latency_pass=False, compare_tiled=True, dump_dir=None):
+    """Builds the device-resident batch (unique pictures uploaded once, tiled on the device), times `steps` passes, writes
+    dump_outputs() to `dump_dir` and, with `compare_tiled`, runs the on-device half of the parity gate.  Returns (record, batch)
+    -- the caller closes the batch."""
     from concurrent.futures import ThreadPoolExecutor
     period = len(datas)
     reps = max(1, per_gpu // period)
     per_gpu = reps * period
     t_h = time.perf_counter()
-    with ThreadPoolExecutor(min(32, os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(host_threads()) as ex:
         scans = list(ex.map(lambda d: mjx.ParsedScan(d, device_destuff=device_destuff), datas))
     t_parse = time.perf_counter() - t_h
     keep = stages == "pixels"
@@ -421,7 +470,7 @@ def run_config(mjx, ctx, datas, per_gpu, stages, steps, warmup, chunk_images=0, 
                 one[label] = v if label not in one else min(one[label], v)
         host_side.update({"files": len(datas), "parse_ms_per_file": round(1e3 * t_parse / len(datas), 3),
                           "parse_ms_per_file_one_thread": one,
-                          "parse_threads": min(32, os.cpu_count() or 1),
+                          "parse_threads": host_threads(),
                           "create_ms_per_file": round(1e3 * t_create / len(datas), 3),
                           "compressed_MB_per_file": round(sum(len(d) for d in datas) / len(datas) / 1e6, 3),
                           "note": "host marker walk + de-stuffing (threads), then planning + decode tables + H2D of the compressed "
@@ -470,6 +519,8 @@ def run_config(mjx, ctx, datas, per_gpu, stages, steps, warmup, chunk_images=0, 
     bad = [i for i in range(len(batch)) if batch.status(i) != mjx.OK]
     assert not bad or os.environ.get("MJX_BENCH_IGNORE_STATUS"), "images failed: %s" % bad[:8]     # (the switch: measurement builds that decode garbage)
     kms = batch.kernel_ms(reset=True)           # (the timed region's kernels; the pass below is not among them)
+    if dump_dir:
+        dump_outputs(batch, dump_dir)
     one_pass = 0.0
     if latency_pass:                            # (not in the PMC / rocprof runs: their collections must hold exactly `steps` passes)
         t1 = time.perf_counter()
@@ -491,7 +542,7 @@ def run_config(mjx, ctx, datas, per_gpu, stages, steps, warmup, chunk_images=0, 
                                    "k_scan_interleave for every scan, as before round 5)"}}
     # on-device half of the parity gate: every picture of the batch equals its unique original bit for bit
     n = len(batch)
-    if n > period:
+    if compare_tiled and n > period:
         mx, cnt = batch.compare_rgb(list(range(period, n)), batch, [i % period for i in range(period, n)])
         rec["tiled_compared"] = int(n - period)
         rec["tiled_max_abs_diff"] = int(mx.max())
@@ -690,6 +741,19 @@ def e2e_pool(mjx, datas, files_per_device, width, height):
                     "it), best of 3 calls; PCIe-inclusive, never part of `value`; slots[].ms = wall clock of the slot's own mjx_decode_batch"}
 
 
+def build_unless_read_only(ge):
+    """build() brings the native libraries up to date under lock files it creates in the tree.  A checkout this user may not
+    write (built by another user) is measured as build() left it: nothing can be rebuilt there, and the package's loaders
+    still refuse a tree in which a library was never built."""
+    import errno
+    try:
+        ge.build()
+    except OSError as e:
+        if e.errno not in (errno.EACCES, errno.EPERM, errno.EROFS):
+            raise
+        sys.stderr.write("bench.py: the tree is not writable here (%s); measuring the libraries build() left\n" % e)
+
+
 def main():
     args = parse_args()
     rank = int(os.environ.get("RANK", "0"))
@@ -700,10 +764,11 @@ def main():
     import torch                       # (first: libmjx.so must find torch's HIP runtime already loaded, not bring its own)
     import torch.distributed as dist
     import __graft_entry__ as ge
-    ge.build()
+    build_unless_read_only(ge)
     # ---- HBM traffic of one step, observed with rocprofv3 PMC passes in child processes (before this process touches the GPU) ----
+    full = args.full
     traffic = None
-    if rank == 0 and world == 1 and not args.no_extra and not args.no_traffic and args.stages == "all" and not profiler_attached():
+    if full and rank == 0 and world == 1 and not args.no_extra and not args.no_traffic and args.stages == "all" and not profiler_attached():
         traffic = observe_traffic(args)
     if traffic is None and args.width == 3840 and args.height == 2160 and args.quality == 75 and args.subsampling == "420":
         traffic = committed_traffic()            # (collected on this workload; other workloads: none)
@@ -731,7 +796,9 @@ def main():
     ctx = mjx.Context(device, profiling=True, throughput_plan=True)       # (the batches are tiled from 64 unique pictures: cut them like the batch they become)
     host_side = {}
     rec, batch = run_config(mjx, ctx, datas, args.images_per_gpu, args.stages, args.steps, args.warmup, args.chunk_images,
-                            args.device_destuff, sync_all, host_side=host_side, latency_pass=not args.no_extra)
+                            args.device_destuff, sync_all, host_side=host_side if full else None,
+                            latency_pass=full and not args.no_extra, compare_tiled=full,
+                            dump_dir=args.dump_outputs if rank == 0 else None)
     rec = reduce_record(rec, world)            # N > 1: MAX over the ranks of the wall clock and of every kernel class's time
     per_gpu, period, by, kernels = rec["per_gpu"], rec["period"], rec["by"], rec["kernels"]
     elapsed = rec["elapsed"]
@@ -757,18 +824,19 @@ def main():
         "bits_per_pixel": round(by["scan"] * 8 / max(by["pixels"], 1), 4),
         "kernels": kernels,
     }
-    out["host_side"] = host_side
+    if full:
+        out["host_side"] = host_side
     out["upload_side"] = rec["upload_side"]
     if rec["upload_side"]["ms_per_batch"] > 0:
         out["upload_side"]["value_with_interleave_in_the_step"] = round(by["pixels"] * world / ((elapsed / args.steps) + rec["upload_side"]["ms_per_batch"] / 1e3) / 1e6, 2)
 
-    # ---- parity gate: no number without it ----
+    # ---- parity gate, --full: every number of the full line stands behind it ----
     parity = {"tiled_images_compared_on_device": rec["tiled_compared"], "tiled_max_abs_diff": rec["tiled_max_abs_diff"],
               "tiled_differing_bytes": rec["tiled_differing_bytes"]}
     failures = []
     if rec["tiled_max_abs_diff"] != 0:
         failures.append("tiled pictures differ from their originals")
-    if not args.no_parity and args.stages == "all":
+    if full and not args.no_parity and args.stages == "all":
         op = oracle_parity(mjx, batch, datas, period, args.parity_images)
         parity.update({"images": op["images"], "max_abs_diff": op["max_abs_diff"], "t0_equal": op["t0_equal"],
                        "differing_fraction": op["differing_fraction"],
@@ -780,7 +848,7 @@ def main():
     batch.close()
 
     out.update(rooflines(rec, args.steps, args.stages, traffic))
-    if not args.no_extra and args.streams != 1:
+    if full and not args.no_extra and args.streams != 1:
         # The library runs the entropy stages of two chunks and stage B on three streams (overlapped), so the kernel durations of the
         # timed region above include the contention between them.  The same workload on one stream gives every kernel's
         # stand-alone duration.
@@ -801,7 +869,7 @@ def main():
         ctx1.close()
 
     extra = []
-    if not args.no_extra and world == 1 and args.stages == "all":
+    if full and not args.no_extra and world == 1 and args.stages == "all":
         small_steps = max(2, min(args.steps, 5))
         for name, w, h, q, n_img, stg in [("config4_1080p_whole_path", 1920, 1080, 75, 4096, "all"),
                                           ("config4_1080p_stage_B_only", 1920, 1080, 75, 4096, "pixels"),
@@ -824,7 +892,7 @@ def main():
                 failures.append(name + ": tiled pictures differ from their originals")
             extra.append(e)
         out["extra_configs"] = extra
-    if not args.no_extra and args.stages == "all":
+    if full and not args.no_extra and args.stages == "all":
         # from file bytes: every rank on its own GPU at the same time (N > 1: the ranks share the host's cores and its PCIe roots --
         # that contention is what the figure is for); the job's rate = all files / the slowest rank's time
         sync_all()
@@ -847,7 +915,7 @@ def main():
             except Exception as e:          # noqa: BLE001
                 out["e2e_from_bytes_pool"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    if rank == 0 and not args.no_cpu_baseline:
+    if full and rank == 0 and not args.no_cpu_baseline:
         # (N > 1: rank 0 times the CPU baseline while the other ranks wait at the closing barrier -- the host's cores are idle then,
         # as they are at N = 1; north star: "next to the reference CPU decoder timed on the same host cores in the same run")
         # (every picture the baseline leg decodes is kept and compared with a REF_COMPAT decode on the GPU)
@@ -860,8 +928,9 @@ def main():
             parity["ref_compat_max_abs_diff"] = rp["max_abs_diff"]
             if rp["max_abs_diff"] > 1:
                 failures.append("REF_COMPAT RGB differs from the CPU baseline's pictures by %d" % rp["max_abs_diff"])
-    parity["ok"] = not failures
-    out["parity"] = parity
+    if full:
+        parity["ok"] = not failures
+        out["parity"] = parity
     ctx.close()
     if world > 1:
         dist.barrier()

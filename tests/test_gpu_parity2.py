@@ -255,7 +255,7 @@ def test_bench_two_ranks_over_gloo_on_one_gpu(tmp_path):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--images-per-gpu", "64", "--width", "640", "--height", "480", "--unique", "16"]
+           "--images-per-gpu", "64", "--width", "640", "--height", "480", "--unique", "16", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -272,18 +272,43 @@ def test_bench_two_ranks_over_gloo_on_one_gpu(tmp_path):
 
 
 def test_bench_line_has_a_pool_leg_at_one_gpu():
-    """The N = 1 line times the library's own multi-GPU front (mjx_pool_decode_batch over every visible device; one here), so the
-    driver's run on an 8-GPU node measures it without a flag."""
+    """The N = 1 --full line times the library's own multi-GPU front (mjx_pool_decode_batch over every visible device; one here), so
+    the full run on an 8-GPU node measures it without a further flag."""
     import json
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--images-per-gpu", "64", "--width", "640",
-           "--height", "480", "--unique", "16", "--no-cpu-baseline", "--no-traffic"]
+           "--height", "480", "--unique", "16", "--no-cpu-baseline", "--no-traffic", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     pool = rec["e2e_from_bytes_pool"]
     assert pool["devices"] >= 1 and pool["files"] == 512 * pool["devices"] and pool["Mpixels/s"] > 0
     assert len(pool["slots"]) == pool["devices"] and all(s["ms"] > 0 and s["files"] > 0 and s["parse_threads"] >= 1 for s in pool["slots"])
+
+
+def test_plain_bench_line_and_dumped_outputs(mjx, orc, tmp_path):
+    """A plain run (no --full) prints the headline fields and none of the full line's legs, and --dump-outputs writes the last
+    timed step's RGB at the pictures and pixels bench.dump_sample() picks: float32, each within 1 of the CPU oracle's picture."""
+    import json
+    import subprocess
+    import bench
+    w, h, n, unique = 640, 480, 64, 16
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--images-per-gpu", str(n), "--width", str(w),
+           "--height", str(h), "--unique", str(unique), "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["unit"] == "Mpixels/s"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "f32" and rec["unconverged_chunk_runs"] == 0
+    assert not {"parity", "cpu_baseline", "extra_configs", "e2e_from_bytes", "roofline_isolated", "host_side"} & set(rec)
+    assert os.listdir(str(tmp_path / "out")) == ["rgb.npy"]
+    got = np.load(str(tmp_path / "out" / "rgb.npy"))
+    pics, px = bench.dump_sample(n, w * h)
+    assert got.dtype == np.float32 and got.shape == (len(pics), len(px), 3) and len(px) < w * h
+    datas = bench.make_inputs(mjx, w, h, "420", 75, bench.shard_seeds(0, 1, unique))
+    for k, i in enumerate(pics):                       # (picture i of the tiled batch is unique picture i % unique)
+        ref = orc.decode(datas[i % unique], layout=orc.LAYOUT_STD).rgb.reshape(-1, 3)[px].astype(np.float32)
+        assert np.abs(got[k] - ref).max() <= TOL, i
 
 
 # ---- multi-GPU front: per-device work queues, no collective (SURVEY s8(e)) -------------------------------------------------

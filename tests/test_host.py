@@ -596,6 +596,40 @@ def test_traffic_collection_sums_per_step_and_bench_refuses_per_launch_files(tmp
     assert old.get("basis") != "per_step"                     # (what committed_traffic() would have scaled to half the real traffic)
 
 
+def test_bench_dump_sample_is_fixed_and_at_most_64_mb():
+    """bench.py --dump-outputs: the same pictures and pixels for the same batch, distinct and in range, every pixel of a small
+    picture, and at most 64 MB of float32 RGB at the headline size."""
+    import numpy as np
+    import bench
+    pics, px = bench.dump_sample(2048, 3840 * 2160)
+    again = bench.dump_sample(2048, 3840 * 2160)
+    assert np.array_equal(pics, again[0]) and np.array_equal(px, again[1])
+    assert len(set(pics.tolist())) == len(pics) == bench.DUMP_PICTURES and 0 <= pics.min() and pics.max() < 2048
+    assert len(set(px.tolist())) == len(px) and 0 <= px.min() and px.max() < 3840 * 2160
+    assert len(pics) * len(px) * 3 * 4 <= 64 << 20
+    small_pics, small_px = bench.dump_sample(4, 100)
+    assert sorted(small_pics.tolist()) == [0, 1, 2, 3] and small_px.tolist() == list(range(100))
+
+
+def test_bench_measures_a_tree_it_may_not_write_but_not_a_failed_build():
+    """bench.py calls build(); in a checkout built by another user its lock files cannot be opened, and the run goes on with
+    the libraries build() left.  Any other failure of build() ends the run."""
+    import errno
+    import bench
+
+    class Tree:
+        def __init__(self, exc):
+            self.exc = exc
+
+        def build(self):
+            raise self.exc
+    for code in (errno.EACCES, errno.EPERM, errno.EROFS):
+        bench.build_unless_read_only(Tree(OSError(code, os.strerror(code), ".build.lock")))
+    for exc in (OSError(errno.ENOSPC, "no space"), RuntimeError("build step failed: hipcc")):
+        with pytest.raises(type(exc)):
+            bench.build_unless_read_only(Tree(exc))
+
+
 # ---- round 5: multi-scan pictures without the gather; what the planner decides per scan -----------------------------------------------
 @pytest.fixture(scope="module")
 def emul_lib(mjx):

@@ -26,7 +26,7 @@ run() {   # lib, env, mode
   local extra="" pre=""
   case "$3" in one) pre="MJX_STREAMS=1";; pixels) extra="--stages pixels --width 1920 --height 1080 --images-per-gpu 4096 --steps 5";; esac
   local e="$2"; [ "$e" = "-" ] && e=""
-  env $e $pre $GARBAGE MJX_LIB=$PWD/$1 timeout 900 python3 bench.py --no-cpu-baseline --no-extra --no-parity $extra "${@:4}" 2>/dev/null | show "$1" "$2" "$3"
+  env $e $pre $GARBAGE MJX_LIB=$PWD/$1 timeout 900 python3 bench.py --full --no-cpu-baseline --no-extra --no-parity $extra "${@:4}" 2>/dev/null | show "$1" "$2" "$3"
 }
 for r in $(seq $ROUNDS); do for L in $LIBS; do for E in "${ENVS[@]}"; do
   if [ "$MODE" = both ]; then run "$L" "$E" one "$@"; run "$L" "$E" default "$@"; else run "$L" "$E" "$MODE" "$@"; fi

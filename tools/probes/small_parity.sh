@@ -1,6 +1,6 @@
 # Round 5 probe: parity-gated bench lines for batches of small pictures (scans below one workgroup are cut shorter), the multi-scan
 # forms, and the headline; bench.py refuses timed regions in which a chunk had not converged.
-for wh in "256 256 32768" "512 512 16384" "1024 768 8192" "640 480 8192" "1920 1080 4096" "3840 2160 2048"; do set -- $wh; python bench.py --no-cpu-baseline --no-extra --width $1 --height $2 --images-per-gpu $3 2>&1 | grep '^{\|Assert' | python3 -c "
+for wh in "256 256 32768" "512 512 16384" "1024 768 8192" "640 480 8192" "1920 1080 4096" "3840 2160 2048"; do set -- $wh; python bench.py --full --no-cpu-baseline --no-extra --width $1 --height $2 --images-per-gpu $3 2>&1 | grep '^{\|Assert' | python3 -c "
 import sys,json
 t=sys.stdin.read()
 try:

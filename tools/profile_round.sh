@@ -8,7 +8,7 @@ R=$1
 O=gpurun_out/$R; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 Q="--no-cpu-baseline --no-extra --no-parity"
-timeout 900 python3 bench.py > $O/bench_2048x4K.json 2> $O/bench_2048x4K.err
+timeout 900 python3 bench.py --full > $O/bench_2048x4K.json 2> $O/bench_2048x4K.err
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/stats2 -o out --output-format csv -- python3 bench.py $Q --steps 3 --warmup 1 > $O/stats2.log 2>&1
 export MJX_STREAMS=1
 timeout 300 python3 bench.py $Q > $O/bench_2048x4K_1stream.json 2>/dev/null
