@@ -97,7 +97,6 @@ struct mjx_ctx {
     bool single_decode = true;
     bool merge_memo = true;        // two generations per subsequence in the merge rounds (MJX_MERGE_MEMO=0: one, as before round 5)
     bool planar_direct = true;     // multi-scan pictures: stage B reads the scans' streams (MJX_PLANAR_DIRECT=0: always through the gather kernels)
-    bool emit_merge_listed = true;  // MJX_EMIT_MERGE_LISTED=0: the first merge round of such pictures runs its head slices in place, as for the others
     // (emit_min_sub_bits = the long subsequences of scans of 0.79 MB and more, mjx_huff.h: with the 4096 .. 5120-bit subsequences of
     // shorter scans the warm-up is half a subsequence -- 4096 x 1080p 15.3-16.4 ms per step at 2048 / 1024 / 512 bits of warm-up
     // against 14.9-15.1 on the two-pass kernels, 2048 x 4K at quality 50 24.1-24.7 against 23.8 --, so those keep the two passes)
@@ -107,8 +106,6 @@ struct mjx_ctx {
     std::mutex batch_mu;            // mjx_decode_batch: one call at a time per context (the pinned arena is shared state)
     int nstreams = 2;
     bool profiling = false;
-    bool upload_kernels_apart = true;   // mjx_decode_batch: upload-time kernels on a decode stream, the upload stream carries transfers only (MJX_UPLOAD_APART=0: all on the upload stream)
-    bool group_alt_stream = true;       // ... and every second group's entropy stage on the third stream (MJX_GROUP_ALT=0: all on the first)
     bool throughput_plan = false;   // mjx_ctx_set_throughput_plan: never cut a batch into short subsequences (a base that will be tiled)
     // mjx_decode_batch: pinned arena the files of a call are de-stuffed into; kept between calls (fresh pages cost ~0.35 us
     // per KB to fault in and unmap again -- four times the parsing itself), released with the context
@@ -818,7 +815,7 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
                                   k > 0 ? b->d_mismatch + ci * kMisWords + k - 1 : nullptr,
                                   // (a chunk of pictures whose lanes warmed up: a fifth of the subsequences re-decode, not all of them --
                                   // the first round, too, only lists its items and the straggler kernel decodes them packed)
-                                  k == 0 && (phases & PH_SYNC) && !(c.has_emit && !c.has_spec && b->ctx->emit_merge_listed), SCR(d_esub),
+                                  k == 0 && (phases & PH_SYNC) && !(c.has_emit && !c.has_spec), SCR(d_esub),
                                   c.max_nsub ? c.max_nsub - 1 : 0u, SCR(d_gen), gen_stride);
                 prof_end(b, st);
             }
@@ -876,7 +873,7 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
         if (c.plane_words) HIPOK(hipMemsetAsync(SCR(d_planes), 0, size_t(c.plane_words) * 8, sp));
         // (dense: over ~1400 bytes of scan per stage-B tile -- more than the 2048 stream entries the kernel's default form prefetches)
         launch_idct_color(sp, c.max_tiles, nimg, b->idct_lds + b->ctx->idct_lds_pad, imgs, SCR(d_entries), SCR(d_tile_eoff), dcb, b->d_qm, b->d_rgb, c.mode_mask, SCR(d_planes), b->d_img_flags,
-                          c.scan_bytes > uint64_t(c.tiles) * (1400u * tile_mcus_420() / 32u), c.layout_mask, b->ctx->idct_lds_pad);
+                          c.scan_bytes > uint64_t(c.tiles) * (1400u * tile_mcus_420() / 32u), c.layout_mask);
         if (c.plane_words) launch_ref_color(sp, c.max_pixel_wgs, nimg, imgs, SCR(d_planes), b->d_rgb, b->d_img_flags);
         prof_end(b, sp);
         if (sp != st) {
@@ -1399,11 +1396,10 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
             // transfers, so that the DMA engine goes from one group's bytes straight to the next group's -- with the de-stuffing
             // and interleave kernels between them it idled 0.15 ms per group (a kernel, a small copy and two engine hand-overs).
             // The kernels go to the decode stream the group's entropy stage runs on, behind an event that marks the copies.
-            b->alt_entropy_stream = async_upload && alt_entropy_stream && ctx->stream3 && ctx->group_alt_stream;
-            const bool apart = async_upload && ctx->upload_kernels_apart;
-            hipStream_t ks = apart ? (b->alt_entropy_stream ? ctx->stream3 : ctx->stream) : up;
+            b->alt_entropy_stream = async_upload && alt_entropy_stream && ctx->stream3;
+            hipStream_t ks = async_upload ? (b->alt_entropy_stream ? ctx->stream3 : ctx->stream) : up;
             auto kernels_behind_copies = [&]() -> int {
-                if (!apart || b->copied) return MJX_OK;
+                if (!async_upload || b->copied) return MJX_OK;
                 HIPOK(hipEventCreateWithFlags(&b->copied, hipEventDisableTiming));
                 HIPOK(hipEventRecord(b->copied, up));
                 HIPOK(hipStreamWaitEvent(ks, b->copied, 0));
@@ -1608,16 +1604,7 @@ extern "C" int mjx_ctx_create(int device, mjx_ctx **out)
     mjx_ctx *c = new (std::nothrow) mjx_ctx;
     if (!c) return MJX_ERR_NOMEM;
     c->device = device;
-    {
-        // MJX_HIGH_PRIO = entropy | pixels | none: which of the two decode streams is created with the high priority
-        int lo = 0, hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        const char *hp = std::getenv("MJX_HIGH_PRIO");
-        const bool ent_high = hp && std::strcmp(hp, "entropy") == 0 && hi != lo;
-        const hipError_t e1 = ent_high ? hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi)
-                                       : hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-        if (e1 != hipSuccess) { (void)hipGetLastError(); delete c; return MJX_ERR_DEVICE; }
-    }
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); delete c; return MJX_ERR_DEVICE; }
     if (hipStreamCreateWithFlags(&c->upload, hipStreamNonBlocking) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return MJX_ERR_DEVICE; }
     if (const char *e = std::getenv("MJX_CACHE_GB")) c->cache_limit = size_t(std::max(0L, std::atol(e))) << 30;
     c->nstreams = 2;
@@ -1631,29 +1618,24 @@ extern "C" int mjx_ctx_create(int device, mjx_ctx **out)
     if (const char *e = std::getenv("MJX_SINGLE_DECODE")) c->single_decode = std::atoi(e) != 0;
     if (const char *e = std::getenv("MJX_PLANAR_DIRECT")) c->planar_direct = std::atoi(e) != 0;
     if (const char *e = std::getenv("MJX_MERGE_MEMO")) c->merge_memo = std::atoi(e) != 0;
-    if (const char *e = std::getenv("MJX_EMIT_MERGE_LISTED")) c->emit_merge_listed = std::atoi(e) != 0;
     if (const char *e = std::getenv("MJX_EMIT_CP_BITS")) c->emit_cp_bits = uint32_t(std::max(long(kCpBits), std::atol(e))) / uint32_t(kCpBits) * uint32_t(kCpBits);
     if (const char *e = std::getenv("MJX_EMIT_WARM_BITS")) c->emit_warm_bits = uint32_t(std::max(0L, std::atol(e))) / 32u * 32u;
     if (const char *e = std::getenv("MJX_EMIT_MIN_SUB_BITS")) c->emit_min_sub_bits = uint32_t(std::max(long(kCpBits), std::atol(e)));
     if (const char *e = std::getenv("MJX_EMIT_HEAD")) c->emit_head = uint32_t(std::max(0L, std::min(long(kEmitHeadGroups), std::atol(e))));      // (tests: no head room = every prefix that grows falls back)
     if (const char *e = std::getenv("MJX_LATENCY_SUB_BITS")) c->latency_sub_bits = uint32_t(std::max(512L, std::min(long(kSubseqBits), std::atol(e))));
     if (const char *e = std::getenv("MJX_DC_ONE_PASS")) c->dc_one_pass = std::atoi(e) != 0;
-    if (const char *e = std::getenv("MJX_UPLOAD_APART")) c->upload_kernels_apart = std::atoi(e) != 0;
-    if (const char *e = std::getenv("MJX_GROUP_ALT")) c->group_alt_stream = std::atoi(e) != 0;
     if (const char *e = std::getenv("MJX_LOOP_FAULT")) c->loop_fault = std::atoi(e) != 0;
     if (const char *e = std::getenv("MJX_DC_FAULT")) c->dc_fault = std::atoi(e) != 0;
     if (const char *e = std::getenv("MJX_MERGE_LOOP")) c->merge_loop_max = uint32_t(std::min(192L, std::max(0L, std::atol(e))));
     if (c->nstreams == 2) {
-        // With two streams stage B's gets the higher priority (MJX_PIXEL_PRIORITY=0: equal): its workgroups are placed first when
+        // With two streams stage B's gets the higher priority (the entropy stream has none): its workgroups are placed first when
         // a CU frees resources, so the pixel kernel keeps close to its stand-alone pace and the entropy kernels fill what it
         // leaves.  With three (two chunks' entropy stages side by side: the write pass waits for HBM, the synchronisation
         // passes for instruction issue) equal priorities measured better: 30.1 against 30.5 ms per step, 31.3 with two streams.
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        const char *pe = std::getenv("MJX_PIXEL_PRIORITY"), *hp = std::getenv("MJX_HIGH_PRIO");
-        const bool prio = hp ? std::strcmp(hp, "pixels") == 0 : (pe ? std::atoi(pe) != 0 : !third);
-        const hipError_t e2 = (prio && hi != lo) ? hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, hi)
-                                                 : hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking);
+        const hipError_t e2 = (!third && hi != lo) ? hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, hi)
+                                                   : hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking);
         if (e2 != hipSuccess) { (void)hipGetLastError(); c->stream2 = nullptr; c->nstreams = 1; }
         if (third && c->stream2 && hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); c->stream3 = nullptr; }
     }
@@ -2324,8 +2306,8 @@ extern "C" int mjx_batch_geometry(const mjx_batch *b, uint64_t *subsequences, ui
     // scans de-stuffed on the device: the host planned with the stuffed length as an upper bound, the exact number of
     // subsequences is in the device's copy of the images (k_destuff_prefix / k_restart_geometry)
     std::vector<DevImage> dev_images;
-    // (the upload-time kernels run on the upload stream or -- groups of a pipelined list, upload_kernels_apart -- on a decode
-    // stream behind the copies; b->uploaded is recorded behind them on whichever stream ran them)
+    // (the upload-time kernels run on the upload stream or -- groups of a pipelined list -- on a decode stream behind the
+    // copies; b->uploaded is recorded behind them on whichever stream ran them)
     const bool upload_done = b->has_stuffed && !b->himages.empty() && hipSetDevice(b->ctx->device) == hipSuccess &&
                              (b->uploaded ? hipEventSynchronize(b->uploaded) : hipStreamSynchronize(b->ctx->upload)) == hipSuccess;
     if (upload_done) {

@@ -251,16 +251,6 @@ MJX_UNROLL
     if (o < total) {
         const uint32_t at = (first + o - before) * 8u;
         cell.phys = uint32_t(stream_phys(s, at, q.rows));
-        // (measurement builds only, garbage out: the tile's groups read from consecutive addresses; ... from the tile's own
-        // first row on, so that tiles read different addresses; from three neighbouring columns in turn, what numbering the
-        // groups across the columns would touch at best)
-#if defined(MJX_EXP_QUAD_CONTIG)
-        cell.phys = uint32_t(stream_phys(s0 & ~3u, 0, q.rows)) + o * 8u;
-#elif defined(MJX_EXP_QUAD_CONTIG2)
-        cell.phys = uint32_t(stream_phys(s0 & ~3u, (j0 >> 3) * 8u, q.rows)) + o * 8u;
-#elif defined(MJX_EXP_QUAD_ZIP)
-        cell.phys = uint32_t(stream_phys((s0 & ~3u) + o % 3u, (o / 3u) * 8u, q.rows));
-#endif
         cell.k_lo = (o == 0u) ? j0 & 7u : 0u;
         cell.k_hi = (o == total - 1u && (j1 & 7u) != 0u) ? j1 & 7u : 8u;
     }
@@ -387,8 +377,7 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
                        const uint32_t *entries, const uint32_t *tile_eoff, const int32_t *dcbuf, const float *qmult,
                        uint8_t *rgb, uint32_t mode_mask, unsigned long long *planes, const uint32_t *img_flags,
                        bool dense /* the chunk's linear streams are dense (many entries per tile): deeper prefetch in the 4:2:0 kernel */,
-                       uint32_t layout_mask /* bit 0: pictures with a linear stream, bit 1: with a quad-interleaved one */,
-                       size_t lds_pad = 0 /* part of `lds` that is occupancy padding (a test knob): the 4:2:0 form sizes its own tile and adds it */);
+                       uint32_t layout_mask /* bit 0: pictures with a linear stream, bit 1: with a quad-interleaved one */);
 // multi-scan pictures: component streams (raster order) -> the picture's stream in MCU order, tile offsets, DC values
 void launch_planar_gather(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint32_t *entries,
                           uint32_t *tile_eoff, int32_t *dcbuf, uint32_t *img_flags, bool copy);

@@ -61,9 +61,6 @@ __device__ __forceinline__ uint32_t cps_byte_off(uint32_t idx)
     return (idx / kCpRow) * (kMaxCp * kCpRowBytes) + (idx % kCpRow) * 8;
 }
 
-#ifndef MJX_GRID_WG_FAST
-#define MJX_GRID_WG_FAST 0      // 1: the layout of rounds 1-3 (a picture's workgroups fast), for A/B
-#endif
 // The grid of the entropy kernels that walk (picture, workgroup of the picture): the PICTURE is the fast dimension.  Workgroups go
 // to the eight XCDs round robin in launch order; with the picture's workgroups fast and a grid of 4 x pictures, the fourth
 // workgroup of every picture -- the short one, or an empty one when another picture of the chunk needs four -- always met the
@@ -74,17 +71,14 @@ __device__ __forceinline__ uint32_t cps_byte_off(uint32_t idx)
 // it -- put all the long pictures' second and third workgroups onto the same two XCDs (1024 three-scan 4K files, one stream:
 // counting pass 3.9 ms, write pass 13.0; the same bits as luma + interleaved chroma, three images per file: 1.65 and 6.6).
 // (picture_of_slot: for every kernel whose fast grid dimension is the picture)
-#ifndef MJX_GRID_ROTATE
-#define MJX_GRID_ROTATE 1
-#endif
 __device__ __forceinline__ uint32_t picture_of_slot(uint32_t x, uint32_t n)
 {
-    if (!MJX_GRID_ROTATE || x >= (n & ~7u)) return x;                       // (the last, partial run keeps its order)
+    if (x >= (n & ~7u)) return x;                                            // (the last, partial run keeps its order)
     return (x & ~7u) | ((x + (((x >> 3) * 0x9E3779B1u) >> 29)) & 7u);
 }
-__device__ __forceinline__ uint32_t entropy_grid_image() { return MJX_GRID_WG_FAST ? blockIdx.y : picture_of_slot(blockIdx.x, gridDim.x); }
-__device__ __forceinline__ uint32_t entropy_grid_wg() { return MJX_GRID_WG_FAST ? blockIdx.x : blockIdx.y; }
-inline dim3 entropy_grid(uint32_t max_wg, uint32_t nimg) { return MJX_GRID_WG_FAST ? dim3(max_wg, nimg) : dim3(nimg, max_wg); }
+__device__ __forceinline__ uint32_t entropy_grid_image() { return picture_of_slot(blockIdx.x, gridDim.x); }
+__device__ __forceinline__ uint32_t entropy_grid_wg() { return blockIdx.y; }
+inline dim3 entropy_grid(uint32_t max_wg, uint32_t nimg) { return dim3(nimg, max_wg); }
 
 struct GlobalCps {
     unsigned char *base;    // the chunk's checkpoint array (wave-uniform)
@@ -143,18 +137,10 @@ struct LaneRing {
         if constexpr (GROUP >= 4) {
             static_assert(GROUP == 4 || GROUP == 8, "one or two 16-byte stores");
             const uint4 *src = reinterpret_cast<const uint4 *>(ring + (flushed & (kRing - 1)));
-#ifdef MJX_EXP_STORE_SMALL              // (measurement builds only: the same store instructions, into 8 KB per image -- they stay in L2)
-            uint4 *dst = reinterpret_cast<uint4 *>(out + (flushed & 0x7f8u));
-#else
             uint4 *dst = reinterpret_cast<uint4 *>(ALIGNED ? out + size_t(flushed / GROUP) * gstride : out + flushed);
-#endif
             const uint4 v0 = src[0], v1 = src[GROUP / 4 - 1];
-#ifndef MJX_EXP_NOSTORE                 // (measurement builds only: what the write pass costs without its global stores)
             dst[0] = v0;
             if constexpr (GROUP == 8) dst[1] = v1;
-#else
-            asm volatile("" :: "v"(v0.x), "v"(v0.y), "v"(v0.z), "v"(v0.w), "v"(v1.x), "v"(v1.y), "v"(v1.z), "v"(v1.w), "v"(dst));
-#endif
         } else if constexpr (GROUP == 2) {
             *reinterpret_cast<uint2 *>(out + flushed) = *reinterpret_cast<const uint2 *>(ring + (flushed & (kRing - 1)));
         } else {
@@ -384,18 +370,11 @@ __device__ __forceinline__ SubLoc locate_sub(const DevImage &im, const HuffImage
 // would also queue behind the scattered stores.)  Instead every lane owns kWinDwords big-endian dwords in LDS; the
 // wave restages all its windows together (wave-uniform branch, 16-byte loads) whenever one lane is about to run
 // out, about every 40 symbols, and the per-symbol refills only touch LDS.
-#ifndef MJX_WIN_DWORDS
-#define MJX_WIN_DWORDS 8
-#endif
-constexpr int kWinDwords = MJX_WIN_DWORDS;
+constexpr int kWinDwords = 8;                             // two 16-byte pieces: what the restage in wave_decode moves
 #ifndef MJX_WIN_PAD
 #define MJX_WIN_PAD 1
 #endif
 constexpr int kWinStride = kWinDwords + MJX_WIN_PAD;      // odd stride: lanes spread over all banks
-#ifndef MJX_WIN_PREFETCH
-#define MJX_WIN_PREFETCH 1
-#endif
-static_assert(MJX_WIN_DWORDS == 8 || !MJX_WIN_PREFETCH, "the prefetching restage moves windows of two 16-byte pieces");
 struct LdsWindow {
     const unsigned char *lds;    // lane's window
     uint32_t wbase;              // stream byte offset of the window's first dword (as of the last fill the caller noted)
@@ -476,7 +455,6 @@ __device__ __forceinline__ SubseqState wave_decode(bool live, SubseqState entry,
     WaveStamp sp;
     if (WRITE) sp.begin();
 #endif
-#if MJX_WIN_PREFETCH
     // Round 6: the pieces a restage will write are requested right behind the restage before it, into registers -- a restage used to be
     // load, wait for L2 / HBM, write, with the whole wave parked (a fifth of an emitting wave's cycles in the stamps).  Between two
     // restages a lane moves on by less than a window, so what it will need is two of the three pieces behind its window's first one:
@@ -489,9 +467,7 @@ __device__ __forceinline__ SubseqState wave_decode(bool live, SubseqState entry,
         pb = g.piece(min(wb + 2u, last_piece));
         pc = g.piece(min(wb + 3u, last_piece));
     }
-#endif
     while (running) {                                                          // per-lane loop: finished lanes are masked off
-#if MJX_WIN_PREFETCH
         if (__builtin_amdgcn_ballot_w64(win.rp >= win_end)) {                  // uniform over the active lanes: restage
             const uint32_t q1 = (st.wn - 4u) >> 4;                             // (w0, w1 are in registers; wn - 4 is read next)
             if (q1 != wb) {
@@ -506,12 +482,6 @@ __device__ __forceinline__ SubseqState wave_decode(bool live, SubseqState entry,
             pb = g.piece(min(wb + 2u, last_piece));
             pc = g.piece(min(wb + 3u, last_piece));
         }
-#else
-        if (__builtin_amdgcn_ballot_w64(win.rp >= win_end)) {                  // uniform over the active lanes: restage
-            window_fill(my_win, g, (st.wn - 4u) & ~15u);                       // (w0, w1 are in registers; wn - 4 is read next)
-            win.rp = win_addr + ((st.wn - 4u) & 15u);
-        }
-#endif
 #ifdef MJX_STAMP
         if (WRITE) { sp.at(0); (void)symbol_step<WRITE, PAIRSTEP>(st, win, lut, h, blk, sink, sp); sp.at(5); }
         else
@@ -1505,14 +1475,9 @@ extern "C" __global__ __launch_bounds__(kHuffWg) void k_huff_write(const DevImag
         sink.tile_idx = (first_start + im.tile_blocks - 1) / im.tile_blocks;
         sink.next_tile_blk = sink.tile_idx * im.tile_blocks;
     }
-#ifdef MJX_EXP_WRITE_CP      // (measurement build: what an emitting pass pays for recording checkpoints as the counting pass does)
-    GlobalCps cpw{reinterpret_cast<unsigned char *>(g_cps), cps_byte_off(im.sub_off + (live ? s : 0u)), 0};
-    wave_decode<true, 1>(live && live_entry, e, end_bit, blk, blk_limit, gbits, s_win + threadIdx.x * kWinStride, lut, *h, sink, cpw, 0, e);
-#else
     (void)g_cps;
     NoCheckpoints nocp;
     wave_decode<true, 0>(live && live_entry, e, end_bit, blk, blk_limit, gbits, s_win + threadIdx.x * kWinStride, lut, *h, sink, nocp, 0, e);
-#endif
     sink.flush_groups();                                                   // (the rings hold one flush period, no more)
     for (uint32_t it = 1; __builtin_amdgcn_ballot_w64(sink.ac_ring.off < pad_to); it++) {
         if (sink.ac_ring.off < pad_to) sink.ac_ring.push(0u);              // null entry
@@ -2627,43 +2592,18 @@ __device__ __forceinline__ void store4(uint8_t *dst, const Rgb4 &v, bool aligned
 // A workgroup walks kTilesPerWg consecutive tiles of one image.  While it transforms tile t it already holds the loads
 // of tile t+1 in flight (stream offsets, up to kPrefetch entries per lane, the lane's DC), so the HBM round trips of a
 // tile overlap the arithmetic of the previous one instead of sitting on the workgroup's critical path.
-#ifndef MJX_PREFETCH
-#define MJX_PREFETCH 8
-#endif
 #ifndef MJX_PREFETCH_DENSE
 #define MJX_PREFETCH_DENSE 12
 #endif
 #ifndef MJX_TILES_PER_WG
 #define MJX_TILES_PER_WG 16
 #endif
-constexpr int kPrefetch = MJX_PREFETCH;         // stream entries per lane held in registers (2048 per tile; the rest is read when the tile is scattered)
+constexpr int kPrefetch = 8;                    // stream entries per lane held in registers (2048 per tile; the rest is read when the tile is scattered)
 constexpr int kPrefetchDense = MJX_PREFETCH_DENSE;   // ... in the 4:2:0 kernel's form for dense streams (3072 per tile: quality 90 and up), chosen per chunk by the host
-static_assert(MJX_PREFETCH == 8 && MJX_PREFETCH_DENSE > 8, "scatter batches of 4, 6, 8 and the full depth");
+static_assert(kPrefetchDense > kPrefetch, "scatter batches of 4, 6, 8 and the full depth");
 constexpr int kTilesPerWg = MJX_TILES_PER_WG;
-// The 4:2:0 kernel has two forms.  MJX_WIDE420 = 1 (round 6, MODE 3 below): 16 lanes per MCU, tiles of 16 MCUs = 25 KB of LDS, the
-// inverse DCT split into a column pass (two lanes per block) and a row pass fused with the colour step (a lane per 8 x 2 pixels) --
-// twice the waves per LDS byte of the other form.  MJX_WIDE420 = 0: 8 lanes per MCU, tiles of 32 MCUs = 52 KB, a lane per block
-// for the whole transform (rounds 1-5, MODE 1).
-#ifndef MJX_WIDE420
-#define MJX_WIDE420 0
-#endif
-#ifndef MJX_TILE420
-#define MJX_TILE420 (MJX_WIDE420 ? 16 : 32)
-#endif
-constexpr uint32_t kTile420 = MJX_TILE420;        // MCUs per tile of the 4:2:0 kernel
-constexpr uint32_t kLanes420 = kTile420 * (MJX_WIDE420 ? 16 : 8);
-constexpr int kMode420 = MJX_WIDE420 ? 3 : 1;     // the kernel form (template MODE) that takes the pictures of DevImage::mode 1
-static_assert(!MJX_WIDE420 || kTile420 == 16, "the wide form's lane maps are written for 256 lanes = 16 MCUs");
-// MODE 3: an MCU's six blocks lie in three SUPER-ROWS of kWRow floats -- (Y00, Y01), (Y10, Y11), (Cb, Cr) --, 128 values + 4 of padding
-// (an odd number of 16-byte slots: the 16 lanes of a ds_read_b128 group, one MCU apart, fall into 16 different slots).  Inside a
-// super-row, lane q (0..3) of the column pass owns the eight floats  m * 32 + 8 q .. + 7  of every row pair m (0..3):
-//   coefficients   Y, block side sd = q >> 1, columns c = 4 (q & 1) .. + 3:   (r >> 1) * 32 + 8 q + (r & 1) * 4 + (c & 3)
-//                  chroma, columns c = 2 q, 2 q + 1, both components:          (r >> 1) * 32 + 8 q + (r & 1) * 4 + (c & 1) * 2 + comp
-//   after the column pass (written back in place)
-//                  Y:       (r >> 1) * 32 + sd * 16 + c * 2 + (r & 1)      -- (row 2m, row 2m+1) of a column side by side: the row pass's pairs
-//                  chroma:  unchanged                                       -- (Cb, Cr) of a column side by side
-constexpr uint32_t kWRow = 132, kWMcu = 3 * kWRow;
-constexpr uint32_t wide_tile_bytes() { return kTile420 * kWMcu * 4; }
+constexpr uint32_t kTile420 = 32;                 // MCUs per tile of the 4:2:0 kernel
+constexpr uint32_t kLanes420 = kTile420 * 8;      // ... and a lane per block
 
 template <int PF>
 struct TileFetch {
@@ -2693,8 +2633,8 @@ __device__ __forceinline__ void tile_fetch(const uint32_t *__restrict__ src, con
 // the tile's i-th store group (+ 256 per further round) -- all eight entries of the 32-byte group, two 16-byte loads -- and
 // masks what belongs to the neighbouring tiles (k_lo / k_hi).  QuadFetch<R>: R rounds are prefetched; a tile of the bench
 // content has ~190 groups, at quality 90 ~380.  (Half a group per lane, so that a wave's load touches 32 rows instead of 64 twice
-// over: 16.1 instead of 15.8 ms per 2048 pictures in stage B.  The same groups read from consecutive addresses --
-// -DMJX_EXP_QUAD_CONTIG2, garbage out -- 14.9: the spread over rows shared with the neighbours costs 0.9 ms)
+// over: 16.1 instead of 15.8 ms per 2048 pictures in stage B.  The same groups read from consecutive addresses -- a measurement
+// build, garbage out, HISTORY.md s3.2 -- 14.9: the spread over rows shared with the neighbours costs 0.9 ms)
 template <int R>
 struct QuadFetch {
     uint32_t ncells;                                    // the tile's groups
@@ -2776,23 +2716,13 @@ __device__ __forceinline__ void quad_mask(uint32_t *ent, uint32_t k_lo, uint32_t
 template <int MODE>
 __device__ __forceinline__ uint32_t dump_bytes()
 {
-    // (MODE 3: the four padding words of super-rows 0..7 -- 32 lanes, 32 banks)
-    if (MODE == 3) return (threadIdx.x & 7u) * (kWRow * 4u) + (128u + ((threadIdx.x >> 3) & 3u)) * 4u;
     return (threadIdx.x & 127u) * uint32_t(kPixStride * 4) + (64u + ((threadIdx.x >> 3) & 3u)) * 4u;
-}
-// MODE 3: where block b of the tile (MCU order, Y Y Y Y Cb Cr) keeps its coefficients -- bytes into the tile, to which the position's
-// table entry is added (s_nat: 64 entries for luminance, 64 for chrominance)
-__device__ __forceinline__ uint32_t wide_block_bytes(uint32_t b)
-{
-    const uint32_t t = (b * 171u) >> 10, j = b - 6u * t;
-    const uint32_t in_mcu = j < 4u ? (j >> 1) * (kWRow * 4u) + (j & 1u) * 64u : 2u * kWRow * 4u + (j & 1u) * 4u;
-    return t * (kWMcu * 4u) + in_mcu;
 }
 
 template <int MODE>
 __device__ __forceinline__ uint32_t comp_of_block(uint32_t b, const uint8_t *s_comp)
 {
-    if (MODE == 1 || MODE == 3) {                           // Y Y Y Y Cb Cr: block b of the tile, b < 256
+    if (MODE == 1) {                                        // Y Y Y Y Cb Cr: block b of the tile, b < 256
         const uint32_t j = b - 6u * ((b * 171u) >> 10);     // (171 / 1024: exact quotient by 6 below 512)
         return j < 4u ? 0u : j - 3u;
     }
@@ -2821,18 +2751,18 @@ __device__ __forceinline__ void scatter_at(const uint32_t *ent, const uint32_t *
 #pragma unroll
     for (int k = 0; k < N; k++) pos[k] = (ent[k] >> 16) & 63u;
 #pragma unroll
-    for (int k = 0; k < N; k++) comp[k] = comp_of_block<MODE>((MODE == 1 || MODE == 3) ? b[k] : (b[k] < nblk ? b[k] : 0u), s_comp);
+    for (int k = 0; k < N; k++) comp[k] = comp_of_block<MODE>(MODE == 1 ? b[k] : (b[k] < nblk ? b[k] : 0u), s_comp);
 #pragma unroll
     for (int k = 0; k < N; k++) {
         qm[k] = s_qm[comp[k] * 64u + pos[k]];
-        nat[k] = s_nat[MODE == 3 ? pos[k] + (comp[k] ? 64u : 0u) : pos[k]];
+        nat[k] = s_nat[pos[k]];
     }
     unsigned char *base = reinterpret_cast<unsigned char *>(tile_f);
     const uint32_t dump = dump_bytes<MODE>();
 #pragma unroll
     for (int k = 0; k < N; k++) {
         const bool ok = b[k] < nblk && pos[k] != 0;           // pos == 0 marks a null entry (the write pass fills up its runs with them)
-        const uint32_t at = ok ? (MODE == 3 ? wide_block_bytes(b[k]) : b[k] * uint32_t(kPixStride * 4)) + nat[k] * 4u : dump;
+        const uint32_t at = ok ? b[k] * uint32_t(kPixStride * 4) + nat[k] * 4u : dump;
 #if defined(MJX_EXP_NO_SCATTER_STORE)  // (measurement build, garbage out: the scatter phase without its LDS stores)
         asm volatile("" :: "v"(at), "v"(float(int32_t(int16_t(ent[k] & 0xffffu))) * qm[k]));
 #else
@@ -3075,15 +3005,6 @@ __device__ __forceinline__ void load4(const float *tile, const GenShape &g, uint
     }
 }
 
-#ifndef MJX_PIX_XCHG
-#define MJX_PIX_XCHG 1
-#endif
-#ifndef MJX_PIX_PKADD
-#define MJX_PIX_PKADD 1
-#endif
-#ifndef MJX_FETCH_EARLY
-#define MJX_FETCH_EARLY 1
-#endif
 // (y.x + t.x, y.y + t.x) and (y.x + t.y, y.y + t.y): one v_pk_add_f32 each, the second operand's half chosen by op_sel / op_sel_hi
 __device__ __forceinline__ float_pair pk_add_lo(float_pair y, float_pair t)
 {
@@ -3133,7 +3054,7 @@ __device__ __forceinline__ void pixels_420(uint32_t width, uint32_t height, uint
 #if defined(MJX_EXP_PLAIN_READS)       // (measurement build, garbage out: plain reads where the exchanges with zero are, no zero-fill pass either)
     if (false) {
 #else
-    if (XCHG && MJX_PIX_XCHG) {
+    if (XCHG) {
 #endif
         // An interior tile: every sample of the tile is read exactly once in this phase, by exactly one lane -- so the read is an
         // exchange with zero (ds_wrxchg), and the tile is clean for the next one's coefficients without a zero-fill pass
@@ -3190,7 +3111,6 @@ __device__ __forceinline__ void pixels_420(uint32_t width, uint32_t height, uint
         if (!INTERIOR && (py >= height || npix == 0)) break;
         const ChromaTerms c0 = chroma_terms(cb[j].x, cr[j].x), c1 = chroma_terms(cb[j].y, cr[j].y);
         Rgb p[4];
-#if MJX_PIX_PKADD
         // two pixels per addition (v_pk_add_f32, the chroma term broadcast to both halves by op_sel): 12 packed instead of 24 plain
         // additions per lane and step.  A packed instruction takes 4 cycles of the SIMD whatever the occupancy, a plain one 2 -- when
         // two or more of the SIMD's waves have one ready, 4 for a lone wave (tools/probes/op_cost_probe.hip): never slower, and
@@ -3204,20 +3124,11 @@ __device__ __forceinline__ void pixels_420(uint32_t width, uint32_t height, uint
             q[2] = Rgb{r23.x, g23.x, b23.x}; q[3] = Rgb{r23.y, g23.y, b23.y};
         };
         rows(ya[j], p);
-#else
-        p[0] = ycc_to_rgb(ya[j].x, c0); p[1] = ycc_to_rgb(ya[j].y, c0);
-        p[2] = ycc_to_rgb(ya[j].z, c1); p[3] = ycc_to_rgb(ya[j].w, c1);
-#endif
         uint8_t *dst = col + size_t(rp) * 2 * width * 3;
         if (INTERIOR) store_rgb4(dst, pack4(p));
         else store4(dst, pack4(p), aligned, npix);
         if (INTERIOR || py + 1 < height) {
-#if MJX_PIX_PKADD
             rows(yb[j], p);
-#else
-            p[0] = ycc_to_rgb(yb[j].x, c0); p[1] = ycc_to_rgb(yb[j].y, c0);
-            p[2] = ycc_to_rgb(yb[j].z, c1); p[3] = ycc_to_rgb(yb[j].w, c1);
-#endif
             if (INTERIOR) store_rgb4(dst + size_t(width) * 3, pack4(p));
             else store4(dst + size_t(width) * 3, pack4(p), aligned, npix);
         }
@@ -3365,140 +3276,7 @@ extern "C" __global__ __launch_bounds__(256) void k_ref_color(const DevImage *im
     dst[0] = uint8_t(word); dst[1] = uint8_t(word >> 8); dst[2] = uint8_t(word >> 16);
 }
 
-// ---- MODE 3: the wide 4:2:0 form (round 6; layout: kWRow above) ----------------------------------------------------------------
-// Phase 2, the column pass: a lane owns four columns of a luminance block, or two columns of both chrominance blocks of an MCU --
-// eight rows x four floats, one ds_read_b128 per row, two packed 8-point transforms down the columns (the two columns of a pair, or
-// the Cb and the Cr column, side by side in packed fp32 instructions), eight ds_write_b128 back to where the rows came from.
-// Lanes 0 .. 8T-1 are luminance (MCU t = lane % T, then super-row and q), lanes 8T .. 12T-1 chrominance: the kind is uniform over a
-// wave, and the 16 lanes of a ds_read_b128 group are 16 MCUs of one q -- 16 different 16-byte slots (kWMcu / 4 = 99 is odd).
-__device__ __forceinline__ void wide_column_pass(float *tile_f, uint32_t nm)
-{
-    constexpr uint32_t T = kTile420;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t t = tid % T, g = tid / T;                 // g: 0..7 luminance (super-row g >> 2, q = g & 3), 8..11 chrominance (q = g - 8)
-    if (g >= 12u || t >= nm) return;
-    const bool chroma = g >= 8u;
-    float4 *p = reinterpret_cast<float4 *>(tile_f + t * kWMcu + (chroma ? 2u : g >> 2) * kWRow + 8u * (g & 3u));
-    float_pair a[8], b[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const float4 v = p[(r >> 1) * 8 + (r & 1)];
-        a[r] = float_pair{v.x, v.y};
-        b[r] = float_pair{v.z, v.w};
-    }
-    idct8(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]);
-    idct8(b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7]);
-    if (chroma) {
-#pragma unroll
-        for (int r = 0; r < 8; r++) p[(r >> 1) * 8 + (r & 1)] = make_float4(a[r].x, a[r].y, b[r].x, b[r].y);
-    } else {
-#pragma unroll
-        for (int m = 0; m < 4; m++) {
-            p[m * 8] = make_float4(a[2 * m].x, a[2 * m + 1].x, a[2 * m].y, a[2 * m + 1].y);
-            p[m * 8 + 1] = make_float4(b[2 * m].x, b[2 * m + 1].x, b[2 * m].y, b[2 * m + 1].y);
-        }
-    }
-}
-
-__device__ __forceinline__ void store_rgb4_plain(uint8_t *dst, const Rgb4 &v)
-{
-#if defined(MJX_EXP_NO_RGB_STORE)
-    asm volatile("" :: "v"(v.a), "v"(v.b), "v"(v.c), "v"(dst));
-    return;
-#endif
-    *reinterpret_cast<Rgb4 *>(dst) = v;
-}
-
-// Phase 3, row pass + colour: lane -> (row pair k of the MCU, side sd, MCU t) = 8 x 2 pixels.  It takes the two luminance rows as
-// eight (row 2m, row 2m+1) pairs -- 64 contiguous bytes -- and row k of both chrominance blocks as eight (Cb, Cr) pairs, runs one
-// packed 8-point transform along each, keeps the four chrominance samples over its pixels (columns 4 sd .. 4 sd + 3; the other side's
-// lane computes the same transform for the other four) and converts: 2 x 24 bytes, two 12-byte stores per row.  A wave's 64 lanes
-// write the 8-pixel halves of 16 MCUs of two row pairs: 768 contiguous bytes per row from each pair of store instructions (plain
-// stores: L2 merges the two halves of a line; as streaming stores the same shape took 19.8 instead of 9.1 ms per 51 GB,
-// tools/probes/rgb_store_probe.hip).
-//   XCHG   the tile holds all its MCUs: the luminance rows are read as an exchange with zero and the chrominance rows -- read by both
-//          sides' lanes -- are cleared by them, two pieces each, behind the reads: the tile is clean for the next one
-//   BOUNDS pixels may lie outside the picture, or rows are not 4-byte aligned: stores predicated per pixel
-template <bool XCHG, bool BOUNDS>
-__device__ __forceinline__ void pixels_wide(uint32_t width, uint32_t height, uint32_t mcux, float *tile, uint32_t m0, uint32_t nm,
-                                            uint8_t *out_img, bool aligned)
-{
-    constexpr uint32_t T = kTile420;
-    constexpr bool INTERIOR = XCHG && !BOUNDS;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t t = tid % T, sd = (tid / T) & 1u, k = tid / (2u * T);
-    if (!XCHG && t >= nm) return;
-    const uint32_t m = m0 + t;
-    const uint32_t mx = m % mcux, my = m / mcux;
-    float *yb = tile + t * kWMcu + (k >> 2) * kWRow + (k & 3u) * 32u + sd * 16u;
-    float *cb = tile + t * kWMcu + 2u * kWRow + (k >> 1) * 32u + (k & 1u) * 4u;
-    float_pair y[8], c[8];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const float4 v = *reinterpret_cast<const float4 *>(cb + 8 * q);
-        c[2 * q] = float_pair{v.x, v.y};
-        c[2 * q + 1] = float_pair{v.z, v.w};
-    }
-    if (XCHG && MJX_PIX_XCHG) {
-        // (one statement with its wait: the compiler does not track LDS operations inside asm, see pixels_420)
-        const f32x2 zero = {0.0f, 0.0f};
-        const uint32_t ay = uint32_t(uintptr_t((const __attribute__((address_space(3))) float *)(yb)));
-        f32x4 y0, y1, y2, y3;
-        asm volatile(
-            "ds_wrxchg2_rtn_b64 %0, %4, %5, %5 offset1:1\n\t"
-            "ds_wrxchg2_rtn_b64 %1, %4, %5, %5 offset0:2 offset1:3\n\t"
-            "ds_wrxchg2_rtn_b64 %2, %4, %5, %5 offset0:4 offset1:5\n\t"
-            "ds_wrxchg2_rtn_b64 %3, %4, %5, %5 offset0:6 offset1:7\n\t"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(y0), "=&v"(y1), "=&v"(y2), "=&v"(y3)
-            : "v"(ay), "v"(zero)
-            : "memory");
-        y[0] = float_pair{y0.x, y0.y}; y[1] = float_pair{y0.z, y0.w};
-        y[2] = float_pair{y1.x, y1.y}; y[3] = float_pair{y1.z, y1.w};
-        y[4] = float_pair{y2.x, y2.y}; y[5] = float_pair{y2.z, y2.w};
-        y[6] = float_pair{y3.x, y3.y}; y[7] = float_pair{y3.z, y3.w};
-        // the chrominance row: this side's lane clears pieces 2 sd and 2 sd + 1 (every lane of the wave has read by now: the reads
-        // above are earlier instructions of the same wave, and a wave's LDS instructions execute in order)
-        *reinterpret_cast<float4 *>(cb + 16u * sd) = make_float4(0.f, 0.f, 0.f, 0.f);
-        *reinterpret_cast<float4 *>(cb + 16u * sd + 8u) = make_float4(0.f, 0.f, 0.f, 0.f);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const float4 v = *reinterpret_cast<const float4 *>(yb + 4 * q);
-            y[2 * q] = float_pair{v.x, v.y};
-            y[2 * q + 1] = float_pair{v.z, v.w};
-        }
-    }
-    idct8(y[0], y[1], y[2], y[3], y[4], y[5], y[6], y[7]);          // y[x] = (pixel x of row 2k, of row 2k + 1)
-    idct8(c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]);          // c[x] = (Cb, Cr) sample x of chrominance row k
-    const uint32_t px = mx * 16u + sd * 8u, py = my * 16u + k * 2u;
-    uint8_t *dst = out_img + (size_t(py) * width + px) * 3;
-    const uint32_t npix = INTERIOR ? 8u : (px < width ? min(8u, width - px) : 0u);
-    if (!INTERIOR && (py >= height || npix == 0)) return;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {                                    // four pixels x two rows at a time
-        Rgb r0[4], r1[4];
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const float_pair cc = sd ? c[4 + 2 * h + i] : c[2 * h + i];
-            const ChromaTerms ct = chroma_terms(cc.x, cc.y);
-            const float_pair ya = y[4 * h + 2 * i], yb2 = y[4 * h + 2 * i + 1];
-            r0[2 * i] = ycc_to_rgb(ya.x, ct); r0[2 * i + 1] = ycc_to_rgb(yb2.x, ct);
-            r1[2 * i] = ycc_to_rgb(ya.y, ct); r1[2 * i + 1] = ycc_to_rgb(yb2.y, ct);
-        }
-        const uint32_t left = npix > 4u * h ? npix - 4u * h : 0u;
-        if (INTERIOR) {
-            store_rgb4_plain(dst + 12 * h, pack4(r0));
-            store_rgb4_plain(dst + size_t(width) * 3 + 12 * h, pack4(r1));
-        } else if (left) {
-            store4(dst + 12 * h, pack4(r0), aligned, left);
-            if (py + 1 < height) store4(dst + size_t(width) * 3 + 12 * h, pack4(r1), aligned, left);
-        }
-    }
-}
-
 // MODE 0: any sampling layout.  MODE 1: Y 2x2 + Cb 1x1 + Cr 1x1 (4:2:0, 6 blocks per MCU, tile = 32 MCUs).
-// MODE 3: the same pictures (DevImage::mode 1) in the wide form (above): 16 lanes per MCU, tile = 16 MCUs.
 // MODE 2: any sampling layout, REF_COMPAT placement into the f32 plane scratch (k_ref_color finishes the image).
 //   phase 0  zero the tile's sample rows in LDS
 //   phase 1  scatter the tile's slice of the compact coefficient stream into them, entry-parallel (lane i holds
@@ -3519,8 +3297,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     // (its own symbol: dynamic LDS arrays of one name share their alignment, and the entropy kernels ask for 2 KiB)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_px[];
     __shared__ float s_qm[3 * 64];
-    __shared__ uint8_t s_nat[MODE == 3 ? 128 : 64];     // (MODE 3: the luminance table, then the chrominance one)
-    __shared__ uint8_t s_comp[(MODE == 1 || MODE == 3) ? 4 : 256];     // (4:2:0: the component comes from arithmetic on the block index)
+    __shared__ uint8_t s_nat[64];
+    __shared__ uint8_t s_comp[MODE == 1 ? 4 : 256];     // (4:2:0: the component comes from arithmetic on the block index)
     // per tile of the workgroup (+ sentinel).  Linear stream: s_eoff = the tile's first entry.  Quad-interleaved stream (QUAD):
     // s_eoff = the subsequence and s_at = the entry in its column where the tile starts; s_cum: see quad_prepare
     constexpr bool QUAD = SRC == 1, PLANAR = SRC == 2;
@@ -3530,9 +3308,9 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     __shared__ PlanarKindL s_kind[PLANAR ? kPlanarKinds : 1];
     __shared__ PlanarTile s_ptile[PLANAR ? 3 : 1];
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || im.mode != uint32_t(MODE == 3 ? 1 : MODE) || (im.planar ? 2 : im.ent_rows != 0 ? 1 : 0) != SRC || img_flags[im.status_idx]) return;
+    if (!im.valid || im.mode != uint32_t(MODE) || (im.planar ? 2 : im.ent_rows != 0 ? 1 : 0) != SRC || img_flags[im.status_idx]) return;
     // everything the tile loop needs from the descriptor, read once (uniform -> scalar registers)
-    constexpr bool M420 = MODE == 1 || MODE == 3;
+    constexpr bool M420 = MODE == 1;
     constexpr uint32_t LANES = M420 ? kLanes420 : 256u;
     const uint32_t T = M420 ? kTile420 : (1u << im.log2_tile);
     const uint32_t bpm = M420 ? 6u : im.bpm;
@@ -3612,11 +3390,6 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
         constexpr uint8_t ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-        if (MODE == 3) {    // ... -> the float inside the block's quarter of its super-row (kWRow above), luminance and chrominance
-            const uint32_t r = ZZ[tid] >> 3, c = ZZ[tid] & 7u;
-            s_nat[tid] = uint8_t((r >> 1) * 32u + (c >> 2) * 8u + (r & 1u) * 4u + (c & 3u));
-            s_nat[64 + tid] = uint8_t((r >> 1) * 32u + (c >> 1) * 8u + (r & 1u) * 4u + (c & 1u) * 2u);
-        } else
         s_nat[tid] = uint8_t(idct_slot(ZZ[tid]));      // zig-zag position -> where the inverse DCT expects the coefficient
     }
     if (!M420 && tid < tile_blocks) s_comp[tid] = im.blk_comp[tid % bpm];
@@ -3649,7 +3422,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
         const uint32_t nm = min(T, nmcu - m0), nblk = nm * bpm;
         if (!clean) {   // phase 0
             float4 *z = reinterpret_cast<float4 *>(smem_px);
-            const uint32_t nq = MODE == 3 ? nm * (kWMcu / 4) : nblk * (kPixStride / 4);
+            const uint32_t nq = nblk * (kPixStride / 4);
             for (uint32_t i = tid; i < nq; i += LANES) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
             __syncthreads();
         }
@@ -3670,12 +3443,12 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                 }
             }
         }
-        // The next tile's loads go out BEFORE this tile's entries are scattered (round 6; MJX_FETCH_EARLY=0: behind the scatter, as in
-        // rounds 2-5): what finds a lane's group -- quad_cell's reads of the workgroup's tables in LDS -- is then not queued behind the
-        // scatter's LDS stores, and the loads have the scatter phase on top of the inverse DCT to land in (13 more registers: cur and
-        // nxt are live together; still three waves per SIMD).
+        // The next tile's loads go out BEFORE this tile's entries are scattered (round 6; rounds 2-5 issued them behind the scatter, as
+        // the planar form still does): what finds a lane's group -- quad_cell's reads of the workgroup's tables in LDS -- is then not
+        // queued behind the scatter's LDS stores, and the loads have the scatter phase on top of the inverse DCT to land in (13 more
+        // registers: cur and nxt are live together; still three waves per SIMD).
         auto nxt = cur;
-        if (MJX_FETCH_EARLY && !PLANAR && tile + 1 < tile1) {
+        if (!PLANAR && tile + 1 < tile1) {
             if constexpr (QUAD) tile_fetch_quad<LANES>(src, qv, tile + 1 - tile0, dcs, tile + 1, tile_blocks, total_blocks, nxt);
             else if constexpr (!PLANAR) tile_fetch<LANES, PF>(src, s_eoff + (tile + 1 - tile0), dcs, tile + 1, tile_blocks, total_blocks, nxt);
         }
@@ -3739,21 +3512,14 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             // prescaled transform is the same constant on all 64 samples); REF_COMPAT adds it per pixel in k_ref_color,
             // where samples no block covers must come out as 0 + 128
             MJX_SB(1);
-            if (MODE == 3) {
-                if (tid < nblk) *reinterpret_cast<float *>(smem_px + wide_block_bytes(tid)) = float(cur.dc) * my_dc_qm + my_dc_add;
-            } else
             if (tid < nblk) tile_f[tid * kPixStride] = float(cur.dc) * my_dc_qm + my_dc_add;
         }
-        if (!(MJX_FETCH_EARLY && !PLANAR) && tile + 1 < tile1) {
-            if constexpr (QUAD) tile_fetch_quad<LANES>(src, qv, tile + 1 - tile0, dcs, tile + 1, tile_blocks, total_blocks, nxt);
-            else if constexpr (PLANAR) tile_fetch_planar<LANES, PF>(psrc, s_ptile[(tile + 1) % 3u], dcbuf, pdc, (tile + 1) * T, pr1, pa1, nmcu, mcux, nxt);
-            else tile_fetch<LANES, PF>(src, s_eoff + (tile + 1 - tile0), dcs, tile + 1, tile_blocks, total_blocks, nxt);
+        if constexpr (PLANAR) {
+            if (tile + 1 < tile1) tile_fetch_planar<LANES, PF>(psrc, s_ptile[(tile + 1) % 3u], dcbuf, pdc, (tile + 1) * T, pr1, pa1, nmcu, mcux, nxt);
         }
         MJX_SB(2);
         __syncthreads();
         MJX_SB(3);
-        if (MODE == 3) wide_column_pass(tile_f, nm);                      // phase 2
-        else
         if (tid < nblk) idct_row_inplace(tile_f + tid * kPixStride);
         MJX_SB(4);
         __syncthreads();
@@ -3769,15 +3535,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             pa0 = pa1;
         }
         MJX_SB(5);
-        if (MODE == 3) {                                                  // phase 3
-            const uint32_t mx0 = m0 % mcux, my1 = (m0 + T - 1) / mcux;
-            const bool whole = nm == T;
-            const bool interior = whole && aligned && (my1 + 1) * 16 <= height && (mcux * 16 <= width || mx0 + T < mcux);
-            if (interior) pixels_wide<true, false>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
-            else if (whole) pixels_wide<true, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
-            else pixels_wide<false, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
-            clean = whole && MJX_PIX_XCHG;
-        } else if (MODE == 1) {
+        if (MODE == 1) {
             // interior tile: all 32 MCUs in one MCU row, fully inside the image, rows 4-byte aligned
             // whole tile: all its 32 MCUs exist; interior: ... and every one of them lies fully inside the picture (the tile may wrap
             // into the next MCU row), rows 4-byte aligned
@@ -3787,7 +3545,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             if (interior) pixels_420<true, false>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
             else if (whole) pixels_420<true, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
             else pixels_420<false, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
-            clean = whole && MJX_PIX_XCHG;
+            clean = whole;
         } else if (MODE == 2) {
             place_ref(im, tile_f, tile * tile_blocks, nblk, planes);
         } else {
@@ -3880,10 +3638,10 @@ int configure_kernels(size_t huff_lds, size_t idct_lds)
     }
     if (e == hipSuccess && idct_lds > 64 * 1024) {
         const void *fns[] = {reinterpret_cast<const void *>(k_idct_color<0, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<0, 8, 1>),
-                             reinterpret_cast<const void *>(k_idct_color<kMode420, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<kMode420, kPrefetchDense, 0>),
-                             reinterpret_cast<const void *>(k_idct_color<kMode420, 8, 1>), reinterpret_cast<const void *>(k_idct_color<kMode420, 16, 1>),
+                             reinterpret_cast<const void *>(k_idct_color<1, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<1, kPrefetchDense, 0>),
+                             reinterpret_cast<const void *>(k_idct_color<1, 8, 1>), reinterpret_cast<const void *>(k_idct_color<1, 16, 1>),
                              reinterpret_cast<const void *>(k_idct_color<2, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<2, 8, 1>),
-                             reinterpret_cast<const void *>(k_idct_color<0, 8, 2>), reinterpret_cast<const void *>(k_idct_color<kMode420, 8, 2>)};
+                             reinterpret_cast<const void *>(k_idct_color<0, 8, 2>), reinterpret_cast<const void *>(k_idct_color<1, 8, 2>)};
         for (const void *f : fns)
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(idct_lds));
     }
@@ -4025,7 +3783,7 @@ void launch_dc_scan(hipStream_t st, uint32_t max_segs, uint32_t nimg, const DevI
 void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t lds, const DevImage *images,
                        const uint32_t *entries, const uint32_t *tile_eoff, const int32_t *dcbuf, const float *qmult,
                        uint8_t *rgb, uint32_t mode_mask, unsigned long long *planes, const uint32_t *img_flags, bool dense,
-                       uint32_t layout_mask, size_t lds_pad)
+                       uint32_t layout_mask)
 {
     // A workgroup walks up to kTilesPerWg consecutive tiles of its image (offsets fetched once, the next tile's loads in
     // flight during this tile's arithmetic) -- when the launch has tiles to spare: with fewer than a few rounds of 3
@@ -4036,9 +3794,7 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
     const uint32_t gx = (max_tiles + tpw - 1) / tpw;
     // (layout_mask: bit 0 = the chunk has pictures with a linear stream, bit 1 = with a quad-interleaved one, bit 2 = multi-scan
     // pictures read straight from their scans' streams; a kernel form leaves the other kinds' pictures alone)
-    // (the 4:2:0 form's tile has its own size: the wide form's 25 KB must not be rounded up to the other pictures' tiles)
-    const size_t lds420 = MJX_WIDE420 ? wide_tile_bytes() + lds_pad : lds;
-#define MJX_IDCT(M, P, Q) hipLaunchKernelGGL((k_idct_color<M, P, Q>), dim3(gx, nimg), dim3((M == 1 || M == 3) ? kLanes420 : 256u), (M == 3 ? lds420 : lds), st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw)
+#define MJX_IDCT(M, P, Q) hipLaunchKernelGGL((k_idct_color<M, P, Q>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw)
     if (mode_mask & 1u) {
         if (layout_mask & 1u) MJX_IDCT(0, kPrefetch, 0);
         if (layout_mask & 2u) MJX_IDCT(0, 8, 1);
@@ -4049,15 +3805,15 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
         // twelve words per lane instead of eight: 18.2 -> 17.2 ms per 2048 4K pictures at quality 90; at quality 75 the four
         // extra loads per lane and tile cost 0.15 ms)
         if (layout_mask & 1u) {
-            if (dense) MJX_IDCT(kMode420, kPrefetchDense, 0);
-            else MJX_IDCT(kMode420, kPrefetch, 0);
+            if (dense) MJX_IDCT(1, kPrefetchDense, 0);
+            else MJX_IDCT(1, kPrefetch, 0);
         }
         // (quad-interleaved streams: one round of 256 groups prefetched, two for dense streams -- 20.2 -> ... ms at quality 90)
         if (layout_mask & 2u) {
-            if (dense) MJX_IDCT(kMode420, 16, 1);
-            else MJX_IDCT(kMode420, 8, 1);
+            if (dense) MJX_IDCT(1, 16, 1);
+            else MJX_IDCT(1, 8, 1);
         }
-        if (layout_mask & 4u) MJX_IDCT(kMode420, 8, 2);
+        if (layout_mask & 4u) MJX_IDCT(1, 8, 2);
     }
     if (mode_mask & 4u) {
         if (layout_mask & 1u) MJX_IDCT(2, kPrefetch, 0);

@@ -10,7 +10,7 @@ settings = [dict(kv.split("=") for kv in a.split(",") if kv) for a in sys.argv[2
 res = {i: [] for i in range(len(settings))}
 for rnd in range(3):
     for i, env in enumerate(settings):
-        for k in ("MJX_UPLOAD_APART", "MJX_GROUP_ALT", "MJX_GROUP_MB", "MJX_GROUP_FIRST_MB", "MJX_GROUP_GROW"):
+        for k in ("MJX_GROUP_MB", "MJX_GROUP_FIRST_MB", "MJX_GROUP_GROW"):
             os.environ.pop(k, None)
         os.environ.update(env)
         ctx = mjx.Context(0)
