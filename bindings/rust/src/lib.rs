@@ -26,6 +26,8 @@ pub struct mjx_opts {
     pub keep_coefs: u8,
     pub device_destuff: u8,
     pub chunk_images: u32,
+    /// scaled decode: 0 or 1 full size, 2 / 4 / 8 = 1/2, 1/4, 1/8 in the DCT domain (include/mjx.h)
+    pub scale_denom: u8,
 }
 
 #[repr(C)]

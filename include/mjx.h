@@ -61,6 +61,18 @@ typedef struct mjx_opts {
                              same.  Never on the GPU with strict_ref (the byte pass stays, for the reference's unguarded read
                              behind a last FF) nor for multi-scan files (their scans are cut apart on the host). */
     uint32_t chunk_images;/* images per kernel chunk; 0 = library default */
+    uint8_t scale_denom;  /* scaled decode in the DCT domain: 0 or 1 = full size; 2, 4, 8 = 1/2, 1/4, 1/8 (anything else:
+                             MJX_ERR_INVALID_ARG).  The picture is ceil(W/s) x ceil(H/s) (libjpeg's jdiv_round_up).  Per block the
+                             low N x N corner (N = 8/s) of the dequantised coefficients F(u,v), natural order, goes through the
+                             N-point inverse DCT with the 8-point normalisation:
+                               f(x,y) = 1/4 sum_{u,v<N} C(u) C(v) F(u,v) cos((2x+1)u pi/2N) cos((2y+1)v pi/2N),
+                               C(0) = 1/sqrt(2), C(k>0) = 1  (N = 1: F(0,0)/8),
+                             so a flat block gives the same level at every scale.  Level shift, colour formula and truncating
+                             store are the STANDARD layout's; chroma is box-replicated at the output resolution (output pixel
+                             (X,Y) takes the sample at (X h/Hmax, Y v/Vmax) of the component's scaled plane).  STANDARD layout
+                             only: MJX_LAYOUT_REF_COMPAT with a scale above 1 is MJX_ERR_INVALID_ARG.  For a scaled batch
+                             mjx_batch_image_info, mjx_batch_copy_rgb, mjx_batch_rgb_device and mjx_batch_bytes speak of the
+                             output picture. */
 } mjx_opts;
 
 /* ---- inner seam: what jpeg/mod.rs:388-415 hands to JPEGDecoder -------------------------- */

@@ -43,7 +43,7 @@ class MjxError(RuntimeError):
 
 class Opts(ctypes.Structure):
     _fields_ = [("strict_ref", ctypes.c_uint8), ("layout", ctypes.c_uint8), ("keep_coefs", ctypes.c_uint8),
-                ("device_destuff", ctypes.c_uint8), ("chunk_images", ctypes.c_uint32)]
+                ("device_destuff", ctypes.c_uint8), ("chunk_images", ctypes.c_uint32), ("scale_denom", ctypes.c_uint8)]
 
 
 class Comp(ctypes.Structure):
@@ -153,10 +153,14 @@ def _check(rc, what=""):
 DESTUFF_AUTO, DESTUFF_DEVICE, DESTUFF_HOST = 0, 1, 2
 
 
-def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0, device_destuff=False):
-    """device_destuff: True = on the GPU, False = on the host, None = the library's choice (mjx.h: MJX_DESTUFF_*)."""
+def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0, device_destuff=False, scale=1):
+    """device_destuff: True = on the GPU, False = on the host, None = the library's choice (mjx.h: MJX_DESTUFF_*).
+    scale: 1, 2, 4 or 8 -- the picture decoded at 1/scale in the DCT domain (mjx.h: mjx_opts.scale_denom)."""
     dd = DESTUFF_AUTO if device_destuff is None else (DESTUFF_DEVICE if device_destuff else DESTUFF_HOST)
-    return Opts(int(bool(strict_ref)), int(layout), int(bool(keep_coefs)), dd, int(chunk_images))
+    scale = int(scale)
+    if not 0 <= scale <= 255:
+        raise MjxError(ERR_INVALID_ARG, "scale=%d" % scale)
+    return Opts(int(bool(strict_ref)), int(layout), int(bool(keep_coefs)), dd, int(chunk_images), scale)
 
 
 # ---- host parse ------------------------------------------------------------------------------------
@@ -173,9 +177,9 @@ class ParsedScan:
     def scan_bytes(self):
         return ctypes.string_at(self.desc.scan, self.desc.scan_len)
 
-    def validate(self, layout=LAYOUT_STANDARD, strict_ref=False):
+    def validate(self, layout=LAYOUT_STANDARD, strict_ref=False, scale=1):
         """Status mjx_batch_create would give this image (host only)."""
-        o = _opts(layout=layout, strict_ref=strict_ref)
+        o = _opts(layout=layout, strict_ref=strict_ref, scale=scale)
         return int(lib().mjx_validate(ctypes.byref(self.desc), ctypes.byref(o)))
 
     def close(self):
@@ -224,7 +228,9 @@ class Batch:
     """Device-resident batch: inputs uploaded at construction, ``decode()`` only enqueues kernels."""
 
     def __init__(self, ctx, scans=None, strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0,
-                 _handle=None):
+                 _handle=None, scale=1):
+        """scale: 1, 2, 4 or 8 -- every picture decoded at 1/scale (info(), rgb(), rgb_device() and bytes() then speak of the
+        scaled picture; tile() keeps the scale)."""
         self.ctx = ctx
         self.h = _vp()
         if _handle is not None:
@@ -236,7 +242,7 @@ class Batch:
             ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(s.desc if isinstance(s, ParsedScan) else s),
                            ctypes.sizeof(ScanDesc))
         st = (_int * max(n, 1))()
-        o = _opts(strict_ref, layout, keep_coefs, chunk_images)
+        o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale)
         _check(lib().mjx_batch_create(ctx.h, arr, n, ctypes.byref(o), ctypes.byref(self.h), st), "mjx_batch_create")
         self.create_status = list(st)[:n]
 
@@ -475,11 +481,12 @@ class JPEGImage:
         self._w, self._h, self._rgb = width, height, rgb
 
     @staticmethod
-    def parse(data, strict_ref=False, layout=LAYOUT_STANDARD, ctx=None):
+    def parse(data, strict_ref=False, layout=LAYOUT_STANDARD, ctx=None, scale=1):
+        """scale: 1, 2, 4 or 8 -- the picture at 1/scale (width() and height() are the scaled picture's)."""
         ctx = ctx or default_context()
         scan = ParsedScan(data, strict_ref=strict_ref)
         try:
-            b = Batch(ctx, [scan], strict_ref=strict_ref, layout=layout)
+            b = Batch(ctx, [scan], strict_ref=strict_ref, layout=layout, scale=scale)
             try:
                 if b.create_status[0] != OK:
                     raise MjxError(b.create_status[0])
@@ -487,7 +494,8 @@ class JPEGImage:
                 b.wait()
                 if b.status(0) != OK:
                     raise MjxError(b.status(0))
-                return JPEGImage(scan.desc.width, scan.desc.height, b.rgb(0))
+                rgb = b.rgb(0)
+                return JPEGImage(rgb.shape[1], rgb.shape[0], rgb)
             finally:
                 b.close()
         finally:
@@ -504,8 +512,8 @@ class JPEGImage:
         return self._rgb
 
 
-def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False):
-    """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).
+def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False, scale=1):
+    """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale: see Batch.
     device_destuff: the host copies the entropy-coded bytes as they are; de-stuffing, restart markers and the scan's length
     are found on the GPU."""
     n = len(datas)
@@ -514,7 +522,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     st = (_int * max(n, 1))()
     ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
     h = _vp()
-    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, device_destuff=device_destuff)
+    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, device_destuff=device_destuff, scale=scale)
     _check(lib().mjx_decode_batch(ctx.h, arr, lens, n, ctypes.byref(o), int(threads), ptrs, st, ctypes.byref(h)), "mjx_decode_batch")
     return Batch(ctx, _handle=h), list(st)[:n]
 
@@ -538,8 +546,9 @@ class Pool:
     def set_deal(self, round_robin):
         _check(lib().mjx_pool_set_deal(self.h, 1 if round_robin else 0), "mjx_pool_set_deal")
 
-    def decode_batch(self, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads_per_device=0, device_destuff=None):
-        """-> PoolResult; .slot_of[i], .status[i], .rgb(i), .rc (the call's return code: a failed slot fails its own files only)"""
+    def decode_batch(self, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads_per_device=0, device_destuff=None, scale=1):
+        """-> PoolResult; .slot_of[i], .status[i], .rgb(i), .rc (the call's return code: a failed slot fails its own files only).
+        scale: see Batch."""
         n = len(datas)
         arr = (ctypes.c_char_p * max(n, 1))(*[bytes(d) for d in datas])
         lens = (_sz * max(n, 1))(*[len(d) for d in datas])
@@ -547,7 +556,7 @@ class Pool:
         slots = (_int * max(n, 1))()
         ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
         h = _vp()
-        o = _opts(strict_ref, layout, device_destuff=device_destuff)
+        o = _opts(strict_ref, layout, device_destuff=device_destuff, scale=scale)
         rc = lib().mjx_pool_decode_batch(self.h, arr, lens, n, ctypes.byref(o), int(threads_per_device), slots, ptrs, st, ctypes.byref(h))
         if not h:
             _check(rc, "mjx_pool_decode_batch")
@@ -635,10 +644,10 @@ class PoolResult:
             pass
 
 
-def decode(data, strict_ref=False, layout=LAYOUT_STANDARD):
-    """One-shot C entry point mjx_decode (parse + GPU decode + copy back) -> ndarray [H, W, 3] uint8."""
+def decode(data, strict_ref=False, layout=LAYOUT_STANDARD, scale=1):
+    """One-shot C entry point mjx_decode (parse + GPU decode + copy back) -> ndarray [H, W, 3] uint8.  scale: see Batch."""
     img = Image()
-    o = _opts(strict_ref, layout)
+    o = _opts(strict_ref, layout, scale=scale)
     _check(lib().mjx_decode(bytes(data), len(data), ctypes.byref(o), ctypes.byref(img)), "mjx_decode")
     try:
         return np.ctypeslib.as_array(img.rgb, (img.height, img.width, 3)).copy()

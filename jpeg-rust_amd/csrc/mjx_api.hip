@@ -151,6 +151,7 @@ struct Chunk {
     uint32_t max_wg = 0, merge_wgs = 0, max_tiles = 0, lut_cap = 0, max_tile_blocks = 0, mode_mask = 0, layout_mask = 0, max_segs = 0, bpm_mask = 0, max_restart_segs = 0;
     uint64_t plane_words = 0;      // REF_COMPAT scratch of the chunk
     uint32_t max_pixel_wgs = 0;
+    uint32_t max_dc_wgs = 0;       // scaled decode at 1/8: workgroups of k_dc_color for the chunk's largest picture
     uint32_t min_sub_bits = 0xffffffffu;   // shortest subsequence length among its scans (chunk_fix_passes)
     uint32_t max_nsub = 0;                 // subsequences of its longest scan
     uint32_t wg = 128;                     // lanes of its k_huff_spec / k_huff_write workgroups: the largest its scans were cut for (ImagePlan::wg_lanes)
@@ -450,6 +451,10 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
     d.nseg = p.nseg;
     d.restart_mcus = p.restart_mcus;
     d.mode = (p.ncomp == 3 && p.h[0] == 2 && p.v[0] == 2 && p.h[1] == 1 && p.v[1] == 1 && p.h[2] == 1 && p.v[2] == 1) ? 1 : 0;
+    d.scale = p.scale;
+    d.out_w = p.out_w;
+    d.out_h = p.out_h;
+    if (p.scale > 1) d.mode = p.scale == 2 ? 3 : p.scale == 4 ? 4 : 5;      // scaled decode: the generic tile (a power of two) below
     uint32_t t = (d.mode == 1 && p.layout != MJX_LAYOUT_REF_COMPAT) ? tile_mcus_420() : tile_mcus(p.bpm, p.hmax), l2 = 0;
     while ((1u << (l2 + 1)) <= t) l2++;
     if (!(d.mode == 1 && p.layout != MJX_LAYOUT_REF_COMPAT)) t = 1u << l2;      // (the generic pixel phase needs a power of two)
@@ -566,6 +571,7 @@ void plan_chunks(mjx_batch *b)
                 if (d.role != 1) c.layout_mask |= d.planar ? 4u : d.ent_rows ? 2u : 1u;
                 c.bpm_mask |= 1u << d.bpm;
                 if (d.nseg > 1) c.max_restart_segs = std::max(c.max_restart_segs, d.nseg);
+                if (d.mode == 5) c.max_dc_wgs = std::max<uint32_t>(c.max_dc_wgs, uint32_t((uint64_t(d.out_w) * d.out_h + 255) / 256));
                 if (d.mode == 2) {
                     d.plane_off = c.plane_words;
                     c.plane_words += uint64_t(d.width) * d.height * d.ncomp;
@@ -875,6 +881,7 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
         launch_idct_color(sp, c.max_tiles, nimg, b->idct_lds + b->ctx->idct_lds_pad, imgs, SCR(d_entries), SCR(d_tile_eoff), dcb, b->d_qm, b->d_rgb, c.mode_mask, SCR(d_planes), b->d_img_flags,
                           c.scan_bytes > uint64_t(c.tiles) * (1400u * tile_mcus_420() / 32u), c.layout_mask);
         if (c.plane_words) launch_ref_color(sp, c.max_pixel_wgs, nimg, imgs, SCR(d_planes), b->d_rgb, b->d_img_flags);
+        if (c.max_dc_wgs) launch_dc_color(sp, c.max_dc_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags);
         prof_end(b, sp);
         if (sp != st) {
             HIPOK(hipEventRecord(b->ev_pixels[set], sp));
@@ -1106,8 +1113,9 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
         d.lut2_off = lut_off[k] + p.lut_plain_n;
         d.lut2_n = lut_n[k] - p.lut_plain_n;
         d.qm_off = uint32_t(k * 192);
+        if (p.scale > 1) d.qm_off = uint32_t((nu + k) * 192);       // (the reduced transforms' multipliers: the second half of the pool)
         d.seg_off = seg_off[k];
-        inf.width = p.width; inf.height = p.height; inf.bpm = p.bpm; inf.nmcu = p.nmcu;
+        inf.width = p.out_w; inf.height = p.out_h; inf.bpm = p.bpm; inf.nmcu = p.nmcu;      // (the picture written: scaled decode)
         inf.nblocks = uint64_t(p.nmcu) * p.bpm;
         inf.tile_blocks = d.tile_blocks;
         inf.ntiles = uint32_t((inf.nblocks + d.tile_blocks - 1) / d.tile_blocks);
@@ -1197,14 +1205,14 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
         d.ent_cap = uint32_t(std::min<uint64_t>(inf.ent_cap, 0xffffffffu));
         inf.scan_len = p.scan_len;
         inf.rgb_off = rgb_pool;
-        inf.rgb_bytes = p.role == 1 ? 0 : uint64_t(p.width) * p.height * 3;     // (a scan of a multi-scan file has no picture)
+        inf.rgb_bytes = p.role == 1 ? 0 : uint64_t(p.out_w) * p.out_h * 3;     // (a scan of a multi-scan file has no picture)
         d.rgb_off = rgb_pool;
         rgb_pool += align_up(inf.rgb_bytes, 256);
         b->scan_bytes += p.scan_len;
         b->rgb_bytes += inf.rgb_bytes;
         if (p.role != 1) {
             b->coef_bytes += inf.nblocks * 128;
-            b->pixels += uint64_t(p.width) * p.height;
+            b->pixels += uint64_t(p.out_w) * p.out_h;
         }
     }
     for (size_t i = 0; i < n; i++)
@@ -1315,7 +1323,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 // the small pools first, back to back: they go up in one transfer from one host block (meta_*)
                 ar.take(&b->d_images, std::max<size_t>(n, 1) * sizeof(DevImage));
                 ar.take(&b->d_lut, std::max<size_t>(lut_pool, 8) * sizeof(LutEntry));
-                ar.take(&b->d_qm, std::max<size_t>(nu, 1) * 192 * sizeof(float));
+                ar.take(&b->d_qm, std::max<size_t>(nu, 1) * 384 * sizeof(float));      // (the multipliers, then those of the reduced transforms)
                 ar.take(&b->d_segs, std::max<size_t>(b->h_segs.size(), 2) * sizeof(uint32_t));
                 ar.take(&b->d_ii, std::max<size_t>(ii.size(), 1) * sizeof(InterleaveImg));
                 // per-image words the kernels expect to be zero: inside the block, so that its one transfer clears them (three
@@ -1386,7 +1394,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
             for (size_t rep = 0; rep < times; rep++)
                 HIPOK(hipMemcpyAsync(b->d_scan + rep * scan_pool, src->d_scan, scan_pool, hipMemcpyDeviceToDevice, up));
             HIPOK(hipMemcpyAsync(b->d_lut, src->d_lut, std::max<size_t>(lut_pool, 8) * sizeof(LutEntry), hipMemcpyDeviceToDevice, up));
-            HIPOK(hipMemcpyAsync(b->d_qm, src->d_qm, std::max<size_t>(nu, 1) * 192 * sizeof(float), hipMemcpyDeviceToDevice, up));
+            HIPOK(hipMemcpyAsync(b->d_qm, src->d_qm, std::max<size_t>(nu, 1) * 384 * sizeof(float), hipMemcpyDeviceToDevice, up));
         } else {
             const bool timing = std::getenv("MJX_TIMING") != nullptr;
             auto now = [] { return std::chrono::steady_clock::now(); };
@@ -1412,7 +1420,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 h_qm = reinterpret_cast<float *>(mirror(b->d_qm));
             } else {
                 b->h_lut.assign(std::max<size_t>(lut_pool, 8), 0);
-                b->h_qm.assign(std::max<size_t>(nu, 1) * 192, 0.f);
+                b->h_qm.assign(std::max<size_t>(nu, 1) * 384, 0.f);
                 h_lut = b->h_lut.data();
                 h_qm = b->h_qm.data();
             }
@@ -1421,6 +1429,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 if (p.status != MJX_OK) continue;
                 if (lut_first[k]) std::memcpy(h_lut + lut_off[k], p.lut.data(), p.lut.size() * sizeof(LutEntry));
                 std::memcpy(h_qm + k * 192, p.qmult, sizeof p.qmult);
+                std::memcpy(h_qm + (nu + k) * 192, p.qmult_scaled, sizeof p.qmult_scaled);
             }
             if (!meta_block) {
                 HIPOK(hipMemcpyAsync(b->d_lut, b->h_lut.data(), b->h_lut.size() * sizeof(LutEntry), hipMemcpyHostToDevice, up));
@@ -1771,6 +1780,7 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
         p.status = src->info[k].status;
         if (p.status != MJX_OK) continue;
         p.width = d.width; p.height = d.height; p.ncomp = d.ncomp; p.bpm = d.bpm; p.hmax = d.hmax; p.vmax = d.vmax;
+        p.scale = d.scale ? d.scale : 1u; p.out_w = d.out_w; p.out_h = d.out_h;      // (the copies keep the source's scale)
         p.mcux = d.mcux; p.mcuy = d.mcuy; p.nmcu = d.nmcu;
         for (uint32_t c = 0; c < 3; c++) { p.h[c] = d.ch[c]; p.v[c] = d.cv[c]; }
         std::memcpy(p.blk_comp, d.blk_comp, sizeof p.blk_comp);

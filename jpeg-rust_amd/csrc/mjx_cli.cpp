@@ -1,16 +1,18 @@
 // mjx_cli.cpp -- counterpart of the reference's CLI (src/main.rs:24-40):  mjx_cli <in.jpeg> <out.ppm> [--p6] [--strict]
+// [--scale N]  (N = 2, 4, 8: the picture decoded at 1/N in the DCT domain, mjx_opts.scale_denom)
 // Writes the same ASCII P3 file ("P3\n{w} {h}\n255\n" then "r g b\n" per pixel, main.rs:35-39), buffered; --p6 writes
 // binary PPM instead.  Exit code = MJX_* status.
 #include "jpeg.hpp"
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s <input.jpeg> <output.ppm> [--p6] [--strict] [--ref-compat]\n", argv[0]);   // main.rs:26-28 expect()
+        std::fprintf(stderr, "usage: %s <input.jpeg> <output.ppm> [--p6] [--strict] [--ref-compat] [--scale N]\n", argv[0]);   // main.rs:26-28 expect()
         return MJX_ERR_INVALID_ARG;
     }
     bool p6 = false;
@@ -19,6 +21,11 @@ int main(int argc, char **argv)
         if (!std::strcmp(argv[i], "--p6")) p6 = true;
         else if (!std::strcmp(argv[i], "--strict")) opts.strict_ref = 1;
         else if (!std::strcmp(argv[i], "--ref-compat")) opts.layout = MJX_LAYOUT_REF_COMPAT;
+        else if (!std::strcmp(argv[i], "--scale")) {
+            const long v = i + 1 < argc ? std::strtol(argv[++i], nullptr, 10) : -1;
+            if (v < 0 || v > 255) { std::fprintf(stderr, "--scale takes 1, 2, 4 or 8\n"); return MJX_ERR_INVALID_ARG; }
+            opts.scale_denom = uint8_t(v);           // (other values: mjx_decode says MJX_ERR_INVALID_ARG)
+        }
     }
     std::FILE *f = std::fopen(argv[1], "rb");                                   // file_to_bytes, main.rs:16-22
     if (!f) { std::perror(argv[1]); return MJX_ERR_INVALID_ARG; }

@@ -81,6 +81,10 @@ struct DevImage {
     // k_huff_spec ... k_huff_write): pictures of one scan without restart intervals, quad-interleaved stream
     uint32_t emit;
     uint32_t emit_head;         // groups of head room in front of the first decode's entries (kEmitHeadGroups; tests shrink it)
+    // scaled decode (mjx_opts.scale_denom): 1, 2, 4 or 8; the picture written is out_w x out_h = ceil(width / scale) x
+    // ceil(height / scale).  Modes 3 (1/2) and 4 (1/4) run k_idct_color with a 4- or 2-point inverse DCT on the low corner of
+    // each block, mode 5 (1/8) runs k_dc_color on the DC values alone; qm_off then points at the reduced multipliers.
+    uint32_t scale, out_w, out_h;
 };
 
 // Where the segments of a scan begin (DevImage::seg_S): the first cut at or after scan MCU q0, as the scan MCU it lies at and its
@@ -385,6 +389,10 @@ void launch_rgb_compare(hipStream_t st, uint32_t npairs, uint64_t max_bytes, con
                         unsigned long long *ndiff);
 void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images,
                       const unsigned long long *planes, uint8_t *rgb, const uint32_t *img_flags);
+// scaled decode at 1/8 (mode 5): one lane per output pixel from the blocks' DC values; max_pixel_wgs = the chunk's largest
+// ceil(out_w * out_h / 256)
+void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
+                     const float *qmult, uint8_t *rgb, const uint32_t *img_flags);
 #endif
 
 }   // namespace mjx

@@ -13,6 +13,7 @@
 //   stage B (pixels, replaces decoder.rs:227-235, 239-331 and src/transform.rs:55-87):
 //     k_idct_color  dequant + un-zigzag + 8x8 float IDCT + chroma replication + YCbCr->RGB + packed store
 //     k_ref_color   REF_COMPAT layout only: the reference's plane-wise colour step
+//     k_dc_color    scaled decode at 1/8: one sample per block from its DC value (1/2 and 1/4: k_idct_color modes 3, 4)
 //
 // Without restart markers (the reference panics on DRI, jpeg/mod.rs:424-428; files that have them are cut at the markers
 // as well) intra-image parallelism comes from the self-synchronisation of Huffman codes: a lane that starts decoding
@@ -2472,6 +2473,7 @@ extern "C" __global__ __launch_bounds__(256) void k_dc_restart(const DevImage *i
 // stage B
 // ------------------------------------------------------------------------------------------------
 constexpr int kPixStride = 68;       // floats per IDCT output block (64 + 4)
+constexpr uint8_t kScaledDrop = 0xff;   // s_nat of the scaled forms: a coefficient outside the block's low corner
 
 // 8-point inverse DCT, Arai-Agui-Nakajima factorisation on inputs pre-scaled by the AAN factors (folded into the
 // dequantisation multipliers on the host, mjx_plan.cpp).  5 multiplies, 29 additions.  Same transform as the
@@ -2761,7 +2763,9 @@ __device__ __forceinline__ void scatter_at(const uint32_t *ent, const uint32_t *
     const uint32_t dump = dump_bytes<MODE>();
 #pragma unroll
     for (int k = 0; k < N; k++) {
-        const bool ok = b[k] < nblk && pos[k] != 0;           // pos == 0 marks a null entry (the write pass fills up its runs with them)
+        // pos == 0 marks a null entry (the write pass fills up its runs with them); the scaled forms (MODE 3, 4) drop what lies
+        // outside the low corner of the block (kScaledDrop in s_nat)
+        const bool ok = b[k] < nblk && pos[k] != 0 && (MODE < 3 || nat[k] != kScaledDrop);
         const uint32_t at = ok ? b[k] * uint32_t(kPixStride * 4) + nat[k] * 4u : dump;
 #if defined(MJX_EXP_NO_SCATTER_STORE)  // (measurement build, garbage out: the scatter phase without its LDS stores)
         asm volatile("" :: "v"(at), "v"(float(int32_t(int16_t(ent[k] & 0xffffu))) * qm[k]));
@@ -2852,13 +2856,10 @@ struct PlanarDc {
     uint32_t mt;                     // the lane's MCU inside the tile
     bool lane;                       // the lane has a block slot at all
 };
-__device__ __forceinline__ PlanarDc planar_dc_prepare(const DevImage *images, const DevImage &im, uint32_t img, uint32_t bpm, uint32_t tile_blocks)
+// (block slot k of the MCU; fills all but mt and lane)
+__device__ __forceinline__ void planar_dc_slot(const DevImage *images, const DevImage &im, uint32_t img, uint32_t k, PlanarDc &d)
 {
-    PlanarDc d{};
-    const uint32_t tid = threadIdx.x;
-    d.lane = tid < tile_blocks;
-    d.mt = tid / bpm;
-    const uint32_t k = tid - d.mt * bpm, c = im.blk_comp[k];
+    const uint32_t c = im.blk_comp[k];
     const DevImage &sim = images[img - im.src_back[c]];
     d.base = sim.coef_off;
     if (sim.ncomp == 1) {            // raster order over the component's own grid
@@ -2870,6 +2871,14 @@ __device__ __forceinline__ PlanarDc planar_dc_prepare(const DevImage *images, co
         d.rx = 1; d.r0x = 0; d.lx = sim.mcux;
         d.ry = 1; d.r0y = 0; d.ly = sim.mcuy;
     }
+}
+__device__ __forceinline__ PlanarDc planar_dc_prepare(const DevImage *images, const DevImage &im, uint32_t img, uint32_t bpm, uint32_t tile_blocks)
+{
+    PlanarDc d{};
+    const uint32_t tid = threadIdx.x;
+    d.lane = tid < tile_blocks;
+    d.mt = tid / bpm;
+    planar_dc_slot(images, im, img, tid - d.mt * bpm, d);
     return d;
 }
 template <int PF>
@@ -3276,8 +3285,103 @@ extern "C" __global__ __launch_bounds__(256) void k_ref_color(const DevImage *im
     dst[0] = uint8_t(word); dst[1] = uint8_t(word >> 8); dst[2] = uint8_t(word >> 16);
 }
 
+// ---- scaled decode (mjx_opts.scale_denom; modes 3 and 4 of k_idct_color, k_dc_color) --------------------------------------------
+// Scale 1/s keeps the low N x N corner (N = 8 / s) of every block and runs the N-point inverse DCT with the 8-point
+// normalisation on it (include/mjx.h):  f(x,y) = 1/4 sum_{u,v<N} C(u) C(v) F(u,v) cos((2x+1)u pi/2N) cos((2y+1)v pi/2N).
+// The host folds DQT x C(u) C(v) / 4 into the multipliers (mjx_plan.cpp, qmult_scaled), so the kernel's transforms are plain
+// cosine sums.  A block's samples sit in the first N x N floats of its tile row, row-major (the tile keeps kPixStride per block,
+// so the entries dropped by the scatter still find their padding words).
+template <int MODE> constexpr uint32_t scaled_n() { return MODE == 3 ? 4u : 2u; }
+// natural position -> the float of the block row it lands on (row-major N x N), or kScaledDrop outside the corner
+__device__ __host__ constexpr uint32_t scaled_slot(uint32_t natural, uint32_t n)
+{
+    return ((natural >> 3) < n && (natural & 7u) < n) ? (natural >> 3) * n + (natural & 7u) : kScaledDrop;
+}
+// out[x] = sum_{u<4} g[u] cos((2x+1) u pi / 8): even part (u = 0, 2), odd part (u = 1, 3)
+__device__ __forceinline__ void idct4(float &g0, float &g1, float &g2, float &g3)
+{
+    const float c4 = 0.707106781f, c1 = 0.923879533f, c3 = 0.382683432f;
+    const float e0 = __builtin_fmaf(g2, c4, g0), e1 = __builtin_fmaf(g2, -c4, g0);
+    const float o0 = __builtin_fmaf(g1, c1, g3 * c3), o1 = __builtin_fmaf(g1, c3, g3 * -c1);
+    g0 = e0 + o0; g3 = e0 - o0;
+    g1 = e1 + o1; g2 = e1 - o1;
+}
+// out[x] = g0 + g1 cos((2x+1) pi / 4)
+__device__ __forceinline__ void idct2(float &g0, float &g1)
+{
+    const float c4 = 0.707106781f;
+    const float a = __builtin_fmaf(g1, c4, g0), b = __builtin_fmaf(g1, -c4, g0);
+    g0 = a; g1 = b;
+}
+// one lane = one block: rows, then columns, in registers; the samples go back to the same N x N floats
+template <uint32_t N>
+__device__ __forceinline__ void idct_scaled_inplace(float *blk)
+{
+    float v[N * N];
+    if constexpr (N == 4) {
+        float4 *q = reinterpret_cast<float4 *>(blk);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const float4 t = q[r];
+            v[4 * r] = t.x; v[4 * r + 1] = t.y; v[4 * r + 2] = t.z; v[4 * r + 3] = t.w;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) idct4(v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
+#pragma unroll
+        for (int c = 0; c < 4; c++) idct4(v[c], v[4 + c], v[8 + c], v[12 + c]);
+#pragma unroll
+        for (int r = 0; r < 4; r++) q[r] = make_float4(v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
+    } else {
+        float4 *q = reinterpret_cast<float4 *>(blk);
+        const float4 t = q[0];
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+        idct2(v[0], v[1]);
+        idct2(v[2], v[3]);
+        idct2(v[0], v[2]);
+        idct2(v[1], v[3]);
+        q[0] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+// Phase 3 of the scaled forms: an MCU is an (N hmax) x (N vmax) patch of the output; a lane takes a strip of SW = min(4, N hmax)
+// pixels of one patch row (box replication of the chroma samples at the output resolution, as pixels_generic does at scale 1).
+// Output rows need not be 4-byte aligned; pixels outside out_w x out_h (g.width, g.height) are not written.
+template <uint32_t N>
+__device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm, uint8_t *out_img, bool aligned)
+{
+    const uint32_t PW = N * g.hmax, PH = N * g.vmax, SW = PW < 4u ? PW : 4u;
+    const uint32_t lspr = PW / SW == 2u ? 1u : 0u, lph = 31u - __builtin_clz(PH);
+    const uint32_t items = nm << (lph + lspr);
+    const bool al = aligned && SW == 4u;
+    for (uint32_t i = threadIdx.x; i < items; i += 256u) {
+        const uint32_t t = i >> (lph + lspr), r = (i >> lspr) & (PH - 1u), sx = i & ((1u << lspr) - 1u);
+        const uint32_t m = m0 + t, my = m / g.mcux, mx = m - my * g.mcux;
+        const uint32_t X = mx * PW + sx * SW, Y = my * PH + r;
+        if (X >= g.width || Y >= g.height) continue;
+        const uint32_t npix = min(SW, g.width - X);
+        float s[3][4];
+#pragma unroll
+        for (uint32_t c = 0; c < 3; c++) {
+            if (c >= g.ncomp) break;
+            const uint32_t ys = r >> g.ysh[c], bro = g.first[c] + (ys / N) * g.ch[c];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                const uint32_t xs = min(sx * SW + k, PW - 1u) >> g.xsh[c];
+                s[c][k] = tile[(t * g.bpm + bro + xs / N) * kPixStride + (ys % N) * N + xs % N];
+            }
+        }
+        Rgb p[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (g.ncomp == 3) p[k] = ycc_to_rgb(s[0][k], chroma_terms(s[1][k], s[2][k]));
+            else p[k].r = p[k].g = p[k].b = s[0][k];
+        }
+        store4(out_img + (size_t(Y) * g.width + X) * 3, pack4(p), al, npix);
+    }
+}
+
 // MODE 0: any sampling layout.  MODE 1: Y 2x2 + Cb 1x1 + Cr 1x1 (4:2:0, 6 blocks per MCU, tile = 32 MCUs).
 // MODE 2: any sampling layout, REF_COMPAT placement into the f32 plane scratch (k_ref_color finishes the image).
+// MODE 3, 4: any sampling layout, scaled decode at 1/2 and 1/4 (phases 0-2 on the low 4x4 / 2x2 corner, pixels_scaled).
 //   phase 0  zero the tile's sample rows in LDS
 //   phase 1  scatter the tile's slice of the compact coefficient stream into them, entry-parallel (lane i holds
 //            entries i, i+256, ... prefetched during the previous tile), DC values from dcbuf (prediction-summed);
@@ -3326,7 +3430,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     const uint32_t *__restrict__ eoff = tile_eoff + im.tile_off;
     const int32_t *__restrict__ dcs = dcbuf + im.coef_off;
     uint8_t *__restrict__ out_img = rgb + im.rgb_off;
-    const bool aligned = ((width * 3u) & 3u) == 0 && (im.rgb_off & 3u) == 0;
+    constexpr bool SCALED = MODE >= 3;
+    const bool aligned = (((SCALED ? im.out_w : width) * 3u) & 3u) == 0 && (im.rgb_off & 3u) == 0;
     // The stream offsets of all the workgroup's tiles are fetched once: a tile's entries can then be requested without
     // first waiting for its offsets (two dependent round trips per tile were what paced the tile loop).
     // (Quad-interleaved stream: an offset is subsequence * column capacity + entry index in the column; split here, once.)
@@ -3390,7 +3495,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
         constexpr uint8_t ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-        s_nat[tid] = uint8_t(idct_slot(ZZ[tid]));      // zig-zag position -> where the inverse DCT expects the coefficient
+        if constexpr (SCALED) s_nat[tid] = uint8_t(scaled_slot(ZZ[tid], scaled_n<MODE>()));
+        else s_nat[tid] = uint8_t(idct_slot(ZZ[tid]));      // zig-zag position -> where the inverse DCT expects the coefficient
     }
     if (!M420 && tid < tile_blocks) s_comp[tid] = im.blk_comp[tid % bpm];
     // the lane's own block slot (tid) has the same component in every tile (a tile is whole MCUs): its DC multiplier and level shift
@@ -3399,7 +3505,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     float my_dc_add = (MODE != 2 && my_comp == 0) ? 128.0f : 0.0f;
     float *tile_f = reinterpret_cast<float *>(smem_px);
     GenShape gshape{};
-    if (MODE == 0) gshape = gen_shape(im);
+    if (MODE == 0 || SCALED) gshape = gen_shape(im);
+    if constexpr (SCALED) { gshape.width = im.out_w; gshape.height = im.out_h; }
     // (the first tile's words are settled before the loop, so that on no path into a tile iteration a load is pending
     // on them: see the settle point behind phase 2)
     settle(cur);
@@ -3420,7 +3527,12 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     for (uint32_t tile = tile0; tile < tile1; tile++) {
         const uint32_t m0 = tile * T;
         const uint32_t nm = min(T, nmcu - m0), nblk = nm * bpm;
-        if (!clean) {   // phase 0
+        if constexpr (SCALED) {   // phase 0 (scaled: the corner's N x N floats of every block)
+            constexpr uint32_t Q = scaled_n<MODE>() * scaled_n<MODE>() / 4u;
+            float4 *z = reinterpret_cast<float4 *>(smem_px);
+            for (uint32_t i = tid; i < nblk * Q; i += LANES) z[(i / Q) * (kPixStride / 4) + i % Q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            __syncthreads();
+        } else if (!clean) {   // phase 0
             float4 *z = reinterpret_cast<float4 *>(smem_px);
             const uint32_t nq = nblk * (kPixStride / 4);
             for (uint32_t i = tid; i < nq; i += LANES) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -3520,7 +3632,9 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
         MJX_SB(2);
         __syncthreads();
         MJX_SB(3);
-        if (tid < nblk) idct_row_inplace(tile_f + tid * kPixStride);
+        if constexpr (SCALED) {
+            if (tid < nblk) idct_scaled_inplace<scaled_n<MODE>()>(tile_f + tid * kPixStride);
+        } else if (tid < nblk) idct_row_inplace(tile_f + tid * kPixStride);
         MJX_SB(4);
         __syncthreads();
         MJX_SB(3);
@@ -3548,6 +3662,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             clean = whole;
         } else if (MODE == 2) {
             place_ref(im, tile_f, tile * tile_blocks, nblk, planes);
+        } else if constexpr (SCALED) {
+            pixels_scaled<scaled_n<MODE>()>(gshape, tile_f, m0, nm, out_img, aligned);
         } else {
             pixels_generic(gshape, tile_f, m0, nm, out_img, aligned);
         }
@@ -3560,6 +3676,46 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     sp.end();
 #endif
 #undef MJX_SB
+}
+
+// Scaled decode at 1/8 (mode 5): a block gives one sample, F(0,0) / 8 (the multiplier at qm_off), so stage B reads nothing of the
+// coefficient stream, only the blocks' DC values.  One lane per output pixel: at 1/8 an MCU is an hmax x vmax patch of the output,
+// and pixel (X, Y) takes block (X h / hmax, Y v / vmax) of each component's plane (box replication, as pixels_scaled).
+// Multi-scan pictures read without the gather keep their DC values in their scans' regions (planar_dc_slot, as stage B finds them).
+extern "C" __global__ __launch_bounds__(256) void k_dc_color(const DevImage *__restrict__ images, const int32_t *__restrict__ dcbuf,
+                                                              const float *__restrict__ qmult, uint8_t *__restrict__ rgb,
+                                                              const uint32_t *__restrict__ img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    if (!im.valid || im.mode != 5u || img_flags[im.status_idx]) return;
+    const uint32_t ow = im.out_w, oh = im.out_h;
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= uint64_t(ow) * oh) return;
+    const uint32_t Y = uint32_t(i / ow), X = uint32_t(i - uint64_t(Y) * ow);
+    const uint32_t hmax = im.hmax, vmax = im.vmax;
+    const uint32_t mx = X / hmax, my = Y / vmax, lx = X - mx * hmax, ly = Y - my * vmax;
+    float s[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (uint32_t c = 0; c < 3; c++) {
+        if (c >= im.ncomp) break;
+        const uint32_t bx = hmax > im.ch[c] ? lx >> 1 : lx, by = vmax > im.cv[c] ? ly >> 1 : ly;
+        const uint32_t k = im.cfirst[c] + by * im.ch[c] + bx;
+        int32_t dc = 0;
+        if (im.planar) {
+            PlanarDc d{};
+            planar_dc_slot(images, im, blockIdx.y, k, d);
+            if (mx * d.rx + d.r0x < d.lx && my * d.ry + d.r0y < d.ly) dc = dcbuf[d.base + (my * d.ky + mx * d.kx + d.k0)];
+        } else {
+            dc = dcbuf[im.coef_off + (uint64_t(my) * im.mcux + mx) * im.bpm + k];
+        }
+        s[c] = float(dc) * qmult[im.qm_off + c * 64u] + (c == 0 ? 128.0f : 0.0f);
+    }
+    Rgb p;
+    if (im.ncomp == 3) p = ycc_to_rgb(s[0], chroma_terms(s[1], s[2]));
+    else p.r = p.g = p.b = s[0];
+    const uint32_t word = pack_u8(p.b, 2, pack_u8(p.g, 1, pack_u8(p.r, 0, 0)));
+    uint8_t *dst = rgb + im.rgb_off + i * 3;
+    dst[0] = uint8_t(word); dst[1] = uint8_t(word >> 8); dst[2] = uint8_t(word >> 16);
 }
 
 // ---- verification helper: byte-wise comparison of decoded pictures on the device ------------------------------
@@ -3641,7 +3797,10 @@ int configure_kernels(size_t huff_lds, size_t idct_lds)
                              reinterpret_cast<const void *>(k_idct_color<1, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<1, kPrefetchDense, 0>),
                              reinterpret_cast<const void *>(k_idct_color<1, 8, 1>), reinterpret_cast<const void *>(k_idct_color<1, 16, 1>),
                              reinterpret_cast<const void *>(k_idct_color<2, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<2, 8, 1>),
-                             reinterpret_cast<const void *>(k_idct_color<0, 8, 2>), reinterpret_cast<const void *>(k_idct_color<1, 8, 2>)};
+                             reinterpret_cast<const void *>(k_idct_color<0, 8, 2>), reinterpret_cast<const void *>(k_idct_color<1, 8, 2>),
+                             reinterpret_cast<const void *>(k_idct_color<3, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<3, 8, 1>),
+                             reinterpret_cast<const void *>(k_idct_color<3, 8, 2>), reinterpret_cast<const void *>(k_idct_color<4, kPrefetch, 0>),
+                             reinterpret_cast<const void *>(k_idct_color<4, 8, 1>), reinterpret_cast<const void *>(k_idct_color<4, 8, 2>)};
         for (const void *f : fns)
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(idct_lds));
     }
@@ -3819,6 +3978,17 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
         if (layout_mask & 1u) MJX_IDCT(2, kPrefetch, 0);
         if (layout_mask & 2u) MJX_IDCT(2, 8, 1);
     }
+    // scaled decode at 1/2 (mode 3) and 1/4 (mode 4); 1/8 is launch_dc_color's
+    if (mode_mask & 8u) {
+        if (layout_mask & 1u) MJX_IDCT(3, kPrefetch, 0);
+        if (layout_mask & 2u) MJX_IDCT(3, 8, 1);
+        if (layout_mask & 4u) MJX_IDCT(3, 8, 2);
+    }
+    if (mode_mask & 16u) {
+        if (layout_mask & 1u) MJX_IDCT(4, kPrefetch, 0);
+        if (layout_mask & 2u) MJX_IDCT(4, 8, 1);
+        if (layout_mask & 4u) MJX_IDCT(4, 8, 2);
+    }
 #undef MJX_IDCT
 }
 
@@ -3846,6 +4016,13 @@ void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, con
                       const unsigned long long *planes, uint8_t *rgb, const uint32_t *img_flags)
 {
     hipLaunchKernelGGL(k_ref_color, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, planes, rgb, img_flags);
+}
+
+void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
+                     const float *qmult, uint8_t *rgb, const uint32_t *img_flags)
+{
+    if (max_pixel_wgs == 0 || nimg == 0) return;
+    hipLaunchKernelGGL(k_dc_color, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
 }
 
 }   // namespace mjx

@@ -177,6 +177,10 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
 {
     p = ImagePlan{};
     auto fail = [&](int code) { p.status = code; return code; };
+    const uint32_t scale = opts.scale_denom <= 1 ? 1u : opts.scale_denom;
+    if (scale != 1 && scale != 2 && scale != 4 && scale != 8) return fail(MJX_ERR_INVALID_ARG);
+    if (scale != 1 && opts.layout == MJX_LAYOUT_REF_COMPAT) return fail(MJX_ERR_INVALID_ARG);    // (the reference has no scaled decode)
+    p.scale = scale;
     const bool gather = d.n_parts != 0;            // the picture of a multi-scan file: geometry only, no scan of its own
     if (gather) {
         if (!d.parts || d.n_parts < 2 || d.n_parts > 3 || d.ncomp != 3) return fail(MJX_ERR_UNSUPPORTED_FORMAT);
@@ -193,6 +197,8 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     if (d.scan_len >= (size_t(1) << 28)) return fail(MJX_ERR_UNSUPPORTED_FORMAT);  // bit positions are 32 bit
     p.width = d.width;
     p.height = d.height;
+    p.out_w = (p.width + scale - 1) / scale;
+    p.out_h = (p.height + scale - 1) / scale;
     p.ncomp = d.ncomp;
     p.layout = opts.layout;
     p.scan = d.scan;
@@ -396,6 +402,16 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
         for (int k = 0; k < 64; k++) {
             const int nat = kZigZag[k];
             p.qmult[c][k] = float(double(d.qt[p.tq[c]][k]) * aan[nat >> 3] * aan[nat & 7] / 8.0);
+        }
+    // scaled decode: the N-point transforms of the kernels are plain cosine sums, C(u) C(v) / 4 goes here (N = 8 / scale)
+    const uint32_t n = 8 / scale;
+    std::memset(p.qmult_scaled, 0, sizeof p.qmult_scaled);
+    for (uint32_t c = 0; c < p.ncomp; c++)
+        for (int k = 0; k < 64; k++) {
+            const uint32_t nat = kZigZag[k], v = nat >> 3, u = nat & 7;
+            if (u >= n || v >= n) continue;
+            const double cu = u == 0 ? std::sqrt(0.5) : 1.0, cv = v == 0 ? std::sqrt(0.5) : 1.0;
+            p.qmult_scaled[c][k] = float(double(d.qt[p.tq[c]][k]) * cu * cv / 4.0);
         }
     return p.status;
 }

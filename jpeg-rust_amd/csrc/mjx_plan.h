@@ -29,6 +29,10 @@ struct ImagePlan {
     std::vector<LutEntry> lut;                     // all decode tables of the image, concatenated: the plain set (what the write pass
     uint32_t lut_plain_n = 0;                      // uses), then from lut_plain_n on the set with pair parts (the counting passes)
     float qmult[3][64];                            // per component, zig-zag order: q[k] * idct prescale
+    // scaled decode (mjx_opts.scale_denom): 1, 2, 4 or 8, the output size ceil(width / scale) x ceil(height / scale), and the
+    // multipliers of the reduced transforms (zig-zag order: q[k] * C(u) C(v) / 4 inside the low N x N corner, 0 outside)
+    uint32_t scale = 1, out_w = 0, out_h = 0;
+    float qmult_scaled[3][64];
     const uint8_t *scan = nullptr;
     size_t scan_len = 0;
     // The scan still holds FF00 pairs (and RSTn markers): it is de-stuffed on the device at upload (k_destuff_*), scan_len is

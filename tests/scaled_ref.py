@@ -1,0 +1,131 @@
+"""Numpy reference of the scaled decode (include/mjx.h, mjx_opts.scale_denom), in float64.
+
+Inputs: the oracle's STANDARD-layout T0 coefficients (per component, blocks in decode order, MCU-major, v x h inside the MCU,
+zig-zag order, DC prediction applied), the file's DQT tables and its SOF sampling factors.  Per block the low N x N corner
+(N = 8 / s) of the dequantised coefficients goes through
+
+    f(x,y) = 1/4 sum_{u,v<N} C(u) C(v) F(u,v) cos((2x+1) u pi / 2N) cos((2y+1) v pi / 2N),   C(0) = 1/sqrt(2), C(k>0) = 1
+
+(+ 128 on luminance); output pixel (X, Y) takes the sample at (X h / Hmax, Y v / Vmax) of each component's plane, then the
+STANDARD layout's colour formula (decoder.rs:392-402) and its clamping, truncating store (decoder.rs:382-390).
+"""
+import math
+import struct
+
+import numpy as np
+
+import oracle_binding as orc
+
+ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
+                   28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54,
+                   47, 55, 62, 63])
+
+
+def jpeg_tables(data):
+    """-> (width, height, [(h, v, tq) per component in frame order], {slot: 64 DQT entries in zig-zag order}), from the
+    first SOF0/SOF1 and the DQT segments in front of it."""
+    qt, comps, i = {}, None, 2
+    while i + 4 <= len(data):
+        if data[i] != 0xFF:
+            i += 1
+            continue
+        m = data[i + 1]
+        if m in (0x01, 0xFF) or 0xD0 <= m <= 0xD8:
+            i += 2 if m != 0xFF else 1
+            continue
+        ln = struct.unpack(">H", data[i + 2:i + 4])[0]
+        seg = data[i + 4:i + 2 + ln]
+        if m == 0xDB:
+            j = 0
+            while j < len(seg):
+                pq, tq = seg[j] >> 4, seg[j] & 15
+                if pq:
+                    qt[tq] = list(struct.unpack(">64H", seg[j + 1:j + 129]))
+                    j += 129
+                else:
+                    qt[tq] = list(seg[j + 1:j + 65])
+                    j += 65
+        elif m in (0xC0, 0xC1):
+            h_, w_ = struct.unpack(">HH", seg[1:5])
+            nc = seg[5]
+            comps = [(seg[6 + 3 * k + 1] >> 4, seg[6 + 3 * k + 1] & 15, seg[6 + 3 * k + 2]) for k in range(nc)]
+            return w_, h_, comps, qt
+        elif m == 0xDA:
+            break
+        i += 2 + ln
+    raise ValueError("no baseline SOF")
+
+
+def _basis(n):
+    """M[x, u] = C(u) cos((2x+1) u pi / 2N)"""
+    m = np.empty((n, n))
+    for x in range(n):
+        for u in range(n):
+            m[x, u] = (math.sqrt(0.5) if u == 0 else 1.0) * math.cos((2 * x + 1) * u * math.pi / (2 * n))
+    return m
+
+
+def planes(data, scale, dec=None):
+    """-> (width, height, comps, [scaled plane per component, float64, the full MCU grid], hmax, vmax)"""
+    w, h, comps, qt = jpeg_tables(data)
+    if dec is None:
+        dec = orc.decode(data, layout=orc.LAYOUT_STD, ext_1bit=True, ext_dri=True, ext_multiscan=True)
+    if len(comps) == 1:
+        comps = [(1, 1, comps[0][2])]          # (one component: non-interleaved, one block per MCU whatever SOF0 says)
+    hmax, vmax = max(c[0] for c in comps), max(c[1] for c in comps)
+    mcux, mcuy = -(-w // (8 * hmax)), -(-h // (8 * vmax))
+    n = 8 // scale
+    M = _basis(n)
+    out = []
+    for c, (hc, vc, tq) in enumerate(comps):
+        co = dec.coefs[c].astype(np.float64)
+        assert co.shape[0] == mcux * mcuy * hc * vc, (co.shape, mcux, mcuy, hc, vc)
+        deq = co * np.asarray(qt[tq], np.float64)[None, :]
+        nat = np.zeros_like(deq)
+        nat[:, ZIGZAG] = deq                    # natural index = row (vertical frequency) * 8 + column
+        F = nat.reshape(-1, 8, 8)[:, :n, :n]
+        S = 0.25 * np.einsum("yv,bvu,xu->byx", M, F, M)
+        if c == 0:
+            S = S + 128.0
+        S = S.reshape(mcuy, mcux, vc, hc, n, n).transpose(0, 2, 4, 1, 3, 5).reshape(mcuy * vc * n, mcux * hc * n)
+        out.append(S)
+    return w, h, comps, out, hmax, vmax
+
+
+def to_u8(x):
+    """decoder.rs:382-390 f32_to_u8: clamp to [0, 255], truncate.  A value within 1e-9 of an integer counts as that integer: the
+    float64 sums can leave an exactly integral sample (a flat block, C(0)^2 = 1/2 times a negative DC) a few ulps below it, where
+    truncation would drop a whole level the contract does not drop."""
+    return np.trunc(np.clip(np.round(x, 9), 0.0, 255.0)).astype(np.uint8)
+
+
+def scaled_rgb(data, scale, dec=None):
+    """-> the expected picture [ceil(H/s), ceil(W/s), 3] uint8 of `data` decoded at 1/scale (scale 1: the full-size picture)"""
+    w, h, comps, pl, hmax, vmax = planes(data, scale, dec)
+    ow, oh = -(-w // scale), -(-h // scale)
+    X, Y = np.arange(ow), np.arange(oh)
+    smp = []
+    for (hc, vc, _), p in zip(comps, pl):
+        smp.append(p[(Y * vc // vmax)[:, None], (X * hc // hmax)[None, :]])
+    if len(smp) == 1:
+        v = to_u8(smp[0])
+        return np.repeat(v[:, :, None], 3, axis=2)
+    y, cb, cr = smp
+    c_red, c_green, c_blue = 0.299, 0.587, 0.114
+    r = cr * (2 - 2 * c_red) + y
+    b = cb * (2 - 2 * c_blue) + y
+    g = (y - c_blue * b - c_red * r) / c_green
+    return np.stack([to_u8(r), to_u8(g), to_u8(b)], axis=2)
+
+
+def box_mean(rgb, s):
+    """s x s box mean of a full-size picture (edge boxes: what they cover) -> float64 [ceil(H/s), ceil(W/s), 3]"""
+    h, w, _ = rgb.shape
+    oh, ow = -(-h // s), -(-w // s)
+    pad = np.zeros((oh * s, ow * s, 3))
+    cnt = np.zeros((oh * s, ow * s, 1))
+    pad[:h, :w] = rgb
+    cnt[:h, :w] = 1
+    ps = pad.reshape(oh, s, ow, s, 3).sum(axis=(1, 3))
+    cs = cnt.reshape(oh, s, ow, s, 1).sum(axis=(1, 3))
+    return ps / cs
