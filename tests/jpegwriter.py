@@ -3,9 +3,11 @@
 Builds files the synthetic generator cannot: pictures from chosen coefficient blocks (the T1 per-block tier),
 custom Huffman tables (every run/size symbol, including the degenerate `0x?0` ones of SURVEY Q9), and entropy-coded
 segments that are syntactically valid symbol sequences but semantically corrupt (runs past the end of a block), on which
-the reference does not panic but clamps (src/jpeg/huffman.rs:170-189).  Only markers the reference parses are written
-(src/jpeg/mod.rs:166-179): SOI, DQT, SOF0, DHT, SOS, EOI.
+the reference does not panic but clamps (src/jpeg/huffman.rs:170-189), and pictures of every sampling layout (layout_jpeg).
+Only markers the reference parses are written (src/jpeg/mod.rs:166-179): SOI, DQT, SOF0, DHT, SOS, EOI -- and DRI with RSTn
+markers where a test asks for restart intervals.
 """
+import os
 import struct
 
 import numpy as np
@@ -107,9 +109,10 @@ def encode_blocks(blocks, comp_of_block, dc_codes, ac_codes):
     return w.flush()
 
 
-def write_jpeg(width, height, comps, qts, dhts, entropy, qt16=False):
+def write_jpeg(width, height, comps, qts, dhts, entropy, qt16=False, restart_interval=0):
     """comps: [(id, h, v, tq, td, ta)] in frame = scan order; qts: {slot: 64 values in zig-zag (file) order};
-    dhts: {(class, slot): (bits, vals)}; entropy: the stuffed entropy-coded segment."""
+    dhts: {(class, slot): (bits, vals)}; entropy: the stuffed entropy-coded segment (with its RSTn markers);
+    restart_interval: > 0 writes a DRI segment in front of the scan."""
     out = bytearray(b"\xff\xd8")
     for slot, q in sorted(qts.items()):
         if qt16:
@@ -121,6 +124,8 @@ def write_jpeg(width, height, comps, qts, dhts, entropy, qt16=False):
         out += bytes([cid, (h << 4) | v, tq])
     for (tc, th), (bits, vals) in sorted(dhts.items()):
         out += b"\xff\xc4" + struct.pack(">H", 2 + 17 + len(vals)) + bytes([(tc << 4) | th]) + bytes(bits) + bytes(vals)
+    if restart_interval:
+        out += b"\xff\xdd" + struct.pack(">HH", 4, restart_interval)
     out += b"\xff\xda" + struct.pack(">HB", 6 + 2 * len(comps), len(comps))
     for cid, _, _, _, td, ta in comps:
         out += bytes([cid, (td << 4) | ta])
@@ -193,31 +198,38 @@ def random_symbol_stream(rng, nsymbols, dc_tab, ac_tab, p_dc=0.12, max_size=15):
     return w.flush(), blocks
 
 
-# ---- non-interleaved twins of interleaved files, without Pillow (tests/golden/make_multiscan.py is the checked version) ---
-def _fast_encode_blocks(blocks, dc_codes, ac_codes):
-    """encode_blocks for one component, touching only the non-zero coefficients (a 4K picture has 200 000 blocks)."""
-    w, pred = BitWriter(), 0
+# ---- fast entropy coding, non-interleaved twins without Pillow (tests/golden/make_multiscan.py is the checked version) ---
+def encode_scan(blocks, comp_of_block, dc_codes, ac_codes, restart_blocks=0):
+    """encode_blocks touching only the non-zero coefficients (a 4K picture has 200 000 blocks).  restart_blocks > 0: after every
+    restart_blocks blocks (one restart interval) but the last, pad with 1-bits to a byte, write RST0..RST7 in turn and reset the
+    DC predictors (T.81 F.1.2.3, E.1.4)."""
+    w, pred, rst = BitWriter(), {}, 0
     nzr, nzc = np.nonzero(blocks[:, 1:])
     starts = np.searchsorted(nzr, np.arange(blocks.shape[0] + 1))
     for k in range(blocks.shape[0]):
+        if restart_blocks and k and k % restart_blocks == 0:
+            w.flush()
+            w.out += bytes([0xff, 0xd0 + rst % 8])
+            rst += 1
+            pred = {}
+        c = comp_of_block[k]
         blk = blocks[k]
-        s, bits = magnitude(int(blk[0]) - pred)
-        pred = int(blk[0])
-        w.put(*dc_codes[s])
+        s, bits = magnitude(int(blk[0]) - pred.get(c, 0))
+        pred[c] = int(blk[0])
+        w.put(*dc_codes[c][s])
         w.put(bits, s)
         prev = 0
-        cols = nzc[starts[k]:starts[k + 1]] + 1
-        for i in cols:
+        for i in nzc[starts[k]:starts[k + 1]] + 1:
             run = int(i) - prev - 1
             while run > 15:
-                w.put(*ac_codes[0xf0])
+                w.put(*ac_codes[c][0xf0])
                 run -= 16
             s, bits = magnitude(int(blk[i]))
-            w.put(*ac_codes[(run << 4) | s])
+            w.put(*ac_codes[c][(run << 4) | s])
             w.put(bits, s)
             prev = int(i)
         if prev < 63:
-            w.put(*ac_codes[0x00])
+            w.put(*ac_codes[c][0x00])
     return w.flush()
 
 
@@ -251,6 +263,101 @@ def noninterleaved_twin(data, ref):
         raster = mc[(yy // v) * mcux + (xx // h), yy % v, xx % h].reshape(-1, 64)
         _, td, ta = sos_comp[c]
         out += bytes([0xff, 0xda, 0, 8, 1, cid, (td << 4) | ta, 0, 63, 0])
-        out += _fast_encode_blocks(raster, dht[(0, td)], dht[(1, ta)])
+        out += encode_scan(raster, [0] * len(raster), {0: dht[(0, td)]}, {0: dht[(1, ta)]})
     out += b"\xff\xd9"
     return bytes(out)
+
+
+# ---- any sampling layout: h, v in {1, 2} per component (tests/test_sampling_layouts.py) --------------------------------
+ANNEX_K_LUMA = [16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29,
+                51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120,
+                101, 72, 92, 95, 98, 112, 100, 103, 99]            # T.81 Table K.1, natural order
+ANNEX_K_CHROMA = [17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99,
+                  99, 99, 99, 99] + [99] * 32                       # T.81 Table K.2
+
+
+def quality_table(base, quality):
+    """A K.1/K.2 table scaled to `quality` (the usual 5000/q, 200-2q rule), zig-zag (file) order, entries 1..255."""
+    q = max(1, min(100, int(quality)))
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    nat = [max(1, min(255, (b * s + 50) // 100)) for b in base]
+    return [nat[z] for z in ZIGZAG]
+
+
+def _dct_matrix():
+    m = np.empty((8, 8))
+    for u in range(8):
+        for x in range(8):
+            m[u, x] = (np.sqrt(0.125) if u == 0 else 0.5) * np.cos((2 * x + 1) * u * np.pi / 16)
+    return m
+
+
+def fdct_quantise(plane, qt_zz):
+    """float64 forward DCT of a plane (level-shifted samples; both sides multiples of 8) -> quantised blocks int [n, 64] in
+    raster order over the plane's block grid, zig-zag order (AC clamped to the Annex-K tables' size 10)."""
+    h, w = plane.shape
+    m = _dct_matrix()
+    b = plane.reshape(h // 8, 8, w // 8, 8).transpose(0, 2, 1, 3).reshape(-1, 8, 8)
+    f = np.einsum("ux,bxy,vy->buv", m, b, m).reshape(-1, 64)[:, ZIGZAG]
+    q = np.rint(f / np.asarray(qt_zz, np.float64)[None, :]).astype(np.int32)
+    q[:, 1:] = np.clip(q[:, 1:], -1023, 1023)
+    return q
+
+
+def _annex_k_tables():
+    p = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pil", "std_420_q100.jpg")     # Pillow writes Annex K
+    with open(p, "rb") as f:
+        return tables_from_jpeg(f.read())
+
+
+def layout_jpeg(width, height, hv, quality=75, seed=0, tables="split", restart=None, gray_hv=None, noise=4.0):
+    """A baseline file of any sampling layout, written from float64 DCT coefficients (not by the project's own generator).
+
+    hv: [(h, v)] * 3 (Y, Cb, Cr), h, v in {1, 2}; or None with gray_hv = (h, v): one component whose SOF carries those factors
+    (its scan is non-interleaved: one block per MCU over ceil(W/8) x ceil(H/8) blocks whatever they are).  Content: smooth
+    plane waves plus gaussian noise per component at its own resolution over the whole MCU grid.  tables: "split" (Y on
+    slot 0, Cb and Cr on slot 1), "shared" (all on slot 0) or "three" (Cr on slot 2, its DQT coarser than Cb's).
+    restart=n: DRI n and an RSTn marker every n MCUs.
+    -> (bytes, [quantised blocks per component: int [n, 64], zig-zag, absolute DC, in decode order -- the oracle's T0])"""
+    rng = np.random.default_rng(seed)
+    if hv is None:
+        comps_hv, mcu_hv = [tuple(gray_hv)], [(1, 1)]
+    else:
+        comps_hv = mcu_hv = [tuple(x) for x in hv]
+    hmax, vmax = max(h for h, _ in mcu_hv), max(v for _, v in mcu_hv)
+    mcux, mcuy = -(-width // (8 * hmax)), -(-height // (8 * vmax))
+    slot = {"split": [0, 1, 1], "shared": [0, 0, 0], "three": [0, 1, 2]}[tables]
+    qts = {0: quality_table(ANNEX_K_LUMA, quality)}
+    if len(comps_hv) == 3 and tables != "shared":
+        qts[1] = quality_table(ANNEX_K_CHROMA, quality)
+        if tables == "three":
+            qts[2] = quality_table(ANNEX_K_CHROMA, max(1, quality // 2))
+    ak = _annex_k_tables()
+    dhts = {}
+    for s in sorted(set(slot[:len(comps_hv)])):
+        src = 0 if s == 0 else 1
+        dhts[(0, s)], dhts[(1, s)] = ak[(0, src)], ak[(1, src)]
+    per_comp, comp_rows = [], []
+    for c, (h, v) in enumerate(mcu_hv):
+        ph, pw = mcuy * v * 8, mcux * h * 8
+        yy, xx = np.mgrid[0:ph, 0:pw].astype(np.float64)
+        amp, base = (60.0, 0.0) if c == 0 else (35.0, 0.0)
+        p = np.full((ph, pw), base)
+        for _ in range(3):
+            fx, fy, ph0 = rng.uniform(-0.08, 0.08), rng.uniform(-0.08, 0.08), rng.uniform(0, 2 * np.pi)
+            p += amp / 3 * np.sin(2 * np.pi * (fx * xx + fy * yy) + ph0)
+        p += rng.normal(0.0, noise, p.shape)
+        p = np.clip(p, -128.0, 127.0)
+        blocks = fdct_quantise(p, qts[slot[c]])
+        # raster over the component's grid -> decode order (MCU-major, v x h inside the MCU)
+        g = blocks.reshape(mcuy, v, mcux, h, 64).transpose(0, 2, 1, 3, 4).reshape(-1, 64)
+        per_comp.append(g)
+        comp_rows.append(h * v)
+    bpm = sum(comp_rows)
+    order = np.concatenate([pc.reshape(mcux * mcuy, k, 64) for pc, k in zip(per_comp, comp_rows)], axis=1).reshape(-1, 64)
+    comp_of_block = [c for c, k in enumerate(comp_rows) for _ in range(k)] * (mcux * mcuy)
+    dc = {c: huff_codes(*dhts[(0, slot[c])]) for c in range(len(comps_hv))}
+    ac = {c: huff_codes(*dhts[(1, slot[c])]) for c in range(len(comps_hv))}
+    ent = encode_scan(order, comp_of_block, dc, ac, restart_blocks=(restart or 0) * bpm)
+    comps = [(c + 1, h, v, slot[c], slot[c], slot[c]) for c, (h, v) in enumerate(comps_hv)]
+    return write_jpeg(width, height, comps, qts, dhts, ent, restart_interval=restart or 0), per_comp
