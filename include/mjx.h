@@ -118,7 +118,11 @@ typedef struct mjx_scan_desc {
     uint32_t n_restart;            /* entries of restart_offsets */
     const uint32_t *restart_offsets; /* byte offset in `scan` of the first byte of interval 1, 2, ... (interval 0 starts at 0) */
     /* Multi-scan files: n_parts > 0 means `scan` is NULL, `comp` lists the frame's components in frame order and every
-       component is carried by exactly one of `parts`; the dc / ac slots above are not used. */
+       component is carried by exactly one of `parts`; the dc / ac slots above are not used.  DQT, DHT and DRI segments may
+       stand between the scans (T.81 B.2.4): a part keeps the Huffman tables and the restart interval in force at its SOS, and a
+       component keeps the quantisation table its slot holds when the scan that carries it starts (libjpeg's rule; a DQT
+       further on does not change it, a slot not defined by then is MJX_ERR_MISSING_TABLE).  mjx_parse puts component c's
+       table in qt[c] and sets comp[c].tq = c (qt_present = 7, qt[3] zero). */
     uint8_t n_parts;
     const mjx_scan_part *parts;
     void *owner_;                  /* internal: storage behind `scan` / `parts` when filled by mjx_parse */

@@ -50,6 +50,7 @@ struct ParserState {
         uint8_t ncomp = 0, comp[3] = {0, 0, 0}, td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
         unsigned restart_interval = 0;
         mjx_hufftab dc[3], ac[3];
+        uint16_t qt[3][64];            // each component's quantisation table, latched when the SOS was read
     };
     std::vector<Part> parts;
     // storage lent by the caller for the de-stuffed scan (mjx_parse_into); null: the parser allocates
@@ -154,6 +155,11 @@ size_t read_part(const ByteView &f, size_t i, const ScanCompSel *sel, unsigned n
             for (unsigned k = 0; k < p.ncomp; k++) if (p.comp[k] == ci) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};   // twice
         for (unsigned k = 0; k < q; k++) if (part.comp[k] == ci) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};
         if (!((d->dc_present >> sel[q].td) & 1) || !((d->ac_present >> sel[q].ta) & 1)) throw ParseError{MJX_ERR_MISSING_TABLE};
+        // the component's quantisation table is the one its slot holds now, when its scan starts (libjpeg's
+        // latch_quant_tables): a DQT further on does not change it
+        const unsigned tq = st.frame[size_t(ci)].tq;
+        if (tq > 3 || !((d->qt_present >> tq) & 1)) throw ParseError{MJX_ERR_MISSING_TABLE};
+        std::memcpy(part.qt[q], d->qt[tq], sizeof part.qt[q]);
         part.comp[q] = uint8_t(ci);
         part.td[q] = sel[q].td;
         part.ta[q] = sel[q].ta;
@@ -200,9 +206,10 @@ void finish_parts(ParserState &st)
     d->ncomp = uint8_t(st.frame.size());
     for (size_t k = 0; k < n; k++) {
         const ParserState::Part &p = st.parts[k];
-        for (unsigned q = 0; q < p.ncomp; q++) {
+        for (unsigned q = 0; q < p.ncomp; q++) {                                  // component c: its latched table in slot c
             const FrameComp &fc = st.frame[p.comp[q]];
-            d->comp[p.comp[q]] = mjx_comp{fc.id, fc.h, fc.v, fc.tq, p.td[q], p.ta[q]};
+            d->comp[p.comp[q]] = mjx_comp{fc.id, fc.h, fc.v, p.comp[q], p.td[q], p.ta[q]};
+            std::memcpy(d->qt[p.comp[q]], p.qt[q], sizeof d->qt[0]);
         }
         mjx_scan_part &o = parts[k];
         std::memset(&o, 0, sizeof o);
@@ -221,6 +228,8 @@ void finish_parts(ParserState &st)
         o.n_restart = uint32_t(p.rst.size());
         o.restart_offsets = p.rst.empty() ? nullptr : rst;
     }
+    std::memset(d->qt[3], 0, sizeof d->qt[3]);
+    d->qt_present = 7;
     d->scan = nullptr;
     d->scan_len = 0;
     d->n_parts = uint8_t(n);

@@ -358,6 +358,7 @@ typedef struct {
         int ncomp;
         int comp[2];                   /* indices into fcomp, scan order */
         orc_htable dc[2], ac[2];       /* the tables the scan selected, as they were when its SOS was read */
+        uint16_t qt[2][64];            /* each component's quantisation table, latched when its SOS was read */
         const uint8_t *data;           /* its entropy-coded segment, FF00 compacted, RSTn left in */
         size_t len;
         int restart_interval;
@@ -629,12 +630,18 @@ static void orc_decode_parts(orc_env *env, const orc_opts *opts, orc_parse *ps, 
     int covered = 0;
     for (int q = 0; q < ps->nparts; q++) covered += ps->parts[q].ncomp;
     if (covered != ps->ncomp_frame || covered != 3) orc_panic(env, ORC_ERR_UNSUPPORTED, "multi-scan file: a component without a scan");
+    /* every component dequantises with the table it latched at its scan: from here on slot c holds component c's */
+    for (int q = 0; q < ps->nparts; q++)
+        for (int k = 0; k < ps->parts[q].ncomp; k++) {
+            memcpy(ps->qt[ps->parts[q].comp[k]], ps->parts[q].qt[k], sizeof ps->qt[0]);
+            ps->qt_present[ps->parts[q].comp[k]] = 1;
+        }
     orc_compfields ordered[3];
     for (int c = 0; c < 3; c++) {
         ordered[c].component = ps->fcomp[c].id;
         ordered[c].h = ps->fcomp[c].h;
         ordered[c].v = ps->fcomp[c].v;
-        ordered[c].quantization_id = ps->fcomp[c].tq;
+        ordered[c].quantization_id = (uint8_t)c;
         ordered[c].dc_table_id = ordered[c].ac_table_id = 0;
     }
     out->width = ps->width; out->height = ps->height; out->ncomp = 3;
@@ -773,6 +780,10 @@ static void orc_parse_and_decode(orc_env *env, const uint8_t *vec, size_t len, c
                         for (int j = 0; j < ps->parts[p].ncomp; j++) if (ps->parts[p].comp[j] == ci) orc_panic(env, ORC_ERR_UNSUPPORTED, "multi-scan file: component coded twice");
                     PANIC_IF(!ps->dc[sc[k].dc_sel].present || !ps->ac[sc[k].ac_sel].present, "table unwrap on None");
                     ps->parts[q].comp[k] = ci;
+                    /* the component's quantisation table is the one its slot holds now, when its scan starts (libjpeg's
+                       latch_quant_tables): a DQT further on does not change it */
+                    PANIC_IF(ps->fcomp[ci].tq > 3 || !ps->qt_present[ps->fcomp[ci].tq], "Did not find quantization table");
+                    memcpy(ps->parts[q].qt[k], ps->qt[ps->fcomp[ci].tq], sizeof ps->parts[q].qt[k]);
                     ps->parts[q].dc[k] = ps->dc[sc[k].dc_sel];
                     ps->parts[q].ac[k] = ps->ac[sc[k].ac_sel];
                 }

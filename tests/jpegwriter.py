@@ -236,36 +236,222 @@ def encode_scan(blocks, comp_of_block, dc_codes, ac_codes, restart_blocks=0):
 def noninterleaved_twin(data, ref):
     """One scan per component, blocks in raster order over the component's own block grid (T.81 A.2.2), from the quantised
     coefficients `ref` (oracle decode of `data`, STANDARD layout).  Same coefficients, same picture."""
-    comps, dht, sos_comp, sos_at, i = [], {}, [], None, 2
+    return script_twin(data, ref, "Y;Cb;Cr")
+
+
+# ---- every multi-scan script of a three-component baseline frame (tests/test_multiscan_scripts.py) ---------------------------
+# Scans in file order, ';' between scans, the components of a scan in frame order: each component alone in any order, or a
+# pair interleaved and the third alone, either first.
+SCRIPTS = ["Y;Cb;Cr", "Y;Cr;Cb", "Cb;Y;Cr", "Cb;Cr;Y", "Cr;Y;Cb", "Cr;Cb;Y",
+           "Y Cb;Cr", "Cr;Y Cb", "Y Cr;Cb", "Cb;Y Cr", "Cb Cr;Y", "Y;Cb Cr"]
+_COMP = {"Y": 0, "Cb": 1, "Cr": 2}
+
+
+def parse_script(script):
+    """'Cr;Y Cb' -> [[2], [0, 1]]: frame indices per scan"""
+    return [sorted(_COMP[c] for c in scan.split()) for scan in script.split(";")]
+
+
+def optimal_table(counts):
+    """T.81 K.2 (Figures K.1 to K.3, the procedure of libjpeg's jpeg_gen_optimal_table): (bits[16], vals) of a Huffman table
+    for the symbol counts {symbol: n}; codes of at most 16 bits, none of them all ones."""
+    freq = [0] * 257
+    for sym, n in counts.items():
+        freq[sym] = n
+    freq[256] = 1                                   # the reserved code point
+    size, others = [0] * 257, [-1] * 257
+    while True:
+        live = [i for i in range(257) if freq[i]]
+        if len(live) < 2:
+            break
+        c1 = max(live, key=lambda i: (-freq[i], i))                 # the least frequent; on a tie the larger symbol
+        c2 = max((i for i in live if i != c1), key=lambda i: (-freq[i], i))
+        freq[c1] += freq[c2]
+        freq[c2] = 0
+        for c in (c1, c2):
+            size[c] += 1
+            while others[c] >= 0:
+                c = others[c]
+                size[c] += 1
+        c = c1
+        while others[c] >= 0:
+            c = others[c]
+        others[c] = c2
+    bits = [0] * 33
+    for i in range(257):
+        if size[i]:
+            bits[size[i]] += 1
+    for i in range(32, 16, -1):                     # Figure K.3: no code longer than 16 bits
+        while bits[i] > 0:
+            j = i - 2
+            while bits[j] == 0:
+                j -= 1
+            bits[i] -= 2
+            bits[i - 1] += 1
+            bits[j + 1] += 2
+            bits[j] -= 1
+    i = 16
+    while bits[i] == 0:
+        i -= 1
+    bits[i] -= 1                                    # drop the reserved code point
+    vals = [s for ln in range(1, 33) for s in range(256) if size[s] == ln]
+    return bits[1:17], vals
+
+
+class _Tally(dict):
+    """Stands in for a code table of encode_scan: counts the symbols it is asked for and codes nothing."""
+
+    def __init__(self):
+        super().__init__()
+        self.n = {}
+
+    def __getitem__(self, sym):
+        self.n[sym] = self.n.get(sym, 0) + 1
+        return (0, 0)
+
+
+def _segment(marker, payload):
+    return bytes([0xff, marker]) + struct.pack(">H", 2 + len(payload)) + bytes(payload)
+
+
+def _ones_dqt(slot):
+    return bytes([slot]) + b"\x01" * 64
+
+
+def script_twins(data, ref, scripts, tables="source", dqt=None, restart=None, markers=False):
+    """The quantised coefficients `ref` (oracle decode of the interleaved baseline file `data`, STANDARD layout) re-encoded as
+    multi-scan files, one per script of `scripts` (see SCRIPTS).  A single-component scan is non-interleaved: raster order over
+    the component's own block grid (T.81 A.2.2).  A pair is interleaved on the frame's MCU grid with each component's h x v
+    blocks per MCU (A.2.3), as in `data`.  A scan that several scripts share is encoded once.
+
+    tables: "source" (the source's DHT segments in front of the frame; every scan selects the source's slots) or "per_scan"
+    (no DHT up front; right before each SOS a DHT built from that scan's symbol counts (K.2), slot q for its q-th component).
+    dqt: where quantisation tables are defined.  None: as in the source.  "after": behind each scan, every slot whose components
+    have all been scanned is redefined as a table of ones.  "split": Cr takes Cb's slot number in the frame header, and that slot
+    is defined right before each scan that carries Cb or Cr, with that component's own table (the source needs three slots,
+    layout_jpeg tables="three"; the script must keep Cb and Cr apart).  "tail": a table of ones on every slot behind the last
+    scan.  "late": the slot of the first scan's first component is left out in front and defined behind that scan (a file
+    T.81 decoders refuse: a component's table is latched when its scan starts).
+    restart: None, one interval for every scan, or one per scan of the script (0: none for that scan): a DRI segment in front of
+    each scan whose interval differs from the one in force, and RSTn markers in its data.
+    markers: a COM and an APP1 segment in front of every scan but the first, and a COM behind the last."""
+    segs, i = [], 2
     while True:
         m = data[i + 1]
         ln = struct.unpack(">H", data[i + 2:i + 4])[0]
-        p = data[i + 4:i + 2 + ln]
-        if m == 0xc0:
-            H, W, n = struct.unpack(">HH", p[1:5]) + (p[5],)
-            comps = [(p[6 + 3 * c], p[7 + 3 * c] >> 4, p[7 + 3 * c] & 15) for c in range(n)]
-        elif m == 0xda:
-            sos_comp = [(p[1 + 2 * c], p[2 + 2 * c] >> 4, p[2 + 2 * c] & 15) for c in range(p[0])]
-            sos_at = i
+        p = bytes(data[i + 4:i + 2 + ln])
+        if m == 0xda:
             break
+        segs.append((m, p))
         i += 2 + ln
-    for key, (bits, vals) in tables_from_jpeg(data).items():
-        dht[key] = huff_codes(bits, vals)
-    assert len(comps) == 3 and [c[0] for c in sos_comp] == [c[0] for c in comps]
+    sel = [(p[2 + 2 * c] >> 4, p[2 + 2 * c] & 15) for c in range(p[0])]
+    sof = [q for mk, q in segs if mk == 0xc0][0]
+    H, W = struct.unpack(">HH", sof[1:5])
+    comps = [(sof[6 + 3 * c], sof[7 + 3 * c] >> 4, sof[7 + 3 * c] & 15, sof[8 + 3 * c]) for c in range(sof[5])]
+    assert len(comps) == 3 and [p[1 + 2 * c] for c in range(p[0])] == [c[0] for c in comps]
+    qts = {}
+    for mk, q in segs:
+        j = 0
+        while mk == 0xdb and j < len(q):
+            nb = 129 if q[j] >> 4 else 65
+            qts[q[j] & 15] = q[j:j + nb]
+            j += nb
+    dht = {key: huff_codes(*t) for key, t in tables_from_jpeg(data).items()}
     hmax, vmax = max(c[1] for c in comps), max(c[2] for c in comps)
     mcux = (W + 8 * hmax - 1) // (8 * hmax)
-    out = bytearray(data[:sos_at])
-    for c, (cid, h, v) in enumerate(comps):
-        bw = ((W * h + hmax - 1) // hmax + 7) // 8
-        bh = ((H * v + vmax - 1) // vmax + 7) // 8
-        mc = ref.coefs[c].reshape(ref.mcus, v, h, 64)
-        yy, xx = np.mgrid[0:bh, 0:bw]
-        raster = mc[(yy // v) * mcux + (xx // h), yy % v, xx % h].reshape(-1, 64)
-        _, td, ta = sos_comp[c]
-        out += bytes([0xff, 0xda, 0, 8, 1, cid, (td << 4) | ta, 0, 63, 0])
-        out += encode_scan(raster, [0] * len(raster), {0: dht[(0, td)]}, {0: dht[(1, ta)]})
-    out += b"\xff\xd9"
-    return bytes(out)
+    slots = sorted({c[3] for c in comps})
+    cb_slot = comps[1][3]
+    if dqt == "split":
+        assert len(slots) == 3, "dqt='split' needs three quantisation slots"
+    encoded = {}
+
+    def scan(cs, r):
+        """-> (DHT payload in front of the scan or b'', SOS payload, entropy-coded segment)"""
+        if (tuple(cs), r) in encoded:
+            return encoded[(tuple(cs), r)]
+        if len(cs) == 1:
+            _, h, v, _ = comps[cs[0]]
+            bw = ((W * h + hmax - 1) // hmax + 7) // 8
+            bh = ((H * v + vmax - 1) // vmax + 7) // 8
+            mc = ref.coefs[cs[0]].reshape(ref.mcus, v, h, 64)
+            yy, xx = np.mgrid[0:bh, 0:bw]
+            blocks = mc[(yy // v) * mcux + (xx // h), yy % v, xx % h].reshape(-1, 64)
+            owner, unit = [0] * len(blocks), 1
+        else:
+            ks = [comps[c][1] * comps[c][2] for c in cs]
+            blocks = np.concatenate([ref.coefs[c].reshape(ref.mcus, k, 64) for c, k in zip(cs, ks)], axis=1).reshape(-1, 64)
+            owner, unit = [q for q, k in enumerate(ks) for _ in range(k)] * ref.mcus, sum(ks)
+        if tables == "per_scan":
+            tally = [(_Tally(), _Tally()) for _ in cs]
+            encode_scan(blocks, owner, {q: t[0] for q, t in enumerate(tally)}, {q: t[1] for q, t in enumerate(tally)}, r * unit)
+            tabs = [(optimal_table(t[0].n), optimal_table(t[1].n)) for t in tally]
+            head = b"".join(bytes([(cls << 4) | q]) + bytes(t[cls][0]) + bytes(t[cls][1]) for q, t in enumerate(tabs) for cls in (0, 1))
+            selq = [(q, q) for q in range(len(cs))]
+            dcc = {q: huff_codes(*t[0]) for q, t in enumerate(tabs)}
+            acc = {q: huff_codes(*t[1]) for q, t in enumerate(tabs)}
+        else:
+            head, selq = b"", [sel[c] for c in cs]
+            dcc = {q: dht[(0, sel[c][0])] for q, c in enumerate(cs)}
+            acc = {q: dht[(1, sel[c][1])] for q, c in enumerate(cs)}
+        ent = encode_scan(blocks, owner, dcc, acc, restart_blocks=r * unit)
+        sos = bytes([len(cs)]) + b"".join(bytes([comps[c][0], (td << 4) | ta]) for c, (td, ta) in zip(cs, selq)) + bytes([0, 63, 0])
+        encoded[(tuple(cs), r)] = (head, sos, ent)
+        return encoded[(tuple(cs), r)]
+
+    out = []
+    for script in scripts:
+        plan = parse_script(script)
+        rs = [0] * len(plan) if restart is None else [restart] * len(plan) if isinstance(restart, int) else list(restart)
+        assert len(rs) == len(plan) and sorted(sum(plan, [])) == [0, 1, 2], script
+        late = comps[plan[0][0]][3]
+        f = bytearray(b"\xff\xd8")
+        for mk, q in segs:
+            if mk == 0xdd or (mk == 0xc4 and tables == "per_scan") or (mk == 0xdb and dqt in ("split", "late")):
+                continue
+            if mk == 0xc0 and dqt in ("split", "late"):
+                for s in slots:
+                    if s not in ((cb_slot, comps[2][3]) if dqt == "split" else (late,)):
+                        f += _segment(0xdb, qts[s])
+                if dqt == "split":
+                    q = q[:14] + bytes([cb_slot]) + q[15:]          # Cr's Tq
+            f += _segment(mk, q)
+        done, redone, in_force = set(), set(), 0
+        for k, cs in enumerate(plan):
+            if k and markers:
+                f += _segment(0xfe, b"scan %d of %s" % (k, script.encode())) + _segment(0xe1, b"between scans")
+            if dqt == "after":
+                for s in slots:
+                    if s not in redone and all(c in done for c in range(3) if comps[c][3] == s):
+                        f += _segment(0xdb, _ones_dqt(s))
+                        redone.add(s)
+            if dqt == "split":
+                chroma = [c for c in cs if c in (1, 2)]
+                assert len(chroma) <= 1, "dqt='split' needs Cb and Cr in different scans"
+                if chroma:
+                    own = qts[comps[chroma[0]][3]]
+                    f += _segment(0xdb, bytes([(own[0] & 0xf0) | cb_slot]) + own[1:])
+            if dqt == "late" and k == 1:
+                f += _segment(0xdb, qts[late])
+            if rs[k] != in_force:
+                f += _segment(0xdd, struct.pack(">H", rs[k]))
+                in_force = rs[k]
+            head, sos, ent = scan(cs, rs[k])
+            if head:
+                f += _segment(0xc4, head)
+            f += _segment(0xda, sos) + ent
+            done.update(cs)
+        if dqt == "tail":
+            for s in slots:
+                f += _segment(0xdb, _ones_dqt(s))
+        if markers:
+            f += _segment(0xfe, b"behind the last scan")
+        out.append(bytes(f + b"\xff\xd9"))
+    return out
+
+
+def script_twin(data, ref, script, **kw):
+    """script_twins for one script"""
+    return script_twins(data, ref, [script], **kw)[0]
 
 
 # ---- any sampling layout: h, v in {1, 2} per component (tests/test_sampling_layouts.py) --------------------------------

@@ -399,6 +399,11 @@ def planar_direct(lname, w, scale):
     at most 128 / hmax) touches at most two MCU rows, and the scans give at most kPlanarKinds = 4 block rows per MCU (the sum of
     the v factors), at most kPlanarSegs = 8 segments per tile."""
     hv = parse_name(lname)
+    return planar_fits(hv, w, scale, sum(v for _, v in hv))
+
+
+def planar_fits(hv, w, scale, kinds):
+    """planar_ok's tile rule for a picture of layout hv and width w whose scans give `kinds` block rows per MCU"""
     bpm, hmax = sum(a * b for a, b in hv), max(a for a, _ in hv)
     mcux = -(-w // (8 * hmax))
     if hv == [(2, 2), (1, 1), (1, 1)] and scale == 1:
@@ -408,7 +413,6 @@ def planar_direct(lname, w, scale):
         while t * 2 * bpm <= 192:
             t *= 2
         t = min(t, 128 // hmax)
-    kinds = sum(v for _, v in hv)
     pieces = (mcux + t - 2) // mcux + 1
     return kinds <= 4 and pieces <= 2 and pieces * kinds <= 8
 
