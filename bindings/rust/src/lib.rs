@@ -18,8 +18,18 @@ pub const MJX_DESTUFF_AUTO: u8 = 0;
 pub const MJX_DESTUFF_DEVICE: u8 = 1;
 pub const MJX_DESTUFF_HOST: u8 = 2;
 
+/// A rectangle in the coordinates of the picture a call would otherwise produce; w == h == 0: the whole picture.
 #[repr(C)]
-#[derive(Clone, Copy, Default)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct mjx_rect {
+    pub x: u32,
+    pub y: u32,
+    pub w: u32,
+    pub h: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct mjx_opts {
     pub strict_ref: u8,
     pub layout: u8,
@@ -28,6 +38,16 @@ pub struct mjx_opts {
     pub chunk_images: u32,
     /// scaled decode: 0 or 1 full size, 2 / 4 / 8 = 1/2, 1/4, 1/8 in the DCT domain (include/mjx.h)
     pub scale_denom: u8,
+    /// region-of-interest decode: null = whole pictures; borrowed for the duration of the call (include/mjx.h)
+    pub rois: *const mjx_rect,
+    /// 0 with rois == null; 1: the one rectangle applies to every input; n: rois[i] belongs to input i
+    pub n_rois: u32,
+}
+
+impl Default for mjx_opts {
+    fn default() -> Self {
+        mjx_opts { strict_ref: 0, layout: 0, keep_coefs: 0, device_destuff: 0, chunk_images: 0, scale_denom: 0, rois: std::ptr::null(), n_rois: 0 }
+    }
 }
 
 #[repr(C)]
@@ -100,6 +120,8 @@ extern "C" {
     pub fn mjx_parse(jpeg: *const u8, len: usize, opts: *const mjx_opts, out: *mut mjx_scan_desc) -> c_int;
     pub fn mjx_free_scan(desc: *mut mjx_scan_desc);
     pub fn mjx_validate(desc: *const mjx_scan_desc, opts: *const mjx_opts) -> c_int;
+    pub fn mjx_plan_tiles(desc: *const mjx_scan_desc, opts: *const mjx_opts, tiles_read: *mut u64, tiles_total: *mut u64,
+                          tile_mcus: *mut u32) -> c_int;
     pub fn mjx_decode(jpeg: *const u8, len: usize, opts: *const mjx_opts, out: *mut mjx_image) -> c_int;
     pub fn mjx_free_image(img: *mut mjx_image);
     pub fn mjx_ctx_create(device: c_int, out: *mut *mut mjx_ctx) -> c_int;
@@ -118,6 +140,8 @@ extern "C" {
     pub fn mjx_batch_status(b: *const mjx_batch, i: usize) -> c_int;
     pub fn mjx_batch_image_info(b: *const mjx_batch, i: usize, width: *mut u32, height: *mut u32,
                                 blocks_per_mcu: *mut u32, mcus: *mut u32) -> c_int;
+    pub fn mjx_batch_image_roi(b: *const mjx_batch, i: usize, x: *mut u32, y: *mut u32, full_width: *mut u32,
+                               full_height: *mut u32) -> c_int;
     pub fn mjx_batch_rgb_device(b: *const mjx_batch, i: usize, dev_ptr: *mut *mut c_void, bytes: *mut usize) -> c_int;
     pub fn mjx_batch_copy_rgb(b: *mut mjx_batch, i: usize, host_rgb: *mut u8) -> c_int;
     pub fn mjx_batch_copy_coefs(b: *mut mjx_batch, i: usize, host_coefs: *mut i16, cap_blocks: usize,

@@ -47,6 +47,10 @@ enum mjx_destuff {
     MJX_DESTUFF_HOST = 2
 };
 
+/* A rectangle in the coordinates of the picture a call would otherwise produce (STANDARD layout at the call's scale_denom:
+ * out_w x out_h = ceil(W/s) x ceil(H/s)).  No alignment is asked of x, y, w or h; w == 0 && h == 0 means the whole picture. */
+typedef struct mjx_rect { uint32_t x, y, w, h; } mjx_rect;
+
 typedef struct mjx_opts {
     uint8_t strict_ref;   /* 1: unknown / APP12 / APP14 markers are errors like the reference; 0: skip them */
     uint8_t layout;       /* MJX_LAYOUT_* */
@@ -73,6 +77,17 @@ typedef struct mjx_opts {
                              only: MJX_LAYOUT_REF_COMPAT with a scale above 1 is MJX_ERR_INVALID_ARG.  For a scaled batch
                              mjx_batch_image_info, mjx_batch_copy_rgb, mjx_batch_rgb_device and mjx_batch_bytes speak of the
                              output picture. */
+    const mjx_rect *rois; /* region-of-interest decode: NULL = whole pictures.  A picture with a rectangle is w x h x 3 bytes, R,G,B,
+                             row-major, unpadded: the pixels [y, y+h) x [x, x+w) of the picture the call would otherwise write, byte
+                             for byte.  Stage B fetches and transforms only the tiles that touch the rectangle (mjx_plan_tiles), and
+                             the picture's RGB region is the rectangle's.  A rectangle that does not lie inside out_w x out_h, or has
+                             exactly one of w and h zero, gives that picture MJX_ERR_INVALID_ARG (the others are unaffected);
+                             MJX_LAYOUT_REF_COMPAT with a rectangle is MJX_ERR_INVALID_ARG.  mjx_batch_image_info, _copy_rgb,
+                             _rgb_device, _bytes and _compare_rgb speak of the cropped picture (mjx_batch_image_roi: where it
+                             lies); mjx_batch_copy_coefs is unchanged.  The array is only borrowed for the duration of the call. */
+    uint32_t n_rois;      /* 0 with rois == NULL; 1: the one rectangle applies to every input of the call (mjx_validate,
+                             mjx_plan_tiles: rois[0]); n, the call's number of inputs: rois[i] belongs to input i.  Anything else,
+                             or rois == NULL with n_rois != 0, fails the call with MJX_ERR_INVALID_ARG. */
 } mjx_opts;
 
 /* ---- inner seam: what jpeg/mod.rs:388-415 hands to JPEGDecoder -------------------------- */
@@ -144,6 +159,14 @@ void mjx_free_scan(mjx_scan_desc *desc);
  * MJX_ERR_REF_PANIC).  The same check mjx_batch_create applies per image. */
 int mjx_validate(const mjx_scan_desc *desc, const mjx_opts *opts);
 
+/* Host-only: the stage-B tiles a decode of this picture with these options reads.  A tile is *tile_mcus consecutive MCUs in raster
+ * order; with a rectangle (opts->rois[0]) stage B fetches and transforms only the tiles that hold an MCU of the rectangle's MCU
+ * rows and columns -- *tiles_read of the picture's *tiles_total.  Multi-scan pictures that are read straight from their scans'
+ * streams skip by MCU rows only: every tile from the first to the last one that touches the rectangle's MCU rows is read.
+ * The numbers come from the planner and the tile rule of the kernels themselves.  Returns the picture's plan status. */
+int mjx_plan_tiles(const mjx_scan_desc *desc, const mjx_opts *opts, uint64_t *tiles_read, uint64_t *tiles_total,
+                   uint32_t *tile_mcus);
+
 /* JPEGImage::parse + image_data() in one call on device `0` (main.rs:31-36 usage): parse, upload, decode on the
  * GPU, copy the RGB back.  Release with mjx_free_image. */
 int mjx_decode(const uint8_t *jpeg, size_t len, const mjx_opts *opts, mjx_image *out);
@@ -178,7 +201,8 @@ int mjx_batch_create(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const m
 void mjx_batch_free(mjx_batch *b);
 
 /* Replicate the uploaded images `times`x on the device (image i*n+k is a byte copy of image k): builds the
- * large synthetic batches of BASELINE.json configs 4/5 from n unique images without re-uploading. */
+ * large synthetic batches of BASELINE.json configs 4/5 from n unique images without re-uploading.  The copies keep their
+ * source's scale and rectangle. */
 int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, mjx_batch **out);
 
 /* JPEGDecoder::decode, decoder.rs:162 -- the hot path.  Enqueues every kernel for the whole batch on the
@@ -193,6 +217,9 @@ int mjx_batch_status(const mjx_batch *b, size_t i);
 /* geometry of image i: width, height, number of blocks per MCU, MCUs decoded */
 int mjx_batch_image_info(const mjx_batch *b, size_t i, uint32_t *width, uint32_t *height, uint32_t *blocks_per_mcu,
                          uint32_t *mcus);
+/* region-of-interest decode: the origin of image i's rectangle and the size of the uncropped picture (out_w x out_h at the
+ * batch's scale); without a rectangle 0, 0 and the picture's own size */
+int mjx_batch_image_roi(const mjx_batch *b, size_t i, uint32_t *x, uint32_t *y, uint32_t *full_width, uint32_t *full_height);
 /* device pointer + byte size of image i's packed RGB (valid until mjx_batch_free) */
 int mjx_batch_rgb_device(const mjx_batch *b, size_t i, void **dev_ptr, size_t *bytes);
 /* copy image i's RGB to host memory (width*height*3 bytes) */

@@ -41,9 +41,15 @@ class MjxError(RuntimeError):
         super().__init__("mjx error %d (%s)%s" % (self.code, msg, (": " + what) if what else ""))
 
 
+class Rect(ctypes.Structure):
+    """mjx_rect: a rectangle in the coordinates of the picture a call would otherwise produce; w == h == 0: the whole picture."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("x", "y", "w", "h")]
+
+
 class Opts(ctypes.Structure):
     _fields_ = [("strict_ref", ctypes.c_uint8), ("layout", ctypes.c_uint8), ("keep_coefs", ctypes.c_uint8),
-                ("device_destuff", ctypes.c_uint8), ("chunk_images", ctypes.c_uint32), ("scale_denom", ctypes.c_uint8)]
+                ("device_destuff", ctypes.c_uint8), ("chunk_images", ctypes.c_uint32), ("scale_denom", ctypes.c_uint8),
+                ("rois", ctypes.POINTER(Rect)), ("n_rois", ctypes.c_uint32)]
 
 
 class Comp(ctypes.Structure):
@@ -81,6 +87,7 @@ SYMBOLS = {
     "mjx_parse": (_int, [ctypes.c_char_p, _sz, _P(Opts), _P(ScanDesc)]),
     "mjx_free_scan": (None, [_P(ScanDesc)]),
     "mjx_validate": (_int, [_P(ScanDesc), _P(Opts)]),
+    "mjx_plan_tiles": (_int, [_P(ScanDesc), _P(Opts), _P(ctypes.c_uint64), _P(ctypes.c_uint64), _P(ctypes.c_uint32)]),
     "mjx_decode": (_int, [ctypes.c_char_p, _sz, _P(Opts), _P(Image)]),
     "mjx_decode_batch": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(_P(ctypes.c_uint8)), _P(_int), _P(_vp)]),
     "mjx_free_image": (None, [_P(Image)]),
@@ -98,6 +105,7 @@ SYMBOLS = {
     "mjx_batch_size": (_sz, [_vp]),
     "mjx_batch_status": (_int, [_vp, _sz]),
     "mjx_batch_image_info": (_int, [_vp, _sz] + [_P(ctypes.c_uint32)] * 4),
+    "mjx_batch_image_roi": (_int, [_vp, _sz] + [_P(ctypes.c_uint32)] * 4),
     "mjx_batch_rgb_device": (_int, [_vp, _sz, _P(_vp), _P(_sz)]),
     "mjx_batch_copy_rgb": (_int, [_vp, _sz, _vp]),
     "mjx_batch_copy_coefs": (_int, [_vp, _sz, _vp, _sz, _P(_sz)]),
@@ -153,14 +161,37 @@ def _check(rc, what=""):
 DESTUFF_AUTO, DESTUFF_DEVICE, DESTUFF_HOST = 0, 1, 2
 
 
-def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0, device_destuff=False, scale=1):
+def _rects(rois):
+    """None, one (x, y, w, h) or a list of them (None in the list: the whole picture) -> a ctypes array of Rect, or None."""
+    if rois is None:
+        return None
+    if len(rois) == 4 and all(isinstance(v, (int, np.integer)) for v in rois):
+        rois = [rois]
+    arr = (Rect * max(len(rois), 1))()
+    for i, r in enumerate(rois):
+        x, y, w, h = (0, 0, 0, 0) if r is None else r
+        if min(x, y, w, h) < 0 or max(x, y, w, h) > 0xffffffff:
+            raise MjxError(ERR_INVALID_ARG, "roi=%s" % (r,))
+        arr[i] = Rect(int(x), int(y), int(w), int(h))
+    arr._n = len(rois)
+    return arr
+
+
+def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0, device_destuff=False, scale=1, rois=None):
     """device_destuff: True = on the GPU, False = on the host, None = the library's choice (mjx.h: MJX_DESTUFF_*).
-    scale: 1, 2, 4 or 8 -- the picture decoded at 1/scale in the DCT domain (mjx.h: mjx_opts.scale_denom)."""
+    scale: 1, 2, 4 or 8 -- the picture decoded at 1/scale in the DCT domain (mjx.h: mjx_opts.scale_denom).
+    rois: see _rects (mjx.h: mjx_opts.rois, n_rois); the Opts returned keeps the array alive."""
     dd = DESTUFF_AUTO if device_destuff is None else (DESTUFF_DEVICE if device_destuff else DESTUFF_HOST)
     scale = int(scale)
     if not 0 <= scale <= 255:
         raise MjxError(ERR_INVALID_ARG, "scale=%d" % scale)
-    return Opts(int(bool(strict_ref)), int(layout), int(bool(keep_coefs)), dd, int(chunk_images), scale)
+    o = Opts(int(bool(strict_ref)), int(layout), int(bool(keep_coefs)), dd, int(chunk_images), scale)
+    arr = _rects(rois)
+    if arr is not None:
+        o._rects = arr                      # (the library borrows the array for the duration of the call)
+        o.rois = ctypes.cast(arr, _P(Rect))
+        o.n_rois = arr._n
+    return o
 
 
 # ---- host parse ------------------------------------------------------------------------------------
@@ -177,10 +208,18 @@ class ParsedScan:
     def scan_bytes(self):
         return ctypes.string_at(self.desc.scan, self.desc.scan_len)
 
-    def validate(self, layout=LAYOUT_STANDARD, strict_ref=False, scale=1):
-        """Status mjx_batch_create would give this image (host only)."""
-        o = _opts(layout=layout, strict_ref=strict_ref, scale=scale)
+    def validate(self, layout=LAYOUT_STANDARD, strict_ref=False, scale=1, roi=None):
+        """Status mjx_batch_create would give this image (host only).  roi: (x, y, w, h) in the scaled picture's coordinates."""
+        o = _opts(layout=layout, strict_ref=strict_ref, scale=scale, rois=roi)
         return int(lib().mjx_validate(ctypes.byref(self.desc), ctypes.byref(o)))
+
+    def plan_tiles(self, roi=None, scale=1):
+        """mjx_plan_tiles (host only) -> dict(tiles_read, tiles_total, tile_mcus): the stage-B tiles a decode with this rectangle
+        fetches and transforms, of the picture's tiles, and the MCUs a tile holds."""
+        o = _opts(scale=scale, rois=roi)
+        rd, tot, t = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+        _check(lib().mjx_plan_tiles(ctypes.byref(self.desc), ctypes.byref(o), ctypes.byref(rd), ctypes.byref(tot), ctypes.byref(t)), "mjx_plan_tiles")
+        return dict(tiles_read=rd.value, tiles_total=tot.value, tile_mcus=t.value)
 
     def close(self):
         if self._owned:
@@ -228,9 +267,12 @@ class Batch:
     """Device-resident batch: inputs uploaded at construction, ``decode()`` only enqueues kernels."""
 
     def __init__(self, ctx, scans=None, strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0,
-                 _handle=None, scale=1):
+                 _handle=None, scale=1, rois=None):
         """scale: 1, 2, 4 or 8 -- every picture decoded at 1/scale (info(), rgb(), rgb_device() and bytes() then speak of the
-        scaled picture; tile() keeps the scale)."""
+        scaled picture; tile() keeps the scale).
+        rois: one (x, y, w, h) for every picture, or a list with one per picture (None or (0, 0, 0, 0): the whole picture), in the
+        coordinates of the scaled picture -- info(), rgb(), rgb_device(), bytes() and compare_rgb() then speak of the cropped
+        picture, roi(i) says where it lies; tile() keeps the rectangles."""
         self.ctx = ctx
         self.h = _vp()
         if _handle is not None:
@@ -242,7 +284,7 @@ class Batch:
             ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(s.desc if isinstance(s, ParsedScan) else s),
                            ctypes.sizeof(ScanDesc))
         st = (_int * max(n, 1))()
-        o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale)
+        o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois)
         _check(lib().mjx_batch_create(ctx.h, arr, n, ctypes.byref(o), ctypes.byref(self.h), st), "mjx_batch_create")
         self.create_status = list(st)[:n]
 
@@ -267,6 +309,13 @@ class Batch:
         v = [ctypes.c_uint32() for _ in range(4)]
         lib().mjx_batch_image_info(self.h, i, *[ctypes.byref(x) for x in v])
         return dict(width=v[0].value, height=v[1].value, bpm=v[2].value, mcus=v[3].value)
+
+    def roi(self, i):
+        """Where picture i lies in the uncropped picture: dict(x, y, w, h, full_width, full_height)."""
+        v = [ctypes.c_uint32() for _ in range(4)]
+        lib().mjx_batch_image_roi(self.h, i, *[ctypes.byref(x) for x in v])
+        inf = self.info(i)
+        return dict(x=v[0].value, y=v[1].value, w=inf["width"], h=inf["height"], full_width=v[2].value, full_height=v[3].value)
 
     def rgb(self, i):
         inf = self.info(i)
@@ -481,12 +530,13 @@ class JPEGImage:
         self._w, self._h, self._rgb = width, height, rgb
 
     @staticmethod
-    def parse(data, strict_ref=False, layout=LAYOUT_STANDARD, ctx=None, scale=1):
-        """scale: 1, 2, 4 or 8 -- the picture at 1/scale (width() and height() are the scaled picture's)."""
+    def parse(data, strict_ref=False, layout=LAYOUT_STANDARD, ctx=None, scale=1, roi=None):
+        """scale: 1, 2, 4 or 8 -- the picture at 1/scale (width() and height() are the scaled picture's).
+        roi: (x, y, w, h) of the scaled picture -- only that rectangle is produced (width() and height() are its)."""
         ctx = ctx or default_context()
         scan = ParsedScan(data, strict_ref=strict_ref)
         try:
-            b = Batch(ctx, [scan], strict_ref=strict_ref, layout=layout, scale=scale)
+            b = Batch(ctx, [scan], strict_ref=strict_ref, layout=layout, scale=scale, rois=roi)
             try:
                 if b.create_status[0] != OK:
                     raise MjxError(b.create_status[0])
@@ -512,8 +562,8 @@ class JPEGImage:
         return self._rgb
 
 
-def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False, scale=1):
-    """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale: see Batch.
+def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False, scale=1, rois=None):
+    """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale, rois: see Batch.
     device_destuff: the host copies the entropy-coded bytes as they are; de-stuffing, restart markers and the scan's length
     are found on the GPU."""
     n = len(datas)
@@ -522,7 +572,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     st = (_int * max(n, 1))()
     ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
     h = _vp()
-    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, device_destuff=device_destuff, scale=scale)
+    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, device_destuff=device_destuff, scale=scale, rois=rois)
     _check(lib().mjx_decode_batch(ctx.h, arr, lens, n, ctypes.byref(o), int(threads), ptrs, st, ctypes.byref(h)), "mjx_decode_batch")
     return Batch(ctx, _handle=h), list(st)[:n]
 
@@ -546,9 +596,9 @@ class Pool:
     def set_deal(self, round_robin):
         _check(lib().mjx_pool_set_deal(self.h, 1 if round_robin else 0), "mjx_pool_set_deal")
 
-    def decode_batch(self, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads_per_device=0, device_destuff=None, scale=1):
+    def decode_batch(self, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads_per_device=0, device_destuff=None, scale=1, rois=None):
         """-> PoolResult; .slot_of[i], .status[i], .rgb(i), .rc (the call's return code: a failed slot fails its own files only).
-        scale: see Batch."""
+        scale, rois: see Batch (a file's rectangle follows it to its slot)."""
         n = len(datas)
         arr = (ctypes.c_char_p * max(n, 1))(*[bytes(d) for d in datas])
         lens = (_sz * max(n, 1))(*[len(d) for d in datas])
@@ -556,7 +606,7 @@ class Pool:
         slots = (_int * max(n, 1))()
         ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
         h = _vp()
-        o = _opts(strict_ref, layout, device_destuff=device_destuff, scale=scale)
+        o = _opts(strict_ref, layout, device_destuff=device_destuff, scale=scale, rois=rois)
         rc = lib().mjx_pool_decode_batch(self.h, arr, lens, n, ctypes.byref(o), int(threads_per_device), slots, ptrs, st, ctypes.byref(h))
         if not h:
             _check(rc, "mjx_pool_decode_batch")
@@ -644,10 +694,20 @@ class PoolResult:
             pass
 
 
-def decode(data, strict_ref=False, layout=LAYOUT_STANDARD, scale=1):
-    """One-shot C entry point mjx_decode (parse + GPU decode + copy back) -> ndarray [H, W, 3] uint8.  scale: see Batch."""
+def plan_tiles(data, roi=None, scale=1):
+    """Host only: the stage-B tiles a decode of this file with this rectangle and scale reads -> see ParsedScan.plan_tiles."""
+    scan = ParsedScan(data)
+    try:
+        return scan.plan_tiles(roi=roi, scale=scale)
+    finally:
+        scan.close()
+
+
+def decode(data, strict_ref=False, layout=LAYOUT_STANDARD, scale=1, roi=None):
+    """One-shot C entry point mjx_decode (parse + GPU decode + copy back) -> ndarray [H, W, 3] uint8.  scale: see Batch.
+    roi: (x, y, w, h) of the scaled picture -- the array is that rectangle, [h, w, 3]."""
     img = Image()
-    o = _opts(strict_ref, layout, scale=scale)
+    o = _opts(strict_ref, layout, scale=scale, rois=roi)
     _check(lib().mjx_decode(bytes(data), len(data), ctypes.byref(o), ctypes.byref(img)), "mjx_decode")
     try:
         return np.ctypeslib.as_array(img.rgb, (img.height, img.width, 3)).copy()

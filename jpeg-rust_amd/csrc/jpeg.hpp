@@ -108,15 +108,19 @@ public:
         std::string message;
         bool ok() const { return code == MJX_OK; }
     };
-    // JPEGImage::parse, src/jpeg/mod.rs:202.  scale_denom (2, 4, 8; 0 = whatever opts says): scaled decode, mjx_opts.scale_denom
-    static Result parse(const std::vector<uint8_t> &vec, JPEGImage &image, const mjx_opts *opts = nullptr, unsigned scale_denom = 0)
+    // JPEGImage::parse, src/jpeg/mod.rs:202.  scale_denom (2, 4, 8; 0 = whatever opts says): scaled decode, mjx_opts.scale_denom.
+    // roi (null = whatever opts says): only that rectangle of the (scaled) picture is produced, mjx_opts.rois; width() and
+    // height() are then the rectangle's.
+    static Result parse(const std::vector<uint8_t> &vec, JPEGImage &image, const mjx_opts *opts = nullptr, unsigned scale_denom = 0,
+                        const mjx_rect *roi = nullptr)
     {
         mjx_image img{0, 0, nullptr};
         Result r;
         mjx_opts o{};
         if (opts) o = *opts;
         if (scale_denom) o.scale_denom = uint8_t(scale_denom > 255 ? 255 : scale_denom);
-        r.code = mjx_decode(vec.data(), vec.size(), (opts || scale_denom) ? &o : nullptr, &img);
+        if (roi) { o.rois = roi; o.n_rois = 1; }
+        r.code = mjx_decode(vec.data(), vec.size(), (opts || scale_denom || roi) ? &o : nullptr, &img);
         r.message = mjx_strerror(r.code);
         if (!r.ok()) return r;
         image.dimensions_ = {uint16_t(img.width), uint16_t(img.height)};

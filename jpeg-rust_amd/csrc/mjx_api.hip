@@ -122,7 +122,8 @@ namespace {
 
 struct ImageInfo {
     int status = MJX_OK;
-    uint32_t width = 0, height = 0, bpm = 0, nmcu = 0;
+    uint32_t width = 0, height = 0, bpm = 0, nmcu = 0;      // (width x height: the picture written -- scaled, cropped)
+    uint32_t roi_x = 0, roi_y = 0, full_w = 0, full_h = 0;  // where it lies in the uncropped out_w x out_h picture (mjx_batch_image_roi)
     uint64_t nblocks = 0;
     uint64_t rgb_off = 0, rgb_bytes = 0;
     uint64_t coef_off = 0;         // blocks, inside the per-block arrays of its chunk (or of the batch with keep_coefs)
@@ -152,6 +153,9 @@ struct Chunk {
     uint64_t plane_words = 0;      // REF_COMPAT scratch of the chunk
     uint32_t max_pixel_wgs = 0;
     uint32_t max_dc_wgs = 0;       // scaled decode at 1/8: workgroups of k_dc_color for the chunk's largest picture
+    uint32_t max_dc_roi_wgs = 0;   // ... and of k_dc_color_roi for its largest rectangle
+    uint32_t max_b_tiles = 0;      // tiles the workgroups of stage B walk in the chunk's largest picture: all its tiles, or those of its
+                                   // rectangle's MCU rows (DevImage::roi_ntiles) -- max_tiles without rectangles
     uint32_t min_sub_bits = 0xffffffffu;   // shortest subsequence length among its scans (chunk_fix_passes)
     uint32_t max_nsub = 0;                 // subsequences of its longest scan
     uint32_t wg = 128;                     // lanes of its k_huff_spec / k_huff_write workgroups: the largest its scans were cut for (ImagePlan::wg_lanes)
@@ -399,14 +403,21 @@ void release(mjx_batch *b)
 
 void fill_dev_image(const ImagePlan &p, DevImage &d);
 
+// (MJX_PLANAR_DIRECT=0: multi-scan pictures always go through the gather kernels)
+bool planar_direct_default()
+{
+    const char *e = std::getenv("MJX_PLANAR_DIRECT");
+    return !e || std::atoi(e) != 0;
+}
+
 // A multi-scan picture (role 2, plans[kp]; its scans are the nparts plans in front of it): can stage B read its tiles straight
 // from the scans' streams (DevImage::planar)?  Not with keep_coefs (mjx_batch_copy_coefs expands the gathered stream), not when a
 // tile touches more than two MCU rows or more segments than the kernel holds, not when an interleaved scan's MCU grid is not the
 // picture's -- those go through the gather kernels as before.
-bool planar_ok(const mjx_ctx *ctx, bool keep_coefs, const std::vector<ImagePlan> &plans, size_t kp, uint32_t *tile_mcus_out)
+bool planar_ok(bool planar_direct, bool keep_coefs, const std::vector<ImagePlan> &plans, size_t kp, uint32_t *tile_mcus_out)
 {
     const ImagePlan &pic = plans[kp];
-    if (!ctx->planar_direct || keep_coefs || pic.role != 2 || pic.status != MJX_OK || kp < pic.nparts || pic.ncomp != 3) return false;
+    if (!planar_direct || keep_coefs || pic.role != 2 || pic.status != MJX_OK || kp < pic.nparts || pic.ncomp != 3) return false;
     DevImage pd;
     fill_dev_image(pic, pd);
     const uint32_t T = pd.tile_mcus;
@@ -467,9 +478,20 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
         d.nbx = p.nbx;
         d.nby = p.nby;
     }
+    // region-of-interest decode: the rectangle, and the tiles from the one that holds its first MCU to the one that holds its last
+    // (stage B walks these and passes over those among them that hold none of its MCU columns, roi_tile_wanted)
+    d.roi_x = p.roi_x; d.roi_y = p.roi_y; d.roi_w = p.roi_w; d.roi_h = p.roi_h;
+    d.roi_mr0 = p.roi_mr0; d.roi_mr1 = p.roi_mr1; d.roi_mc0 = p.roi_mc0; d.roi_mc1 = p.roi_mc1;
+    d.roi_tile0 = 0;
+    d.roi_ntiles = (p.nmcu + t - 1) / t;
+    if (p.cropped) {
+        d.mode += kRoiMode;
+        d.roi_tile0 = (p.roi_mr0 * p.mcux + p.roi_mc0) / t;
+        d.roi_ntiles = (p.roi_mr1 * p.mcux + p.roi_mc1) / t - d.roi_tile0 + 1;
+    }
     d.role = p.role;
     d.wg_lanes = p.wg_lanes;
-    if (p.role == 1) {                 // a scan of a multi-scan file: no stage B; one tile offset per block for the gather (build_batch: or segment cuts, seg_S)
+    if (p.role == 1) {                // a scan of a multi-scan file: no stage B; one tile offset per block for the gather (build_batch: or segment cuts, seg_S)
         d.mode = 7;
         d.log2_tile = 0;
         d.tile_mcus = 1;
@@ -561,6 +583,7 @@ void plan_chunks(mjx_batch *b)
                 const uint32_t T = d.tile_mcus;
                 if (d.role != 1) {
                     c.max_tiles = std::max<uint32_t>(c.max_tiles, (d.nmcu + T - 1) / T);
+                    c.max_b_tiles = std::max<uint32_t>(c.max_b_tiles, d.roi_ntiles);
                     c.max_tile_blocks = std::max<uint32_t>(c.max_tile_blocks, T * d.bpm);
                 }
                 if (d.role == 2) { c.has_gather = true; if (!d.planar) c.has_copy = true; }
@@ -572,6 +595,7 @@ void plan_chunks(mjx_batch *b)
                 c.bpm_mask |= 1u << d.bpm;
                 if (d.nseg > 1) c.max_restart_segs = std::max(c.max_restart_segs, d.nseg);
                 if (d.mode == 5) c.max_dc_wgs = std::max<uint32_t>(c.max_dc_wgs, uint32_t((uint64_t(d.out_w) * d.out_h + 255) / 256));
+                if (d.mode == 5 + kRoiMode) c.max_dc_roi_wgs = std::max<uint32_t>(c.max_dc_roi_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
                 if (d.mode == 2) {
                     d.plane_off = c.plane_words;
                     c.plane_words += uint64_t(d.width) * d.height * d.ncomp;
@@ -878,10 +902,11 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
         prof_begin(b, MJX_K_IDCT_COLOR, sp);
         if (c.plane_words) HIPOK(hipMemsetAsync(SCR(d_planes), 0, size_t(c.plane_words) * 8, sp));
         // (dense: over ~1400 bytes of scan per stage-B tile -- more than the 2048 stream entries the kernel's default form prefetches)
-        launch_idct_color(sp, c.max_tiles, nimg, b->idct_lds + b->ctx->idct_lds_pad, imgs, SCR(d_entries), SCR(d_tile_eoff), dcb, b->d_qm, b->d_rgb, c.mode_mask, SCR(d_planes), b->d_img_flags,
+        launch_idct_color(sp, c.max_b_tiles, nimg, b->idct_lds + b->ctx->idct_lds_pad, imgs, SCR(d_entries), SCR(d_tile_eoff), dcb, b->d_qm, b->d_rgb, c.mode_mask, SCR(d_planes), b->d_img_flags,
                           c.scan_bytes > uint64_t(c.tiles) * (1400u * tile_mcus_420() / 32u), c.layout_mask);
         if (c.plane_words) launch_ref_color(sp, c.max_pixel_wgs, nimg, imgs, SCR(d_planes), b->d_rgb, b->d_img_flags);
         if (c.max_dc_wgs) launch_dc_color(sp, c.max_dc_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags);
+        if (c.max_dc_roi_wgs) launch_dc_color(sp, c.max_dc_roi_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true);
         prof_end(b, sp);
         if (sp != st) {
             HIPOK(hipEventRecord(b->ev_pixels[set], sp));
@@ -1037,6 +1062,8 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
     } owner{b};
     b->ctx = ctx;
     b->opts = opts;
+    b->opts.rois = nullptr;          // (borrowed for the call: the plans carry the rectangles)
+    b->opts.n_rois = 0;
     const size_t nu = plans.size(), n = nu * times;
     b->info.resize(n);
     b->himages.resize(n);
@@ -1115,7 +1142,8 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
         d.qm_off = uint32_t(k * 192);
         if (p.scale > 1) d.qm_off = uint32_t((nu + k) * 192);       // (the reduced transforms' multipliers: the second half of the pool)
         d.seg_off = seg_off[k];
-        inf.width = p.out_w; inf.height = p.out_h; inf.bpm = p.bpm; inf.nmcu = p.nmcu;      // (the picture written: scaled decode)
+        inf.width = p.roi_w; inf.height = p.roi_h; inf.bpm = p.bpm; inf.nmcu = p.nmcu;      // (the picture written: scaled decode, rectangle)
+        inf.roi_x = p.roi_x; inf.roi_y = p.roi_y; inf.full_w = p.out_w; inf.full_h = p.out_h;
         inf.nblocks = uint64_t(p.nmcu) * p.bpm;
         inf.tile_blocks = d.tile_blocks;
         inf.ntiles = uint32_t((inf.nblocks + d.tile_blocks - 1) / d.tile_blocks);
@@ -1149,7 +1177,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
         if (p.role == 1 && k + (p.nparts - p.part_idx) < nu) {       // a scan of a multi-scan file: segments instead of an offset per block?
             const size_t kp = k + (p.nparts - p.part_idx);
             uint32_t T = 0;
-            if (planar_ok(ctx, b->opts.keep_coefs != 0, plans, kp, &T)) {
+            if (planar_ok(ctx->planar_direct, b->opts.keep_coefs != 0, plans, kp, &T)) {
                 const ImagePlan &pic = plans[kp];
                 d.seg_T = T;
                 d.seg_mcux = pic.mcux;
@@ -1161,7 +1189,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 inf.ntiles = p.mcuy * d.seg_S;
             }
         }
-        if (p.role == 2 && planar_ok(ctx, b->opts.keep_coefs != 0, plans, k, nullptr)) {
+        if (p.role == 2 && planar_ok(ctx->planar_direct, b->opts.keep_coefs != 0, plans, k, nullptr)) {
             d.planar = 1;
             uint32_t nk = 0, first[3] = {0, 0, 0};
             for (uint32_t c = 1; c < 3; c++) first[c] = first[c - 1] + p.h[c - 1] * p.v[c - 1];
@@ -1205,14 +1233,14 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
         d.ent_cap = uint32_t(std::min<uint64_t>(inf.ent_cap, 0xffffffffu));
         inf.scan_len = p.scan_len;
         inf.rgb_off = rgb_pool;
-        inf.rgb_bytes = p.role == 1 ? 0 : uint64_t(p.out_w) * p.out_h * 3;     // (a scan of a multi-scan file has no picture)
+        inf.rgb_bytes = p.role == 1 ? 0 : uint64_t(p.roi_w) * p.roi_h * 3;     // (a scan of a multi-scan file has no picture)
         d.rgb_off = rgb_pool;
         rgb_pool += align_up(inf.rgb_bytes, 256);
         b->scan_bytes += p.scan_len;
         b->rgb_bytes += inf.rgb_bytes;
         if (p.role != 1) {
             b->coef_bytes += inf.nblocks * 128;
-            b->pixels += uint64_t(p.out_w) * p.out_h;
+            b->pixels += uint64_t(p.roi_w) * p.roi_h;
         }
     }
     for (size_t i = 0; i < n; i++)
@@ -1625,7 +1653,7 @@ extern "C" int mjx_ctx_create(int device, mjx_ctx **out)
     if (const char *e = std::getenv("MJX_HOST_INTERLEAVE")) c->host_interleave = std::atoi(e) != 0;
     if (const char *e = std::getenv("MJX_DESTUFF_DIRECT")) c->destuff_direct = std::atoi(e) != 0;
     if (const char *e = std::getenv("MJX_SINGLE_DECODE")) c->single_decode = std::atoi(e) != 0;
-    if (const char *e = std::getenv("MJX_PLANAR_DIRECT")) c->planar_direct = std::atoi(e) != 0;
+    c->planar_direct = planar_direct_default();
     if (const char *e = std::getenv("MJX_MERGE_MEMO")) c->merge_memo = std::atoi(e) != 0;
     if (const char *e = std::getenv("MJX_EMIT_CP_BITS")) c->emit_cp_bits = uint32_t(std::max(long(kCpBits), std::atol(e))) / uint32_t(kCpBits) * uint32_t(kCpBits);
     if (const char *e = std::getenv("MJX_EMIT_WARM_BITS")) c->emit_warm_bits = uint32_t(std::max(0L, std::atol(e))) / 32u * 32u;
@@ -1724,13 +1752,14 @@ extern "C" int mjx_batch_create(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t
     *out = nullptr;
     mjx_opts o{};
     if (opts) o = *opts;
+    if (!rois_fit(o, n)) return MJX_ERR_INVALID_ARG;
     const mjx_scan_desc *dd = descs;
     std::vector<ImagePlan> plans;
     std::vector<size_t> plan_of(n);                    // input i -> its picture's plan (multi-scan files add plans in front)
     plans.reserve(n);
     const auto tp0 = std::chrono::steady_clock::now();
     for (size_t i = 0; i < n; i++) {
-        plan_input(dd[i], o, plans);
+        plan_input(dd[i], opts_for_input(o, n, i), plans);      // (rois[i] goes with input i: a multi-scan file's picture plan takes it)
         plan_of[i] = plans.size() - 1;
     }
     if (std::getenv("MJX_TIMING"))
@@ -1748,9 +1777,40 @@ extern "C" int mjx_validate(const mjx_scan_desc *desc, const mjx_opts *opts)
     if (!desc) return MJX_ERR_INVALID_ARG;
     mjx_opts o{};
     if (opts) o = *opts;
+    if (!rois_fit(o, 1)) return MJX_ERR_INVALID_ARG;
     std::vector<ImagePlan> plans;                      // (a multi-scan file: every scan is checked, the picture's plan is last)
     plan_input(*desc, o, plans);
     return plans.back().status;
+    });
+}
+
+// Host-only: the tiles stage B reads for this picture -- the planner's geometry (fill_dev_image) and the kernels' own tile rule
+// (roi_tile_wanted); a multi-scan picture that is read straight from its scans' streams walks every tile of its range.
+extern "C" int mjx_plan_tiles(const mjx_scan_desc *desc, const mjx_opts *opts, uint64_t *tiles_read, uint64_t *tiles_total,
+                              uint32_t *tile_mcus_out)
+{
+    return guarded([&]() -> int {
+    if (!desc) return MJX_ERR_INVALID_ARG;
+    mjx_opts o{};
+    if (opts) o = *opts;
+    if (!rois_fit(o, 1)) return MJX_ERR_INVALID_ARG;
+    std::vector<ImagePlan> plans;
+    plan_input(*desc, o, plans);
+    const ImagePlan &p = plans.back();
+    if (p.status != MJX_OK) return p.status;
+    DevImage d;
+    fill_dev_image(p, d);
+    const uint32_t T = d.tile_mcus, ntiles = (p.nmcu + T - 1) / T;
+    uint64_t read = 0;
+    if (!p.cropped) read = ntiles;
+    else if (planar_ok(planar_direct_default(), o.keep_coefs != 0, plans, plans.size() - 1, nullptr)) read = d.roi_ntiles;
+    else
+        for (uint32_t t = d.roi_tile0; t < d.roi_tile0 + d.roi_ntiles; t++)
+            read += roi_tile_wanted(t, T, p.nmcu, p.mcux, p.roi_mr0, p.roi_mr1, p.roi_mc0, p.roi_mc1) ? 1u : 0u;
+    if (tiles_read) *tiles_read = read;
+    if (tiles_total) *tiles_total = ntiles;
+    if (tile_mcus_out) *tile_mcus_out = T;
+    return MJX_OK;
     });
 }
 
@@ -1781,6 +1841,9 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
         if (p.status != MJX_OK) continue;
         p.width = d.width; p.height = d.height; p.ncomp = d.ncomp; p.bpm = d.bpm; p.hmax = d.hmax; p.vmax = d.vmax;
         p.scale = d.scale ? d.scale : 1u; p.out_w = d.out_w; p.out_h = d.out_h;      // (the copies keep the source's scale)
+        p.cropped = d.mode >= kRoiMode;                                               // (... and its rectangle)
+        p.roi_x = d.roi_x; p.roi_y = d.roi_y; p.roi_w = d.roi_w; p.roi_h = d.roi_h;
+        p.roi_mr0 = d.roi_mr0; p.roi_mr1 = d.roi_mr1; p.roi_mc0 = d.roi_mc0; p.roi_mc1 = d.roi_mc1;
         p.mcux = d.mcux; p.mcuy = d.mcuy; p.nmcu = d.nmcu;
         for (uint32_t c = 0; c < 3; c++) { p.h[c] = d.ch[c]; p.v[c] = d.cv[c]; }
         std::memcpy(p.blk_comp, d.blk_comp, sizeof p.blk_comp);
@@ -2057,6 +2120,19 @@ extern "C" int mjx_batch_image_info(const mjx_batch *b, size_t iu, uint32_t *wid
     if (height) *height = inf.height;
     if (blocks_per_mcu) *blocks_per_mcu = inf.bpm;
     if (mcus) *mcus = inf.nmcu;
+    return inf.status;
+}
+
+extern "C" int mjx_batch_image_roi(const mjx_batch *b, size_t iu, uint32_t *x, uint32_t *y, uint32_t *full_width, uint32_t *full_height)
+{
+    if (b && !b->parts.empty()) { mjx_batch *pb; size_t pi; return route(b, iu, pb, pi) ? mjx_batch_image_roi(pb, pi, x, y, full_width, full_height) : MJX_ERR_INVALID_ARG; }
+    size_t i;
+    if (!visible_index(b, iu, i)) return MJX_ERR_INVALID_ARG;
+    const ImageInfo &inf = b->info[i];
+    if (x) *x = inf.roi_x;
+    if (y) *y = inf.roi_y;
+    if (full_width) *full_width = inf.full_w;
+    if (full_height) *full_height = inf.full_h;
     return inf.status;
 }
 
@@ -2425,6 +2501,7 @@ extern "C" int mjx_decode_batch(mjx_ctx *ctx, const uint8_t *const *jpegs, const
     std::lock_guard<std::mutex> serial(ctx->batch_mu);        // the pinned arena is shared state of the context
     mjx_opts o{};
     if (opts) o = *opts;
+    if (!rois_fit(o, n)) return MJX_ERR_INVALID_ARG;
     const bool timing = std::getenv("MJX_TIMING") != nullptr;
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
@@ -2554,7 +2631,7 @@ extern "C" int mjx_decode_batch(mjx_ctx *ctx, const uint8_t *const *jpegs, const
             prc[i] = rc;
             if (rc != MJX_OK) std::memset(&descs[i], 0, sizeof descs[i]);
             try {
-                plan_input(descs[i], o, file_plans[i]);          // geometry + decode tables, also on the worker
+                plan_input(descs[i], opts_for_input(o, n, i), file_plans[i]);          // geometry + decode tables, also on the worker (rois[i] goes with file i)
             } catch (...) {
                 file_plans[i].clear();
             }
@@ -2579,6 +2656,8 @@ extern "C" int mjx_decode_batch(mjx_ctx *ctx, const uint8_t *const *jpegs, const
     struct Owner { mjx_batch *b; ~Owner() { if (b) { (void)hipDeviceSynchronize(); release(b); } } } owner{dir};
     dir->ctx = ctx;
     dir->opts = o;
+    dir->opts.rois = nullptr;
+    dir->opts.n_rois = 0;
     dir->part_index.resize(n);
     dir->h_mismatch = pinned_get(ctx, ngroups * 8 * kMisWords * sizeof(uint32_t), &dir->h_mismatch_bytes);
     if (!dir->h_mismatch) return MJX_ERR_NOMEM;

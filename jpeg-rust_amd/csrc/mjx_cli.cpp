@@ -1,5 +1,6 @@
 // mjx_cli.cpp -- counterpart of the reference's CLI (src/main.rs:24-40):  mjx_cli <in.jpeg> <out.ppm> [--p6] [--strict]
-// [--scale N]  (N = 2, 4, 8: the picture decoded at 1/N in the DCT domain, mjx_opts.scale_denom)
+// [--scale N] [--crop X,Y,W,H]  (N = 2, 4, 8: the picture decoded at 1/N in the DCT domain, mjx_opts.scale_denom; --crop: only that
+// rectangle of the -- scaled -- picture is decoded and written, mjx_opts.rois)
 // Writes the same ASCII P3 file ("P3\n{w} {h}\n255\n" then "r g b\n" per pixel, main.rs:35-39), buffered; --p6 writes
 // binary PPM instead.  Exit code = MJX_* status.
 #include "jpeg.hpp"
@@ -12,11 +13,12 @@
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s <input.jpeg> <output.ppm> [--p6] [--strict] [--ref-compat] [--scale N]\n", argv[0]);   // main.rs:26-28 expect()
+        std::fprintf(stderr, "usage: %s <input.jpeg> <output.ppm> [--p6] [--strict] [--ref-compat] [--scale N] [--crop X,Y,W,H]\n", argv[0]);   // main.rs:26-28 expect()
         return MJX_ERR_INVALID_ARG;
     }
     bool p6 = false;
     mjx_opts opts{};
+    mjx_rect crop{0, 0, 0, 0};
     for (int i = 3; i < argc; i++) {
         if (!std::strcmp(argv[i], "--p6")) p6 = true;
         else if (!std::strcmp(argv[i], "--strict")) opts.strict_ref = 1;
@@ -25,6 +27,13 @@ int main(int argc, char **argv)
             const long v = i + 1 < argc ? std::strtol(argv[++i], nullptr, 10) : -1;
             if (v < 0 || v > 255) { std::fprintf(stderr, "--scale takes 1, 2, 4 or 8\n"); return MJX_ERR_INVALID_ARG; }
             opts.scale_denom = uint8_t(v);           // (other values: mjx_decode says MJX_ERR_INVALID_ARG)
+        } else if (!std::strcmp(argv[i], "--crop")) {
+            unsigned x, y, w, h;
+            char tail;
+            if (i + 1 >= argc || std::sscanf(argv[++i], "%u,%u,%u,%u%c", &x, &y, &w, &h, &tail) != 4) { std::fprintf(stderr, "--crop takes X,Y,W,H\n"); return MJX_ERR_INVALID_ARG; }
+            crop = mjx_rect{x, y, w, h};             // (a rectangle outside the picture: mjx_decode says MJX_ERR_INVALID_ARG)
+            opts.rois = &crop;
+            opts.n_rois = 1;
         }
     }
     std::FILE *f = std::fopen(argv[1], "rb");                                   // file_to_bytes, main.rs:16-22

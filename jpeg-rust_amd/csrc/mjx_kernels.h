@@ -31,6 +31,8 @@ struct DevImage {
     uint32_t log2_tile;     // stage-B tile = 1 << log2_tile MCUs (modes 0 and 2; mode 1: floor(log2(tile_mcus)), unused)
     uint32_t tile_mcus;     // MCUs per stage-B tile (mode 1: tile_mcus_420(), which need not be a power of two)
     uint32_t mode;          // stage-B specialisation: 0 generic, 1 = 4:2:0 (Y 2x2, Cb 1x1, Cr 1x1), 2 = REF_COMPAT placement
+                            // (3, 4, 5: scaled decode, below; 7: a scan of a multi-scan file, no stage B; + kRoiMode: the same
+                            // form for a picture with a rectangle -- the forms for whole pictures leave those alone)
     uint32_t tile_off;      // index of the image's first tile offset in the tile_eoff array
     uint32_t tile_blocks;   // blocks per stage-B tile = tile_mcus * bpm  (<= 256)
     uint8_t blk_comp[kMaxBlocksPerMcu], blk_bx[kMaxBlocksPerMcu], blk_by[kMaxBlocksPerMcu];
@@ -85,7 +87,30 @@ struct DevImage {
     // ceil(height / scale).  Modes 3 (1/2) and 4 (1/4) run k_idct_color with a 4- or 2-point inverse DCT on the low corner of
     // each block, mode 5 (1/8) runs k_dc_color on the DC values alone; qm_off then points at the reduced multipliers.
     uint32_t scale, out_w, out_h;
+    // region-of-interest decode (mjx_opts.rois; mode >= kRoiMode): the rectangle in the coordinates of the out_w x out_h picture
+    // -- the picture written is roi_w x roi_h, rgb_off its first byte --, the MCU rows and columns that touch it, and the tiles
+    // that can: roi_ntiles tiles from roi_tile0 on hold the MCU rows roi_mr0 .. roi_mr1 (roi_tile_wanted says which of them also
+    // hold one of the columns).  Without a rectangle: 0, 0, out_w, out_h and all the picture's tiles.
+    uint32_t roi_x, roi_y, roi_w, roi_h;
+    uint32_t roi_mr0, roi_mr1, roi_mc0, roi_mc1;
+    uint32_t roi_tile0, roi_ntiles;
 };
+constexpr uint32_t kRoiMode = 8;
+
+// Region-of-interest decode: does tile t -- T consecutive MCUs in raster order, so it may wrap into the next MCU row -- hold an MCU
+// of the MCU rows r0 .. r1 and the MCU columns c0 .. c1?  Arithmetic on uniform values only: stage B decides per tile without a
+// memory access, and the host counts with the same rule (mjx_plan_tiles).
+MJX_HD bool roi_tile_wanted(uint32_t t, uint32_t T, uint32_t nmcu, uint32_t mcux, uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1)
+{
+    const uint32_t m_lo = t * T, m_end = m_lo + T < nmcu ? m_lo + T : nmcu, m_hi = m_end - 1u;
+    const uint32_t ra = m_lo / mcux, ca = m_lo - ra * mcux, rb = m_hi / mcux, cb = m_hi - rb * mcux;
+    const uint32_t rs = ra > r0 ? ra : r0, re = rb < r1 ? rb : r1;
+    if (rs > re) return false;
+    if (re > rs + 1u) return true;                                 // (a row strictly between the tile's first and last: all its columns)
+    const bool first = (rs == ra ? ca : 0u) <= c1 && (rs == rb ? cb : mcux - 1u) >= c0;
+    const bool last = (re == ra ? ca : 0u) <= c1 && (re == rb ? cb : mcux - 1u) >= c0;
+    return first || last;
+}
 
 // Where the segments of a scan begin (DevImage::seg_S): the first cut at or after scan MCU q0, as the scan MCU it lies at and its
 // slot in the scan's table.  A cut lies at the start of every scan-MCU row and wherever a tile of the picture (seg_T picture MCUs
@@ -377,6 +402,8 @@ void launch_dc_scan(hipStream_t st, uint32_t max_segs, uint32_t nimg, const DevI
                     uint32_t *segflag = nullptr, uint32_t gen = 0,
                     uint32_t *fail = nullptr /* device word, set when the one-pass kernel gave up waiting */, uint32_t spin_limit = 1u << 20,
                     bool fault = false /* test knob: a workgroup never publishes */);
+// (max_tiles: the chunk's largest count of tiles a picture's workgroups walk -- DevImage::roi_ntiles; mode_mask bits kRoiMode + m:
+// pictures with a rectangle, which take the forms k_idct_color<kRoiMode + m, ...>)
 void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t lds, const DevImage *images,
                        const uint32_t *entries, const uint32_t *tile_eoff, const int32_t *dcbuf, const float *qmult,
                        uint8_t *rgb, uint32_t mode_mask, unsigned long long *planes, const uint32_t *img_flags,
@@ -392,7 +419,7 @@ void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, con
 // scaled decode at 1/8 (mode 5): one lane per output pixel from the blocks' DC values; max_pixel_wgs = the chunk's largest
 // ceil(out_w * out_h / 256)
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
-                     const float *qmult, uint8_t *rgb, const uint32_t *img_flags);
+                     const float *qmult, uint8_t *rgb, const uint32_t *img_flags, bool roi = false /* the form for pictures with a rectangle */);
 #endif
 
 }   // namespace mjx

@@ -2590,6 +2590,24 @@ __device__ __forceinline__ void store4(uint8_t *dst, const Rgb4 &v, bool aligned
     }
 }
 
+// Region-of-interest decode (mjx_opts.rois): the picture written is the rectangle [y, y + h) x [x, x + w) of the picture the
+// pixel phase computes.  A strip of npix pixels at (px, py) of that picture goes to ((py - y) w + (px - x)) 3 of the result, cut
+// at both ends; nothing is written outside the rectangle.  A strip cut at its left end leaves byte by byte (one strip per row).
+struct Roi { uint32_t x, y, w, h; };
+__device__ __forceinline__ void store4_roi(uint8_t *out, const Roi &r, uint32_t px, uint32_t py, const Rgb4 &v, uint32_t npix)
+{
+    if (py < r.y || py - r.y >= r.h) return;
+    const uint32_t lo = max(px, r.x), hi = min(px + npix, r.x + r.w);
+    if (lo >= hi) return;
+    uint8_t *dst = out + (size_t(py - r.y) * r.w + (lo - r.x)) * 3;
+    if (lo == px) {
+        store4(dst, v, (uintptr_t(dst) & 3u) == 0, hi - lo);
+    } else {
+        const uint32_t w[3] = {v.a, v.b, v.c};
+        for (uint32_t k = (lo - px) * 3; k < (hi - px) * 3; k++) dst[k - (lo - px) * 3] = uint8_t(w[k >> 2] >> ((k & 3) * 8));
+    }
+}
+
 // ---- stage B pipeline pieces ---------------------------------------------------------------------
 // A workgroup walks kTilesPerWg consecutive tiles of one image.  While it transforms tile t it already holds the loads
 // of tile t+1 in flight (stream offsets, up to kPrefetch entries per lane, the lane's DC), so the HBM round trips of a
@@ -3039,10 +3057,14 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // (round 5: the exchange form used to need a tile inside one MCU row and fully inside the picture; a tile that wraps into the next
 // row -- one in 7.5 at 4K, one in 3.75 at 1080p -- or touches the picture's edge took plain reads, bounds everywhere, and cost
 // the tile behind it a zero-fill pass)
-template <bool XCHG, bool BOUNDS>
+//   ROI     (with plain reads and BOUNDS) the picture written is the rectangle `roi` of this one: lanes whose strips lie outside its
+//           columns leave, rows outside it are passed over, strips are cut at its edges (store4_roi).  The colour arithmetic is the
+//           whole picture's -- the same packed additions, no fused form --, so the bytes are the whole picture's.
+template <bool XCHG, bool BOUNDS, bool ROI = false>
 __device__ __forceinline__ void pixels_420(uint32_t width, uint32_t height, uint32_t mcux, const float *tile, uint32_t m0,
-                                           uint32_t nm, uint8_t *out_img, bool aligned)
+                                           uint32_t nm, uint8_t *out_img, bool aligned, const Roi &roi = Roi{})
 {
+    static_assert(!ROI || (!XCHG && BOUNDS), "a cropped tile's pixel phase does not read the whole tile: no exchange form");
     constexpr bool INTERIOR = XCHG && !BOUNDS;
     const uint32_t tid = threadIdx.x;
     const uint32_t q = tid % (kTile420 * 4), t = q >> 2, sx = q & 3;
@@ -3052,6 +3074,7 @@ __device__ __forceinline__ void pixels_420(uint32_t width, uint32_t height, uint
     const uint32_t px = mx * 16 + sx * 4;
     if (!XCHG && px >= width) return;
     const uint32_t npix = INTERIOR ? 4u : (px < width ? min(4u, width - px) : 0u);
+    if (ROI && (px + 4u <= roi.x || px >= roi.x + roi.w)) return;
     const float *ybase = tile + (t * 6 + (sx >> 1)) * kPixStride + (sx & 1) * 4;
     const float *cbase = tile + (t * 6 + 4) * kPixStride + sx * 2;
     uint8_t *col = out_img + (size_t(my) * 16 * width + px) * 3;
@@ -3118,6 +3141,7 @@ __device__ __forceinline__ void pixels_420(uint32_t width, uint32_t height, uint
         const uint32_t rp = tid / (kTile420 * 4) + 2 * j;
         const uint32_t py = my * 16 + rp * 2;
         if (!INTERIOR && (py >= height || npix == 0)) break;
+        if (ROI && (py + 2u <= roi.y || py >= roi.y + roi.h)) continue;
         const ChromaTerms c0 = chroma_terms(cb[j].x, cr[j].x), c1 = chroma_terms(cb[j].y, cr[j].y);
         Rgb p[4];
         // two pixels per addition (v_pk_add_f32, the chroma term broadcast to both halves by op_sel): 12 packed instead of 24 plain
@@ -3134,11 +3158,13 @@ __device__ __forceinline__ void pixels_420(uint32_t width, uint32_t height, uint
         };
         rows(ya[j], p);
         uint8_t *dst = col + size_t(rp) * 2 * width * 3;
-        if (INTERIOR) store_rgb4(dst, pack4(p));
+        if (ROI) store4_roi(out_img, roi, px, py, pack4(p), npix);
+        else if (INTERIOR) store_rgb4(dst, pack4(p));
         else store4(dst, pack4(p), aligned, npix);
         if (INTERIOR || py + 1 < height) {
             rows(yb[j], p);
-            if (INTERIOR) store_rgb4(dst + size_t(width) * 3, pack4(p));
+            if (ROI) store4_roi(out_img, roi, px, py + 1, pack4(p), npix);
+            else if (INTERIOR) store_rgb4(dst + size_t(width) * 3, pack4(p));
             else store4(dst + size_t(width) * 3, pack4(p), aligned, npix);
         }
     }
@@ -3146,10 +3172,12 @@ __device__ __forceinline__ void pixels_420(uint32_t width, uint32_t height, uint
 
 // Phase 3 for any sampling layout: 4-pixel strips; lane -> (MCU t, strip sx) is fixed, rows advance by 256/R per step.
 // INTERIOR: every MCU of the tile lies in one MCU row and fully inside the picture, rows are 4-byte aligned -- no bounds, plain 12-byte stores
-template <bool INTERIOR, bool COLOUR>
+// ROI: the picture written is the rectangle `roi` of this one (as pixels_420)
+template <bool INTERIOR, bool COLOUR, bool ROI = false>
 __device__ __forceinline__ void pixels_generic_t(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm,
-                                                 uint8_t *out_img, bool aligned)
+                                                 uint8_t *out_img, bool aligned, const Roi &roi = Roi{})
 {
+    static_assert(!ROI || !INTERIOR, "strips of a cropped picture are cut at the rectangle's edges");
     const uint32_t tid = threadIdx.x, bpm = g.bpm;
     const uint32_t lstrips = g.hmax == 2 ? 2u : 1u;          // log2 of the 4-pixel strips per MCU row (2*hmax)
     const uint32_t R = (1u << g.log2_tile) << lstrips;       // strips per pixel row of the tile (power of two <= 256)
@@ -3162,10 +3190,12 @@ __device__ __forceinline__ void pixels_generic_t(const GenShape &g, const float 
     const uint32_t px = mx * 8 * g.hmax + sx * 4;
     if (!INTERIOR && px >= g.width) return;
     const uint32_t npix = INTERIOR ? 4u : min(4u, g.width - px);
+    if (ROI && (px + 4u <= roi.x || px >= roi.x + roi.w)) return;
     uint8_t *dst = out_img + (size_t(my * rows + (tid >> lR)) * g.width + px) * 3;
     const size_t dstep = size_t(rstep) * g.width * 3;
     for (uint32_t r = tid >> lR; r < rows; r += rstep, dst += dstep) {
         if (!INTERIOR && my * rows + r >= g.height) break;
+        if (ROI && (my * rows + r < roi.y || my * rows + r >= roi.y + roi.h)) continue;
         float yv[4], cbv[4], crv[4];
         load4(tile, g, t * bpm, 0, sx * 4, r, yv);
         Rgb p[4];
@@ -3178,9 +3208,16 @@ __device__ __forceinline__ void pixels_generic_t(const GenShape &g, const float 
 #pragma unroll
             for (int k = 0; k < 4; k++) p[k].r = p[k].g = p[k].b = yv[k];                          // decoder.rs:318-325 (+128 is in the samples)
         }
-        if (INTERIOR) store_rgb4(dst, pack4(p));
+        if (ROI) store4_roi(out_img, roi, px, my * rows + r, pack4(p), npix);
+        else if (INTERIOR) store_rgb4(dst, pack4(p));
         else store4(dst, pack4(p), aligned, npix);
     }
+}
+__device__ __forceinline__ void pixels_generic_roi(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm,
+                                                   uint8_t *out_img, bool aligned, const Roi &roi)
+{
+    if (g.ncomp == 3) pixels_generic_t<false, true, true>(g, tile, m0, nm, out_img, aligned, roi);
+    else pixels_generic_t<false, false, true>(g, tile, m0, nm, out_img, aligned, roi);
 }
 __device__ __forceinline__ void pixels_generic(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm,
                                                uint8_t *out_img, bool aligned)
@@ -3345,8 +3382,10 @@ __device__ __forceinline__ void idct_scaled_inplace(float *blk)
 // Phase 3 of the scaled forms: an MCU is an (N hmax) x (N vmax) patch of the output; a lane takes a strip of SW = min(4, N hmax)
 // pixels of one patch row (box replication of the chroma samples at the output resolution, as pixels_generic does at scale 1).
 // Output rows need not be 4-byte aligned; pixels outside out_w x out_h (g.width, g.height) are not written.
-template <uint32_t N>
-__device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm, uint8_t *out_img, bool aligned)
+// ROI: the picture written is the rectangle `roi` of this one (as pixels_420)
+template <uint32_t N, bool ROI = false>
+__device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm, uint8_t *out_img, bool aligned,
+                                              const Roi &roi = Roi{})
 {
     const uint32_t PW = N * g.hmax, PH = N * g.vmax, SW = PW < 4u ? PW : 4u;
     const uint32_t lspr = PW / SW == 2u ? 1u : 0u, lph = 31u - __builtin_clz(PH);
@@ -3357,6 +3396,7 @@ __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *ti
         const uint32_t m = m0 + t, my = m / g.mcux, mx = m - my * g.mcux;
         const uint32_t X = mx * PW + sx * SW, Y = my * PH + r;
         if (X >= g.width || Y >= g.height) continue;
+        if (ROI && (Y < roi.y || Y >= roi.y + roi.h || X + SW <= roi.x || X >= roi.x + roi.w)) continue;
         const uint32_t npix = min(SW, g.width - X);
         float s[3][4];
 #pragma unroll
@@ -3375,7 +3415,8 @@ __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *ti
             if (g.ncomp == 3) p[k] = ycc_to_rgb(s[0][k], chroma_terms(s[1][k], s[2][k]));
             else p[k].r = p[k].g = p[k].b = s[0][k];
         }
-        store4(out_img + (size_t(Y) * g.width + X) * 3, pack4(p), al, npix);
+        if (ROI) store4_roi(out_img, roi, X, Y, pack4(p), npix);
+        else store4(out_img + (size_t(Y) * g.width + X) * 3, pack4(p), al, npix);
     }
 }
 
@@ -3390,7 +3431,13 @@ __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *ti
 //   phase 3  chroma replication + YCbCr->RGB + packed stores
 //   SRC  where the entries come from: 0 the picture's linear stream, 1 its quad-interleaved stream, 2 the linear streams of the scans of
 //        a multi-scan picture (planar, above)
-template <int MODE, int PF, int SRC>
+//   ROI  region-of-interest decode (MODE_ = MODE + kRoiMode, the mode of a picture with a rectangle): the workgroups walk only the tiles that
+//        can touch the rectangle's MCU rows (DevImage::roi_tile0, roi_ntiles) and, among them, only those that hold one of its MCU
+//        columns (roi_tile_wanted: uniform arithmetic, no memory access) -- a tile that is passed over issues no stream fetch, no DC
+//        load, no scatter, no transform and no barrier, and the prefetch chain runs from one wanted tile to the next.  The planar
+//        form (its segment lists are prepared two tiles ahead in a ring of three) walks every tile of the row band.  Phase 3 writes
+//        the rectangle's pixels only (store4_roi); the 4:2:0 form takes plain reads there, so `clean` stays false.
+template <int MODE_, int PF, int SRC>
 __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__ images,
                                                      const uint32_t *__restrict__ entries,
                                                      const uint32_t *__restrict__ tile_eoff,
@@ -3398,6 +3445,9 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                                                      uint8_t *__restrict__ rgb, unsigned long long *__restrict__ planes,
                                                      const uint32_t *__restrict__ img_flags, uint32_t tiles_per_wg)
 {
+    constexpr bool ROI = MODE_ >= int(kRoiMode);
+    constexpr int MODE = MODE_ - (ROI ? int(kRoiMode) : 0);
+    static_assert(!ROI || MODE != 2, "REF_COMPAT has no rectangles");
     // (its own symbol: dynamic LDS arrays of one name share their alignment, and the entropy kernels ask for 2 KiB)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_px[];
     __shared__ float s_qm[3 * 64];
@@ -3412,7 +3462,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     __shared__ PlanarKindL s_kind[PLANAR ? kPlanarKinds : 1];
     __shared__ PlanarTile s_ptile[PLANAR ? 3 : 1];
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || im.mode != uint32_t(MODE) || (im.planar ? 2 : im.ent_rows != 0 ? 1 : 0) != SRC || img_flags[im.status_idx]) return;
+    if (!im.valid || im.mode != uint32_t(MODE_) || (im.planar ? 2 : im.ent_rows != 0 ? 1 : 0) != SRC || img_flags[im.status_idx]) return;
     // everything the tile loop needs from the descriptor, read once (uniform -> scalar registers)
     constexpr bool M420 = MODE == 1;
     constexpr uint32_t LANES = M420 ? kLanes420 : 256u;
@@ -3422,9 +3472,25 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     const uint32_t total_blocks = im.himg.total_blocks;
     const uint32_t tile_blocks = T * bpm;
     const uint32_t ntiles = (nmcu + T - 1) / T;
-    const uint32_t tile0 = blockIdx.x * tiles_per_wg;             // (tiles_per_wg <= kTilesPerWg: few for small launches, see launch_idct_color)
-    if (tile0 >= ntiles) return;
-    const uint32_t tile1 = min(ntiles, tile0 + tiles_per_wg);
+    // (ROI: the tiles of the rectangle's MCU rows only; which of them hold one of its MCU columns -- the planar form takes them all)
+    const uint32_t tile_end = ROI ? min(ntiles, im.roi_tile0 + im.roi_ntiles) : ntiles;
+    const uint32_t tile0 = (ROI ? im.roi_tile0 : 0u) + blockIdx.x * tiles_per_wg;             // (tiles_per_wg <= kTilesPerWg: few for small launches, see launch_idct_color)
+    if (tile0 >= tile_end) return;
+    const uint32_t tile1 = min(tile_end, tile0 + tiles_per_wg);
+    Roi roi{};
+    uint32_t roi_r0 = 0, roi_r1 = 0, roi_c0 = 0, roi_c1 = 0;
+    if constexpr (ROI) {
+        roi = Roi{im.roi_x, im.roi_y, im.roi_w, im.roi_h};
+        roi_r0 = im.roi_mr0; roi_r1 = im.roi_mr1; roi_c0 = im.roi_mc0; roi_c1 = im.roi_mc1;
+    }
+    constexpr bool SKIP = ROI && SRC != 2;
+    auto wanted_from = [&](uint32_t t) {          // the first tile at or behind t that the rectangle wants (uniform)
+        if constexpr (SKIP)
+            while (t < tile1 && !roi_tile_wanted(t, T, nmcu, mcux, roi_r0, roi_r1, roi_c0, roi_c1)) t++;
+        return t;
+    };
+    const uint32_t tile_first = wanted_from(tile0);
+    if (SKIP && tile_first >= tile1) return;
     const uint32_t tid = threadIdx.x;
     const uint32_t *__restrict__ src = entries + im.ent_off + im.ent_hdr;
     const uint32_t *__restrict__ eoff = tile_eoff + im.tile_off;
@@ -3487,9 +3553,9 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     static_assert(!QUAD || PF % 8 == 0, "whole groups per lane and round");
     static_assert(!PLANAR || PF == 8, "the planar form prefetches eight rounds");
     typename std::conditional<QUAD, QuadFetch<QR>, typename std::conditional<PLANAR, PlanarFetch<PF>, TileFetch<PF>>::type>::type cur;
-    if constexpr (QUAD) tile_fetch_quad<LANES>(src, qv, 0, dcs, tile0, tile_blocks, total_blocks, cur);
+    if constexpr (QUAD) tile_fetch_quad<LANES>(src, qv, tile_first - tile0, dcs, tile_first, tile_blocks, total_blocks, cur);
     else if constexpr (PLANAR) tile_fetch_planar<LANES, PF>(psrc, s_ptile[tile0 % 3u], dcbuf, pdc, tile0 * T, pr0, pa0, nmcu, mcux, cur);
-    else tile_fetch<LANES, PF>(src, s_eoff, dcs, tile0, tile_blocks, total_blocks, cur);
+    else tile_fetch<LANES, PF>(src, s_eoff + (tile_first - tile0), dcs, tile_first, tile_blocks, total_blocks, cur);
     for (uint32_t i = tid; i < 192; i += LANES) s_qm[i] = qmult[im.qm_off + i];
     if (tid < 64) {
         constexpr uint8_t ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -3524,7 +3590,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
 #define MJX_SB(k)
 #endif
     bool clean = false;          // the tile's sample rows are zero already (the pixel phase of an interior 4:2:0 tile clears what it reads)
-    for (uint32_t tile = tile0; tile < tile1; tile++) {
+    for (uint32_t tile = tile_first; tile < tile1; tile++) {
+        const uint32_t tile_next = wanted_from(tile + 1);       // the next tile the rectangle wants (without one: tile + 1)
         const uint32_t m0 = tile * T;
         const uint32_t nm = min(T, nmcu - m0), nblk = nm * bpm;
         if constexpr (SCALED) {   // phase 0 (scaled: the corner's N x N floats of every block)
@@ -3560,9 +3627,9 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
         // queued behind the scatter's LDS stores, and the loads have the scatter phase on top of the inverse DCT to land in (13 more
         // registers: cur and nxt are live together; still three waves per SIMD).
         auto nxt = cur;
-        if (!PLANAR && tile + 1 < tile1) {
-            if constexpr (QUAD) tile_fetch_quad<LANES>(src, qv, tile + 1 - tile0, dcs, tile + 1, tile_blocks, total_blocks, nxt);
-            else if constexpr (!PLANAR) tile_fetch<LANES, PF>(src, s_eoff + (tile + 1 - tile0), dcs, tile + 1, tile_blocks, total_blocks, nxt);
+        if (!PLANAR && tile_next < tile1) {
+            if constexpr (QUAD) tile_fetch_quad<LANES>(src, qv, tile_next - tile0, dcs, tile_next, tile_blocks, total_blocks, nxt);
+            else if constexpr (!PLANAR) tile_fetch<LANES, PF>(src, s_eoff + (tile_next - tile0), dcs, tile_next, tile_blocks, total_blocks, nxt);
         }
         {   // phase 1
             const uint32_t first_lo = (tile * tile_blocks) & 0xffu;
@@ -3656,21 +3723,28 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             const uint32_t mx0 = m0 % mcux, my1 = (m0 + T - 1) / mcux;
             const bool whole = nm == T;
             const bool interior = whole && aligned && (my1 + 1) * 16 <= height && (mcux * 16 <= width || mx0 + T < mcux);
-            if (interior) pixels_420<true, false>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
-            else if (whole) pixels_420<true, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
-            else pixels_420<false, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
-            clean = whole;
+            if constexpr (ROI) {
+                // (plain reads: a cropped tile's pixel phase does not read -- so does not clear -- the whole tile; `clean` stays false)
+                pixels_420<false, true, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned, roi);
+            } else {
+                if (interior) pixels_420<true, false>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
+                else if (whole) pixels_420<true, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
+                else pixels_420<false, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
+                clean = whole;
+            }
         } else if (MODE == 2) {
             place_ref(im, tile_f, tile * tile_blocks, nblk, planes);
         } else if constexpr (SCALED) {
-            pixels_scaled<scaled_n<MODE>()>(gshape, tile_f, m0, nm, out_img, aligned);
+            pixels_scaled<scaled_n<MODE>(), ROI>(gshape, tile_f, m0, nm, out_img, aligned, roi);
         } else {
-            pixels_generic(gshape, tile_f, m0, nm, out_img, aligned);
+            if constexpr (ROI) pixels_generic_roi(gshape, tile_f, m0, nm, out_img, aligned, roi);
+            else pixels_generic(gshape, tile_f, m0, nm, out_img, aligned);
         }
         MJX_SB(6);
         __syncthreads();
         MJX_SB(7);
         cur = nxt;
+        if constexpr (SKIP) tile = tile_next - 1u;            // (the loop's own step makes it tile_next)
     }
 #ifdef MJX_STAMP_B
     sp.end();
@@ -3682,16 +3756,19 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
 // coefficient stream, only the blocks' DC values.  One lane per output pixel: at 1/8 an MCU is an hmax x vmax patch of the output,
 // and pixel (X, Y) takes block (X h / hmax, Y v / vmax) of each component's plane (box replication, as pixels_scaled).
 // Multi-scan pictures read without the gather keep their DC values in their scans' regions (planar_dc_slot, as stage B finds them).
-extern "C" __global__ __launch_bounds__(256) void k_dc_color(const DevImage *__restrict__ images, const int32_t *__restrict__ dcbuf,
-                                                              const float *__restrict__ qmult, uint8_t *__restrict__ rgb,
-                                                              const uint32_t *__restrict__ img_flags)
+// ROI (k_dc_color_roi, mode 5 + kRoiMode): one lane per pixel of the rectangle.
+template <bool ROI>
+__device__ __forceinline__ void dc_color_body(const DevImage *__restrict__ images, const int32_t *__restrict__ dcbuf,
+                                              const float *__restrict__ qmult, uint8_t *__restrict__ rgb,
+                                              const uint32_t *__restrict__ img_flags)
 {
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || im.mode != 5u || img_flags[im.status_idx]) return;
-    const uint32_t ow = im.out_w, oh = im.out_h;
+    if (!im.valid || im.mode != 5u + (ROI ? kRoiMode : 0u) || img_flags[im.status_idx]) return;
+    const uint32_t ow = ROI ? im.roi_w : im.out_w, oh = ROI ? im.roi_h : im.out_h;
     const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
     if (i >= uint64_t(ow) * oh) return;
-    const uint32_t Y = uint32_t(i / ow), X = uint32_t(i - uint64_t(Y) * ow);
+    uint32_t Y = uint32_t(i / ow), X = uint32_t(i - uint64_t(Y) * ow);
+    if constexpr (ROI) { X += im.roi_x; Y += im.roi_y; }
     const uint32_t hmax = im.hmax, vmax = im.vmax;
     const uint32_t mx = X / hmax, my = Y / vmax, lx = X - mx * hmax, ly = Y - my * vmax;
     float s[3] = {0.f, 0.f, 0.f};
@@ -3716,6 +3793,18 @@ extern "C" __global__ __launch_bounds__(256) void k_dc_color(const DevImage *__r
     const uint32_t word = pack_u8(p.b, 2, pack_u8(p.g, 1, pack_u8(p.r, 0, 0)));
     uint8_t *dst = rgb + im.rgb_off + i * 3;
     dst[0] = uint8_t(word); dst[1] = uint8_t(word >> 8); dst[2] = uint8_t(word >> 16);
+}
+extern "C" __global__ __launch_bounds__(256) void k_dc_color(const DevImage *__restrict__ images, const int32_t *__restrict__ dcbuf,
+                                                              const float *__restrict__ qmult, uint8_t *__restrict__ rgb,
+                                                              const uint32_t *__restrict__ img_flags)
+{
+    dc_color_body<false>(images, dcbuf, qmult, rgb, img_flags);
+}
+extern "C" __global__ __launch_bounds__(256) void k_dc_color_roi(const DevImage *__restrict__ images, const int32_t *__restrict__ dcbuf,
+                                                                  const float *__restrict__ qmult, uint8_t *__restrict__ rgb,
+                                                                  const uint32_t *__restrict__ img_flags)
+{
+    dc_color_body<true>(images, dcbuf, qmult, rgb, img_flags);
 }
 
 // ---- verification helper: byte-wise comparison of decoded pictures on the device ------------------------------
@@ -3800,7 +3889,10 @@ int configure_kernels(size_t huff_lds, size_t idct_lds)
                              reinterpret_cast<const void *>(k_idct_color<0, 8, 2>), reinterpret_cast<const void *>(k_idct_color<1, 8, 2>),
                              reinterpret_cast<const void *>(k_idct_color<3, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<3, 8, 1>),
                              reinterpret_cast<const void *>(k_idct_color<3, 8, 2>), reinterpret_cast<const void *>(k_idct_color<4, kPrefetch, 0>),
-                             reinterpret_cast<const void *>(k_idct_color<4, 8, 1>), reinterpret_cast<const void *>(k_idct_color<4, 8, 2>)};
+                             reinterpret_cast<const void *>(k_idct_color<4, 8, 1>), reinterpret_cast<const void *>(k_idct_color<4, 8, 2>),
+#define MJX_ROI_FORMS(M) reinterpret_cast<const void *>(k_idct_color<kRoiMode + M, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<kRoiMode + M, 8, 1>), reinterpret_cast<const void *>(k_idct_color<kRoiMode + M, 8, 2>)
+                             MJX_ROI_FORMS(0), MJX_ROI_FORMS(1), MJX_ROI_FORMS(3), MJX_ROI_FORMS(4)};
+#undef MJX_ROI_FORMS
         for (const void *f : fns)
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(idct_lds));
     }
@@ -3990,6 +4082,18 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
         if (layout_mask & 4u) MJX_IDCT(4, 8, 2);
     }
 #undef MJX_IDCT
+    // region-of-interest decode: pictures with a rectangle (mode + kRoiMode) take the forms that skip tiles and crop
+#define MJX_IDCT_ROI(M)                                                                                                                   \
+    if (mode_mask & (1u << (kRoiMode + M))) {                                                                                             \
+        if (layout_mask & 1u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M, kPrefetch, 0>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw); \
+        if (layout_mask & 2u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M, 8, 1>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw);         \
+        if (layout_mask & 4u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M, 8, 2>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw);         \
+    }
+    MJX_IDCT_ROI(0)
+    MJX_IDCT_ROI(1)
+    MJX_IDCT_ROI(3)
+    MJX_IDCT_ROI(4)
+#undef MJX_IDCT_ROI
 }
 
 void launch_planar_gather(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint32_t *entries,
@@ -4019,10 +4123,11 @@ void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, con
 }
 
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
-                     const float *qmult, uint8_t *rgb, const uint32_t *img_flags)
+                     const float *qmult, uint8_t *rgb, const uint32_t *img_flags, bool roi)
 {
     if (max_pixel_wgs == 0 || nimg == 0) return;
-    hipLaunchKernelGGL(k_dc_color, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
+    if (roi) hipLaunchKernelGGL(k_dc_color_roi, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
+    else hipLaunchKernelGGL(k_dc_color, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
 }
 
 }   // namespace mjx

@@ -235,6 +235,21 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
             }
     p.mcux = (p.width + 8 * p.hmax - 1) / (8 * p.hmax);
     p.mcuy = (p.height + 8 * p.vmax - 1) / (8 * p.vmax);
+    // region-of-interest decode: the rectangle must lie inside the picture the call would otherwise write
+    p.roi_w = p.out_w;
+    p.roi_h = p.out_h;
+    if (!scan_part && opts.rois && opts.n_rois && (opts.rois[0].w || opts.rois[0].h)) {
+        const mjx_rect &r = opts.rois[0];
+        if (p.layout == MJX_LAYOUT_REF_COMPAT) return fail(MJX_ERR_INVALID_ARG);            // (as with a scale)
+        if (!r.w || !r.h || r.x >= p.out_w || r.y >= p.out_h || r.w > p.out_w - r.x || r.h > p.out_h - r.y) return fail(MJX_ERR_INVALID_ARG);
+        p.cropped = true;
+        p.roi_x = r.x; p.roi_y = r.y; p.roi_w = r.w; p.roi_h = r.h;
+    }
+    {
+        const uint32_t pw = 8 / scale * p.hmax, ph = 8 / scale * p.vmax;      // an MCU's patch of the output picture
+        p.roi_mc0 = p.roi_x / pw; p.roi_mc1 = (p.roi_x + p.roi_w - 1) / pw;
+        p.roi_mr0 = p.roi_y / ph; p.roi_mr1 = (p.roi_y + p.roi_h - 1) / ph;
+    }
     if (p.layout == MJX_LAYOUT_REF_COMPAT) {
         const uint64_t nb = uint64_t((p.width + 7) / 8) * ((p.height + 7) / 8);    // decoder.rs:164-166
         const uint64_t f = uint64_t(p.hmax) * p.vmax;
@@ -414,6 +429,21 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
             p.qmult_scaled[c][k] = float(double(d.qt[p.tq[c]][k]) * cu * cv / 4.0);
         }
     return p.status;
+}
+
+bool rois_fit(const mjx_opts &opts, size_t n)
+{
+    if (!opts.rois) return opts.n_rois == 0;
+    return opts.n_rois <= 1 || opts.n_rois == n;
+}
+
+mjx_opts opts_for_input(const mjx_opts &opts, size_t n, size_t i)
+{
+    mjx_opts o = opts;
+    if (!o.rois || o.n_rois == 0) { o.rois = nullptr; o.n_rois = 0; return o; }
+    if (o.n_rois == n && n > 1) o.rois += i;
+    o.n_rois = 1;
+    return o;
 }
 
 void plan_input(const mjx_scan_desc &d, const mjx_opts &opts, std::vector<ImagePlan> &out)

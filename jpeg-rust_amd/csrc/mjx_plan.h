@@ -33,6 +33,12 @@ struct ImagePlan {
     // multipliers of the reduced transforms (zig-zag order: q[k] * C(u) C(v) / 4 inside the low N x N corner, 0 outside)
     uint32_t scale = 1, out_w = 0, out_h = 0;
     float qmult_scaled[3][64];
+    // region-of-interest decode (mjx_opts.rois): the rectangle in the coordinates of the out_w x out_h picture -- the whole of it
+    // without one -- and the MCU rows and columns that touch it.  The picture written is roi_w x roi_h.  A multi-scan file's
+    // rectangle belongs to its role-2 plan, not to its scans.
+    bool cropped = false;
+    uint32_t roi_x = 0, roi_y = 0, roi_w = 0, roi_h = 0;
+    uint32_t roi_mr0 = 0, roi_mr1 = 0, roi_mc0 = 0, roi_mc1 = 0;
     const uint8_t *scan = nullptr;
     size_t scan_len = 0;
     // The scan still holds FF00 pairs (and RSTn markers): it is de-stuffed on the device at upload (k_destuff_*), scan_len is
@@ -68,7 +74,7 @@ bool ref_get_indices(long x, long y, long max_x, long x_factor, long y_factor, l
                      long *ox, long *oy);
 
 // Validates `d` and fills `plan`.  Returns plan.status.  `scan_part`: d is one scan of a multi-scan file (two interleaved
-// components are then allowed).
+// components are then allowed; opts.rois is not looked at).  Otherwise the picture's rectangle is opts.rois[0] (n_rois <= 1).
 int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &plan, bool scan_part = false);
 
 // Re-cuts a planned picture's scan into subsequences of about `base_bits` bits (at most kSubseqBits; plan_image uses
@@ -78,6 +84,11 @@ void replan_subsequences(ImagePlan &plan, uint32_t base_bits, bool allow_long = 
 // The plans of one input: `plan_image` for an ordinary file; for a multi-scan file one role-1 plan per scan (in file
 // order) followed by the role-2 plan of the picture.  The last plan appended is the picture's.
 void plan_input(const mjx_scan_desc &d, const mjx_opts &opts, std::vector<ImagePlan> &out);
+
+// The options input i of a call of n inputs is planned with: opts with its own rectangle as rois[0] (n_rois 0 or 1).
+// false: opts.rois / opts.n_rois do not fit a call of n inputs (MJX_ERR_INVALID_ARG for the call).
+bool rois_fit(const mjx_opts &opts, size_t n);
+mjx_opts opts_for_input(const mjx_opts &opts, size_t n, size_t i);
 
 // mjx_parse.cpp: mjx_parse with caller-lent storage for the de-stuffed scan (see there)
 int parse_into(const uint8_t *jpeg, size_t len, const mjx_opts *opts, mjx_scan_desc *out, uint8_t *storage, size_t cap);

@@ -193,6 +193,8 @@ struct PoolCall {
     std::vector<std::vector<size_t>> sizes;
     std::vector<std::vector<int>> st;
     std::vector<std::vector<uint8_t *>> rgb;
+    std::vector<std::vector<mjx_rect>> rois;          // per slot: the rectangles of its files, in the slot's order (opts.n_rois == n)
+    std::vector<mjx_opts> opts;                       // per slot: the call's options with the slot's rectangles
     mjx_pool_result res;
 };
 }   // namespace
@@ -203,6 +205,9 @@ extern "C" int mjx_pool_decode_batch(mjx_pool *pool, const uint8_t *const *jpegs
 {
     if (!pool || !out || ((!jpegs || !lens) && n)) return MJX_ERR_INVALID_ARG;
     *out = nullptr;
+    // rectangles: none, one for every file, or one per file (they follow their files to the slots)
+    const bool per_file_rois = opts && opts->rois && opts->n_rois == n && n > 1;
+    if (opts && (opts->rois ? (opts->n_rois > 1 && opts->n_rois != n) : opts->n_rois != 0)) return MJX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> serial(pool->call_mu);
     const size_t N = pool->workers.size();
     PoolCall *call = nullptr;
@@ -225,6 +230,8 @@ extern "C" int mjx_pool_decode_batch(mjx_pool *pool, const uint8_t *const *jpegs
         r.index_in_slot.resize(n);
         call->ptrs.resize(N);
         call->sizes.resize(N);
+        call->rois.resize(N);
+        call->opts.assign(N, opts ? *opts : mjx_opts{});
         // Dealing.  Pictures are independent, so any assignment is correct; what matters is that the slots
         // finish together.  By compressed bytes (default): the files are taken largest first (a stable order: equal files keep
         // their list order) and each goes to the slot that has been dealt the fewest bytes so far, the lowest slot on a tie
@@ -251,12 +258,14 @@ extern "C" int mjx_pool_decode_batch(mjx_pool *pool, const uint8_t *const *jpegs
             r.index_in_slot[i] = uint32_t(call->ptrs[s].size());
             call->ptrs[s].push_back(jpegs[i]);
             call->sizes[s].push_back(lens[i]);
+            if (per_file_rois) call->rois[s].push_back(opts->rois[i]);
         }
         call->st.resize(N);
         call->rgb.resize(N);
         for (size_t s = 0; s < N; s++) {
             call->st[s].assign(call->ptrs[s].size(), MJX_OK);
             call->rgb[s].assign(call->ptrs[s].size(), nullptr);
+            if (per_file_rois) { call->opts[s].rois = call->rois[s].data(); call->opts[s].n_rois = uint32_t(call->rois[s].size()); }
         }
         // hand out the jobs, one per slot that has files.  (Assigning the job can allocate -- its captures are larger than
         // std::function's inline buffer -- and so can throw: a slot counts as posted, and its `done` is cleared, only once its
@@ -269,10 +278,10 @@ extern "C" int mjx_pool_decode_batch(mjx_pool *pool, const uint8_t *const *jpegs
             r.slot_threads[s] = threads;
             r.slot_node[s] = w->numa_node;
             std::lock_guard<std::mutex> lk(w->mu);
-            w->job = [call, s, w, opts, threads, fault_slot] {
+            w->job = [call, s, w, threads, fault_slot] {
                 if (int(s) == fault_slot) return;            // this slot's device has "failed": MJX_ERR_DEVICE stands
                 const auto t0 = std::chrono::steady_clock::now();
-                call->res.slot_rc[s] = mjx_decode_batch(w->ctx, call->ptrs[s].data(), call->sizes[s].data(), call->ptrs[s].size(), opts,
+                call->res.slot_rc[s] = mjx_decode_batch(w->ctx, call->ptrs[s].data(), call->sizes[s].data(), call->ptrs[s].size(), &call->opts[s],
                                                         threads, call->rgb[s].data(), call->st[s].data(), &call->res.batches[s]);
                 call->res.slot_ms[s] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             };
