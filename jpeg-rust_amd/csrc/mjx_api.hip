@@ -130,6 +130,7 @@ struct ImageInfo {
     uint64_t ent_off = 0, ent_cap = 0;   // region of the compact coefficient stream (entries)
     uint32_t ent_rows = 0, ent_hdr = 0;  // > 0: quad-interleaved (DevImage::ent_rows, ent_hdr)
     bool emit = false;             // single decode: the picture's first decode emits (DevImage::emit)
+    bool emit_fits = true;         // ImagePlan::emit_fits, kept for mjx_batch_tile: its plans are rebuilt from the device images, which hold no tables
     uint32_t emit_head = 0;
     uint32_t tile_off = 0, ntiles = 0, tile_blocks = 0;
     uint64_t scan_len = 0;
@@ -1156,7 +1157,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
         if (p.restart_mcus) inf.ent_cap = (uint64_t(p.scan_len) * 4 + 64 + group_pad) / stream_group_entries() * stream_group_entries();
         // A picture of one scan gets the quad-interleaved stream: one column of fixed capacity per subsequence (mjx_kernels.h,
         // stream_phys); tile offsets are 32-bit virtual indices into the columns.
-        const bool will_emit = ctx->single_decode && p.role == 0 && !ctx->linear_stream && p.nseg <= 1 && p.restart_mcus == 0 && p.himg.sub_bits >= ctx->emit_min_sub_bits;
+        const bool will_emit = ctx->single_decode && p.role == 0 && !ctx->linear_stream && p.nseg <= 1 && p.restart_mcus == 0 && p.himg.sub_bits >= ctx->emit_min_sub_bits && p.emit_fits;
         if (p.role == 0 && !ctx->linear_stream) {
             const uint32_t rows = stream_rows_for(p.himg.sub_bits, will_emit);
             const uint64_t cap = stream_quad_entries(layout_nsub(p), rows);
@@ -1219,6 +1220,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
             inf.planar = true;
         }
         inf.emit = d.emit != 0;
+        inf.emit_fits = p.emit_fits;
         inf.emit_head = d.emit_head;
         inf.ent_rows = d.ent_rows;
         inf.ent_hdr = d.ent_hdr;
@@ -1872,6 +1874,7 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
         p.nsub_layout = src->himages[k].scan_cols;        // (the region the source's pool was laid out for)
         p.scan = nullptr;
         p.scan_len = src->info[k].scan_len;
+        p.emit_fits = src->info[k].emit_fits;             // (a picture too dense for the emitting pass stays off it in every copy)
     }
     return build_batch(ctx, plans, src->opts, src, times, out, nullptr);
     });

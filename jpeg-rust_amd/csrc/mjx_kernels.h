@@ -147,7 +147,8 @@ constexpr uint32_t kStreamQuad = MJX_STREAM_QUAD;      // columns interleaved pe
 // Single decode (round 5, k_huff_emit): a column also holds one word per block -- {DC difference, column index where the block's
 // entries begin} -- filled from its top downwards (block word i at column index cap - 4 - 4 * (i >> 2) + (i & 3): 16-byte groups).
 // A block takes at least two bits of scan and every entry two more, so entries and block words together are at most
-// sub_bits / 2 + 2 words and never meet.  kEmitHeadGroups rows of head room on top of that: the first decode of a subsequence starts
+// sub_bits / 2 + 2 words and never meet -- for tables that allow no denser block: ImagePlan::emit_fits keeps the others off this
+// path.  kEmitHeadGroups rows of head room on top of that: the first decode of a subsequence starts
 // its entries at index kEmitHeadGroups * 8 (its block words at kEmitHeadWords), so that a prefix that is decoded again
 // from the true entry state can be written RIGHT-ALIGNED against the part of the first decode that stays valid, whatever the
 // difference between the two prefixes' counts (photographic content: <= 24 entries, <= 33 blocks; flat content, whose blocks take

@@ -354,6 +354,17 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
         p.lut_plain_n = uint32_t(p.lut.size());
         p.lut.insert(p.lut.end(), second.begin(), second.end());
     }
+    // (see ImagePlan::emit_fits: a 1-bit DC code and a 2-bit entry -- a 1-bit code for an AC symbol of size 1 --, per component)
+    p.emit_fits = true;
+    for (uint32_t c = 0; c < p.ncomp; c++) {
+        const mjx_hufftab &dc = d.dc[d.comp[c].td], &ac = d.ac[d.comp[c].ta];
+        uint32_t dc_min = 0, entry_min = 0xffffu, v = 0;
+        for (uint32_t l = 1; l <= 16 && !dc_min; l++) if (dc.bits[l - 1]) dc_min = l;
+        for (uint32_t l = 1; l <= 16; l++)
+            for (uint32_t k = 0; k < ac.bits[l - 1]; k++, v++)
+                if (ac.vals[v] & 15u) entry_min = std::min(entry_min, l + (ac.vals[v] & 15u));
+        if (dc_min == 1u && entry_min == 2u) p.emit_fits = false;
+    }
     std::memset(&p.himg, 0, sizeof p.himg);
     for (uint32_t b = 0; b < p.bpm; b++) {
         const mjx_comp &k = d.comp[p.blk_comp[b]];

@@ -28,6 +28,14 @@ struct ImagePlan {
     HuffImage himg{};
     std::vector<LutEntry> lut;                     // all decode tables of the image, concatenated: the plain set (what the write pass
     uint32_t lut_plain_n = 0;                      // uses), then from lut_plain_n on the set with pair parts (the counting passes)
+    // Single decode (k_huff_emit): a column holds a subsequence's entries AND a word per block, sized for sub_bits / 2 + 2 words --
+    // every entry takes two bits at least and every block two more (a DC code and an end-of-block).  A block can end without an
+    // end-of-block: after 63 coded coefficients, or -- in a stream that is corrupt, or decoded from a wrong state, where runs are
+    // clamped -- after four symbols of run 15.  With a 1-bit DC code and 2-bit entries (a 1-bit code for an AC symbol of size 1)
+    // that is 64 words in 127 bits, or 5 words in 9 bits, and the entries would run into the block words; with any longer DC code
+    // or entry a block of j entries takes 2 j + 2 bits at least.  false: the tables are of that kind; the picture takes the
+    // two-pass kernels, in this batch and in every batch tiled from it.
+    bool emit_fits = true;
     float qmult[3][64];                            // per component, zig-zag order: q[k] * idct prescale
     // scaled decode (mjx_opts.scale_denom): 1, 2, 4 or 8, the output size ceil(width / scale) x ceil(height / scale), and the
     // multipliers of the reduced transforms (zig-zag order: q[k] * C(u) C(v) / 4 inside the low N x N corner, 0 outside)

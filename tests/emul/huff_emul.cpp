@@ -459,7 +459,10 @@ extern "C" int emul_single_decode_cp(const uint8_t *jpeg, size_t len, int layout
         EmitSink sink{region, s, rows, H, Hb, 0u, H, cap, 0xffffffffu, &overflow};
         HostCps hc{g_cps.data() + size_t(s) * kMaxCp * 2};
         const SubseqState x = decode_subseq<true, 1>(bits, plan.lut.data(), imgw, e, end_of(s), 0, sink, hc, s * L, e);
-        while (sink.eoff & 7u) region[stream_phys(s, sink.eoff++, rows)] = 0u;     // null entries up to the group boundary
+        while (sink.eoff & 7u) {                                                   // null entries up to the group boundary
+            if (sink.eoff >= sink.lowest_bword) { overflow = 1; break; }            // (they would land on block words: ImagePlan::emit_fits keeps such pictures off this path)
+            region[stream_phys(s, sink.eoff++, rows)] = 0u;
+        }
         g_entry[s] = make_state(e.p, e.z, e.c);
         g_exit[s] = x;
         d0n[s] = x.n; d0m[s] = x.m;
@@ -499,7 +502,7 @@ extern "C" int emul_single_decode_cp(const uint8_t *jpeg, size_t len, int layout
         }
         rounds++;
         if (redone == 0) break;
-        if (rounds > 64) { bad = 11; break; }
+        if (rounds > long(nsub) + 1) { bad = 11; break; }          // (a round puts at least one more subsequence right: the device keeps repairing, mjx_batch_wait)
     }
     // ---- k_huff_scan: blocks completed before every subsequence
     std::vector<uint32_t> B(nsub + 1, 0);
@@ -649,4 +652,31 @@ extern "C" int emul_plan_parts(const uint8_t *jpeg, size_t len, int *out /* [cap
     }
     mjx_free_scan(&d);
     return n;
+}
+
+// ---- decode tables as the host builds them (tests/test_huffman_tables.py walks them over every 16-bit window) ------------------------
+// build_decode_table on one DHT table (vals: 256 bytes) -> entries written, or the negative status
+extern "C" int emul_build_table(const uint8_t *bits, const uint8_t *vals, int is_dc, int pair, uint32_t *out, int cap)
+{
+    return build_decode_table(bits, vals, is_dc != 0, out, cap, pair != 0);
+}
+// plan_image on a file: out = {entries of the plain table set, entries of the set with pair parts, blocks per MCU, BlockTab::tabs per
+// block of the MCU [12], ImagePlan::emit_fits}; returns the plan's status
+extern "C" int emul_table_set(const uint8_t *jpeg, size_t len, uint32_t *out /* [16] */)
+{
+    mjx_opts opts{};
+    mjx_scan_desc d;
+    int rc = mjx_parse(jpeg, len, &opts, &d);
+    if (rc) return rc;
+    ImagePlan plan;
+    rc = plan_image(d, opts, plan);
+    if (rc == 0) {
+        out[0] = plan.lut_plain_n;
+        out[1] = uint32_t(plan.lut.size()) - plan.lut_plain_n;
+        out[2] = plan.bpm;
+        for (uint32_t b = 0; b < uint32_t(kMaxBlocksPerMcu); b++) out[3 + b] = b < plan.bpm ? plan.himg.btab[b].tabs : 0u;
+        out[15] = plan.emit_fits ? 1u : 0u;
+    }
+    mjx_free_scan(&d);
+    return rc;
 }

@@ -325,7 +325,8 @@ def script_twins(data, ref, scripts, tables="source", dqt=None, restart=None, ma
     blocks per MCU (A.2.3), as in `data`.  A scan that several scripts share is encoded once.
 
     tables: "source" (the source's DHT segments in front of the frame; every scan selects the source's slots) or "per_scan"
-    (no DHT up front; right before each SOS a DHT built from that scan's symbol counts (K.2), slot q for its q-th component).
+    (no DHT up front; right before each SOS a DHT built from that scan's symbol counts (K.2), slot q for its q-th component),
+    or {frame index of a component: ((bits, vals) DC, (bits, vals) AC)}: as "per_scan" with these tables (huffman_shapes).
     dqt: where quantisation tables are defined.  None: as in the source.  "after": behind each scan, every slot whose components
     have all been scanned is redefined as a table of ones.  "split": Cr takes Cb's slot number in the frame header, and that slot
     is defined right before each scan that carries Cb or Cr, with that component's own table (the source needs three slots,
@@ -381,10 +382,13 @@ def script_twins(data, ref, scripts, tables="source", dqt=None, restart=None, ma
             ks = [comps[c][1] * comps[c][2] for c in cs]
             blocks = np.concatenate([ref.coefs[c].reshape(ref.mcus, k, 64) for c, k in zip(cs, ks)], axis=1).reshape(-1, 64)
             owner, unit = [q for q, k in enumerate(ks) for _ in range(k)] * ref.mcus, sum(ks)
-        if tables == "per_scan":
-            tally = [(_Tally(), _Tally()) for _ in cs]
-            encode_scan(blocks, owner, {q: t[0] for q, t in enumerate(tally)}, {q: t[1] for q, t in enumerate(tally)}, r * unit)
-            tabs = [(optimal_table(t[0].n), optimal_table(t[1].n)) for t in tally]
+        if tables == "per_scan" or isinstance(tables, dict):
+            if isinstance(tables, dict):
+                tabs = [tables[c] for c in cs]
+            else:
+                tally = [(_Tally(), _Tally()) for _ in cs]
+                encode_scan(blocks, owner, {q: t[0] for q, t in enumerate(tally)}, {q: t[1] for q, t in enumerate(tally)}, r * unit)
+                tabs = [(optimal_table(t[0].n), optimal_table(t[1].n)) for t in tally]
             head = b"".join(bytes([(cls << 4) | q]) + bytes(t[cls][0]) + bytes(t[cls][1]) for q, t in enumerate(tabs) for cls in (0, 1))
             selq = [(q, q) for q in range(len(cs))]
             dcc = {q: huff_codes(*t[0]) for q, t in enumerate(tabs)}
@@ -406,7 +410,7 @@ def script_twins(data, ref, scripts, tables="source", dqt=None, restart=None, ma
         late = comps[plan[0][0]][3]
         f = bytearray(b"\xff\xd8")
         for mk, q in segs:
-            if mk == 0xdd or (mk == 0xc4 and tables == "per_scan") or (mk == 0xdb and dqt in ("split", "late")):
+            if mk == 0xdd or (mk == 0xc4 and tables != "source") or (mk == 0xdb and dqt in ("split", "late")):
                 continue
             if mk == 0xc0 and dqt in ("split", "late"):
                 for s in slots:
@@ -544,6 +548,280 @@ def layout_jpeg(width, height, hv, quality=75, seed=0, tables="split", restart=N
     comp_of_block = [c for c, k in enumerate(comp_rows) for _ in range(k)] * (mcux * mcuy)
     dc = {c: huff_codes(*dhts[(0, slot[c])]) for c in range(len(comps_hv))}
     ac = {c: huff_codes(*dhts[(1, slot[c])]) for c in range(len(comps_hv))}
-    ent = encode_scan(order, comp_of_block, dc, ac, restart_blocks=(restart or 0) * bpm)
+    ent = encode_scan_np(order, comp_of_block, dc, ac, restart_blocks=(restart or 0) * bpm)
     comps = [(c + 1, h, v, slot[c], slot[c], slot[c]) for c, (h, v) in enumerate(comps_hv)]
     return write_jpeg(width, height, comps, qts, dhts, ent, restart_interval=restart or 0), per_comp
+
+
+# ---- Huffman tables of every shape, and files re-coded with them (tests/test_huffman_tables.py) --------------------------------
+DC_SYMBOLS = list(range(12))                                                      # baseline difference sizes (T.81 Table F.1)
+AC_SYMBOLS = [0x00, 0xf0] + [(r << 4) | s for r in range(16) for s in range(1, 11)]   # the 162 symbols of Table F.2 ("the sane ones")
+N_RANDOM_SHAPES = 24
+
+
+def kraft(lengths):
+    """sum of 2^(16 - l): a prefix code exists iff <= 65536; the all-ones code of the longest length stays free iff < 65536"""
+    return sum(1 << (16 - l) for l in lengths)
+
+
+def table_of_lengths(ranked, lengths):
+    """(bits, vals): the k-th symbol of `ranked` gets the k-th shortest of `lengths` (canonical codes, T.81 C.2)"""
+    lengths = sorted(lengths)
+    assert len(ranked) == len(lengths) and 1 <= lengths[0] and lengths[-1] <= 16 and kraft(lengths) < 65536, lengths
+    bits = [0] * 16
+    for l in lengths:
+        bits[l - 1] += 1
+    return bits, [int(s) for s in ranked]
+
+
+def _random_lengths(rng, n, style, slack):
+    """n code lengths from a tree grown by splitting leaves: n + 1 leaves of depth <= 16, one of them the reserved code point
+    (left out: the code is complete but for it).  style: which leaf is split -- "deep" the deepest, "wide" the shallowest, "any" a
+    random one.  slack > 0: afterwards that many codes are made longer, which leaves code points no code reaches."""
+    leaves = [1, 1]
+    while len(leaves) < n + 1:
+        open_ = [k for k, d in enumerate(leaves) if d < 16]
+        if style == "deep" and rng.random() < 0.8:
+            k = max(open_, key=lambda j: leaves[j])
+        elif style == "wide" and rng.random() < 0.8:
+            k = min(open_, key=lambda j: leaves[j])
+        else:
+            k = open_[int(rng.integers(len(open_)))]
+        leaves[k] += 1
+        leaves.append(leaves[k])
+    leaves.remove(max(leaves))                                      # the reserved code point: one of the longest
+    for _ in range(slack):
+        k = int(rng.integers(n))
+        leaves[k] = int(rng.integers(leaves[k], 17))
+    return leaves
+
+
+def huffman_shapes(symbols, freq=None, seed=0):
+    """{name: (bits, vals)}: Huffman tables of every shape over `symbols` (at most 255 of them; DC size categories or AC run/size
+    symbols).  freq: {symbol: count}, what "frequent" means (ties and missing symbols: symbol order).  Every table is a prefix
+    code of at most 16 bits (T.81 C.2) in which the all-ones code is free, as Annex K.2 leaves it; deterministic in its
+    arguments.
+      ladder        lengths 1..7, every other symbol 16 bits; frequent symbols short
+      anti          the same lengths, frequent symbols on the 16-bit codes
+      flat          one length, the shortest that holds all symbols
+      edge9 edge10 edge9_10   every code 9 bits / 10 bits / half and half: at and just past a 9-bit primary table
+      sub1 .. sub7  a few short codes, then codes of 10 and of 9 + k bits: the longest code under some 9-bit prefix is 9 + k bits
+                    and shorter ones share its second-level table
+      all256        AC: all 256 run/size symbols, DC: 16 symbols, lengths 2 .. 16 (`symbols` first, by frequency)
+      k2            T.81 K.2 (optimal_table) on freq, or on equal counts
+      random0 .. random23   lengths of trees grown by random splits (_random_lengths): a third of them complete but for the reserved
+                    code point, the others with many code points unused; symbols ranked by frequency, against it or at random"""
+    symbols = [int(s) for s in symbols]
+    n = len(symbols)
+    assert 2 <= n <= 255 and len(set(symbols)) == n
+    f = dict(freq or {})
+    ranked = sorted(symbols, key=lambda s: (-f.get(s, 0), s))
+    out = {}
+    lad = list(range(1, 8))[:n - 1] + [16] * max(0, n - 7)
+    lad = lad if len(lad) == n else list(range(1, n + 1))
+    out["ladder"] = table_of_lengths(ranked, lad)
+    out["anti"] = table_of_lengths(ranked[::-1], lad)
+    out["flat"] = table_of_lengths(ranked, [n.bit_length()] * n)
+    out["edge9"] = table_of_lengths(ranked, [9] * n)
+    out["edge10"] = table_of_lengths(ranked, [10] * n)
+    out["edge9_10"] = table_of_lengths(ranked, [9] * (n // 2) + [10] * (n - n // 2))
+    nhead = min(9, n // 2)
+    for k in range(1, 8):
+        head = ([2, 3, 4, 5, 6, 7, 8, 9, 9])[:nhead]
+        rest = n - nhead
+        n10 = rest // 3 if k > 1 else 0
+        out["sub%d" % k] = table_of_lengths(ranked, head + [10] * n10 + [9 + k] * (rest - n10))
+    is_dc = max(symbols) <= 15 and n <= 16
+    every = ranked + [s for s in range(16 if is_dc else 256) if s not in symbols]
+    prof = [2, 3, 4, 5, 6, 7, 8] + [9] * 20 + [10] * 30 + [12] * 60 + [14] * 60 + [16] * 79
+    if is_dc:
+        prof = [2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 16]
+    out["all256"] = table_of_lengths(every, prof)
+    counts = {s: f.get(s, 0) for s in symbols if f.get(s, 0) > 0}
+    out["k2"] = optimal_table(counts if len(counts) >= 2 else {s: 1 for s in symbols})
+    if set(out["k2"][1]) != set(symbols):                           # (a symbol the picture does not use gets a count of one)
+        out["k2"] = optimal_table({s: f.get(s, 0) + 1 for s in symbols})
+    for r in range(N_RANDOM_SHAPES):
+        rng = np.random.default_rng([int(seed), r, n])
+        style = ("deep", "wide", "any")[r % 3]
+        slack = 0 if r % 3 == r // 3 % 3 else int(rng.integers(1, n))
+        lengths = _random_lengths(rng, n, style, slack)
+        order = (ranked, ranked[::-1], [ranked[int(k)] for k in rng.permutation(n)])[(r // 3) % 3]
+        out["random%d" % r] = table_of_lengths(order, lengths)
+    return out
+
+
+SHAPES = (["ladder", "anti", "flat", "edge9", "edge10", "edge9_10"] + ["sub%d" % k for k in range(1, 8)] + ["all256", "k2"]
+          + ["random%d" % r for r in range(N_RANDOM_SHAPES)])
+
+
+def has_1bit_code(table):
+    return table[0][0] != 0
+
+
+def head_segments(data):
+    """-> ([(marker, payload)] in front of the first SOS, that SOS's payload)"""
+    segs, i = [], 2
+    while True:
+        m = data[i + 1]
+        ln = struct.unpack(">H", data[i + 2:i + 4])[0]
+        p = bytes(data[i + 4:i + 2 + ln])
+        if m == 0xda:
+            return segs, p
+        segs.append((m, p))
+        i += 2 + ln
+
+
+def scan_blocks(ref):
+    """the blocks of an interleaved scan in coding order, and the component each belongs to, from an oracle decode (STANDARD layout;
+    a greyscale frame: one block per MCU)"""
+    ks = [len(c) // ref.mcus for c in ref.coefs]
+    blocks = np.concatenate([c.reshape(ref.mcus, k, 64) for c, k in zip(ref.coefs, ks)], axis=1).reshape(-1, 64)
+    return blocks, [q for q, k in enumerate(ks) for _ in range(k)] * ref.mcus, sum(ks)
+
+
+def symbol_counts(ref, restart=None):
+    """[({DC symbol: n}, {AC symbol: n})] per component: what coding the picture's interleaved scan asks of each table"""
+    blocks, owner, bpm = scan_blocks(ref)
+    tally = [(_Tally(), _Tally()) for _ in ref.coefs]
+    encode_scan_np(blocks, owner, {q: t[0] for q, t in enumerate(tally)}, {q: t[1] for q, t in enumerate(tally)}, (restart or 0) * bpm)
+    return [(t[0].n, t[1].n) for t in tally]
+
+
+def recode_huffman(data, ref, tables, slots=(0, 1, 3), restart=None):
+    """The interleaved baseline file `data` (any layout layout_jpeg writes, or greyscale) with its entropy-coded segment coded
+    again: component c with the table pair tables[c] = ((bits, vals) DC, (bits, vals) AC) on slot slots[c] of both classes.
+    ref: the oracle's decode of `data` (STANDARD layout).  restart=n: DRI n and an RSTn marker every n MCUs (the source's own
+    restart interval is dropped).  Everything else -- frame, quantisation tables, other segments -- is the source's."""
+    segs, sos = head_segments(data)
+    ncomp = sos[0]
+    assert ncomp == len(ref.coefs) and len(tables) >= ncomp and len(slots) >= ncomp
+    blocks, owner, bpm = scan_blocks(ref)
+    dcc = {c: huff_codes(*tables[c][0]) for c in range(ncomp)}
+    acc = {c: huff_codes(*tables[c][1]) for c in range(ncomp)}
+    ent = encode_scan_np(blocks, owner, dcc, acc, restart_blocks=(restart or 0) * bpm)
+    f = bytearray(b"\xff\xd8")
+    for mk, q in segs:
+        if mk not in (0xc4, 0xdd):
+            f += _segment(mk, q)
+    written = {}
+    for c in range(ncomp):
+        for cls in (0, 1):
+            t = (list(tables[c][cls][0]), list(tables[c][cls][1]))
+            assert written.setdefault((cls, slots[c]), t) == t, "two tables on one slot"
+    for (cls, s), (bits, vals) in sorted(written.items()):
+        f += _segment(0xc4, bytes([(cls << 4) | s]) + bytes(bits) + bytes(vals))
+    if restart:
+        f += _segment(0xdd, struct.pack(">H", restart))
+    f += _segment(0xda, bytes([ncomp]) + b"".join(bytes([sos[1 + 2 * c], (slots[c] << 4) | slots[c]]) for c in range(ncomp))
+                  + bytes([0, 63, 0]))
+    return bytes(f + ent + b"\xff\xd9")
+
+
+def _code_arrays(codes):
+    """{symbol: (code, length)} -> (code[256], length[256]); length 0: the table has no such symbol"""
+    code, ln = np.zeros(256, np.int64), np.zeros(256, np.int64)
+    if isinstance(codes, _Tally):
+        return code, ln + 1                                     # (counting, not coding: see encode_scan_np)
+    for s, (c, l) in codes.items():
+        code[s], ln[s] = c, l
+    return code, ln
+
+
+def encode_scan_np(blocks, comp_of_block, dc_codes, ac_codes, restart_blocks=0):
+    """encode_scan in numpy (a 1080p picture in a second instead of a minute); the same bytes, which tests/test_huffman_tables.py
+    checks.  Every symbol becomes one token (code and value bits, at most 27 bits); the tokens are sorted into coding order and
+    added into 32-bit words; stuffing and the RSTn markers go in at byte level."""
+    blocks = np.asarray(blocks, np.int64)
+    n = blocks.shape[0]
+    owner = np.asarray(comp_of_block, np.int64)
+    ncomp = int(owner.max()) + 1
+    dcc = [_code_arrays(dc_codes[c]) for c in range(ncomp)]
+    acc = [_code_arrays(ac_codes[c]) for c in range(ncomp)]
+    interval = np.arange(n) // restart_blocks if restart_blocks else np.zeros(n, np.int64)
+
+    def sized(v):                                              # magnitude() on an array
+        a = np.abs(v)
+        s = np.where(a > 0, np.floor(np.log2(np.maximum(a, 1))).astype(np.int64) + 1, 0)
+        return s, np.where(v >= 0, v, v + (1 << s) - 1)
+    keys, vals, lens = [], [], []
+    diff = np.zeros(n, np.int64)
+    for c in range(ncomp):
+        idx = np.nonzero(owner == c)[0]
+        dc = blocks[idx, 0]
+        prev = np.concatenate([[0], dc[:-1]])
+        prev[np.concatenate([[True], interval[idx][1:] != interval[idx][:-1]])] = 0
+        diff[idx] = dc - prev
+    s, b = sized(diff)
+    code = np.array([dcc[c][0] for c in range(ncomp)])[owner, s]
+    ln = np.array([dcc[c][1] for c in range(ncomp)])[owner, s]
+    assert np.all(ln > 0), "a DC size the table lacks"
+    keys.append(np.arange(n) * 260 + 3)
+    vals.append((code << s) | b)
+    lens.append(ln + s)
+    acode, alen = np.array([a[0] for a in acc]), np.array([a[1] for a in acc])
+    nzr, nzc = np.nonzero(blocks[:, 1:])
+    nzc = nzc + 1
+    first = np.concatenate([[True], nzr[1:] != nzr[:-1]]) if len(nzr) else np.zeros(0, bool)
+    run = nzc - np.where(first, 0, np.concatenate([[0], nzc[:-1]])) - 1
+    o = owner[nzr]
+    for j in range(3):                                         # up to three ZRL in front of a coefficient
+        m = run >= 16 * (j + 1)
+        assert np.all(alen[o[m], 0xf0] > 0), "the AC table lacks ZRL"
+        keys.append(nzr[m] * 260 + nzc[m] * 4 + j)
+        vals.append(acode[o[m], 0xf0])
+        lens.append(alen[o[m], 0xf0])
+    s, b = sized(blocks[nzr, nzc])
+    sym = ((run & 15) << 4) | s
+    assert np.all(s <= 15) and np.all(alen[o, sym] > 0), "an AC symbol the table lacks"
+    keys.append(nzr * 260 + nzc * 4 + 3)
+    vals.append((acode[o, sym] << s) | b)
+    lens.append(alen[o, sym] + s)
+    last = np.zeros(n, np.int64)
+    last[nzr] = nzc                                            # (ascending inside a block: the last one stays)
+    m = last < 63
+    assert np.all(alen[owner[m], 0] > 0), "the AC table lacks EOB"
+    keys.append(np.nonzero(m)[0] * 260 + 257)
+    vals.append(acode[owner[m], 0])
+    lens.append(alen[owner[m], 0])
+    if isinstance(dc_codes[0], _Tally):                         # the symbols are counted, nothing is coded
+        for c in range(ncomp):
+            dsz = sized(diff[owner == c])[0]
+            zrl = sum(int(np.count_nonzero((run >= 16 * (j + 1)) & (o == c))) for j in range(3))
+            asym = np.bincount(sym[o == c], minlength=256)
+            asym[0xf0] += zrl
+            asym[0] += int(np.count_nonzero(m & (owner == c)))
+            dc_codes[c].n.update({int(k): int(v) for k, v in enumerate(np.bincount(dsz, minlength=16)) if v})
+            ac_codes[c].n.update({int(k): int(v) for k, v in enumerate(asym) if v})
+        return b""
+    keys, vals, lens = np.concatenate(keys), np.concatenate(vals), np.concatenate(lens)
+    order = np.argsort(keys, kind="stable")
+    keys, vals, lens = keys[order], vals[order], lens[order]
+    # pad every restart interval (and the scan) to a byte with 1-bits: a pad token behind the interval's last token
+    tint = interval[keys // 260]
+    ends = np.nonzero(np.concatenate([tint[1:] != tint[:-1], [True]]))[0]
+    cum = np.cumsum(lens)
+    pads, shift, byte_ends = np.zeros(len(ends), np.int64), 0, []
+    for j, e in enumerate(ends):                               # (a loop over the intervals only)
+        pads[j] = -(int(cum[e]) + shift) % 8
+        shift += int(pads[j])
+        byte_ends.append((int(cum[e]) + shift) // 8)
+    vals = np.insert(vals, ends + 1, (1 << pads) - 1)
+    lens = np.insert(lens, ends + 1, pads)
+    start = np.cumsum(lens) - lens
+    total = int(start[-1] + lens[-1])
+    words = np.zeros(total // 32 + 2, np.uint64)
+    w, off = start >> 5, start & 31
+    v64 = vals.astype(np.uint64) << (np.uint64(64) - off.astype(np.uint64) - lens.astype(np.uint64))      # lens <= 27, off <= 31
+    v64[lens == 0] = 0
+    np.add.at(words, w, v64 >> np.uint64(32))
+    np.add.at(words, w + 1, v64 & np.uint64(0xffffffff))
+    raw = np.frombuffer(words.astype(">u4").tobytes(), np.uint8)[:total // 8]
+    ff = np.nonzero(raw == 0xff)[0]
+    out = np.insert(raw, ff + 1, 0)
+    if restart_blocks and len(byte_ends) > 1:
+        cuts = np.asarray(byte_ends[:-1], np.int64)
+        at = cuts + np.searchsorted(ff, cuts)                  # stuffed position of every interval's end
+        marks = np.stack([np.full(len(cuts), 0xff), 0xd0 + np.arange(len(cuts)) % 8], axis=1).reshape(-1)
+        out = np.insert(out, np.repeat(at, 2), marks.astype(np.uint8))
+    return out.astype(np.uint8).tobytes()

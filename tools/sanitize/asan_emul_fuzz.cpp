@@ -10,11 +10,13 @@
 #include <cstring>
 #include <random>
 #include <vector>
+extern "C" int emul_single_decode(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, unsigned warm_bits, unsigned headroom_groups,
+                                  int16_t *out, size_t cap_blocks, size_t *nblocks, int *stats);
 extern "C" int emul_decode_coefs(const uint8_t *jpeg, size_t len, int layout, int mode, int16_t *out, size_t cap_blocks, size_t *nblocks, int *stats);
 int main(int argc, char **argv)
 {
     std::mt19937_64 rng(777);
-    long runs = 0, ok = 0;
+    long runs = 0, ok = 0, plain = 0, plain_ok = 0;      // (plain: the files as they are, decoded before their mutations)
     std::vector<int16_t> out(size_t(200000) * 64);
     const int per_file = argc > 1 ? std::atoi(argv[1]) : 60;
     for (int a = 2; a < argc; a++) {
@@ -35,7 +37,7 @@ int main(int argc, char **argv)
         }
         for (int k = 0; k < per_file; k++) {
             std::vector<uint8_t> b = base;
-            const int muts = 1 + int(rng() % 4);
+            const int muts = k == 0 ? 0 : 1 + int(rng() % 4);        // (the file itself first)
             for (int m = 0; m < muts; m++) {
                 if (!dht.empty() && (rng() & 1)) { auto d = dht[rng() % dht.size()]; b[d.first + rng() % d.second] = uint8_t(rng()); }
                 else b[rng() % b.size()] = uint8_t(rng());
@@ -44,9 +46,11 @@ int main(int argc, char **argv)
             uint8_t *heap = static_cast<uint8_t *>(std::malloc(b.size()));
             std::memcpy(heap, b.data(), b.size());
             const int rc = emul_decode_coefs(heap, b.size(), 0, int(k & 1), out.data(), 200000, &nb, st);
+            (void)emul_single_decode(heap, b.size(), 0, int(k & 1), 0, k & 2 ? 1024u : 0u, 32, out.data(), 200000, &nb, st);      // (the other kernel sequence)
             std::free(heap);
             runs++; ok += rc == 0;
+            if (k == 0) { plain++; plain_ok += rc == 0; }
         }
     }
-    std::printf("asan emul fuzz: %ld decodes, %ld clean\n", runs, ok);
+    std::printf("asan emul fuzz: %ld decodes, %ld clean, %ld unmutated, %ld clean\n", runs, ok, plain, plain_ok);
 }
