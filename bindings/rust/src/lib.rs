@@ -28,6 +28,35 @@ pub struct mjx_rect {
     pub h: u32,
 }
 
+pub const MJX_DTYPE_U8: u8 = 0;
+pub const MJX_DTYPE_F16: u8 = 1;
+pub const MJX_DTYPE_F32: u8 = 2;
+
+/// Caller-owned device memory for one picture; pitches in elements (include/mjx.h).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mjx_dst {
+    pub dev: *mut c_void,
+    pub width: u32,
+    pub height: u32,
+    pub row_pitch: u64,
+    pub plane_pitch: u64,
+}
+
+/// What the pictures of a call leave as: u8 / f16 / f32, planar or interleaved, R,G,B or B,G,R, a float element
+/// fmaf(u8 as f32, scale[c], bias[c]) by OUTPUT channel; dst null = library-owned (include/mjx.h).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mjx_output {
+    pub dtype: u8,
+    pub planar: u8,
+    pub bgr: u8,
+    pub scale: [f32; 3],
+    pub bias: [f32; 3],
+    pub dst: *const mjx_dst,
+    pub n_dst: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct mjx_opts {
@@ -132,6 +161,14 @@ extern "C" {
     pub fn mjx_host_processors() -> c_uint;
     pub fn mjx_batch_create(ctx: *mut mjx_ctx, descs: *const mjx_scan_desc, n: usize, opts: *const mjx_opts,
                             out: *mut *mut mjx_batch, status: *mut c_int) -> c_int;
+    pub fn mjx_batch_create_out(ctx: *mut mjx_ctx, descs: *const mjx_scan_desc, n: usize, opts: *const mjx_opts, out: *const mjx_output,
+                                b: *mut *mut mjx_batch, status: *mut c_int) -> c_int;
+    pub fn mjx_output_layout(desc: *const mjx_scan_desc, opts: *const mjx_opts, out: *const mjx_output, i: usize, layout: *mut mjx_dst,
+                             bytes: *mut usize) -> c_int;
+    pub fn mjx_batch_output_info(b: *const mjx_batch, i: usize, layout: *mut mjx_dst, dtype: *mut u8, planar: *mut u8, bgr: *mut u8) -> c_int;
+    pub fn mjx_batch_copy_output(b: *mut mjx_batch, i: usize, host: *mut c_void, cap_bytes: usize) -> c_int;
+    pub fn mjx_decode_batch_out(ctx: *mut mjx_ctx, jpegs: *const *const u8, lens: *const usize, n: usize, opts: *const mjx_opts,
+                                threads: c_uint, out: *const mjx_output, status: *mut c_int, b: *mut *mut mjx_batch) -> c_int;
     pub fn mjx_batch_tile(ctx: *mut mjx_ctx, src: *const mjx_batch, times: usize, out: *mut *mut mjx_batch) -> c_int;
     pub fn mjx_batch_free(b: *mut mjx_batch);
     pub fn mjx_batch_decode(b: *mut mjx_batch, stages: c_uint) -> c_int;

@@ -90,6 +90,44 @@ typedef struct mjx_opts {
                              or rois == NULL with n_rois != 0, fails the call with MJX_ERR_INVALID_ARG. */
 } mjx_opts;
 
+/* ---- output formats: what a picture leaves as, and where -------------------------------------------------------------
+ * Without an output description a picture is packed R,G,B uint8 in the batch's own memory.  With one (mjx_batch_create_out,
+ * mjx_decode_batch_out) stage B writes, in its one pass over the pixels, H x W x 3 or 3 x H x W elements of uint8, float16 or
+ * float32, channels R,G,B or B,G,R, into the batch's memory or into device memory of the caller's.
+ * Values: the u8 value of a sample is exactly the byte the packed decode of the same build writes for that pixel and channel
+ * (same scale, same rectangle, STANDARD layout).  U8 outputs are a permutation of those bytes.  F32 is the single-rounded
+ * fmaf((float)u8, scale[c], bias[c]), round to nearest even; F16 is that float rounded to nearest even to half.  c is the
+ * OUTPUT channel (with bgr, c = 0 is blue).  An element so takes one of 256 values per channel.
+ * Ordering: the library writes on streams of its own.  A caller-owned destination must be idle when mjx_batch_decode (or
+ * mjx_decode_batch_out) is called and is complete when mjx_batch_wait (mjx_decode_batch_out) returns; nothing is written outside
+ * height rows x width elements (3 width interleaved) x 3 channels at the given pitches. */
+enum { MJX_DTYPE_U8 = 0, MJX_DTYPE_F16 = 1, MJX_DTYPE_F32 = 2 };
+typedef struct mjx_dst {      /* caller-owned device memory for one picture; pitches in elements */
+    void *dev;                /* first element of channel 0, row 0 */
+    uint32_t width, height;   /* the picture the caller expects (after scale and rectangle) */
+    uint64_t row_pitch;       /* elements between rows: >= width (planar) or >= 3*width (interleaved) */
+    uint64_t plane_pitch;     /* planar only: elements between channel planes, >= height*row_pitch */
+} mjx_dst;
+typedef struct mjx_output {
+    uint8_t dtype;            /* MJX_DTYPE_* */
+    uint8_t planar;           /* 0: H x W x 3 interleaved, 1: 3 x H x W */
+    uint8_t bgr;              /* 0: channel order R,G,B; 1: B,G,R */
+    float scale[3], bias[3];  /* F16/F32 only, indexed by OUTPUT channel: value = fmaf((float)u8, scale[c], bias[c]) */
+    const mjx_dst *dst;       /* NULL: library-owned, dense (row_pitch = width or 3*width, plane_pitch = height*width) */
+    uint32_t n_dst;           /* 0 with dst == NULL, else the call's number of inputs; dst[i] belongs to input i */
+} mjx_output;
+/* Per picture, MJX_ERR_INVALID_ARG (nothing is written for it, the others are unaffected): an unknown dtype; MJX_LAYOUT_REF_COMPAT;
+ * dst[i].width / height other than the picture's output size; a pitch too small; dev NULL or not aligned to the element size; a
+ * non-finite scale / bias with a float dtype.  n_dst other than 0 or the call's number of inputs, or dst == NULL with n_dst != 0,
+ * fails the call.  The description and dst[] are only borrowed for the duration of the call.
+ * A batch that carries an output description: mjx_batch_copy_rgb returns MJX_ERR_INVALID_ARG (mjx_batch_copy_output is its
+ * counterpart), mjx_batch_compare_rgb reports 0xffffffff for its pictures, mjx_batch_rgb_device gives the output's first byte and
+ * the span from there to the end of its last element, mjx_batch_bytes' rgb_bytes counts the bytes written.  mjx_batch_tile keeps
+ * a library-owned format and refuses a batch with caller-owned destinations (the copies would share them).  With caller-owned
+ * destinations the batch's device block holds no picture pool at all; with library-owned output the pool is sized by the format.
+ * Not built: mjx_decode, the pool (mjx_pool_decode_batch: the slot -- so the device -- of a file is not known to the caller before the
+ * deal) and the CLI keep packed RGB. */
+
 /* ---- inner seam: what jpeg/mod.rs:388-415 hands to JPEGDecoder -------------------------- */
 typedef struct mjx_comp {          /* decoder.rs:39-52 JPEGDecoderComponentFields */
     uint8_t id, h, v, tq, td, ta;
@@ -199,6 +237,21 @@ unsigned mjx_host_processors(void);
 int mjx_batch_create(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts,
                      mjx_batch **out, int *status);
 void mjx_batch_free(mjx_batch *b);
+/* mjx_batch_create with an output description (above); out == NULL: mjx_batch_create itself. */
+int mjx_batch_create_out(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_output *out,
+                         mjx_batch **b, int *status);
+/* Host-only, in the spirit of mjx_plan_tiles: what a decode of this picture as input i of a call with these options and this
+ * description would write -- size, pitches, for a caller-owned destination dst[i]'s own -- and *bytes, the span from the first
+ * element's first byte to the last element's last.  layout->dev stays NULL for library-owned output.  out == NULL: the packed
+ * picture (interleaved u8, width * height * 3 bytes).  The numbers come from the planner itself.  Returns the picture's status. */
+int mjx_output_layout(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_output *out, size_t i, mjx_dst *layout,
+                      size_t *bytes);
+/* The output of picture i of a batch: where it lies (layout->dev: device pointer), its pitches and its format.  A batch without
+ * an output description answers with the packed picture's (u8, interleaved, R,G,B). */
+int mjx_batch_output_info(const mjx_batch *b, size_t i, mjx_dst *layout, uint8_t *dtype, uint8_t *planar, uint8_t *bgr);
+/* Copy picture i's library-owned output to host memory, dense, as mjx_output_layout sizes it; cap_bytes smaller than that, a
+ * caller-owned destination or a batch without an output description: MJX_ERR_INVALID_ARG. */
+int mjx_batch_copy_output(mjx_batch *b, size_t i, void *host, size_t cap_bytes);
 
 /* Replicate the uploaded images `times`x on the device (image i*n+k is a byte copy of image k): builds the
  * large synthetic batches of BASELINE.json configs 4/5 from n unique images without re-uploading.  The copies keep their
@@ -286,6 +339,12 @@ int mjx_decode_scans(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const m
  * pinned arena belongs to the context).  Release with mjx_batch_free. */
 int mjx_decode_batch(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
                      unsigned threads, uint8_t **rgb_dev, int *status, mjx_batch **out);
+
+/* mjx_decode_batch with an output description; dst[i] follows file i through the groups of the pipelined call, as rois[i] does.
+ * out == NULL: mjx_decode_batch (without its rgb_dev array: mjx_batch_output_info says where picture i lies).  ctx == NULL -- what a
+ * failed mjx_ctx_create leaves -- is MJX_ERR_DEVICE: there is no device to write the output, and no CPU path. */
+int mjx_decode_batch_out(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
+                         unsigned threads, const mjx_output *out, int *status, mjx_batch **b);
 
 /* ---- multi-GPU front: one context + one host thread + one work queue per device, no collective ----------
  * Pictures are independent (decoder.rs:162-343 touches only `self`), so a list of files shards over the GPUs of a node

@@ -52,6 +52,23 @@ class Opts(ctypes.Structure):
                 ("rois", ctypes.POINTER(Rect)), ("n_rois", ctypes.c_uint32)]
 
 
+class Dst(ctypes.Structure):
+    """mjx_dst: caller-owned device memory for one picture; pitches in elements."""
+    _fields_ = [("dev", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("row_pitch", ctypes.c_uint64), ("plane_pitch", ctypes.c_uint64)]
+
+
+class OutputDesc(ctypes.Structure):
+    """mjx_output: what the pictures of a call leave as (see Output)."""
+    _fields_ = [("dtype", ctypes.c_uint8), ("planar", ctypes.c_uint8), ("bgr", ctypes.c_uint8),
+                ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3),
+                ("dst", ctypes.POINTER(Dst)), ("n_dst", ctypes.c_uint32)]
+
+
+DTYPE_U8, DTYPE_F16, DTYPE_F32 = 0, 1, 2
+_NP_DTYPES = {DTYPE_U8: np.uint8, DTYPE_F16: np.float16, DTYPE_F32: np.float32}
+
+
 class Comp(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint8) for n in ("id", "h", "v", "tq", "td", "ta")]
 
@@ -89,6 +106,11 @@ SYMBOLS = {
     "mjx_validate": (_int, [_P(ScanDesc), _P(Opts)]),
     "mjx_plan_tiles": (_int, [_P(ScanDesc), _P(Opts), _P(ctypes.c_uint64), _P(ctypes.c_uint64), _P(ctypes.c_uint32)]),
     "mjx_decode": (_int, [ctypes.c_char_p, _sz, _P(Opts), _P(Image)]),
+    "mjx_decode_batch_out": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(OutputDesc), _P(_int), _P(_vp)]),
+    "mjx_batch_create_out": (_int, [_vp, _P(ScanDesc), _sz, _P(Opts), _P(OutputDesc), _P(_vp), _P(_int)]),
+    "mjx_output_layout": (_int, [_P(ScanDesc), _P(Opts), _P(OutputDesc), _sz, _P(Dst), _P(_sz)]),
+    "mjx_batch_output_info": (_int, [_vp, _sz, _P(Dst)] + [_P(ctypes.c_uint8)] * 3),
+    "mjx_batch_copy_output": (_int, [_vp, _sz, _vp, _sz]),
     "mjx_decode_batch": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(_P(ctypes.c_uint8)), _P(_int), _P(_vp)]),
     "mjx_free_image": (None, [_P(Image)]),
     "mjx_ctx_create": (_int, [_int, _P(_vp)]),
@@ -194,6 +216,56 @@ def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_imag
     return o
 
 
+class Output:
+    """What the pictures of a call leave as (mjx.h: mjx_output): dtype "uint8" / "float16" / "float32" (or DTYPE_*), planar
+    (3 x H x W) or interleaved (H x W x 3), channels R,G,B or B,G,R.  A float element is fmaf(float(u8), scale[c], bias[c]) with c
+    the OUTPUT channel; mean / std (of values in [0, 1], per output channel: (v / 255 - mean) / std) become scale = 1 / (255 std)
+    and bias = -mean / std, computed in float64 and rounded once to float32.
+    dst: None -- the library owns the output, dense -- or one (device pointer, width, height, row_pitch, plane_pitch) per input,
+    pitches in elements."""
+
+    def __init__(self, dtype="uint8", planar=False, bgr=False, mean=None, std=None, scale=None, bias=None, dst=None):
+        names = {"uint8": DTYPE_U8, "u8": DTYPE_U8, "float16": DTYPE_F16, "f16": DTYPE_F16, "float32": DTYPE_F32, "f32": DTYPE_F32}
+        self.dtype = names[dtype] if isinstance(dtype, str) else int(dtype)
+        self.planar, self.bgr = bool(planar), bool(bgr)
+        if (mean is not None or std is not None) and (scale is not None or bias is not None):
+            raise MjxError(ERR_INVALID_ARG, "mean / std or scale / bias, not both")
+        three = lambda v, d: [float(d)] * 3 if v is None else ([float(v)] * 3 if np.isscalar(v) else [float(x) for x in v])
+        if mean is not None or std is not None:
+            m, sd = np.array(three(mean, 0.0), np.float64), np.array(three(std, 1.0), np.float64)
+            sc, bi = 1.0 / (255.0 * sd), -m / sd
+        else:
+            sc, bi = np.array(three(scale, 1.0), np.float64), np.array(three(bias, 0.0), np.float64)
+        if len(sc) != 3 or len(bi) != 3:
+            raise MjxError(ERR_INVALID_ARG, "three values per channel")
+        self.scale, self.bias = sc.astype(np.float32), bi.astype(np.float32)
+        self.dst = None if dst is None else [tuple(int(v) for v in d) for d in dst]
+
+    def desc(self):
+        """-> the ctypes mjx_output (it keeps its dst array alive)."""
+        d = OutputDesc(self.dtype, int(self.planar), int(self.bgr))
+        for c in range(3):
+            d.scale[c], d.bias[c] = float(self.scale[c]), float(self.bias[c])
+        if self.dst is not None:
+            arr = (Dst * max(len(self.dst), 1))()
+            for i, v in enumerate(self.dst):
+                arr[i] = Dst(v[0] or None, v[1], v[2], v[3], v[4])
+            d._arr = arr
+            d.dst = ctypes.cast(arr, _P(Dst))
+            d.n_dst = len(self.dst)
+        return d
+
+    def numpy_dtype(self):
+        return _NP_DTYPES[self.dtype]
+
+
+def _out_ref(output):
+    if output is None:
+        return None, None
+    d = output.desc() if isinstance(output, Output) else output
+    return d, ctypes.byref(d)
+
+
 # ---- host parse ------------------------------------------------------------------------------------
 class ParsedScan:
     """Owns one mjx_scan_desc filled by mjx_parse (reference: the state JPEGImage::parse hands to JPEGDecoder)."""
@@ -221,6 +293,15 @@ class ParsedScan:
         _check(lib().mjx_plan_tiles(ctypes.byref(self.desc), ctypes.byref(o), ctypes.byref(rd), ctypes.byref(tot), ctypes.byref(t)), "mjx_plan_tiles")
         return dict(tiles_read=rd.value, tiles_total=tot.value, tile_mcus=t.value)
 
+    def output_layout(self, output=None, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD):
+        """mjx_output_layout (host only) -> dict(width, height, row_pitch, plane_pitch, bytes, dev): what a decode of this picture
+        as input i of a call with this Output would write; pitches in elements, bytes from the first element to the last."""
+        o = _opts(layout=layout, scale=scale, rois=roi)
+        keep, ref = _out_ref(output)
+        lay, nb = Dst(), _sz()
+        _check(lib().mjx_output_layout(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(lay), ctypes.byref(nb)), "mjx_output_layout")
+        return dict(width=lay.width, height=lay.height, row_pitch=lay.row_pitch, plane_pitch=lay.plane_pitch, bytes=nb.value, dev=lay.dev or 0)
+
     def close(self):
         if self._owned:
             lib().mjx_free_scan(ctypes.byref(self.desc))
@@ -238,6 +319,7 @@ class Context:
     def __init__(self, device=0, profiling=False, throughput_plan=False):
         """throughput_plan: batches are always cut into 512-byte subsequences (for a small base that Batch.tile replicates)."""
         self.h = _vp()
+        self.device = int(device)
         _check(lib().mjx_ctx_create(int(device), ctypes.byref(self.h)), "mjx_ctx_create(device=%d)" % device)
         if profiling:
             self.set_profiling(True)
@@ -267,12 +349,15 @@ class Batch:
     """Device-resident batch: inputs uploaded at construction, ``decode()`` only enqueues kernels."""
 
     def __init__(self, ctx, scans=None, strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0,
-                 _handle=None, scale=1, rois=None):
+                 _handle=None, scale=1, rois=None, output=None):
         """scale: 1, 2, 4 or 8 -- every picture decoded at 1/scale (info(), rgb(), rgb_device() and bytes() then speak of the
         scaled picture; tile() keeps the scale).
         rois: one (x, y, w, h) for every picture, or a list with one per picture (None or (0, 0, 0, 0): the whole picture), in the
         coordinates of the scaled picture -- info(), rgb(), rgb_device(), bytes() and compare_rgb() then speak of the cropped
-        picture, roi(i) says where it lies; tile() keeps the rectangles."""
+        picture, roi(i) says where it lies; tile() keeps the rectangles.
+        output: an Output -- the pictures leave in that format (output(i), output_info(i); rgb() and compare_rgb() do not serve
+        such a batch), in the batch's memory or, Output(dst=...), in device memory of the caller's: idle when decode() is called,
+        complete when wait() returns."""
         self.ctx = ctx
         self.h = _vp()
         if _handle is not None:
@@ -285,7 +370,8 @@ class Batch:
                            ctypes.sizeof(ScanDesc))
         st = (_int * max(n, 1))()
         o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois)
-        _check(lib().mjx_batch_create(ctx.h, arr, n, ctypes.byref(o), ctypes.byref(self.h), st), "mjx_batch_create")
+        keep, ref = _out_ref(output)
+        _check(lib().mjx_batch_create_out(ctx.h, arr, n, ctypes.byref(o), ref, ctypes.byref(self.h), st), "mjx_batch_create_out")
         self.create_status = list(st)[:n]
 
     def tile(self, times):
@@ -321,6 +407,22 @@ class Batch:
         inf = self.info(i)
         out = np.empty((inf["height"], inf["width"], 3), np.uint8)
         _check(lib().mjx_batch_copy_rgb(self.h, i, out.ctypes.data_as(_vp)), "mjx_batch_copy_rgb")
+        return out
+
+    def output_info(self, i):
+        """mjx_batch_output_info -> dict(dev, width, height, row_pitch, plane_pitch, dtype, planar, bgr); pitches in elements."""
+        lay = Dst()
+        v = [ctypes.c_uint8() for _ in range(3)]
+        _check(lib().mjx_batch_output_info(self.h, i, ctypes.byref(lay), *[ctypes.byref(x) for x in v]), "mjx_batch_output_info")
+        return dict(dev=lay.dev or 0, width=lay.width, height=lay.height, row_pitch=lay.row_pitch, plane_pitch=lay.plane_pitch,
+                    dtype=v[0].value, planar=bool(v[1].value), bgr=bool(v[2].value))
+
+    def output(self, i):
+        """Picture i's library-owned output as an ndarray of its dtype: [3, H, W] (planar) or [H, W, 3]."""
+        inf = self.output_info(i)
+        shape = (3, inf["height"], inf["width"]) if inf["planar"] else (inf["height"], inf["width"], 3)
+        out = np.empty(shape, _NP_DTYPES[inf["dtype"]])
+        _check(lib().mjx_batch_copy_output(self.h, i, out.ctypes.data_as(_vp), out.nbytes), "mjx_batch_copy_output")
         return out
 
     def rgb_device(self, i):
@@ -562,19 +664,71 @@ class JPEGImage:
         return self._rgb
 
 
-def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False, scale=1, rois=None):
+def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False, scale=1, rois=None,
+                 output=None, chunk_images=0):
     """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale, rois: see Batch.
     device_destuff: the host copies the entropy-coded bytes as they are; de-stuffing, restart markers and the scan's length
-    are found on the GPU."""
+    are found on the GPU.  output: an Output (mjx_decode_batch_out) -- see Batch."""
     n = len(datas)
     arr = (ctypes.c_char_p * max(n, 1))(*[bytes(d) for d in datas])
     lens = (_sz * max(n, 1))(*[len(d) for d in datas])
     st = (_int * max(n, 1))()
     ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
     h = _vp()
-    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, device_destuff=device_destuff, scale=scale, rois=rois)
+    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois)
+    if output is not None:
+        keep, ref = _out_ref(output)
+        _check(lib().mjx_decode_batch_out(ctx.h, arr, lens, n, ctypes.byref(o), int(threads), ref, st, ctypes.byref(h)), "mjx_decode_batch_out")
+        return Batch(ctx, _handle=h), list(st)[:n]
     _check(lib().mjx_decode_batch(ctx.h, arr, lens, n, ctypes.byref(o), int(threads), ptrs, st, ctypes.byref(h)), "mjx_decode_batch")
     return Batch(ctx, _handle=h), list(st)[:n]
+
+
+def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=False, threads=0, device_destuff=None, planar=None):
+    """Decodes the files straight into a torch tensor on the context's device: N x 3 x H x W (planar) or N x H x W x 3, of uint8,
+    float16 or float32; picture i -- at 1/scale, its rectangle rois[i] -- must be H x W.  Float tensors take (v / 255 - mean) / std
+    per OUTPUT channel (see Output); bgr: channel 0 is blue.  The pointers and pitches come from data_ptr() and stride(): the
+    innermost dimension must be dense (planar: stride 1 along W; interleaved: stride 1 along the channels and 3 along W), rows
+    and planes may be padded, and the pictures must not overlap (the batch stride covers a picture's span).
+    planar: True / False says which form the tensor is.  None takes it from the shape: N x 3 x H x W when the second dimension is
+    3, N x H x W x 3 when only the last is; a shape that reads both ways (N x 3 x H x 3) needs the keyword.
+    torch's current stream is synchronised before the call (the library writes on streams of its
+    own) and the batch is complete when this returns.  -> the per-picture statuses."""
+    import torch
+    n = len(datas)
+    if not isinstance(out, torch.Tensor) or out.dim() != 4 or out.shape[0] != n:
+        raise MjxError(ERR_INVALID_ARG, "out: a tensor of %d pictures" % n)
+    names = {torch.uint8: DTYPE_U8, torch.float16: DTYPE_F16, torch.float32: DTYPE_F32}
+    if out.dtype not in names:
+        raise MjxError(ERR_INVALID_ARG, "out.dtype %s" % out.dtype)
+    if out.device.type != "cuda" or out.device.index != ctx.device:
+        raise MjxError(ERR_INVALID_ARG, "out lies on %s, not on the context's device %d" % (out.device, ctx.device))
+    sn, s1, s2, s3 = out.stride()
+    if planar is None:
+        if out.shape[1] == 3 and out.shape[3] == 3:
+            raise MjxError(ERR_INVALID_ARG, "out: %s reads as 3 x H x W and as H x W x 3: say planar=True or planar=False" % (tuple(out.shape),))
+        planar = out.shape[1] == 3
+    if planar and out.shape[1] == 3:
+        h, w = int(out.shape[2]), int(out.shape[3])
+        ok = s3 == 1 and s2 >= w and s1 >= h * s2
+        row_pitch, plane_pitch = s2, s1
+        span = 2 * s1 + (h - 1) * s2 + w
+    elif not planar and out.shape[3] == 3:
+        h, w = int(out.shape[1]), int(out.shape[2])
+        ok = s3 == 1 and s2 == 3 and s1 >= 3 * w
+        row_pitch, plane_pitch = s1, 0
+        span = (h - 1) * s1 + 3 * w
+    else:
+        raise MjxError(ERR_INVALID_ARG, "out: N x 3 x H x W or N x H x W x 3")
+    if not ok or (n > 1 and sn < span):
+        raise MjxError(ERR_INVALID_ARG, "out.stride() %s: neither 3 x H x W nor H x W x 3 with a dense innermost dimension, or the pictures overlap" % (tuple(out.stride()),))
+    esz = out.element_size()
+    dst = [(out.data_ptr() + i * sn * esz, w, h, row_pitch, plane_pitch) for i in range(n)]
+    fmt = Output(names[out.dtype], planar=bool(planar), bgr=bgr, mean=mean, std=std, dst=dst)
+    torch.cuda.current_stream(out.device).synchronize()
+    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt)
+    batch.close()
+    return status
 
 
 class Pool:
@@ -699,6 +853,15 @@ def plan_tiles(data, roi=None, scale=1):
     scan = ParsedScan(data)
     try:
         return scan.plan_tiles(roi=roi, scale=scale)
+    finally:
+        scan.close()
+
+
+def output_layout(data, output=None, i=0, roi=None, scale=1):
+    """Host only: what a decode of this file as input i with this Output would write -> see ParsedScan.output_layout."""
+    scan = ParsedScan(data)
+    try:
+        return scan.output_layout(output, i=i, roi=roi, scale=scale)
     finally:
         scan.close()
 

@@ -126,6 +126,11 @@ struct ImageInfo {
     uint32_t roi_x = 0, roi_y = 0, full_w = 0, full_h = 0;  // where it lies in the uncropped out_w x out_h picture (mjx_batch_image_roi)
     uint64_t nblocks = 0;
     uint64_t rgb_off = 0, rgb_bytes = 0;
+    // output formats (mjx_output): the picture has a description; where it lies -- out_dev, or 0: at rgb_off of the batch's pool --,
+    // its pitches in elements and the span of bytes from its first element to its last (rgb_bytes: the bytes written)
+    bool out_on = false, cropped = false;
+    uint32_t out_dtype = 0, out_planar = 0, out_bgr = 0;
+    uint64_t out_dev = 0, out_row_pitch = 0, out_plane_pitch = 0, out_span = 0;
     uint64_t coef_off = 0;         // blocks, inside the per-block arrays of its chunk (or of the batch with keep_coefs)
     uint64_t ent_off = 0, ent_cap = 0;   // region of the compact coefficient stream (entries)
     uint32_t ent_rows = 0, ent_hdr = 0;  // > 0: quad-interleaved (DevImage::ent_rows, ent_hdr)
@@ -155,6 +160,7 @@ struct Chunk {
     uint32_t max_pixel_wgs = 0;
     uint32_t max_dc_wgs = 0;       // scaled decode at 1/8: workgroups of k_dc_color for the chunk's largest picture
     uint32_t max_dc_roi_wgs = 0;   // ... and of k_dc_color_roi for its largest rectangle
+    uint32_t max_dc_out_wgs = 0;   // ... and of k_dc_color_out for its largest picture with an output description
     uint32_t max_b_tiles = 0;      // tiles the workgroups of stage B walk in the chunk's largest picture: all its tiles, or those of its
                                    // rectangle's MCU rows (DevImage::roi_ntiles) -- max_tiles without rectangles
     uint32_t min_sub_bits = 0xffffffffu;   // shortest subsequence length among its scans (chunk_fix_passes)
@@ -490,6 +496,14 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
         d.roi_tile0 = (p.roi_mr0 * p.mcux + p.roi_mc0) / t;
         d.roi_ntiles = (p.roi_mr1 * p.mcux + p.roi_mc1) / t - d.roi_tile0 + 1;
     }
+    // output formats: the forms built on the cropped ones (a picture without a rectangle is its own whole rectangle: every tile above)
+    if (p.out_on) {
+        d.mode = d.mode % kRoiMode + kOutMode;
+        d.out_dev = p.out_dev;
+        d.out_row_pitch = p.out_row_pitch; d.out_plane_pitch = p.out_plane_pitch;
+        d.out_dtype = p.out_dtype; d.out_planar = p.out_planar; d.out_bgr = p.out_bgr;
+        for (uint32_t c = 0; c < 3; c++) { d.out_scale[c] = p.out_scale[c]; d.out_bias[c] = p.out_bias[c]; }
+    }
     d.role = p.role;
     d.wg_lanes = p.wg_lanes;
     if (p.role == 1) {                // a scan of a multi-scan file: no stage B; one tile offset per block for the gather (build_batch: or segment cuts, seg_S)
@@ -596,6 +610,7 @@ void plan_chunks(mjx_batch *b)
                 c.bpm_mask |= 1u << d.bpm;
                 if (d.nseg > 1) c.max_restart_segs = std::max(c.max_restart_segs, d.nseg);
                 if (d.mode == 5) c.max_dc_wgs = std::max<uint32_t>(c.max_dc_wgs, uint32_t((uint64_t(d.out_w) * d.out_h + 255) / 256));
+                if (d.mode == 5 + kOutMode) c.max_dc_out_wgs = std::max<uint32_t>(c.max_dc_out_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
                 if (d.mode == 5 + kRoiMode) c.max_dc_roi_wgs = std::max<uint32_t>(c.max_dc_roi_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
                 if (d.mode == 2) {
                     d.plane_off = c.plane_words;
@@ -908,6 +923,7 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
         if (c.plane_words) launch_ref_color(sp, c.max_pixel_wgs, nimg, imgs, SCR(d_planes), b->d_rgb, b->d_img_flags);
         if (c.max_dc_wgs) launch_dc_color(sp, c.max_dc_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags);
         if (c.max_dc_roi_wgs) launch_dc_color(sp, c.max_dc_roi_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true);
+        if (c.max_dc_out_wgs) launch_dc_color(sp, c.max_dc_out_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true, true);
         prof_end(b, sp);
         if (sp != st) {
             HIPOK(hipEventRecord(b->ev_pixels[set], sp));
@@ -1236,7 +1252,18 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
         inf.scan_len = p.scan_len;
         inf.rgb_off = rgb_pool;
         inf.rgb_bytes = p.role == 1 ? 0 : uint64_t(p.roi_w) * p.roi_h * 3;     // (a scan of a multi-scan file has no picture)
+        inf.cropped = p.cropped;
         d.rgb_off = rgb_pool;
+        if (p.out_on && p.role != 1) {
+            // output formats: the pool region is sized by the format; a caller-owned destination takes none of the pool
+            if (times > 1 && p.out_dev) return MJX_ERR_INVALID_ARG;          // (copies would share the destination)
+            inf.out_on = true;
+            inf.out_dtype = p.out_dtype; inf.out_planar = p.out_planar; inf.out_bgr = p.out_bgr;
+            inf.out_dev = p.out_dev; inf.out_row_pitch = p.out_row_pitch; inf.out_plane_pitch = p.out_plane_pitch;
+            inf.out_span = p.out_bytes;
+            inf.rgb_bytes *= p.out_dtype == MJX_DTYPE_U8 ? 1u : p.out_dtype == MJX_DTYPE_F16 ? 2u : 4u;      // (the bytes written)
+            rgb_pool += p.out_dev ? 0 : align_up(inf.out_span, 256);
+        } else
         rgb_pool += align_up(inf.rgb_bytes, 256);
         b->scan_bytes += p.scan_len;
         b->rgb_bytes += inf.rgb_bytes;
@@ -1749,12 +1776,18 @@ extern "C" unsigned mjx_host_processors(void) { return usable_processors(); }
 extern "C" int mjx_batch_create(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts,
                                 mjx_batch **out, int *status)
 {
+    return mjx_batch_create_out(ctx, descs, n, opts, nullptr, out, status);
+}
+
+extern "C" int mjx_batch_create_out(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_output *fmt,
+                                    mjx_batch **out, int *status)
+{
     return guarded([&]() -> int {
     if (!ctx || !out || (!descs && n)) return MJX_ERR_INVALID_ARG;
     *out = nullptr;
     mjx_opts o{};
     if (opts) o = *opts;
-    if (!rois_fit(o, n)) return MJX_ERR_INVALID_ARG;
+    if (!rois_fit(o, n) || !output_fits(fmt, n)) return MJX_ERR_INVALID_ARG;
     const mjx_scan_desc *dd = descs;
     std::vector<ImagePlan> plans;
     std::vector<size_t> plan_of(n);                    // input i -> its picture's plan (multi-scan files add plans in front)
@@ -1762,6 +1795,7 @@ extern "C" int mjx_batch_create(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t
     const auto tp0 = std::chrono::steady_clock::now();
     for (size_t i = 0; i < n; i++) {
         plan_input(dd[i], opts_for_input(o, n, i), plans);      // (rois[i] goes with input i: a multi-scan file's picture plan takes it)
+        plan_output_of_input(plans, fmt, i);                    // (... and dst[i])
         plan_of[i] = plans.size() - 1;
     }
     if (std::getenv("MJX_TIMING"))
@@ -1816,11 +1850,39 @@ extern "C" int mjx_plan_tiles(const mjx_scan_desc *desc, const mjx_opts *opts, u
     });
 }
 
+// Host-only: what a decode of this picture as input i would write -- plan_output's own numbers.
+extern "C" int mjx_output_layout(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_output *fmt, size_t i, mjx_dst *layout,
+                                 size_t *bytes)
+{
+    return guarded([&]() -> int {
+    if (!desc) return MJX_ERR_INVALID_ARG;
+    mjx_opts o{};
+    if (opts) o = *opts;
+    if (!rois_fit(o, 1)) return MJX_ERR_INVALID_ARG;
+    if (fmt && (fmt->dst ? i >= fmt->n_dst : fmt->n_dst != 0)) return MJX_ERR_INVALID_ARG;
+    std::vector<ImagePlan> plans;
+    plan_input(*desc, o, plans);
+    plan_output_of_input(plans, fmt, i);
+    ImagePlan &p = plans.back();
+    if (p.status != MJX_OK) return p.status;
+    if (layout) {
+        layout->dev = reinterpret_cast<void *>(uintptr_t(p.out_dev));
+        layout->width = p.roi_w; layout->height = p.roi_h;
+        layout->row_pitch = p.out_on ? p.out_row_pitch : uint64_t(p.roi_w) * 3;
+        layout->plane_pitch = p.out_on ? p.out_plane_pitch : 0;
+    }
+    if (bytes) *bytes = size_t(p.out_bytes);
+    return MJX_OK;
+    });
+}
+
 extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, mjx_batch **out)
 {
     return guarded([&]() -> int {
     if (!ctx || !src || !out || times == 0 || !src->parts.empty()) return MJX_ERR_INVALID_ARG;
     *out = nullptr;
+    for (const ImageInfo &fi : src->info)
+        if (fi.out_on && fi.out_dev) return MJX_ERR_INVALID_ARG;       // (caller-owned destinations: the copies would share them)
     // rebuild light-weight plans from the source batch's device images (geometry only; tables stay on the device)
     const size_t nu = src->info.size();
     std::vector<ImagePlan> plans(nu);
@@ -1843,7 +1905,15 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
         if (p.status != MJX_OK) continue;
         p.width = d.width; p.height = d.height; p.ncomp = d.ncomp; p.bpm = d.bpm; p.hmax = d.hmax; p.vmax = d.vmax;
         p.scale = d.scale ? d.scale : 1u; p.out_w = d.out_w; p.out_h = d.out_h;      // (the copies keep the source's scale)
-        p.cropped = d.mode >= kRoiMode;                                               // (... and its rectangle)
+        p.cropped = src->info[k].cropped;                                             // (... and its rectangle)
+        if (src->info[k].out_on) {                                                    // (... and its output format)
+            const ImageInfo &fi = src->info[k];
+            p.out_on = true;
+            p.out_dtype = fi.out_dtype; p.out_planar = fi.out_planar; p.out_bgr = fi.out_bgr;
+            p.out_dev = fi.out_dev; p.out_row_pitch = fi.out_row_pitch; p.out_plane_pitch = fi.out_plane_pitch;
+            p.out_bytes = fi.out_span;
+            for (uint32_t c = 0; c < 3; c++) { p.out_scale[c] = src->himages[k].out_scale[c]; p.out_bias[c] = src->himages[k].out_bias[c]; }
+        }
         p.roi_x = d.roi_x; p.roi_y = d.roi_y; p.roi_w = d.roi_w; p.roi_h = d.roi_h;
         p.roi_mr0 = d.roi_mr0; p.roi_mr1 = d.roi_mr1; p.roi_mc0 = d.roi_mc0; p.roi_mc1 = d.roi_mc1;
         p.mcux = d.mcux; p.mcuy = d.mcuy; p.nmcu = d.nmcu;
@@ -2146,8 +2216,28 @@ extern "C" int mjx_batch_rgb_device(const mjx_batch *b, size_t iu, void **dev_pt
     if (!visible_index(b, iu, i) || !dev_ptr) return MJX_ERR_INVALID_ARG;
     const ImageInfo &inf = b->info[i];
     if (inf.status != MJX_OK) { *dev_ptr = nullptr; if (bytes) *bytes = 0; return inf.status; }
-    *dev_ptr = b->d_rgb + inf.rgb_off;
-    if (bytes) *bytes = size_t(inf.rgb_bytes);
+    *dev_ptr = inf.out_on && inf.out_dev ? reinterpret_cast<void *>(uintptr_t(inf.out_dev)) : b->d_rgb + inf.rgb_off;
+    if (bytes) *bytes = size_t(inf.out_on ? inf.out_span : inf.rgb_bytes);
+    return MJX_OK;
+}
+
+extern "C" int mjx_batch_output_info(const mjx_batch *b, size_t iu, mjx_dst *layout, uint8_t *dtype, uint8_t *planar, uint8_t *bgr)
+{
+    if (b && !b->parts.empty()) { mjx_batch *pb; size_t pi; return route(b, iu, pb, pi) ? mjx_batch_output_info(pb, pi, layout, dtype, planar, bgr) : MJX_ERR_INVALID_ARG; }
+    size_t i;
+    if (!visible_index(b, iu, i)) return MJX_ERR_INVALID_ARG;
+    const ImageInfo &inf = b->info[i];
+    if (layout) std::memset(layout, 0, sizeof *layout);
+    if (dtype) *dtype = uint8_t(inf.out_dtype);
+    if (planar) *planar = uint8_t(inf.out_planar);
+    if (bgr) *bgr = uint8_t(inf.out_bgr);
+    if (inf.status != MJX_OK) return inf.status;
+    if (layout) {
+        layout->dev = inf.out_on && inf.out_dev ? reinterpret_cast<void *>(uintptr_t(inf.out_dev)) : b->d_rgb + inf.rgb_off;
+        layout->width = inf.width; layout->height = inf.height;
+        layout->row_pitch = inf.out_on ? inf.out_row_pitch : uint64_t(inf.width) * 3;
+        layout->plane_pitch = inf.out_on ? inf.out_plane_pitch : 0;
+    }
     return MJX_OK;
 }
 
@@ -2189,9 +2279,25 @@ extern "C" int mjx_batch_copy_rgb(mjx_batch *b, size_t iu, uint8_t *host_rgb)
     if (!visible_index(b, iu, i) || !host_rgb) return MJX_ERR_INVALID_ARG;
     const ImageInfo &inf = b->info[i];
     if (inf.status != MJX_OK) return inf.status;
+    if (inf.out_on) return MJX_ERR_INVALID_ARG;          // (not packed RGB: mjx_batch_copy_output)
     HIPOK(hipSetDevice(b->ctx->device));
     { const int rcs = sync_streams(b); if (rcs != MJX_OK) return rcs; }
     return copy_from_device(b->ctx, host_rgb, b->d_rgb + inf.rgb_off, size_t(inf.rgb_bytes));
+    });
+}
+
+extern "C" int mjx_batch_copy_output(mjx_batch *b, size_t iu, void *host, size_t cap_bytes)
+{
+    if (b && !b->parts.empty()) { mjx_batch *pb; size_t pi; return route(b, iu, pb, pi) ? mjx_batch_copy_output(pb, pi, host, cap_bytes) : MJX_ERR_INVALID_ARG; }
+    return guarded([&]() -> int {
+    size_t i;
+    if (!visible_index(b, iu, i) || !host) return MJX_ERR_INVALID_ARG;
+    const ImageInfo &inf = b->info[i];
+    if (inf.status != MJX_OK) return inf.status;
+    if (!inf.out_on || inf.out_dev || cap_bytes < inf.out_span) return MJX_ERR_INVALID_ARG;
+    HIPOK(hipSetDevice(b->ctx->device));
+    { const int rcs = sync_streams(b); if (rcs != MJX_OK) return rcs; }
+    return copy_from_device(b->ctx, host, b->d_rgb + inf.rgb_off, size_t(inf.out_span));
     });
 }
 
@@ -2280,7 +2386,7 @@ extern "C" int mjx_batch_compare_rgb(mjx_batch *a, const size_t *ia, mjx_batch *
             if (!visible_index(pa, ka, xa) || !visible_index(pb, kb, xb)) return MJX_ERR_INVALID_ARG;
             const ImageInfo &fa = pa->info[xa], &fb = pb->info[xb];
             pairs[k] = RgbPair{pa->d_rgb + fa.rgb_off, pb->d_rgb + fb.rgb_off, fa.rgb_bytes};
-            if (fa.status != MJX_OK || fb.status != MJX_OK || fa.width != fb.width || fa.height != fb.height) {
+            if (fa.status != MJX_OK || fb.status != MJX_OK || fa.width != fb.width || fa.height != fb.height || fa.out_on || fb.out_on) {
                 bad[k] = 1;
                 pairs[k].bytes = 0;
             }
@@ -2495,8 +2601,9 @@ unsigned usable_processors()
 // transfer per group, on the upload stream) and its kernels (on the decode streams, behind the upload's event), and
 // turns to the next group -- so parsing of group g+2, the transfer of group g+1 and the kernels of group g run at the
 // same time, and the call takes about as long as the slowest of the three (on PCIe Gen5: the transfer).
-extern "C" int mjx_decode_batch(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
-                                unsigned threads, uint8_t **rgb_dev, int *status, mjx_batch **out)
+// (fmt: the call's output description, or null -- mjx_decode_batch_out; dst[i] goes with file i wherever its group falls)
+static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
+                             unsigned threads, const mjx_output *fmt, uint8_t **rgb_dev, int *status, mjx_batch **out)
 {
     return guarded([&]() -> int {
     if (!ctx || !out || ((!jpegs || !lens) && n)) return MJX_ERR_INVALID_ARG;
@@ -2504,7 +2611,7 @@ extern "C" int mjx_decode_batch(mjx_ctx *ctx, const uint8_t *const *jpegs, const
     std::lock_guard<std::mutex> serial(ctx->batch_mu);        // the pinned arena is shared state of the context
     mjx_opts o{};
     if (opts) o = *opts;
-    if (!rois_fit(o, n)) return MJX_ERR_INVALID_ARG;
+    if (!rois_fit(o, n) || !output_fits(fmt, n)) return MJX_ERR_INVALID_ARG;
     const bool timing = std::getenv("MJX_TIMING") != nullptr;
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
@@ -2635,6 +2742,7 @@ extern "C" int mjx_decode_batch(mjx_ctx *ctx, const uint8_t *const *jpegs, const
             if (rc != MJX_OK) std::memset(&descs[i], 0, sizeof descs[i]);
             try {
                 plan_input(descs[i], opts_for_input(o, n, i), file_plans[i]);          // geometry + decode tables, also on the worker (rois[i] goes with file i)
+                plan_output_of_input(file_plans[i], fmt, i);                           // (... and dst[i])
             } catch (...) {
                 file_plans[i].clear();
             }
@@ -2709,6 +2817,19 @@ extern "C" int mjx_decode_batch(mjx_ctx *ctx, const uint8_t *const *jpegs, const
     *out = dir;
     return MJX_OK;
     });
+}
+
+extern "C" int mjx_decode_batch(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
+                                unsigned threads, uint8_t **rgb_dev, int *status, mjx_batch **out)
+{
+    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, nullptr, rgb_dev, status, out);
+}
+
+extern "C" int mjx_decode_batch_out(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
+                                    unsigned threads, const mjx_output *fmt, int *status, mjx_batch **out)
+{
+    if (!ctx) { if (out) *out = nullptr; return MJX_ERR_DEVICE; }      // (no context is no device: mjx_ctx_create failed, and there is no CPU path)
+    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, fmt, nullptr, status, out);
 }
 
 // ---- one-shot surface ------------------------------------------------------------------------------

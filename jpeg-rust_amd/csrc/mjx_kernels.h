@@ -94,8 +94,17 @@ struct DevImage {
     uint32_t roi_x, roi_y, roi_w, roi_h;
     uint32_t roi_mr0, roi_mr1, roi_mc0, roi_mc1;
     uint32_t roi_tile0, roi_ntiles;
+    // output formats (mjx_output; mode >= kOutMode): the picture leaves as 3 x H x W or H x W x 3 elements of u8 / f16 / f32 in the
+    // channel order asked for, a float element as fmaf(float(u8), out_scale[c], out_bias[c]) with c the OUTPUT channel.  The first
+    // element lies at out_dev (caller-owned memory) or, out_dev == 0, at byte rgb_off of the batch's picture pool; pitches count
+    // elements.  Such a picture is its own whole rectangle unless it has one (roi_* above say which either way).
+    uint64_t out_dev;
+    uint64_t out_row_pitch, out_plane_pitch;
+    uint32_t out_dtype, out_planar, out_bgr;
+    float out_scale[3], out_bias[3];
 };
 constexpr uint32_t kRoiMode = 8;
+constexpr uint32_t kOutMode = 16;      // + m (0, 1, 3, 4; 5: k_dc_color_out): the forms for pictures with an output description
 
 // Region-of-interest decode: does tile t -- T consecutive MCUs in raster order, so it may wrap into the next MCU row -- hold an MCU
 // of the MCU rows r0 .. r1 and the MCU columns c0 .. c1?  Arithmetic on uniform values only: stage B decides per tile without a
@@ -404,7 +413,8 @@ void launch_dc_scan(hipStream_t st, uint32_t max_segs, uint32_t nimg, const DevI
                     uint32_t *fail = nullptr /* device word, set when the one-pass kernel gave up waiting */, uint32_t spin_limit = 1u << 20,
                     bool fault = false /* test knob: a workgroup never publishes */);
 // (max_tiles: the chunk's largest count of tiles a picture's workgroups walk -- DevImage::roi_ntiles; mode_mask bits kRoiMode + m:
-// pictures with a rectangle, which take the forms k_idct_color<kRoiMode + m, ...>)
+// pictures with a rectangle, which take the forms k_idct_color<kRoiMode + m, ...>; bits kOutMode + m: pictures with an output
+// description, k_idct_color<kOutMode + m, ...>)
 void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t lds, const DevImage *images,
                        const uint32_t *entries, const uint32_t *tile_eoff, const int32_t *dcbuf, const float *qmult,
                        uint8_t *rgb, uint32_t mode_mask, unsigned long long *planes, const uint32_t *img_flags,
@@ -420,7 +430,8 @@ void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, con
 // scaled decode at 1/8 (mode 5): one lane per output pixel from the blocks' DC values; max_pixel_wgs = the chunk's largest
 // ceil(out_w * out_h / 256)
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
-                     const float *qmult, uint8_t *rgb, const uint32_t *img_flags, bool roi = false /* the form for pictures with a rectangle */);
+                     const float *qmult, uint8_t *rgb, const uint32_t *img_flags, bool roi = false /* the form for pictures with a rectangle */,
+                     bool out = false /* the form for pictures with an output description (mode 5 + kOutMode) */);
 #endif
 
 }   // namespace mjx

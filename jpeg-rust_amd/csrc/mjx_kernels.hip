@@ -2608,6 +2608,147 @@ __device__ __forceinline__ void store4_roi(uint8_t *out, const Roi &r, uint32_t 
     }
 }
 
+// Output formats (mjx_output; DevImage::out_*): the picture leaves as 3 x H x W or H x W x 3 elements of u8, f16 or f32, channels
+// R,G,B or B,G,R, in the batch's pool or in memory of the caller's.  Everything here is uniform over the picture -- it sits in
+// scalar registers and the branches are uniform; the kernel template is not multiplied by format.  The bytes are pack4's (the
+// conversions to u8 ran under round-toward-zero inside its one asm block, and the mode is nearest-even again here): a float element
+// is ONE fma of the byte's value -- __builtin_fmaf is the fused operation whatever -ffp-contract says --, a half element that float
+// rounded to nearest even.
+struct OutFmt {
+    uint8_t *base;                  // first element of channel 0, row 0
+    uint64_t row_pitch, plane_pitch;// elements
+    uint32_t dtype, planar, bgr;    // MJX_DTYPE_*: 0 u8, 1 f16, 2 f32
+    float scale[3], bias[3];        // by OUTPUT channel
+};
+__device__ __forceinline__ OutFmt out_fmt(const DevImage &im, uint8_t *rgb_pool)
+{
+    OutFmt f;
+    f.base = im.out_dev ? reinterpret_cast<uint8_t *>(uintptr_t(im.out_dev)) : rgb_pool + im.rgb_off;
+    f.row_pitch = im.out_row_pitch; f.plane_pitch = im.out_plane_pitch;
+    f.dtype = im.out_dtype; f.planar = im.out_planar; f.bgr = im.out_bgr;
+#pragma unroll
+    for (int c = 0; c < 3; c++) { f.scale[c] = im.out_scale[c]; f.bias[c] = im.out_bias[c]; }
+    return f;
+}
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+__device__ __forceinline__ uint32_t half_bits(float v)
+{
+    const _Float16 h = static_cast<_Float16>(v);            // v_cvt_f16_f32, nearest even
+    return uint32_t(__builtin_bit_cast(uint16_t, h));
+}
+// One element of the output: value `u` (a byte of the packed picture) as output channel oc, at element index `at` from the base.
+__device__ __forceinline__ void out_store1(const OutFmt &f, uint64_t at, uint32_t u, float sc, float bi)
+{
+    if (f.dtype == 0u) {
+        __builtin_nontemporal_store(uint8_t(u), f.base + at);
+    } else {
+        const float v = __builtin_fmaf(float(u), sc, bi);
+        if (f.dtype == 1u) __builtin_nontemporal_store(uint16_t(half_bits(v)), reinterpret_cast<uint16_t *>(f.base) + at);
+        else __builtin_nontemporal_store(v, reinterpret_cast<float *>(f.base) + at);
+    }
+}
+// A strip of npix pixels at (px, py) of the picture the pixel phase computes, as store4_roi takes it: cut at the rectangle's edges,
+// nothing written outside height rows x width pixels x 3 channels at the picture's pitches.  A whole strip whose address allows it
+// leaves in wide stores -- planar: 4 / 8 / 16 bytes per channel; interleaved: 12 / 24 / 48 contiguous bytes --, a cut or
+// misaligned one element by element.  All register indices are constants (no scratch): the cut is a predicate per pixel.
+__device__ __forceinline__ void store4_out(const OutFmt &f, const Roi &r, uint32_t px, uint32_t py, const Rgb4 &v, uint32_t npix)
+{
+    if (py < r.y || py - r.y >= r.h) return;
+    const uint32_t lo = max(px, r.x), hi = min(px + npix, r.x + r.w);
+    if (lo >= hi) return;
+    const uint32_t k0 = lo - px, k1 = hi - px;                      // the strip's pixels [k0, k1) are the rectangle's
+    const uint32_t w[3] = {v.a, v.b, v.c};
+    // the twelve bytes, by pixel and OUTPUT channel (B,G,R: the outer two change places -- a uniform select)
+    uint32_t u[4][3];
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        uint32_t t[3];
+#pragma unroll
+        for (uint32_t c = 0; c < 3; c++) t[c] = (w[(3 * k + c) >> 2] >> (((3 * k + c) & 3u) * 8u)) & 0xffu;
+        u[k][0] = f.bgr ? t[2] : t[0];
+        u[k][1] = t[1];
+        u[k][2] = f.bgr ? t[0] : t[2];
+    }
+    const uint64_t row = uint64_t(py - r.y) * f.row_pitch;
+    const bool whole = k0 == 0u && k1 == 4u;
+    if (f.planar) {
+        const uint64_t at0 = row + (lo - r.x);                      // element of the strip's first pixel kept, channel 0
+#pragma unroll
+        for (uint32_t oc = 0; oc < 3; oc++) {
+            const uint64_t at = at0 + oc * f.plane_pitch;
+            const float sc = f.scale[oc], bi = f.bias[oc];
+            if (f.dtype == 0u) {
+                uint8_t *d = f.base + at;
+                if (whole && (uintptr_t(d) & 3u) == 0) {
+                    __builtin_nontemporal_store(u[0][oc] | (u[1][oc] << 8) | (u[2][oc] << 16) | (u[3][oc] << 24), reinterpret_cast<uint32_t *>(d));
+                    continue;
+                }
+            } else if (f.dtype == 1u) {
+                uint16_t *d = reinterpret_cast<uint16_t *>(f.base) + at;
+                if (whole && (uintptr_t(d) & 3u) == 0) {
+                    u32x2_a4 h;
+                    h.x = half_bits(__builtin_fmaf(float(u[0][oc]), sc, bi)) | (half_bits(__builtin_fmaf(float(u[1][oc]), sc, bi)) << 16);
+                    h.y = half_bits(__builtin_fmaf(float(u[2][oc]), sc, bi)) | (half_bits(__builtin_fmaf(float(u[3][oc]), sc, bi)) << 16);
+                    __builtin_nontemporal_store(h, reinterpret_cast<u32x2_a4 *>(d));
+                    continue;
+                }
+            } else if (whole) {
+                f32x4_a4 q;
+                q.x = __builtin_fmaf(float(u[0][oc]), sc, bi); q.y = __builtin_fmaf(float(u[1][oc]), sc, bi);
+                q.z = __builtin_fmaf(float(u[2][oc]), sc, bi); q.w = __builtin_fmaf(float(u[3][oc]), sc, bi);
+                __builtin_nontemporal_store(q, reinterpret_cast<f32x4_a4 *>(reinterpret_cast<float *>(f.base) + at));
+                continue;
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++)
+                if (k >= k0 && k < k1) out_store1(f, at + (k - k0), u[k][oc], sc, bi);
+        }
+    } else {
+        const uint64_t at0 = row + uint64_t(lo - r.x) * 3u;         // element of the strip's first pixel kept, channel 0
+        if (whole && f.dtype == 0u && (uintptr_t(f.base + at0) & 3u) == 0) {
+            // (dword stores that the compiler fuses, as store_rgb4: a three-vector would be stored as four words)
+            uint32_t *d = reinterpret_cast<uint32_t *>(f.base + at0);
+            __builtin_nontemporal_store(u[0][0] | (u[0][1] << 8) | (u[0][2] << 16) | (u[1][0] << 24), d);
+            __builtin_nontemporal_store(u[1][1] | (u[1][2] << 8) | (u[2][0] << 16) | (u[2][1] << 24), d + 1);
+            __builtin_nontemporal_store(u[2][2] | (u[3][0] << 8) | (u[3][1] << 16) | (u[3][2] << 24), d + 2);
+            return;
+        }
+        if (whole && f.dtype == 1u && (uintptr_t(reinterpret_cast<uint16_t *>(f.base) + at0) & 3u) == 0) {
+            uint32_t h[6];
+#pragma unroll
+            for (uint32_t e = 0; e < 6; e++) {
+                const uint32_t a = 2 * e, b = 2 * e + 1;
+                h[e] = half_bits(__builtin_fmaf(float(u[a / 3][a % 3]), f.scale[a % 3], f.bias[a % 3])) |
+                       (half_bits(__builtin_fmaf(float(u[b / 3][b % 3]), f.scale[b % 3], f.bias[b % 3])) << 16);
+            }
+            uint32_t *d = reinterpret_cast<uint32_t *>(reinterpret_cast<uint16_t *>(f.base) + at0);
+#pragma unroll
+            for (uint32_t e = 0; e < 6; e++) __builtin_nontemporal_store(h[e], d + e);
+            return;
+        }
+        if (whole && f.dtype == 2u) {
+            f32x4_a4 *d = reinterpret_cast<f32x4_a4 *>(reinterpret_cast<float *>(f.base) + at0);
+#pragma unroll
+            for (uint32_t e = 0; e < 3; e++) {
+                f32x4_a4 q;
+                q.x = __builtin_fmaf(float(u[(4 * e) / 3][(4 * e) % 3]), f.scale[(4 * e) % 3], f.bias[(4 * e) % 3]);
+                q.y = __builtin_fmaf(float(u[(4 * e + 1) / 3][(4 * e + 1) % 3]), f.scale[(4 * e + 1) % 3], f.bias[(4 * e + 1) % 3]);
+                q.z = __builtin_fmaf(float(u[(4 * e + 2) / 3][(4 * e + 2) % 3]), f.scale[(4 * e + 2) % 3], f.bias[(4 * e + 2) % 3]);
+                q.w = __builtin_fmaf(float(u[(4 * e + 3) / 3][(4 * e + 3) % 3]), f.scale[(4 * e + 3) % 3], f.bias[(4 * e + 3) % 3]);
+                __builtin_nontemporal_store(q, d + e);
+            }
+            return;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++)
+            if (k >= k0 && k < k1) {
+#pragma unroll
+                for (uint32_t oc = 0; oc < 3; oc++) out_store1(f, at0 + uint64_t(k - k0) * 3u + oc, u[k][oc], f.scale[oc], f.bias[oc]);
+            }
+    }
+}
+
 // ---- stage B pipeline pieces ---------------------------------------------------------------------
 // A workgroup walks kTilesPerWg consecutive tiles of one image.  While it transforms tile t it already holds the loads
 // of tile t+1 in flight (stream offsets, up to kPrefetch entries per lane, the lane's DC), so the HBM round trips of a
@@ -3170,13 +3311,54 @@ __device__ __forceinline__ void pixels_420(uint32_t width, uint32_t height, uint
     }
 }
 
+// Phase 3 for 4:2:0 with an output description (k_idct_color<kOutMode + 1, ...>): pixels_420's ROI form -- the same lane -> strip mapping,
+// the same reads and the same packed additions, so the bytes are the packed picture's -- with ONE store site: the rows of the
+// lane's strip are walked by a loop that is not unrolled (store4_out is a few hundred instructions of uniform branches; eight
+// copies of it cost the kernel its third wave per SIMD), each row reading its own samples.
+__device__ __forceinline__ void pixels_420_out(uint32_t width, uint32_t height, uint32_t mcux, const float *tile, uint32_t m0,
+                                               uint32_t nm, const Roi &roi, const OutFmt &of)
+{
+    const uint32_t tid = threadIdx.x;
+    const uint32_t q = tid % (kTile420 * 4), t = q >> 2, sx = q & 3;
+    if (t >= nm) return;
+    const uint32_t m = m0 + t;
+    const uint32_t mx = m % mcux, my = m / mcux;
+    const uint32_t px = mx * 16 + sx * 4;
+    if (px >= width) return;
+    const uint32_t npix = min(4u, width - px);
+    if (px + 4u <= roi.x || px >= roi.x + roi.w) return;
+    const float *ybase = tile + (t * 6 + (sx >> 1)) * kPixStride + (sx & 1) * 4;
+    const float *cbase = tile + (t * 6 + 4) * kPixStride + sx * 2;
+#pragma unroll 1
+    for (uint32_t i = 0; i < 8; i++) {
+        const uint32_t rp = tid / (kTile420 * 4) + 2 * (i >> 1);                 // row pair 0..7 inside the MCU, then its two rows
+        const uint32_t py = my * 16 + rp * 2 + (i & 1u);
+        if (py >= height) break;
+        if (py < roi.y || py >= roi.y + roi.h) continue;
+        const f32x4 y = *reinterpret_cast<const f32x4 *>(ybase + (rp >> 2) * 2 * kPixStride + ((rp * 2) & 7) * 8 + (i & 1u) * 8);
+        const f32x2 cb = *reinterpret_cast<const f32x2 *>(cbase + rp * 8);
+        const f32x2 cr = *reinterpret_cast<const f32x2 *>(cbase + kPixStride + rp * 8);
+        const ChromaTerms c0 = chroma_terms(cb.x, cr.x), c1 = chroma_terms(cb.y, cr.y);
+        const float_pair t0rg = {c0.r, c0.g}, t0b = {c0.b, c0.b}, t1rg = {c1.r, c1.g}, t1b = {c1.b, c1.b};
+        const float_pair y01 = __builtin_shufflevector(y, y, 0, 1), y23 = __builtin_shufflevector(y, y, 2, 3);
+        const float_pair r01 = pk_add_lo(y01, t0rg), g01 = pk_add_hi(y01, t0rg), b01 = pk_add_lo(y01, t0b);
+        const float_pair r23 = pk_add_lo(y23, t1rg), g23 = pk_add_hi(y23, t1rg), b23 = pk_add_lo(y23, t1b);
+        Rgb p[4];
+        p[0] = Rgb{r01.x, g01.x, b01.x}; p[1] = Rgb{r01.y, g01.y, b01.y};
+        p[2] = Rgb{r23.x, g23.x, b23.x}; p[3] = Rgb{r23.y, g23.y, b23.y};
+        store4_out(of, roi, px, py, pack4(p), npix);
+    }
+}
+
 // Phase 3 for any sampling layout: 4-pixel strips; lane -> (MCU t, strip sx) is fixed, rows advance by 256/R per step.
 // INTERIOR: every MCU of the tile lies in one MCU row and fully inside the picture, rows are 4-byte aligned -- no bounds, plain 12-byte stores
 // ROI: the picture written is the rectangle `roi` of this one (as pixels_420)
-template <bool INTERIOR, bool COLOUR, bool ROI = false>
+// OUT: (a ROI form) the rectangle leaves in the picture's output format (store4_out)
+template <bool INTERIOR, bool COLOUR, bool ROI = false, bool OUT = false>
 __device__ __forceinline__ void pixels_generic_t(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm,
-                                                 uint8_t *out_img, bool aligned, const Roi &roi = Roi{})
+                                                 uint8_t *out_img, bool aligned, const Roi &roi = Roi{}, const OutFmt *of = nullptr)
 {
+    static_assert(!OUT || ROI, "the output formats are built on the cropped forms");
     static_assert(!ROI || !INTERIOR, "strips of a cropped picture are cut at the rectangle's edges");
     const uint32_t tid = threadIdx.x, bpm = g.bpm;
     const uint32_t lstrips = g.hmax == 2 ? 2u : 1u;          // log2 of the 4-pixel strips per MCU row (2*hmax)
@@ -3208,7 +3390,8 @@ __device__ __forceinline__ void pixels_generic_t(const GenShape &g, const float 
 #pragma unroll
             for (int k = 0; k < 4; k++) p[k].r = p[k].g = p[k].b = yv[k];                          // decoder.rs:318-325 (+128 is in the samples)
         }
-        if (ROI) store4_roi(out_img, roi, px, my * rows + r, pack4(p), npix);
+        if (OUT) store4_out(*of, roi, px, my * rows + r, pack4(p), npix);
+        else if (ROI) store4_roi(out_img, roi, px, my * rows + r, pack4(p), npix);
         else if (INTERIOR) store_rgb4(dst, pack4(p));
         else store4(dst, pack4(p), aligned, npix);
     }
@@ -3218,6 +3401,11 @@ __device__ __forceinline__ void pixels_generic_roi(const GenShape &g, const floa
 {
     if (g.ncomp == 3) pixels_generic_t<false, true, true>(g, tile, m0, nm, out_img, aligned, roi);
     else pixels_generic_t<false, false, true>(g, tile, m0, nm, out_img, aligned, roi);
+}
+__device__ __forceinline__ void pixels_generic_out(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm, const Roi &roi, const OutFmt &of)
+{
+    if (g.ncomp == 3) pixels_generic_t<false, true, true, true>(g, tile, m0, nm, nullptr, false, roi, &of);
+    else pixels_generic_t<false, false, true, true>(g, tile, m0, nm, nullptr, false, roi, &of);
 }
 __device__ __forceinline__ void pixels_generic(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm,
                                                uint8_t *out_img, bool aligned)
@@ -3383,10 +3571,12 @@ __device__ __forceinline__ void idct_scaled_inplace(float *blk)
 // pixels of one patch row (box replication of the chroma samples at the output resolution, as pixels_generic does at scale 1).
 // Output rows need not be 4-byte aligned; pixels outside out_w x out_h (g.width, g.height) are not written.
 // ROI: the picture written is the rectangle `roi` of this one (as pixels_420)
-template <uint32_t N, bool ROI = false>
+// OUT: (a ROI form) the rectangle leaves in the picture's output format (store4_out)
+template <uint32_t N, bool ROI = false, bool OUT = false>
 __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm, uint8_t *out_img, bool aligned,
-                                              const Roi &roi = Roi{})
+                                              const Roi &roi = Roi{}, const OutFmt *of = nullptr)
 {
+    static_assert(!OUT || ROI, "the output formats are built on the cropped forms");
     const uint32_t PW = N * g.hmax, PH = N * g.vmax, SW = PW < 4u ? PW : 4u;
     const uint32_t lspr = PW / SW == 2u ? 1u : 0u, lph = 31u - __builtin_clz(PH);
     const uint32_t items = nm << (lph + lspr);
@@ -3415,7 +3605,8 @@ __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *ti
             if (g.ncomp == 3) p[k] = ycc_to_rgb(s[0][k], chroma_terms(s[1][k], s[2][k]));
             else p[k].r = p[k].g = p[k].b = s[0][k];
         }
-        if (ROI) store4_roi(out_img, roi, X, Y, pack4(p), npix);
+        if (OUT) store4_out(*of, roi, X, Y, pack4(p), npix);
+        else if (ROI) store4_roi(out_img, roi, X, Y, pack4(p), npix);
         else store4(out_img + (size_t(Y) * g.width + X) * 3, pack4(p), al, npix);
     }
 }
@@ -3437,6 +3628,8 @@ __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *ti
 //        load, no scatter, no transform and no barrier, and the prefetch chain runs from one wanted tile to the next.  The planar
 //        form (its segment lists are prepared two tiles ahead in a ring of three) walks every tile of the row band.  Phase 3 writes
 //        the rectangle's pixels only (store4_roi); the 4:2:0 form takes plain reads there, so `clean` stays false.
+//   OUT  output formats (MODE_ = MODE + kOutMode, the mode of a picture with an output description): the ROI form -- a picture without a
+//        rectangle is its own whole rectangle --, phase 3 writing the picture's format (store4_out, DevImage::out_*)
 template <int MODE_, int PF, int SRC>
 __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__ images,
                                                      const uint32_t *__restrict__ entries,
@@ -3445,8 +3638,9 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                                                      uint8_t *__restrict__ rgb, unsigned long long *__restrict__ planes,
                                                      const uint32_t *__restrict__ img_flags, uint32_t tiles_per_wg)
 {
+    constexpr bool OUT = MODE_ >= int(kOutMode);              // output formats: the cropped form, the picture its own whole rectangle without one
     constexpr bool ROI = MODE_ >= int(kRoiMode);
-    constexpr int MODE = MODE_ - (ROI ? int(kRoiMode) : 0);
+    constexpr int MODE = MODE_ - (OUT ? int(kOutMode) : ROI ? int(kRoiMode) : 0);
     static_assert(!ROI || MODE != 2, "REF_COMPAT has no rectangles");
     // (its own symbol: dynamic LDS arrays of one name share their alignment, and the entropy kernels ask for 2 KiB)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_px[];
@@ -3483,6 +3677,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
         roi = Roi{im.roi_x, im.roi_y, im.roi_w, im.roi_h};
         roi_r0 = im.roi_mr0; roi_r1 = im.roi_mr1; roi_c0 = im.roi_mc0; roi_c1 = im.roi_mc1;
     }
+    OutFmt ofmt{};
+    if constexpr (OUT) ofmt = out_fmt(im, rgb);
     constexpr bool SKIP = ROI && SRC != 2;
     auto wanted_from = [&](uint32_t t) {          // the first tile at or behind t that the rectangle wants (uniform)
         if constexpr (SKIP)
@@ -3725,7 +3921,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             const bool interior = whole && aligned && (my1 + 1) * 16 <= height && (mcux * 16 <= width || mx0 + T < mcux);
             if constexpr (ROI) {
                 // (plain reads: a cropped tile's pixel phase does not read -- so does not clear -- the whole tile; `clean` stays false)
-                pixels_420<false, true, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned, roi);
+                if constexpr (OUT) pixels_420_out(width, height, mcux, tile_f, m0, nm, roi, ofmt);
+                else pixels_420<false, true, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned, roi);
             } else {
                 if (interior) pixels_420<true, false>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
                 else if (whole) pixels_420<true, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
@@ -3735,9 +3932,11 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
         } else if (MODE == 2) {
             place_ref(im, tile_f, tile * tile_blocks, nblk, planes);
         } else if constexpr (SCALED) {
-            pixels_scaled<scaled_n<MODE>(), ROI>(gshape, tile_f, m0, nm, out_img, aligned, roi);
+            if constexpr (OUT) pixels_scaled<scaled_n<MODE>(), true, true>(gshape, tile_f, m0, nm, nullptr, false, roi, &ofmt);
+            else pixels_scaled<scaled_n<MODE>(), ROI>(gshape, tile_f, m0, nm, out_img, aligned, roi);
         } else {
-            if constexpr (ROI) pixels_generic_roi(gshape, tile_f, m0, nm, out_img, aligned, roi);
+            if constexpr (OUT) pixels_generic_out(gshape, tile_f, m0, nm, roi, ofmt);
+            else if constexpr (ROI) pixels_generic_roi(gshape, tile_f, m0, nm, out_img, aligned, roi);
             else pixels_generic(gshape, tile_f, m0, nm, out_img, aligned);
         }
         MJX_SB(6);
@@ -3757,13 +3956,14 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
 // and pixel (X, Y) takes block (X h / hmax, Y v / vmax) of each component's plane (box replication, as pixels_scaled).
 // Multi-scan pictures read without the gather keep their DC values in their scans' regions (planar_dc_slot, as stage B finds them).
 // ROI (k_dc_color_roi, mode 5 + kRoiMode): one lane per pixel of the rectangle.
-template <bool ROI>
+// OUT (k_dc_color_out, mode 5 + kOutMode): the ROI form writing the picture's output format, one element at a time.
+template <bool ROI, bool OUT = false>
 __device__ __forceinline__ void dc_color_body(const DevImage *__restrict__ images, const int32_t *__restrict__ dcbuf,
                                               const float *__restrict__ qmult, uint8_t *__restrict__ rgb,
                                               const uint32_t *__restrict__ img_flags)
 {
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || im.mode != 5u + (ROI ? kRoiMode : 0u) || img_flags[im.status_idx]) return;
+    if (!im.valid || im.mode != 5u + (OUT ? kOutMode : ROI ? kRoiMode : 0u) || img_flags[im.status_idx]) return;
     const uint32_t ow = ROI ? im.roi_w : im.out_w, oh = ROI ? im.roi_h : im.out_h;
     const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
     if (i >= uint64_t(ow) * oh) return;
@@ -3791,6 +3991,18 @@ __device__ __forceinline__ void dc_color_body(const DevImage *__restrict__ image
     if (im.ncomp == 3) p = ycc_to_rgb(s[0], chroma_terms(s[1], s[2]));
     else p.r = p.g = p.b = s[0];
     const uint32_t word = pack_u8(p.b, 2, pack_u8(p.g, 1, pack_u8(p.r, 0, 0)));
+    if constexpr (OUT) {
+        const OutFmt f = out_fmt(im, rgb);
+        const uint32_t col = X - im.roi_x;
+        const uint64_t row = uint64_t(Y - im.roi_y) * f.row_pitch;
+#pragma unroll
+        for (uint32_t oc = 0; oc < 3; oc++) {
+            const uint32_t u = (word >> ((f.bgr ? 2u - oc : oc) * 8u)) & 0xffu;
+            const uint64_t at = f.planar ? row + oc * f.plane_pitch + col : row + uint64_t(col) * 3u + oc;
+            out_store1(f, at, u, f.scale[oc], f.bias[oc]);
+        }
+        return;
+    }
     uint8_t *dst = rgb + im.rgb_off + i * 3;
     dst[0] = uint8_t(word); dst[1] = uint8_t(word >> 8); dst[2] = uint8_t(word >> 16);
 }
@@ -3805,6 +4017,12 @@ extern "C" __global__ __launch_bounds__(256) void k_dc_color_roi(const DevImage 
                                                                   const uint32_t *__restrict__ img_flags)
 {
     dc_color_body<true>(images, dcbuf, qmult, rgb, img_flags);
+}
+extern "C" __global__ __launch_bounds__(256) void k_dc_color_out(const DevImage *__restrict__ images, const int32_t *__restrict__ dcbuf,
+                                                                  const float *__restrict__ qmult, uint8_t *__restrict__ rgb,
+                                                                  const uint32_t *__restrict__ img_flags)
+{
+    dc_color_body<true, true>(images, dcbuf, qmult, rgb, img_flags);
 }
 
 // ---- verification helper: byte-wise comparison of decoded pictures on the device ------------------------------
@@ -3891,7 +4109,9 @@ int configure_kernels(size_t huff_lds, size_t idct_lds)
                              reinterpret_cast<const void *>(k_idct_color<3, 8, 2>), reinterpret_cast<const void *>(k_idct_color<4, kPrefetch, 0>),
                              reinterpret_cast<const void *>(k_idct_color<4, 8, 1>), reinterpret_cast<const void *>(k_idct_color<4, 8, 2>),
 #define MJX_ROI_FORMS(M) reinterpret_cast<const void *>(k_idct_color<kRoiMode + M, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<kRoiMode + M, 8, 1>), reinterpret_cast<const void *>(k_idct_color<kRoiMode + M, 8, 2>)
-                             MJX_ROI_FORMS(0), MJX_ROI_FORMS(1), MJX_ROI_FORMS(3), MJX_ROI_FORMS(4)};
+                             MJX_ROI_FORMS(0), MJX_ROI_FORMS(1), MJX_ROI_FORMS(3), MJX_ROI_FORMS(4),
+                             MJX_ROI_FORMS(kOutMode - kRoiMode + 0), MJX_ROI_FORMS(kOutMode - kRoiMode + 1),        // (the output formats' forms, kOutMode + m)
+                             MJX_ROI_FORMS(kOutMode - kRoiMode + 3), MJX_ROI_FORMS(kOutMode - kRoiMode + 4)};
 #undef MJX_ROI_FORMS
         for (const void *f : fns)
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(idct_lds));
@@ -4083,16 +4303,22 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
     }
 #undef MJX_IDCT
     // region-of-interest decode: pictures with a rectangle (mode + kRoiMode) take the forms that skip tiles and crop
-#define MJX_IDCT_ROI(M)                                                                                                                   \
-    if (mode_mask & (1u << (kRoiMode + M))) {                                                                                             \
-        if (layout_mask & 1u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M, kPrefetch, 0>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw); \
-        if (layout_mask & 2u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M, 8, 1>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw);         \
-        if (layout_mask & 4u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M, 8, 2>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw);         \
+    // ... and pictures with an output description (mode + kOutMode) the forms that write it
+#define MJX_IDCT_ROI(M_)                                                                                                                  \
+    if (mode_mask & (1u << (kRoiMode + M_))) {                                                                                            \
+        constexpr int M = (M_) % int(kRoiMode);                                                                                           \
+        if (layout_mask & 1u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M_, kPrefetch, 0>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw); \
+        if (layout_mask & 2u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M_, 8, 1>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw);         \
+        if (layout_mask & 4u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M_, 8, 2>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw);         \
     }
     MJX_IDCT_ROI(0)
     MJX_IDCT_ROI(1)
     MJX_IDCT_ROI(3)
     MJX_IDCT_ROI(4)
+    MJX_IDCT_ROI(kOutMode - kRoiMode + 0)
+    MJX_IDCT_ROI(kOutMode - kRoiMode + 1)
+    MJX_IDCT_ROI(kOutMode - kRoiMode + 3)
+    MJX_IDCT_ROI(kOutMode - kRoiMode + 4)
 #undef MJX_IDCT_ROI
 }
 
@@ -4123,10 +4349,11 @@ void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, con
 }
 
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
-                     const float *qmult, uint8_t *rgb, const uint32_t *img_flags, bool roi)
+                     const float *qmult, uint8_t *rgb, const uint32_t *img_flags, bool roi, bool out)
 {
     if (max_pixel_wgs == 0 || nimg == 0) return;
-    if (roi) hipLaunchKernelGGL(k_dc_color_roi, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
+    if (out) hipLaunchKernelGGL(k_dc_color_out, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
+    else if (roi) hipLaunchKernelGGL(k_dc_color_roi, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
     else hipLaunchKernelGGL(k_dc_color, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
 }
 

@@ -457,6 +457,65 @@ mjx_opts opts_for_input(const mjx_opts &opts, size_t n, size_t i)
     return o;
 }
 
+bool output_fits(const mjx_output *out, size_t n)
+{
+    if (!out) return true;
+    if (!out->dst) return out->n_dst == 0;
+    return out->n_dst == n;
+}
+
+int plan_output(ImagePlan &p, const mjx_output *out, size_t i)
+{
+    p.out_on = false;
+    p.out_dev = 0;
+    p.out_bytes = uint64_t(p.roi_w) * p.roi_h * 3;
+    if (!out || p.status != MJX_OK) return p.status;
+    auto fail = [&]() { p.status = MJX_ERR_INVALID_ARG; return p.status; };
+    if (out->dtype > MJX_DTYPE_F32 || p.layout == MJX_LAYOUT_REF_COMPAT) return fail();
+    const uint64_t esz = out->dtype == MJX_DTYPE_U8 ? 1u : out->dtype == MJX_DTYPE_F16 ? 2u : 4u;
+    const bool planar = out->planar != 0;
+    for (int c = 0; c < 3; c++) {
+        if (out->dtype != MJX_DTYPE_U8 && !(std::isfinite(out->scale[c]) && std::isfinite(out->bias[c]))) return fail();
+        p.out_scale[c] = out->dtype == MJX_DTYPE_U8 ? 1.f : out->scale[c];
+        p.out_bias[c] = out->dtype == MJX_DTYPE_U8 ? 0.f : out->bias[c];
+    }
+    const uint64_t w = p.roi_w, h = p.roi_h, row_min = planar ? w : 3 * w;
+    p.out_row_pitch = row_min;
+    p.out_plane_pitch = planar ? h * w : 0;
+    if (out->dst) {
+        const mjx_dst &d = out->dst[i];
+        if (d.width != p.roi_w || d.height != p.roi_h || d.row_pitch < row_min) return fail();
+        if (d.row_pitch > (uint64_t(1) << 40) || d.plane_pitch > (uint64_t(1) << 56)) return fail();      // (no overflow below)
+        if (planar && d.plane_pitch < h * d.row_pitch) return fail();
+        if (!d.dev || (uint64_t(uintptr_t(d.dev)) & (esz - 1))) return fail();
+        p.out_dev = uint64_t(uintptr_t(d.dev));
+        p.out_row_pitch = d.row_pitch;
+        p.out_plane_pitch = planar ? d.plane_pitch : 0;
+    }
+    // the last element: channel 2's last row's last pixel (planar) or the last row's last channel (interleaved)
+    p.out_bytes = ((planar ? 2 * p.out_plane_pitch : 0) + (h - 1) * p.out_row_pitch + row_min) * esz;
+    p.out_on = true;
+    p.out_dtype = out->dtype;
+    p.out_planar = planar ? 1u : 0u;
+    p.out_bgr = out->bgr ? 1u : 0u;
+    return p.status;
+}
+
+int plan_output_of_input(std::vector<ImagePlan> &plans, const mjx_output *out, size_t i)
+{
+    ImagePlan &p = plans.back();
+    const bool was_ok = p.status == MJX_OK;
+    const size_t nparts = p.role == 2 ? p.nparts : 0;
+    const int rc = plan_output(p, out, i);
+    if (was_ok && rc != MJX_OK && nparts && plans.size() > nparts) {       // one status for the whole picture, as plan_input: its scans go
+        ImagePlan pic;
+        pic.status = rc;
+        plans.resize(plans.size() - 1 - nparts);
+        plans.push_back(pic);
+    }
+    return rc;
+}
+
 void plan_input(const mjx_scan_desc &d, const mjx_opts &opts, std::vector<ImagePlan> &out)
 {
     if (d.n_parts == 0) {

@@ -47,6 +47,13 @@ struct ImagePlan {
     bool cropped = false;
     uint32_t roi_x = 0, roi_y = 0, roi_w = 0, roi_h = 0;
     uint32_t roi_mr0 = 0, roi_mr1 = 0, roi_mc0 = 0, roi_mc1 = 0;
+    // output formats (mjx_output, plan_output): what the picture leaves as -- roi_w x roi_h elements per channel at these pitches (in
+    // elements), in caller-owned memory at out_dev or, out_dev == 0, in the batch's pool; out_bytes: the span from the first element's
+    // first byte to the last element's last.  Without a description (out_on false): packed R,G,B bytes, out_bytes = roi_w roi_h 3.
+    bool out_on = false;
+    uint32_t out_dtype = 0, out_planar = 0, out_bgr = 0;
+    float out_scale[3] = {1.f, 1.f, 1.f}, out_bias[3] = {0.f, 0.f, 0.f};
+    uint64_t out_dev = 0, out_row_pitch = 0, out_plane_pitch = 0, out_bytes = 0;
     const uint8_t *scan = nullptr;
     size_t scan_len = 0;
     // The scan still holds FF00 pairs (and RSTn markers): it is de-stuffed on the device at upload (k_destuff_*), scan_len is
@@ -97,6 +104,16 @@ void plan_input(const mjx_scan_desc &d, const mjx_opts &opts, std::vector<ImageP
 // false: opts.rois / opts.n_rois do not fit a call of n inputs (MJX_ERR_INVALID_ARG for the call).
 bool rois_fit(const mjx_opts &opts, size_t n);
 mjx_opts opts_for_input(const mjx_opts &opts, size_t n, size_t i);
+
+// Output formats: does out->dst / n_dst fit a call of n inputs (false: MJX_ERR_INVALID_ARG for the call)?  And the one place that
+// knows the rules of a picture's output: plan_output gives the planned picture `p` (the last plan of input i) its format and
+// destination -- the pitches of a dense library-owned picture, or dst[i]'s after checking them -- or fails it with
+// MJX_ERR_INVALID_ARG.  out == nullptr: the packed picture.  mjx_output_layout reports what it finds here.
+bool output_fits(const mjx_output *out, size_t n);
+int plan_output(ImagePlan &p, const mjx_output *out, size_t i);
+// ... applied to the plans of one input as plan_input left them (the last is the picture's): a multi-scan picture that is refused
+// takes its scans' plans with it, so that nothing of the file is uploaded or decoded.
+int plan_output_of_input(std::vector<ImagePlan> &plans, const mjx_output *out, size_t i);
 
 // mjx_parse.cpp: mjx_parse with caller-lent storage for the de-stuffed scan (see there)
 int parse_into(const uint8_t *jpeg, size_t len, const mjx_opts *opts, mjx_scan_desc *out, uint8_t *storage, size_t cap);
