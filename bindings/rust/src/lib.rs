@@ -57,6 +57,16 @@ pub struct mjx_output {
     pub n_dst: u32,
 }
 
+/// Resize on the device: every picture of a call leaves at `width` x `height` (include/mjx.h: mjx_resize).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mjx_resize {
+    pub width: u32,
+    pub height: u32,
+    pub antialias: u8,
+    pub auto_scale: u8,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct mjx_opts {
@@ -169,6 +179,17 @@ extern "C" {
     pub fn mjx_batch_copy_output(b: *mut mjx_batch, i: usize, host: *mut c_void, cap_bytes: usize) -> c_int;
     pub fn mjx_decode_batch_out(ctx: *mut mjx_ctx, jpegs: *const *const u8, lens: *const usize, n: usize, opts: *const mjx_opts,
                                 threads: c_uint, out: *const mjx_output, status: *mut c_int, b: *mut *mut mjx_batch) -> c_int;
+    pub fn mjx_batch_create_resize(ctx: *mut mjx_ctx, descs: *const mjx_scan_desc, n: usize, opts: *const mjx_opts, out: *const mjx_output,
+                                   rs: *const mjx_resize, b: *mut *mut mjx_batch, status: *mut c_int) -> c_int;
+    pub fn mjx_decode_batch_resize(ctx: *mut mjx_ctx, jpegs: *const *const u8, lens: *const usize, n: usize, opts: *const mjx_opts,
+                                   threads: c_uint, out: *const mjx_output, rs: *const mjx_resize, status: *mut c_int,
+                                   b: *mut *mut mjx_batch) -> c_int;
+    pub fn mjx_resize_plan(desc: *const mjx_scan_desc, opts: *const mjx_opts, rs: *const mjx_resize, i: usize, scale_denom: *mut u8,
+                           rect: *mut mjx_rect, taps_x: *mut u32, taps_y: *mut u32) -> c_int;
+    pub fn mjx_resize_weights(n_in: u32, n_out: u32, antialias: c_int, x: u32, first: *mut u32, weights: *mut f32, cap: usize,
+                              count: *mut usize) -> c_int;
+    pub fn mjx_batch_image_scale(b: *const mjx_batch, i: usize, scale_denom: *mut u8) -> c_int;
+    pub fn mjx_batch_resize_rect(b: *const mjx_batch, i: usize, rect: *mut mjx_rect) -> c_int;
     pub fn mjx_batch_tile(ctx: *mut mjx_ctx, src: *const mjx_batch, times: usize, out: *mut *mut mjx_batch) -> c_int;
     pub fn mjx_batch_free(b: *mut mjx_batch);
     pub fn mjx_batch_decode(b: *mut mjx_batch, stages: c_uint) -> c_int;

@@ -128,6 +128,38 @@ typedef struct mjx_output {
  * Not built: mjx_decode, the pool (mjx_pool_decode_batch: the slot -- so the device -- of a file is not known to the caller before the
  * deal) and the CLI keep packed RGB. */
 
+/* ---- resize on the device: every picture of a call leaves at one target size -------------------------------------------
+ * With a resize description (mjx_batch_create_resize, mjx_decode_batch_resize) picture i is decoded as a packed picture at a
+ * scale s and a rectangle R (the intermediate: byte for byte what a plain call with scale_denom = s, rois[i] = R writes; it
+ * lives in the batch's own memory) and a further kernel resamples it to height x width with the separable triangle filter of
+ * torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=...): "crop, then resize", taps never reach
+ * outside R.  Per axis (n_in -> n_out, r = n_in / n_out, fs = antialias ? max(1, r) : 1), for output coordinate X:
+ *   c = (X + 0.5) r,  lo = max(0, floor(c - fs + 0.5)),  hi = min(n_in, floor(c + fs + 0.5)),
+ *   w_j = max(0, 1 - |j + 0.5 - c| / fs) for j in [lo, hi), divided by their sum
+ * (coordinates in exact integer arithmetic: (2X+1) n_in divided by 2 n_out, quotient and remainder).  The resized sample
+ * v = sum_y sum_x wy wx I[y][x][ch] is computed in float32 and is not rounded between the two passes.  The element written:
+ * U8 rint (half to even) of v clamped to [0, 255]; F32 fmaf(v, scale[c], bias[c]) on the unrounded v; F16 that float rounded to
+ * nearest even; c the OUTPUT channel.  bgr, planar, pitches and caller-owned dst are mjx_output's, at the target size; nothing is
+ * written outside height rows x width elements x 3 channels.
+ * Scale and rectangle.  auto_scale = 0: s = opts->scale_denom and R = rois[i] (or the whole picture), as in any call.
+ * auto_scale = 1: opts->scale_denom must be 0 or 1 and rois[i] = (x, y, w, h) is in FULL-SIZE coordinates; the library picks the
+ * largest s in {1, 2, 4, 8} for which R_s = (floor(x/s), floor(y/s), ceil((x+w)/s) - floor(x/s), ceil((y+h)/s) - floor(y/s)) is at
+ * least width wide and height high (s = 1 when even that is smaller: the DCT scale never forces an upsample) and R = R_s: a
+ * rectangle that is not aligned to s is rounded OUTWARD, by less than s full-size pixels per side.
+ * Per picture, MJX_ERR_INVALID_ARG (nothing is written for it, the others are unaffected): width or height 0 (or above 2^24);
+ * MJX_LAYOUT_REF_COMPAT; auto_scale with scale_denom > 1; dst[i].width / height other than the target; and mjx_output's and the
+ * rectangle's own rules.
+ * A resized batch: mjx_batch_image_info and mjx_batch_output_info speak of the target picture, mjx_batch_image_roi gives R's
+ * origin and the picture's size at the chosen scale (mjx_batch_resize_rect: all of R), mjx_batch_image_scale the scale,
+ * mjx_batch_bytes' rgb_bytes counts the bytes written; mjx_batch_copy_output serves library-owned output; mjx_batch_copy_rgb and
+ * mjx_batch_compare_rgb behave as for any batch with an output description; mjx_batch_tile carries the resize along
+ * (library-owned output only).  Not built: mjx_decode, the pool and the CLI keep packed RGB. */
+typedef struct mjx_resize {
+    uint32_t width, height;   /* the target size of every picture of the call */
+    uint8_t antialias;        /* 1: the filter widens with the ratio when shrinking (fs = max(1, r)); 0: two taps */
+    uint8_t auto_scale;       /* 1: the library picks the DCT-domain scale per picture; rois are in full-size coordinates */
+} mjx_resize;
+
 /* ---- inner seam: what jpeg/mod.rs:388-415 hands to JPEGDecoder -------------------------- */
 typedef struct mjx_comp {          /* decoder.rs:39-52 JPEGDecoderComponentFields */
     uint8_t id, h, v, tq, td, ta;
@@ -253,6 +285,21 @@ int mjx_batch_output_info(const mjx_batch *b, size_t i, mjx_dst *layout, uint8_t
  * caller-owned destination or a batch without an output description: MJX_ERR_INVALID_ARG. */
 int mjx_batch_copy_output(mjx_batch *b, size_t i, void *host, size_t cap_bytes);
 
+/* mjx_batch_create_out with a resize description (above); rs == NULL: mjx_batch_create_out itself.  out == NULL with a resize:
+ * interleaved u8 R,G,B, library-owned. */
+int mjx_batch_create_resize(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_output *out,
+                            const mjx_resize *rs, mjx_batch **b, int *status);
+/* Host-only, from the planner itself, in the spirit of mjx_plan_tiles: the scale and the rectangle (at that scale) picture `desc`
+ * is decoded at as input i of a call with these options (rois[i], or rois[0] when n_rois <= 1) and this resize, and the largest
+ * number of taps of an output column / row (what the resize kernel's loops run to).  Returns the picture's status. */
+int mjx_resize_plan(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_resize *rs, size_t i, uint8_t *scale_denom,
+                    mjx_rect *rect, uint32_t *taps_x, uint32_t *taps_y);
+/* Host-only: the filter of one output coordinate X of an axis n_in -> n_out -- the routine the resize kernel itself runs
+ * (resize_axis / resize_weight, mjx_kernels.h).  *first: the first tap's input index, weights[0 .. *count): the normalised weights
+ * (at most cap are written; *count is the window's length either way).  n_in, n_out in 1 .. 2^24, X < n_out. */
+int mjx_resize_weights(uint32_t n_in, uint32_t n_out, int antialias, uint32_t X, uint32_t *first, float *weights, size_t cap,
+                       size_t *count);
+
 /* Replicate the uploaded images `times`x on the device (image i*n+k is a byte copy of image k): builds the
  * large synthetic batches of BASELINE.json configs 4/5 from n unique images without re-uploading.  The copies keep their
  * source's scale and rectangle. */
@@ -273,6 +320,11 @@ int mjx_batch_image_info(const mjx_batch *b, size_t i, uint32_t *width, uint32_t
 /* region-of-interest decode: the origin of image i's rectangle and the size of the uncropped picture (out_w x out_h at the
  * batch's scale); without a rectangle 0, 0 and the picture's own size */
 int mjx_batch_image_roi(const mjx_batch *b, size_t i, uint32_t *x, uint32_t *y, uint32_t *full_width, uint32_t *full_height);
+/* the DCT-domain scale picture i was decoded at (1, 2, 4 or 8): the call's, or the one auto_scale picked */
+int mjx_batch_image_scale(const mjx_batch *b, size_t i, uint8_t *scale_denom);
+/* a resized batch: the rectangle R picture i's intermediate covers, in the coordinates of the picture at its scale
+ * (mjx_batch_image_roi: that picture's size); any other batch: the picture's own rectangle */
+int mjx_batch_resize_rect(const mjx_batch *b, size_t i, mjx_rect *rect);
 /* device pointer + byte size of image i's packed RGB (valid until mjx_batch_free) */
 int mjx_batch_rgb_device(const mjx_batch *b, size_t i, void **dev_ptr, size_t *bytes);
 /* copy image i's RGB to host memory (width*height*3 bytes) */
@@ -319,7 +371,8 @@ enum {
     MJX_K_HUFF_EMIT = 8,  /* single decode (pictures of one scan without restart intervals): the first decode, which emits -- instead of
                              MJX_K_HUFF_SYNC and the decode of MJX_K_HUFF_WRITE */
     MJX_K_HUFF_PREFIX = 9,/* ... the prefixes of the subsequences whose entry state was wrong, and block words -> DC differences + tile offsets */
-    MJX_K_COUNT = 10
+    MJX_K_RESIZE = 10,    /* resize on the device (k_resize_out): no launches for a batch without a resize description */
+    MJX_K_COUNT = 11
 };
 int mjx_batch_kernel_ms(mjx_batch *b, double ms[MJX_K_COUNT], uint64_t launches[MJX_K_COUNT], int reset);
 
@@ -345,6 +398,11 @@ int mjx_decode_batch(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *le
  * failed mjx_ctx_create leaves -- is MJX_ERR_DEVICE: there is no device to write the output, and no CPU path. */
 int mjx_decode_batch_out(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
                          unsigned threads, const mjx_output *out, int *status, mjx_batch **b);
+
+/* mjx_decode_batch_out with a resize description; rs follows file i through the groups of the pipelined call, as rois[i] and
+ * dst[i] do.  rs == NULL: mjx_decode_batch_out.  out == NULL with a resize: interleaved u8 R,G,B, library-owned. */
+int mjx_decode_batch_resize(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
+                            unsigned threads, const mjx_output *out, const mjx_resize *rs, int *status, mjx_batch **b);
 
 /* ---- multi-GPU front: one context + one host thread + one work queue per device, no collective ----------
  * Pictures are independent (decoder.rs:162-343 touches only `self`), so a list of files shards over the GPUs of a node

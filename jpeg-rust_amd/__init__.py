@@ -30,7 +30,7 @@ OK, ERR_TRUNCATED, ERR_UNSUPPORTED_MARKER, ERR_DRI_UNSUPPORTED, ERR_BAD_HUFFMAN,
     ERR_UNSUPPORTED_FORMAT, ERR_NO_SCAN, ERR_INVALID_ARG, ERR_NOMEM, ERR_MISSING_TABLE = range(12)
 LAYOUT_STANDARD, LAYOUT_REF_COMPAT = 0, 1
 STAGE_ENTROPY, STAGE_PIXELS, STAGE_ALL = 1, 2, 3
-KERNEL_NAMES = ["gather", "huff_sync", "huff_fix", "huff_scan", "huff_write", "dc_scan", "idct_color", "upload", "huff_emit", "huff_prefix"]
+KERNEL_NAMES = ["gather", "huff_sync", "huff_fix", "huff_scan", "huff_write", "dc_scan", "idct_color", "upload", "huff_emit", "huff_prefix", "resize"]
 SUBSAMPLING = {"444": 0, "422": 1, "420": 2, "gray": 3, "440": 4}
 
 
@@ -63,6 +63,11 @@ class OutputDesc(ctypes.Structure):
     _fields_ = [("dtype", ctypes.c_uint8), ("planar", ctypes.c_uint8), ("bgr", ctypes.c_uint8),
                 ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3),
                 ("dst", ctypes.POINTER(Dst)), ("n_dst", ctypes.c_uint32)]
+
+
+class ResizeDesc(ctypes.Structure):
+    """mjx_resize: the one target size of a call's pictures (see Resize)."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("antialias", ctypes.c_uint8), ("auto_scale", ctypes.c_uint8)]
 
 
 DTYPE_U8, DTYPE_F16, DTYPE_F32 = 0, 1, 2
@@ -111,6 +116,12 @@ SYMBOLS = {
     "mjx_output_layout": (_int, [_P(ScanDesc), _P(Opts), _P(OutputDesc), _sz, _P(Dst), _P(_sz)]),
     "mjx_batch_output_info": (_int, [_vp, _sz, _P(Dst)] + [_P(ctypes.c_uint8)] * 3),
     "mjx_batch_copy_output": (_int, [_vp, _sz, _vp, _sz]),
+    "mjx_batch_create_resize": (_int, [_vp, _P(ScanDesc), _sz, _P(Opts), _P(OutputDesc), _P(ResizeDesc), _P(_vp), _P(_int)]),
+    "mjx_decode_batch_resize": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(OutputDesc), _P(ResizeDesc), _P(_int), _P(_vp)]),
+    "mjx_resize_plan": (_int, [_P(ScanDesc), _P(Opts), _P(ResizeDesc), _sz, _P(ctypes.c_uint8), _P(Rect), _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
+    "mjx_resize_weights": (_int, [ctypes.c_uint32, ctypes.c_uint32, _int, ctypes.c_uint32, _P(ctypes.c_uint32), _P(ctypes.c_float), _sz, _P(_sz)]),
+    "mjx_batch_image_scale": (_int, [_vp, _sz, _P(ctypes.c_uint8)]),
+    "mjx_batch_resize_rect": (_int, [_vp, _sz, _P(Rect)]),
     "mjx_decode_batch": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(_P(ctypes.c_uint8)), _P(_int), _P(_vp)]),
     "mjx_free_image": (None, [_P(Image)]),
     "mjx_ctx_create": (_int, [_int, _P(_vp)]),
@@ -259,6 +270,40 @@ class Output:
         return _NP_DTYPES[self.dtype]
 
 
+class Resize:
+    """Resize on the device (mjx.h: mjx_resize): every picture of the call leaves at width x height, resampled from its decoded
+    rectangle with the triangle filter of torch.nn.functional.interpolate(mode="bilinear", align_corners=False,
+    antialias=antialias).  auto_scale: the library picks the DCT-domain scale (1, 1/2, 1/4, 1/8) per picture so that the filter
+    never has to shrink by more than it must; rois are then in FULL-SIZE coordinates and scale must be 1.  Without it the call's
+    scale and rois apply as in any call."""
+
+    def __init__(self, width, height, antialias=True, auto_scale=True):
+        self.width, self.height = int(width), int(height)
+        self.antialias, self.auto_scale = bool(antialias), bool(auto_scale)
+        if not (0 <= self.width <= 0xffffffff and 0 <= self.height <= 0xffffffff):
+            raise MjxError(ERR_INVALID_ARG, "resize to %d x %d" % (self.width, self.height))
+
+    def desc(self):
+        return ResizeDesc(self.width, self.height, int(self.antialias), int(self.auto_scale))
+
+
+def _rs_ref(resize):
+    if resize is None:
+        return None, None
+    d = resize.desc() if isinstance(resize, Resize) else resize
+    return d, ctypes.byref(d)
+
+
+def resize_weights(n_in, n_out, antialias, X):
+    """mjx_resize_weights (host only; the routine the resize kernel runs) -> (first input index, float32 weights of the window)."""
+    first, cnt = ctypes.c_uint32(), _sz()
+    _check(lib().mjx_resize_weights(int(n_in), int(n_out), int(bool(antialias)), int(X), ctypes.byref(first), None, 0, ctypes.byref(cnt)), "mjx_resize_weights")
+    w = np.zeros(max(cnt.value, 1), np.float32)
+    _check(lib().mjx_resize_weights(int(n_in), int(n_out), int(bool(antialias)), int(X), ctypes.byref(first),
+                                    w.ctypes.data_as(_P(ctypes.c_float)), cnt.value, ctypes.byref(cnt)), "mjx_resize_weights")
+    return first.value, w[:cnt.value]
+
+
 def _out_ref(output):
     if output is None:
         return None, None
@@ -301,6 +346,15 @@ class ParsedScan:
         lay, nb = Dst(), _sz()
         _check(lib().mjx_output_layout(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(lay), ctypes.byref(nb)), "mjx_output_layout")
         return dict(width=lay.width, height=lay.height, row_pitch=lay.row_pitch, plane_pitch=lay.plane_pitch, bytes=nb.value, dev=lay.dev or 0)
+
+    def resize_plan(self, resize, roi=None, scale=1, i=0, layout=LAYOUT_STANDARD):
+        """mjx_resize_plan (host only) -> dict(scale, rect=(x, y, w, h) at that scale, taps_x, taps_y): what a resized decode of this
+        picture with this Resize takes; roi in full-size coordinates with auto_scale, else in the scaled picture's."""
+        o = _opts(layout=layout, scale=scale, rois=roi)
+        keep, ref = _rs_ref(resize)
+        s, r, tx, ty = ctypes.c_uint8(), Rect(), ctypes.c_uint32(), ctypes.c_uint32()
+        _check(lib().mjx_resize_plan(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(s), ctypes.byref(r), ctypes.byref(tx), ctypes.byref(ty)), "mjx_resize_plan")
+        return dict(scale=s.value, rect=(r.x, r.y, r.w, r.h), taps_x=tx.value, taps_y=ty.value)
 
     def close(self):
         if self._owned:
@@ -349,7 +403,7 @@ class Batch:
     """Device-resident batch: inputs uploaded at construction, ``decode()`` only enqueues kernels."""
 
     def __init__(self, ctx, scans=None, strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0,
-                 _handle=None, scale=1, rois=None, output=None):
+                 _handle=None, scale=1, rois=None, output=None, resize=None):
         """scale: 1, 2, 4 or 8 -- every picture decoded at 1/scale (info(), rgb(), rgb_device() and bytes() then speak of the
         scaled picture; tile() keeps the scale).
         rois: one (x, y, w, h) for every picture, or a list with one per picture (None or (0, 0, 0, 0): the whole picture), in the
@@ -357,7 +411,9 @@ class Batch:
         picture, roi(i) says where it lies; tile() keeps the rectangles.
         output: an Output -- the pictures leave in that format (output(i), output_info(i); rgb() and compare_rgb() do not serve
         such a batch), in the batch's memory or, Output(dst=...), in device memory of the caller's: idle when decode() is called,
-        complete when wait() returns."""
+        complete when wait() returns.
+        resize: a Resize -- every picture leaves at its width x height, through `output` (None: interleaved uint8); info(),
+        output_info() and output() speak of the target picture, scale(i) and rect(i) of what was decoded for it."""
         self.ctx = ctx
         self.h = _vp()
         if _handle is not None:
@@ -371,7 +427,11 @@ class Batch:
         st = (_int * max(n, 1))()
         o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois)
         keep, ref = _out_ref(output)
-        _check(lib().mjx_batch_create_out(ctx.h, arr, n, ctypes.byref(o), ref, ctypes.byref(self.h), st), "mjx_batch_create_out")
+        if resize is not None:
+            keep_rs, rs_ref = _rs_ref(resize)
+            _check(lib().mjx_batch_create_resize(ctx.h, arr, n, ctypes.byref(o), ref, rs_ref, ctypes.byref(self.h), st), "mjx_batch_create_resize")
+        else:
+            _check(lib().mjx_batch_create_out(ctx.h, arr, n, ctypes.byref(o), ref, ctypes.byref(self.h), st), "mjx_batch_create_out")
         self.create_status = list(st)[:n]
 
     def tile(self, times):
@@ -402,6 +462,18 @@ class Batch:
         lib().mjx_batch_image_roi(self.h, i, *[ctypes.byref(x) for x in v])
         inf = self.info(i)
         return dict(x=v[0].value, y=v[1].value, w=inf["width"], h=inf["height"], full_width=v[2].value, full_height=v[3].value)
+
+    def scale(self, i):
+        """The DCT-domain scale picture i was decoded at: the call's, or the one Resize(auto_scale=True) picked."""
+        v = ctypes.c_uint8()
+        lib().mjx_batch_image_scale(self.h, i, ctypes.byref(v))
+        return v.value
+
+    def rect(self, i):
+        """(x, y, w, h) of what was decoded for picture i, in the coordinates of the picture at scale(i) (roi(i): its size)."""
+        r = Rect()
+        lib().mjx_batch_resize_rect(self.h, i, ctypes.byref(r))
+        return (r.x, r.y, r.w, r.h)
 
     def rgb(self, i):
         inf = self.info(i)
@@ -665,10 +737,10 @@ class JPEGImage:
 
 
 def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False, scale=1, rois=None,
-                 output=None, chunk_images=0):
+                 output=None, chunk_images=0, resize=None):
     """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale, rois: see Batch.
     device_destuff: the host copies the entropy-coded bytes as they are; de-stuffing, restart markers and the scan's length
-    are found on the GPU.  output: an Output (mjx_decode_batch_out) -- see Batch."""
+    are found on the GPU.  output: an Output (mjx_decode_batch_out) -- see Batch.  resize: a Resize (mjx_decode_batch_resize)."""
     n = len(datas)
     arr = (ctypes.c_char_p * max(n, 1))(*[bytes(d) for d in datas])
     lens = (_sz * max(n, 1))(*[len(d) for d in datas])
@@ -676,6 +748,11 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
     h = _vp()
     o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois)
+    if resize is not None:
+        keep, ref = _out_ref(output)
+        keep_rs, rs_ref = _rs_ref(resize)
+        _check(lib().mjx_decode_batch_resize(ctx.h, arr, lens, n, ctypes.byref(o), int(threads), ref, rs_ref, st, ctypes.byref(h)), "mjx_decode_batch_resize")
+        return Batch(ctx, _handle=h), list(st)[:n]
     if output is not None:
         keep, ref = _out_ref(output)
         _check(lib().mjx_decode_batch_out(ctx.h, arr, lens, n, ctypes.byref(o), int(threads), ref, st, ctypes.byref(h)), "mjx_decode_batch_out")
@@ -684,7 +761,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     return Batch(ctx, _handle=h), list(st)[:n]
 
 
-def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=False, threads=0, device_destuff=None, planar=None):
+def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=False, threads=0, device_destuff=None, planar=None, resize=None):
     """Decodes the files straight into a torch tensor on the context's device: N x 3 x H x W (planar) or N x H x W x 3, of uint8,
     float16 or float32; picture i -- at 1/scale, its rectangle rois[i] -- must be H x W.  Float tensors take (v / 255 - mean) / std
     per OUTPUT channel (see Output); bgr: channel 0 is blue.  The pointers and pitches come from data_ptr() and stride(): the
@@ -693,7 +770,9 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
     planar: True / False says which form the tensor is.  None takes it from the shape: N x 3 x H x W when the second dimension is
     3, N x H x W x 3 when only the last is; a shape that reads both ways (N x 3 x H x 3) needs the keyword.
     torch's current stream is synchronised before the call (the library writes on streams of its
-    own) and the batch is complete when this returns.  -> the per-picture statuses."""
+    own) and the batch is complete when this returns.  -> the per-picture statuses.
+    resize: True, or a Resize (its antialias and auto_scale; a size, if it names one, must be the tensor's) -- the pictures, of any
+    size, are resampled on the device to the tensor's H x W (see Resize); None: every picture must be H x W as it is."""
     import torch
     n = len(datas)
     if not isinstance(out, torch.Tensor) or out.dim() != 4 or out.shape[0] != n:
@@ -726,7 +805,13 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
     dst = [(out.data_ptr() + i * sn * esz, w, h, row_pitch, plane_pitch) for i in range(n)]
     fmt = Output(names[out.dtype], planar=bool(planar), bgr=bgr, mean=mean, std=std, dst=dst)
     torch.cuda.current_stream(out.device).synchronize()
-    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt)
+    if resize is not None and resize is not False:
+        rs = Resize(w, h) if resize is True else Resize(w, h, resize.antialias, resize.auto_scale)
+        if resize is not True and (resize.width or resize.height) and (resize.width, resize.height) != (w, h):
+            raise MjxError(ERR_INVALID_ARG, "resize to %d x %d into a tensor of %d x %d" % (resize.width, resize.height, w, h))
+    else:
+        rs = None
+    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt, resize=rs)
     batch.close()
     return status
 
@@ -853,6 +938,15 @@ def plan_tiles(data, roi=None, scale=1):
     scan = ParsedScan(data)
     try:
         return scan.plan_tiles(roi=roi, scale=scale)
+    finally:
+        scan.close()
+
+
+def resize_plan(data, resize, roi=None, scale=1):
+    """Host only: the scale, rectangle and tap counts of a resized decode of this file -> see ParsedScan.resize_plan."""
+    scan = ParsedScan(data)
+    try:
+        return scan.resize_plan(resize, roi=roi, scale=scale)
     finally:
         scan.close()
 

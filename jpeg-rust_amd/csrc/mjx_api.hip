@@ -131,6 +131,10 @@ struct ImageInfo {
     bool out_on = false, cropped = false;
     uint32_t out_dtype = 0, out_planar = 0, out_bgr = 0;
     uint64_t out_dev = 0, out_row_pitch = 0, out_plane_pitch = 0, out_span = 0;
+    // resize on the device: width x height above is the target; the intermediate is src_w x src_h (the rectangle at roi_x, roi_y of
+    // the full_w x full_h picture at `scale`) and lies at DevImage::rgb_off; rgb_off here is the output's place in the pool
+    bool rs_on = false;
+    uint32_t scale = 1, src_w = 0, src_h = 0;
     uint64_t coef_off = 0;         // blocks, inside the per-block arrays of its chunk (or of the batch with keep_coefs)
     uint64_t ent_off = 0, ent_cap = 0;   // region of the compact coefficient stream (entries)
     uint32_t ent_rows = 0, ent_hdr = 0;  // > 0: quad-interleaved (DevImage::ent_rows, ent_hdr)
@@ -161,6 +165,7 @@ struct Chunk {
     uint32_t max_dc_wgs = 0;       // scaled decode at 1/8: workgroups of k_dc_color for the chunk's largest picture
     uint32_t max_dc_roi_wgs = 0;   // ... and of k_dc_color_roi for its largest rectangle
     uint32_t max_dc_out_wgs = 0;   // ... and of k_dc_color_out for its largest picture with an output description
+    uint32_t max_rs_tiles = 0;     // resize on the device: workgroups of k_resize_out for the chunk's largest target (0: no picture is resized)
     uint32_t max_b_tiles = 0;      // tiles the workgroups of stage B walk in the chunk's largest picture: all its tiles, or those of its
                                    // rectangle's MCU rows (DevImage::roi_ntiles) -- max_tiles without rectangles
     uint32_t min_sub_bits = 0xffffffffu;   // shortest subsequence length among its scans (chunk_fix_passes)
@@ -497,8 +502,11 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
         d.roi_ntiles = (p.roi_mr1 * p.mcux + p.roi_mc1) / t - d.roi_tile0 + 1;
     }
     // output formats: the forms built on the cropped ones (a picture without a rectangle is its own whole rectangle: every tile above)
+    // (a resized picture keeps the packed forms: its description is k_resize_out's, behind stage B)
     if (p.out_on) {
-        d.mode = d.mode % kRoiMode + kOutMode;
+        if (!p.rs_on) d.mode = d.mode % kRoiMode + kOutMode;
+        d.rs_on = p.rs_on ? 1u : 0u;
+        d.rs_w = p.rs_w; d.rs_h = p.rs_h; d.rs_aa = p.rs_aa;
         d.out_dev = p.out_dev;
         d.out_row_pitch = p.out_row_pitch; d.out_plane_pitch = p.out_plane_pitch;
         d.out_dtype = p.out_dtype; d.out_planar = p.out_planar; d.out_bgr = p.out_bgr;
@@ -611,6 +619,7 @@ void plan_chunks(mjx_batch *b)
                 if (d.nseg > 1) c.max_restart_segs = std::max(c.max_restart_segs, d.nseg);
                 if (d.mode == 5) c.max_dc_wgs = std::max<uint32_t>(c.max_dc_wgs, uint32_t((uint64_t(d.out_w) * d.out_h + 255) / 256));
                 if (d.mode == 5 + kOutMode) c.max_dc_out_wgs = std::max<uint32_t>(c.max_dc_out_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
+                if (d.rs_on && d.role != 1) c.max_rs_tiles = std::max<uint32_t>(c.max_rs_tiles, resize_tiles(d.rs_w, d.rs_h));
                 if (d.mode == 5 + kRoiMode) c.max_dc_roi_wgs = std::max<uint32_t>(c.max_dc_roi_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
                 if (d.mode == 2) {
                     d.plane_off = c.plane_words;
@@ -925,6 +934,11 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
         if (c.max_dc_roi_wgs) launch_dc_color(sp, c.max_dc_roi_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true);
         if (c.max_dc_out_wgs) launch_dc_color(sp, c.max_dc_out_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true, true);
         prof_end(b, sp);
+        if (c.max_rs_tiles) {          // resize on the device: the chunk's intermediates -> the target pictures, behind its stage B
+            prof_begin(b, MJX_K_RESIZE, sp);
+            launch_resize_out(sp, c.max_rs_tiles, nimg, imgs, b->d_rgb, b->d_img_flags);
+            prof_end(b, sp);
+        }
         if (sp != st) {
             HIPOK(hipEventRecord(b->ev_pixels[set], sp));
             b->pixels_recorded[set] = true;
@@ -1161,6 +1175,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
         d.seg_off = seg_off[k];
         inf.width = p.roi_w; inf.height = p.roi_h; inf.bpm = p.bpm; inf.nmcu = p.nmcu;      // (the picture written: scaled decode, rectangle)
         inf.roi_x = p.roi_x; inf.roi_y = p.roi_y; inf.full_w = p.out_w; inf.full_h = p.out_h;
+        inf.scale = p.scale; inf.src_w = p.roi_w; inf.src_h = p.roi_h;
         inf.nblocks = uint64_t(p.nmcu) * p.bpm;
         inf.tile_blocks = d.tile_blocks;
         inf.ntiles = uint32_t((inf.nblocks + d.tile_blocks - 1) / d.tile_blocks);
@@ -1261,6 +1276,16 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
             inf.out_dtype = p.out_dtype; inf.out_planar = p.out_planar; inf.out_bgr = p.out_bgr;
             inf.out_dev = p.out_dev; inf.out_row_pitch = p.out_row_pitch; inf.out_plane_pitch = p.out_plane_pitch;
             inf.out_span = p.out_bytes;
+            if (p.rs_on) {
+                // resize on the device: the packed intermediate first (always in the pool), then the output's region
+                rgb_pool += align_up(inf.rgb_bytes, 256);
+                inf.rs_on = true;
+                inf.src_w = p.roi_w; inf.src_h = p.roi_h;
+                inf.width = p.rs_w; inf.height = p.rs_h;
+                inf.rgb_off = rgb_pool;
+                d.rs_off = rgb_pool;
+                inf.rgb_bytes = uint64_t(p.rs_w) * p.rs_h * 3;
+            }
             inf.rgb_bytes *= p.out_dtype == MJX_DTYPE_U8 ? 1u : p.out_dtype == MJX_DTYPE_F16 ? 2u : 4u;      // (the bytes written)
             rgb_pool += p.out_dev ? 0 : align_up(inf.out_span, 256);
         } else
@@ -1782,6 +1807,12 @@ extern "C" int mjx_batch_create(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t
 extern "C" int mjx_batch_create_out(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_output *fmt,
                                     mjx_batch **out, int *status)
 {
+    return mjx_batch_create_resize(ctx, descs, n, opts, fmt, nullptr, out, status);
+}
+
+extern "C" int mjx_batch_create_resize(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_output *fmt,
+                                       const mjx_resize *rs, mjx_batch **out, int *status)
+{
     return guarded([&]() -> int {
     if (!ctx || !out || (!descs && n)) return MJX_ERR_INVALID_ARG;
     *out = nullptr;
@@ -1794,13 +1825,13 @@ extern "C" int mjx_batch_create_out(mjx_ctx *ctx, const mjx_scan_desc *descs, si
     plans.reserve(n);
     const auto tp0 = std::chrono::steady_clock::now();
     for (size_t i = 0; i < n; i++) {
-        plan_input(dd[i], opts_for_input(o, n, i), plans);      // (rois[i] goes with input i: a multi-scan file's picture plan takes it)
-        plan_output_of_input(plans, fmt, i);                    // (... and dst[i])
+        plan_input_for(dd[i], opts_for_input(o, n, i), fmt, rs, i, plans);      // (rois[i] and dst[i] go with input i: a multi-scan file's picture plan takes them)
         plan_of[i] = plans.size() - 1;
     }
     if (std::getenv("MJX_TIMING"))
         std::fprintf(stderr, "[mjx] planning %zu inputs %.2f ms\n", n, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count());
     (void)plan_of;
+    if (rs && rs->auto_scale) o.scale_denom = 1;                // (the pictures' own scales are in their plans)
     return build_batch(ctx, plans, o, nullptr, 1, out, status);
     });
 }
@@ -1876,6 +1907,46 @@ extern "C" int mjx_output_layout(const mjx_scan_desc *desc, const mjx_opts *opts
     });
 }
 
+// Host-only: the scale and rectangle a resized decode of this picture takes (the planner's own: plan_input_for) and the longest
+// tap loops of the kernel (resize_window, the routine it runs).
+extern "C" int mjx_resize_plan(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_resize *rs, size_t i, uint8_t *scale_denom,
+                               mjx_rect *rect, uint32_t *taps_x, uint32_t *taps_y)
+{
+    return guarded([&]() -> int {
+    if (!desc || !rs) return MJX_ERR_INVALID_ARG;
+    mjx_opts o{};
+    if (opts) o = *opts;
+    if (!o.rois ? o.n_rois != 0 : (o.n_rois == 0 || (o.n_rois > 1 && i >= o.n_rois))) return MJX_ERR_INVALID_ARG;
+    if (o.rois) { if (o.n_rois > 1) o.rois += i; o.n_rois = 1; }
+    std::vector<ImagePlan> plans;
+    plan_input_for(*desc, o, nullptr, rs, 0, plans);
+    const ImagePlan &p = plans.back();
+    if (p.status != MJX_OK) return p.status;
+    if (scale_denom) *scale_denom = uint8_t(p.scale);
+    if (rect) *rect = mjx_rect{p.roi_x, p.roi_y, p.roi_w, p.roi_h};
+    auto taps = [&](uint32_t n_in, uint32_t n_out) {
+        uint32_t t = 0;
+        for (uint32_t X = 0; X < n_out; X++) { const ResizeAxis a = resize_window(n_in, n_out, p.rs_aa != 0, X); t = std::max(t, a.hi - a.lo); }
+        return t;
+    };
+    if (taps_x) *taps_x = taps(p.roi_w, p.rs_w);
+    if (taps_y) *taps_y = taps(p.roi_h, p.rs_h);
+    return MJX_OK;
+    });
+}
+
+// Host-only: one output coordinate's filter from the kernel's own routine.
+extern "C" int mjx_resize_weights(uint32_t n_in, uint32_t n_out, int antialias, uint32_t X, uint32_t *first, float *weights, size_t cap,
+                                  size_t *count)
+{
+    if (!n_in || !n_out || n_in > kResizeMaxDim || n_out > kResizeMaxDim || X >= n_out) return MJX_ERR_INVALID_ARG;
+    const ResizeAxis a = resize_axis(n_in, n_out, antialias != 0, X);
+    if (first) *first = a.lo;
+    if (count) *count = a.hi - a.lo;
+    for (uint32_t j = a.lo; j < a.hi && weights && size_t(j - a.lo) < cap; j++) weights[j - a.lo] = float(resize_num(a, j)) / a.sum;
+    return MJX_OK;
+}
+
 extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, mjx_batch **out)
 {
     return guarded([&]() -> int {
@@ -1913,6 +1984,8 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
             p.out_dev = fi.out_dev; p.out_row_pitch = fi.out_row_pitch; p.out_plane_pitch = fi.out_plane_pitch;
             p.out_bytes = fi.out_span;
             for (uint32_t c = 0; c < 3; c++) { p.out_scale[c] = src->himages[k].out_scale[c]; p.out_bias[c] = src->himages[k].out_bias[c]; }
+            p.rs_on = src->himages[k].rs_on != 0;                                     // (... and its resize)
+            p.rs_w = src->himages[k].rs_w; p.rs_h = src->himages[k].rs_h; p.rs_aa = src->himages[k].rs_aa;
         }
         p.roi_x = d.roi_x; p.roi_y = d.roi_y; p.roi_w = d.roi_w; p.roi_h = d.roi_h;
         p.roi_mr0 = d.roi_mr0; p.roi_mr1 = d.roi_mr1; p.roi_mc0 = d.roi_mc0; p.roi_mc1 = d.roi_mc1;
@@ -2206,6 +2279,26 @@ extern "C" int mjx_batch_image_roi(const mjx_batch *b, size_t iu, uint32_t *x, u
     if (y) *y = inf.roi_y;
     if (full_width) *full_width = inf.full_w;
     if (full_height) *full_height = inf.full_h;
+    return inf.status;
+}
+
+extern "C" int mjx_batch_image_scale(const mjx_batch *b, size_t iu, uint8_t *scale_denom)
+{
+    if (b && !b->parts.empty()) { mjx_batch *pb; size_t pi; return route(b, iu, pb, pi) ? mjx_batch_image_scale(pb, pi, scale_denom) : MJX_ERR_INVALID_ARG; }
+    size_t i;
+    if (!visible_index(b, iu, i)) return MJX_ERR_INVALID_ARG;
+    const ImageInfo &inf = b->info[i];
+    if (scale_denom) *scale_denom = uint8_t(inf.scale ? inf.scale : 1u);
+    return inf.status;
+}
+
+extern "C" int mjx_batch_resize_rect(const mjx_batch *b, size_t iu, mjx_rect *rect)
+{
+    if (b && !b->parts.empty()) { mjx_batch *pb; size_t pi; return route(b, iu, pb, pi) ? mjx_batch_resize_rect(pb, pi, rect) : MJX_ERR_INVALID_ARG; }
+    size_t i;
+    if (!visible_index(b, iu, i)) return MJX_ERR_INVALID_ARG;
+    const ImageInfo &inf = b->info[i];
+    if (rect) *rect = mjx_rect{inf.roi_x, inf.roi_y, inf.src_w, inf.src_h};
     return inf.status;
 }
 
@@ -2603,7 +2696,7 @@ unsigned usable_processors()
 // same time, and the call takes about as long as the slowest of the three (on PCIe Gen5: the transfer).
 // (fmt: the call's output description, or null -- mjx_decode_batch_out; dst[i] goes with file i wherever its group falls)
 static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
-                             unsigned threads, const mjx_output *fmt, uint8_t **rgb_dev, int *status, mjx_batch **out)
+                             unsigned threads, const mjx_output *fmt, const mjx_resize *rs, uint8_t **rgb_dev, int *status, mjx_batch **out)
 {
     return guarded([&]() -> int {
     if (!ctx || !out || ((!jpegs || !lens) && n)) return MJX_ERR_INVALID_ARG;
@@ -2741,8 +2834,7 @@ static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const si
             prc[i] = rc;
             if (rc != MJX_OK) std::memset(&descs[i], 0, sizeof descs[i]);
             try {
-                plan_input(descs[i], opts_for_input(o, n, i), file_plans[i]);          // geometry + decode tables, also on the worker (rois[i] goes with file i)
-                plan_output_of_input(file_plans[i], fmt, i);                           // (... and dst[i])
+                plan_input_for(descs[i], opts_for_input(o, n, i), fmt, rs, i, file_plans[i]);     // geometry + decode tables, also on the worker (rois[i], dst[i] and the resize go with file i)
             } catch (...) {
                 file_plans[i].clear();
             }
@@ -2822,14 +2914,21 @@ static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const si
 extern "C" int mjx_decode_batch(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
                                 unsigned threads, uint8_t **rgb_dev, int *status, mjx_batch **out)
 {
-    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, nullptr, rgb_dev, status, out);
+    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, nullptr, nullptr, rgb_dev, status, out);
 }
 
 extern "C" int mjx_decode_batch_out(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
                                     unsigned threads, const mjx_output *fmt, int *status, mjx_batch **out)
 {
     if (!ctx) { if (out) *out = nullptr; return MJX_ERR_DEVICE; }      // (no context is no device: mjx_ctx_create failed, and there is no CPU path)
-    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, fmt, nullptr, status, out);
+    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, fmt, nullptr, nullptr, status, out);
+}
+
+extern "C" int mjx_decode_batch_resize(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
+                                       unsigned threads, const mjx_output *fmt, const mjx_resize *rs, int *status, mjx_batch **out)
+{
+    if (!ctx) { if (out) *out = nullptr; return MJX_ERR_DEVICE; }      // (as mjx_decode_batch_out: no device, no CPU path)
+    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, fmt, rs, nullptr, status, out);
 }
 
 // ---- one-shot surface ------------------------------------------------------------------------------

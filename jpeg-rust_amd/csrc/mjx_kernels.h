@@ -102,6 +102,11 @@ struct DevImage {
     uint64_t out_row_pitch, out_plane_pitch;
     uint32_t out_dtype, out_planar, out_bgr;
     float out_scale[3], out_bias[3];
+    // resize on the device (mjx_resize; rs_on): stage B writes the picture as a packed (cropped) one -- roi_w x roi_h x 3 bytes at
+    // rgb_off, mode below kOutMode -- and k_resize_out resamples that to rs_w x rs_h elements per channel in the format out_* above
+    // describe, at out_dev or, out_dev == 0, at byte rs_off of the batch's picture pool.
+    uint32_t rs_on, rs_w, rs_h, rs_aa;
+    uint64_t rs_off;
 };
 constexpr uint32_t kRoiMode = 8;
 constexpr uint32_t kOutMode = 16;      // + m (0, 1, 3, 4; 5: k_dc_color_out): the forms for pictures with an output description
@@ -119,6 +124,61 @@ MJX_HD bool roi_tile_wanted(uint32_t t, uint32_t T, uint32_t nmcu, uint32_t mcux
     const bool first = (rs == ra ? ca : 0u) <= c1 && (rs == rb ? cb : mcux - 1u) >= c0;
     const bool last = (re == ra ? ca : 0u) <= c1 && (re == rb ? cb : mcux - 1u) >= c0;
     return first || last;
+}
+
+// ---- resize on the device (mjx_resize): the separable triangle filter, one axis -----------------------------------------------
+// Output coordinate X of an axis n_in -> n_out samples the input at c = (2X + 1) n_in / (2 n_out) with a triangle of half width
+// fs = F / n_out, F = n_in when shrinking with antialias, n_out otherwise (fs = 1).  Everything stays in integers (n_in and n_out
+// below stand for the two sizes divided by their greatest common divisor, which leaves c and fs as they are): with
+// c = q + rem / (2 n_out), tap j lies at  j + 1/2 - c = t_j / (2 n_out),  t_j = (2 (j - q) + 1) n_out - rem,  and its weight is
+// max(0, 2F - |t_j|) / 2F -- the numerators are whole numbers, so the weight of a tap is ONE rounding (the division by their sum,
+// which is also a whole number) whatever the sizes; a float32 product (X + 0.5) r near 4000 would be 2e-4 pixels off.
+// lo = max(0, floor(c - fs + 1/2)), hi = min(n_in, floor(c + fs + 1/2)); outside [lo, hi) the numerator is <= 0.
+// The kernel (k_resize_out) and the host (mjx_resize_weights, mjx_resize_plan) run this one routine.  n_in, n_out <= kResizeMaxDim.
+constexpr uint32_t kResizeMaxDim = 1u << 24;
+constexpr uint32_t kResizeTileW = 64, kResizeTileH = 16;     // the target tile of a workgroup of k_resize_out
+MJX_HD uint32_t resize_tiles(uint32_t w, uint32_t h) { return ((w + kResizeTileW - 1) / kResizeTileW) * ((h + kResizeTileH - 1) / kResizeTileH); }
+struct ResizeAxis {
+    uint32_t lo, hi;        // taps [lo, hi)
+    int32_t t_lo;           // t_j at j = lo; t_(j+1) = t_j + step
+    int32_t step;           // 2 n_out
+    int32_t full;           // 2 F
+    float sum;              // sum of the numerators over [lo, hi), added up as a whole number and rounded once (> 0)
+};
+MJX_HD uint32_t resize_num(const ResizeAxis &a, uint32_t j)       // numerator of tap j's weight (any j: 0 outside the triangle)
+{
+    const int32_t t = a.t_lo + int32_t(j - a.lo) * a.step, m = t < 0 ? -t : t;
+    return m < a.full ? uint32_t(a.full - m) : 0u;
+}
+// the window and the first tap's offset, without the sum (uniform values a workgroup only needs the window of)
+MJX_HD ResizeAxis resize_window(uint32_t n_in, uint32_t n_out, bool antialias, uint32_t X)
+{
+    ResizeAxis a;
+    // in lowest terms (uniform over the picture): the ratio, so c, is the same, and the numerators are as small as they get -- an
+    // integer ratio keeps them, the sums and their products with a byte exact in float32 (equal sizes: 2 and 0; 2:1: 1, 3, 3, 1)
+    uint32_t g = n_in, g2 = n_out;
+    while (g2) { const uint32_t r = g % g2; g = g2; g2 = r; }
+    const uint64_t ni = n_in / g, no = n_out / g;
+    const uint64_t num = (2ull * X + 1ull) * ni, den = 2ull * no;
+    const uint64_t q = num / den, rem = num - q * den;
+    const uint64_t F = antialias && ni > no ? ni : no;
+    const int64_t lo_num = int64_t(num) + int64_t(no) - int64_t(2 * F);
+    const uint64_t hi_q = (num + no + 2 * F) / den;
+    a.lo = lo_num > 0 ? uint32_t(uint64_t(lo_num) / den) : 0u;
+    a.hi = hi_q < n_in ? uint32_t(hi_q) : n_in;
+    a.step = int32_t(den);
+    a.full = int32_t(2 * F);
+    a.t_lo = int32_t((2 * (int64_t(a.lo) - int64_t(q)) + 1) * int64_t(no) - int64_t(rem));
+    a.sum = 0.f;
+    return a;
+}
+MJX_HD ResizeAxis resize_axis(uint32_t n_in, uint32_t n_out, bool antialias, uint32_t X)
+{
+    ResizeAxis a = resize_window(n_in, n_out, antialias, X);
+    uint64_t sum = 0;       // (a whole number; 65535 -> 1 passes 2^32)
+    for (uint32_t j = a.lo; j < a.hi; j++) sum += resize_num(a, j);
+    a.sum = float(sum);
+    return a;
 }
 
 // Where the segments of a scan begin (DevImage::seg_S): the first cut at or after scan MCU q0, as the scan MCU it lies at and its
@@ -432,6 +492,8 @@ void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, con
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
                      const float *qmult, uint8_t *rgb, const uint32_t *img_flags, bool roi = false /* the form for pictures with a rectangle */,
                      bool out = false /* the form for pictures with an output description (mode 5 + kOutMode) */);
+// resize on the device: one workgroup per tile of the target (resize_tiles) and picture with DevImage::rs_on, behind stage B
+void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
 #endif
 
 }   // namespace mjx

@@ -4025,6 +4025,120 @@ extern "C" __global__ __launch_bounds__(256) void k_dc_color_out(const DevImage 
     dc_color_body<true, true>(images, dcbuf, qmult, rgb, img_flags);
 }
 
+// ---- resize on the device (mjx_resize; DevImage::rs_*) -------------------------------------------------------------------------
+// Stage B has written the picture as a packed (cropped) one: roi_h x roi_w x 3 bytes at rgb_off, the intermediate.  A workgroup
+// owns a tile of kRsTileW x kRsTileH pixels of the rs_w x rs_h target, all three channels; lane (lx, ly) owns column lx of the
+// rows ly, ly + 4, ly + 8, ly + 12 and keeps their twelve sums in registers.  The source rows the tile's windows span are streamed
+// in slabs of kRsSlab rows: every lane filters its column of four of the slab's rows horizontally (bytes of the intermediate,
+// which is small and sits in the caches) into LDS as float, barrier, every lane adds the slab's rows to its four outputs with
+// their vertical weights (zero outside a row's window), barrier.  LDS is 12 KB whatever the ratio, the tap loops are plain loops,
+// and the weights come from resize_window / resize_num (mjx_kernels.h), in the lane: whole-number numerators, so a sum is
+// sum_y ny (sum_x nx I) in float32 and ONE division by (sum nx)(sum ny) at the end -- exact wherever the numerators and the sums
+// stay below 2^24 (48 x 32 -> 24 x 16 with antialias: 24, 72, 72, 24 of 192).  A wave's 64 lanes store 64 neighbouring elements
+// (planar) or 192 (interleaved) of a row, non-temporal; the format's fields are uniform and so are the branches on them.
+constexpr uint32_t kRsTileW = kResizeTileW, kRsTileH = kResizeTileH, kRsSlab = 16, kRsRows = kRsTileH / 4;
+static_assert(kRsTileW == 64 && kRsTileH % 4 == 0 && kRsSlab == 4 * kRsRows, "k_resize_out: a wave per row of the slab, four rows per lane");
+// One element of the output from the unrounded sample v: U8 rint (nearest even) of v clamped to [0, 255]; F32 fmaf(v, sc, bi);
+// F16 that float rounded to nearest even.
+__device__ __forceinline__ void out_store1f(const OutFmt &f, uint64_t at, float v, float sc, float bi)
+{
+    if (f.dtype == 0u) {
+        const float r = __builtin_rintf(fminf(fmaxf(v, 0.0f), 255.0f));
+        __builtin_nontemporal_store(uint8_t(uint32_t(r)), f.base + at);
+    } else {
+        const float e = __builtin_fmaf(v, sc, bi);
+        if (f.dtype == 1u) __builtin_nontemporal_store(uint16_t(half_bits(e)), reinterpret_cast<uint16_t *>(f.base) + at);
+        else __builtin_nontemporal_store(e, reinterpret_cast<float *>(f.base) + at);
+    }
+}
+extern "C" __global__ __launch_bounds__(256) void k_resize_out(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,
+                                                                const uint32_t *__restrict__ img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    if (!im.valid || !im.rs_on || img_flags[im.status_idx]) return;
+    const uint32_t W = im.rs_w, H = im.rs_h, w_in = im.roi_w, h_in = im.roi_h;
+    const uint32_t tiles_x = (W + kRsTileW - 1) / kRsTileW, tiles_y = (H + kRsTileH - 1) / kRsTileH;
+    if (blockIdx.x >= tiles_x * tiles_y) return;
+    const uint32_t tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const bool aa = im.rs_aa != 0;
+    const uint8_t *__restrict__ src = rgb + im.rgb_off;
+    __shared__ float s_h[kRsSlab][3][kRsTileW];
+    const uint32_t lx = threadIdx.x & (kRsTileW - 1), ly = threadIdx.x / kRsTileW;       // (ly: the wave)
+    const uint32_t X = tile_x * kRsTileW + lx, Y0 = tile_y * kRsTileH;
+    // (a lane past the right or bottom edge works on the last column / row -- the barriers stay uniform -- and stores nothing)
+    const ResizeAxis ax = resize_axis(w_in, W, aa, X < W ? X : W - 1u);
+    const uint32_t Y1 = (Y0 + kRsTileH < H ? Y0 + kRsTileH : H) - 1u;
+    const uint32_t row_lo = resize_window(h_in, H, aa, Y0).lo, row_hi = resize_window(h_in, H, aa, Y1).hi;
+    int32_t ty[kRsRows];            // numerator offset t of the lane's output row k at the source row the loop stands at
+    float sy[kRsRows], acc[kRsRows][3];
+    int32_t ystep = 0, yfull = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kRsRows; k++) {
+        const uint32_t Y = Y0 + ly + 4u * k;
+        const ResizeAxis a = resize_axis(h_in, H, aa, Y < H ? Y : H - 1u);
+        ty[k] = a.t_lo - int32_t(a.lo - row_lo) * a.step;
+        sy[k] = a.sum;
+        ystep = a.step; yfull = a.full;
+        acc[k][0] = acc[k][1] = acc[k][2] = 0.0f;
+    }
+    for (uint32_t r0 = row_lo; r0 < row_hi; r0 += kRsSlab) {
+        float h[kRsRows][3];
+#pragma unroll
+        for (uint32_t k = 0; k < kRsRows; k++) h[k][0] = h[k][1] = h[k][2] = 0.0f;
+        int32_t t = ax.t_lo;
+        for (uint32_t j = ax.lo; j < ax.hi; j++, t += ax.step) {
+            const int32_t m = t < 0 ? -t : t;
+            const float wn = m < ax.full ? float(ax.full - m) : 0.0f;
+#pragma unroll
+            for (uint32_t k = 0; k < kRsRows; k++) {
+                const uint32_t row = r0 + ly + 4u * k;
+                if (row < row_hi) {
+                    const uint8_t *p = src + (uint64_t(row) * w_in + j) * 3u;
+                    h[k][0] = __builtin_fmaf(wn, float(p[0]), h[k][0]);
+                    h[k][1] = __builtin_fmaf(wn, float(p[1]), h[k][1]);
+                    h[k][2] = __builtin_fmaf(wn, float(p[2]), h[k][2]);
+                }
+            }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kRsRows; k++) {
+#pragma unroll
+            for (uint32_t c = 0; c < 3; c++) s_h[ly + 4u * k][c][lx] = h[k][c];
+        }
+        __syncthreads();
+        const uint32_t nrows = row_hi - r0 < kRsSlab ? row_hi - r0 : kRsSlab;
+        for (uint32_t rr = 0; rr < nrows; rr++) {
+            const float v0 = s_h[rr][0][lx], v1 = s_h[rr][1][lx], v2 = s_h[rr][2][lx];
+#pragma unroll
+            for (uint32_t k = 0; k < kRsRows; k++) {
+                const int32_t m = ty[k] < 0 ? -ty[k] : ty[k];
+                const float wn = m < yfull ? float(yfull - m) : 0.0f;
+                ty[k] += ystep;
+                acc[k][0] = __builtin_fmaf(wn, v0, acc[k][0]);
+                acc[k][1] = __builtin_fmaf(wn, v1, acc[k][1]);
+                acc[k][2] = __builtin_fmaf(wn, v2, acc[k][2]);
+            }
+        }
+        __syncthreads();
+    }
+    if (X >= W) return;
+    OutFmt f = out_fmt(im, rgb);
+    if (!im.out_dev) f.base = rgb + im.rs_off;
+#pragma unroll
+    for (uint32_t k = 0; k < kRsRows; k++) {
+        const uint32_t Y = Y0 + ly + 4u * k;
+        if (Y >= H) continue;
+        const float norm = ax.sum * sy[k];
+        const uint64_t row = uint64_t(Y) * f.row_pitch;
+#pragma unroll
+        for (uint32_t oc = 0; oc < 3; oc++) {
+            const float a = f.bgr ? acc[k][2u - oc] : acc[k][oc];
+            const uint64_t at = f.planar ? row + oc * f.plane_pitch + X : row + uint64_t(X) * 3u + oc;
+            out_store1f(f, at, a / norm, f.scale[oc], f.bias[oc]);
+        }
+    }
+}
+
 // ---- verification helper: byte-wise comparison of decoded pictures on the device ------------------------------
 // (mjx_batch_compare_rgb: the parity gate of bench.py and the batch-scale tests compare tens of gigabytes of output
 // without copying them to the host.)  One workgroup per 16 KiB of a pair; per pair the largest absolute byte
@@ -4346,6 +4460,11 @@ void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, con
                       const unsigned long long *planes, uint8_t *rgb, const uint32_t *img_flags)
 {
     hipLaunchKernelGGL(k_ref_color, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, planes, rgb, img_flags);
+}
+
+void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags)
+{
+    hipLaunchKernelGGL(k_resize_out, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
 }
 
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,

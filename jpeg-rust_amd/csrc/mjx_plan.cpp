@@ -1,5 +1,6 @@
 // mjx_plan.cpp -- see mjx_plan.h.
 #include "mjx_plan.h"
+#include "mjx_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -479,12 +480,12 @@ int plan_output(ImagePlan &p, const mjx_output *out, size_t i)
         p.out_scale[c] = out->dtype == MJX_DTYPE_U8 ? 1.f : out->scale[c];
         p.out_bias[c] = out->dtype == MJX_DTYPE_U8 ? 0.f : out->bias[c];
     }
-    const uint64_t w = p.roi_w, h = p.roi_h, row_min = planar ? w : 3 * w;
+    const uint64_t w = p.rs_on ? p.rs_w : p.roi_w, h = p.rs_on ? p.rs_h : p.roi_h, row_min = planar ? w : 3 * w;      // (a resized picture: the target)
     p.out_row_pitch = row_min;
     p.out_plane_pitch = planar ? h * w : 0;
     if (out->dst) {
         const mjx_dst &d = out->dst[i];
-        if (d.width != p.roi_w || d.height != p.roi_h || d.row_pitch < row_min) return fail();
+        if (d.width != w || d.height != h || d.row_pitch < row_min) return fail();
         if (d.row_pitch > (uint64_t(1) << 40) || d.plane_pitch > (uint64_t(1) << 56)) return fail();      // (no overflow below)
         if (planar && d.plane_pitch < h * d.row_pitch) return fail();
         if (!d.dev || (uint64_t(uintptr_t(d.dev)) & (esz - 1))) return fail();
@@ -514,6 +515,64 @@ int plan_output_of_input(std::vector<ImagePlan> &plans, const mjx_output *out, s
         plans.push_back(pic);
     }
     return rc;
+}
+
+// one status for the whole input: a multi-scan picture that is refused takes its scans' plans with it
+static void fail_input(std::vector<ImagePlan> &plans, size_t first, int rc)
+{
+    plans.resize(first);
+    ImagePlan pic;
+    pic.status = rc;
+    plans.push_back(pic);
+}
+
+int resize_opts(uint32_t width, uint32_t height, const mjx_opts &opts_i, const mjx_resize &rs, mjx_opts &eff, mjx_rect &rect)
+{
+    eff = opts_i;
+    if (!rs.width || !rs.height || rs.width > kResizeMaxDim || rs.height > kResizeMaxDim) return MJX_ERR_INVALID_ARG;
+    if (opts_i.layout == MJX_LAYOUT_REF_COMPAT) return MJX_ERR_INVALID_ARG;
+    if (!rs.auto_scale) return MJX_OK;
+    if (opts_i.scale_denom > 1) return MJX_ERR_INVALID_ARG;
+    if (!width || !height) return MJX_OK;                                  // (plan_image says what is wrong with the picture)
+    uint32_t x = 0, y = 0, w = width, h = height;
+    if (opts_i.rois && opts_i.n_rois && (opts_i.rois[0].w || opts_i.rois[0].h)) {
+        const mjx_rect &r = opts_i.rois[0];
+        if (!r.w || !r.h || r.x >= width || r.y >= height || r.w > width - r.x || r.h > height - r.y) return MJX_ERR_INVALID_ARG;
+        x = r.x; y = r.y; w = r.w; h = r.h;
+    }
+    uint32_t s = 8;
+    for (;; s /= 2) {
+        rect.x = x / s; rect.y = y / s;
+        rect.w = (x + w + s - 1) / s - rect.x; rect.h = (y + h + s - 1) / s - rect.y;
+        if (s == 1 || (rect.w >= rs.width && rect.h >= rs.height)) break;
+    }
+    eff.scale_denom = uint8_t(s);
+    const uint32_t ow = (width + s - 1) / s, oh = (height + s - 1) / s;
+    if (rect.x == 0 && rect.y == 0 && rect.w == ow && rect.h == oh) { eff.rois = nullptr; eff.n_rois = 0; }   // the whole picture: the plain forms
+    else { eff.rois = &rect; eff.n_rois = 1; }
+    return MJX_OK;
+}
+
+void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_output *out, const mjx_resize *rs, size_t i,
+                    std::vector<ImagePlan> &plans)
+{
+    if (!rs) {
+        plan_input(d, opts_i, plans);
+        plan_output_of_input(plans, out, i);
+        return;
+    }
+    const size_t first = plans.size();
+    mjx_opts eff;
+    mjx_rect rect{0, 0, 0, 0};
+    const int rc = resize_opts(d.width, d.height, opts_i, *rs, eff, rect);
+    plan_input(d, eff, plans);
+    if (plans.back().status != MJX_OK) return;                             // (the picture's own fault comes first)
+    if (rc != MJX_OK) { fail_input(plans, first, rc); return; }
+    ImagePlan &p = plans.back();
+    p.rs_on = true;
+    p.rs_w = rs->width; p.rs_h = rs->height; p.rs_aa = rs->antialias ? 1u : 0u;
+    static const mjx_output packed = {MJX_DTYPE_U8, 0, 0, {1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}, nullptr, 0};
+    plan_output_of_input(plans, out ? out : &packed, i);
 }
 
 void plan_input(const mjx_scan_desc &d, const mjx_opts &opts, std::vector<ImagePlan> &out)

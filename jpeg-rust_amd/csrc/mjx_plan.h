@@ -54,6 +54,11 @@ struct ImagePlan {
     uint32_t out_dtype = 0, out_planar = 0, out_bgr = 0;
     float out_scale[3] = {1.f, 1.f, 1.f}, out_bias[3] = {0.f, 0.f, 0.f};
     uint64_t out_dev = 0, out_row_pitch = 0, out_plane_pitch = 0, out_bytes = 0;
+    // resize on the device (mjx_resize, plan_resize): the picture is planned as the packed (cropped) picture roi_w x roi_h at `scale`
+    // -- the intermediate -- and leaves as rs_w x rs_h elements per channel: out_* above then describe the TARGET picture, and
+    // stage B keeps its packed forms (fill_dev_image).
+    bool rs_on = false;
+    uint32_t rs_w = 0, rs_h = 0, rs_aa = 0;
     const uint8_t *scan = nullptr;
     size_t scan_len = 0;
     // The scan still holds FF00 pairs (and RSTn markers): it is de-stuffed on the device at upload (k_destuff_*), scan_len is
@@ -114,6 +119,16 @@ int plan_output(ImagePlan &p, const mjx_output *out, size_t i);
 // ... applied to the plans of one input as plan_input left them (the last is the picture's): a multi-scan picture that is refused
 // takes its scans' plans with it, so that nothing of the file is uploaded or decoded.
 int plan_output_of_input(std::vector<ImagePlan> &plans, const mjx_output *out, size_t i);
+
+// Resize on the device.  resize_opts: the options input i is planned with under `rs` -- the call's own (auto_scale 0), or the scale
+// and the rectangle at that scale the auto-scale rule picks for a picture of width x height (`rect` is the storage the options
+// returned point at).  MJX_ERR_INVALID_ARG: a target of 0 (or above kResizeMaxDim), auto_scale with scale_denom > 1, REF_COMPAT, a
+// full-size rectangle outside the picture.  plan_resize marks the planned picture (the last plan of the input).
+// plan_input_for: plan_input + plan_resize + plan_output_of_input in the one order every entry point uses; rs == nullptr: as before.
+// A resize without an output description leaves interleaved u8 R,G,B, library-owned.
+int resize_opts(uint32_t width, uint32_t height, const mjx_opts &opts_i, const mjx_resize &rs, mjx_opts &eff, mjx_rect &rect);
+void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_output *out, const mjx_resize *rs, size_t i,
+                    std::vector<ImagePlan> &plans);
 
 // mjx_parse.cpp: mjx_parse with caller-lent storage for the de-stuffed scan (see there)
 int parse_into(const uint8_t *jpeg, size_t len, const mjx_opts *opts, mjx_scan_desc *out, uint8_t *storage, size_t cap);
