@@ -145,6 +145,38 @@ def grey_jpeg_from_blocks(blocks_zz, blocks_x, qt_zz, tables, qt16=False):
                       {(0, 0): tables[(0, 0)], (1, 0): tables[(1, 0)]}, ent, qt16=qt16)
 
 
+def jpeg_from_blocks(blocks, hv, mcux, mcuy, qts, tables, qt16=False, width=None, height=None, restart=None):
+    """grey_jpeg_from_blocks for any sampling layout: an interleaved baseline file whose blocks carry exactly the coefficients
+    given (tests/test_stageb_arithmetic.py).
+
+    blocks: int [mcux * mcuy * bpm, 64] in MCU-interleaved decode order (per MCU each component's v x h blocks, components in frame
+    order), zig-zag, absolute DC, before dequantisation.  hv: [(h, v)] per component, one or three of them (one component: a
+    non-interleaved scan of one block per MCU, and (h, v) only goes into the frame header).  qts: one table of 64 zig-zag entries
+    per component, component c on slot c.  tables: {(class, slot): (bits, vals)}; luminance codes with slot 0, chroma with slot 1
+    where the dictionary has one.  width, height: the frame's; default the whole MCU grid, smaller values clip the last MCUs
+    (they must still need all mcux x mcuy of them).  restart=n: DRI n and an RSTn marker every n MCUs."""
+    blocks = np.asarray(blocks, np.int64)
+    hv = [tuple(x) for x in hv]
+    assert len(hv) in (1, 3) and len(qts) == len(hv)
+    mcu_hv = [(1, 1)] if len(hv) == 1 else hv
+    hmax, vmax = max(h for h, _ in mcu_hv), max(v for _, v in mcu_hv)
+    per_mcu = [h * v for h, v in mcu_hv]
+    bpm = sum(per_mcu)
+    assert blocks.shape == (mcux * mcuy * bpm, 64), (blocks.shape, mcux, mcuy, bpm)
+    width = mcux * 8 * hmax if width is None else width
+    height = mcuy * 8 * vmax if height is None else height
+    assert -(-width // (8 * hmax)) == mcux and -(-height // (8 * vmax)) == mcuy, (width, height, mcux, mcuy)
+    slot = [0 if c == 0 or (0, 1) not in tables else 1 for c in range(len(hv))]
+    dc = {c: huff_codes(*tables[(0, slot[c])]) for c in range(len(hv))}
+    ac = {c: huff_codes(*tables[(1, slot[c])]) for c in range(len(hv))}
+    owner = [c for c, k in enumerate(per_mcu) for _ in range(k)] * (mcux * mcuy)
+    ent = encode_scan_np(blocks, owner, dc, ac, restart_blocks=(restart or 0) * bpm)
+    comps = [(c + 1, h, v, c, slot[c], slot[c]) for c, (h, v) in enumerate(hv)]
+    dhts = {(cls, s): tables[(cls, s)] for s in sorted(set(slot)) for cls in (0, 1)}
+    return write_jpeg(width, height, comps, {c: [int(v) for v in q] for c, q in enumerate(qts)}, dhts, ent, qt16=qt16,
+                      restart_interval=restart or 0)
+
+
 # ---- syntactically valid, semantically corrupt streams (SURVEY Q9) ---------------------------------------------------
 def full_ac_table():
     """An AC table that holds all 256 run/size symbols -- including the degenerate `0x?0` ones (r zeros then a 0,

@@ -65,8 +65,10 @@ def _basis(n):
     return m
 
 
-def planes(data, scale, dec=None):
-    """-> (width, height, comps, [scaled plane per component, float64, the full MCU grid], hmax, vmax)"""
+def planes(data, scale, dec=None, magnitude=False):
+    """-> (width, height, comps, [scaled plane per component, float64, the full MCU grid], hmax, vmax)
+    magnitude=True: the planes hold, at every sample, S_c of its block instead: sum |coef q| / 8 over the N x N corner the transform
+    reads (+ 128 on luminance) -- what a sample's rounding error scales with (rgb_interval)."""
     w, h, comps, qt = jpeg_tables(data)
     if dec is None:
         dec = orc.decode(data, layout=orc.LAYOUT_STD, ext_1bit=True, ext_dri=True, ext_multiscan=True)
@@ -84,7 +86,10 @@ def planes(data, scale, dec=None):
         nat = np.zeros_like(deq)
         nat[:, ZIGZAG] = deq                    # natural index = row (vertical frequency) * 8 + column
         F = nat.reshape(-1, 8, 8)[:, :n, :n]
-        S = 0.25 * np.einsum("yv,bvu,xu->byx", M, F, M)
+        if magnitude:
+            S = np.broadcast_to((np.abs(F).sum(axis=(1, 2)) / 8.0)[:, None, None], (F.shape[0], n, n))
+        else:
+            S = 0.25 * np.einsum("yv,bvu,xu->byx", M, F, M)
         if c == 0:
             S = S + 128.0
         S = S.reshape(mcuy, mcux, vc, hc, n, n).transpose(0, 2, 4, 1, 3, 5).reshape(mcuy * vc * n, mcux * hc * n)
@@ -99,23 +104,60 @@ def to_u8(x):
     return np.trunc(np.clip(np.round(x, 9), 0.0, 255.0)).astype(np.uint8)
 
 
-def scaled_rgb(data, scale, dec=None):
-    """-> the expected picture [ceil(H/s), ceil(W/s), 3] uint8 of `data` decoded at 1/scale (scale 1: the full-size picture)"""
-    w, h, comps, pl, hmax, vmax = planes(data, scale, dec)
+def _samples(data, scale, dec, magnitude=False):
+    """-> [per component the plane sample (or its block's magnitude) under every output pixel, float64 [ceil(H/s), ceil(W/s)]]"""
+    w, h, comps, pl, hmax, vmax = planes(data, scale, dec, magnitude)
     ow, oh = -(-w // scale), -(-h // scale)
     X, Y = np.arange(ow), np.arange(oh)
-    smp = []
-    for (hc, vc, _), p in zip(comps, pl):
-        smp.append(p[(Y * vc // vmax)[:, None], (X * hc // hmax)[None, :]])
+    return [p[(Y * vc // vmax)[:, None], (X * hc // hmax)[None, :]] for (hc, vc, _), p in zip(comps, pl)]
+
+
+def rgb_f64(data, scale, dec=None):
+    """-> the picture of `data` at 1/scale before the store, float64 [ceil(H/s), ceil(W/s), 3] (unclamped; one component: R = G = B)"""
+    smp = _samples(data, scale, dec)
     if len(smp) == 1:
-        v = to_u8(smp[0])
-        return np.repeat(v[:, :, None], 3, axis=2)
+        return np.repeat(smp[0][:, :, None], 3, axis=2)
     y, cb, cr = smp
     c_red, c_green, c_blue = 0.299, 0.587, 0.114
     r = cr * (2 - 2 * c_red) + y
     b = cb * (2 - 2 * c_blue) + y
     g = (y - c_blue * b - c_red * r) / c_green
-    return np.stack([to_u8(r), to_u8(g), to_u8(b)], axis=2)
+    return np.stack([r, g, b], axis=2)
+
+
+def scaled_rgb(data, scale, dec=None):
+    """-> the expected picture [ceil(H/s), ceil(W/s), 3] uint8 of `data` decoded at 1/scale (scale 1: the full-size picture)"""
+    return to_u8(rgb_f64(data, scale, dec))
+
+
+def magnitude(data, scale, dec=None):
+    """m = S_Y + 2 S_Cb + 2 S_Cr under every output pixel, float64 [ceil(H/s), ceil(W/s)]: S_c = sum |coef q| / 8 over the corner
+    of the block the pixel's sample of component c comes from (+ 128 on luminance).  Every float32 operation between the
+    coefficients and a channel value works on numbers no larger than this (the colour formula's chroma gains are below 2)."""
+    s = _samples(data, scale, dec, magnitude=True)
+    return s[0] if len(s) == 1 else s[0] + 2.0 * s[1] + 2.0 * s[2]
+
+
+def trunc_u8(x):
+    """clamp to [0, 255], truncate: to_u8 without its 1e-9 rounding (rgb_interval's delta takes its place)"""
+    return np.trunc(np.clip(x, 0.0, 255.0)).astype(np.uint8)
+
+
+def rgb_interval(data, scale, K, dec=None):
+    """-> (lo, hi), uint8 [ceil(H/s), ceil(W/s), 3]: the bytes a float32 decoder of `data` at 1/scale may produce.  With w the float64
+    value of a channel (rgb_f64) and m the pixel's magnitude, delta = K 2^-24 m, lo = trunc_u8(w - delta), hi = trunc_u8(w + delta):
+    K half-ulps of the largest number the sample's arithmetic handles.  lo == hi (nearly everywhere): the byte is float64's.
+    A channel whose components' blocks have nothing inside the corner (all N x N coefficients zero; R takes Y and Cr, B takes Y and
+    Cb, G all three) is exactly 128 in any arithmetic: there delta = 0 and lo = hi = 128."""
+    w = rgb_f64(data, scale, dec)
+    mag = _samples(data, scale, dec, magnitude=True)
+    e = [s == (128.0 if c == 0 else 0.0) for c, s in enumerate(mag)]
+    empty = np.stack([e[0]] * 3 if len(e) == 1 else [e[0] & e[2], e[0] & e[1] & e[2], e[0] & e[1]], axis=2)
+    m = mag[0] if len(mag) == 1 else mag[0] + 2.0 * mag[1] + 2.0 * mag[2]
+    d = (K * 2.0 ** -24 * m)[:, :, None]
+    lo, hi = trunc_u8(w - d), trunc_u8(w + d)
+    lo[empty], hi[empty] = 128, 128
+    return lo, hi
 
 
 def box_mean(rgb, s):
