@@ -114,7 +114,7 @@ def build_emul(force=False):
     src = os.path.join(d, "huff_emul.cpp")
     out = os.path.join(d, "libhuff_emul.so")
     host_only = [s for s in CXX_SOURCES if s != "mjx_pool.cpp"]      # (the pool needs the device entry points)
-    deps = [src] + [os.path.join(CSRC, s) for s in host_only + ["mjx_huff.h", "mjx_plan.h"]]
+    deps = [src] + [os.path.join(CSRC, s) for s in host_only + ["mjx_huff.h", "mjx_kernels.h", "mjx_plan.h"]]
     if os.path.exists(src) and (force or _newer(out, deps)):
         _link(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
                "-o", out, src] + [os.path.join(CSRC, s) for s in host_only], out)

@@ -384,6 +384,50 @@ struct DestuffImg {
     uint32_t pad_;
 };
 
+MJX_HD uint32_t mjx_popcount64(uint64_t v) { return uint32_t(__builtin_popcountll(v)); }
+
+// The rule of one 64-byte piece, shared by k_destuff_count, k_destuff_scatter and the CPU emulation (tests/emul: emul_destuff).
+// keep flags of the 64 bytes [i0, i0+64) of `raw` as a bit mask (+ the bytes themselves in q[0..3]); returns the
+// number of kept bytes.  *rst_out: bit j set = a marker FF Dn begins at byte j (restarts only).  The raw staging buffer is
+// 64-byte aligned per image and padded by 64 bytes (build_batch), so the four 16-byte loads of a piece and the byte behind
+// it stay inside the image's own region.  V4: four 32-bit words x, y, z, w that are loaded as one (uint4 on the device).
+template <class V4>
+MJX_HD uint32_t destuff_keep_mask(const uint8_t *raw, uint64_t i0, uint64_t raw_len, V4 q[4], uint64_t *mask_out, bool restarts,
+                                  uint64_t *rst_out)
+{
+    uint64_t mask = 0, rst = 0;
+    if (i0 < raw_len) {
+        const V4 *src = reinterpret_cast<const V4 *>(raw + i0);
+#pragma unroll
+        for (int k = 0; k < 4; k++) q[k] = src[k];
+        uint32_t prev = i0 > 0 ? raw[i0 - 1] : 0u;
+        const uint32_t n = uint32_t(raw_len - i0 < uint64_t(64) ? raw_len - i0 : uint64_t(64));
+        const uint32_t behind = i0 + 64 < raw_len ? raw[i0 + 64] : 0u;       // (a marker may straddle two pieces)
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t w[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const uint32_t b = (w[j >> 2] >> ((j & 3) * 8)) & 0xffu;
+                const uint32_t jj = uint32_t(k * 16 + j);
+                const uint32_t next = j < 15 ? (w[(j + 1) >> 2] >> (((j + 1) & 3) * 8)) & 0xffu
+                                             : (k < 3 ? (k == 0 ? q[1].x : k == 1 ? q[2].x : q[3].x) & 0xffu : behind);
+                bool keep = !(b == 0x00u && prev == 0xffu);
+                if (restarts) {
+                    const bool marker = b == 0xffu && (next & 0xf8u) == 0xd0u && jj + 1 < n + (i0 + 64 < raw_len ? 1u : 0u);
+                    if (marker) { keep = false; if (jj < n) rst |= 1ull << jj; }
+                    if ((b & 0xf8u) == 0xd0u && prev == 0xffu) keep = false;
+                }
+                if (keep && jj < n) mask |= 1ull << jj;
+                prev = b;
+            }
+        }
+    }
+    *mask_out = mask;
+    *rst_out = rst;
+    return mjx_popcount64(mask);
+}
+
 // mjx_batch_compare_rgb: one pair of pictures (device pointers: the pictures may live in different pools)
 struct RgbPair { const uint8_t *a, *b; uint64_t bytes; };
 

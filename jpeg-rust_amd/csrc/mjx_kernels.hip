@@ -1070,45 +1070,7 @@ __device__ __forceinline__ uint32_t wg_exclusive_scan(uint32_t v, uint32_t *s_tm
 //                       and the offsets of its markers into the scan's marker list
 //   k_restart_geometry  scans with restart intervals: the list becomes the picture's segment table (see locate_sub)
 // All of it runs once per upload, before any decode, on the upload stream.
-// keep flags of the 64 bytes [i0, i0+64) of `raw` as a bit mask (+ the bytes themselves in q[0..3]); returns the
-// number of kept bytes.  *rst_out: bit j set = a marker FF Dn begins at byte j (restarts only).  The raw staging buffer is
-// 64-byte aligned per image and padded by 64 bytes (build_batch), so the four 16-byte loads of a piece and the byte behind
-// it stay inside the image's own region.
-__device__ __forceinline__ uint32_t destuff_keep_mask(const uint8_t *raw, uint64_t i0, uint64_t raw_len, uint4 q[4],
-                                                      uint64_t *mask_out, bool restarts, uint64_t *rst_out)
-{
-    uint64_t mask = 0, rst = 0;
-    if (i0 < raw_len) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(raw + i0);
-#pragma unroll
-        for (int k = 0; k < 4; k++) q[k] = src[k];
-        uint32_t prev = i0 > 0 ? raw[i0 - 1] : 0u;
-        const uint32_t n = uint32_t(min(uint64_t(64), raw_len - i0));
-        const uint32_t behind = i0 + 64 < raw_len ? raw[i0 + 64] : 0u;       // (a marker may straddle two pieces)
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t w[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-                const uint32_t b = (w[j >> 2] >> ((j & 3) * 8)) & 0xffu;
-                const uint32_t jj = uint32_t(k * 16 + j);
-                const uint32_t next = j < 15 ? (w[(j + 1) >> 2] >> (((j + 1) & 3) * 8)) & 0xffu
-                                             : (k < 3 ? (k == 0 ? q[1].x : k == 1 ? q[2].x : q[3].x) & 0xffu : behind);
-                bool keep = !(b == 0x00u && prev == 0xffu);
-                if (restarts) {
-                    const bool marker = b == 0xffu && (next & 0xf8u) == 0xd0u && jj + 1 < n + (i0 + 64 < raw_len ? 1u : 0u);
-                    if (marker) { keep = false; if (jj < n) rst |= 1ull << jj; }
-                    if ((b & 0xf8u) == 0xd0u && prev == 0xffu) keep = false;
-                }
-                if (keep && jj < n) mask |= 1ull << jj;
-                prev = b;
-            }
-        }
-    }
-    *mask_out = mask;
-    *rst_out = rst;
-    return uint32_t(__popcll(mask));
-}
+// The rule of a lane's 64-byte piece is destuff_keep_mask (mjx_kernels.h): the kernels and the CPU emulation of the tests share it.
 
 extern "C" __global__ __launch_bounds__(256) void k_destuff_count(const DestuffImg *imgs, const uint8_t *raw,
                                                                    uint2 *segcount)

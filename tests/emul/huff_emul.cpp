@@ -680,3 +680,62 @@ extern "C" int emul_table_set(const uint8_t *jpeg, size_t len, uint32_t *out /* 
     mjx_free_scan(&d);
     return rc;
 }
+
+// ---- device-side de-stuffing and marker scan (tests/test_destuff_boundaries.py) ------------------------------------------------------
+// What k_destuff_count, k_destuff_prefix and k_destuff_scatter do, serially, with the kernels' own rule per 64-byte piece
+// (destuff_keep_mask, mjx_kernels.h): per 16 KiB workgroup the bytes kept and the markers found -> seg_counts[2 g], [2 g + 1];
+// exclusive sums of both; then every piece's kept bytes at workgroup base + offset inside the workgroup, and the offsets of its
+// markers into the list.  The input is copied into a buffer laid out as build_batch lays out the raw staging buffer -- 64-byte
+// aligned, 64 bytes of padding behind the length rounded up to 64, here filled with `pad` -- and not one byte longer, so that a
+// read the rule should not make is one AddressSanitizer sees.  Returns the de-stuffed length (-1: out_cap or rst_cap too small);
+// *n_rst: markers found.
+namespace {
+struct Word4 { uint32_t x, y, z, w; };          // the piece loads of the kernels are uint4
+}
+extern "C" long emul_destuff(const uint8_t *raw, size_t len, int restarts, int pad, uint8_t *out, size_t out_cap,
+                             uint32_t *rst_off, size_t rst_cap, uint32_t *seg_counts, uint32_t *n_rst)
+{
+    const size_t room = ((len + 63) & ~size_t(63)) + 64;
+    std::vector<Word4> store(room / sizeof(Word4));
+    uint8_t *buf = reinterpret_cast<uint8_t *>(store.data());
+    std::memset(buf, pad, room);
+    if (len) std::memcpy(buf, raw, len);
+    const uint32_t nseg = uint32_t((len + kDestuffSeg - 1) / kDestuffSeg), lanes = uint32_t(kDestuffSeg / 64);
+    std::vector<uint32_t> cnt(size_t(nseg) * 2), base(size_t(nseg) * 2);
+    for (uint32_t g = 0; g < nseg; g++)                                      // k_destuff_count
+        for (uint32_t t = 0; t < lanes; t++) {
+            uint64_t mask, rst;
+            Word4 q[4];
+            cnt[2 * g] += destuff_keep_mask(buf, uint64_t(g) * kDestuffSeg + t * 64ull, len, q, &mask, restarts != 0, &rst);
+            cnt[2 * g + 1] += mjx_popcount64(rst);
+        }
+    uint32_t run = 0, run_rst = 0;
+    for (uint32_t g = 0; g < nseg; g++) {                                    // k_destuff_prefix
+        base[2 * g] = run;
+        base[2 * g + 1] = run_rst;
+        run += cnt[2 * g];
+        run_rst += cnt[2 * g + 1];
+        if (seg_counts) { seg_counts[2 * g] = cnt[2 * g]; seg_counts[2 * g + 1] = cnt[2 * g + 1]; }
+    }
+    if (n_rst) *n_rst = run_rst;
+    if (run > out_cap || run_rst > rst_cap) return -1;
+    for (uint32_t g = 0; g < nseg; g++) {                                    // k_destuff_scatter
+        uint32_t o = 0, r = base[2 * g + 1];
+        for (uint32_t t = 0; t < lanes; t++) {
+            uint64_t mask, rst;
+            Word4 q[4];
+            (void)destuff_keep_mask(buf, uint64_t(g) * kDestuffSeg + t * 64ull, len, q, &mask, restarts != 0, &rst);
+            for (uint64_t m = rst; m; m &= m - 1) {
+                const uint32_t j = uint32_t(__builtin_ctzll(m));
+                rst_off[r++] = base[2 * g] + o + mjx_popcount64(mask & ((1ull << j) - 1ull));
+            }
+            for (int k = 0; k < 4; k++) {
+                const uint32_t w[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
+                for (int j = 0; j < 16; j++)
+                    if ((mask >> (k * 16 + j)) & 1) out[base[2 * g] + o++] = uint8_t(w[j >> 2] >> ((j & 3) * 8));
+            }
+        }
+        if (o != cnt[2 * g] || r != base[2 * g + 1] + cnt[2 * g + 1]) return -2;          // (the two kernels must count alike)
+    }
+    return long(run);
+}
