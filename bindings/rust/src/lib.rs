@@ -57,6 +57,15 @@ pub struct mjx_output {
     pub n_dst: u32,
 }
 
+/// Orientation on the device: the file's EXIF orientation and / or one code 1..8 per input on top (include/mjx.h: mjx_orient).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mjx_orient {
+    pub from_exif: u8,
+    pub extra: *const u8,
+    pub n_extra: u32,
+}
+
 /// Resize on the device: every picture of a call leaves at `width` x `height` (include/mjx.h: mjx_resize).
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -188,6 +197,16 @@ extern "C" {
                            rect: *mut mjx_rect, taps_x: *mut u32, taps_y: *mut u32) -> c_int;
     pub fn mjx_resize_weights(n_in: u32, n_out: u32, antialias: c_int, x: u32, first: *mut u32, weights: *mut f32, cap: usize,
                               count: *mut usize) -> c_int;
+    pub fn mjx_exif_orientation(jpeg: *const u8, len: usize, code: *mut u8) -> c_int;
+    pub fn mjx_orient_compose(first: u8, then: u8) -> u8;
+    pub fn mjx_batch_create_orient(ctx: *mut mjx_ctx, descs: *const mjx_scan_desc, n: usize, opts: *const mjx_opts, out: *const mjx_output,
+                                   rs: *const mjx_resize, orient: *const mjx_orient, b: *mut *mut mjx_batch, status: *mut c_int) -> c_int;
+    pub fn mjx_decode_batch_orient(ctx: *mut mjx_ctx, jpegs: *const *const u8, lens: *const usize, n: usize, opts: *const mjx_opts,
+                                   threads: c_uint, out: *const mjx_output, rs: *const mjx_resize, orient: *const mjx_orient,
+                                   status: *mut c_int, b: *mut *mut mjx_batch) -> c_int;
+    pub fn mjx_orient_plan(desc: *const mjx_scan_desc, opts: *const mjx_opts, rs: *const mjx_resize, code: u8, i: usize, out_w: *mut u32,
+                           out_h: *mut u32, stored_rect: *mut mjx_rect, scale_denom: *mut u8) -> c_int;
+    pub fn mjx_batch_image_orientation(b: *const mjx_batch, i: usize, code: *mut u8) -> c_int;
     pub fn mjx_batch_image_scale(b: *const mjx_batch, i: usize, scale_denom: *mut u8) -> c_int;
     pub fn mjx_batch_resize_rect(b: *const mjx_batch, i: usize, rect: *mut mjx_rect) -> c_int;
     pub fn mjx_batch_tile(ctx: *mut mjx_ctx, src: *const mjx_batch, times: usize, out: *mut *mut mjx_batch) -> c_int;

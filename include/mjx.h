@@ -160,6 +160,37 @@ typedef struct mjx_resize {
     uint8_t auto_scale;       /* 1: the library picks the DCT-domain scale per picture; rois are in full-size coordinates */
 } mjx_resize;
 
+/* ---- orientation on the device: EXIF orientation, with per-picture flips on top -----------------------------------------
+ * A camera file stores its pixels as the sensor saw them and names, in EXIF tag 0x0112, one of eight ways to turn them upright.
+ * S is the stored picture (h rows of w) at the call's scale, D = orient_c(S) the picture that leaves:
+ *   code  D[y][x]               size      |  code  D[y][x]               size
+ *    1    S[y][x]               w x h     |   5    S[x][y]               h x w
+ *    2    S[y][w-1-x]           w x h     |   6    S[h-1-x][y]           h x w
+ *    3    S[h-1-y][w-1-x]       w x h     |   7    S[h-1-x][w-1-y]       h x w
+ *    4    S[h-1-y][x]           w x h     |   8    S[x][w-1-y]           h x w
+ * With an orientation description (mjx_batch_create_orient, mjx_decode_batch_orient) picture i has the resolved code c: the file's
+ * own tag (from_exif; mjx_exif_orientation) followed by extra[i] (mjx_orient_compose) -- a horizontal flip as augmentation is
+ * extra[i] = 2.  rois[i] is in D's coordinates (full-size D with auto_scale); the planner maps it back to S (full-size S with
+ * auto_scale, after which the outward rounding above applies unchanged) and plans the picture as the cropped packed picture at
+ * (s, R_S): stage B still reads only the tiles that touch the rectangle, and that packed picture is the intermediate I.
+ * Without a resize an element of the output is mjx_output's table applied to the byte of I at the mapped pixel, bit for bit, in
+ * every format (U8 outputs are a permutation of I's bytes).  With a resize the output is the resize rule above applied to
+ * orient_c(I): axis sizes, taps and mjx_resize_plan's taps_x / taps_y are in D's axes.
+ * c == 1 without a resize: the picture is planned exactly as mjx_batch_create_out plans it (no intermediate, no further launch);
+ * c == 1 with a resize: exactly as mjx_batch_create_resize.  A batch built through these entry points always carries an output
+ * description: out == NULL is interleaved u8 R,G,B, library-owned.
+ * Per picture, MJX_ERR_INVALID_ARG (the others are unaffected): a code outside 1 .. 8 in extra; a rectangle outside D;
+ * MJX_LAYOUT_REF_COMPAT with c != 1; dst[i] of another size than D's rectangle or the target; and the rules above.  n_extra other
+ * than 0 or the call's number of inputs, or extra == NULL with n_extra != 0, fails the call.
+ * An oriented batch: mjx_batch_image_info and mjx_batch_output_info speak of the picture that leaves, mjx_batch_image_roi and
+ * mjx_batch_resize_rect stay in S's coordinates (they describe the intermediate), mjx_batch_image_orientation gives c;
+ * mjx_batch_tile carries the code along (library-owned output only).  Not built: mjx_decode, the pool and the CLI do not turn. */
+typedef struct mjx_orient {
+    uint8_t from_exif;        /* 1: picture i starts from the code mjx_exif_orientation finds in file i */
+    const uint8_t *extra;     /* NULL, or one code 1..8 per input, applied AFTER the EXIF one (mjx_orient_compose) */
+    uint32_t n_extra;         /* 0 with extra == NULL, else the call's number of inputs */
+} mjx_orient;
+
 /* ---- inner seam: what jpeg/mod.rs:388-415 hands to JPEGDecoder -------------------------- */
 typedef struct mjx_comp {          /* decoder.rs:39-52 JPEGDecoderComponentFields */
     uint8_t id, h, v, tq, td, ta;
@@ -223,6 +254,15 @@ typedef struct mjx_image {         /* JPEGImage: width() mod.rs:467, height() :4
  * exactly as mod.rs:228-362 does, de-stuffs the scan (mod.rs:371-385).  Release with mjx_free_scan. */
 int mjx_parse(const uint8_t *jpeg, size_t len, const mjx_opts *opts, mjx_scan_desc *out);
 void mjx_free_scan(mjx_scan_desc *desc);
+
+/* Host-only: the EXIF orientation of a file.  Walks the markers up to the first SOS, takes the first APP1 whose payload starts
+ * "Exif\0\0", reads the TIFF header (either byte order) and IFD0 and looks for tag 0x0112 of type SHORT, count 1.  Everything else --
+ * no such segment, no tag, another type or count, a value outside 1 .. 8, an offset or an entry count that points outside the
+ * segment, a file that ends inside it -- gives *code = 1 and MJX_OK; nothing outside [jpeg, jpeg + len) is read.  Only NULL arguments
+ * are an error.  mjx_parse is not involved (it skips APP1; with strict_ref it still refuses it). */
+int mjx_exif_orientation(const uint8_t *jpeg, size_t len, uint8_t *code);
+/* The one code that does what `first` followed by `then` does; 0 when either lies outside 1 .. 8. */
+uint8_t mjx_orient_compose(uint8_t first, uint8_t then);
 
 /* Host-only check of a parsed scan: tables present and valid, geometry supported and, for MJX_LAYOUT_REF_COMPAT, not
  * one of the inputs on which the reference's placement code panics (decoder.rs:300-303, 370-371; SURVEY Q5 ->
@@ -300,6 +340,17 @@ int mjx_resize_plan(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_r
 int mjx_resize_weights(uint32_t n_in, uint32_t n_out, int antialias, uint32_t X, uint32_t *first, float *weights, size_t cap,
                        size_t *count);
 
+/* mjx_batch_create_resize with an orientation description (above); orient == NULL: mjx_batch_create_resize itself.  Descriptors
+ * carry no file bytes: from_exif = 1 is MJX_ERR_INVALID_ARG for the call -- read the tag with mjx_exif_orientation and pass it in
+ * extra. */
+int mjx_batch_create_orient(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_output *out,
+                            const mjx_resize *rs, const mjx_orient *orient, mjx_batch **b, int *status);
+/* Host-only, from the planner itself, in the spirit of mjx_plan_tiles: picture `desc` as input i of a call with these options, this
+ * resize (or NULL) and the resolved code `code` -- the size of the picture that leaves, the rectangle of the stored picture its
+ * intermediate covers (at the scale it is decoded at) and that scale.  Returns the picture's status. */
+int mjx_orient_plan(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_resize *rs, uint8_t code, size_t i, uint32_t *out_w,
+                    uint32_t *out_h, mjx_rect *stored_rect, uint8_t *scale_denom);
+
 /* Replicate the uploaded images `times`x on the device (image i*n+k is a byte copy of image k): builds the
  * large synthetic batches of BASELINE.json configs 4/5 from n unique images without re-uploading.  The copies keep their
  * source's scale and rectangle. */
@@ -322,6 +373,8 @@ int mjx_batch_image_info(const mjx_batch *b, size_t i, uint32_t *width, uint32_t
 int mjx_batch_image_roi(const mjx_batch *b, size_t i, uint32_t *x, uint32_t *y, uint32_t *full_width, uint32_t *full_height);
 /* the DCT-domain scale picture i was decoded at (1, 2, 4 or 8): the call's, or the one auto_scale picked */
 int mjx_batch_image_scale(const mjx_batch *b, size_t i, uint8_t *scale_denom);
+/* the orientation code picture i left with (1 .. 8: the file's tag followed by extra[i]; 1 for any batch without an orientation) */
+int mjx_batch_image_orientation(const mjx_batch *b, size_t i, uint8_t *code);
 /* a resized batch: the rectangle R picture i's intermediate covers, in the coordinates of the picture at its scale
  * (mjx_batch_image_roi: that picture's size); any other batch: the picture's own rectangle */
 int mjx_batch_resize_rect(const mjx_batch *b, size_t i, mjx_rect *rect);
@@ -371,7 +424,8 @@ enum {
     MJX_K_HUFF_EMIT = 8,  /* single decode (pictures of one scan without restart intervals): the first decode, which emits -- instead of
                              MJX_K_HUFF_SYNC and the decode of MJX_K_HUFF_WRITE */
     MJX_K_HUFF_PREFIX = 9,/* ... the prefixes of the subsequences whose entry state was wrong, and block words -> DC differences + tile offsets */
-    MJX_K_RESIZE = 10,    /* resize on the device (k_resize_out): no launches for a batch without a resize description */
+    MJX_K_RESIZE = 10,    /* the pass behind stage B that brings a picture to the form it leaves in: resize on the device (k_resize_out),
+                             orientation (k_orient_out, k_resize_orient).  No launches for a batch without a resized or oriented picture */
     MJX_K_COUNT = 11
 };
 int mjx_batch_kernel_ms(mjx_batch *b, double ms[MJX_K_COUNT], uint64_t launches[MJX_K_COUNT], int reset);
@@ -403,6 +457,12 @@ int mjx_decode_batch_out(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t
  * dst[i] do.  rs == NULL: mjx_decode_batch_out.  out == NULL with a resize: interleaved u8 R,G,B, library-owned. */
 int mjx_decode_batch_resize(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
                             unsigned threads, const mjx_output *out, const mjx_resize *rs, int *status, mjx_batch **b);
+
+/* mjx_decode_batch_resize with an orientation description; the code goes with file i through the groups of the pipelined call, as
+ * rois[i], dst[i] and rs do, and the worker that plans file i reads its tag.  orient == NULL: mjx_decode_batch_resize. */
+int mjx_decode_batch_orient(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
+                            unsigned threads, const mjx_output *out, const mjx_resize *rs, const mjx_orient *orient, int *status,
+                            mjx_batch **b);
 
 /* ---- multi-GPU front: one context + one host thread + one work queue per device, no collective ----------
  * Pictures are independent (decoder.rs:162-343 touches only `self`), so a list of files shards over the GPUs of a node

@@ -70,6 +70,11 @@ class ResizeDesc(ctypes.Structure):
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("antialias", ctypes.c_uint8), ("auto_scale", ctypes.c_uint8)]
 
 
+class OrientDesc(ctypes.Structure):
+    """mjx_orient: where a picture's orientation code comes from (see Orient)."""
+    _fields_ = [("from_exif", ctypes.c_uint8), ("extra", ctypes.POINTER(ctypes.c_uint8)), ("n_extra", ctypes.c_uint32)]
+
+
 DTYPE_U8, DTYPE_F16, DTYPE_F32 = 0, 1, 2
 _NP_DTYPES = {DTYPE_U8: np.uint8, DTYPE_F16: np.float16, DTYPE_F32: np.float32}
 
@@ -120,6 +125,12 @@ SYMBOLS = {
     "mjx_decode_batch_resize": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(OutputDesc), _P(ResizeDesc), _P(_int), _P(_vp)]),
     "mjx_resize_plan": (_int, [_P(ScanDesc), _P(Opts), _P(ResizeDesc), _sz, _P(ctypes.c_uint8), _P(Rect), _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
     "mjx_resize_weights": (_int, [ctypes.c_uint32, ctypes.c_uint32, _int, ctypes.c_uint32, _P(ctypes.c_uint32), _P(ctypes.c_float), _sz, _P(_sz)]),
+    "mjx_exif_orientation": (_int, [ctypes.c_char_p, _sz, _P(ctypes.c_uint8)]),
+    "mjx_orient_compose": (ctypes.c_uint8, [ctypes.c_uint8, ctypes.c_uint8]),
+    "mjx_batch_create_orient": (_int, [_vp, _P(ScanDesc), _sz, _P(Opts), _P(OutputDesc), _P(ResizeDesc), _P(OrientDesc), _P(_vp), _P(_int)]),
+    "mjx_decode_batch_orient": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(OutputDesc), _P(ResizeDesc), _P(OrientDesc), _P(_int), _P(_vp)]),
+    "mjx_orient_plan": (_int, [_P(ScanDesc), _P(Opts), _P(ResizeDesc), ctypes.c_uint8, _sz, _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(Rect), _P(ctypes.c_uint8)]),
+    "mjx_batch_image_orientation": (_int, [_vp, _sz, _P(ctypes.c_uint8)]),
     "mjx_batch_image_scale": (_int, [_vp, _sz, _P(ctypes.c_uint8)]),
     "mjx_batch_resize_rect": (_int, [_vp, _sz, _P(Rect)]),
     "mjx_decode_batch": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(_P(ctypes.c_uint8)), _P(_int), _P(_vp)]),
@@ -294,6 +305,44 @@ def _rs_ref(resize):
     return d, ctypes.byref(d)
 
 
+class Orient:
+    """Orientation on the device (mjx.h: mjx_orient): picture i leaves turned by its EXIF orientation tag (exif=True; read from the
+    file's bytes) followed by extra[i] -- None, one code 1..8 for every picture, or a list with one per picture (2 is the horizontal
+    flip).  Rectangles are then in the coordinates of the picture that leaves."""
+
+    def __init__(self, exif=True, extra=None):
+        self.exif = bool(exif)
+        self.extra = extra
+
+    def codes(self, n):
+        if self.extra is None:
+            return None
+        return [int(self.extra)] * n if isinstance(self.extra, (int, np.integer)) else [int(c) for c in self.extra]
+
+    def desc(self, n, exif=None):
+        """-> (what must stay alive, the mjx_orient); exif=False: the tags have been folded into `extra` already."""
+        codes = self.codes(n)
+        arr = (ctypes.c_uint8 * max(len(codes), 1))(*codes) if codes is not None else None
+        d = OrientDesc(int(self.exif if exif is None else exif), ctypes.cast(arr, _P(ctypes.c_uint8)) if arr is not None else None,
+                       len(codes) if codes is not None else 0)
+        return (arr, d), d
+
+
+def exif_orientation(data):
+    """mjx_exif_orientation (host only): the EXIF orientation code 1..8 of a file; 1 when it has no readable tag."""
+    c = ctypes.c_uint8()
+    _check(lib().mjx_exif_orientation(bytes(data), len(data), ctypes.byref(c)), "mjx_exif_orientation")
+    return c.value
+
+
+def orient_compose(first, then):
+    """mjx_orient_compose: the one code that does what `first` followed by `then` does."""
+    c = int(lib().mjx_orient_compose(int(first), int(then)))
+    if not c:
+        raise MjxError(ERR_INVALID_ARG, "orient_compose(%r, %r)" % (first, then))
+    return c
+
+
 def resize_weights(n_in, n_out, antialias, X):
     """mjx_resize_weights (host only; the routine the resize kernel runs) -> (first input index, float32 weights of the window)."""
     first, cnt = ctypes.c_uint32(), _sz()
@@ -356,6 +405,16 @@ class ParsedScan:
         _check(lib().mjx_resize_plan(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(s), ctypes.byref(r), ctypes.byref(tx), ctypes.byref(ty)), "mjx_resize_plan")
         return dict(scale=s.value, rect=(r.x, r.y, r.w, r.h), taps_x=tx.value, taps_y=ty.value)
 
+    def orient_plan(self, code, resize=None, roi=None, scale=1, i=0, layout=LAYOUT_STANDARD):
+        """mjx_orient_plan (host only) -> dict(width, height, stored_rect=(x, y, w, h), scale): the picture that leaves when this one is
+        decoded with orientation code `code` (roi in the oriented picture's coordinates), and what is decoded for it."""
+        o = _opts(layout=layout, scale=scale, rois=roi)
+        keep, ref = _rs_ref(resize)
+        w, h, r, s = ctypes.c_uint32(), ctypes.c_uint32(), Rect(), ctypes.c_uint8()
+        _check(lib().mjx_orient_plan(ctypes.byref(self.desc), ctypes.byref(o), ref, int(code), int(i), ctypes.byref(w), ctypes.byref(h),
+                                     ctypes.byref(r), ctypes.byref(s)), "mjx_orient_plan")
+        return dict(width=w.value, height=h.value, stored_rect=(r.x, r.y, r.w, r.h), scale=s.value)
+
     def close(self):
         if self._owned:
             lib().mjx_free_scan(ctypes.byref(self.desc))
@@ -403,7 +462,7 @@ class Batch:
     """Device-resident batch: inputs uploaded at construction, ``decode()`` only enqueues kernels."""
 
     def __init__(self, ctx, scans=None, strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0,
-                 _handle=None, scale=1, rois=None, output=None, resize=None):
+                 _handle=None, scale=1, rois=None, output=None, resize=None, orient=None, datas=None):
         """scale: 1, 2, 4 or 8 -- every picture decoded at 1/scale (info(), rgb(), rgb_device() and bytes() then speak of the
         scaled picture; tile() keeps the scale).
         rois: one (x, y, w, h) for every picture, or a list with one per picture (None or (0, 0, 0, 0): the whole picture), in the
@@ -413,7 +472,10 @@ class Batch:
         such a batch), in the batch's memory or, Output(dst=...), in device memory of the caller's: idle when decode() is called,
         complete when wait() returns.
         resize: a Resize -- every picture leaves at its width x height, through `output` (None: interleaved uint8); info(),
-        output_info() and output() speak of the target picture, scale(i) and rect(i) of what was decoded for it."""
+        output_info() and output() speak of the target picture, scale(i) and rect(i) of what was decoded for it.
+        orient: an Orient -- every picture leaves turned (orientation(i): by which code), rois are in the coordinates of the turned
+        picture, info(), output_info() and output() speak of it, roi(i) and rect(i) of the stored picture.  Parsed scans hold no
+        EXIF segment: with Orient(exif=True) pass the files' bytes as `datas`, and the tags are read from them here."""
         self.ctx = ctx
         self.h = _vp()
         if _handle is not None:
@@ -427,7 +489,18 @@ class Batch:
         st = (_int * max(n, 1))()
         o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois)
         keep, ref = _out_ref(output)
-        if resize is not None:
+        if orient is not None:
+            if orient.exif:
+                if datas is None or len(datas) != n:
+                    raise MjxError(ERR_INVALID_ARG, "Orient(exif=True) needs the files' bytes: datas")
+                extra = orient.codes(n) or [1] * n
+                if len(extra) != n:
+                    raise MjxError(ERR_INVALID_ARG, "Orient(extra=...): %d codes for %d pictures" % (len(extra), n))
+                orient = Orient(False, [orient_compose(exif_orientation(d), e) if 1 <= e <= 8 else e for d, e in zip(datas, extra)])
+            keep_rs, rs_ref = _rs_ref(resize)
+            keep_or, od = orient.desc(n, exif=False)
+            _check(lib().mjx_batch_create_orient(ctx.h, arr, n, ctypes.byref(o), ref, rs_ref, ctypes.byref(od), ctypes.byref(self.h), st), "mjx_batch_create_orient")
+        elif resize is not None:
             keep_rs, rs_ref = _rs_ref(resize)
             _check(lib().mjx_batch_create_resize(ctx.h, arr, n, ctypes.byref(o), ref, rs_ref, ctypes.byref(self.h), st), "mjx_batch_create_resize")
         else:
@@ -467,6 +540,12 @@ class Batch:
         """The DCT-domain scale picture i was decoded at: the call's, or the one Resize(auto_scale=True) picked."""
         v = ctypes.c_uint8()
         lib().mjx_batch_image_scale(self.h, i, ctypes.byref(v))
+        return v.value
+
+    def orientation(self, i):
+        """The orientation code picture i left with: the file's tag followed by its extra code (1: as stored)."""
+        v = ctypes.c_uint8(1)
+        lib().mjx_batch_image_orientation(self.h, i, ctypes.byref(v))
         return v.value
 
     def rect(self, i):
@@ -737,10 +816,11 @@ class JPEGImage:
 
 
 def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False, scale=1, rois=None,
-                 output=None, chunk_images=0, resize=None):
+                 output=None, chunk_images=0, resize=None, orient=None):
     """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale, rois: see Batch.
     device_destuff: the host copies the entropy-coded bytes as they are; de-stuffing, restart markers and the scan's length
-    are found on the GPU.  output: an Output (mjx_decode_batch_out) -- see Batch.  resize: a Resize (mjx_decode_batch_resize)."""
+    are found on the GPU.  output: an Output (mjx_decode_batch_out) -- see Batch.  resize: a Resize (mjx_decode_batch_resize).  orient: an Orient
+    (mjx_decode_batch_orient): the files' EXIF orientation and / or a code per file on top."""
     n = len(datas)
     arr = (ctypes.c_char_p * max(n, 1))(*[bytes(d) for d in datas])
     lens = (_sz * max(n, 1))(*[len(d) for d in datas])
@@ -748,6 +828,12 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
     h = _vp()
     o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois)
+    if orient is not None:
+        keep, ref = _out_ref(output)
+        keep_rs, rs_ref = _rs_ref(resize)
+        keep_or, od = orient.desc(n)
+        _check(lib().mjx_decode_batch_orient(ctx.h, arr, lens, n, ctypes.byref(o), int(threads), ref, rs_ref, ctypes.byref(od), st, ctypes.byref(h)), "mjx_decode_batch_orient")
+        return Batch(ctx, _handle=h), list(st)[:n]
     if resize is not None:
         keep, ref = _out_ref(output)
         keep_rs, rs_ref = _rs_ref(resize)
@@ -761,7 +847,8 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     return Batch(ctx, _handle=h), list(st)[:n]
 
 
-def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=False, threads=0, device_destuff=None, planar=None, resize=None):
+def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=False, threads=0, device_destuff=None, planar=None, resize=None,
+                orient=None):
     """Decodes the files straight into a torch tensor on the context's device: N x 3 x H x W (planar) or N x H x W x 3, of uint8,
     float16 or float32; picture i -- at 1/scale, its rectangle rois[i] -- must be H x W.  Float tensors take (v / 255 - mean) / std
     per OUTPUT channel (see Output); bgr: channel 0 is blue.  The pointers and pitches come from data_ptr() and stride(): the
@@ -772,7 +859,8 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
     torch's current stream is synchronised before the call (the library writes on streams of its
     own) and the batch is complete when this returns.  -> the per-picture statuses.
     resize: True, or a Resize (its antialias and auto_scale; a size, if it names one, must be the tensor's) -- the pictures, of any
-    size, are resampled on the device to the tensor's H x W (see Resize); None: every picture must be H x W as it is."""
+    size, are resampled on the device to the tensor's H x W (see Resize); None: every picture must be H x W as it is.
+    orient: an Orient -- the pictures are turned on the device (see Orient); H x W and rois speak of the turned pictures."""
     import torch
     n = len(datas)
     if not isinstance(out, torch.Tensor) or out.dim() != 4 or out.shape[0] != n:
@@ -811,7 +899,7 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
             raise MjxError(ERR_INVALID_ARG, "resize to %d x %d into a tensor of %d x %d" % (resize.width, resize.height, w, h))
     else:
         rs = None
-    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt, resize=rs)
+    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt, resize=rs, orient=orient)
     batch.close()
     return status
 
@@ -947,6 +1035,15 @@ def resize_plan(data, resize, roi=None, scale=1):
     scan = ParsedScan(data)
     try:
         return scan.resize_plan(resize, roi=roi, scale=scale)
+    finally:
+        scan.close()
+
+
+def orient_plan(data, code, resize=None, roi=None, scale=1):
+    """Host only: the picture that leaves when this file is decoded with orientation code `code` -> see ParsedScan.orient_plan."""
+    scan = ParsedScan(data)
+    try:
+        return scan.orient_plan(code, resize=resize, roi=roi, scale=scale)
     finally:
         scan.close()
 

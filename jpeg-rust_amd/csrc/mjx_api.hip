@@ -135,6 +135,7 @@ struct ImageInfo {
     // the full_w x full_h picture at `scale`) and lies at DevImage::rgb_off; rgb_off here is the output's place in the pool
     bool rs_on = false;
     uint32_t scale = 1, src_w = 0, src_h = 0;
+    uint32_t orient = 1;           // orientation on the device: the picture that leaves is orient_c of the intermediate (rs_on is set for c != 1)
     uint64_t coef_off = 0;         // blocks, inside the per-block arrays of its chunk (or of the batch with keep_coefs)
     uint64_t ent_off = 0, ent_cap = 0;   // region of the compact coefficient stream (entries)
     uint32_t ent_rows = 0, ent_hdr = 0;  // > 0: quad-interleaved (DevImage::ent_rows, ent_hdr)
@@ -165,6 +166,7 @@ struct Chunk {
     uint32_t max_dc_wgs = 0;       // scaled decode at 1/8: workgroups of k_dc_color for the chunk's largest picture
     uint32_t max_dc_roi_wgs = 0;   // ... and of k_dc_color_roi for its largest rectangle
     uint32_t max_dc_out_wgs = 0;   // ... and of k_dc_color_out for its largest picture with an output description
+    uint32_t max_or_tiles = 0, max_rso_tiles = 0;     // orientation on the device: workgroups of k_orient_out for the chunk's largest oriented picture, of k_resize_orient for its largest target (0: none)
     uint32_t max_rs_tiles = 0;     // resize on the device: workgroups of k_resize_out for the chunk's largest target (0: no picture is resized)
     uint32_t max_b_tiles = 0;      // tiles the workgroups of stage B walk in the chunk's largest picture: all its tiles, or those of its
                                    // rectangle's MCU rows (DevImage::roi_ntiles) -- max_tiles without rectangles
@@ -505,7 +507,9 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
     // (a resized picture keeps the packed forms: its description is k_resize_out's, behind stage B)
     if (p.out_on) {
         if (!p.rs_on) d.mode = d.mode % kRoiMode + kOutMode;
-        d.rs_on = p.rs_on ? 1u : 0u;
+        d.rs_on = p.rs_on && p.orient == 1 ? 1u : 0u;
+        d.orient = p.orient;                                     // (an oriented picture is k_orient_out's or k_resize_orient's)
+        d.or_on = !p.rs_on || p.orient == 1 ? 0u : p.or_copy ? 1u : 2u;
         d.rs_w = p.rs_w; d.rs_h = p.rs_h; d.rs_aa = p.rs_aa;
         d.out_dev = p.out_dev;
         d.out_row_pitch = p.out_row_pitch; d.out_plane_pitch = p.out_plane_pitch;
@@ -620,6 +624,8 @@ void plan_chunks(mjx_batch *b)
                 if (d.mode == 5) c.max_dc_wgs = std::max<uint32_t>(c.max_dc_wgs, uint32_t((uint64_t(d.out_w) * d.out_h + 255) / 256));
                 if (d.mode == 5 + kOutMode) c.max_dc_out_wgs = std::max<uint32_t>(c.max_dc_out_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
                 if (d.rs_on && d.role != 1) c.max_rs_tiles = std::max<uint32_t>(c.max_rs_tiles, resize_tiles(d.rs_w, d.rs_h));
+                if (d.or_on == 1 && d.role != 1) c.max_or_tiles = std::max<uint32_t>(c.max_or_tiles, orient_tiles(d.rs_w, d.rs_h));
+                if (d.or_on == 2 && d.role != 1) c.max_rso_tiles = std::max<uint32_t>(c.max_rso_tiles, resize_tiles(d.rs_w, d.rs_h));
                 if (d.mode == 5 + kRoiMode) c.max_dc_roi_wgs = std::max<uint32_t>(c.max_dc_roi_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
                 if (d.mode == 2) {
                     d.plane_off = c.plane_words;
@@ -937,6 +943,16 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
         if (c.max_rs_tiles) {          // resize on the device: the chunk's intermediates -> the target pictures, behind its stage B
             prof_begin(b, MJX_K_RESIZE, sp);
             launch_resize_out(sp, c.max_rs_tiles, nimg, imgs, b->d_rgb, b->d_img_flags);
+            prof_end(b, sp);
+        }
+        if (c.max_or_tiles) {          // orientation on the device, the same class: the pass behind stage B that brings a picture to the form it leaves in
+            prof_begin(b, MJX_K_RESIZE, sp);
+            launch_orient_out(sp, c.max_or_tiles, nimg, imgs, b->d_rgb, b->d_img_flags);
+            prof_end(b, sp);
+        }
+        if (c.max_rso_tiles) {
+            prof_begin(b, MJX_K_RESIZE, sp);
+            launch_resize_orient(sp, c.max_rso_tiles, nimg, imgs, b->d_rgb, b->d_img_flags);
             prof_end(b, sp);
         }
         if (sp != st) {
@@ -1280,6 +1296,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 // resize on the device: the packed intermediate first (always in the pool), then the output's region
                 rgb_pool += align_up(inf.rgb_bytes, 256);
                 inf.rs_on = true;
+                inf.orient = p.orient;
                 inf.src_w = p.roi_w; inf.src_h = p.roi_h;
                 inf.width = p.rs_w; inf.height = p.rs_h;
                 inf.rgb_off = rgb_pool;
@@ -1813,19 +1830,44 @@ extern "C" int mjx_batch_create_out(mjx_ctx *ctx, const mjx_scan_desc *descs, si
 extern "C" int mjx_batch_create_resize(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_output *fmt,
                                        const mjx_resize *rs, mjx_batch **out, int *status)
 {
+    return mjx_batch_create_orient(ctx, descs, n, opts, fmt, rs, nullptr, out, status);
+}
+
+// Orientation: does orient->extra / n_extra fit a call of n inputs, and the resolved code of input i -- the file's own tag (from_exif,
+// where there are file bytes) followed by extra[i]; 0 for a code outside 1 .. 8, which fails that picture in plan_input_for.
+static bool orient_fits(const mjx_orient *orient, size_t n)
+{
+    if (!orient) return true;
+    return orient->extra ? orient->n_extra == n : orient->n_extra == 0;
+}
+static uint32_t orient_code(const mjx_orient *orient, size_t i, const uint8_t *jpeg, size_t len)
+{
+    if (!orient) return 1;
+    uint8_t c = 1;
+    if (orient->from_exif && jpeg) (void)mjx_exif_orientation(jpeg, len, &c);
+    return orient->extra ? orient_compose(c, orient->extra[i]) : c;
+}
+// an orientation always comes with an output description: without one, interleaved u8 R,G,B, library-owned (as a resize)
+static const mjx_output kPackedOutput = {MJX_DTYPE_U8, 0, 0, {1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}, nullptr, 0};
+
+extern "C" int mjx_batch_create_orient(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_output *fmt,
+                                       const mjx_resize *rs, const mjx_orient *orient, mjx_batch **out, int *status)
+{
     return guarded([&]() -> int {
     if (!ctx || !out || (!descs && n)) return MJX_ERR_INVALID_ARG;
     *out = nullptr;
     mjx_opts o{};
     if (opts) o = *opts;
-    if (!rois_fit(o, n) || !output_fits(fmt, n)) return MJX_ERR_INVALID_ARG;
+    if (!rois_fit(o, n) || !output_fits(fmt, n) || !orient_fits(orient, n)) return MJX_ERR_INVALID_ARG;
+    if (orient && orient->from_exif) return MJX_ERR_INVALID_ARG;       // (descriptors carry no file bytes: mjx_exif_orientation, then `extra`)
+    if (orient && !fmt) fmt = &kPackedOutput;
     const mjx_scan_desc *dd = descs;
     std::vector<ImagePlan> plans;
     std::vector<size_t> plan_of(n);                    // input i -> its picture's plan (multi-scan files add plans in front)
     plans.reserve(n);
     const auto tp0 = std::chrono::steady_clock::now();
     for (size_t i = 0; i < n; i++) {
-        plan_input_for(dd[i], opts_for_input(o, n, i), fmt, rs, i, plans);      // (rois[i] and dst[i] go with input i: a multi-scan file's picture plan takes them)
+        plan_input_for(dd[i], opts_for_input(o, n, i), fmt, rs, i, plans, orient_code(orient, i, nullptr, 0));      // (rois[i], dst[i] and extra[i] go with input i: a multi-scan file's picture plan takes them)
         plan_of[i] = plans.size() - 1;
     }
     if (std::getenv("MJX_TIMING"))
@@ -1947,6 +1989,31 @@ extern "C" int mjx_resize_weights(uint32_t n_in, uint32_t n_out, int antialias, 
     return MJX_OK;
 }
 
+// Host-only: what an oriented decode of this picture as input i takes and gives -- the planner's own (plan_input_for): the size of
+// the picture that leaves, the rectangle of the stored picture the intermediate covers and the scale it is decoded at.
+extern "C" int mjx_orient_plan(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_resize *rs, uint8_t code, size_t i,
+                               uint32_t *out_w, uint32_t *out_h, mjx_rect *stored_rect, uint8_t *scale_denom)
+{
+    return guarded([&]() -> int {
+    if (!desc) return MJX_ERR_INVALID_ARG;
+    mjx_opts o{};
+    if (opts) o = *opts;
+    if (!o.rois ? o.n_rois != 0 : (o.n_rois == 0 || (o.n_rois > 1 && i >= o.n_rois))) return MJX_ERR_INVALID_ARG;
+    if (o.rois) { if (o.n_rois > 1) o.rois += i; o.n_rois = 1; }
+    std::vector<ImagePlan> plans;
+    plan_input_for(*desc, o, &kPackedOutput, rs, 0, plans, code);
+    const ImagePlan &p = plans.back();
+    if (p.status != MJX_OK) return p.status;
+    if (out_w) *out_w = p.rs_on ? p.rs_w : p.roi_w;
+    if (out_h) *out_h = p.rs_on ? p.rs_h : p.roi_h;
+    if (stored_rect) *stored_rect = mjx_rect{p.roi_x, p.roi_y, p.roi_w, p.roi_h};
+    if (scale_denom) *scale_denom = uint8_t(p.scale);
+    return MJX_OK;
+    });
+}
+
+extern "C" uint8_t mjx_orient_compose(uint8_t first, uint8_t then) { return uint8_t(orient_compose(first, then)); }
+
 extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, mjx_batch **out)
 {
     return guarded([&]() -> int {
@@ -1984,7 +2051,9 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
             p.out_dev = fi.out_dev; p.out_row_pitch = fi.out_row_pitch; p.out_plane_pitch = fi.out_plane_pitch;
             p.out_bytes = fi.out_span;
             for (uint32_t c = 0; c < 3; c++) { p.out_scale[c] = src->himages[k].out_scale[c]; p.out_bias[c] = src->himages[k].out_bias[c]; }
-            p.rs_on = src->himages[k].rs_on != 0;                                     // (... and its resize)
+            p.rs_on = src->himages[k].rs_on != 0 || src->himages[k].or_on != 0;       // (... and its resize and orientation)
+            p.orient = src->himages[k].or_on ? src->himages[k].orient : 1u;
+            p.or_copy = src->himages[k].or_on == 1;
             p.rs_w = src->himages[k].rs_w; p.rs_h = src->himages[k].rs_h; p.rs_aa = src->himages[k].rs_aa;
         }
         p.roi_x = d.roi_x; p.roi_y = d.roi_y; p.roi_w = d.roi_w; p.roi_h = d.roi_h;
@@ -2289,6 +2358,16 @@ extern "C" int mjx_batch_image_scale(const mjx_batch *b, size_t iu, uint8_t *sca
     if (!visible_index(b, iu, i)) return MJX_ERR_INVALID_ARG;
     const ImageInfo &inf = b->info[i];
     if (scale_denom) *scale_denom = uint8_t(inf.scale ? inf.scale : 1u);
+    return inf.status;
+}
+
+extern "C" int mjx_batch_image_orientation(const mjx_batch *b, size_t iu, uint8_t *code)
+{
+    if (b && !b->parts.empty()) { mjx_batch *pb; size_t pi; return route(b, iu, pb, pi) ? mjx_batch_image_orientation(pb, pi, code) : MJX_ERR_INVALID_ARG; }
+    size_t i;
+    if (!visible_index(b, iu, i)) return MJX_ERR_INVALID_ARG;
+    const ImageInfo &inf = b->info[i];
+    if (code) *code = uint8_t(inf.orient);
     return inf.status;
 }
 
@@ -2696,7 +2775,8 @@ unsigned usable_processors()
 // same time, and the call takes about as long as the slowest of the three (on PCIe Gen5: the transfer).
 // (fmt: the call's output description, or null -- mjx_decode_batch_out; dst[i] goes with file i wherever its group falls)
 static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
-                             unsigned threads, const mjx_output *fmt, const mjx_resize *rs, uint8_t **rgb_dev, int *status, mjx_batch **out)
+                             unsigned threads, const mjx_output *fmt, const mjx_resize *rs, const mjx_orient *orient, uint8_t **rgb_dev, int *status,
+                             mjx_batch **out)
 {
     return guarded([&]() -> int {
     if (!ctx || !out || ((!jpegs || !lens) && n)) return MJX_ERR_INVALID_ARG;
@@ -2704,7 +2784,8 @@ static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const si
     std::lock_guard<std::mutex> serial(ctx->batch_mu);        // the pinned arena is shared state of the context
     mjx_opts o{};
     if (opts) o = *opts;
-    if (!rois_fit(o, n) || !output_fits(fmt, n)) return MJX_ERR_INVALID_ARG;
+    if (!rois_fit(o, n) || !output_fits(fmt, n) || !orient_fits(orient, n)) return MJX_ERR_INVALID_ARG;
+    if (orient && !fmt) fmt = &kPackedOutput;
     const bool timing = std::getenv("MJX_TIMING") != nullptr;
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
@@ -2834,7 +2915,8 @@ static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const si
             prc[i] = rc;
             if (rc != MJX_OK) std::memset(&descs[i], 0, sizeof descs[i]);
             try {
-                plan_input_for(descs[i], opts_for_input(o, n, i), fmt, rs, i, file_plans[i]);     // geometry + decode tables, also on the worker (rois[i], dst[i] and the resize go with file i)
+                // geometry + decode tables, also on the worker (rois[i], dst[i], the resize and the orientation -- the file's tag is read here -- go with file i)
+                plan_input_for(descs[i], opts_for_input(o, n, i), fmt, rs, i, file_plans[i], orient_code(orient, i, jpegs[i], lens[i]));
             } catch (...) {
                 file_plans[i].clear();
             }
@@ -2914,21 +2996,29 @@ static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const si
 extern "C" int mjx_decode_batch(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
                                 unsigned threads, uint8_t **rgb_dev, int *status, mjx_batch **out)
 {
-    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, nullptr, nullptr, rgb_dev, status, out);
+    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, nullptr, nullptr, nullptr, rgb_dev, status, out);
 }
 
 extern "C" int mjx_decode_batch_out(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
                                     unsigned threads, const mjx_output *fmt, int *status, mjx_batch **out)
 {
     if (!ctx) { if (out) *out = nullptr; return MJX_ERR_DEVICE; }      // (no context is no device: mjx_ctx_create failed, and there is no CPU path)
-    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, fmt, nullptr, nullptr, status, out);
+    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, fmt, nullptr, nullptr, nullptr, status, out);
 }
 
 extern "C" int mjx_decode_batch_resize(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
                                        unsigned threads, const mjx_output *fmt, const mjx_resize *rs, int *status, mjx_batch **out)
 {
     if (!ctx) { if (out) *out = nullptr; return MJX_ERR_DEVICE; }      // (as mjx_decode_batch_out: no device, no CPU path)
-    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, fmt, rs, nullptr, status, out);
+    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, fmt, rs, nullptr, nullptr, status, out);
+}
+
+extern "C" int mjx_decode_batch_orient(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
+                                       unsigned threads, const mjx_output *fmt, const mjx_resize *rs, const mjx_orient *orient, int *status,
+                                       mjx_batch **out)
+{
+    if (!ctx) { if (out) *out = nullptr; return MJX_ERR_DEVICE; }      // (as mjx_decode_batch_out: no device, no CPU path)
+    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, fmt, rs, orient, nullptr, status, out);
 }
 
 // ---- one-shot surface ------------------------------------------------------------------------------

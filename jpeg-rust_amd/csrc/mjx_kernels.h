@@ -107,6 +107,12 @@ struct DevImage {
     // describe, at out_dev or, out_dev == 0, at byte rs_off of the batch's picture pool.
     uint32_t rs_on, rs_w, rs_h, rs_aa;
     uint64_t rs_off;
+    // orientation on the device (mjx_orient; or_on): the picture that leaves is orient_c(S), S the packed intermediate above, c =
+    // orient (an EXIF code 2 .. 8; a picture whose code is 1 has or_on = 0 and is planned as if there were no orientation).
+    // or_on = 1: k_orient_out copies S to rs_w x rs_h = the oriented size, element by element through the formats' table, to out_dev
+    // or byte rs_off of the pool; or_on = 2: k_resize_orient resamples orient_c(S) to rs_w x rs_h (rs_on stays 0: k_resize_out
+    // passes over the picture).
+    uint32_t orient, or_on;
 };
 constexpr uint32_t kRoiMode = 8;
 constexpr uint32_t kOutMode = 16;      // + m (0, 1, 3, 4; 5: k_dc_color_out): the forms for pictures with an output description
@@ -125,6 +131,54 @@ MJX_HD bool roi_tile_wanted(uint32_t t, uint32_t T, uint32_t nmcu, uint32_t mcux
     const bool last = (re == ra ? ca : 0u) <= c1 && (re == rb ? cb : mcux - 1u) >= c0;
     return first || last;
 }
+
+// ---- orientation (mjx_orient): the eight EXIF codes ------------------------------------------------------------------------------
+// S is the stored picture, h rows of w; D = orient_c(S) is the picture that leaves.  Every code is "swap the axes or not, then mirror
+// S's columns and / or rows":  D(x, y) = S[v][u],  u = (T ? y : x) mirrored in w when FU,  v = (T ? x : y) mirrored in h when FV
+//   code  1      2      3      4      5      6      7      8
+//   T     .      .      .      .      x      x      x      x
+//   FU    .      x      x      .      .      .      x      x
+//   FV    .      .      x      x      .      x      x      .
+// The host (plan, mjx_orient_plan), k_orient_out and k_resize_orient run these routines.
+MJX_HD bool orient_valid(uint32_t c) { return c >= 1u && c <= 8u; }
+MJX_HD bool orient_swaps(uint32_t c) { return c >= 5u; }
+MJX_HD bool orient_flips_u(uint32_t c) { return c == 2u || c == 3u || c == 7u || c == 8u; }
+MJX_HD bool orient_flips_v(uint32_t c) { return c == 3u || c == 4u || c == 6u || c == 7u; }
+// D's size and, in pixels of the row-major w x h picture, the base and the two signed strides:  D(x, y) = S[base + x sx + y sy]
+struct OrientMap { uint32_t dw, dh; int64_t base, sx, sy; };
+MJX_HD OrientMap orient_map(uint32_t c, uint32_t w, uint32_t h)
+{
+    OrientMap m;
+    const bool T = orient_swaps(c), fu = orient_flips_u(c), fv = orient_flips_v(c);
+    m.dw = T ? h : w; m.dh = T ? w : h;
+    const int64_t du = fu ? -1 : 1, dv = fv ? -int64_t(w) : int64_t(w);         // one step along S's columns / rows
+    m.base = (fu ? int64_t(w) - 1 : 0) + (fv ? (int64_t(h) - 1) * int64_t(w) : 0);
+    m.sx = T ? dv : du;
+    m.sy = T ? du : dv;
+    return m;
+}
+// The rectangle of S that holds exactly the pixels of the rectangle (x, y, rw, rh) of D (rw, rh > 0, inside D): its two opposite
+// corners through the map.
+MJX_HD void orient_rect_to_stored(uint32_t c, uint32_t w, uint32_t h, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh,
+                                  uint32_t *sx0, uint32_t *sy0, uint32_t *sw, uint32_t *sh)
+{
+    const OrientMap m = orient_map(c, w, h);
+    const int64_t i0 = m.base + int64_t(x) * m.sx + int64_t(y) * m.sy;
+    const int64_t i1 = m.base + int64_t(x + rw - 1u) * m.sx + int64_t(y + rh - 1u) * m.sy;
+    const uint32_t r0 = uint32_t(i0 / int64_t(w)), c0 = uint32_t(i0 - int64_t(r0) * int64_t(w));
+    const uint32_t r1 = uint32_t(i1 / int64_t(w)), c1 = uint32_t(i1 - int64_t(r1) * int64_t(w));
+    *sx0 = c0 < c1 ? c0 : c1; *sy0 = r0 < r1 ? r0 : r1;
+    *sw = (c0 < c1 ? c1 - c0 : c0 - c1) + 1u; *sh = (r0 < r1 ? r1 - r0 : r0 - r1) + 1u;
+}
+// orient_compose(first, then): the one code that does what `first` followed by `then` does (0: a code outside 1 .. 8)
+MJX_HD uint32_t orient_compose(uint32_t first, uint32_t then)
+{
+    const uint8_t t[8][8] = {{1, 2, 3, 4, 5, 6, 7, 8}, {2, 1, 4, 3, 8, 7, 6, 5}, {3, 4, 1, 2, 7, 8, 5, 6}, {4, 3, 2, 1, 6, 5, 8, 7},
+                             {5, 6, 7, 8, 1, 2, 3, 4}, {6, 5, 8, 7, 4, 3, 2, 1}, {7, 8, 5, 6, 3, 4, 1, 2}, {8, 7, 6, 5, 2, 1, 4, 3}};
+    return orient_valid(first) && orient_valid(then) ? t[first - 1u][then - 1u] : 0u;
+}
+constexpr uint32_t kOrientTile = 64;                        // k_orient_out: a workgroup owns kOrientTile x kOrientTile pixels of D
+MJX_HD uint32_t orient_tiles(uint32_t w, uint32_t h) { return ((w + kOrientTile - 1) / kOrientTile) * ((h + kOrientTile - 1) / kOrientTile); }
 
 // ---- resize on the device (mjx_resize): the separable triangle filter, one axis -----------------------------------------------
 // Output coordinate X of an axis n_in -> n_out samples the input at c = (2X + 1) n_in / (2 n_out) with a triangle of half width
@@ -538,6 +592,10 @@ void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, cons
                      bool out = false /* the form for pictures with an output description (mode 5 + kOutMode) */);
 // resize on the device: one workgroup per tile of the target (resize_tiles) and picture with DevImage::rs_on, behind stage B
 void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
+// orientation on the device, behind stage B like the resize: one workgroup per tile of D (orient_tiles) and picture with or_on == 1
+// (k_orient_out), or per tile of the target (resize_tiles) and picture with or_on == 2 (k_resize_orient)
+void launch_orient_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
+void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
 #endif
 
 }   // namespace mjx

@@ -4013,12 +4013,20 @@ __device__ __forceinline__ void out_store1f(const OutFmt &f, uint64_t at, float 
         else __builtin_nontemporal_store(e, reinterpret_cast<float *>(f.base) + at);
     }
 }
-extern "C" __global__ __launch_bounds__(256) void k_resize_out(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,
-                                                                const uint32_t *__restrict__ img_flags)
+// ORIENT (k_resize_orient): the filter runs on D = orient_c(I), I the intermediate -- w_in and h_in are D's axes and the horizontal
+// pass reaches D(j, row) through orient_map's base and strides; the identity form (k_resize_out) keeps its own addressing.
+template <bool ORIENT>
+__device__ __forceinline__ void resize_body(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
 {
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || !im.rs_on || img_flags[im.status_idx]) return;
-    const uint32_t W = im.rs_w, H = im.rs_h, w_in = im.roi_w, h_in = im.roi_h;
+    if (!im.valid || (ORIENT ? im.or_on != 2u : !im.rs_on) || img_flags[im.status_idx]) return;
+    const bool swaps = ORIENT && orient_swaps(im.orient);
+    const uint32_t W = im.rs_w, H = im.rs_h, w_in = swaps ? im.roi_h : im.roi_w, h_in = swaps ? im.roi_w : im.roi_h;
+    int64_t o_base = 0, o_sx = 0, o_sy = 0;                // bytes
+    if constexpr (ORIENT) {
+        const OrientMap om = orient_map(im.orient, im.roi_w, im.roi_h);
+        o_base = om.base * 3; o_sx = om.sx * 3; o_sy = om.sy * 3;
+    }
     const uint32_t tiles_x = (W + kRsTileW - 1) / kRsTileW, tiles_y = (H + kRsTileH - 1) / kRsTileH;
     if (blockIdx.x >= tiles_x * tiles_y) return;
     const uint32_t tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
@@ -4055,7 +4063,7 @@ extern "C" __global__ __launch_bounds__(256) void k_resize_out(const DevImage *_
             for (uint32_t k = 0; k < kRsRows; k++) {
                 const uint32_t row = r0 + ly + 4u * k;
                 if (row < row_hi) {
-                    const uint8_t *p = src + (uint64_t(row) * w_in + j) * 3u;
+                    const uint8_t *p = ORIENT ? src + (o_base + int64_t(row) * o_sy + int64_t(j) * o_sx) : src + (uint64_t(row) * w_in + j) * 3u;
                     h[k][0] = __builtin_fmaf(wn, float(p[0]), h[k][0]);
                     h[k][1] = __builtin_fmaf(wn, float(p[1]), h[k][1]);
                     h[k][2] = __builtin_fmaf(wn, float(p[2]), h[k][2]);
@@ -4097,6 +4105,80 @@ extern "C" __global__ __launch_bounds__(256) void k_resize_out(const DevImage *_
             const float a = f.bgr ? acc[k][2u - oc] : acc[k][oc];
             const uint64_t at = f.planar ? row + oc * f.plane_pitch + X : row + uint64_t(X) * 3u + oc;
             out_store1f(f, at, a / norm, f.scale[oc], f.bias[oc]);
+        }
+    }
+}
+extern "C" __global__ __launch_bounds__(256) void k_resize_out(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,
+                                                                const uint32_t *__restrict__ img_flags)
+{
+    resize_body<false>(images, rgb, img_flags);
+}
+extern "C" __global__ __launch_bounds__(256) void k_resize_orient(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,
+                                                                   const uint32_t *__restrict__ img_flags)
+{
+    resize_body<true>(images, rgb, img_flags);
+}
+
+// ---- orientation on the device (mjx_orient; DevImage::or_on == 1): an oriented picture that is not resized --------------------
+// Stage B has written the picture as a packed (cropped) one, S: roi_h x roi_w x 3 bytes at rgb_off.  A workgroup owns a tile of
+// kOrientTile x kOrientTile pixels of D = orient_c(S).  The tile of S that holds the same pixels (orient_rect_to_stored; at most
+// 64 x 64 as well) is read along S's rows -- a wave per row, consecutive lanes consecutive bytes; the rows are 3 w bytes and not
+// word-aligned, so they are read as bytes -- into LDS, rows padded to 49 words: after the barrier lane x of a wave takes pixel x
+// of a row of D, which for the codes that swap the axes is a walk down a column of the tile, 49 words apart, so the 32 lanes of
+// a half wave touch 32 different banks; for the others it is the row itself, forwards or backwards.  An element is the formats'
+// table applied to the byte (out_store1), so the picture is bit for bit what the plain decode would give for the mapped pixel;
+// a wave stores 64 neighbouring elements of a plane row (192 of an interleaved one), non-temporal.  The format's fields and the
+// code are uniform and sit in scalars.  Codes 2 .. 4 could copy a row piece of S straight to a row piece of D with the lanes reversed;
+// they take the tile as well -- an LDS round trip and a barrier more than they need, both sides coalesced either way -- so that one
+// form serves all eight codes.
+constexpr uint32_t kOrientRowBytes = kOrientTile * 3u + 4u;
+static_assert((kOrientRowBytes / 4u) % 2u == 1u, "k_orient_out: an odd number of words per LDS row");
+extern "C" __global__ __launch_bounds__(256) void k_orient_out(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,
+                                                                const uint32_t *__restrict__ img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    if (!im.valid || im.or_on != 1u || img_flags[im.status_idx]) return;
+    const uint32_t code = im.orient, w = im.roi_w, h = im.roi_h;
+    const bool swaps = orient_swaps(code), fu = orient_flips_u(code), fv = orient_flips_v(code);
+    const uint32_t W = swaps ? h : w, H = swaps ? w : h;
+    const uint32_t tiles_x = (W + kOrientTile - 1) / kOrientTile, tiles_y = (H + kOrientTile - 1) / kOrientTile;
+    if (blockIdx.x >= tiles_x * tiles_y) return;
+    const uint32_t tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const uint32_t X0 = tile_x * kOrientTile, Y0 = tile_y * kOrientTile;
+    const uint32_t tw = W - X0 < kOrientTile ? W - X0 : kOrientTile, th = H - Y0 < kOrientTile ? H - Y0 : kOrientTile;
+    // the tile of S that holds the tile's pixels -- orient_rect_to_stored's rectangle, from the rule itself in 32-bit arithmetic:
+    // D's x runs along S's columns, or along its rows for the codes that swap, from the far end where that axis is mirrored
+    const uint32_t sw = swaps ? th : tw, sh = swaps ? tw : th;
+    const uint32_t u0 = swaps ? Y0 : X0, v0 = swaps ? X0 : Y0;
+    const uint32_t sx0 = fu ? w - u0 - sw : u0, sy0 = fv ? h - v0 - sh : v0;
+    __shared__ uint8_t s_t[kOrientTile][kOrientRowBytes];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint8_t *__restrict__ src = rgb + im.rgb_off + (uint64_t(sy0) * w + sx0) * 3u;
+    const uint32_t row_bytes = sw * 3u;
+    for (uint32_t r = wave; r < sh; r += 4u) {
+        const uint8_t *__restrict__ p = src + uint64_t(r) * w * 3u;
+#pragma unroll
+        for (uint32_t k = 0; k < 3u; k++) {
+            const uint32_t b = lane + 64u * k;
+            if (b < row_bytes) s_t[r][b] = p[b];
+        }
+    }
+    __syncthreads();
+    if (lane >= tw) return;
+    OutFmt f = out_fmt(im, rgb);
+    if (!im.out_dev) f.base = rgb + im.rs_off;
+    const uint32_t X = X0 + lane;
+    for (uint32_t y = wave; y < th; y += 4u) {
+        const uint32_t ur = swaps ? y : lane, vr = swaps ? lane : y;
+        const uint32_t u = fu ? sw - 1u - ur : ur, v = fv ? sh - 1u - vr : vr;
+        const uint8_t *q = &s_t[v][u * 3u];
+        const uint32_t c0 = q[0], c1 = q[1], c2 = q[2];
+        const uint64_t row = uint64_t(Y0 + y) * f.row_pitch;
+#pragma unroll
+        for (uint32_t oc = 0; oc < 3; oc++) {
+            const uint32_t val = oc == 1u ? c1 : (oc == 0u) != (f.bgr != 0u) ? c0 : c2;
+            const uint64_t at = f.planar ? row + oc * f.plane_pitch + X : row + uint64_t(X) * 3u + oc;
+            out_store1(f, at, val, f.scale[oc], f.bias[oc]);
         }
     }
 }
@@ -4427,6 +4509,14 @@ void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, con
 void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags)
 {
     hipLaunchKernelGGL(k_resize_out, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
+}
+void launch_orient_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags)
+{
+    hipLaunchKernelGGL(k_orient_out, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
+}
+void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags)
+{
+    hipLaunchKernelGGL(k_resize_orient, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
 }
 
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,

@@ -420,6 +420,53 @@ int mjx::parse_into(const uint8_t *jpeg, size_t len, const mjx_opts *opts, mjx_s
     return MJX_OK;
 }
 
+// The EXIF orientation of a file (TIFF tag 0x0112 in IFD0 of the first APP1 "Exif\0\0" in front of the first SOS).  A walk of its
+// own, apart from mjx_parse's (which skips APP1 and whose strict_ref form refuses it): every read is checked against the segment,
+// and the segment against the file; whatever does not hold together means "no tag", code 1.
+static uint8_t tiff_orientation(const uint8_t *t, size_t n)
+{
+    if (n < 8) return 1;
+    const bool le = t[0] == 'I' && t[1] == 'I', be = t[0] == 'M' && t[1] == 'M';
+    if (!le && !be) return 1;
+    auto u16 = [&](size_t o) { return le ? uint32_t(t[o]) | uint32_t(t[o + 1]) << 8 : uint32_t(t[o]) << 8 | uint32_t(t[o + 1]); };
+    auto u32 = [&](size_t o) { return le ? u16(o) | u16(o + 2) << 16 : u16(o) << 16 | u16(o + 2); };
+    if (u16(2) != 42) return 1;
+    const size_t ifd = u32(4);
+    if (ifd > n - 2) return 1;
+    const size_t count = u16(ifd);
+    if (count * 12 > n - 2 - ifd) return 1;                // (the entries run past the segment)
+    for (size_t k = 0; k < count; k++) {
+        const size_t e = ifd + 2 + 12 * k;
+        if (u16(e) != 0x0112) continue;
+        const uint32_t v = u16(e + 8);
+        return u16(e + 2) == 3 && u32(e + 4) == 1 && v >= 1 && v <= 8 ? uint8_t(v) : uint8_t(1);
+    }
+    return 1;
+}
+
+extern "C" int mjx_exif_orientation(const uint8_t *jpeg, size_t len, uint8_t *code)
+{
+    if (!jpeg || !code) return MJX_ERR_INVALID_ARG;
+    *code = 1;
+    size_t i = 0;
+    while (len - i >= 2 && i < len) {
+        if (jpeg[i] != 0xff) return MJX_OK;
+        const uint8_t m = jpeg[i + 1];
+        if (m == 0xff) { i++; continue; }                                          // fill byte
+        if (m == 0xd8 || m == 0x01 || (m >= 0xd0 && m <= 0xd7)) { i += 2; continue; }   // stand-alone markers
+        if (m == 0xd9 || m == 0xda || len - i < 4) return MJX_OK;                  // EOI, the first SOS, or no room for a length
+        const size_t seglen = size_t(jpeg[i + 2]) << 8 | jpeg[i + 3], body = i + 4;
+        if (seglen < 2 || seglen - 2 > len - body) return MJX_OK;                  // (the file ends inside the segment)
+        const size_t n = seglen - 2;
+        if (m == 0xe1 && n >= 6 && std::memcmp(jpeg + body, "Exif\0\0", 6) == 0) {
+            *code = tiff_orientation(jpeg + body + 6, n - 6);
+            return MJX_OK;
+        }
+        i = body + n;
+    }
+    return MJX_OK;
+}
+
 extern "C" void mjx_free_scan(mjx_scan_desc *desc)
 {
     if (!desc) return;

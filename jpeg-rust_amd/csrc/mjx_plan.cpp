@@ -554,23 +554,51 @@ int resize_opts(uint32_t width, uint32_t height, const mjx_opts &opts_i, const m
 }
 
 void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_output *out, const mjx_resize *rs, size_t i,
-                    std::vector<ImagePlan> &plans)
+                    std::vector<ImagePlan> &plans, uint32_t code)
 {
-    if (!rs) {
+    if (!rs && code == 1) {
         plan_input(d, opts_i, plans);
         plan_output_of_input(plans, out, i);
         return;
     }
     const size_t first = plans.size();
-    mjx_opts eff;
-    mjx_rect rect{0, 0, 0, 0};
-    const int rc = resize_opts(d.width, d.height, opts_i, *rs, eff, rect);
+    mjx_opts eff = opts_i;
+    mjx_rect rect{0, 0, 0, 0}, stored{0, 0, 0, 0};
+    int rc = MJX_OK;
+    mjx_resize rs_s{};                                                     // the resize in S's axes
+    if (rs) rs_s = *rs;
+    if (code != 1) {
+        // orientation: the rectangle is D's; back to S at the scale it is given in (full size with auto_scale)
+        const uint32_t s = rs && rs->auto_scale ? 1u : opts_i.scale_denom > 1 ? opts_i.scale_denom : 1u;
+        const uint32_t w = (d.width + s - 1) / s, h = (d.height + s - 1) / s;
+        if (!orient_valid(code) || opts_i.layout == MJX_LAYOUT_REF_COMPAT) rc = MJX_ERR_INVALID_ARG;
+        else if (w && h && (s == 1 || s == 2 || s == 4 || s == 8) && opts_i.rois && opts_i.n_rois && (opts_i.rois[0].w || opts_i.rois[0].h)) {
+            const mjx_rect &r = opts_i.rois[0];
+            const OrientMap m = orient_map(code, w, h);
+            if (!r.w || !r.h || r.x >= m.dw || r.y >= m.dh || r.w > m.dw - r.x || r.h > m.dh - r.y) rc = MJX_ERR_INVALID_ARG;
+            else {
+                orient_rect_to_stored(code, w, h, r.x, r.y, r.w, r.h, &stored.x, &stored.y, &stored.w, &stored.h);
+                eff.rois = &stored; eff.n_rois = 1;
+            }
+        }
+        if (orient_swaps(code)) std::swap(rs_s.width, rs_s.height);
+    }
+    if (rs && rc == MJX_OK) {
+        const mjx_opts in = eff;
+        rc = resize_opts(d.width, d.height, in, rs_s, eff, rect);
+    }
+    if (rc != MJX_OK && code != 1) { eff.rois = nullptr; eff.n_rois = 0; }  // (the rectangle is D's: the picture's own fault, which comes first, is found on the whole picture)
     plan_input(d, eff, plans);
-    if (plans.back().status != MJX_OK) return;                             // (the picture's own fault comes first)
+    if (plans.back().status != MJX_OK) return;
     if (rc != MJX_OK) { fail_input(plans, first, rc); return; }
     ImagePlan &p = plans.back();
     p.rs_on = true;
-    p.rs_w = rs->width; p.rs_h = rs->height; p.rs_aa = rs->antialias ? 1u : 0u;
+    p.orient = code;
+    if (rs) { p.rs_w = rs->width; p.rs_h = rs->height; p.rs_aa = rs->antialias ? 1u : 0u; }
+    else {
+        p.or_copy = true;
+        p.rs_w = orient_swaps(code) ? p.roi_h : p.roi_w; p.rs_h = orient_swaps(code) ? p.roi_w : p.roi_h; p.rs_aa = 0;
+    }
     static const mjx_output packed = {MJX_DTYPE_U8, 0, 0, {1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}, nullptr, 0};
     plan_output_of_input(plans, out ? out : &packed, i);
 }

@@ -59,6 +59,11 @@ struct ImagePlan {
     // stage B keeps its packed forms (fill_dev_image).
     bool rs_on = false;
     uint32_t rs_w = 0, rs_h = 0, rs_aa = 0;
+    // orientation on the device (mjx_orient, plan_input_for): orient = the EXIF code 2 .. 8 of a picture that leaves as orient_c(S), S
+    // the packed intermediate as above (rs_on is set either way: the pool, the output's rules and the accessors are the resize's).
+    // or_copy: there is no resize, rs_w x rs_h is the oriented size of roi_w x roi_h and k_orient_out copies.  Code 1 leaves no trace.
+    uint32_t orient = 1;
+    bool or_copy = false;
     const uint8_t *scan = nullptr;
     size_t scan_len = 0;
     // The scan still holds FF00 pairs (and RSTn markers): it is de-stuffed on the device at upload (k_destuff_*), scan_len is
@@ -126,9 +131,13 @@ int plan_output_of_input(std::vector<ImagePlan> &plans, const mjx_output *out, s
 // full-size rectangle outside the picture.  plan_resize marks the planned picture (the last plan of the input).
 // plan_input_for: plan_input + plan_resize + plan_output_of_input in the one order every entry point uses; rs == nullptr: as before.
 // A resize without an output description leaves interleaved u8 R,G,B, library-owned.
+// code: the picture's resolved orientation (mjx_orient), an EXIF code.  1: as before.  2 .. 8: rois[0] is in the coordinates of the
+// oriented picture D (full-size D with auto_scale), is mapped back to the stored picture S (orient_rect_to_stored) and the picture
+// is planned as the cropped packed picture there; with auto_scale the target's axes are swapped into S's for codes 5 .. 8 before the
+// scale is picked.  Anything else, a rectangle outside D, or REF_COMPAT: MJX_ERR_INVALID_ARG for the picture.
 int resize_opts(uint32_t width, uint32_t height, const mjx_opts &opts_i, const mjx_resize &rs, mjx_opts &eff, mjx_rect &rect);
 void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_output *out, const mjx_resize *rs, size_t i,
-                    std::vector<ImagePlan> &plans);
+                    std::vector<ImagePlan> &plans, uint32_t code = 1);
 
 // mjx_parse.cpp: mjx_parse with caller-lent storage for the de-stuffed scan (see there)
 int parse_into(const uint8_t *jpeg, size_t len, const mjx_opts *opts, mjx_scan_desc *out, uint8_t *storage, size_t cap);
