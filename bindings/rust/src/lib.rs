@@ -13,6 +13,10 @@ use std::os::raw::{c_char, c_double, c_int, c_uint, c_void};
 pub const MJX_OK: c_int = 0;
 pub const MJX_LAYOUT_STANDARD: u8 = 0;
 pub const MJX_LAYOUT_REF_COMPAT: u8 = 1;
+/// layout of the structs below (include/mjx.h: 2 = mjx_opts.pixels in front of scale_denom); mjx_version() prints the library's as "abi=<n>"
+pub const MJX_ABI_VERSION: u32 = 2;
+pub const MJX_PIXELS_REFERENCE: u8 = 0;
+pub const MJX_PIXELS_LIBJPEG: u8 = 1;
 pub const MJX_STAGE_ALL: c_uint = 3;
 pub const MJX_DESTUFF_AUTO: u8 = 0;
 pub const MJX_DESTUFF_DEVICE: u8 = 1;
@@ -84,6 +88,8 @@ pub struct mjx_opts {
     pub keep_coefs: u8,
     pub device_destuff: u8,
     pub chunk_images: u32,
+    /// MJX_PIXELS_*: 0 the reference's pixels, 1 libjpeg's (rounded samples, fancy upsampling, integer colour tables; include/mjx.h)
+    pub pixels: u8,
     /// scaled decode: 0 or 1 full size, 2 / 4 / 8 = 1/2, 1/4, 1/8 in the DCT domain (include/mjx.h)
     pub scale_denom: u8,
     /// region-of-interest decode: null = whole pictures; borrowed for the duration of the call (include/mjx.h)
@@ -94,7 +100,7 @@ pub struct mjx_opts {
 
 impl Default for mjx_opts {
     fn default() -> Self {
-        mjx_opts { strict_ref: 0, layout: 0, keep_coefs: 0, device_destuff: 0, chunk_images: 0, scale_denom: 0, rois: std::ptr::null(), n_rois: 0 }
+        mjx_opts { strict_ref: 0, layout: 0, keep_coefs: 0, device_destuff: 0, chunk_images: 0, pixels: 0, scale_denom: 0, rois: std::ptr::null(), n_rois: 0 }
     }
 }
 
@@ -167,6 +173,8 @@ pub enum mjx_pool_result {}
 extern "C" {
     pub fn mjx_parse(jpeg: *const u8, len: usize, opts: *const mjx_opts, out: *mut mjx_scan_desc) -> c_int;
     pub fn mjx_free_scan(desc: *mut mjx_scan_desc);
+    pub fn mjx_upsample_color_host(planes: *const *const u8, cw: *const u32, ch: *const u32, rh: *const u8, rv: *const u8, ncomp: u32,
+                                   rect: *const mjx_rect, rgb: *mut u8) -> c_int;
     pub fn mjx_validate(desc: *const mjx_scan_desc, opts: *const mjx_opts) -> c_int;
     pub fn mjx_plan_tiles(desc: *const mjx_scan_desc, opts: *const mjx_opts, tiles_read: *mut u64, tiles_total: *mut u64,
                           tile_mcus: *mut u32) -> c_int;

@@ -20,6 +20,12 @@
 extern "C" {
 #endif
 
+/* The binary layout of the structs below.  1: up to scaled decode, rectangles, output formats, resize and orientation.  2: mjx_opts
+ * gained `pixels` at byte 8 and its scale_denom moved from byte 8 to byte 9 (size and every other offset unchanged): a caller built
+ * against layout 1 that sets scale_denom is refused with MJX_ERR_INVALID_ARG, never served another picture.  mjx_version() prints the
+ * layout the library was built with as "abi=<n>". */
+#define MJX_ABI_VERSION 2
+
 /* ---- status codes ------------------------------------------------------------------------ */
 enum {
     MJX_OK = 0,
@@ -39,6 +45,11 @@ enum {
 enum {
     MJX_LAYOUT_STANDARD = 0,  /* standard MCU count, block placement, box chroma replication, edge clipping */
     MJX_LAYOUT_REF_COMPAT = 1 /* bug-for-bug placement of decoder.rs:239-312 */
+};
+
+enum {
+    MJX_PIXELS_REFERENCE = 0, /* box chroma replication, float colour conversion, truncating store (the reference's pixels) */
+    MJX_PIXELS_LIBJPEG = 1    /* rounded samples, fancy (triangle) chroma upsampling, libjpeg's integer colour tables */
 };
 
 enum mjx_destuff {
@@ -65,6 +76,25 @@ typedef struct mjx_opts {
                              same.  Never on the GPU with strict_ref (the byte pass stays, for the reference's unguarded read
                              behind a last FF) nor for multi-scan files (their scans are cut apart on the host). */
     uint32_t chunk_images;/* images per kernel chunk; 0 = library default */
+    uint8_t pixels;       /* MJX_PIXELS_*.  MJX_PIXELS_LIBJPEG: the picture libjpeg's pipeline gives behind its inverse DCT.  Component c
+                             with factors (h, v) is a plane of ceil(W h / hmax) x ceil(H v / vmax) samples s = clamp(floor(f + 128 + 0.5),
+                             0, 255), f the float sample of the default pixels.  Each plane is upsampled by (rh, rv) = (hmax / h,
+                             vmax / v) in integers, indices outside the plane clamped to its edge:
+                               (2, 1) out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2;
+                               (1, 2) the same down the columns, bias 1 for the upper output row and 2 for the lower;
+                               (2, 2) t[i] = 3 near[i] + far[i] (near: the chroma row under the output row, far: the one above it for
+                                      even output rows, below for odd), out[2i] = (3 t[i] + t[i-1] + 8) >> 4,
+                                      out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4;
+                             (no fall-back to replication for planes of one or two columns).  Colour is jdcolor.c's, FIX(x) =
+                             int(x 65536 + 0.5), cb = Cb - 128, cr = Cr - 128: R = clamp(Y + ((FIX(1.40200) cr + 32768) >> 16)),
+                             B = clamp(Y + ((FIX(1.77200) cb + 32768) >> 16)), G = clamp(Y + ((-FIX(0.34414) cb + 32768
+                             - FIX(0.71414) cr) >> 16)); one component: R = G = B = s.  STANDARD layout at full size only:
+                             MJX_LAYOUT_REF_COMPAT, strict_ref or scale_denom > 1 give the picture MJX_ERR_INVALID_ARG (a resize with
+                             auto_scale picks scale 1).  Rectangles, output formats, resize and orientation compose as with the
+                             default pixels: a rectangle is byte for byte the crop of the whole picture.  Anything but 0 and 1:
+                             MJX_ERR_INVALID_ARG.  (The field stands in front of scale_denom, not at the struct's end: the struct's
+                             size and the other fields' offsets are as before, scale_denom's moved by one byte -- callers are
+                             rebuilt against this header.  A zero-filled struct keeps the default pixels.) */
     uint8_t scale_denom;  /* scaled decode in the DCT domain: 0 or 1 = full size; 2, 4, 8 = 1/2, 1/4, 1/8 (anything else:
                              MJX_ERR_INVALID_ARG).  The picture is ceil(W/s) x ceil(H/s) (libjpeg's jdiv_round_up).  Per block the
                              low N x N corner (N = 8/s) of the dequantised coefficients F(u,v), natural order, goes through the
@@ -339,6 +369,12 @@ int mjx_resize_plan(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_r
  * (at most cap are written; *count is the window's length either way).  n_in, n_out in 1 .. 2^24, X < n_out. */
 int mjx_resize_weights(uint32_t n_in, uint32_t n_out, int antialias, uint32_t X, uint32_t *first, float *weights, size_t cap,
                        size_t *count);
+/* Host-only: MJX_PIXELS_LIBJPEG's upsampling and colour step on the CPU -- the routines k_upsample_color itself runs (lj_strip8 /
+ * lj_color, mjx_kernels.h).  ncomp (1 or 3) dense planes of cw[c] x ch[c] samples, upsampled by rh[c], rv[c] (each 1 or 2); rgb receives
+ * the rectangle's rect->w x rect->h pixels, packed R,G,B.  The rectangle must lie inside every upsampled plane (cw[c] rh[c] x
+ * ch[c] rv[c]); the plane of an odd picture is one sample short of the picture's size, which the rule allows. */
+int mjx_upsample_color_host(const uint8_t *const *planes, const uint32_t *cw, const uint32_t *ch, const uint8_t *rh, const uint8_t *rv,
+                            uint32_t ncomp, const mjx_rect *rect, uint8_t *rgb);
 
 /* mjx_batch_create_resize with an orientation description (above); orient == NULL: mjx_batch_create_resize itself.  Descriptors
  * carry no file bytes: from_exif = 1 is MJX_ERR_INVALID_ARG for the call -- read the tag with mjx_exif_orientation and pass it in
@@ -425,7 +461,8 @@ enum {
                              MJX_K_HUFF_SYNC and the decode of MJX_K_HUFF_WRITE */
     MJX_K_HUFF_PREFIX = 9,/* ... the prefixes of the subsequences whose entry state was wrong, and block words -> DC differences + tile offsets */
     MJX_K_RESIZE = 10,    /* the pass behind stage B that brings a picture to the form it leaves in: resize on the device (k_resize_out),
-                             orientation (k_orient_out, k_resize_orient).  No launches for a batch without a resized or oriented picture */
+                             orientation (k_orient_out, k_resize_orient), MJX_PIXELS_LIBJPEG's upsampling and colour step (k_upsample_color).  No launches
+                             for a batch without a resized or oriented picture or that option */
     MJX_K_COUNT = 11
 };
 int mjx_batch_kernel_ms(mjx_batch *b, double ms[MJX_K_COUNT], uint64_t launches[MJX_K_COUNT], int reset);

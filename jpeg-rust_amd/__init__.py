@@ -29,6 +29,8 @@ ROOT = os.path.dirname(_PKG)
 OK, ERR_TRUNCATED, ERR_UNSUPPORTED_MARKER, ERR_DRI_UNSUPPORTED, ERR_BAD_HUFFMAN, ERR_REF_PANIC, ERR_DEVICE, \
     ERR_UNSUPPORTED_FORMAT, ERR_NO_SCAN, ERR_INVALID_ARG, ERR_NOMEM, ERR_MISSING_TABLE = range(12)
 LAYOUT_STANDARD, LAYOUT_REF_COMPAT = 0, 1
+PIXELS_REFERENCE, PIXELS_LIBJPEG = 0, 1
+ABI_VERSION = 2                  # mjx.h: MJX_ABI_VERSION, the layout the structures below mirror (mjx_version() prints the library's)
 STAGE_ENTROPY, STAGE_PIXELS, STAGE_ALL = 1, 2, 3
 KERNEL_NAMES = ["gather", "huff_sync", "huff_fix", "huff_scan", "huff_write", "dc_scan", "idct_color", "upload", "huff_emit", "huff_prefix", "resize"]
 SUBSAMPLING = {"444": 0, "422": 1, "420": 2, "gray": 3, "440": 4}
@@ -48,8 +50,8 @@ class Rect(ctypes.Structure):
 
 class Opts(ctypes.Structure):
     _fields_ = [("strict_ref", ctypes.c_uint8), ("layout", ctypes.c_uint8), ("keep_coefs", ctypes.c_uint8),
-                ("device_destuff", ctypes.c_uint8), ("chunk_images", ctypes.c_uint32), ("scale_denom", ctypes.c_uint8),
-                ("rois", ctypes.POINTER(Rect)), ("n_rois", ctypes.c_uint32)]
+                ("device_destuff", ctypes.c_uint8), ("chunk_images", ctypes.c_uint32), ("pixels", ctypes.c_uint8),
+                ("scale_denom", ctypes.c_uint8), ("rois", ctypes.POINTER(Rect)), ("n_rois", ctypes.c_uint32)]
 
 
 class Dst(ctypes.Structure):
@@ -125,6 +127,8 @@ SYMBOLS = {
     "mjx_decode_batch_resize": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(OutputDesc), _P(ResizeDesc), _P(_int), _P(_vp)]),
     "mjx_resize_plan": (_int, [_P(ScanDesc), _P(Opts), _P(ResizeDesc), _sz, _P(ctypes.c_uint8), _P(Rect), _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
     "mjx_resize_weights": (_int, [ctypes.c_uint32, ctypes.c_uint32, _int, ctypes.c_uint32, _P(ctypes.c_uint32), _P(ctypes.c_float), _sz, _P(_sz)]),
+    "mjx_upsample_color_host": (_int, [_P(_P(ctypes.c_uint8)), _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(ctypes.c_uint8), _P(ctypes.c_uint8), ctypes.c_uint32,
+                                       _P(Rect), _P(ctypes.c_uint8)]),
     "mjx_exif_orientation": (_int, [ctypes.c_char_p, _sz, _P(ctypes.c_uint8)]),
     "mjx_orient_compose": (ctypes.c_uint8, [ctypes.c_uint8, ctypes.c_uint8]),
     "mjx_batch_create_orient": (_int, [_vp, _P(ScanDesc), _sz, _P(Opts), _P(OutputDesc), _P(ResizeDesc), _P(OrientDesc), _P(_vp), _P(_int)]),
@@ -221,15 +225,28 @@ def _rects(rois):
     return arr
 
 
-def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0, device_destuff=False, scale=1, rois=None):
+def _pixels(pixels):
+    """None / "reference" / PIXELS_REFERENCE, or "libjpeg" / PIXELS_LIBJPEG (mjx.h: mjx_opts.pixels)."""
+    names = {None: PIXELS_REFERENCE, "reference": PIXELS_REFERENCE, "libjpeg": PIXELS_LIBJPEG}
+    if pixels is None or isinstance(pixels, str):
+        if pixels not in names:
+            raise MjxError(ERR_INVALID_ARG, "pixels=%r" % (pixels,))
+        return names[pixels]
+    if not 0 <= int(pixels) <= 255:
+        raise MjxError(ERR_INVALID_ARG, "pixels=%r" % (pixels,))
+    return int(pixels)
+
+
+def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0, device_destuff=False, scale=1, rois=None, pixels=None):
     """device_destuff: True = on the GPU, False = on the host, None = the library's choice (mjx.h: MJX_DESTUFF_*).
     scale: 1, 2, 4 or 8 -- the picture decoded at 1/scale in the DCT domain (mjx.h: mjx_opts.scale_denom).
-    rois: see _rects (mjx.h: mjx_opts.rois, n_rois); the Opts returned keeps the array alive."""
+    rois: see _rects (mjx.h: mjx_opts.rois, n_rois); the Opts returned keeps the array alive.
+    pixels: see _pixels -- "libjpeg": rounded samples, fancy chroma upsampling and libjpeg's integer colour tables."""
     dd = DESTUFF_AUTO if device_destuff is None else (DESTUFF_DEVICE if device_destuff else DESTUFF_HOST)
     scale = int(scale)
     if not 0 <= scale <= 255:
         raise MjxError(ERR_INVALID_ARG, "scale=%d" % scale)
-    o = Opts(int(bool(strict_ref)), int(layout), int(bool(keep_coefs)), dd, int(chunk_images), scale)
+    o = Opts(int(bool(strict_ref)), int(layout), int(bool(keep_coefs)), dd, int(chunk_images), _pixels(pixels), scale)
     arr = _rects(rois)
     if arr is not None:
         o._rects = arr                      # (the library borrows the array for the duration of the call)
@@ -353,6 +370,24 @@ def resize_weights(n_in, n_out, antialias, X):
     return first.value, w[:cnt.value]
 
 
+def upsample_color_host(planes, rh, rv, rect):
+    """mjx_upsample_color_host (host only; the routines k_upsample_color runs): one or three uint8 planes [ch, cw], their upsampling
+    ratios rh[c], rv[c] (1 or 2) and a rectangle (x, y, w, h) of the upsampled picture -> ndarray [h, w, 3] uint8, the "libjpeg"
+    pixels of that rectangle."""
+    n = len(planes)
+    pl = [np.ascontiguousarray(q, np.uint8) for q in planes]
+    ptrs = (_P(ctypes.c_uint8) * n)(*[q.ctypes.data_as(_P(ctypes.c_uint8)) for q in pl])
+    cw = (ctypes.c_uint32 * n)(*[q.shape[1] for q in pl])
+    ch = (ctypes.c_uint32 * n)(*[q.shape[0] for q in pl])
+    a_rh = (ctypes.c_uint8 * n)(*[int(v) for v in rh])
+    a_rv = (ctypes.c_uint8 * n)(*[int(v) for v in rv])
+    x, y, w, h = (int(v) for v in rect)
+    r = Rect(x, y, w, h)
+    out = np.zeros((max(h, 1), max(w, 1), 3), np.uint8)
+    _check(lib().mjx_upsample_color_host(ptrs, cw, ch, a_rh, a_rv, n, ctypes.byref(r), out.ctypes.data_as(_P(ctypes.c_uint8))), "mjx_upsample_color_host")
+    return out[:h, :w]
+
+
 def _out_ref(output):
     if output is None:
         return None, None
@@ -374,15 +409,15 @@ class ParsedScan:
     def scan_bytes(self):
         return ctypes.string_at(self.desc.scan, self.desc.scan_len)
 
-    def validate(self, layout=LAYOUT_STANDARD, strict_ref=False, scale=1, roi=None):
+    def validate(self, layout=LAYOUT_STANDARD, strict_ref=False, scale=1, roi=None, pixels=None):
         """Status mjx_batch_create would give this image (host only).  roi: (x, y, w, h) in the scaled picture's coordinates."""
-        o = _opts(layout=layout, strict_ref=strict_ref, scale=scale, rois=roi)
+        o = _opts(layout=layout, strict_ref=strict_ref, scale=scale, rois=roi, pixels=pixels)
         return int(lib().mjx_validate(ctypes.byref(self.desc), ctypes.byref(o)))
 
-    def plan_tiles(self, roi=None, scale=1):
+    def plan_tiles(self, roi=None, scale=1, pixels=None):
         """mjx_plan_tiles (host only) -> dict(tiles_read, tiles_total, tile_mcus): the stage-B tiles a decode with this rectangle
         fetches and transforms, of the picture's tiles, and the MCUs a tile holds."""
-        o = _opts(scale=scale, rois=roi)
+        o = _opts(scale=scale, rois=roi, pixels=pixels)
         rd, tot, t = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
         _check(lib().mjx_plan_tiles(ctypes.byref(self.desc), ctypes.byref(o), ctypes.byref(rd), ctypes.byref(tot), ctypes.byref(t)), "mjx_plan_tiles")
         return dict(tiles_read=rd.value, tiles_total=tot.value, tile_mcus=t.value)
@@ -396,10 +431,10 @@ class ParsedScan:
         _check(lib().mjx_output_layout(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(lay), ctypes.byref(nb)), "mjx_output_layout")
         return dict(width=lay.width, height=lay.height, row_pitch=lay.row_pitch, plane_pitch=lay.plane_pitch, bytes=nb.value, dev=lay.dev or 0)
 
-    def resize_plan(self, resize, roi=None, scale=1, i=0, layout=LAYOUT_STANDARD):
+    def resize_plan(self, resize, roi=None, scale=1, i=0, layout=LAYOUT_STANDARD, pixels=None):
         """mjx_resize_plan (host only) -> dict(scale, rect=(x, y, w, h) at that scale, taps_x, taps_y): what a resized decode of this
         picture with this Resize takes; roi in full-size coordinates with auto_scale, else in the scaled picture's."""
-        o = _opts(layout=layout, scale=scale, rois=roi)
+        o = _opts(layout=layout, scale=scale, rois=roi, pixels=pixels)
         keep, ref = _rs_ref(resize)
         s, r, tx, ty = ctypes.c_uint8(), Rect(), ctypes.c_uint32(), ctypes.c_uint32()
         _check(lib().mjx_resize_plan(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(s), ctypes.byref(r), ctypes.byref(tx), ctypes.byref(ty)), "mjx_resize_plan")
@@ -462,7 +497,7 @@ class Batch:
     """Device-resident batch: inputs uploaded at construction, ``decode()`` only enqueues kernels."""
 
     def __init__(self, ctx, scans=None, strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0,
-                 _handle=None, scale=1, rois=None, output=None, resize=None, orient=None, datas=None):
+                 _handle=None, scale=1, rois=None, output=None, resize=None, orient=None, datas=None, pixels=None):
         """scale: 1, 2, 4 or 8 -- every picture decoded at 1/scale (info(), rgb(), rgb_device() and bytes() then speak of the
         scaled picture; tile() keeps the scale).
         rois: one (x, y, w, h) for every picture, or a list with one per picture (None or (0, 0, 0, 0): the whole picture), in the
@@ -475,7 +510,9 @@ class Batch:
         output_info() and output() speak of the target picture, scale(i) and rect(i) of what was decoded for it.
         orient: an Orient -- every picture leaves turned (orientation(i): by which code), rois are in the coordinates of the turned
         picture, info(), output_info() and output() speak of it, roi(i) and rect(i) of the stored picture.  Parsed scans hold no
-        EXIF segment: with Orient(exif=True) pass the files' bytes as `datas`, and the tags are read from them here."""
+        EXIF segment: with Orient(exif=True) pass the files' bytes as `datas`, and the tags are read from them here.
+        pixels: "libjpeg" (PIXELS_LIBJPEG) -- the pictures libjpeg-based decoders give: rounded samples, fancy chroma upsampling,
+        integer colour tables (STANDARD layout at full size only); everything above composes with it; tile() keeps it."""
         self.ctx = ctx
         self.h = _vp()
         if _handle is not None:
@@ -487,7 +524,7 @@ class Batch:
             ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(s.desc if isinstance(s, ParsedScan) else s),
                            ctypes.sizeof(ScanDesc))
         st = (_int * max(n, 1))()
-        o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois)
+        o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois, pixels=pixels)
         keep, ref = _out_ref(output)
         if orient is not None:
             if orient.exif:
@@ -783,13 +820,14 @@ class JPEGImage:
         self._w, self._h, self._rgb = width, height, rgb
 
     @staticmethod
-    def parse(data, strict_ref=False, layout=LAYOUT_STANDARD, ctx=None, scale=1, roi=None):
+    def parse(data, strict_ref=False, layout=LAYOUT_STANDARD, ctx=None, scale=1, roi=None, pixels=None):
         """scale: 1, 2, 4 or 8 -- the picture at 1/scale (width() and height() are the scaled picture's).
-        roi: (x, y, w, h) of the scaled picture -- only that rectangle is produced (width() and height() are its)."""
+        roi: (x, y, w, h) of the scaled picture -- only that rectangle is produced (width() and height() are its).
+        pixels: "libjpeg" -- see Batch."""
         ctx = ctx or default_context()
         scan = ParsedScan(data, strict_ref=strict_ref)
         try:
-            b = Batch(ctx, [scan], strict_ref=strict_ref, layout=layout, scale=scale, rois=roi)
+            b = Batch(ctx, [scan], strict_ref=strict_ref, layout=layout, scale=scale, rois=roi, pixels=pixels)
             try:
                 if b.create_status[0] != OK:
                     raise MjxError(b.create_status[0])
@@ -816,8 +854,8 @@ class JPEGImage:
 
 
 def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False, scale=1, rois=None,
-                 output=None, chunk_images=0, resize=None, orient=None):
-    """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale, rois: see Batch.
+                 output=None, chunk_images=0, resize=None, orient=None, pixels=None):
+    """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale, rois, pixels: see Batch.
     device_destuff: the host copies the entropy-coded bytes as they are; de-stuffing, restart markers and the scan's length
     are found on the GPU.  output: an Output (mjx_decode_batch_out) -- see Batch.  resize: a Resize (mjx_decode_batch_resize).  orient: an Orient
     (mjx_decode_batch_orient): the files' EXIF orientation and / or a code per file on top."""
@@ -827,7 +865,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     st = (_int * max(n, 1))()
     ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
     h = _vp()
-    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois)
+    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels)
     if orient is not None:
         keep, ref = _out_ref(output)
         keep_rs, rs_ref = _rs_ref(resize)
@@ -848,7 +886,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
 
 
 def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=False, threads=0, device_destuff=None, planar=None, resize=None,
-                orient=None):
+                orient=None, pixels=None):
     """Decodes the files straight into a torch tensor on the context's device: N x 3 x H x W (planar) or N x H x W x 3, of uint8,
     float16 or float32; picture i -- at 1/scale, its rectangle rois[i] -- must be H x W.  Float tensors take (v / 255 - mean) / std
     per OUTPUT channel (see Output); bgr: channel 0 is blue.  The pointers and pitches come from data_ptr() and stride(): the
@@ -860,7 +898,8 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
     own) and the batch is complete when this returns.  -> the per-picture statuses.
     resize: True, or a Resize (its antialias and auto_scale; a size, if it names one, must be the tensor's) -- the pictures, of any
     size, are resampled on the device to the tensor's H x W (see Resize); None: every picture must be H x W as it is.
-    orient: an Orient -- the pictures are turned on the device (see Orient); H x W and rois speak of the turned pictures."""
+    orient: an Orient -- the pictures are turned on the device (see Orient); H x W and rois speak of the turned pictures.
+    pixels: "libjpeg" -- see Batch."""
     import torch
     n = len(datas)
     if not isinstance(out, torch.Tensor) or out.dim() != 4 or out.shape[0] != n:
@@ -899,7 +938,7 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
             raise MjxError(ERR_INVALID_ARG, "resize to %d x %d into a tensor of %d x %d" % (resize.width, resize.height, w, h))
     else:
         rs = None
-    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt, resize=rs, orient=orient)
+    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt, resize=rs, orient=orient, pixels=pixels)
     batch.close()
     return status
 
@@ -923,9 +962,9 @@ class Pool:
     def set_deal(self, round_robin):
         _check(lib().mjx_pool_set_deal(self.h, 1 if round_robin else 0), "mjx_pool_set_deal")
 
-    def decode_batch(self, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads_per_device=0, device_destuff=None, scale=1, rois=None):
+    def decode_batch(self, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads_per_device=0, device_destuff=None, scale=1, rois=None, pixels=None):
         """-> PoolResult; .slot_of[i], .status[i], .rgb(i), .rc (the call's return code: a failed slot fails its own files only).
-        scale, rois: see Batch (a file's rectangle follows it to its slot)."""
+        scale, rois, pixels: see Batch (a file's rectangle follows it to its slot)."""
         n = len(datas)
         arr = (ctypes.c_char_p * max(n, 1))(*[bytes(d) for d in datas])
         lens = (_sz * max(n, 1))(*[len(d) for d in datas])
@@ -933,7 +972,7 @@ class Pool:
         slots = (_int * max(n, 1))()
         ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
         h = _vp()
-        o = _opts(strict_ref, layout, device_destuff=device_destuff, scale=scale, rois=rois)
+        o = _opts(strict_ref, layout, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels)
         rc = lib().mjx_pool_decode_batch(self.h, arr, lens, n, ctypes.byref(o), int(threads_per_device), slots, ptrs, st, ctypes.byref(h))
         if not h:
             _check(rc, "mjx_pool_decode_batch")
@@ -1021,20 +1060,20 @@ class PoolResult:
             pass
 
 
-def plan_tiles(data, roi=None, scale=1):
+def plan_tiles(data, roi=None, scale=1, pixels=None):
     """Host only: the stage-B tiles a decode of this file with this rectangle and scale reads -> see ParsedScan.plan_tiles."""
     scan = ParsedScan(data)
     try:
-        return scan.plan_tiles(roi=roi, scale=scale)
+        return scan.plan_tiles(roi=roi, scale=scale, pixels=pixels)
     finally:
         scan.close()
 
 
-def resize_plan(data, resize, roi=None, scale=1):
+def resize_plan(data, resize, roi=None, scale=1, pixels=None):
     """Host only: the scale, rectangle and tap counts of a resized decode of this file -> see ParsedScan.resize_plan."""
     scan = ParsedScan(data)
     try:
-        return scan.resize_plan(resize, roi=roi, scale=scale)
+        return scan.resize_plan(resize, roi=roi, scale=scale, pixels=pixels)
     finally:
         scan.close()
 
@@ -1057,11 +1096,11 @@ def output_layout(data, output=None, i=0, roi=None, scale=1):
         scan.close()
 
 
-def decode(data, strict_ref=False, layout=LAYOUT_STANDARD, scale=1, roi=None):
+def decode(data, strict_ref=False, layout=LAYOUT_STANDARD, scale=1, roi=None, pixels=None):
     """One-shot C entry point mjx_decode (parse + GPU decode + copy back) -> ndarray [H, W, 3] uint8.  scale: see Batch.
     roi: (x, y, w, h) of the scaled picture -- the array is that rectangle, [h, w, 3]."""
     img = Image()
-    o = _opts(strict_ref, layout, scale=scale, rois=roi)
+    o = _opts(strict_ref, layout, scale=scale, rois=roi, pixels=pixels)
     _check(lib().mjx_decode(bytes(data), len(data), ctypes.byref(o), ctypes.byref(img)), "mjx_decode")
     try:
         return np.ctypeslib.as_array(img.rgb, (img.height, img.width, 3)).copy()

@@ -163,6 +163,8 @@ struct Chunk {
     uint32_t max_wg = 0, merge_wgs = 0, max_tiles = 0, lut_cap = 0, max_tile_blocks = 0, mode_mask = 0, layout_mask = 0, max_segs = 0, bpm_mask = 0, max_restart_segs = 0;
     uint64_t plane_words = 0;      // REF_COMPAT scratch of the chunk
     uint32_t max_pixel_wgs = 0;
+    uint64_t lj_words = 0;         // libjpeg's pixels: the component planes of the chunk's pictures, in the same scratch (a call is one or the other)
+    uint32_t max_lj_tiles = 0;     // ... and the workgroups of k_upsample_color for its largest rectangle (0: no such picture)
     uint32_t max_dc_wgs = 0;       // scaled decode at 1/8: workgroups of k_dc_color for the chunk's largest picture
     uint32_t max_dc_roi_wgs = 0;   // ... and of k_dc_color_roi for its largest rectangle
     uint32_t max_dc_out_wgs = 0;   // ... and of k_dc_color_out for its largest picture with an output description
@@ -475,7 +477,7 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
     d.valid = 1;
     d.nseg = p.nseg;
     d.restart_mcus = p.restart_mcus;
-    d.mode = (p.ncomp == 3 && p.h[0] == 2 && p.v[0] == 2 && p.h[1] == 1 && p.v[1] == 1 && p.h[2] == 1 && p.v[2] == 1) ? 1 : 0;
+    d.mode = (!p.lj && p.ncomp == 3 && p.h[0] == 2 && p.v[0] == 2 && p.h[1] == 1 && p.v[1] == 1 && p.h[2] == 1 && p.v[2] == 1) ? 1 : 0;
     d.scale = p.scale;
     d.out_w = p.out_w;
     d.out_h = p.out_h;
@@ -515,6 +517,19 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
         d.out_row_pitch = p.out_row_pitch; d.out_plane_pitch = p.out_plane_pitch;
         d.out_dtype = p.out_dtype; d.out_planar = p.out_planar; d.out_bgr = p.out_bgr;
         for (uint32_t c = 0; c < 3; c++) { d.out_scale[c] = p.out_scale[c]; d.out_bias[c] = p.out_bias[c]; }
+    }
+    // libjpeg's pixels: one plane form for every sampling layout (4:2:0 takes the generic tile), whatever the picture leaves as --
+    // k_upsample_color writes the packed picture (also a resize's or an orientation's intermediate) or the output format
+    if (p.lj) {
+        d.mode = kPlaneMode;
+        d.lj_on = 1;
+        d.lj_out = p.out_on && !p.rs_on ? 1u : 0u;
+        uint64_t off = 0;
+        for (uint32_t c = 0; c < p.ncomp; c++) {
+            d.lj_stride[c] = p.mcux * 8 * p.h[c];
+            d.lj_off[c] = off;
+            off += uint64_t(d.lj_stride[c]) * p.mcuy * 8 * p.v[c];
+        }
     }
     d.role = p.role;
     d.wg_lanes = p.wg_lanes;
@@ -632,6 +647,11 @@ void plan_chunks(mjx_batch *b)
                     c.plane_words += uint64_t(d.width) * d.height * d.ncomp;
                     c.max_pixel_wgs = std::max<uint32_t>(c.max_pixel_wgs, uint32_t((uint64_t(d.width) * d.height + 255) / 256));
                 }
+                if (d.lj_on && d.role != 1) {        // (the planes span the MCU grid: whole 64-byte block rows, so every plane starts on a multiple of 8)
+                    d.plane_off = c.lj_words;
+                    c.lj_words += (d.lj_off[d.ncomp - 1] + uint64_t(d.lj_stride[d.ncomp - 1]) * d.mcuy * 8 * d.cv[d.ncomp - 1]) / 8;
+                    c.max_lj_tiles = std::max<uint32_t>(c.max_lj_tiles, lj_tiles(d.roi_x, d.roi_w, d.roi_h));
+                }
                 c.max_segs = std::max<uint32_t>(c.max_segs, (d.nmcu + kDcSegMcus - 1) / kDcSegMcus);
             }
             b->info[i].chunk = uint32_t(b->chunks.size());
@@ -691,7 +711,7 @@ int allocate_work_buffers(mjx_batch *b, DevArena &ar)
     ar.take(&b->d_segsum, max_segsum * 3 * sizeof(int32_t));
     {
         uint64_t max_planes = 0;
-        for (const Chunk &c : b->chunks) max_planes = std::max(max_planes, c.plane_words);
+        for (const Chunk &c : b->chunks) max_planes = std::max({max_planes, c.plane_words, c.lj_words});
         if (max_planes) ar.take(&b->d_planes, size_t(max_planes) * 8);
     }
     ar.take(&b->d_entries, size_t(b->opts.keep_coefs ? std::max<uint64_t>(total_entries, 4) : max_entries) * 4 + 64);
@@ -723,7 +743,7 @@ int allocate_work_buffers(mjx_batch *b, DevArena &ar)
         ar.take(&a.d_items, size_t(max_nsub) * 6 * sizeof(uint32_t));
         ar.take(&a.d_segsum, max_segsum * 3 * sizeof(int32_t));
         uint64_t max_planes = 0;
-        for (const Chunk &c : b->chunks) max_planes = std::max(max_planes, c.plane_words);
+        for (const Chunk &c : b->chunks) max_planes = std::max({max_planes, c.plane_words, c.lj_words});
         if (max_planes) ar.take(&a.d_planes, size_t(max_planes) * 8);
         if (b->opts.keep_coefs) {
             a.d_entries = b->d_entries; a.d_tile_eoff = b->d_tile_eoff; a.d_dc = b->d_dc; a.d_dcd = b->d_dcd;
@@ -940,6 +960,11 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
         if (c.max_dc_roi_wgs) launch_dc_color(sp, c.max_dc_roi_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true);
         if (c.max_dc_out_wgs) launch_dc_color(sp, c.max_dc_out_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true, true);
         prof_end(b, sp);
+        if (c.max_lj_tiles) {          // libjpeg's pixels: the chunk's component planes -> its pictures (or the intermediates of the passes below)
+            prof_begin(b, MJX_K_RESIZE, sp);
+            launch_upsample_color(sp, c.max_lj_tiles, nimg, imgs, reinterpret_cast<const uint8_t *>(SCR(d_planes)), b->d_rgb, b->d_img_flags);
+            prof_end(b, sp);
+        }
         if (c.max_rs_tiles) {          // resize on the device: the chunk's intermediates -> the target pictures, behind its stage B
             prof_begin(b, MJX_K_RESIZE, sp);
             launch_resize_out(sp, c.max_rs_tiles, nimg, imgs, b->d_rgb, b->d_img_flags);
@@ -1989,6 +2014,42 @@ extern "C" int mjx_resize_weights(uint32_t n_in, uint32_t n_out, int antialias, 
     return MJX_OK;
 }
 
+// Host-only: libjpeg's pixels from given component planes, through the routines k_upsample_color runs (lj_pixels8).  The planes are
+// copied into rows padded as the kernel's are (LjPlane: multiples of 8), the padding filled with a value no edge sample is likely
+// to have, so that a read the clamping should have replaced shows.
+extern "C" int mjx_upsample_color_host(const uint8_t *const *planes, const uint32_t *cw, const uint32_t *ch, const uint8_t *rh,
+                                       const uint8_t *rv, uint32_t ncomp, const mjx_rect *rect, uint8_t *rgb)
+{
+    return guarded([&]() -> int {
+    if (!planes || !cw || !ch || !rh || !rv || !rect || !rgb || (ncomp != 1 && ncomp != 3) || !rect->w || !rect->h) return MJX_ERR_INVALID_ARG;
+    if (rect->x > kResizeMaxDim || rect->y > kResizeMaxDim || rect->w > kResizeMaxDim || rect->h > kResizeMaxDim) return MJX_ERR_INVALID_ARG;
+    std::vector<std::vector<uint64_t>> store(ncomp);
+    LjPlane pl[3];
+    for (uint32_t c = 0; c < ncomp; c++) {
+        if (!planes[c] || !cw[c] || !ch[c] || cw[c] > kResizeMaxDim || ch[c] > kResizeMaxDim || rh[c] < 1 || rh[c] > 2 || rv[c] < 1 || rv[c] > 2) return MJX_ERR_INVALID_ARG;
+        if ((rect->x + rect->w - 1) / rh[c] >= cw[c] || (rect->y + rect->h - 1) / rv[c] >= ch[c]) return MJX_ERR_INVALID_ARG;
+        const uint32_t stride = (cw[c] + 7u) & ~7u;
+        store[c].assign(size_t(stride) / 8 * ch[c], 0xa5a5a5a5a5a5a5a5ull);
+        uint8_t *dst = reinterpret_cast<uint8_t *>(store[c].data());
+        for (uint32_t y = 0; y < ch[c]; y++) std::memcpy(dst + size_t(y) * stride, planes[c] + size_t(y) * cw[c], cw[c]);
+        pl[c] = LjPlane{dst, stride, cw[c], ch[c], rh[c], rv[c]};
+    }
+    for (uint32_t c = ncomp; c < 3; c++) pl[c] = pl[0];
+    for (uint32_t y = rect->y; y < rect->y + rect->h; y++)
+        for (uint32_t X0 = rect->x & ~(kLjStrip - 1u); X0 < rect->x + rect->w; X0 += kLjStrip) {
+            uint32_t w[6];
+            lj_pixels8(pl, ncomp, X0, y, w);
+            for (uint32_t k = 0; k < kLjStrip; k++) {
+                const uint32_t x = X0 + k;
+                if (x < rect->x || x >= rect->x + rect->w) continue;
+                uint8_t *o = rgb + (size_t(y - rect->y) * rect->w + (x - rect->x)) * 3;
+                for (uint32_t q = 0; q < 3; q++) o[q] = uint8_t(w[(3 * k + q) >> 2] >> (((3 * k + q) & 3u) * 8u));
+            }
+        }
+    return MJX_OK;
+    });
+}
+
 // Host-only: what an oriented decode of this picture as input i takes and gives -- the planner's own (plan_input_for): the size of
 // the picture that leaves, the rectangle of the stored picture the intermediate covers and the scale it is decoded at.
 extern "C" int mjx_orient_plan(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_resize *rs, uint8_t code, size_t i,
@@ -2044,6 +2105,7 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
         p.width = d.width; p.height = d.height; p.ncomp = d.ncomp; p.bpm = d.bpm; p.hmax = d.hmax; p.vmax = d.vmax;
         p.scale = d.scale ? d.scale : 1u; p.out_w = d.out_w; p.out_h = d.out_h;      // (the copies keep the source's scale)
         p.cropped = src->info[k].cropped;                                             // (... and its rectangle)
+        p.lj = src->himages[k].lj_on != 0;                                            // (... and its pixels)
         if (src->info[k].out_on) {                                                    // (... and its output format)
             const ImageInfo &fi = src->info[k];
             p.out_on = true;
@@ -3076,8 +3138,8 @@ extern "C" const char *mjx_version(void)
     static char v[160];
     static std::once_flag once;
     std::call_once(once, [] {
-        std::snprintf(v, sizeof v, "mjx 0.2 gfx950 subseq_bits=%d..%d checkpoint_bits=%d lut_primary_bits=%d huff_wg_lanes=%d merge_wg_lanes=%d",
-                      kSubseqBits, kSubseqBits * 5 / 4, kCpBits, kLutPrimaryBits, kHuffWg, kMergeWg);
+        std::snprintf(v, sizeof v, "mjx 0.3 abi=%d gfx950 subseq_bits=%d..%d checkpoint_bits=%d lut_primary_bits=%d huff_wg_lanes=%d merge_wg_lanes=%d",
+                      MJX_ABI_VERSION, kSubseqBits, kSubseqBits * 5 / 4, kCpBits, kLutPrimaryBits, kHuffWg, kMergeWg);
     });
     return v;
 }

@@ -1,6 +1,7 @@
 // mjx_cli.cpp -- counterpart of the reference's CLI (src/main.rs:24-40):  mjx_cli <in.jpeg> <out.ppm> [--p6] [--strict]
-// [--scale N] [--crop X,Y,W,H]  (N = 2, 4, 8: the picture decoded at 1/N in the DCT domain, mjx_opts.scale_denom; --crop: only that
-// rectangle of the -- scaled -- picture is decoded and written, mjx_opts.rois)
+// [--scale N] [--crop X,Y,W,H] [--libjpeg-pixels]  (N = 2, 4, 8: the picture decoded at 1/N in the DCT domain, mjx_opts.scale_denom;
+// --crop: only that rectangle of the -- scaled -- picture is decoded and written, mjx_opts.rois; --libjpeg-pixels: rounded samples,
+// fancy chroma upsampling and libjpeg's integer colour tables, mjx_opts.pixels = MJX_PIXELS_LIBJPEG)
 // Writes the same ASCII P3 file ("P3\n{w} {h}\n255\n" then "r g b\n" per pixel, main.rs:35-39), buffered; --p6 writes
 // binary PPM instead.  Exit code = MJX_* status.
 #include "jpeg.hpp"
@@ -13,7 +14,7 @@
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s <input.jpeg> <output.ppm> [--p6] [--strict] [--ref-compat] [--scale N] [--crop X,Y,W,H]\n", argv[0]);   // main.rs:26-28 expect()
+        std::fprintf(stderr, "usage: %s <input.jpeg> <output.ppm> [--p6] [--strict] [--ref-compat] [--scale N] [--crop X,Y,W,H] [--libjpeg-pixels]\n", argv[0]);   // main.rs:26-28 expect()
         return MJX_ERR_INVALID_ARG;
     }
     bool p6 = false;
@@ -23,6 +24,7 @@ int main(int argc, char **argv)
         if (!std::strcmp(argv[i], "--p6")) p6 = true;
         else if (!std::strcmp(argv[i], "--strict")) opts.strict_ref = 1;
         else if (!std::strcmp(argv[i], "--ref-compat")) opts.layout = MJX_LAYOUT_REF_COMPAT;
+        else if (!std::strcmp(argv[i], "--libjpeg-pixels")) opts.pixels = MJX_PIXELS_LIBJPEG;
         else if (!std::strcmp(argv[i], "--scale")) {
             const long v = i + 1 < argc ? std::strtol(argv[++i], nullptr, 10) : -1;
             if (v < 0 || v > 255) { std::fprintf(stderr, "--scale takes 1, 2, 4 or 8\n"); return MJX_ERR_INVALID_ARG; }

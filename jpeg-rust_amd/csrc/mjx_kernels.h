@@ -4,6 +4,14 @@
 
 #include "mjx_huff.h"
 
+#include <stddef.h>
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MJX_UNROLL _Pragma("unroll")
+#else
+#define MJX_UNROLL
+#endif
+
 namespace mjx {
 
 constexpr int kWgLanes = 256;                                   // lanes of the scan / prefix-sum workgroups
@@ -113,9 +121,18 @@ struct DevImage {
     // or byte rs_off of the pool; or_on = 2: k_resize_orient resamples orient_c(S) to rs_w x rs_h (rs_on stays 0: k_resize_out
     // passes over the picture).
     uint32_t orient, or_on;
+    // libjpeg's pixels (mjx_opts.pixels = MJX_PIXELS_LIBJPEG; lj_on, mode kPlaneMode): stage B stores the rounded samples of component c
+    // as a uint8 plane over the whole MCU grid -- rows of lj_stride[c] = mcux * 8 * ch[c] bytes, mcuy * 8 * cv[c] of them -- at byte
+    // plane_off * 8 + lj_off[c] of the chunk's plane scratch, and k_upsample_color makes the picture of them: the packed picture at
+    // rgb_off (what a resize or an orientation then works on) or, lj_out = 1, the output format out_* describe.  roi_m* and
+    // roi_tile* are those of the rectangle grown by the filter's reach.
+    uint32_t lj_on, lj_out;
+    uint32_t lj_stride[3];
+    uint64_t lj_off[3];
 };
 constexpr uint32_t kRoiMode = 8;
 constexpr uint32_t kOutMode = 16;      // + m (0, 1, 3, 4; 5: k_dc_color_out): the forms for pictures with an output description
+constexpr uint32_t kPlaneMode = 24;    // + 0: the form that writes component planes (libjpeg's pixels; 4:2:0 takes the generic form too)
 
 // Region-of-interest decode: does tile t -- T consecutive MCUs in raster order, so it may wrap into the next MCU row -- hold an MCU
 // of the MCU rows r0 .. r1 and the MCU columns c0 .. c1?  Arithmetic on uniform values only: stage B decides per tile without a
@@ -179,6 +196,126 @@ MJX_HD uint32_t orient_compose(uint32_t first, uint32_t then)
 }
 constexpr uint32_t kOrientTile = 64;                        // k_orient_out: a workgroup owns kOrientTile x kOrientTile pixels of D
 MJX_HD uint32_t orient_tiles(uint32_t w, uint32_t h) { return ((w + kOrientTile - 1) / kOrientTile) * ((h + kOrientTile - 1) / kOrientTile); }
+
+// ---- libjpeg's pixels (mjx_opts.pixels = MJX_PIXELS_LIBJPEG): fancy upsampling and jdcolor.c's integer colour step ---------------
+// A component plane: cw x ch samples in rows of `stride` bytes; s and stride are multiples of 8 and stride >= cw rounded up to 8, so
+// that the aligned 4- and 8-byte reads below stay inside a row (what they bring in from behind cw is never used: indices clamp to
+// the plane's edge).  rh, rv: the upsampling ratios, 1 or 2.  k_upsample_color and the host (mjx_upsample_color_host) run these
+// routines; a lane makes 8 adjacent pixels of one output row.
+struct LjPlane { const uint8_t *s; uint32_t stride, cw, ch, rh, rv; };
+constexpr uint32_t kLjStrip = 8;                               // pixels a lane makes
+constexpr uint32_t kLjTileW = 64 * kLjStrip, kLjTileH = 16;    // the tile of a workgroup of k_upsample_color: a wave per row, four rows each
+MJX_HD uint32_t lj_tiles(uint32_t x, uint32_t w, uint32_t h)   // strips start on multiples of kLjStrip of the PICTURE (aligned plane reads)
+{
+    const uint32_t span = x % kLjStrip + w;
+    return ((span + kLjTileW - 1) / kLjTileW) * ((h + kLjTileH - 1) / kLjTileH);
+}
+MJX_HD uint32_t lj_ld32(const uint8_t *p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *reinterpret_cast<const uint32_t *>(p);
+#else
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+#endif
+}
+// the samples X0 .. X0 + 7 (X0 a multiple of 8) of one row
+MJX_HD void lj_row8(const uint8_t *row, uint32_t X0, int32_t v[8])
+{
+    const uint32_t a = lj_ld32(row + X0), b = lj_ld32(row + X0 + 4);
+MJX_UNROLL
+    for (uint32_t k = 0; k < 4; k++) { v[k] = int32_t((a >> (8 * k)) & 0xffu); v[4 + k] = int32_t((b >> (8 * k)) & 0xffu); }
+}
+// the samples i0 - 1 .. i0 + 4 (i0 a multiple of 4, i0 < cw) of one row, indices clamped to [0, cw)
+MJX_HD void lj_row6(const uint8_t *row, uint32_t i0, uint32_t cw, int32_t v[6])
+{
+    const uint32_t a = lj_ld32(row + i0);
+MJX_UNROLL
+    for (uint32_t k = 0; k < 4; k++) v[1 + k] = int32_t((a >> (8 * k)) & 0xffu);
+    v[0] = i0 ? int32_t(row[i0 - 1]) : v[1];
+    v[5] = int32_t(row[i0 + 4 < cw ? i0 + 4 : i0]);               // (clamped below when it lies outside; the read stays inside the row)
+MJX_UNROLL
+    for (uint32_t k = 2; k < 6; k++) v[k] = i0 + k - 1 < cw ? v[k] : v[k - 1];
+}
+// Component p at the 8 pixels (X0 .. X0 + 7, Y) of the picture, X0 a multiple of 8 with X0 / rh < cw and Y / rv < ch:
+//   (1, 1) the sample; (2, 1) out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2; (1, 2) the same down the
+//   columns, bias 1 for the upper output row and 2 for the lower; (2, 2) t[i] = 3 near[i] + far[i], out[2i] = (3 t[i] + t[i-1] + 8) >> 4,
+//   out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4 -- jdsample.c's h2v1 / h2v2 fancy upsampling with edge replication.
+MJX_HD void lj_strip8(const LjPlane &p, uint32_t X0, uint32_t Y, int32_t out[8])
+{
+    const uint32_t j = p.rv == 2u ? Y >> 1 : Y;
+    uint32_t jf = j;                                               // the far row: above for even output rows, below for odd, clamped
+    if (p.rv == 2u) jf = (Y & 1u) ? (j + 1u < p.ch ? j + 1u : j) : (j ? j - 1u : 0u);
+    const uint8_t *rn = p.s + size_t(j) * p.stride, *rf = p.s + size_t(jf) * p.stride;     // the near and the far row
+    if (p.rh == 1u) {
+        int32_t a[8];
+        lj_row8(rn, X0, a);
+        if (p.rv == 2u) {
+            int32_t b[8];
+            lj_row8(rf, X0, b);
+            const int32_t bias = (Y & 1u) ? 2 : 1;
+MJX_UNROLL
+            for (uint32_t k = 0; k < 8; k++) a[k] = (3 * a[k] + b[k] + bias) >> 2;
+        }
+MJX_UNROLL
+        for (uint32_t k = 0; k < 8; k++) out[k] = a[k];
+    } else {
+        int32_t t[6];
+        lj_row6(rn, X0 >> 1, p.cw, t);
+        if (p.rv == 2u) {
+            int32_t b[6];
+            lj_row6(rf, X0 >> 1, p.cw, b);
+MJX_UNROLL
+            for (uint32_t k = 0; k < 6; k++) t[k] = 3 * t[k] + b[k];
+        }
+        const int32_t be = p.rv == 2u ? 8 : 1, bo = p.rv == 2u ? 7 : 2, sh = p.rv == 2u ? 4 : 2;
+MJX_UNROLL
+        for (uint32_t k = 0; k < 4; k++) {
+            out[2 * k] = (3 * t[k + 1] + t[k] + be) >> sh;
+            out[2 * k + 1] = (3 * t[k + 1] + t[k + 2] + bo) >> sh;
+        }
+    }
+}
+// jdcolor.c: FIX(x) = int(x 65536 + 0.5), R = Y + ((FIX(1.402) cr + 32768) >> 16) and so on, the shifts arithmetic.  Computed in
+// float32, where it is EXACT: every product and sum is a whole number below 2^24 in magnitude (116130 * 128 + 32768 = 14.9 M), the
+// scaling by 2^-16 is exact and floor is the arithmetic shift -- fused or not, rounding never happens.  On the device that is five
+// full-rate instructions per channel where v_mul_lo_u32 alone costs four, and the clamp and the byte's place are one
+// v_cvt_pk_u8_f32 (it saturates to [0, 255]; the value is a whole number, so its rounding mode does not matter).
+MJX_HD void lj_color(float y, float cb, float cr, float &r, float &g, float &b)      // whole numbers in, whole numbers out, not clamped
+{
+    cb -= 128.0f; cr -= 128.0f;
+    r = y + __builtin_floorf((91881.0f * cr + 32768.0f) * (1.0f / 65536.0f));
+    b = y + __builtin_floorf((116130.0f * cb + 32768.0f) * (1.0f / 65536.0f));
+    g = y + __builtin_floorf(((-22554.0f * cb + 32768.0f) - 46802.0f * cr) * (1.0f / 65536.0f));
+}
+// clamp(v, 0, 255) of a whole number, placed as byte `byte` of `word`
+MJX_HD uint32_t lj_put_u8(float v, uint32_t byte, uint32_t word)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_cvt_pk_u8_f32(v, byte, word);
+#else
+    const uint32_t u = v < 0.0f ? 0u : v > 255.0f ? 255u : uint32_t(v);
+    return (word & ~(0xffu << (8u * byte))) | (u << (8u * byte));
+#endif
+}
+// The 8 pixels (X0 .. X0 + 7, Y) as 24 bytes R,G,B,R,G,B ... in six little-endian words; one component: R = G = B = the sample.
+MJX_HD void lj_pixels8(const LjPlane pl[3], uint32_t ncomp, uint32_t X0, uint32_t Y, uint32_t w[6])
+{
+    int32_t y[8], cb[8], cr[8];
+    lj_strip8(pl[0], X0, Y, y);
+    if (ncomp == 3u) { lj_strip8(pl[1], X0, Y, cb); lj_strip8(pl[2], X0, Y, cr); }
+MJX_UNROLL
+    for (uint32_t k = 0; k < 6; k++) w[k] = 0;
+MJX_UNROLL
+    for (uint32_t k = 0; k < 8; k++) {
+        float c[3];
+        c[0] = c[1] = c[2] = float(y[k]);
+        if (ncomp == 3u) lj_color(float(y[k]), float(cb[k]), float(cr[k]), c[0], c[1], c[2]);
+MJX_UNROLL
+        for (uint32_t q = 0; q < 3; q++) w[(3 * k + q) >> 2] = lj_put_u8(c[q], (3 * k + q) & 3u, w[(3 * k + q) >> 2]);
+    }
+}
 
 // ---- resize on the device (mjx_resize): the separable triangle filter, one axis -----------------------------------------------
 // Output coordinate X of an axis n_in -> n_out samples the input at c = (2X + 1) n_in / (2 n_out) with a triangle of half width
@@ -317,11 +454,6 @@ MJX_HD uint64_t stream_phys(uint32_t s, uint32_t j, uint32_t rows) { return (uin
 // counts of the tile's first kQuadSegs subsequences into 16 bytes; tiles that span more (beyond quality ~97) take the loop over
 // the run lengths at the head of the stream region.  (With a dependent LDS read per subsequence in the fetch -- which sits
 // between the scatter phase and the barrier in front of the inverse DCT -- stage B took 0.3 ms more per 2048 pictures.)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MJX_UNROLL _Pragma("unroll")
-#else
-#define MJX_UNROLL
-#endif
 constexpr uint32_t kQuadSegs = 8;
 // What the workgroup prepares per tile (32 bytes of LDS, two 16-byte reads): one word per subsequence of the tile, in order --
 //   cumulative groups of the tile after this subsequence [13:0] | first group of the subsequence's run [23:14] | label offset [31:24]
@@ -596,6 +728,9 @@ void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const 
 // (k_orient_out), or per tile of the target (resize_tiles) and picture with or_on == 2 (k_resize_orient)
 void launch_orient_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
 void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
+// libjpeg's pixels, behind stage B: one workgroup per tile of the rectangle (lj_tiles) and picture with DevImage::lj_on
+void launch_upsample_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
+                           const uint32_t *img_flags);
 #endif
 
 }   // namespace mjx

@@ -3383,6 +3383,37 @@ __device__ __forceinline__ void pixels_generic(const GenShape &g, const float *t
     }
 }
 
+// Phase 3 of the form that writes component planes (k_idct_color<kPlaneMode, ...>, libjpeg's pixels): the tile's samples leave as
+// bytes clamp(floor(f + 128.5), 0, 255) -- the 128.5 sits on the DC term, pack_u8 floors and saturates --, a lane per row of a
+// block (eight samples, one 8-byte store), into the picture's planes.  These span the whole MCU grid, so nothing is clipped here:
+// k_upsample_color reads only what lies inside the components' true sizes.
+__device__ __forceinline__ void planes_store(const DevImage &im, const float *tile, uint32_t m0, uint32_t nblk, uint32_t bpm, uint32_t mcux,
+                                             uint8_t *pl)
+{
+    const uint32_t tid = threadIdx.x, r = tid & 7u;
+    // (one division per lane and tile: a lane's blocks lie 32 apart, so MCU and place in the MCU advance by uniform steps, and a tile
+    // of at most 64 MCUs leaves its first MCU row at most once unless the picture is narrower than the tile)
+    const uint32_t t_inc = 32u / bpm, b_inc = 32u - t_inc * bpm;
+    const uint32_t my0 = m0 / mcux, mx0 = m0 - my0 * mcux;
+    uint32_t t = (tid >> 3) / bpm, b = (tid >> 3) - t * bpm;
+    for (uint32_t blk = tid >> 3; blk < nblk; blk += 32u, t += t_inc, b += b_inc) {
+        if (b >= bpm) { b -= bpm; t++; }
+        uint32_t mx = mx0 + t, my = my0;
+        if (mx >= mcux) {
+            mx -= mcux; my++;
+            if (mx >= mcux) { const uint32_t q = mx / mcux; my += q; mx -= q * mcux; }
+        }
+        const uint32_t c = im.blk_comp[b];
+        const uint32_t bx = mx * im.ch[c] + im.blk_bx[b], by = my * im.cv[c] + im.blk_by[b];
+        const float4 lo = *reinterpret_cast<const float4 *>(tile + blk * kPixStride + r * 8);
+        const float4 hi = *reinterpret_cast<const float4 *>(tile + blk * kPixStride + r * 8 + 4);
+        uint2 w;
+        w.x = pack_u8(lo.w, 3, pack_u8(lo.z, 2, pack_u8(lo.y, 1, pack_u8(lo.x, 0, 0u))));
+        w.y = pack_u8(hi.w, 3, pack_u8(hi.z, 2, pack_u8(hi.y, 1, pack_u8(hi.x, 0, 0u))));
+        *reinterpret_cast<uint2 *>(pl + im.lj_off[c] + (size_t(by) * 8u + r) * im.lj_stride[c] + bx * 8u) = w;
+    }
+}
+
 // ---- REF_COMPAT placement (MODE 2) ---------------------------------------------------------------------------
 // Reproduces decoder.rs:259-312 + fill_block_in_array (:347-379) bug for bug: the component's blocks
 // are taken in decode order as a raster counter, get_indices maps the counter to a block position with formulas
@@ -3590,6 +3621,9 @@ __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *ti
 //        load, no scatter, no transform and no barrier, and the prefetch chain runs from one wanted tile to the next.  The planar
 //        form (its segment lists are prepared two tiles ahead in a ring of three) walks every tile of the row band.  Phase 3 writes
 //        the rectangle's pixels only (store4_roi); the 4:2:0 form takes plain reads there, so `clean` stays false.
+//   PLANES  libjpeg's pixels (MODE_ = kPlaneMode, every sampling layout): the ROI form over the tiles of the rectangle grown by the
+//        upsampling filter's reach (the planner's roi_m*), phase 3 storing every component's rounded samples as bytes (planes_store);
+//        k_upsample_color makes the picture
 //   OUT  output formats (MODE_ = MODE + kOutMode, the mode of a picture with an output description): the ROI form -- a picture without a
 //        rectangle is its own whole rectangle --, phase 3 writing the picture's format (store4_out, DevImage::out_*)
 template <int MODE_, int PF, int SRC>
@@ -3600,9 +3634,11 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                                                      uint8_t *__restrict__ rgb, unsigned long long *__restrict__ planes,
                                                      const uint32_t *__restrict__ img_flags, uint32_t tiles_per_wg)
 {
-    constexpr bool OUT = MODE_ >= int(kOutMode);              // output formats: the cropped form, the picture its own whole rectangle without one
+    constexpr bool PLANES = MODE_ >= int(kPlaneMode);         // libjpeg's pixels: the cropped form again, phase 3 storing component planes
+    constexpr bool OUT = !PLANES && MODE_ >= int(kOutMode);   // output formats: the cropped form, the picture its own whole rectangle without one
     constexpr bool ROI = MODE_ >= int(kRoiMode);
-    constexpr int MODE = MODE_ - (OUT ? int(kOutMode) : ROI ? int(kRoiMode) : 0);
+    constexpr int MODE = MODE_ - (PLANES ? int(kPlaneMode) : OUT ? int(kOutMode) : ROI ? int(kRoiMode) : 0);
+    static_assert(!PLANES || MODE == 0, "the planes are written by the generic form");
     static_assert(!ROI || MODE != 2, "REF_COMPAT has no rectangles");
     // (its own symbol: dynamic LDS arrays of one name share their alignment, and the entropy kernels ask for 2 KiB)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_px[];
@@ -3727,6 +3763,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     const uint32_t my_comp = im.blk_comp[tid % bpm];
     float my_dc_qm = qmult[im.qm_off + my_comp * 64];
     float my_dc_add = (MODE != 2 && my_comp == 0) ? 128.0f : 0.0f;
+    if constexpr (PLANES) my_dc_add = 128.5f;         // (every component's level shift and the rounding: the store truncates, planes_store)
     float *tile_f = reinterpret_cast<float *>(smem_px);
     GenShape gshape{};
     if (MODE == 0 || SCALED) gshape = gen_shape(im);
@@ -3897,7 +3934,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             if constexpr (OUT) pixels_scaled<scaled_n<MODE>(), true, true>(gshape, tile_f, m0, nm, nullptr, false, roi, &ofmt);
             else pixels_scaled<scaled_n<MODE>(), ROI>(gshape, tile_f, m0, nm, out_img, aligned, roi);
         } else {
-            if constexpr (OUT) pixels_generic_out(gshape, tile_f, m0, nm, roi, ofmt);
+            if constexpr (PLANES) planes_store(im, tile_f, m0, nblk, bpm, mcux, reinterpret_cast<uint8_t *>(planes + im.plane_off));
+            else if constexpr (OUT) pixels_generic_out(gshape, tile_f, m0, nm, roi, ofmt);
             else if constexpr (ROI) pixels_generic_roi(gshape, tile_f, m0, nm, out_img, aligned, roi);
             else pixels_generic(gshape, tile_f, m0, nm, out_img, aligned);
         }
@@ -4183,6 +4221,57 @@ extern "C" __global__ __launch_bounds__(256) void k_orient_out(const DevImage *_
     }
 }
 
+// ---- libjpeg's pixels (mjx_opts.pixels; DevImage::lj_on): component planes -> the picture ------------------------------------------
+// Behind stage B's plane form.  A workgroup owns kLjTileW x kLjTileH pixels of the picture's rectangle, a wave a row at a time (four
+// rows each), a lane kLjStrip = 8 adjacent pixels: per component one or two aligned 8-byte reads, or an aligned 4-byte read and two
+// bytes per chroma row (lj_strip8, mjx_kernels.h -- the routine mjx_upsample_color_host runs), jdcolor.c's integer colour step, and
+// the 24 bytes leave as two strips through the stores stage B itself uses: store4_roi for the packed picture at rgb_off (also the
+// intermediate of a resize or an orientation), store4_out for an output format.  Strips start on multiples of 8 of the PICTURE, so the
+// plane reads are aligned whatever the rectangle's origin; the stores cut a strip at the rectangle's edges.  One store site: the
+// loop over rows and halves is not unrolled (as pixels_420_out).
+// A strip may reach outside the rectangle grown by the filter's reach, into tiles stage B passed over: those plane bytes were never
+// written (the scratch is not cleared), and the lane filters them like any others.  They only ever feed pixels outside the rectangle,
+// which the stores cut away; every read stays inside the picture's planes (the whole MCU grid), whatever they hold.
+__global__ __launch_bounds__(256) void k_upsample_color(const DevImage *__restrict__ images, const uint8_t *__restrict__ planes,
+                                                         uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    if (!im.valid || !im.lj_on || im.role == 1u || img_flags[im.status_idx]) return;
+    const Roi roi{im.roi_x, im.roi_y, im.roi_w, im.roi_h};
+    const uint32_t xb = roi.x & ~(kLjStrip - 1u), tiles_x = (roi.x - xb + roi.w + kLjTileW - 1u) / kLjTileW;
+    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    if (ty * kLjTileH >= roi.h) return;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t px = xb + tx * kLjTileW + (tid & 63u) * kLjStrip;
+    if (px >= roi.x + roi.w) return;
+    const uint32_t width = im.width, height = im.height, ncomp = im.ncomp, hmax = im.hmax, vmax = im.vmax;
+    const uint8_t *base = planes + im.plane_off * 8u;
+    LjPlane pl[3];
+#pragma unroll
+    for (uint32_t c = 0; c < 3; c++) {
+        const uint32_t k = c < ncomp ? c : 0u;
+        pl[c] = LjPlane{base + im.lj_off[k], im.lj_stride[k], (width * im.ch[k] + hmax - 1u) / hmax, (height * im.cv[k] + vmax - 1u) / vmax,
+                        hmax / im.ch[k], vmax / im.cv[k]};
+    }
+    const bool fmt = im.lj_out != 0u;
+    OutFmt of{};
+    if (fmt) of = out_fmt(im, rgb);
+    uint8_t *out_img = rgb + im.rgb_off;
+    uint32_t w[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll 1
+    for (uint32_t it = 0; it < 2u * (kLjTileH / 4u); it++) {
+        const uint32_t py = roi.y + ty * kLjTileH + (tid >> 6) + 4u * (it >> 1), half = it & 1u;
+        if (py >= roi.y + roi.h) break;
+        if (!half) lj_pixels8(pl, ncomp, px, py, w);
+        const uint32_t x4 = px + 4u * half;
+        if (x4 >= width) continue;
+        const Rgb4 v = half ? Rgb4{w[3], w[4], w[5]} : Rgb4{w[0], w[1], w[2]};
+        const uint32_t npix = min(4u, width - x4);
+        if (fmt) store4_out(of, roi, x4, py, v, npix);
+        else store4_roi(out_img, roi, x4, py, v, npix);
+    }
+}
+
 // ---- verification helper: byte-wise comparison of decoded pictures on the device ------------------------------
 // (mjx_batch_compare_rgb: the parity gate of bench.py and the batch-scale tests compare tens of gigabytes of output
 // without copying them to the host.)  One workgroup per 16 KiB of a pair; per pair the largest absolute byte
@@ -4269,7 +4358,8 @@ int configure_kernels(size_t huff_lds, size_t idct_lds)
 #define MJX_ROI_FORMS(M) reinterpret_cast<const void *>(k_idct_color<kRoiMode + M, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<kRoiMode + M, 8, 1>), reinterpret_cast<const void *>(k_idct_color<kRoiMode + M, 8, 2>)
                              MJX_ROI_FORMS(0), MJX_ROI_FORMS(1), MJX_ROI_FORMS(3), MJX_ROI_FORMS(4),
                              MJX_ROI_FORMS(kOutMode - kRoiMode + 0), MJX_ROI_FORMS(kOutMode - kRoiMode + 1),        // (the output formats' forms, kOutMode + m)
-                             MJX_ROI_FORMS(kOutMode - kRoiMode + 3), MJX_ROI_FORMS(kOutMode - kRoiMode + 4)};
+                             MJX_ROI_FORMS(kOutMode - kRoiMode + 3), MJX_ROI_FORMS(kOutMode - kRoiMode + 4),
+                             MJX_ROI_FORMS(kPlaneMode - kRoiMode + 0)};                                              // (libjpeg's pixels: the plane form)
 #undef MJX_ROI_FORMS
         for (const void *f : fns)
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(idct_lds));
@@ -4477,6 +4567,7 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
     MJX_IDCT_ROI(kOutMode - kRoiMode + 1)
     MJX_IDCT_ROI(kOutMode - kRoiMode + 3)
     MJX_IDCT_ROI(kOutMode - kRoiMode + 4)
+    MJX_IDCT_ROI(kPlaneMode - kRoiMode + 0)
 #undef MJX_IDCT_ROI
 }
 
@@ -4517,6 +4608,13 @@ void launch_orient_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const 
 void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags)
 {
     hipLaunchKernelGGL(k_resize_orient, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
+}
+
+void launch_upsample_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
+                           const uint32_t *img_flags)
+{
+    if (max_tiles == 0 || nimg == 0) return;
+    hipLaunchKernelGGL(k_upsample_color, dim3(max_tiles, nimg), dim3(256), 0, st, images, planes, rgb, img_flags);
 }
 
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,

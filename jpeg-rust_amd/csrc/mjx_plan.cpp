@@ -182,6 +182,10 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     if (scale != 1 && scale != 2 && scale != 4 && scale != 8) return fail(MJX_ERR_INVALID_ARG);
     if (scale != 1 && opts.layout == MJX_LAYOUT_REF_COMPAT) return fail(MJX_ERR_INVALID_ARG);    // (the reference has no scaled decode)
     p.scale = scale;
+    // libjpeg's pixels: STANDARD layout at full size only (a scan of a multi-scan file has no pixels: its picture's plan carries the option)
+    if (opts.pixels > MJX_PIXELS_LIBJPEG) return fail(MJX_ERR_INVALID_ARG);
+    const bool lj = opts.pixels == MJX_PIXELS_LIBJPEG && !scan_part;
+    if (lj && (scale != 1 || opts.layout == MJX_LAYOUT_REF_COMPAT || opts.strict_ref)) return fail(MJX_ERR_INVALID_ARG);
     const bool gather = d.n_parts != 0;            // the picture of a multi-scan file: geometry only, no scan of its own
     if (gather) {
         if (!d.parts || d.n_parts < 2 || d.n_parts > 3 || d.ncomp != 3) return fail(MJX_ERR_UNSUPPORTED_FORMAT);
@@ -248,8 +252,13 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     }
     {
         const uint32_t pw = 8 / scale * p.hmax, ph = 8 / scale * p.vmax;      // an MCU's patch of the output picture
-        p.roi_mc0 = p.roi_x / pw; p.roi_mc1 = (p.roi_x + p.roi_w - 1) / pw;
-        p.roi_mr0 = p.roi_y / ph; p.roi_mr1 = (p.roi_y + p.roi_h - 1) / ph;
+        // (libjpeg's pixels: the rectangle grown by the filter's reach -- a pixel's chroma neighbours lie up to hmax x vmax pixels away)
+        const uint32_t gx = lj && p.hmax > 1 ? p.hmax : 0u, gy = lj && p.vmax > 1 ? p.vmax : 0u;
+        const uint32_t x0 = p.roi_x > gx ? p.roi_x - gx : 0u, x1 = std::min(p.out_w - 1, p.roi_x + p.roi_w - 1 + gx);
+        const uint32_t y0 = p.roi_y > gy ? p.roi_y - gy : 0u, y1 = std::min(p.out_h - 1, p.roi_y + p.roi_h - 1 + gy);
+        p.roi_mc0 = x0 / pw; p.roi_mc1 = x1 / pw;
+        p.roi_mr0 = y0 / ph; p.roi_mr1 = y1 / ph;
+        p.lj = lj;
     }
     if (p.layout == MJX_LAYOUT_REF_COMPAT) {
         const uint64_t nb = uint64_t((p.width + 7) / 8) * ((p.height + 7) / 8);    // decoder.rs:164-166
@@ -533,6 +542,7 @@ int resize_opts(uint32_t width, uint32_t height, const mjx_opts &opts_i, const m
     if (opts_i.layout == MJX_LAYOUT_REF_COMPAT) return MJX_ERR_INVALID_ARG;
     if (!rs.auto_scale) return MJX_OK;
     if (opts_i.scale_denom > 1) return MJX_ERR_INVALID_ARG;
+    if (opts_i.pixels == MJX_PIXELS_LIBJPEG) return MJX_OK;               // (libjpeg's pixels exist at full size only: scale 1 for every picture, the rectangle as given)
     if (!width || !height) return MJX_OK;                                  // (plan_image says what is wrong with the picture)
     uint32_t x = 0, y = 0, w = width, h = height;
     if (opts_i.rois && opts_i.n_rois && (opts_i.rois[0].w || opts_i.rois[0].h)) {

@@ -64,6 +64,10 @@ struct ImagePlan {
     // or_copy: there is no resize, rs_w x rs_h is the oriented size of roi_w x roi_h and k_orient_out copies.  Code 1 leaves no trace.
     uint32_t orient = 1;
     bool or_copy = false;
+    // libjpeg's pixels (mjx_opts.pixels = MJX_PIXELS_LIBJPEG): stage B writes component planes and k_upsample_color makes the picture.
+    // roi_m* above are then those of the rectangle grown by the upsampling filter's reach -- one sample of the most subsampled
+    // component, hmax x vmax pixels, on each side, clipped to the picture: the tiles stage B must fill for the rectangle's pixels.
+    bool lj = false;
     const uint8_t *scan = nullptr;
     size_t scan_len = 0;
     // The scan still holds FF00 pairs (and RSTn markers): it is de-stuffed on the device at upload (k_destuff_*), scan_len is

@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""libjpeg's pixels (mjx_opts.pixels = MJX_PIXELS_LIBJPEG) against the default pixels, one process, the headline's inputs.
+
+The batch of bench.py -- 2048 synthetic 3840x2160 4:2:0 q75 pictures, 64 unique ones -- decoded whole, packed RGB
+  reference   the default pixels: stage B converts and stores the picture itself (the parent's path, measured in the same run)
+  libjpeg     stage B stores component planes (about 1.5 bytes per pixel written and read again), k_upsample_color makes the picture
+Both build a base batch of the unique pictures once and tile it per repeat (only one large batch is resident at a time); the two
+take turns inside every repeat and the figure is the best of the repeats.
+
+Per variant: ms per step (every repeat, best, median), per-class kernel ms per step -- idct_color is stage B, resize the class of the
+passes behind it, here k_upsample_color alone --, the bytes written and the device memory the batch took when it was built.
+One JSON object on the last line.
+
+    python tools/bench_libjpeg.py [--steps 5] [--warmup 1] [--repeats 3] [--images 2048]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--images", type=int, default=2048)
+    ap.add_argument("--unique", type=int, default=64)
+    ap.add_argument("--width", type=int, default=3840)
+    ap.add_argument("--height", type=int, default=2160)
+    ap.add_argument("--quality", type=int, default=75)
+    args = ap.parse_args()
+    import torch                         # (first: libmjx.so must find torch's HIP runtime already loaded, as in bench.py)
+    import __graft_entry__ as ge
+    ge.build()
+    mjx = ge.load_package()
+    from bench_output import free_device_bytes
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as ex:
+        datas = list(ex.map(lambda s: mjx.synth_jpeg(args.width, args.height, "420", args.quality, s), range(args.unique)))
+    names = ["reference", "libjpeg"]
+    reps = max(1, args.images // args.unique)
+    n = reps * args.unique
+    ctx = mjx.Context(0, profiling=True, throughput_plan=True)
+    scans = [mjx.ParsedScan(d) for d in datas]
+    bases = {v: mjx.Batch(ctx, scans, pixels=v) for v in names}
+    for v in names:
+        assert all(x == mjx.OK for x in bases[v].create_status), bases[v].create_status
+    runs = {v: [] for v in names}
+    for r in range(args.repeats):
+        for v in names[r % 2:] + names[:r % 2]:
+            free0 = free_device_bytes(mjx)
+            b = bases[v].tile(reps)
+            arena = max(0, free0 - free_device_bytes(mjx))
+            try:
+                for _ in range(args.warmup):
+                    b.decode()
+                    b.wait()
+                b.kernel_ms(reset=True)
+                u0 = b.unconverged_runs()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    b.decode()
+                b.wait()
+                torch.cuda.synchronize()
+                ms = 1e3 * (time.perf_counter() - t0) / args.steps
+                assert b.unconverged_runs() == u0, "a timed region had not converged (%s)" % v
+                bad = [i for i in range(len(b)) if b.status(i) != mjx.OK]
+                assert not bad, "pictures failed (%s): %s" % (v, bad[:8])
+                kms = {k: round(x[0] / args.steps, 4) for k, x in b.kernel_ms(reset=True).items() if x[1]}
+                runs[v].append({"ms_per_step": round(ms, 4), "kernel_ms_per_step": kms, "bytes_written": b.bytes()["rgb"], "arena_bytes": arena})
+                print("%-10s repeat %d: %.3f ms per step, stage B %.3f ms, k_upsample_color %.3f ms, arena %.2f GB"
+                      % (v, r, ms, kms.get("idct_color", 0.0), kms.get("resize", 0.0), arena / 1e9), flush=True)
+            finally:
+                b.close()
+    out = {"images": n, "unique": args.unique, "picture": "%dx%d 4:2:0 q%d" % (args.width, args.height, args.quality), "steps": args.steps,
+           "repeats": args.repeats, "variants": {}}
+    for v in names:
+        best = min(runs[v], key=lambda x: x["ms_per_step"])
+        out["variants"][v] = {"ms_per_step_best": best["ms_per_step"],
+                              "ms_per_step_median": round(statistics.median(x["ms_per_step"] for x in runs[v]), 4),
+                              "all_ms_per_step": [x["ms_per_step"] for x in runs[v]],
+                              "kernel_ms_per_step": best["kernel_ms_per_step"],
+                              "stage_b_ms_all": [x["kernel_ms_per_step"].get("idct_color", 0.0) for x in runs[v]],
+                              "upsample_color_ms_all": [x["kernel_ms_per_step"].get("resize", 0.0) for x in runs[v]],
+                              "bytes_written": best["bytes_written"], "arena_bytes": max(x["arena_bytes"] for x in runs[v])}
+    for b in bases.values():
+        b.close()
+    for s in scans:
+        s.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
