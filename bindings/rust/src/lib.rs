@@ -61,6 +61,18 @@ pub struct mjx_output {
     pub n_dst: u32,
 }
 
+/// MJX_OUTPUT_CHANNELS_OFFSET: the channel count of an output description is byte 3 of mjx_output, the byte behind `bgr`
+/// (0 or 3: three colour channels, 1: luminance).  Set it on the value the call is given.
+pub const MJX_OUTPUT_CHANNELS_OFFSET: usize = 3;
+impl mjx_output {
+    pub fn channels(&self) -> u8 {
+        unsafe { *(self as *const mjx_output as *const u8).add(MJX_OUTPUT_CHANNELS_OFFSET) }
+    }
+    pub fn set_channels(&mut self, channels: u8) {
+        unsafe { *(self as *mut mjx_output as *mut u8).add(MJX_OUTPUT_CHANNELS_OFFSET) = channels }
+    }
+}
+
 /// Orientation on the device: the file's EXIF orientation and / or one code 1..8 per input on top (include/mjx.h: mjx_orient).
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -175,6 +187,7 @@ extern "C" {
     pub fn mjx_free_scan(desc: *mut mjx_scan_desc);
     pub fn mjx_upsample_color_host(planes: *const *const u8, cw: *const u32, ch: *const u32, rh: *const u8, rv: *const u8, ncomp: u32,
                                    rect: *const mjx_rect, rgb: *mut u8) -> c_int;
+    pub fn mjx_upsample_luma_host(plane: *const u8, cw: u32, ch: u32, rh: u8, rv: u8, rect: *const mjx_rect, out: *mut u8) -> c_int;
     pub fn mjx_validate(desc: *const mjx_scan_desc, opts: *const mjx_opts) -> c_int;
     pub fn mjx_plan_tiles(desc: *const mjx_scan_desc, opts: *const mjx_opts, tiles_read: *mut u64, tiles_total: *mut u64,
                           tile_mcus: *mut u32) -> c_int;
@@ -193,6 +206,7 @@ extern "C" {
     pub fn mjx_output_layout(desc: *const mjx_scan_desc, opts: *const mjx_opts, out: *const mjx_output, i: usize, layout: *mut mjx_dst,
                              bytes: *mut usize) -> c_int;
     pub fn mjx_batch_output_info(b: *const mjx_batch, i: usize, layout: *mut mjx_dst, dtype: *mut u8, planar: *mut u8, bgr: *mut u8) -> c_int;
+    pub fn mjx_batch_output_channels(b: *mut mjx_batch, i: usize, channels: *mut u8) -> c_int;
     pub fn mjx_batch_copy_output(b: *mut mjx_batch, i: usize, host: *mut c_void, cap_bytes: usize) -> c_int;
     pub fn mjx_decode_batch_out(ctx: *mut mjx_ctx, jpegs: *const *const u8, lens: *const usize, n: usize, opts: *const mjx_opts,
                                 threads: c_uint, out: *const mjx_output, status: *mut c_int, b: *mut *mut mjx_batch) -> c_int;

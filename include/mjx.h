@@ -130,7 +130,16 @@ typedef struct mjx_opts {
  * OUTPUT channel (with bgr, c = 0 is blue).  An element so takes one of 256 values per channel.
  * Ordering: the library writes on streams of its own.  A caller-owned destination must be idle when mjx_batch_decode (or
  * mjx_decode_batch_out) is called and is complete when mjx_batch_wait (mjx_decode_batch_out) returns; nothing is written outside
- * height rows x width elements (3 width interleaved) x 3 channels at the given pitches. */
+ * height rows x width elements (3 width interleaved) x 3 channels at the given pitches.
+ * Luminance (MJX_OUTPUT_CHANNELS(out) == 1, below): the picture leaves as H x W elements of dtype, one per pixel; chroma is never transformed.  Element
+ * (X, Y) of the rectangle (x, y, w, h) lies at dst + (Y - y) row_pitch + (X - x), row_pitch >= width; plane_pitch, planar and bgr have
+ * no meaning and are ignored (H x W x 1 and 1 x H x W are the same memory); dense library-owned output has row_pitch = width.  The u8
+ * value L is the byte the packed decode of the same build writes into all three channels when the picture's chroma is zero -- the
+ * truncating, saturating store applied to the luminance sample stage B computes, + 128 included -- at the call's scale and
+ * rectangle; for a one-component file the R byte of the packed decode.  With MJX_PIXELS_LIBJPEG L is component 0's rounded sample,
+ * upsampled by its own (rh, rv) with that option's filters where Y is not the most finely sampled component, and there is no
+ * colour step.  A float element is fmaf((float)L, scale[0], bias[0]), F16 rounded from that.  Nothing is written outside height rows
+ * x width elements. */
 enum { MJX_DTYPE_U8 = 0, MJX_DTYPE_F16 = 1, MJX_DTYPE_F32 = 2 };
 typedef struct mjx_dst {      /* caller-owned device memory for one picture; pitches in elements */
     void *dev;                /* first element of channel 0, row 0 */
@@ -146,7 +155,15 @@ typedef struct mjx_output {
     const mjx_dst *dst;       /* NULL: library-owned, dense (row_pitch = width or 3*width, plane_pitch = height*width) */
     uint32_t n_dst;           /* 0 with dst == NULL, else the call's number of inputs; dst[i] belongs to input i */
 } mjx_output;
-/* Per picture, MJX_ERR_INVALID_ARG (nothing is written for it, the others are unaffected): an unknown dtype; MJX_LAYOUT_REF_COMPAT;
+/* The channel count of an output description: byte 3 of mjx_output, the byte behind `bgr` that the declared members leave unused (the
+ * struct's members, size and offsets are as they were; a zero-filled struct means what it meant).  0 or 3: three colour channels;
+ * 1: luminance (above); anything else: MJX_ERR_INVALID_ARG for the picture.  An lvalue: MJX_OUTPUT_CHANNELS(&out) = 1.  Fill the
+ * struct with zeros first (memset, = {0} on a static, value-initialisation in C++) and set the count on the object the call is given:
+ * a member-wise copy of the struct need not carry the byte. */
+#define MJX_OUTPUT_CHANNELS_OFFSET 3
+#define MJX_OUTPUT_CHANNELS(out) (((uint8_t *)(out))[MJX_OUTPUT_CHANNELS_OFFSET])
+/* Per picture, MJX_ERR_INVALID_ARG (nothing is written for it, the others are unaffected): an unknown dtype or channel count;
+ * MJX_LAYOUT_REF_COMPAT;
  * dst[i].width / height other than the picture's output size; a pitch too small; dev NULL or not aligned to the element size; a
  * non-finite scale / bias with a float dtype.  n_dst other than 0 or the call's number of inputs, or dst == NULL with n_dst != 0,
  * fails the call.  The description and dst[] are only borrowed for the duration of the call.
@@ -155,8 +172,8 @@ typedef struct mjx_output {
  * the span from there to the end of its last element, mjx_batch_bytes' rgb_bytes counts the bytes written.  mjx_batch_tile keeps
  * a library-owned format and refuses a batch with caller-owned destinations (the copies would share them).  With caller-owned
  * destinations the batch's device block holds no picture pool at all; with library-owned output the pool is sized by the format.
- * Not built: mjx_decode, the pool (mjx_pool_decode_batch: the slot -- so the device -- of a file is not known to the caller before the
- * deal) and the CLI keep packed RGB. */
+ * Not built: YCbCr output; mjx_decode and the pool (mjx_pool_decode_batch: the slot -- so the device -- of a file is not known to the
+ * caller before the deal) keep packed RGB; the CLI writes packed RGB or, with --luma, the luminance picture. */
 
 /* ---- resize on the device: every picture of a call leaves at one target size -------------------------------------------
  * With a resize description (mjx_batch_create_resize, mjx_decode_batch_resize) picture i is decoded as a packed picture at a
@@ -351,6 +368,8 @@ int mjx_output_layout(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx
 /* The output of picture i of a batch: where it lies (layout->dev: device pointer), its pitches and its format.  A batch without
  * an output description answers with the packed picture's (u8, interleaved, R,G,B). */
 int mjx_batch_output_info(const mjx_batch *b, size_t i, mjx_dst *layout, uint8_t *dtype, uint8_t *planar, uint8_t *bgr);
+/* The channels picture i leaves with: 1 for a luminance picture (MJX_OUTPUT_CHANNELS == 1), 3 for every other batch. */
+int mjx_batch_output_channels(mjx_batch *b, size_t i, uint8_t *channels);
 /* Copy picture i's library-owned output to host memory, dense, as mjx_output_layout sizes it; cap_bytes smaller than that, a
  * caller-owned destination or a batch without an output description: MJX_ERR_INVALID_ARG. */
 int mjx_batch_copy_output(mjx_batch *b, size_t i, void *host, size_t cap_bytes);
@@ -375,6 +394,10 @@ int mjx_resize_weights(uint32_t n_in, uint32_t n_out, int antialias, uint32_t X,
  * ch[c] rv[c]); the plane of an odd picture is one sample short of the picture's size, which the rule allows. */
 int mjx_upsample_color_host(const uint8_t *const *planes, const uint32_t *cw, const uint32_t *ch, const uint8_t *rh, const uint8_t *rv,
                             uint32_t ncomp, const mjx_rect *rect, uint8_t *rgb);
+/* Host-only: MJX_PIXELS_LIBJPEG's luminance picture (MJX_OUTPUT_CHANNELS == 1) on the CPU -- the routine k_upsample_luma itself runs
+ * (lj_luma8, mjx_kernels.h).  One dense plane of cw x ch samples, upsampled by rh, rv (each 1 or 2; 1, 1: the plane itself); out receives
+ * the rectangle's rect->w x rect->h bytes.  The rectangle must lie inside the upsampled plane. */
+int mjx_upsample_luma_host(const uint8_t *plane, uint32_t cw, uint32_t ch, uint8_t rh, uint8_t rv, const mjx_rect *rect, uint8_t *out);
 
 /* mjx_batch_create_resize with an orientation description (above); orient == NULL: mjx_batch_create_resize itself.  Descriptors
  * carry no file bytes: from_exif = 1 is MJX_ERR_INVALID_ARG for the call -- read the tag with mjx_exif_orientation and pass it in

@@ -65,6 +65,15 @@ class OutputDesc(ctypes.Structure):
     _fields_ = [("dtype", ctypes.c_uint8), ("planar", ctypes.c_uint8), ("bgr", ctypes.c_uint8),
                 ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3),
                 ("dst", ctypes.POINTER(Dst)), ("n_dst", ctypes.c_uint32)]
+    CHANNELS_OFFSET = 3                 # MJX_OUTPUT_CHANNELS_OFFSET: the channel count lives in the byte behind bgr
+
+    @property
+    def channels(self):
+        return ctypes.c_uint8.from_address(ctypes.addressof(self) + self.CHANNELS_OFFSET).value
+
+    @channels.setter
+    def channels(self, v):
+        ctypes.c_uint8.from_address(ctypes.addressof(self) + self.CHANNELS_OFFSET).value = int(v)
 
 
 class ResizeDesc(ctypes.Structure):
@@ -122,6 +131,7 @@ SYMBOLS = {
     "mjx_batch_create_out": (_int, [_vp, _P(ScanDesc), _sz, _P(Opts), _P(OutputDesc), _P(_vp), _P(_int)]),
     "mjx_output_layout": (_int, [_P(ScanDesc), _P(Opts), _P(OutputDesc), _sz, _P(Dst), _P(_sz)]),
     "mjx_batch_output_info": (_int, [_vp, _sz, _P(Dst)] + [_P(ctypes.c_uint8)] * 3),
+    "mjx_batch_output_channels": (_int, [_vp, _sz, _P(ctypes.c_uint8)]),
     "mjx_batch_copy_output": (_int, [_vp, _sz, _vp, _sz]),
     "mjx_batch_create_resize": (_int, [_vp, _P(ScanDesc), _sz, _P(Opts), _P(OutputDesc), _P(ResizeDesc), _P(_vp), _P(_int)]),
     "mjx_decode_batch_resize": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(OutputDesc), _P(ResizeDesc), _P(_int), _P(_vp)]),
@@ -129,6 +139,7 @@ SYMBOLS = {
     "mjx_resize_weights": (_int, [ctypes.c_uint32, ctypes.c_uint32, _int, ctypes.c_uint32, _P(ctypes.c_uint32), _P(ctypes.c_float), _sz, _P(_sz)]),
     "mjx_upsample_color_host": (_int, [_P(_P(ctypes.c_uint8)), _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(ctypes.c_uint8), _P(ctypes.c_uint8), ctypes.c_uint32,
                                        _P(Rect), _P(ctypes.c_uint8)]),
+    "mjx_upsample_luma_host": (_int, [_P(ctypes.c_uint8), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8, _P(Rect), _P(ctypes.c_uint8)]),
     "mjx_exif_orientation": (_int, [ctypes.c_char_p, _sz, _P(ctypes.c_uint8)]),
     "mjx_orient_compose": (ctypes.c_uint8, [ctypes.c_uint8, ctypes.c_uint8]),
     "mjx_batch_create_orient": (_int, [_vp, _P(ScanDesc), _sz, _P(Opts), _P(OutputDesc), _P(ResizeDesc), _P(OrientDesc), _P(_vp), _P(_int)]),
@@ -261,28 +272,40 @@ class Output:
     the OUTPUT channel; mean / std (of values in [0, 1], per output channel: (v / 255 - mean) / std) become scale = 1 / (255 std)
     and bias = -mean / std, computed in float64 and rounded once to float32.
     dst: None -- the library owns the output, dense -- or one (device pointer, width, height, row_pitch, plane_pitch) per input,
-    pitches in elements."""
+    pitches in elements.
+    channels: 3, or 1 for luminance -- H x W elements, one per pixel (H x W x 1 and 1 x H x W are the same memory; planar only says
+    which shape Batch.output gives; bgr has no meaning); mean / std / scale / bias are then one value (a scalar or one element)."""
 
-    def __init__(self, dtype="uint8", planar=False, bgr=False, mean=None, std=None, scale=None, bias=None, dst=None):
+    def __init__(self, dtype="uint8", planar=False, bgr=False, mean=None, std=None, scale=None, bias=None, dst=None, channels=3):
         names = {"uint8": DTYPE_U8, "u8": DTYPE_U8, "float16": DTYPE_F16, "f16": DTYPE_F16, "float32": DTYPE_F32, "f32": DTYPE_F32}
         self.dtype = names[dtype] if isinstance(dtype, str) else int(dtype)
         self.planar, self.bgr = bool(planar), bool(bgr)
+        self.channels = int(channels)
+        if not 0 <= self.channels <= 255:
+            raise MjxError(ERR_INVALID_ARG, "channels=%r" % (channels,))
         if (mean is not None or std is not None) and (scale is not None or bias is not None):
             raise MjxError(ERR_INVALID_ARG, "mean / std or scale / bias, not both")
-        three = lambda v, d: [float(d)] * 3 if v is None else ([float(v)] * 3 if np.isscalar(v) else [float(x) for x in v])
+        def three(v, d):
+            if v is None:
+                return [float(d)] * 3
+            if np.isscalar(v):
+                return [float(v)] * 3
+            v = [float(x) for x in v]
+            return v * 3 if self.channels == 1 and len(v) == 1 else v
         if mean is not None or std is not None:
             m, sd = np.array(three(mean, 0.0), np.float64), np.array(three(std, 1.0), np.float64)
             sc, bi = 1.0 / (255.0 * sd), -m / sd
         else:
             sc, bi = np.array(three(scale, 1.0), np.float64), np.array(three(bias, 0.0), np.float64)
         if len(sc) != 3 or len(bi) != 3:
-            raise MjxError(ERR_INVALID_ARG, "three values per channel")
+            raise MjxError(ERR_INVALID_ARG, "one value per channel")
         self.scale, self.bias = sc.astype(np.float32), bi.astype(np.float32)
         self.dst = None if dst is None else [tuple(int(v) for v in d) for d in dst]
 
     def desc(self):
         """-> the ctypes mjx_output (it keeps its dst array alive)."""
         d = OutputDesc(self.dtype, int(self.planar), int(self.bgr))
+        d.channels = self.channels
         for c in range(3):
             d.scale[c], d.bias[c] = float(self.scale[c]), float(self.bias[c])
         if self.dst is not None:
@@ -385,6 +408,18 @@ def upsample_color_host(planes, rh, rv, rect):
     r = Rect(x, y, w, h)
     out = np.zeros((max(h, 1), max(w, 1), 3), np.uint8)
     _check(lib().mjx_upsample_color_host(ptrs, cw, ch, a_rh, a_rv, n, ctypes.byref(r), out.ctypes.data_as(_P(ctypes.c_uint8))), "mjx_upsample_color_host")
+    return out[:h, :w]
+
+
+def upsample_luma_host(plane, rh, rv, rect):
+    """mjx_upsample_luma_host (host only; the routine k_upsample_luma runs): one uint8 plane [ch, cw], its upsampling ratios (1 or 2)
+    and a rectangle (x, y, w, h) of the upsampled plane -> ndarray [h, w] uint8, the "libjpeg" luminance of that rectangle."""
+    pl = np.ascontiguousarray(plane, np.uint8)
+    x, y, w, h = (int(v) for v in rect)
+    r = Rect(x, y, w, h)
+    out = np.zeros((max(h, 1), max(w, 1)), np.uint8)
+    _check(lib().mjx_upsample_luma_host(pl.ctypes.data_as(_P(ctypes.c_uint8)), pl.shape[1], pl.shape[0], int(rh), int(rv), ctypes.byref(r),
+                                        out.ctypes.data_as(_P(ctypes.c_uint8))), "mjx_upsample_luma_host")
     return out[:h, :w]
 
 
@@ -598,17 +633,23 @@ class Batch:
         return out
 
     def output_info(self, i):
-        """mjx_batch_output_info -> dict(dev, width, height, row_pitch, plane_pitch, dtype, planar, bgr); pitches in elements."""
+        """mjx_batch_output_info and mjx_batch_output_channels -> dict(dev, width, height, row_pitch, plane_pitch, dtype, planar, bgr,
+        channels); pitches in elements."""
         lay = Dst()
-        v = [ctypes.c_uint8() for _ in range(3)]
-        _check(lib().mjx_batch_output_info(self.h, i, ctypes.byref(lay), *[ctypes.byref(x) for x in v]), "mjx_batch_output_info")
+        v = [ctypes.c_uint8() for _ in range(4)]
+        _check(lib().mjx_batch_output_info(self.h, i, ctypes.byref(lay), *[ctypes.byref(x) for x in v[:3]]), "mjx_batch_output_info")
+        _check(lib().mjx_batch_output_channels(self.h, i, ctypes.byref(v[3])), "mjx_batch_output_channels")
         return dict(dev=lay.dev or 0, width=lay.width, height=lay.height, row_pitch=lay.row_pitch, plane_pitch=lay.plane_pitch,
-                    dtype=v[0].value, planar=bool(v[1].value), bgr=bool(v[2].value))
+                    dtype=v[0].value, planar=bool(v[1].value), bgr=bool(v[2].value), channels=v[3].value)
 
     def output(self, i):
-        """Picture i's library-owned output as an ndarray of its dtype: [3, H, W] (planar) or [H, W, 3]."""
+        """Picture i's library-owned output as an ndarray of its dtype: [3, H, W] (planar) or [H, W, 3]; a luminance picture [1, H, W] or
+        [H, W, 1] as the call's Output said (the memory is the same)."""
         inf = self.output_info(i)
-        shape = (3, inf["height"], inf["width"]) if inf["planar"] else (inf["height"], inf["width"], 3)
+        if inf["channels"] == 1:
+            shape = (1, inf["height"], inf["width"]) if inf["planar"] else (inf["height"], inf["width"], 1)
+        else:
+            shape = (3, inf["height"], inf["width"]) if inf["planar"] else (inf["height"], inf["width"], 3)
         out = np.empty(shape, _NP_DTYPES[inf["dtype"]])
         _check(lib().mjx_batch_copy_output(self.h, i, out.ctypes.data_as(_vp), out.nbytes), "mjx_batch_copy_output")
         return out
@@ -894,6 +935,8 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
     and planes may be padded, and the pictures must not overlap (the batch stride covers a picture's span).
     planar: True / False says which form the tensor is.  None takes it from the shape: N x 3 x H x W when the second dimension is
     3, N x H x W x 3 when only the last is; a shape that reads both ways (N x 3 x H x 3) needs the keyword.
+    Luminance (Output(channels=1)): N x 1 x H x W or N x H x W x 1 -- taken from the shape when neither of the two dimensions is 3;
+    N x 1 x H x 1 needs the keyword -- with padded rows; mean / std are then scalars or have one element.
     torch's current stream is synchronised before the call (the library writes on streams of its
     own) and the batch is complete when this returns.  -> the per-picture statuses.
     resize: True, or a Resize (its antialias and auto_scale; a size, if it names one, must be the tensor's) -- the pictures, of any
@@ -910,11 +953,29 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
     if out.device.type != "cuda" or out.device.index != ctx.device:
         raise MjxError(ERR_INVALID_ARG, "out lies on %s, not on the context's device %d" % (out.device, ctx.device))
     sn, s1, s2, s3 = out.stride()
+    channels = 3
     if planar is None:
         if out.shape[1] == 3 and out.shape[3] == 3:
             raise MjxError(ERR_INVALID_ARG, "out: %s reads as 3 x H x W and as H x W x 3: say planar=True or planar=False" % (tuple(out.shape),))
-        planar = out.shape[1] == 3
-    if planar and out.shape[1] == 3:
+        if out.shape[1] == 3 or out.shape[3] == 3:
+            planar = out.shape[1] == 3
+        elif out.shape[1] == 1 and out.shape[3] == 1:
+            raise MjxError(ERR_INVALID_ARG, "out: %s reads as 1 x H x W and as H x W x 1: say planar=True or planar=False" % (tuple(out.shape),))
+        else:
+            planar = out.shape[1] == 1
+    if planar and out.shape[1] == 1:                 # luminance, 1 x H x W: one element per pixel, rows may be padded
+        channels = 1
+        h, w = int(out.shape[2]), int(out.shape[3])
+        ok = s3 == 1 and s2 >= w
+        row_pitch, plane_pitch = s2, 0
+        span = (h - 1) * s2 + w
+    elif not planar and out.shape[3] == 1:           # luminance, H x W x 1: the same memory
+        channels = 1
+        h, w = int(out.shape[1]), int(out.shape[2])
+        ok = s2 == 1 and s1 >= w
+        row_pitch, plane_pitch = s1, 0
+        span = (h - 1) * s1 + w
+    elif planar and out.shape[1] == 3:
         h, w = int(out.shape[2]), int(out.shape[3])
         ok = s3 == 1 and s2 >= w and s1 >= h * s2
         row_pitch, plane_pitch = s2, s1
@@ -925,12 +986,12 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
         row_pitch, plane_pitch = s1, 0
         span = (h - 1) * s1 + 3 * w
     else:
-        raise MjxError(ERR_INVALID_ARG, "out: N x 3 x H x W or N x H x W x 3")
+        raise MjxError(ERR_INVALID_ARG, "out: N x 3 x H x W or N x H x W x 3 (luminance: N x 1 x H x W or N x H x W x 1)")
     if not ok or (n > 1 and sn < span):
         raise MjxError(ERR_INVALID_ARG, "out.stride() %s: neither 3 x H x W nor H x W x 3 with a dense innermost dimension, or the pictures overlap" % (tuple(out.stride()),))
     esz = out.element_size()
     dst = [(out.data_ptr() + i * sn * esz, w, h, row_pitch, plane_pitch) for i in range(n)]
-    fmt = Output(names[out.dtype], planar=bool(planar), bgr=bgr, mean=mean, std=std, dst=dst)
+    fmt = Output(names[out.dtype], planar=bool(planar), bgr=bgr, mean=mean, std=std, dst=dst, channels=channels)
     torch.cuda.current_stream(out.device).synchronize()
     if resize is not None and resize is not False:
         rs = Resize(w, h) if resize is True else Resize(w, h, resize.antialias, resize.auto_scale)

@@ -129,7 +129,7 @@ struct ImageInfo {
     // output formats (mjx_output): the picture has a description; where it lies -- out_dev, or 0: at rgb_off of the batch's pool --,
     // its pitches in elements and the span of bytes from its first element to its last (rgb_bytes: the bytes written)
     bool out_on = false, cropped = false;
-    uint32_t out_dtype = 0, out_planar = 0, out_bgr = 0;
+    uint32_t out_dtype = 0, out_planar = 0, out_bgr = 0, out_channels = 3;
     uint64_t out_dev = 0, out_row_pitch = 0, out_plane_pitch = 0, out_span = 0;
     // resize on the device: width x height above is the target; the intermediate is src_w x src_h (the rectangle at roi_x, roi_y of
     // the full_w x full_h picture at `scale`) and lies at DevImage::rgb_off; rgb_off here is the output's place in the pool
@@ -160,7 +160,8 @@ struct Chunk {
     uint32_t tiles = 0, tile_base = 0;    // tile offsets (+1 sentinel per image)
     uint32_t loop_participants = 0;     // > 0: the merge rounds run as one launch (k_huff_merge_loop) with this many workgroups
     uint32_t lut2_cap = 0;         // entries of the largest second table set (pair parts, the counting passes)
-    uint32_t max_wg = 0, merge_wgs = 0, max_tiles = 0, lut_cap = 0, max_tile_blocks = 0, mode_mask = 0, layout_mask = 0, max_segs = 0, bpm_mask = 0, max_restart_segs = 0;
+    uint32_t max_wg = 0, merge_wgs = 0, max_tiles = 0, lut_cap = 0, max_tile_blocks = 0, layout_mask = 0, max_segs = 0, bpm_mask = 0, max_restart_segs = 0;
+    uint64_t mode_mask = 0;        // bit m: the chunk holds a picture of stage-B mode m (kLumaMode + m lies above bit 31)
     uint64_t plane_words = 0;      // REF_COMPAT scratch of the chunk
     uint32_t max_pixel_wgs = 0;
     uint64_t lj_words = 0;         // libjpeg's pixels: the component planes of the chunk's pictures, in the same scratch (a call is one or the other)
@@ -168,6 +169,9 @@ struct Chunk {
     uint32_t max_dc_wgs = 0;       // scaled decode at 1/8: workgroups of k_dc_color for the chunk's largest picture
     uint32_t max_dc_roi_wgs = 0;   // ... and of k_dc_color_roi for its largest rectangle
     uint32_t max_dc_out_wgs = 0;   // ... and of k_dc_color_out for its largest picture with an output description
+    uint32_t max_dc_luma_wgs = 0;  // ... and of k_dc_color_luma for its largest luminance picture
+    uint32_t max_lj_luma_tiles = 0;                   // luminance pictures: workgroups of k_upsample_luma, k_orient_luma and k_resize_luma (0: none)
+    uint32_t max_or_luma_tiles = 0, max_rso_luma_tiles = 0;
     uint32_t max_or_tiles = 0, max_rso_tiles = 0;     // orientation on the device: workgroups of k_orient_out for the chunk's largest oriented picture, of k_resize_orient for its largest target (0: none)
     uint32_t max_rs_tiles = 0;     // resize on the device: workgroups of k_resize_out for the chunk's largest target (0: no picture is resized)
     uint32_t max_b_tiles = 0;      // tiles the workgroups of stage B walk in the chunk's largest picture: all its tiles, or those of its
@@ -517,12 +521,22 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
         d.out_row_pitch = p.out_row_pitch; d.out_plane_pitch = p.out_plane_pitch;
         d.out_dtype = p.out_dtype; d.out_planar = p.out_planar; d.out_bgr = p.out_bgr;
         for (uint32_t c = 0; c < 3; c++) { d.out_scale[c] = p.out_scale[c]; d.out_bias[c] = p.out_bias[c]; }
+        // luminance: stage B's forms for component 0 alone, whatever follows -- a resized or oriented picture's intermediate is the packed
+        // one-channel picture, which these forms write as well (luma_fmt), and the one-channel passes take it from there (or_on 3, 4:
+        // the three-channel passes pass over the picture)
+        if (p.out_channels == 1) {
+            d.out_ch = 1;
+            d.mode = d.mode % kRoiMode + kLumaMode;
+            d.rs_on = 0;
+            d.or_on = !p.rs_on ? 0u : p.or_copy ? 3u : 4u;
+        }
     }
     // libjpeg's pixels: one plane form for every sampling layout (4:2:0 takes the generic tile), whatever the picture leaves as --
     // k_upsample_color writes the packed picture (also a resize's or an orientation's intermediate) or the output format
     if (p.lj) {
         d.mode = kPlaneMode;
-        d.lj_on = 1;
+        d.lj_on = p.out_on && p.out_channels == 1 ? 0u : 1u;       // (a luminance picture is k_upsample_luma's: component 0's plane alone)
+        d.lj_luma = d.lj_on ? 0u : 1u;
         d.lj_out = p.out_on && !p.rs_on ? 1u : 0u;
         uint64_t off = 0;
         for (uint32_t c = 0; c < p.ncomp; c++) {
@@ -632,12 +646,15 @@ void plan_chunks(mjx_batch *b)
                 if (d.emit) c.has_emit = true; else if (d.role != 2) c.has_spec = true;
                 c.lut_cap = std::max<uint32_t>(c.lut_cap, d.lut_n);
                 c.lut2_cap = std::max<uint32_t>(c.lut2_cap, d.lut2_n);
-                c.mode_mask |= 1u << d.mode;
+                c.mode_mask |= uint64_t(1) << d.mode;
                 if (d.role != 1) c.layout_mask |= d.planar ? 4u : d.ent_rows ? 2u : 1u;
                 c.bpm_mask |= 1u << d.bpm;
                 if (d.nseg > 1) c.max_restart_segs = std::max(c.max_restart_segs, d.nseg);
                 if (d.mode == 5) c.max_dc_wgs = std::max<uint32_t>(c.max_dc_wgs, uint32_t((uint64_t(d.out_w) * d.out_h + 255) / 256));
                 if (d.mode == 5 + kOutMode) c.max_dc_out_wgs = std::max<uint32_t>(c.max_dc_out_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
+                if (d.mode == 5 + kLumaMode) c.max_dc_luma_wgs = std::max<uint32_t>(c.max_dc_luma_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
+                if (d.or_on == 3 && d.role != 1) c.max_or_luma_tiles = std::max<uint32_t>(c.max_or_luma_tiles, orient_tiles(d.rs_w, d.rs_h));
+                if (d.or_on == 4 && d.role != 1) c.max_rso_luma_tiles = std::max<uint32_t>(c.max_rso_luma_tiles, resize_tiles(d.rs_w, d.rs_h));
                 if (d.rs_on && d.role != 1) c.max_rs_tiles = std::max<uint32_t>(c.max_rs_tiles, resize_tiles(d.rs_w, d.rs_h));
                 if (d.or_on == 1 && d.role != 1) c.max_or_tiles = std::max<uint32_t>(c.max_or_tiles, orient_tiles(d.rs_w, d.rs_h));
                 if (d.or_on == 2 && d.role != 1) c.max_rso_tiles = std::max<uint32_t>(c.max_rso_tiles, resize_tiles(d.rs_w, d.rs_h));
@@ -647,10 +664,11 @@ void plan_chunks(mjx_batch *b)
                     c.plane_words += uint64_t(d.width) * d.height * d.ncomp;
                     c.max_pixel_wgs = std::max<uint32_t>(c.max_pixel_wgs, uint32_t((uint64_t(d.width) * d.height + 255) / 256));
                 }
-                if (d.lj_on && d.role != 1) {        // (the planes span the MCU grid: whole 64-byte block rows, so every plane starts on a multiple of 8)
+                if ((d.lj_on || d.lj_luma) && d.role != 1) {        // (the planes span the MCU grid: whole 64-byte block rows, so every plane starts on a multiple of 8)
                     d.plane_off = c.lj_words;
                     c.lj_words += (d.lj_off[d.ncomp - 1] + uint64_t(d.lj_stride[d.ncomp - 1]) * d.mcuy * 8 * d.cv[d.ncomp - 1]) / 8;
-                    c.max_lj_tiles = std::max<uint32_t>(c.max_lj_tiles, lj_tiles(d.roi_x, d.roi_w, d.roi_h));
+                    if (d.lj_luma) c.max_lj_luma_tiles = std::max<uint32_t>(c.max_lj_luma_tiles, lj_tiles(d.roi_x, d.roi_w, d.roi_h));
+                    else c.max_lj_tiles = std::max<uint32_t>(c.max_lj_tiles, lj_tiles(d.roi_x, d.roi_w, d.roi_h));
                 }
                 c.max_segs = std::max<uint32_t>(c.max_segs, (d.nmcu + kDcSegMcus - 1) / kDcSegMcus);
             }
@@ -959,10 +977,16 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
         if (c.max_dc_wgs) launch_dc_color(sp, c.max_dc_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags);
         if (c.max_dc_roi_wgs) launch_dc_color(sp, c.max_dc_roi_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true);
         if (c.max_dc_out_wgs) launch_dc_color(sp, c.max_dc_out_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true, true);
+        if (c.max_dc_luma_wgs) launch_dc_color_luma(sp, c.max_dc_luma_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags);
         prof_end(b, sp);
         if (c.max_lj_tiles) {          // libjpeg's pixels: the chunk's component planes -> its pictures (or the intermediates of the passes below)
             prof_begin(b, MJX_K_RESIZE, sp);
             launch_upsample_color(sp, c.max_lj_tiles, nimg, imgs, reinterpret_cast<const uint8_t *>(SCR(d_planes)), b->d_rgb, b->d_img_flags);
+            prof_end(b, sp);
+        }
+        if (c.max_lj_luma_tiles) {     // ... luminance pictures: component 0's plane alone
+            prof_begin(b, MJX_K_RESIZE, sp);
+            launch_upsample_color(sp, c.max_lj_luma_tiles, nimg, imgs, reinterpret_cast<const uint8_t *>(SCR(d_planes)), b->d_rgb, b->d_img_flags, true);
             prof_end(b, sp);
         }
         if (c.max_rs_tiles) {          // resize on the device: the chunk's intermediates -> the target pictures, behind its stage B
@@ -978,6 +1002,16 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
         if (c.max_rso_tiles) {
             prof_begin(b, MJX_K_RESIZE, sp);
             launch_resize_orient(sp, c.max_rso_tiles, nimg, imgs, b->d_rgb, b->d_img_flags);
+            prof_end(b, sp);
+        }
+        if (c.max_or_luma_tiles) {     // the same passes for luminance pictures: one-byte intermediates, one element per pixel
+            prof_begin(b, MJX_K_RESIZE, sp);
+            launch_orient_out(sp, c.max_or_luma_tiles, nimg, imgs, b->d_rgb, b->d_img_flags, true);
+            prof_end(b, sp);
+        }
+        if (c.max_rso_luma_tiles) {
+            prof_begin(b, MJX_K_RESIZE, sp);
+            launch_resize_orient(sp, c.max_rso_luma_tiles, nimg, imgs, b->d_rgb, b->d_img_flags, true);
             prof_end(b, sp);
         }
         if (sp != st) {
@@ -1314,7 +1348,8 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
             // output formats: the pool region is sized by the format; a caller-owned destination takes none of the pool
             if (times > 1 && p.out_dev) return MJX_ERR_INVALID_ARG;          // (copies would share the destination)
             inf.out_on = true;
-            inf.out_dtype = p.out_dtype; inf.out_planar = p.out_planar; inf.out_bgr = p.out_bgr;
+            inf.out_dtype = p.out_dtype; inf.out_planar = p.out_planar; inf.out_bgr = p.out_bgr; inf.out_channels = p.out_channels;
+            if (p.out_channels == 1) inf.rgb_bytes /= 3;                     // (luminance: one element per pixel, the intermediate too)
             inf.out_dev = p.out_dev; inf.out_row_pitch = p.out_row_pitch; inf.out_plane_pitch = p.out_plane_pitch;
             inf.out_span = p.out_bytes;
             if (p.rs_on) {
@@ -1326,7 +1361,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 inf.width = p.rs_w; inf.height = p.rs_h;
                 inf.rgb_off = rgb_pool;
                 d.rs_off = rgb_pool;
-                inf.rgb_bytes = uint64_t(p.rs_w) * p.rs_h * 3;
+                inf.rgb_bytes = uint64_t(p.rs_w) * p.rs_h * p.out_channels;
             }
             inf.rgb_bytes *= p.out_dtype == MJX_DTYPE_U8 ? 1u : p.out_dtype == MJX_DTYPE_F16 ? 2u : 4u;      // (the bytes written)
             rgb_pool += p.out_dev ? 0 : align_up(inf.out_span, 256);
@@ -2050,6 +2085,33 @@ extern "C" int mjx_upsample_color_host(const uint8_t *const *planes, const uint3
     });
 }
 
+// Host-only: the luminance picture of MJX_PIXELS_LIBJPEG on the CPU -- the routine k_upsample_luma itself runs (lj_luma8).
+extern "C" int mjx_upsample_luma_host(const uint8_t *plane, uint32_t cw, uint32_t ch, uint8_t rh, uint8_t rv, const mjx_rect *rect, uint8_t *out)
+{
+    return guarded([&]() -> int {
+    if (!plane || !rect || !out || !rect->w || !rect->h || !cw || !ch || cw > kResizeMaxDim || ch > kResizeMaxDim) return MJX_ERR_INVALID_ARG;
+    if (rh < 1 || rh > 2 || rv < 1 || rv > 2) return MJX_ERR_INVALID_ARG;
+    if (rect->x > kResizeMaxDim || rect->y > kResizeMaxDim || rect->w > kResizeMaxDim || rect->h > kResizeMaxDim) return MJX_ERR_INVALID_ARG;
+    if ((rect->x + rect->w - 1) / rh >= cw || (rect->y + rect->h - 1) / rv >= ch) return MJX_ERR_INVALID_ARG;
+    const uint32_t stride = (cw + 7u) & ~7u;
+    std::vector<uint64_t> store(size_t(stride) / 8 * ch, 0xa5a5a5a5a5a5a5a5ull);
+    uint8_t *dst = reinterpret_cast<uint8_t *>(store.data());
+    for (uint32_t y = 0; y < ch; y++) std::memcpy(dst + size_t(y) * stride, plane + size_t(y) * cw, cw);
+    const LjPlane pl{dst, stride, cw, ch, rh, rv};
+    for (uint32_t y = rect->y; y < rect->y + rect->h; y++)
+        for (uint32_t X0 = rect->x & ~(kLjStrip - 1u); X0 < rect->x + rect->w; X0 += kLjStrip) {
+            uint32_t w[2];
+            lj_luma8(pl, X0, y, w);
+            for (uint32_t k = 0; k < kLjStrip; k++) {
+                const uint32_t x = X0 + k;
+                if (x < rect->x || x >= rect->x + rect->w) continue;
+                out[size_t(y - rect->y) * rect->w + (x - rect->x)] = uint8_t(w[k >> 2] >> ((k & 3u) * 8u));
+            }
+        }
+    return MJX_OK;
+    });
+}
+
 // Host-only: what an oriented decode of this picture as input i takes and gives -- the planner's own (plan_input_for): the size of
 // the picture that leaves, the rectangle of the stored picture the intermediate covers and the scale it is decoded at.
 extern "C" int mjx_orient_plan(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_resize *rs, uint8_t code, size_t i,
@@ -2105,17 +2167,17 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
         p.width = d.width; p.height = d.height; p.ncomp = d.ncomp; p.bpm = d.bpm; p.hmax = d.hmax; p.vmax = d.vmax;
         p.scale = d.scale ? d.scale : 1u; p.out_w = d.out_w; p.out_h = d.out_h;      // (the copies keep the source's scale)
         p.cropped = src->info[k].cropped;                                             // (... and its rectangle)
-        p.lj = src->himages[k].lj_on != 0;                                            // (... and its pixels)
+        p.lj = src->himages[k].lj_on != 0 || src->himages[k].lj_luma != 0;                                            // (... and its pixels)
         if (src->info[k].out_on) {                                                    // (... and its output format)
             const ImageInfo &fi = src->info[k];
             p.out_on = true;
-            p.out_dtype = fi.out_dtype; p.out_planar = fi.out_planar; p.out_bgr = fi.out_bgr;
+            p.out_dtype = fi.out_dtype; p.out_planar = fi.out_planar; p.out_bgr = fi.out_bgr; p.out_channels = fi.out_channels;
             p.out_dev = fi.out_dev; p.out_row_pitch = fi.out_row_pitch; p.out_plane_pitch = fi.out_plane_pitch;
             p.out_bytes = fi.out_span;
             for (uint32_t c = 0; c < 3; c++) { p.out_scale[c] = src->himages[k].out_scale[c]; p.out_bias[c] = src->himages[k].out_bias[c]; }
             p.rs_on = src->himages[k].rs_on != 0 || src->himages[k].or_on != 0;       // (... and its resize and orientation)
             p.orient = src->himages[k].or_on ? src->himages[k].orient : 1u;
-            p.or_copy = src->himages[k].or_on == 1;
+            p.or_copy = src->himages[k].or_on == 1 || src->himages[k].or_on == 3;
             p.rs_w = src->himages[k].rs_w; p.rs_h = src->himages[k].rs_h; p.rs_aa = src->himages[k].rs_aa;
         }
         p.roi_x = d.roi_x; p.roi_y = d.roi_y; p.roi_w = d.roi_w; p.roi_h = d.roi_h;
@@ -2469,10 +2531,20 @@ extern "C" int mjx_batch_output_info(const mjx_batch *b, size_t iu, mjx_dst *lay
     if (layout) {
         layout->dev = inf.out_on && inf.out_dev ? reinterpret_cast<void *>(uintptr_t(inf.out_dev)) : b->d_rgb + inf.rgb_off;
         layout->width = inf.width; layout->height = inf.height;
-        layout->row_pitch = inf.out_on ? inf.out_row_pitch : uint64_t(inf.width) * 3;
+        layout->row_pitch = inf.out_on ? inf.out_row_pitch : uint64_t(inf.width) * 3;       // (a luminance picture: out_on, its pitch = width when dense)
         layout->plane_pitch = inf.out_on ? inf.out_plane_pitch : 0;
     }
     return MJX_OK;
+}
+
+extern "C" int mjx_batch_output_channels(mjx_batch *b, size_t iu, uint8_t *channels)
+{
+    if (b && !b->parts.empty()) { mjx_batch *pb; size_t pi; return route(b, iu, pb, pi) ? mjx_batch_output_channels(pb, pi, channels) : MJX_ERR_INVALID_ARG; }
+    size_t i;
+    if (!visible_index(b, iu, i)) return MJX_ERR_INVALID_ARG;
+    const ImageInfo &inf = b->info[i];
+    if (channels) *channels = uint8_t(inf.out_channels);
+    return inf.status;
 }
 
 // Device -> host memory the library does not own, through a pinned block of the context, in pieces: a copy straight into the

@@ -3,7 +3,8 @@
 // --crop: only that rectangle of the -- scaled -- picture is decoded and written, mjx_opts.rois; --libjpeg-pixels: rounded samples,
 // fancy chroma upsampling and libjpeg's integer colour tables, mjx_opts.pixels = MJX_PIXELS_LIBJPEG)
 // Writes the same ASCII P3 file ("P3\n{w} {h}\n255\n" then "r g b\n" per pixel, main.rs:35-39), buffered; --p6 writes
-// binary PPM instead.  Exit code = MJX_* status.
+// binary PPM instead.  --luma: the luminance picture (MJX_OUTPUT_CHANNELS = 1) through the batch API, written as binary PGM (P5); chroma
+// is never transformed.  Exit code = MJX_* status.
 #include "jpeg.hpp"
 
 #include <cstdio>
@@ -11,17 +12,51 @@
 #include <cstring>
 #include <string>
 
+// --luma: mjx_decode keeps packed RGB, so the one file goes through mjx_decode_batch_out with a luminance description
+static int write_luma(const std::vector<uint8_t> &bytes, const mjx_opts &opts, const char *path)
+{
+    mjx_ctx *ctx = nullptr;
+    int rc = mjx_ctx_create(0, &ctx);
+    if (rc != MJX_OK) { std::fprintf(stderr, "decode failed: %s (%d)\n", mjx_strerror(rc), rc); return rc; }
+    mjx_output fmt{};
+    fmt.dtype = MJX_DTYPE_U8;
+    MJX_OUTPUT_CHANNELS(&fmt) = 1;
+    const uint8_t *ptr = bytes.data();
+    const size_t len = bytes.size();
+    int status = MJX_OK;
+    mjx_batch *b = nullptr;
+    rc = mjx_decode_batch_out(ctx, &ptr, &len, 1, &opts, 1, &fmt, &status, &b);
+    if (rc == MJX_OK) rc = status;
+    uint32_t w = 0, h = 0;
+    std::vector<uint8_t> pix;
+    if (rc == MJX_OK) rc = mjx_batch_image_info(b, 0, &w, &h, nullptr, nullptr);
+    if (rc == MJX_OK) {
+        pix.resize(size_t(w) * h);
+        rc = mjx_batch_copy_output(b, 0, pix.data(), pix.size());
+    }
+    if (b) mjx_batch_free(b);
+    mjx_ctx_destroy(ctx);
+    if (rc != MJX_OK) { std::fprintf(stderr, "decode failed: %s (%d)\n", mjx_strerror(rc), rc); return rc; }
+    std::FILE *o = std::fopen(path, "wb");
+    if (!o) { std::perror(path); return MJX_ERR_INVALID_ARG; }
+    std::fprintf(o, "P5\n%u %u\n255\n", w, h);
+    std::fwrite(pix.data(), 1, pix.size(), o);
+    std::fclose(o);
+    return MJX_OK;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s <input.jpeg> <output.ppm> [--p6] [--strict] [--ref-compat] [--scale N] [--crop X,Y,W,H] [--libjpeg-pixels]\n", argv[0]);   // main.rs:26-28 expect()
+        std::fprintf(stderr, "usage: %s <input.jpeg> <output.ppm> [--p6] [--strict] [--ref-compat] [--scale N] [--crop X,Y,W,H] [--libjpeg-pixels] [--luma]\n", argv[0]);   // main.rs:26-28 expect()
         return MJX_ERR_INVALID_ARG;
     }
-    bool p6 = false;
+    bool p6 = false, luma = false;
     mjx_opts opts{};
     mjx_rect crop{0, 0, 0, 0};
     for (int i = 3; i < argc; i++) {
         if (!std::strcmp(argv[i], "--p6")) p6 = true;
+        else if (!std::strcmp(argv[i], "--luma")) luma = true;
         else if (!std::strcmp(argv[i], "--strict")) opts.strict_ref = 1;
         else if (!std::strcmp(argv[i], "--ref-compat")) opts.layout = MJX_LAYOUT_REF_COMPAT;
         else if (!std::strcmp(argv[i], "--libjpeg-pixels")) opts.pixels = MJX_PIXELS_LIBJPEG;
@@ -45,6 +80,7 @@ int main(int argc, char **argv)
     size_t n;
     while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) bytes.insert(bytes.end(), buf, buf + n);
     std::fclose(f);
+    if (luma) return write_luma(bytes, opts, argv[2]);
     jpeg::JPEGImage image;
     const jpeg::JPEGImage::Result r = jpeg::JPEGImage::parse(bytes, image, &opts);   // main.rs:31
     if (!r.ok()) { std::fprintf(stderr, "decode failed: %s (%d)\n", r.message.c_str(), r.code); return r.code; }

@@ -129,10 +129,18 @@ struct DevImage {
     uint32_t lj_on, lj_out;
     uint32_t lj_stride[3];
     uint64_t lj_off[3];
+    // luminance output (MJX_OUTPUT_CHANNELS == 1; out_ch = 1, mode kLumaMode + m): the picture leaves as roi_w x roi_h elements, one per
+    // pixel, rows of out_row_pitch elements at out_dev or byte rgb_off of the pool, a float element as fmaf(float(L), out_scale[0],
+    // out_bias[0]).  Stage B transforms the luminance blocks only.  A resized or oriented luminance picture has rs_on = 0 and or_on = 3
+    // (k_orient_luma copies) or 4 (k_resize_luma resamples orient_c(S), c = 1 included): stage B then writes S as roi_w x roi_h BYTES at
+    // rgb_off, and the three-channel passes leave the picture alone.  With libjpeg's pixels lj_on stays 0 and lj_luma = 1: stage B's
+    // plane form as it is, k_upsample_luma reads component 0's plane.
+    uint32_t out_ch, lj_luma;
 };
 constexpr uint32_t kRoiMode = 8;
 constexpr uint32_t kOutMode = 16;      // + m (0, 1, 3, 4; 5: k_dc_color_out): the forms for pictures with an output description
 constexpr uint32_t kPlaneMode = 24;    // + 0: the form that writes component planes (libjpeg's pixels; 4:2:0 takes the generic form too)
+constexpr uint32_t kLumaMode = 32;     // + m (0, 1, 3, 4; 5: k_dc_color_luma): the forms for luminance pictures -- a bit each in a 64-bit mode mask
 
 // Region-of-interest decode: does tile t -- T consecutive MCUs in raster order, so it may wrap into the next MCU row -- hold an MCU
 // of the MCU rows r0 .. r1 and the MCU columns c0 .. c1?  Arithmetic on uniform values only: stage B decides per tile without a
@@ -315,6 +323,16 @@ MJX_UNROLL
 MJX_UNROLL
         for (uint32_t q = 0; q < 3; q++) w[(3 * k + q) >> 2] = lj_put_u8(c[q], (3 * k + q) & 3u, w[(3 * k + q) >> 2]);
     }
+}
+// Component p alone at the 8 pixels (X0 .. X0 + 7, Y), as 8 bytes in two little-endian words: a luminance picture (no colour step).
+// k_upsample_luma and the host (mjx_upsample_luma_host) run this routine.
+MJX_HD void lj_luma8(const LjPlane &p, uint32_t X0, uint32_t Y, uint32_t w[2])
+{
+    int32_t y[8];
+    lj_strip8(p, X0, Y, y);
+    w[0] = w[1] = 0;
+MJX_UNROLL
+    for (uint32_t k = 0; k < 8; k++) w[k >> 2] = lj_put_u8(float(y[k]), k & 3u, w[k >> 2]);
 }
 
 // ---- resize on the device (mjx_resize): the separable triangle filter, one axis -----------------------------------------------
@@ -704,10 +722,10 @@ void launch_dc_scan(hipStream_t st, uint32_t max_segs, uint32_t nimg, const DevI
                     bool fault = false /* test knob: a workgroup never publishes */);
 // (max_tiles: the chunk's largest count of tiles a picture's workgroups walk -- DevImage::roi_ntiles; mode_mask bits kRoiMode + m:
 // pictures with a rectangle, which take the forms k_idct_color<kRoiMode + m, ...>; bits kOutMode + m: pictures with an output
-// description, k_idct_color<kOutMode + m, ...>)
+// description, k_idct_color<kOutMode + m, ...>; bits kLumaMode + m: luminance pictures, k_idct_color<kLumaMode + m, ...>)
 void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t lds, const DevImage *images,
                        const uint32_t *entries, const uint32_t *tile_eoff, const int32_t *dcbuf, const float *qmult,
-                       uint8_t *rgb, uint32_t mode_mask, unsigned long long *planes, const uint32_t *img_flags,
+                       uint8_t *rgb, uint64_t mode_mask, unsigned long long *planes, const uint32_t *img_flags,
                        bool dense /* the chunk's linear streams are dense (many entries per tile): deeper prefetch in the 4:2:0 kernel */,
                        uint32_t layout_mask /* bit 0: pictures with a linear stream, bit 1: with a quad-interleaved one */);
 // multi-scan pictures: component streams (raster order) -> the picture's stream in MCU order, tile offsets, DC values
@@ -722,15 +740,19 @@ void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, con
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
                      const float *qmult, uint8_t *rgb, const uint32_t *img_flags, bool roi = false /* the form for pictures with a rectangle */,
                      bool out = false /* the form for pictures with an output description (mode 5 + kOutMode) */);
+// ... luminance pictures (mode 5 + kLumaMode): one lane per pixel of the rectangle, component 0's DC value alone
+void launch_dc_color_luma(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
+                          const float *qmult, uint8_t *rgb, const uint32_t *img_flags);
 // resize on the device: one workgroup per tile of the target (resize_tiles) and picture with DevImage::rs_on, behind stage B
 void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
 // orientation on the device, behind stage B like the resize: one workgroup per tile of D (orient_tiles) and picture with or_on == 1
 // (k_orient_out), or per tile of the target (resize_tiles) and picture with or_on == 2 (k_resize_orient)
-void launch_orient_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
-void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
+// luma: the one-channel forms for luminance pictures -- or_on == 3 (k_orient_luma), or_on == 4 (k_resize_luma, any code, 1 included)
+void launch_orient_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma = false);
+void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma = false);
 // libjpeg's pixels, behind stage B: one workgroup per tile of the rectangle (lj_tiles) and picture with DevImage::lj_on
 void launch_upsample_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
-                           const uint32_t *img_flags);
+                           const uint32_t *img_flags, bool luma = false /* k_upsample_luma: pictures with DevImage::lj_luma */);
 #endif
 
 }   // namespace mjx

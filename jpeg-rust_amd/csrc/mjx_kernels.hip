@@ -2711,6 +2711,77 @@ __device__ __forceinline__ void store4_out(const OutFmt &f, const Roi &r, uint32
     }
 }
 
+// ---- luminance output (MJX_OUTPUT_CHANNELS == 1; k_idct_color<kLumaMode + m, ...>; DevImage::out_ch) ----------------------------------
+// Four luminance samples -> four bytes: pack4's conversions (v_cvt_pk_u8_f32 under round-toward-zero, saturating) on the samples
+// themselves -- the byte pack4 writes into all three channels of a pixel whose chroma terms are zero (y + 0 is y).  One opaque asm
+// block, as pack4: no float arithmetic can move inside it, and the mode is nearest-even again when it ends.
+__device__ __forceinline__ uint32_t pack4_luma(float y0, float y1, float y2, float y3)
+{
+    uint32_t o;
+    asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\n\t"
+                 "s_nop 1\n\t"
+                 "v_cvt_pk_u8_f32 %0, %1, 0, 0\n\t"
+                 "v_cvt_pk_u8_f32 %0, %2, 1, %0\n\t"
+                 "v_cvt_pk_u8_f32 %0, %3, 2, %0\n\t"
+                 "v_cvt_pk_u8_f32 %0, %4, 3, %0\n\t"
+                 "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\n\t"
+                 "s_nop 1"
+                 : "=&v"(o)
+                 : "v"(y0), "v"(y1), "v"(y2), "v"(y3));
+    return o;
+}
+// Where a luminance picture's elements go: its output format, or -- a resized or oriented picture (or_on 3, 4) -- the intermediate,
+// roi_w x roi_h bytes at rgb_off of the pool.
+__device__ __forceinline__ OutFmt luma_fmt(const DevImage &im, uint8_t *rgb_pool)
+{
+    OutFmt f = out_fmt(im, rgb_pool);
+    if (im.or_on) {
+        f.base = rgb_pool + im.rgb_off;
+        f.row_pitch = im.roi_w;
+        f.dtype = 0u;
+    }
+    return f;
+}
+// store4_out's one-channel sibling: the strip's four bytes `w` (pixel k in byte k) at (px, py), cut at the rectangle's edges; element
+// (X, Y) lies at (Y - r.y) row_pitch + (X - r.x).  A whole strip whose address allows it leaves in one non-temporal store of 4 / 8 / 16
+// bytes, a cut or misaligned one as predicated elements.  Nothing is written outside r.h rows x r.w elements.
+__device__ __forceinline__ void store4_luma(const OutFmt &f, const Roi &r, uint32_t px, uint32_t py, uint32_t w, uint32_t npix)
+{
+    if (py < r.y || py - r.y >= r.h) return;
+    const uint32_t lo = max(px, r.x), hi = min(px + npix, r.x + r.w);
+    if (lo >= hi) return;
+    const uint32_t k0 = lo - px, k1 = hi - px;                      // the strip's pixels [k0, k1) are the rectangle's
+    const uint32_t u[4] = {w & 0xffu, (w >> 8) & 0xffu, (w >> 16) & 0xffu, w >> 24};
+    const uint64_t at = uint64_t(py - r.y) * f.row_pitch + (lo - r.x);
+    const bool whole = k0 == 0u && k1 == 4u;
+    const float sc = f.scale[0], bi = f.bias[0];
+    if (f.dtype == 0u) {
+        uint8_t *d = f.base + at;
+        if (whole && (uintptr_t(d) & 3u) == 0) {
+            __builtin_nontemporal_store(w, reinterpret_cast<uint32_t *>(d));
+            return;
+        }
+    } else if (f.dtype == 1u) {
+        uint16_t *d = reinterpret_cast<uint16_t *>(f.base) + at;
+        if (whole && (uintptr_t(d) & 3u) == 0) {
+            u32x2_a4 h;
+            h.x = half_bits(__builtin_fmaf(float(u[0]), sc, bi)) | (half_bits(__builtin_fmaf(float(u[1]), sc, bi)) << 16);
+            h.y = half_bits(__builtin_fmaf(float(u[2]), sc, bi)) | (half_bits(__builtin_fmaf(float(u[3]), sc, bi)) << 16);
+            __builtin_nontemporal_store(h, reinterpret_cast<u32x2_a4 *>(d));
+            return;
+        }
+    } else if (whole) {
+        f32x4_a4 q;
+        q.x = __builtin_fmaf(float(u[0]), sc, bi); q.y = __builtin_fmaf(float(u[1]), sc, bi);
+        q.z = __builtin_fmaf(float(u[2]), sc, bi); q.w = __builtin_fmaf(float(u[3]), sc, bi);
+        __builtin_nontemporal_store(q, reinterpret_cast<f32x4_a4 *>(reinterpret_cast<float *>(f.base) + at));
+        return;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++)
+        if (k >= k0 && k < k1) out_store1(f, at + (k - k0), u[k], sc, bi);
+}
+
 // ---- stage B pipeline pieces ---------------------------------------------------------------------
 // A workgroup walks kTilesPerWg consecutive tiles of one image.  While it transforms tile t it already holds the loads
 // of tile t+1 in flight (stream offsets, up to kPrefetch entries per lane, the lane's DC), so the HBM round trips of a
@@ -2852,20 +2923,20 @@ __device__ __forceinline__ uint32_t comp_of_block(uint32_t b, const uint8_t *s_c
     return s_comp[b];
 }
 
-template <int MODE, int N>
+template <int MODE, int N, bool LUMA = false>
 __device__ __forceinline__ void scatter_at(const uint32_t *ent, const uint32_t *b, uint32_t nblk, float *tile_f,
                                            const float *s_qm, const uint8_t *s_nat, const uint8_t *s_comp);
-template <int MODE, int N>
+template <int MODE, int N, bool LUMA = false>
 __device__ __forceinline__ void scatter_batch(const uint32_t *ent, uint32_t first_lo, uint32_t nblk, float *tile_f,
                                               const float *s_qm, const uint8_t *s_nat, const uint8_t *s_comp)
 {
     uint32_t b[N];
 #pragma unroll
     for (int k = 0; k < N; k++) b[k] = ((ent[k] >> 22) - first_lo) & 0xffu;
-    scatter_at<MODE, N>(ent, b, nblk, tile_f, s_qm, s_nat, s_comp);
+    scatter_at<MODE, N, LUMA>(ent, b, nblk, tile_f, s_qm, s_nat, s_comp);
 }
-// (b[k]: the block slot of entry k in the tile; anything >= nblk is dropped)
-template <int MODE, int N>
+// (b[k]: the block slot of entry k in the tile; anything >= nblk is dropped.  LUMA: so is an entry of a block that is not component 0's)
+template <int MODE, int N, bool LUMA>
 __device__ __forceinline__ void scatter_at(const uint32_t *ent, const uint32_t *b, uint32_t nblk, float *tile_f,
                                            const float *s_qm, const uint8_t *s_nat, const uint8_t *s_comp)
 {
@@ -2886,7 +2957,7 @@ __device__ __forceinline__ void scatter_at(const uint32_t *ent, const uint32_t *
     for (int k = 0; k < N; k++) {
         // pos == 0 marks a null entry (the write pass fills up its runs with them); the scaled forms (MODE 3, 4) drop what lies
         // outside the low corner of the block (kScaledDrop in s_nat)
-        const bool ok = b[k] < nblk && pos[k] != 0 && (MODE < 3 || nat[k] != kScaledDrop);
+        const bool ok = b[k] < nblk && pos[k] != 0 && (MODE < 3 || nat[k] != kScaledDrop) && (!LUMA || comp[k] == 0u);
         const uint32_t at = ok ? b[k] * uint32_t(kPixStride * 4) + nat[k] * 4u : dump;
 #if defined(MJX_EXP_NO_SCATTER_STORE)  // (measurement build, garbage out: the scatter phase without its LDS stores)
         asm volatile("" :: "v"(at), "v"(float(int32_t(int16_t(ent[k] & 0xffffu))) * qm[k]));
@@ -3039,14 +3110,14 @@ __device__ __forceinline__ uint32_t planar_block(uint32_t e, uint32_t how, uint3
     const uint32_t l = how >> 24, fm = jb >> l;                   // its MCU of the picture, counted from the piece's first
     return min(((how >> 8) & 0xffu) + ((how >> 16) & 0xffu) + fm * bpm + (jb - (fm << l)), 255u);
 }
-template <int MODE, int N>
+template <int MODE, int N, bool LUMA = false>
 __device__ __forceinline__ void scatter_planar(const uint32_t *ent, const PlanarTile &t, uint32_t bpm, uint32_t nblk, float *tile_f,
                                                const float *s_qm, const uint8_t *s_nat, const uint8_t *s_comp)
 {
     uint32_t bs[N];
 #pragma unroll
     for (int k = 0; k < N; k++) bs[k] = planar_block(ent[k], __builtin_amdgcn_readfirstlane(t.rnd[k].how), bpm);
-    scatter_at<MODE, N>(ent, bs, nblk, tile_f, s_qm, s_nat, s_comp);
+    scatter_at<MODE, N, LUMA>(ent, bs, nblk, tile_f, s_qm, s_nat, s_comp);
 }
 
 // One lane = one 8x8 block: 16 x ds_read_b128 of its row, 8 row + 8 column transforms in registers, back to the row.
@@ -3312,6 +3383,33 @@ __device__ __forceinline__ void pixels_420_out(uint32_t width, uint32_t height, 
     }
 }
 
+// Phase 3 for 4:2:0, luminance output (k_idct_color<kLumaMode + 1, ...>): pixels_420_out's lane -> strip mapping and row loop; a row is
+// one 16-byte read of the lane's four luminance samples, their four conversions and one store site.  The chroma rows of the tile are
+// never read (nor written: the scatter drops their entries and phase 2 passes over their lanes).
+__device__ __forceinline__ void pixels_420_luma(uint32_t width, uint32_t height, uint32_t mcux, const float *tile, uint32_t m0,
+                                                uint32_t nm, const Roi &roi, const OutFmt &of)
+{
+    const uint32_t tid = threadIdx.x;
+    const uint32_t q = tid % (kTile420 * 4), t = q >> 2, sx = q & 3;
+    if (t >= nm) return;
+    const uint32_t m = m0 + t;
+    const uint32_t mx = m % mcux, my = m / mcux;
+    const uint32_t px = mx * 16 + sx * 4;
+    if (px >= width) return;
+    const uint32_t npix = min(4u, width - px);
+    if (px + 4u <= roi.x || px >= roi.x + roi.w) return;
+    const float *ybase = tile + (t * 6 + (sx >> 1)) * kPixStride + (sx & 1) * 4;
+#pragma unroll 1
+    for (uint32_t i = 0; i < 8; i++) {
+        const uint32_t rp = tid / (kTile420 * 4) + 2 * (i >> 1);                 // row pair 0..7 inside the MCU, then its two rows
+        const uint32_t py = my * 16 + rp * 2 + (i & 1u);
+        if (py >= height) break;
+        if (py < roi.y || py >= roi.y + roi.h) continue;
+        const f32x4 y = *reinterpret_cast<const f32x4 *>(ybase + (rp >> 2) * 2 * kPixStride + ((rp * 2) & 7) * 8 + (i & 1u) * 8);
+        store4_luma(of, roi, px, py, pack4_luma(y.x, y.y, y.z, y.w), npix);
+    }
+}
+
 // Phase 3 for any sampling layout: 4-pixel strips; lane -> (MCU t, strip sx) is fixed, rows advance by 256/R per step.
 // INTERIOR: every MCU of the tile lies in one MCU row and fully inside the picture, rows are 4-byte aligned -- no bounds, plain 12-byte stores
 // ROI: the picture written is the rectangle `roi` of this one (as pixels_420)
@@ -3356,6 +3454,32 @@ __device__ __forceinline__ void pixels_generic_t(const GenShape &g, const float 
         else if (ROI) store4_roi(out_img, roi, px, my * rows + r, pack4(p), npix);
         else if (INTERIOR) store_rgb4(dst, pack4(p));
         else store4(dst, pack4(p), aligned, npix);
+    }
+}
+// ... luminance output (k_idct_color<kLumaMode + 0, ...>): pixels_generic_t's walk, component 0 alone (upsampled by box replication
+// where it is not the most finely sampled component, as load4 does for any component)
+__device__ __forceinline__ void pixels_generic_luma(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm, const Roi &roi, const OutFmt &of)
+{
+    const uint32_t tid = threadIdx.x, bpm = g.bpm;
+    const uint32_t lstrips = g.hmax == 2 ? 2u : 1u;
+    const uint32_t R = (1u << g.log2_tile) << lstrips;
+    const uint32_t q = tid & (R - 1);
+    const uint32_t t = q >> lstrips, sx = q & ((1u << lstrips) - 1);
+    const uint32_t rows = 8 * g.vmax, lR = g.log2_tile + lstrips, rstep = 256u >> lR;
+    if (t >= nm) return;
+    const uint32_t m = m0 + t;
+    const uint32_t my = m / g.mcux, mx = m - my * g.mcux;
+    const uint32_t px = mx * 8 * g.hmax + sx * 4;
+    if (px >= g.width) return;
+    const uint32_t npix = min(4u, g.width - px);
+    if (px + 4u <= roi.x || px >= roi.x + roi.w) return;
+    for (uint32_t r = tid >> lR; r < rows; r += rstep) {
+        const uint32_t py = my * rows + r;
+        if (py >= g.height) break;
+        if (py < roi.y || py >= roi.y + roi.h) continue;
+        float yv[4];
+        load4(tile, g, t * bpm, 0, sx * 4, r, yv);
+        store4_luma(of, roi, px, py, pack4_luma(yv[0], yv[1], yv[2], yv[3]), npix);
     }
 }
 __device__ __forceinline__ void pixels_generic_roi(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm,
@@ -3604,6 +3728,31 @@ __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *ti
     }
 }
 
+// ... luminance output (k_idct_color<kLumaMode + 3 / 4, ...>): pixels_scaled's walk, component 0 alone
+template <uint32_t N>
+__device__ __forceinline__ void pixels_scaled_luma(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm, const Roi &roi, const OutFmt &of)
+{
+    const uint32_t PW = N * g.hmax, PH = N * g.vmax, SW = PW < 4u ? PW : 4u;
+    const uint32_t lspr = PW / SW == 2u ? 1u : 0u, lph = 31u - __builtin_clz(PH);
+    const uint32_t items = nm << (lph + lspr);
+    for (uint32_t i = threadIdx.x; i < items; i += 256u) {
+        const uint32_t t = i >> (lph + lspr), r = (i >> lspr) & (PH - 1u), sx = i & ((1u << lspr) - 1u);
+        const uint32_t m = m0 + t, my = m / g.mcux, mx = m - my * g.mcux;
+        const uint32_t X = mx * PW + sx * SW, Y = my * PH + r;
+        if (X >= g.width || Y >= g.height) continue;
+        if (Y < roi.y || Y >= roi.y + roi.h || X + SW <= roi.x || X >= roi.x + roi.w) continue;
+        const uint32_t npix = min(SW, g.width - X);
+        const uint32_t ys = r >> g.ysh[0], bro = g.first[0] + (ys / N) * g.ch[0];
+        float s[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            const uint32_t xs = min(sx * SW + k, PW - 1u) >> g.xsh[0];
+            s[k] = tile[(t * g.bpm + bro + xs / N) * kPixStride + (ys % N) * N + xs % N];
+        }
+        store4_luma(of, roi, X, Y, pack4_luma(s[0], s[1], s[2], s[3]), npix);
+    }
+}
+
 // MODE 0: any sampling layout.  MODE 1: Y 2x2 + Cb 1x1 + Cr 1x1 (4:2:0, 6 blocks per MCU, tile = 32 MCUs).
 // MODE 2: any sampling layout, REF_COMPAT placement into the f32 plane scratch (k_ref_color finishes the image).
 // MODE 3, 4: any sampling layout, scaled decode at 1/2 and 1/4 (phases 0-2 on the low 4x4 / 2x2 corner, pixels_scaled).
@@ -3626,6 +3775,10 @@ __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *ti
 //        k_upsample_color makes the picture
 //   OUT  output formats (MODE_ = MODE + kOutMode, the mode of a picture with an output description): the ROI form -- a picture without a
 //        rectangle is its own whole rectangle --, phase 3 writing the picture's format (store4_out, DevImage::out_*)
+//   LUMA  luminance output (MODE_ = MODE + kLumaMode, MJX_OUTPUT_CHANNELS == 1): the OUT form with three differences -- an entry whose
+//        block is not component 0's goes to the padding word, as dropped positions do at reduced scale; the DC term and phase 2 run on
+//        luminance blocks only; phase 3 does no colour arithmetic and stores one element per pixel (store4_luma).  The tile keeps the
+//        colour forms' layout (a row per block of the MCU): the chroma rows are cleared with the rest and never touched again.
 template <int MODE_, int PF, int SRC>
 __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__ images,
                                                      const uint32_t *__restrict__ entries,
@@ -3634,10 +3787,11 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                                                      uint8_t *__restrict__ rgb, unsigned long long *__restrict__ planes,
                                                      const uint32_t *__restrict__ img_flags, uint32_t tiles_per_wg)
 {
-    constexpr bool PLANES = MODE_ >= int(kPlaneMode);         // libjpeg's pixels: the cropped form again, phase 3 storing component planes
-    constexpr bool OUT = !PLANES && MODE_ >= int(kOutMode);   // output formats: the cropped form, the picture its own whole rectangle without one
+    constexpr bool LUMA = MODE_ >= int(kLumaMode);            // luminance output: the cropped form, component 0 alone
+    constexpr bool PLANES = !LUMA && MODE_ >= int(kPlaneMode);// libjpeg's pixels: the cropped form again, phase 3 storing component planes
+    constexpr bool OUT = !LUMA && !PLANES && MODE_ >= int(kOutMode);   // output formats: the cropped form, the picture its own whole rectangle without one
     constexpr bool ROI = MODE_ >= int(kRoiMode);
-    constexpr int MODE = MODE_ - (PLANES ? int(kPlaneMode) : OUT ? int(kOutMode) : ROI ? int(kRoiMode) : 0);
+    constexpr int MODE = MODE_ - (LUMA ? int(kLumaMode) : PLANES ? int(kPlaneMode) : OUT ? int(kOutMode) : ROI ? int(kRoiMode) : 0);
     static_assert(!PLANES || MODE == 0, "the planes are written by the generic form");
     static_assert(!ROI || MODE != 2, "REF_COMPAT has no rectangles");
     // (its own symbol: dynamic LDS arrays of one name share their alignment, and the entropy kernels ask for 2 KiB)
@@ -3677,6 +3831,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     }
     OutFmt ofmt{};
     if constexpr (OUT) ofmt = out_fmt(im, rgb);
+    if constexpr (LUMA) ofmt = luma_fmt(im, rgb);
     constexpr bool SKIP = ROI && SRC != 2;
     auto wanted_from = [&](uint32_t t) {          // the first tile at or behind t that the rectangle wants (uniform)
         if constexpr (SKIP)
@@ -3832,9 +3987,9 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             if constexpr (PLANAR) {
                 // as many rounds as the tile has -- a uniform choice between a few batch sizes, as for the linear stream below
                 const PlanarTile &pt = s_ptile[tile % 3u];
-                if (__builtin_amdgcn_readfirstlane(pt.rnd[4].cnt) == 0) scatter_planar<MODE, 4>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
-                else if (__builtin_amdgcn_readfirstlane(pt.rnd[6].cnt) == 0) scatter_planar<MODE, 6>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
-                else scatter_planar<MODE, 8>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
+                if (__builtin_amdgcn_readfirstlane(pt.rnd[4].cnt) == 0) scatter_planar<MODE, 4, LUMA>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
+                else if (__builtin_amdgcn_readfirstlane(pt.rnd[6].cnt) == 0) scatter_planar<MODE, 6, LUMA>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
+                else scatter_planar<MODE, 8, LUMA>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
                 // what the tile has beyond the prefetched rounds (dense streams)
                 for (uint32_t j = pt.rest_seg, r0 = pt.rest_rnd; j < kPlanarSegs; j++, r0 = 0) {
                     const uint32_t rel = s_kind[j >= nk ? j - nk : j].ent_rel + pt.start[j], len = pt.len[j], how = pt.how[j];
@@ -3842,7 +3997,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                         uint32_t e1[1], b1[1];
                         e1[0] = i0 + tid < len ? psrc[rel + i0 + tid] : 0u;
                         b1[0] = planar_block(e1[0], how, bpm);
-                        scatter_at<MODE, 1>(e1, b1, nblk, tile_f, s_qm, s_nat, s_comp);
+                        scatter_at<MODE, 1, LUMA>(e1, b1, nblk, tile_f, s_qm, s_nat, s_comp);
                     }
                 }
             } else if constexpr (QUAD) {
@@ -3852,14 +4007,14 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                     if (cur.ncells > wave0 + LANES * r) {                                    // uniform over the wave
                         quad_mask(cur.ent[r], cur.k_lo[r], cur.k_hi[r]);
                         // (the labels of the group's entries + its subsequence's label offset = the blocks' indices in the picture, mod 256)
-                        scatter_batch<MODE, 8>(cur.ent[r], first_lo - cur.lab[r], nblk, tile_f, s_qm, s_nat, s_comp);
+                        scatter_batch<MODE, 8, LUMA>(cur.ent[r], first_lo - cur.lab[r], nblk, tile_f, s_qm, s_nat, s_comp);
                     }
                 }
                 for (uint32_t h0 = LANES * QR; h0 < cur.ncells; h0 += LANES) {
                     uint32_t more[8], k_lo, k_hi, lab;
                     quad_load(src, qv, tile - tile0, h0 + tid, more, k_lo, k_hi, lab);
                     quad_mask(more, k_lo, k_hi);
-                    scatter_batch<MODE, 8>(more, first_lo - lab, nblk, tile_f, s_qm, s_nat, s_comp);
+                    scatter_batch<MODE, 8, LUMA>(more, first_lo - lab, nblk, tile_f, s_qm, s_nat, s_comp);
                 }
             } else {
                 // The prefetched words the wave really has (a tile of the bench content holds ~1500 entries, 5.9 per lane; at quality
@@ -3868,10 +4023,10 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                 // fetched as 0: null entries.)
                 const uint32_t have = cur.e1 - cur.e0;
                 const uint32_t slots = have > wave0 ? (have - wave0 + LANES - 1) / LANES : 0u;      // uniform over the wave
-                if (slots <= 4) scatter_batch<MODE, 4>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
-                else if (slots <= 6) scatter_batch<MODE, 6>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
-                else if (slots <= 8 || PF == 8) scatter_batch<MODE, 8>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
-                else if (PF > 8) scatter_batch<MODE, PF>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                if (slots <= 4) scatter_batch<MODE, 4, LUMA>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                else if (slots <= 6) scatter_batch<MODE, 6, LUMA>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                else if (slots <= 8 || PF == 8) scatter_batch<MODE, 8, LUMA>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                else if (PF > 8) scatter_batch<MODE, PF, LUMA>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
                 for (uint32_t i0 = cur.e0 + LANES * PF; i0 < cur.e1; i0 += LANES * 4) {     // what a dense tile has beyond the prefetched words
                     uint32_t more[4];
 #pragma unroll
@@ -3879,14 +4034,14 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                         const uint32_t i = i0 + tid + LANES * k;
                         more[k] = i < cur.e1 ? src[i] : 0u;
                     }
-                    scatter_batch<MODE, 4>(more, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                    scatter_batch<MODE, 4, LUMA>(more, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
                 }
             }
             // DC; luminance blocks also take the + 128 of decoder.rs:318-330 here (a constant on the DC term of the
             // prescaled transform is the same constant on all 64 samples); REF_COMPAT adds it per pixel in k_ref_color,
             // where samples no block covers must come out as 0 + 128
             MJX_SB(1);
-            if (tid < nblk) tile_f[tid * kPixStride] = float(cur.dc) * my_dc_qm + my_dc_add;
+            if (tid < nblk && (!LUMA || my_comp == 0u)) tile_f[tid * kPixStride] = float(cur.dc) * my_dc_qm + my_dc_add;
         }
         if constexpr (PLANAR) {
             if (tile + 1 < tile1) tile_fetch_planar<LANES, PF>(psrc, s_ptile[(tile + 1) % 3u], dcbuf, pdc, (tile + 1) * T, pr1, pa1, nmcu, mcux, nxt);
@@ -3895,8 +4050,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
         __syncthreads();
         MJX_SB(3);
         if constexpr (SCALED) {
-            if (tid < nblk) idct_scaled_inplace<scaled_n<MODE>()>(tile_f + tid * kPixStride);
-        } else if (tid < nblk) idct_row_inplace(tile_f + tid * kPixStride);
+            if (tid < nblk && (!LUMA || my_comp == 0u)) idct_scaled_inplace<scaled_n<MODE>()>(tile_f + tid * kPixStride);
+        } else if (tid < nblk && (!LUMA || my_comp == 0u)) idct_row_inplace(tile_f + tid * kPixStride);
         MJX_SB(4);
         __syncthreads();
         MJX_SB(3);
@@ -3920,7 +4075,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             const bool interior = whole && aligned && (my1 + 1) * 16 <= height && (mcux * 16 <= width || mx0 + T < mcux);
             if constexpr (ROI) {
                 // (plain reads: a cropped tile's pixel phase does not read -- so does not clear -- the whole tile; `clean` stays false)
-                if constexpr (OUT) pixels_420_out(width, height, mcux, tile_f, m0, nm, roi, ofmt);
+                if constexpr (LUMA) pixels_420_luma(width, height, mcux, tile_f, m0, nm, roi, ofmt);
+                else if constexpr (OUT) pixels_420_out(width, height, mcux, tile_f, m0, nm, roi, ofmt);
                 else pixels_420<false, true, true>(width, height, mcux, tile_f, m0, nm, out_img, aligned, roi);
             } else {
                 if (interior) pixels_420<true, false>(width, height, mcux, tile_f, m0, nm, out_img, aligned);
@@ -3931,10 +4087,12 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
         } else if (MODE == 2) {
             place_ref(im, tile_f, tile * tile_blocks, nblk, planes);
         } else if constexpr (SCALED) {
-            if constexpr (OUT) pixels_scaled<scaled_n<MODE>(), true, true>(gshape, tile_f, m0, nm, nullptr, false, roi, &ofmt);
+            if constexpr (LUMA) pixels_scaled_luma<scaled_n<MODE>()>(gshape, tile_f, m0, nm, roi, ofmt);
+            else if constexpr (OUT) pixels_scaled<scaled_n<MODE>(), true, true>(gshape, tile_f, m0, nm, nullptr, false, roi, &ofmt);
             else pixels_scaled<scaled_n<MODE>(), ROI>(gshape, tile_f, m0, nm, out_img, aligned, roi);
         } else {
-            if constexpr (PLANES) planes_store(im, tile_f, m0, nblk, bpm, mcux, reinterpret_cast<uint8_t *>(planes + im.plane_off));
+            if constexpr (LUMA) pixels_generic_luma(gshape, tile_f, m0, nm, roi, ofmt);
+            else if constexpr (PLANES) planes_store(im, tile_f, m0, nblk, bpm, mcux, reinterpret_cast<uint8_t *>(planes + im.plane_off));
             else if constexpr (OUT) pixels_generic_out(gshape, tile_f, m0, nm, roi, ofmt);
             else if constexpr (ROI) pixels_generic_roi(gshape, tile_f, m0, nm, out_img, aligned, roi);
             else pixels_generic(gshape, tile_f, m0, nm, out_img, aligned);
@@ -4025,6 +4183,36 @@ extern "C" __global__ __launch_bounds__(256) void k_dc_color_out(const DevImage 
     dc_color_body<true, true>(images, dcbuf, qmult, rgb, img_flags);
 }
 
+// Luminance output at 1/8 (k_dc_color_luma, mode 5 + kLumaMode): one lane per pixel of the rectangle from component 0's DC value alone --
+// dc_color_body's sample and its store (pack_u8), one element through the formats' table.
+extern "C" __global__ __launch_bounds__(256) void k_dc_color_luma(const DevImage *__restrict__ images, const int32_t *__restrict__ dcbuf,
+                                                                   const float *__restrict__ qmult, uint8_t *__restrict__ rgb,
+                                                                   const uint32_t *__restrict__ img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    if (!im.valid || im.mode != 5u + kLumaMode || img_flags[im.status_idx]) return;
+    const uint32_t ow = im.roi_w, oh = im.roi_h;
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= uint64_t(ow) * oh) return;
+    const uint32_t row = uint32_t(i / ow), col = uint32_t(i - uint64_t(row) * ow);
+    const uint32_t X = col + im.roi_x, Y = row + im.roi_y;
+    const uint32_t hmax = im.hmax, vmax = im.vmax;
+    const uint32_t mx = X / hmax, my = Y / vmax, lx = X - mx * hmax, ly = Y - my * vmax;
+    const uint32_t bx = hmax > im.ch[0] ? lx >> 1 : lx, by = vmax > im.cv[0] ? ly >> 1 : ly;
+    const uint32_t k = im.cfirst[0] + by * im.ch[0] + bx;
+    int32_t dc = 0;
+    if (im.planar) {
+        PlanarDc d{};
+        planar_dc_slot(images, im, blockIdx.y, k, d);
+        if (mx * d.rx + d.r0x < d.lx && my * d.ry + d.r0y < d.ly) dc = dcbuf[d.base + (my * d.ky + mx * d.kx + d.k0)];
+    } else {
+        dc = dcbuf[im.coef_off + (uint64_t(my) * im.mcux + mx) * im.bpm + k];
+    }
+    const float s0 = float(dc) * qmult[im.qm_off] + 128.0f;
+    const OutFmt f = luma_fmt(im, rgb);
+    out_store1(f, uint64_t(row) * f.row_pitch + col, pack_u8(s0, 0, 0) & 0xffu, f.scale[0], f.bias[0]);
+}
+
 // ---- resize on the device (mjx_resize; DevImage::rs_*) -------------------------------------------------------------------------
 // Stage B has written the picture as a packed (cropped) one: roi_h x roi_w x 3 bytes at rgb_off, the intermediate.  A workgroup
 // owns a tile of kRsTileW x kRsTileH pixels of the rs_w x rs_h target, all three channels; lane (lx, ly) owns column lx of the
@@ -4053,24 +4241,26 @@ __device__ __forceinline__ void out_store1f(const OutFmt &f, uint64_t at, float 
 }
 // ORIENT (k_resize_orient): the filter runs on D = orient_c(I), I the intermediate -- w_in and h_in are D's axes and the horizontal
 // pass reaches D(j, row) through orient_map's base and strides; the identity form (k_resize_out) keeps its own addressing.
-template <bool ORIENT>
+// CH: the channels of the intermediate and of the target -- 3, or 1 for a luminance picture (always the ORIENT form: or_on == 4, any code)
+template <bool ORIENT, int CH = 3>
 __device__ __forceinline__ void resize_body(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
 {
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || (ORIENT ? im.or_on != 2u : !im.rs_on) || img_flags[im.status_idx]) return;
+    static_assert(CH == 3 || (CH == 1 && ORIENT), "the luminance form is the oriented one");
+    if (!im.valid || (CH == 1 ? im.or_on != 4u : ORIENT ? im.or_on != 2u : !im.rs_on) || img_flags[im.status_idx]) return;
     const bool swaps = ORIENT && orient_swaps(im.orient);
     const uint32_t W = im.rs_w, H = im.rs_h, w_in = swaps ? im.roi_h : im.roi_w, h_in = swaps ? im.roi_w : im.roi_h;
     int64_t o_base = 0, o_sx = 0, o_sy = 0;                // bytes
     if constexpr (ORIENT) {
         const OrientMap om = orient_map(im.orient, im.roi_w, im.roi_h);
-        o_base = om.base * 3; o_sx = om.sx * 3; o_sy = om.sy * 3;
+        o_base = om.base * CH; o_sx = om.sx * CH; o_sy = om.sy * CH;
     }
     const uint32_t tiles_x = (W + kRsTileW - 1) / kRsTileW, tiles_y = (H + kRsTileH - 1) / kRsTileH;
     if (blockIdx.x >= tiles_x * tiles_y) return;
     const uint32_t tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
     const bool aa = im.rs_aa != 0;
     const uint8_t *__restrict__ src = rgb + im.rgb_off;
-    __shared__ float s_h[kRsSlab][3][kRsTileW];
+    __shared__ float s_h[kRsSlab][CH][kRsTileW];
     const uint32_t lx = threadIdx.x & (kRsTileW - 1), ly = threadIdx.x / kRsTileW;       // (ly: the wave)
     const uint32_t X = tile_x * kRsTileW + lx, Y0 = tile_y * kRsTileH;
     // (a lane past the right or bottom edge works on the last column / row -- the barriers stay uniform -- and stores nothing)
@@ -4078,7 +4268,7 @@ __device__ __forceinline__ void resize_body(const DevImage *__restrict__ images,
     const uint32_t Y1 = (Y0 + kRsTileH < H ? Y0 + kRsTileH : H) - 1u;
     const uint32_t row_lo = resize_window(h_in, H, aa, Y0).lo, row_hi = resize_window(h_in, H, aa, Y1).hi;
     int32_t ty[kRsRows];            // numerator offset t of the lane's output row k at the source row the loop stands at
-    float sy[kRsRows], acc[kRsRows][3];
+    float sy[kRsRows], acc[kRsRows][CH];
     int32_t ystep = 0, yfull = 0;
 #pragma unroll
     for (uint32_t k = 0; k < kRsRows; k++) {
@@ -4087,12 +4277,16 @@ __device__ __forceinline__ void resize_body(const DevImage *__restrict__ images,
         ty[k] = a.t_lo - int32_t(a.lo - row_lo) * a.step;
         sy[k] = a.sum;
         ystep = a.step; yfull = a.full;
-        acc[k][0] = acc[k][1] = acc[k][2] = 0.0f;
+#pragma unroll
+        for (int c = 0; c < CH; c++) acc[k][c] = 0.0f;
     }
     for (uint32_t r0 = row_lo; r0 < row_hi; r0 += kRsSlab) {
-        float h[kRsRows][3];
+        float h[kRsRows][CH];
 #pragma unroll
-        for (uint32_t k = 0; k < kRsRows; k++) h[k][0] = h[k][1] = h[k][2] = 0.0f;
+        for (uint32_t k = 0; k < kRsRows; k++) {
+#pragma unroll
+            for (int c = 0; c < CH; c++) h[k][c] = 0.0f;
+        }
         int32_t t = ax.t_lo;
         for (uint32_t j = ax.lo; j < ax.hi; j++, t += ax.step) {
             const int32_t m = t < 0 ? -t : t;
@@ -4101,30 +4295,30 @@ __device__ __forceinline__ void resize_body(const DevImage *__restrict__ images,
             for (uint32_t k = 0; k < kRsRows; k++) {
                 const uint32_t row = r0 + ly + 4u * k;
                 if (row < row_hi) {
-                    const uint8_t *p = ORIENT ? src + (o_base + int64_t(row) * o_sy + int64_t(j) * o_sx) : src + (uint64_t(row) * w_in + j) * 3u;
-                    h[k][0] = __builtin_fmaf(wn, float(p[0]), h[k][0]);
-                    h[k][1] = __builtin_fmaf(wn, float(p[1]), h[k][1]);
-                    h[k][2] = __builtin_fmaf(wn, float(p[2]), h[k][2]);
+                    const uint8_t *p = ORIENT ? src + (o_base + int64_t(row) * o_sy + int64_t(j) * o_sx) : src + (uint64_t(row) * w_in + j) * uint32_t(CH);
+#pragma unroll
+                    for (int c = 0; c < CH; c++) h[k][c] = __builtin_fmaf(wn, float(p[c]), h[k][c]);
                 }
             }
         }
 #pragma unroll
         for (uint32_t k = 0; k < kRsRows; k++) {
 #pragma unroll
-            for (uint32_t c = 0; c < 3; c++) s_h[ly + 4u * k][c][lx] = h[k][c];
+            for (uint32_t c = 0; c < uint32_t(CH); c++) s_h[ly + 4u * k][c][lx] = h[k][c];
         }
         __syncthreads();
         const uint32_t nrows = row_hi - r0 < kRsSlab ? row_hi - r0 : kRsSlab;
         for (uint32_t rr = 0; rr < nrows; rr++) {
-            const float v0 = s_h[rr][0][lx], v1 = s_h[rr][1][lx], v2 = s_h[rr][2][lx];
+            float v[CH];
+#pragma unroll
+            for (int c = 0; c < CH; c++) v[c] = s_h[rr][c][lx];
 #pragma unroll
             for (uint32_t k = 0; k < kRsRows; k++) {
                 const int32_t m = ty[k] < 0 ? -ty[k] : ty[k];
                 const float wn = m < yfull ? float(yfull - m) : 0.0f;
                 ty[k] += ystep;
-                acc[k][0] = __builtin_fmaf(wn, v0, acc[k][0]);
-                acc[k][1] = __builtin_fmaf(wn, v1, acc[k][1]);
-                acc[k][2] = __builtin_fmaf(wn, v2, acc[k][2]);
+#pragma unroll
+                for (int c = 0; c < CH; c++) acc[k][c] = __builtin_fmaf(wn, v[c], acc[k][c]);
             }
         }
         __syncthreads();
@@ -4138,9 +4332,13 @@ __device__ __forceinline__ void resize_body(const DevImage *__restrict__ images,
         if (Y >= H) continue;
         const float norm = ax.sum * sy[k];
         const uint64_t row = uint64_t(Y) * f.row_pitch;
+        if constexpr (CH == 1) {
+            out_store1f(f, row + X, acc[k][0] / norm, f.scale[0], f.bias[0]);
+            continue;
+        }
 #pragma unroll
-        for (uint32_t oc = 0; oc < 3; oc++) {
-            const float a = f.bgr ? acc[k][2u - oc] : acc[k][oc];
+        for (uint32_t oc = 0; oc < uint32_t(CH); oc++) {
+            const float a = f.bgr ? acc[k][uint32_t(CH) - 1u - oc] : acc[k][oc];
             const uint64_t at = f.planar ? row + oc * f.plane_pitch + X : row + uint64_t(X) * 3u + oc;
             out_store1f(f, at, a / norm, f.scale[oc], f.bias[oc]);
         }
@@ -4155,6 +4353,12 @@ extern "C" __global__ __launch_bounds__(256) void k_resize_orient(const DevImage
                                                                    const uint32_t *__restrict__ img_flags)
 {
     resize_body<true>(images, rgb, img_flags);
+}
+// ... of a luminance picture (or_on == 4): the intermediate is roi_w x roi_h bytes, the target one element per pixel
+extern "C" __global__ __launch_bounds__(256) void k_resize_luma(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,
+                                                                 const uint32_t *__restrict__ img_flags)
+{
+    resize_body<true, 1>(images, rgb, img_flags);
 }
 
 // ---- orientation on the device (mjx_orient; DevImage::or_on == 1): an oriented picture that is not resized --------------------
@@ -4171,11 +4375,14 @@ extern "C" __global__ __launch_bounds__(256) void k_resize_orient(const DevImage
 // form serves all eight codes.
 constexpr uint32_t kOrientRowBytes = kOrientTile * 3u + 4u;
 static_assert((kOrientRowBytes / 4u) % 2u == 1u, "k_orient_out: an odd number of words per LDS row");
-extern "C" __global__ __launch_bounds__(256) void k_orient_out(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,
-                                                                const uint32_t *__restrict__ img_flags)
+// CH: 3, or 1 for a luminance picture (or_on == 3; rows of 17 words, odd as well)
+template <int CH>
+__device__ __forceinline__ void orient_body(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
 {
+    constexpr uint32_t kRowBytes = kOrientTile * uint32_t(CH) + 4u;
+    static_assert((kRowBytes / 4u) % 2u == 1u, "an odd number of words per LDS row");
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || im.or_on != 1u || img_flags[im.status_idx]) return;
+    if (!im.valid || im.or_on != (CH == 1 ? 3u : 1u) || img_flags[im.status_idx]) return;
     const uint32_t code = im.orient, w = im.roi_w, h = im.roi_h;
     const bool swaps = orient_swaps(code), fu = orient_flips_u(code), fv = orient_flips_v(code);
     const uint32_t W = swaps ? h : w, H = swaps ? w : h;
@@ -4189,14 +4396,14 @@ extern "C" __global__ __launch_bounds__(256) void k_orient_out(const DevImage *_
     const uint32_t sw = swaps ? th : tw, sh = swaps ? tw : th;
     const uint32_t u0 = swaps ? Y0 : X0, v0 = swaps ? X0 : Y0;
     const uint32_t sx0 = fu ? w - u0 - sw : u0, sy0 = fv ? h - v0 - sh : v0;
-    __shared__ uint8_t s_t[kOrientTile][kOrientRowBytes];
+    __shared__ uint8_t s_t[kOrientTile][kRowBytes];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint8_t *__restrict__ src = rgb + im.rgb_off + (uint64_t(sy0) * w + sx0) * 3u;
-    const uint32_t row_bytes = sw * 3u;
+    const uint8_t *__restrict__ src = rgb + im.rgb_off + (uint64_t(sy0) * w + sx0) * uint32_t(CH);
+    const uint32_t row_bytes = sw * uint32_t(CH);
     for (uint32_t r = wave; r < sh; r += 4u) {
-        const uint8_t *__restrict__ p = src + uint64_t(r) * w * 3u;
+        const uint8_t *__restrict__ p = src + uint64_t(r) * w * uint32_t(CH);
 #pragma unroll
-        for (uint32_t k = 0; k < 3u; k++) {
+        for (uint32_t k = 0; k < uint32_t(CH); k++) {
             const uint32_t b = lane + 64u * k;
             if (b < row_bytes) s_t[r][b] = p[b];
         }
@@ -4209,9 +4416,13 @@ extern "C" __global__ __launch_bounds__(256) void k_orient_out(const DevImage *_
     for (uint32_t y = wave; y < th; y += 4u) {
         const uint32_t ur = swaps ? y : lane, vr = swaps ? lane : y;
         const uint32_t u = fu ? sw - 1u - ur : ur, v = fv ? sh - 1u - vr : vr;
-        const uint8_t *q = &s_t[v][u * 3u];
-        const uint32_t c0 = q[0], c1 = q[1], c2 = q[2];
         const uint64_t row = uint64_t(Y0 + y) * f.row_pitch;
+        if constexpr (CH == 1) {
+            out_store1(f, row + X, s_t[v][u], f.scale[0], f.bias[0]);
+            continue;
+        }
+        const uint8_t *q = &s_t[v][u * uint32_t(CH)];
+        const uint32_t c0 = q[0], c1 = q[CH > 1 ? 1 : 0], c2 = q[CH > 2 ? 2 : 0];
 #pragma unroll
         for (uint32_t oc = 0; oc < 3; oc++) {
             const uint32_t val = oc == 1u ? c1 : (oc == 0u) != (f.bgr != 0u) ? c0 : c2;
@@ -4219,6 +4430,16 @@ extern "C" __global__ __launch_bounds__(256) void k_orient_out(const DevImage *_
             out_store1(f, at, val, f.scale[oc], f.bias[oc]);
         }
     }
+}
+extern "C" __global__ __launch_bounds__(256) void k_orient_out(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,
+                                                                const uint32_t *__restrict__ img_flags)
+{
+    orient_body<3>(images, rgb, img_flags);
+}
+extern "C" __global__ __launch_bounds__(256) void k_orient_luma(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,
+                                                                 const uint32_t *__restrict__ img_flags)
+{
+    orient_body<1>(images, rgb, img_flags);
 }
 
 // ---- libjpeg's pixels (mjx_opts.pixels; DevImage::lj_on): component planes -> the picture ------------------------------------------
@@ -4269,6 +4490,37 @@ __global__ __launch_bounds__(256) void k_upsample_color(const DevImage *__restri
         const uint32_t npix = min(4u, width - x4);
         if (fmt) store4_out(of, roi, x4, py, v, npix);
         else store4_roi(out_img, roi, x4, py, v, npix);
+    }
+}
+
+// ... a luminance picture (DevImage::lj_luma): k_upsample_color's tiles, lanes and row loop on component 0's plane alone -- the plane itself
+// where Y is the most finely sampled component, lj_strip8's filters where it is not --, no colour step; the 8 bytes (lj_luma8) leave as
+// two strips through store4_luma: the output format, or the one-byte intermediate of a resize or an orientation (luma_fmt).
+__global__ __launch_bounds__(256) void k_upsample_luma(const DevImage *__restrict__ images, const uint8_t *__restrict__ planes,
+                                                        uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    if (!im.valid || !im.lj_luma || im.role == 1u || img_flags[im.status_idx]) return;
+    const Roi roi{im.roi_x, im.roi_y, im.roi_w, im.roi_h};
+    const uint32_t xb = roi.x & ~(kLjStrip - 1u), tiles_x = (roi.x - xb + roi.w + kLjTileW - 1u) / kLjTileW;
+    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    if (ty * kLjTileH >= roi.h) return;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t px = xb + tx * kLjTileW + (tid & 63u) * kLjStrip;
+    if (px >= roi.x + roi.w) return;
+    const uint32_t width = im.width, height = im.height, hmax = im.hmax, vmax = im.vmax;
+    const LjPlane pl{planes + im.plane_off * 8u + im.lj_off[0], im.lj_stride[0], (width * im.ch[0] + hmax - 1u) / hmax,
+                     (height * im.cv[0] + vmax - 1u) / vmax, hmax / im.ch[0], vmax / im.cv[0]};
+    const OutFmt of = luma_fmt(im, rgb);
+    uint32_t w[2] = {0u, 0u};
+#pragma unroll 1
+    for (uint32_t it = 0; it < 2u * (kLjTileH / 4u); it++) {
+        const uint32_t py = roi.y + ty * kLjTileH + (tid >> 6) + 4u * (it >> 1), half = it & 1u;
+        if (py >= roi.y + roi.h) break;
+        if (!half) lj_luma8(pl, px, py, w);
+        const uint32_t x4 = px + 4u * half;
+        if (x4 >= width) continue;
+        store4_luma(of, roi, x4, py, half ? w[1] : w[0], min(4u, width - x4));
     }
 }
 
@@ -4359,7 +4611,9 @@ int configure_kernels(size_t huff_lds, size_t idct_lds)
                              MJX_ROI_FORMS(0), MJX_ROI_FORMS(1), MJX_ROI_FORMS(3), MJX_ROI_FORMS(4),
                              MJX_ROI_FORMS(kOutMode - kRoiMode + 0), MJX_ROI_FORMS(kOutMode - kRoiMode + 1),        // (the output formats' forms, kOutMode + m)
                              MJX_ROI_FORMS(kOutMode - kRoiMode + 3), MJX_ROI_FORMS(kOutMode - kRoiMode + 4),
-                             MJX_ROI_FORMS(kPlaneMode - kRoiMode + 0)};                                              // (libjpeg's pixels: the plane form)
+                             MJX_ROI_FORMS(kPlaneMode - kRoiMode + 0),                                               // (libjpeg's pixels: the plane form)
+                             MJX_ROI_FORMS(kLumaMode - kRoiMode + 0), MJX_ROI_FORMS(kLumaMode - kRoiMode + 1),      // (luminance output, kLumaMode + m)
+                             MJX_ROI_FORMS(kLumaMode - kRoiMode + 3), MJX_ROI_FORMS(kLumaMode - kRoiMode + 4)};
 #undef MJX_ROI_FORMS
         for (const void *f : fns)
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(idct_lds));
@@ -4501,7 +4755,7 @@ void launch_dc_scan(hipStream_t st, uint32_t max_segs, uint32_t nimg, const DevI
 
 void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t lds, const DevImage *images,
                        const uint32_t *entries, const uint32_t *tile_eoff, const int32_t *dcbuf, const float *qmult,
-                       uint8_t *rgb, uint32_t mode_mask, unsigned long long *planes, const uint32_t *img_flags, bool dense,
+                       uint8_t *rgb, uint64_t mode_mask, unsigned long long *planes, const uint32_t *img_flags, bool dense,
                        uint32_t layout_mask)
 {
     // A workgroup walks up to kTilesPerWg consecutive tiles of its image (offsets fetched once, the next tile's loads in
@@ -4553,7 +4807,7 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
     // region-of-interest decode: pictures with a rectangle (mode + kRoiMode) take the forms that skip tiles and crop
     // ... and pictures with an output description (mode + kOutMode) the forms that write it
 #define MJX_IDCT_ROI(M_)                                                                                                                  \
-    if (mode_mask & (1u << (kRoiMode + M_))) {                                                                                            \
+    if (mode_mask & (uint64_t(1) << (kRoiMode + M_))) {                                                                                            \
         constexpr int M = (M_) % int(kRoiMode);                                                                                           \
         if (layout_mask & 1u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M_, kPrefetch, 0>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw); \
         if (layout_mask & 2u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M_, 8, 1>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw);         \
@@ -4568,6 +4822,11 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
     MJX_IDCT_ROI(kOutMode - kRoiMode + 3)
     MJX_IDCT_ROI(kOutMode - kRoiMode + 4)
     MJX_IDCT_ROI(kPlaneMode - kRoiMode + 0)
+    // ... and luminance pictures (mode + kLumaMode) the forms that transform and write component 0 alone
+    MJX_IDCT_ROI(kLumaMode - kRoiMode + 0)
+    MJX_IDCT_ROI(kLumaMode - kRoiMode + 1)
+    MJX_IDCT_ROI(kLumaMode - kRoiMode + 3)
+    MJX_IDCT_ROI(kLumaMode - kRoiMode + 4)
 #undef MJX_IDCT_ROI
 }
 
@@ -4601,20 +4860,23 @@ void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const 
 {
     hipLaunchKernelGGL(k_resize_out, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
 }
-void launch_orient_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags)
+void launch_orient_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma)
 {
-    hipLaunchKernelGGL(k_orient_out, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
+    if (luma) hipLaunchKernelGGL(k_orient_luma, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
+    else hipLaunchKernelGGL(k_orient_out, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
 }
-void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags)
+void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma)
 {
-    hipLaunchKernelGGL(k_resize_orient, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
+    if (luma) hipLaunchKernelGGL(k_resize_luma, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
+    else hipLaunchKernelGGL(k_resize_orient, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
 }
 
 void launch_upsample_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
-                           const uint32_t *img_flags)
+                           const uint32_t *img_flags, bool luma)
 {
     if (max_tiles == 0 || nimg == 0) return;
-    hipLaunchKernelGGL(k_upsample_color, dim3(max_tiles, nimg), dim3(256), 0, st, images, planes, rgb, img_flags);
+    if (luma) hipLaunchKernelGGL(k_upsample_luma, dim3(max_tiles, nimg), dim3(256), 0, st, images, planes, rgb, img_flags);
+    else hipLaunchKernelGGL(k_upsample_color, dim3(max_tiles, nimg), dim3(256), 0, st, images, planes, rgb, img_flags);
 }
 
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
@@ -4624,6 +4886,13 @@ void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, cons
     if (out) hipLaunchKernelGGL(k_dc_color_out, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
     else if (roi) hipLaunchKernelGGL(k_dc_color_roi, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
     else hipLaunchKernelGGL(k_dc_color, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
+}
+
+void launch_dc_color_luma(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
+                          const float *qmult, uint8_t *rgb, const uint32_t *img_flags)
+{
+    if (max_pixel_wgs == 0 || nimg == 0) return;
+    hipLaunchKernelGGL(k_dc_color_luma, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
 }
 
 }   // namespace mjx

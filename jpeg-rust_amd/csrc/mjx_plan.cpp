@@ -478,18 +478,22 @@ int plan_output(ImagePlan &p, const mjx_output *out, size_t i)
 {
     p.out_on = false;
     p.out_dev = 0;
+    p.out_channels = 3;
     p.out_bytes = uint64_t(p.roi_w) * p.roi_h * 3;
     if (!out || p.status != MJX_OK) return p.status;
     auto fail = [&]() { p.status = MJX_ERR_INVALID_ARG; return p.status; };
     if (out->dtype > MJX_DTYPE_F32 || p.layout == MJX_LAYOUT_REF_COMPAT) return fail();
+    const uint8_t channels = reinterpret_cast<const uint8_t *>(out)[MJX_OUTPUT_CHANNELS_OFFSET];       // (the byte behind bgr, mjx.h)
+    if (channels != 0 && channels != 1 && channels != 3) return fail();
+    const bool luma = channels == 1;                                  // luminance: H x W elements, one plane whatever `planar` says
     const uint64_t esz = out->dtype == MJX_DTYPE_U8 ? 1u : out->dtype == MJX_DTYPE_F16 ? 2u : 4u;
-    const bool planar = out->planar != 0;
-    for (int c = 0; c < 3; c++) {
+    const bool planar = out->planar != 0 && !luma;
+    for (int c = 0; c < (luma ? 1 : 3); c++) {
         if (out->dtype != MJX_DTYPE_U8 && !(std::isfinite(out->scale[c]) && std::isfinite(out->bias[c]))) return fail();
         p.out_scale[c] = out->dtype == MJX_DTYPE_U8 ? 1.f : out->scale[c];
         p.out_bias[c] = out->dtype == MJX_DTYPE_U8 ? 0.f : out->bias[c];
     }
-    const uint64_t w = p.rs_on ? p.rs_w : p.roi_w, h = p.rs_on ? p.rs_h : p.roi_h, row_min = planar ? w : 3 * w;      // (a resized picture: the target)
+    const uint64_t w = p.rs_on ? p.rs_w : p.roi_w, h = p.rs_on ? p.rs_h : p.roi_h, row_min = planar || luma ? w : 3 * w;      // (a resized picture: the target)
     p.out_row_pitch = row_min;
     p.out_plane_pitch = planar ? h * w : 0;
     if (out->dst) {
@@ -506,8 +510,9 @@ int plan_output(ImagePlan &p, const mjx_output *out, size_t i)
     p.out_bytes = ((planar ? 2 * p.out_plane_pitch : 0) + (h - 1) * p.out_row_pitch + row_min) * esz;
     p.out_on = true;
     p.out_dtype = out->dtype;
-    p.out_planar = planar ? 1u : 0u;
-    p.out_bgr = out->bgr ? 1u : 0u;
+    p.out_planar = out->planar ? 1u : 0u;             // (luminance: no planes -- kept for mjx_batch_output_info, nothing reads it)
+    p.out_bgr = out->bgr && !luma ? 1u : 0u;
+    p.out_channels = luma ? 1u : 3u;
     return p.status;
 }
 

@@ -52,6 +52,7 @@ struct ImagePlan {
     // first byte to the last element's last.  Without a description (out_on false): packed R,G,B bytes, out_bytes = roi_w roi_h 3.
     bool out_on = false;
     uint32_t out_dtype = 0, out_planar = 0, out_bgr = 0;
+    uint32_t out_channels = 3;                     // 1: luminance -- one element per pixel, rows of out_row_pitch, no planes (scale[0], bias[0])
     float out_scale[3] = {1.f, 1.f, 1.f}, out_bias[3] = {0.f, 0.f, 0.f};
     uint64_t out_dev = 0, out_row_pitch = 0, out_plane_pitch = 0, out_bytes = 0;
     // resize on the device (mjx_resize, plan_resize): the picture is planned as the packed (cropped) picture roi_w x roi_h at `scale`
