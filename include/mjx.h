@@ -29,10 +29,23 @@ extern "C" {
 /* ---- status codes ------------------------------------------------------------------------ */
 enum {
     MJX_OK = 0,
-    MJX_ERR_TRUNCATED = 1,          /* ran off the end of the file while parsing (ref: slice-index panic) */
+    MJX_ERR_TRUNCATED = 1,          /* ran off the end of the file while parsing (ref: slice-index panic); or, from the device:
+                                     * the scan ends early.  The device's rule (the band rule): the scan is the
+                                     * de-stuffed bytes behind the SOS header up to the end of the file, the end-of-image marker
+                                     * included, 0xAA behind them; a symbol is decoded when it STARTS at or before the scan's last
+                                     * bit rounded up to a multiple of 32 (with restart intervals: the interval's last bit, counted
+                                     * from the interval's first, and the bits behind it are the next interval's); the picture is
+                                     * truncated when the symbols so decoded do not complete every block it needs (every block of
+                                     * every interval), or when it has fewer RSTn markers than intervals less one.  A scan that
+                                     * ends a few bytes early can therefore come out MJX_OK with wrong last blocks; whatever lies
+                                     * behind the last block needed is never looked at.  Wins over MJX_ERR_BAD_HUFFMAN. */
     MJX_ERR_UNSUPPORTED_MARKER = 2, /* strict_ref: marker outside jpeg/mod.rs:166-179 (incl. APP12/APP14, :445-450) */
     MJX_ERR_DRI_UNSUPPORTED = 3,    /* jpeg/mod.rs:424-428 panics on DRI */
-    MJX_ERR_BAD_HUFFMAN = 4,        /* invalid DHT, or no code matched during decode (huffman.rs:156,162) */
+    MJX_ERR_BAD_HUFFMAN = 4,        /* invalid DHT, or no code matched during decode (huffman.rs:156,162): inside a block the
+                                     * picture needs, the next 16 bits begin with no code of the block's table (or the DC symbol
+                                     * is above 15).  The decode goes on -- such a pattern takes one bit and stands for a symbol of
+                                     * run 0, size 0 -- but the picture's coefficients and pixels are not handed out.  Patterns
+                                     * behind the last block needed do not count.  MJX_ERR_TRUNCATED wins where both hold. */
     MJX_ERR_REF_PANIC = 5,          /* other input on which the reference panics (asserts, bad DQT precision ...) */
     MJX_ERR_DEVICE = 6,             /* HIP error / no device / kernels missing */
     MJX_ERR_UNSUPPORTED_FORMAT = 7, /* non-baseline SOF, ncomp not in {1,3} (decoder.rs:328-330), sampling > 2 */

@@ -222,6 +222,11 @@ MJX_HD uint32_t lane_c(const LaneState &st, const HuffImage &img)
 }
 // byte offset of the first dword a lane fetches after it has left the bits below `bit` (bit rounded up to a dword)
 MJX_HD uint32_t wn_after(uint32_t bit) { return 4u * ((bit + 31u) >> 5) + 12u; }
+// The band rule (include/mjx.h): a lane looks at the end of its subsequence only when it takes a new dword, so the
+// symbols of a subsequence are those that start at or before its end bit rounded up to 32 -- for a scan's (a restart interval's) last
+// subsequence up to 31 bits of what follows.  A lane whose entry lies in that band decodes too: which symbols are decoded must not
+// depend on where the scan was cut into subsequences.
+MJX_HD uint32_t band_end(uint32_t end_bit) { return (end_bit + 31u) & ~31u; }
 
 MJX_HD uint32_t funnel(uint32_t hi, uint32_t lo, uint32_t sh)      // low 32 bits of {hi,lo} >> sh, sh in 0..31
 {
@@ -476,7 +481,7 @@ MJX_HD SubseqState decode_subseq(BitSrc bits, const LutEntry *lut, const HuffIma
                                  uint32_t end_bit, uint32_t blk, Sink &sink, CpStore &cps, uint32_t sub_start,
                                  SubseqState old_exit)
 {
-    if (entry.p > end_bit) return make_state(entry.p, entry.z, entry.c);           // nothing starts inside
+    if (entry.p > band_end(end_bit)) return make_state(entry.p, entry.z, entry.c); // nothing starts inside
     LaneState st;
     LaneEvents ev;
     lane_begin(st, bits, img, entry);

@@ -456,11 +456,19 @@ MJX_HD uint32_t block_word_index(uint32_t i, uint32_t rows) { return rows * 8u -
 struct alignas(16) EmitSub {
     uint32_t d0n, d0m;      // blocks completed / entries produced by the first decode (k_huff_emit)
     uint32_t kfix;          // 0: its entry state was right; k + 1: the true path meets it at checkpoint k; kEmitAll: nowhere inside
-    uint32_t bad;           // bit position (inside the subsequence) of the first symbol of the first decode that no code matches, or 0xffffffff
-    uint32_t bad_lbl;       // ... and the label of its block
+    uint32_t bad;           // the first symbol of the first decode that no code matches: bit position inside the subsequence [15:0] | label of its block [31:16], or 0xffffffff
+    uint32_t bad_tail2;     // ... the first one inside the scan's tail behind the checkpoint boundary that lies in the tail (emit_tail_cp), same form
     int32_t lbl;            // label of the first decode's block at the merge point minus the true path's (k_huff_prefix)
-    uint32_t pad_[2];
+    // The first one may lie in front of the merge point, on the part k_huff_prefix replaces; what it decides on then
+    // (position inside the subsequence [15:0] | label [31:16], or 0xffffffff):
+    uint32_t bad_last;      // the last such symbol in front of the scan's tail (emit_tail_start)
+    uint32_t bad_tail;      // the first one inside the tail
 };
+// The tail of a scan: the bits a valid file has behind its last block at the least -- up to 7 padding bits and the end-of-image marker,
+// which the scan keeps -- and what is read behind them.  Invalid codes of a valid file's true path lie there and nowhere else.
+// (the tail and what is read behind it is shorter than the distance of two checkpoints: at most one boundary lies in it, this one)
+MJX_HD uint32_t emit_tail_cp(uint32_t tail_start, uint32_t cp_bits) { return (tail_start + cp_bits - 1u) / cp_bits * cp_bits; }
+MJX_HD uint32_t emit_tail_start(uint32_t total_bits, uint32_t sub_start) { return total_bits > sub_start + 23u ? total_bits - 23u - sub_start : 0u; }
 constexpr uint32_t kEmitAll = 0xffffu;
 MJX_HD uint64_t stream_phys(uint32_t s, uint32_t j, uint32_t rows) { return (uint64_t(s / kStreamQuad) * rows + (j >> 3)) * (8u * kStreamQuad) + (s % kStreamQuad) * 8u + (j & 7u); }
 

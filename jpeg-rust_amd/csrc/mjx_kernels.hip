@@ -449,7 +449,7 @@ __device__ __forceinline__ SubseqState wave_decode(bool live, SubseqState entry,
     events_begin<CP>(ev, sub_start, end_bit, h.cp_bits);
     const uint32_t win_end = win_addr + 4u * kWinDwords;
     const uint32_t total_blocks = blk_limit;                               // (write pass: first block the lane must not write)
-    bool running = live && entry.p <= end_bit && !(WRITE && blk >= total_blocks);
+    bool running = live && entry.p <= band_end(end_bit) && !(WRITE && blk >= total_blocks);
     const bool started = running;
     uint32_t it = 1;
 #ifdef MJX_STAMP
@@ -610,7 +610,7 @@ __device__ __forceinline__ bool merge_slice(MergeItem &it, const DevImage &im, c
     met = 0;
     x = make_state(it.p, it.zc & 0xffu, (it.zc >> 8) & 0xffu, it.n, it.m);
     const uint32_t pl = it.p - sub_start;
-    if (it.p >= sub_start && pl <= end_bit) {                      // (else nothing starts inside s)
+    if (it.p >= sub_start && pl <= band_end(end_bit)) {            // (else nothing starts inside s)
         // it.k counts slices (intervals of kCpBits); a checkpoint lies at the end of slice it.k when that boundary is a multiple of the
         // picture's cp_bits (every slice for the pictures of the two-pass path, every fourth or so for those whose first decode emits)
         const uint32_t per = h.cp_bits / uint32_t(kCpBits);
@@ -1520,7 +1520,10 @@ struct EmitSink {
     LaneRing<kAcGroup, true> ac_ring;   // index = entry index in the lane's column
     BlkRing blk_ring;                   // index = head room + label of the block
     uint32_t blk_bits;                  // the current block's label, placed as in coef_entry, + 63 << 16 (see StreamSink)
-    uint32_t bad_pos, bad_lbl;
+    uint32_t bad_pos, bad_lbl;          // the first bit pattern no code matched: position, label of its block
+    uint32_t bad_last, bad_tail;        // ... the last one in front of the scan's tail and the first one inside it (EmitSub: position | label << 16)
+    uint32_t bad_tail2;                 // ... and the first one there behind the checkpoint boundary that lies in the tail
+    uint32_t tail_start, tail_cp;       // emit_tail_start, emit_tail_cp of the lane's subsequence
 #if defined(MJX_EXP_EMIT_NOBLK)        // (measurement build, garbage out: the emitting pass without its block words)
     __device__ __forceinline__ void dc(uint32_t, int v) { asm volatile("" :: "v"(v)); }
 #else
@@ -1528,7 +1531,15 @@ struct EmitSink {
 #endif
     __device__ __forceinline__ void ac(uint32_t, uint32_t r_scaled, int v) { ac_ring.push((uint32_t(v) & 0xffffu) | (blk_bits - r_scaled)); }
     __device__ __forceinline__ void block_done(uint32_t) { blk_bits += 1u << 22; }
-    __device__ __forceinline__ void bad_code(uint32_t b, uint32_t pos) { if (bad_pos == 0xffffffffu) { bad_pos = pos; bad_lbl = b; } }
+    __device__ __forceinline__ void bad_code(uint32_t b, uint32_t pos)
+    {
+        if (bad_pos == 0xffffffffu) { bad_pos = pos; bad_lbl = b; }
+        if (pos < tail_start) bad_last = (pos & 0xffffu) | (b << 16);
+        else {
+            if (bad_tail == 0xffffffffu) bad_tail = (pos & 0xffffu) | (b << 16);
+            if (pos > tail_cp && bad_tail2 == 0xffffffffu) bad_tail2 = (pos & 0xffffu) | (b << 16);
+        }
+    }
     __device__ __forceinline__ void tick() const {}
     __device__ __forceinline__ void flush_groups() { ac_ring.flush_groups(); blk_ring.flush_groups(); }
 #if defined(MJX_EXP_EMIT_NOBLK)
@@ -1586,7 +1597,9 @@ extern "C" __global__ __launch_bounds__(kHuffWg) void k_huff_emit(const DevImage
         sink.blk_ring.begin(rings + threadIdx.x * BlkRing::kRing, column, im.ent_rows, Hb + (e0.z ? 1u : 0u));
     }
     sink.blk_bits = StreamSink::block_bits(0);
-    sink.bad_pos = sink.bad_lbl = 0xffffffffu;
+    sink.bad_pos = sink.bad_lbl = sink.bad_last = sink.bad_tail = sink.bad_tail2 = 0xffffffffu;
+    sink.tail_start = emit_tail_start(h->total_bits, start);
+    sink.tail_cp = emit_tail_cp(sink.tail_start, h->cp_bits);
     GlobalCps cps{reinterpret_cast<unsigned char *>(g_cps), cps_byte_off(im.sub_off + sl), 0};
 #if defined(MJX_EXP_EMIT_NOCP)         // (measurement build, garbage out: the emitting pass without recording checkpoints)
     NoCheckpoints nocp2;
@@ -1607,7 +1620,7 @@ extern "C" __global__ __launch_bounds__(kHuffWg) void k_huff_emit(const DevImage
     x.p += start;
     g_exit[im.sub_off + s] = x;
     EmitSub es;
-    es.d0n = x.n; es.d0m = x.m; es.kfix = 0; es.bad = sink.bad_pos; es.bad_lbl = sink.bad_lbl; es.lbl = 0; es.pad_[0] = es.pad_[1] = 0;
+    es.d0n = x.n; es.d0m = x.m; es.kfix = 0; es.bad = sink.bad_pos == 0xffffffffu ? 0xffffffffu : (sink.bad_pos & 0xffffu) | (sink.bad_lbl << 16); es.bad_tail2 = sink.bad_tail2; es.lbl = 0; es.bad_last = sink.bad_last; es.bad_tail = sink.bad_tail;
     g_esub[im.sub_off + s] = es;
 }
 
@@ -1730,7 +1743,7 @@ extern "C" __global__ __launch_bounds__(kPrefixWg) void k_huff_prefix(const DevI
         if (k == 0) for (uint32_t j = off_e & ~7u; j < off_e; j++) *sink.at(j) = 0u;   // null entries in front of the run's first entry
         uint32_t n = n_start;
         uint32_t matched_word = 0;
-        if (p <= end_rel) {
+        if (p <= band_end(end_rel)) {
             const uint32_t end_wn = wn_after(end_rel), last_wn = min(wn_after(stop_rel), end_wn);
             uint32_t *my_win = s_win + tid * kMergeStride;
             const LaneBits bits{scan_pool + im.scan_off, s * 16u, im.scan_cols * 16u};
@@ -1786,7 +1799,29 @@ extern "C" __global__ __launch_bounds__(kPrefixWg) void k_huff_prefix(const DevI
     if (es.bad != 0xffffffffu && es.kfix != kEmitAll) {
         // an invalid bit pattern the first decode met: it counts if it lies on the part of that decode that stays (at or behind the merge point)
         const uint32_t pK = 8u * (wn_after(es.kfix * cpb) - 8u) - (recK & 31u);
-        if (es.bad >= pK && int64_t(B) + int64_t(es.bad_lbl) - lbl < int64_t(total_blocks)) atomicOr(status + im.status_idx, 1);
+        // The first one may lie in front of it, on the discarded part, and a later one behind it.  Positions and labels only grow along
+        // a decode.  The last one in front of the scan's tail says whether the body of the kept part has one, and its block is inside
+        // the picture in every file whose blocks end where the scan does.  If not -- bytes behind the last block, in front of the tail --
+        // the ones between are not known, and the picture goes to the two-pass kernels; a valid file has none outside the tail.  Inside
+        // the tail the first one decides (blocks read from the end-of-image marker's bits are still the picture's).
+        auto inside = [&](uint32_t w) { return int64_t(B) + int64_t(w >> 16) - lbl < int64_t(total_blocks); };
+        bool give_up = false;
+        if ((es.bad & 0xffffu) >= pK) {
+            if (inside(es.bad)) atomicOr(status + im.status_idx, 1);
+        } else if (!inside(es.bad)) {
+            // (the first one's block is already behind the picture's last: so is every later one's)
+        } else if (es.bad_last != 0xffffffffu && (es.bad_last & 0xffffu) >= pK) {
+            if (inside(es.bad_last)) atomicOr(status + im.status_idx, 1);
+            else give_up = true;
+        } else {
+            // (a merge point in the tail lies behind the one checkpoint boundary there, and so does every symbol from it on)
+            const uint32_t tw = pK > emit_tail_cp(emit_tail_start(h->total_bits, sub_start), cpb) ? es.bad_tail2 : es.bad_tail;
+            if (tw != 0xffffffffu && (tw & 0xffffu) >= pK && inside(tw)) atomicOr(status + im.status_idx, 1);
+        }
+        if (give_up) {
+            img_flags[im.status_idx] = 2u;
+            if (atomicOr(fallback, 256u) == 0u) atomicAdd(unconverged, 1u);      // (see k_huff_scan)
+        }
     }
 }
 
@@ -1823,7 +1858,7 @@ extern "C" __global__ __launch_bounds__(256) void k_block_gather(const DevImage 
             // the lane's entry was right: its run is what k_huff_emit wrote, its labels count from the first block of the subsequence
             // (the others' run words: k_huff_prefix)
             (entries + im.ent_off)[s] = run_word(H >> 3, (H + es.d0m + 7u) >> 3, B0 & 0xffu);
-            if (es.bad != 0xffffffffu && B0 + es.bad_lbl < total_blocks) atomicOr(status + im.status_idx, 1);
+            if (es.bad != 0xffffffffu && B0 + (es.bad >> 16) < total_blocks) atomicOr(status + im.status_idx, 1);
         }
     }
     __syncthreads();

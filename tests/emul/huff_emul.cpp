@@ -206,7 +206,7 @@ extern "C" int emul_decode_coefs_sub(const uint8_t *jpeg, size_t len, int layout
                 uint32_t met = 0, nrec = 0;
                 SubseqState x = make_state(e.p, e.z, e.c);
                 const long t0 = ns.ticks;
-                if (e.p <= end_of(s)) {
+                if (e.p <= s * img.sub_bits + band_end(end_of(s) - s * img.sub_bits)) {
                     LaneState st; LaneEvents ev;
                     lane_begin(st, bits, img2, e);
                     events_begin<2>(ev, s * img.sub_bits, end_of(s), img2.cp_bits);
@@ -289,7 +289,9 @@ extern "C" int emul_decode_coefs_sub(const uint8_t *jpeg, size_t len, int layout
     const size_t nb = img.total_blocks;
     *nblocks = nb;
     int bad = 0;
-    if (nb <= cap_blocks) {
+    const bool truncated = acc < nb;          // k_huff_scan: the picture is flagged and every later kernel skips it
+    if (truncated) bad = 3;
+    if (nb <= cap_blocks && !truncated) {
         const uint32_t tile_blocks = tile_mcus(plan.bpm, plan.hmax) * plan.bpm;
         const uint32_t ntiles = uint32_t((nb + tile_blocks - 1) / tile_blocks);
         std::vector<uint32_t> entries(size_t(eacc) + 1, 0xffffffffu), tile_eoff(ntiles + 1, 0xffffffffu);
@@ -357,7 +359,8 @@ extern "C" int emul_decode_coefs_sub(const uint8_t *jpeg, size_t len, int layout
         stats[4] = int(plan.bpm); stats[5] = int(plan.lut.size()); stats[6] = bad; stats[7] = 0;
     }
     mjx_free_scan(&d);
-    return nb <= cap_blocks ? (bad ? MJX_ERR_BAD_HUFFMAN : MJX_OK) : MJX_ERR_NOMEM;
+    if (nb > cap_blocks) return MJX_ERR_NOMEM;
+    return truncated ? MJX_ERR_TRUNCATED : bad ? MJX_ERR_BAD_HUFFMAN : MJX_OK;      // (as mjx_batch_wait: truncated wins)
 }
 
 // ---- single decode (round 5): the counting pass emits ------------------------------------------------------------------
@@ -381,6 +384,9 @@ struct EmitSink {                  // first decode and prefix pass: the column o
     uint32_t e_lo, e_hi;                      // bounds the entry indices must stay inside (a violation = fall back to the two-pass path)
     uint32_t bad_label; int *overflow;
     uint32_t bad_pos = 0;
+    uint32_t bad_last = 0xffffffffu, bad_tail = 0xffffffffu, nbad = 0;   // EmitSub::bad_last, bad_tail: position inside the subsequence | label << 16
+    uint32_t bad_tail2 = 0xffffffffu;                    // EmitSub::bad_tail2
+    uint32_t sub_start = 0, tail_start = 0, tail_cp = 0; // the subsequence's first bit; emit_tail_start, emit_tail_cp
     uint32_t lowest_bword = 0xffffffffu;      // lowest column index a block word went to (entries must stay below it)
     long ticks = 0;
     void dc(uint32_t b, int v)
@@ -396,13 +402,25 @@ struct EmitSink {                  // first decode and prefix pass: the column o
         col[stream_phys(s, eoff++, rows)] = coef_entry(v, 63u - (r_scaled >> kRShift), b + label_add);
     }
     void block_done(uint32_t) const {}
-    void bad_code(uint32_t b, uint32_t pos) { if (bad_label == 0xffffffffu) { bad_label = b; bad_pos = pos; } }
+    void bad_code(uint32_t b, uint32_t pos)
+    {
+        if (bad_label == 0xffffffffu) { bad_label = b; bad_pos = pos; }
+        nbad++;
+        if (pos - sub_start < tail_start) bad_last = ((pos - sub_start) & 0xffffu) | (b << 16);
+        else {
+            if (bad_tail == 0xffffffffu) bad_tail = ((pos - sub_start) & 0xffffu) | (b << 16);
+            if (pos - sub_start > tail_cp && bad_tail2 == 0xffffffffu) bad_tail2 = ((pos - sub_start) & 0xffffu) | (b << 16);
+        }
+    }
     void tick() { ticks++; }
 };
 }   // namespace
 
 extern "C" int emul_single_decode_cp(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, unsigned warm_bits,
                                      unsigned headroom_groups, unsigned cp_bits, int16_t *out, size_t cap_blocks, size_t *nblocks, int *stats /* [8] */);
+extern "C" int emul_single_decode_lanes(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, unsigned warm_bits,
+                                        unsigned headroom_groups, unsigned cp_bits, int16_t *out, size_t cap_blocks, size_t *nblocks, int *stats /* [8] */,
+                                        uint32_t *lanes /* [lanes_cap][4] */, size_t lanes_cap);
 extern "C" int emul_single_decode(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, unsigned warm_bits,
                                   unsigned headroom_groups, int16_t *out, size_t cap_blocks, size_t *nblocks, int *stats /* [8] */)
 {
@@ -411,6 +429,17 @@ extern "C" int emul_single_decode(const uint8_t *jpeg, size_t len, int layout, i
 // cp_bits: bits between the checkpoints the emitting decode records (0: kCpBits; a multiple of kCpBits)
 extern "C" int emul_single_decode_cp(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, unsigned warm_bits,
                                      unsigned headroom_groups, unsigned cp_bits, int16_t *out, size_t cap_blocks, size_t *nblocks, int *stats /* [8] */)
+{
+    return emul_single_decode_lanes(jpeg, len, layout, mode, sub_base_bits, warm_bits, headroom_groups, cp_bits, out, cap_blocks, nblocks, stats, nullptr, 0);
+}
+// lanes: per subsequence (the first lanes_cap of them) what the first decode knows of the bit patterns no code matched --
+//   [0] position of the first one inside the subsequence (0xffffffff: none)   [1] the merge point pK inside the subsequence (0: the
+//   lane's entry was right, everything it decoded stays; 0xffffffff: nothing stays)   [2] position of a later one the sink keeps   [3] how many
+// and behind the last subsequence's a row {bits per subsequence, subsequences, bits between checkpoints, warm-up bits}.
+// A lane with [0] < [1] has spent "the first one" on a code that does not count: what k_huff_prefix decides on is the last one.
+extern "C" int emul_single_decode_lanes(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, unsigned warm_bits,
+                                        unsigned headroom_groups, unsigned cp_bits, int16_t *out, size_t cap_blocks, size_t *nblocks, int *stats /* [8] */,
+                                        uint32_t *lanes, size_t lanes_cap)
 {
     mjx_opts opts{};
     opts.layout = uint8_t(layout);
@@ -441,11 +470,11 @@ extern "C" int emul_single_decode_cp(const uint8_t *jpeg, size_t len, int layout
     std::vector<uint32_t> whole(size_t(hdr) + size_t(stream_quad_entries(nsub, rows)), 0xdeadbeefu);
     uint32_t *runs = whole.data(), *region = whole.data() + hdr;
     std::vector<SubseqState> g_entry(nsub), g_exit(nsub);
-    std::vector<uint32_t> g_cps(size_t(nsub) * kMaxCp * 2, 0xdeadbeefu), d0n(nsub), d0m(nsub), kfix(nsub, 0), badl(nsub, 0xffffffffu), badp(nsub, 0);
+    std::vector<uint32_t> g_cps(size_t(nsub) * kMaxCp * 2, 0xdeadbeefu), d0n(nsub), d0m(nsub), kfix(nsub, 0), badl(nsub, 0xffffffffu), badp(nsub, 0), badq(nsub, 0xffffffffu), badql(nsub, 0), badq2(nsub, 0xffffffffu);
     constexpr uint32_t kAll = kEmitAll;
     NoCheckpoints nocp;
     TickSink ns;
-    int overflow = 0, bad = 0;
+    int overflow = 0, bad = 0, give_up = 0, huff_bad = 0;      // (huff_bad: an invalid code in a block of the picture -- the decode goes on, as on the device)
     long merge_ticks = 0, prefix_ticks = 0, prefix_lanes = 0, rounds = 0;
     // ---- k_huff_emit
     for (uint32_t s = 0; s < nsub; s++) {
@@ -457,6 +486,9 @@ extern "C" int emul_single_decode_cp(const uint8_t *jpeg, size_t len, int layout
             e.n = e.m = 0;
         }
         EmitSink sink{region, s, rows, H, Hb, 0u, H, cap, 0xffffffffu, &overflow};
+        sink.sub_start = s * L;
+        sink.tail_start = emit_tail_start(img.total_bits, s * L);
+        sink.tail_cp = emit_tail_cp(sink.tail_start, CPB);
         HostCps hc{g_cps.data() + size_t(s) * kMaxCp * 2};
         const SubseqState x = decode_subseq<true, 1>(bits, plan.lut.data(), imgw, e, end_of(s), 0, sink, hc, s * L, e);
         while (sink.eoff & 7u) {                                                   // null entries up to the group boundary
@@ -468,7 +500,17 @@ extern "C" int emul_single_decode_cp(const uint8_t *jpeg, size_t len, int layout
         d0n[s] = x.n; d0m[s] = x.m;
         badl[s] = sink.bad_label;
         badp[s] = sink.bad_pos - s * L;
+        badq[s] = sink.bad_last;
+        badql[s] = sink.bad_tail;
+        badq2[s] = sink.bad_tail2;
+        if (lanes && s < lanes_cap) {
+            lanes[4 * s] = sink.bad_label == 0xffffffffu ? 0xffffffffu : badp[s];
+            lanes[4 * s + 1] = 0;
+            lanes[4 * s + 2] = sink.bad_tail != 0xffffffffu && sink.nbad ? (sink.bad_tail & 0xffffu) : sink.bad_last == 0xffffffffu ? 0xffffffffu : (sink.bad_last & 0xffffu);
+            lanes[4 * s + 3] = sink.nbad;
+        }
     }
+    if (lanes && nsub < lanes_cap) { lanes[4 * nsub] = L; lanes[4 * nsub + 1] = nsub; lanes[4 * nsub + 2] = CPB; lanes[4 * nsub + 3] = W; }      // (a trailer: the cut)
     // ---- merge rounds (count only); the deepest merge point of a subsequence's re-decodes is kept
     for (;;) {
         long redone = 0;
@@ -481,7 +523,7 @@ extern "C" int emul_single_decode_cp(const uint8_t *jpeg, size_t len, int layout
             g_entry[s] = e;
             HostCps hc{g_cps.data() + size_t(s) * kMaxCp * 2};
             uint32_t depth = kAll;
-            if (e.p > end_of(s)) { g_exit[s] = make_state(e.p, e.z, e.c); }
+            if (e.p > s * L + band_end(end_of(s) - s * L)) { g_exit[s] = make_state(e.p, e.z, e.c); }
             else {
                 LaneState st; LaneEvents ev;
                 lane_begin(st, bits, img2, e);
@@ -534,7 +576,7 @@ extern "C" int emul_single_decode_cp(const uint8_t *jpeg, size_t len, int layout
         for (uint32_t i = off_e & ~7u; i < off_e; i++) region[stream_phys(s, i, rows)] = 0u;      // null entries in front of the run's first entry
         gs[s] = off_e >> 3;
         const SubseqState e = g_entry[s];
-        if (e.p <= end_of(s)) {
+        if (e.p <= s * L + band_end(end_of(s) - s * L)) {
             LaneState st;
             lane_begin(st, bits, imgw, e);
             uint32_t blk = 0;
@@ -546,22 +588,42 @@ extern "C" int emul_single_decode_cp(const uint8_t *jpeg, size_t len, int layout
                 const uint32_t rec = g_cps[(size_t(s) * kMaxCp + kfix[s] - 1) * 2];
                 if ((rec & kCpStateMask) != cp_state_word(st)) bad = 13;        // ... and the prefix must meet the first decode's path there
             }
-            if (sink.bad_label != 0xffffffffu && B[s] + sink.bad_label < nb) bad = 1;
+            if (sink.bad_label != 0xffffffffu && B[s] + sink.bad_label < nb) huff_bad = 1;
         }
-        if (badl[s] != 0xffffffffu) {       // the first decode's invalid code counts if it lies at or behind the merge point
+        if (lanes && s < lanes_cap) lanes[4 * s + 1] = 0xffffffffu;
+        if (badl[s] != 0xffffffffu) {       // the first decode's invalid codes count if they lie at or behind the merge point (k_huff_prefix)
             if (kfix[s] == kAll) badl[s] = 0xffffffffu;
             else {
                 const uint32_t rec = g_cps[(size_t(s) * kMaxCp + kfix[s] - 1) * 2];
                 const uint32_t pK = 8u * (wn_after(kfix[s] * CPB) - 8u) - (rec & 31u);
-                if (badp[s] < pK) badl[s] = 0xffffffffu;
+                if (lanes && s < lanes_cap) lanes[4 * s + 1] = pK;
+                if (badp[s] < pK) {
+                    // the first one lies on the discarded part: the last one in front of the scan's tail, then the first one inside it (k_huff_prefix)
+                    auto inside = [&](uint32_t w) { return int64_t(B[s]) + int64_t(w >> 16) - lbl[s] < int64_t(nb); };
+                    const bool first_inside = int64_t(B[s]) + int64_t(badl[s]) - lbl[s] < int64_t(nb);
+                    badl[s] = 0xffffffffu;
+                    if (!first_inside) {
+                        // (the first one's block is already behind the picture's last: so is every later one's)
+                    } else if (badq[s] != 0xffffffffu && (badq[s] & 0xffffu) >= pK) {
+                        if (inside(badq[s])) badl[s] = badq[s] >> 16;
+                        else give_up = 16;                 // (the device hands the picture to the two-pass kernels: reason bit 256)
+                    } else {
+                        const uint32_t tw = pK > emit_tail_cp(emit_tail_start(img.total_bits, s * L), CPB) ? badq2[s] : badql[s];
+                        if (tw != 0xffffffffu && (tw & 0xffffu) >= pK && inside(tw)) badl[s] = tw >> 16;
+                    }
+                }
             }
         }
     }
     for (uint32_t s = 0; s < nsub; s++) runs[s] = run_word(gs[s], ge[s], uint32_t(int32_t(B[s]) - lbl[s]) & 0xffu);
     if (overflow) bad = 14;                        // (the device hands the picture to the two-pass kernels: nothing else counts)
+    else if (give_up && !bad) bad = give_up;       // (the same, for an invalid code k_huff_prefix cannot place: 16 -- the last one in front of the
+                                                   // scan's tail lies behind the picture's last block, and the first one was discarded)
     for (uint32_t s = 0; s < nsub; s++)
-        if (badl[s] != 0xffffffffu && int64_t(B[s]) + int64_t(badl[s]) - lbl[s] < int64_t(nb)) bad = bad ? bad : 1;
+        if (badl[s] != 0xffffffffu && int64_t(B[s]) + int64_t(badl[s]) - lbl[s] < int64_t(nb)) huff_bad = 1;
     // ---- k_block_gather + stage B's expansion (quad_prepare / quad_cell: the functions the kernel runs)
+    const bool truncated = B[nsub] < nb;            // k_huff_scan: the picture is flagged and every later kernel skips it
+    if (truncated && !bad) bad = 15;
     if (!bad && nb <= cap_blocks && B[nsub] >= nb) {
         const uint32_t tile_blocks = tile_mcus(plan.bpm, plan.hmax) * plan.bpm;
         const uint32_t ntiles = uint32_t((nb + tile_blocks - 1) / tile_blocks);
@@ -606,13 +668,14 @@ extern "C" int emul_single_decode_cp(const uint8_t *jpeg, size_t len, int layout
             pred[c] += dcb[b];
             out[b * 64] = int16_t(pred[c]);
         }
-    } else if (!bad && B[nsub] < nb) bad = 15;                                 // truncated
+    }
     if (stats) {
         stats[0] = int(nsub); stats[1] = int(rounds); stats[2] = int(prefix_lanes); stats[3] = int(prefix_ticks);
-        stats[4] = int(merge_ticks); stats[5] = int(worst_e); stats[6] = bad; stats[7] = int(worst_b);
+        stats[4] = int(merge_ticks); stats[5] = int(worst_e); stats[6] = bad ? bad : huff_bad; stats[7] = int(worst_b);
     }
     mjx_free_scan(&d);
-    return nb <= cap_blocks ? (bad ? MJX_ERR_BAD_HUFFMAN : MJX_OK) : MJX_ERR_NOMEM;
+    if (nb > cap_blocks) return MJX_ERR_NOMEM;
+    return truncated ? MJX_ERR_TRUNCATED : (bad || huff_bad) ? MJX_ERR_BAD_HUFFMAN : MJX_OK;      // (as mjx_batch_wait: truncated wins)
 }
 
 // ---- round 5: multi-scan pictures read without the gather, and what the planner decides per scan ------------------------------------

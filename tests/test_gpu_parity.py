@@ -237,13 +237,18 @@ def test_cli_writes_the_reference_ppm(mjx, orc, gpu_ctx, data_dir, tmp_path):
 
 # ---- hostile inputs: one bad image must not kill the batch, and nothing may fault on the device --------------------
 def test_truncated_and_garbage_scans(mjx, orc, gpu_ctx, data_dir):
+    """Every broken scan gets the status the serial decode of tests/damaged_ref.py gives it (the band rule), in both
+    layouts; the intact neighbour is right."""
     import ctypes
+    import damaged_ref as dr
+    code = {dr.OK: mjx.OK, dr.TRUNCATED: mjx.ERR_TRUNCATED, dr.BAD_HUFFMAN: mjx.ERR_BAD_HUFFMAN}
     good = open(os.path.join(data_dir, "lena.jpeg"), "rb").read()
     big = mjx.synth_jpeg(1024, 768, "420", 75, seed=5)
     rng = np.random.default_rng(11)
     scans, expect = [], []
     for cut in (0.3, 0.7, 0.97):                       # file cut inside the entropy-coded segment
         scans.append(mjx.ParsedScan(big[: int(len(big) * cut)]))
+        assert dr.decode(dr.Picture(big[: int(len(big) * cut)])).verdict == dr.TRUNCATED
         expect.append({mjx.ERR_TRUNCATED})
     for fill in ("random", "ff", "zero"):              # same headers, meaningless scan bytes
         s = mjx.ParsedScan(big)
@@ -251,7 +256,7 @@ def test_truncated_and_garbage_scans(mjx, orc, gpu_ctx, data_dir):
         raw = {"random": rng.integers(0, 256, n, dtype=np.uint8).tobytes(), "ff": b"\xff" * n, "zero": b"\x00" * n}[fill]
         ctypes.memmove(s.desc.scan, raw, n)
         scans.append(s)
-        expect.append({mjx.OK, mjx.ERR_TRUNCATED, mjx.ERR_BAD_HUFFMAN})
+        expect.append({code[dr.decode(dr.Picture(big), raw, []).verdict]})
     scans.append(mjx.ParsedScan(good))
     expect.append({mjx.OK})
     for layout in (mjx.LAYOUT_STANDARD, mjx.LAYOUT_REF_COMPAT):
@@ -506,7 +511,7 @@ def test_restart_intervals_hostile_inputs(mjx, orc, gpu_ctx):
     d = os.path.join(os.path.dirname(__file__), "golden", "pil")
     rng = np.random.default_rng(3)
     good = open(os.path.join(d, "dri_422_rows.jpg"), "rb").read()
-    scans, n_ok_parse = [mjx.ParsedScan(good)], 0
+    scans, files, n_ok_parse = [mjx.ParsedScan(good)], [good], 0
     for name in ("dri_420_r5", "dri_420_720p_rows", "dri_444_r1"):
         base = open(os.path.join(d, name + ".jpg"), "rb").read()
         sos = base.index(b"\xff\xda")
@@ -516,6 +521,7 @@ def test_restart_intervals_hostile_inputs(mjx, orc, gpu_ctx):
                 b[int(rng.integers(sos + 14, len(b)))] = int(rng.choice([0xff, 0xd0, 0xd3, 0x00, int(rng.integers(0, 256))]))
             try:
                 scans.append(mjx.ParsedScan(bytes(b)))
+                files.append(bytes(b))
                 n_ok_parse += 1
             except mjx.MjxError:
                 pass
@@ -523,8 +529,15 @@ def test_restart_intervals_hostile_inputs(mjx, orc, gpu_ctx):
     batch = mjx.Batch(gpu_ctx, scans, keep_coefs=True, chunk_images=7)
     batch.decode()
     batch.wait()
+    # the status and, where the picture is OK, the coefficients of the serial decode (tests/damaged_ref.py)
+    import damaged_ref as dr
+    code = {dr.OK: mjx.OK, dr.TRUNCATED: mjx.ERR_TRUNCATED, dr.BAD_HUFFMAN: mjx.ERR_BAD_HUFFMAN}
+    wrong = []
     for i in range(1, len(scans)):
-        assert batch.status(i) in (mjx.OK, mjx.ERR_TRUNCATED, mjx.ERR_BAD_HUFFMAN, mjx.ERR_INVALID_ARG)
+        want = dr.decode(dr.Picture(files[i]))
+        if batch.status(i) != code[want.verdict] or (want.verdict == dr.OK and not np.array_equal(batch.coefs(i), want.t0)):
+            wrong.append((i, batch.status(i), want.verdict))
+    assert wrong == [], wrong
     ref = orc.decode(good, layout=orc.LAYOUT_STD, ext_dri=True)
     assert batch.status(0) == mjx.OK
     _check(ref, batch.coefs(0), batch.rgb(0), "intact image next to corrupted ones")
@@ -585,11 +598,23 @@ def test_device_side_destuffing_and_marker_scan_through_every_front_door(mjx, or
     datas += [mjx.synth_jpeg(w, h, s, q, seed=i) for i, (w, h, s, q) in enumerate(
         [(1920, 1080, "420", 95), (640, 480, "444", 98), (64, 64, "gray", 100), (17, 9, "420", 99), (3840, 2160, "420", 75)])]
     dri = open(os.path.join(pil, "dri_420_r5.jpg"), "rb").read()
+    h0 = len(datas)
     datas += _hostile_stuffed_variants(mjx, dri) + _hostile_stuffed_variants(mjx, datas[-2])
     datas += [b"not a jpeg", dri[:len(dri) // 2], dri[:700]]
     host, st_host = mjx.decode_batch(gpu_ctx, datas, keep_coefs=True, device_destuff=False)
     n_ok = sum(1 for s in st_host if s == mjx.OK)
     assert n_ok >= len(datas) - 8
+    # the broken files: the status and, where the picture is OK, the coefficients of the serial decode (tests/damaged_ref.py; DESIGN.md
+    # s2) -- on the host path here, and on the device path through the comparisons below
+    import damaged_ref as dr
+    code = {dr.OK: mjx.OK, dr.TRUNCATED: mjx.ERR_TRUNCATED, dr.BAD_HUFFMAN: mjx.ERR_BAD_HUFFMAN}
+    wrong = []
+    for i in list(range(h0, len(datas) - 3)) + [len(datas) - 2, len(datas) - 1]:
+        want = dr.decode(dr.Picture(datas[i]))
+        if st_host[i] != code[want.verdict] or (want.verdict == dr.OK and not np.array_equal(host.coefs(i), want.t0)):
+            wrong.append((i - h0, st_host[i], want.verdict))
+    assert wrong == [], wrong
+    assert len({st_host[i] for i in range(h0, len(datas))}) >= 3          # (OK, truncated and invalid codes all occur among them)
     # (MJX_DESTUFF_AUTO, what a zeroed mjx_opts says: the GPU for lists of MJX_AUTO_DESTUFF_MB and more -- here: for any list)
     for env in ({}, {"MJX_GROUP_MB": "1"}, {"MJX_AUTO_DESTUFF_MB": "0", "MJX_GROUP_MB": "2"}):
         os.environ.update(env)
