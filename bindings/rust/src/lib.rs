@@ -82,6 +82,30 @@ pub struct mjx_orient {
     pub n_extra: u32,
 }
 
+/// The planes of one picture (include/mjx.h: mjx_plane_layout): device pointer and row pitch (elements) per plane, width and height
+/// in samples per component.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mjx_plane_layout {
+    pub dev: [*mut c_void; 3],
+    pub row_pitch: [u64; 3],
+    pub width: [u32; 3],
+    pub height: [u32; 3],
+}
+
+/// YCbCr output: the pictures of a call leave as their component planes at their own sampling -- I420, or NV12 with
+/// interleave_chroma; a float element is fmaf(u8 as f32, scale[c], bias[c]) by COMPONENT; dst null = library-owned (include/mjx.h).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mjx_planes {
+    pub dtype: u8,
+    pub interleave_chroma: u8,
+    pub scale: [f32; 3],
+    pub bias: [f32; 3],
+    pub dst: *const mjx_plane_layout,
+    pub n_dst: u32,
+}
+
 /// Resize on the device: every picture of a call leaves at `width` x `height` (include/mjx.h: mjx_resize).
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -210,6 +234,15 @@ extern "C" {
     pub fn mjx_batch_copy_output(b: *mut mjx_batch, i: usize, host: *mut c_void, cap_bytes: usize) -> c_int;
     pub fn mjx_decode_batch_out(ctx: *mut mjx_ctx, jpegs: *const *const u8, lens: *const usize, n: usize, opts: *const mjx_opts,
                                 threads: c_uint, out: *const mjx_output, status: *mut c_int, b: *mut *mut mjx_batch) -> c_int;
+    pub fn mjx_batch_create_planes(ctx: *mut mjx_ctx, descs: *const mjx_scan_desc, n: usize, opts: *const mjx_opts, planes: *const mjx_planes,
+                                   b: *mut *mut mjx_batch, status: *mut c_int) -> c_int;
+    pub fn mjx_planes_layout(desc: *const mjx_scan_desc, opts: *const mjx_opts, planes: *const mjx_planes, i: usize,
+                             layout: *mut mjx_plane_layout, nplanes: *mut u32, bytes: *mut usize) -> c_int;
+    pub fn mjx_batch_plane_info(b: *const mjx_batch, i: usize, nplanes: *mut u32, layout: *mut mjx_plane_layout, dtype: *mut u8,
+                                interleave: *mut u8) -> c_int;
+    pub fn mjx_batch_copy_planes(b: *mut mjx_batch, i: usize, host: *mut c_void, cap_bytes: usize) -> c_int;
+    pub fn mjx_decode_batch_planes(ctx: *mut mjx_ctx, jpegs: *const *const u8, lens: *const usize, n: usize, opts: *const mjx_opts,
+                                   threads: c_uint, planes: *const mjx_planes, status: *mut c_int, b: *mut *mut mjx_batch) -> c_int;
     pub fn mjx_batch_create_resize(ctx: *mut mjx_ctx, descs: *const mjx_scan_desc, n: usize, opts: *const mjx_opts, out: *const mjx_output,
                                    rs: *const mjx_resize, b: *mut *mut mjx_batch, status: *mut c_int) -> c_int;
     pub fn mjx_decode_batch_resize(ctx: *mut mjx_ctx, jpegs: *const *const u8, lens: *const usize, n: usize, opts: *const mjx_opts,

@@ -185,8 +185,57 @@ typedef struct mjx_output {
  * the span from there to the end of its last element, mjx_batch_bytes' rgb_bytes counts the bytes written.  mjx_batch_tile keeps
  * a library-owned format and refuses a batch with caller-owned destinations (the copies would share them).  With caller-owned
  * destinations the batch's device block holds no picture pool at all; with library-owned output the pool is sized by the format.
- * Not built: YCbCr output; mjx_decode and the pool (mjx_pool_decode_batch: the slot -- so the device -- of a file is not known to the
+ * YCbCr output is the plane description's (mjx_planes, below).  Not built: mjx_decode and the pool (mjx_pool_decode_batch: the slot -- so the device -- of a file is not known to the
  * caller before the deal) keep packed RGB; the CLI writes packed RGB or, with --luma, the luminance picture. */
+
+/* ---- YCbCr output: the component planes at their own sampling (I420, NV12) ---------------------------------------------
+ * With a plane description (mjx_batch_create_planes, mjx_decode_batch_planes) a picture leaves as the planes a JPEG holds -- Y, Cb
+ * and Cr, chroma at its own resolution -- not as RGB: no upsampling, no colour arithmetic, 1.5 bytes per pixel for 4:2:0.
+ * Geometry.  A picture has ncomp components (1 or 3) with factors (h_c, v_c) and maxima hmax, vmax; its size at the call's
+ * scale_denom s is out_w x out_h = ceil(W/s) x ceil(H/s).  Plane c of the whole picture is ceil(out_w h_c / hmax) x
+ * ceil(out_h v_c / vmax) samples.  For a rectangle (x, y, w, h) of the out_w x out_h picture (mjx_opts.rois, same rules) plane c
+ * covers the columns floor(x h_c / hmax) .. ceil((x + w) h_c / hmax) and the rows floor(y v_c / vmax) .. ceil((y + h) v_c / vmax)
+ * of the whole picture's plane: exactly the samples the packed decode of that picture or rectangle reads from component c.  Stage
+ * B reads only the tiles that touch the rectangle, as for any cropped picture.  A one-component file has one plane (its factors
+ * count as 1 x 1).
+ * Values, MJX_PIXELS_REFERENCE: the u8 value of a sample is stage B's truncating, saturating store of the component's float sample
+ * + 128, for every component, at every scale.  Said without this code: build the one-component file that carries component c's
+ * coefficient blocks and quantisation table; its packed decode at the same scale has the sample in its R byte.  Component 0's plane
+ * equals the luminance output (MJX_OUTPUT_CHANNELS == 1) byte for byte wherever Y has the largest factors.
+ * Values, MJX_PIXELS_LIBJPEG (full size only, as that option is): the rounded sample clamp(floor(f + 128 + 0.5), 0, 255) -- the
+ * planes mjx_opts.pixels describes, in front of its upsampling.
+ * Dtypes: U8 as above; F32 is fmaf((float)u8, scale[c], bias[c]), c the COMPONENT; F16 is that float rounded to nearest even.
+ * Layout.  Library-owned output is dense, the planes directly behind one another in component order: a u8 4:2:0 picture is an I420
+ * frame as it stands.  interleave_chroma = 1 writes Cb and Cr into one plane, element (X, Y) as the pair Cb, Cr at dev[1] +
+ * Y row_pitch[1] + 2 X -- NV12's second plane; it needs equal chroma factors and has no meaning for a one-component file.
+ * Caller-owned output (dst) takes a pointer and a row pitch, in elements, per plane: a pitch is at least the plane's width (twice
+ * the width for the interleaved plane), a pointer is aligned to the element size; dev[2] is ignored with interleave_chroma, dev[1]
+ * and dev[2] for a one-component file.  Nothing is written outside each plane's height rows x width elements.  Ordering is
+ * mjx_output's: a caller-owned destination is idle at the call and complete when mjx_batch_wait / the pipelined call returns. */
+typedef struct mjx_plane_layout {  /* the planes of one picture; pitches in elements */
+    void *dev[3];             /* first element of plane c (device memory) */
+    uint64_t row_pitch[3];    /* elements between rows of plane c */
+    uint32_t width[3], height[3];  /* samples of component c; the interleaved plane 1 has 2 * width[1] elements per row */
+} mjx_plane_layout;
+typedef struct mjx_planes {
+    uint8_t dtype;            /* MJX_DTYPE_* */
+    uint8_t interleave_chroma;/* 0: three planes (I420 order); 1: Y, then Cb and Cr interleaved (NV12) */
+    float scale[3], bias[3];  /* F16/F32 only, indexed by COMPONENT: value = fmaf((float)u8, scale[c], bias[c]) */
+    const mjx_plane_layout *dst;  /* NULL: library-owned, dense, planes back to back */
+    uint32_t n_dst;           /* 0 with dst == NULL, else the call's number of inputs; dst[i] belongs to input i */
+} mjx_planes;
+/* Per picture, MJX_ERR_INVALID_ARG (nothing is written for it, the others are unaffected): an unknown dtype; MJX_LAYOUT_REF_COMPAT;
+ * interleave_chroma with unequal chroma factors; dst[i].width / height other than the planes' sizes, or a pitch too small; a
+ * pointer NULL or not aligned to the element size; a non-finite scale / bias with a float dtype; MJX_PIXELS_LIBJPEG with
+ * scale_denom > 1; the rectangle's own rules.  n_dst other than 0 or the call's number of inputs, dst == NULL with n_dst != 0 or a
+ * NULL description fails the call.  The description and dst[] are only borrowed for the duration of the call.
+ * A batch that carries a plane description: mjx_batch_copy_rgb returns MJX_ERR_INVALID_ARG (mjx_batch_copy_planes is its
+ * counterpart), mjx_batch_compare_rgb reports 0xffffffff, mjx_batch_rgb_device gives the first plane's first byte and the span
+ * from there to the last plane's end, mjx_batch_bytes' rgb_bytes counts the bytes written, mjx_batch_image_info, _image_roi and
+ * _image_scale are as for a packed picture, mjx_batch_output_channels answers 3, mjx_batch_tile carries the description along
+ * (library-owned output only), mjx_batch_copy_coefs is unchanged.
+ * Not built: resize and orientation on planes (the entry points take neither); mjx_decode and the pool with planes; a dedicated
+ * 4:2:0 plane form (4:2:0 takes the generic form); skipping anything in the entropy stage. */
 
 /* ---- resize on the device: every picture of a call leaves at one target size -------------------------------------------
  * With a resize description (mjx_batch_create_resize, mjx_decode_batch_resize) picture i is decoded as a packed picture at a
@@ -387,6 +436,24 @@ int mjx_batch_output_channels(mjx_batch *b, size_t i, uint8_t *channels);
  * caller-owned destination or a batch without an output description: MJX_ERR_INVALID_ARG. */
 int mjx_batch_copy_output(mjx_batch *b, size_t i, void *host, size_t cap_bytes);
 
+/* mjx_batch_create with a plane description (YCbCr output, above): the pictures leave as their component planes.  planes == NULL:
+ * MJX_ERR_INVALID_ARG. */
+int mjx_batch_create_planes(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_planes *planes,
+                            mjx_batch **b, int *status);
+/* Host-only, from the planner itself, like mjx_output_layout: the planes a decode of this picture as input i of a call with these
+ * options and this description would write -- *nplanes of them (1 for a one-component file, 3, or 2 with interleave_chroma), per
+ * component width and height in samples, per plane its pitch in elements (a caller-owned plane: dst[i]'s own pitch and pointer;
+ * layout->dev stays NULL for library-owned output) -- and *bytes, the planes' spans added up (dense library-owned output: the
+ * whole of it, what mjx_batch_copy_planes copies).  Returns the picture's status. */
+int mjx_planes_layout(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_planes *planes, size_t i, mjx_plane_layout *layout,
+                      uint32_t *nplanes, size_t *bytes);
+/* The planes of picture i of a batch with a plane description: their number, device pointers, pitches, sizes, dtype and whether
+ * chroma is interleaved.  A batch without a plane description: MJX_ERR_INVALID_ARG. */
+int mjx_batch_plane_info(const mjx_batch *b, size_t i, uint32_t *nplanes, mjx_plane_layout *layout, uint8_t *dtype, uint8_t *interleave);
+/* Copy picture i's library-owned planes to host memory, dense, planes back to back, as mjx_planes_layout sizes them; cap_bytes
+ * smaller than that, caller-owned planes or a batch without a plane description: MJX_ERR_INVALID_ARG. */
+int mjx_batch_copy_planes(mjx_batch *b, size_t i, void *host, size_t cap_bytes);
+
 /* mjx_batch_create_out with a resize description (above); rs == NULL: mjx_batch_create_out itself.  out == NULL with a resize:
  * interleaved u8 R,G,B, library-owned. */
 int mjx_batch_create_resize(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_output *out,
@@ -536,6 +603,12 @@ int mjx_decode_batch_resize(mjx_ctx *ctx, const uint8_t *const *jpegs, const siz
 int mjx_decode_batch_orient(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
                             unsigned threads, const mjx_output *out, const mjx_resize *rs, const mjx_orient *orient, int *status,
                             mjx_batch **b);
+
+/* mjx_decode_batch with a plane description (YCbCr output); dst[i] follows file i through the groups of the pipelined call, as in
+ * mjx_decode_batch_out; mjx_batch_plane_info says where picture i's planes lie.  ctx == NULL is MJX_ERR_DEVICE, planes == NULL
+ * MJX_ERR_INVALID_ARG. */
+int mjx_decode_batch_planes(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
+                            unsigned threads, const mjx_planes *planes, int *status, mjx_batch **b);
 
 /* ---- multi-GPU front: one context + one host thread + one work queue per device, no collective ----------
  * Pictures are independent (decoder.rs:162-343 touches only `self`), so a list of files shards over the GPUs of a node

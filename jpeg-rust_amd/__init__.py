@@ -76,6 +76,18 @@ class OutputDesc(ctypes.Structure):
         ctypes.c_uint8.from_address(ctypes.addressof(self) + self.CHANNELS_OFFSET).value = int(v)
 
 
+class PlaneLayout(ctypes.Structure):
+    """mjx_plane_layout: the planes of one picture; pitches in elements, width / height in samples of the component."""
+    _fields_ = [("dev", ctypes.c_void_p * 3), ("row_pitch", ctypes.c_uint64 * 3), ("width", ctypes.c_uint32 * 3), ("height", ctypes.c_uint32 * 3)]
+
+
+class PlanesDesc(ctypes.Structure):
+    """mjx_planes: the pictures of a call leave as their component planes (see Planes)."""
+    _fields_ = [("dtype", ctypes.c_uint8), ("interleave_chroma", ctypes.c_uint8),
+                ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3),
+                ("dst", ctypes.POINTER(PlaneLayout)), ("n_dst", ctypes.c_uint32)]
+
+
 class ResizeDesc(ctypes.Structure):
     """mjx_resize: the one target size of a call's pictures (see Resize)."""
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("antialias", ctypes.c_uint8), ("auto_scale", ctypes.c_uint8)]
@@ -133,6 +145,11 @@ SYMBOLS = {
     "mjx_batch_output_info": (_int, [_vp, _sz, _P(Dst)] + [_P(ctypes.c_uint8)] * 3),
     "mjx_batch_output_channels": (_int, [_vp, _sz, _P(ctypes.c_uint8)]),
     "mjx_batch_copy_output": (_int, [_vp, _sz, _vp, _sz]),
+    "mjx_batch_create_planes": (_int, [_vp, _P(ScanDesc), _sz, _P(Opts), _P(PlanesDesc), _P(_vp), _P(_int)]),
+    "mjx_decode_batch_planes": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(PlanesDesc), _P(_int), _P(_vp)]),
+    "mjx_planes_layout": (_int, [_P(ScanDesc), _P(Opts), _P(PlanesDesc), _sz, _P(PlaneLayout), _P(ctypes.c_uint32), _P(_sz)]),
+    "mjx_batch_plane_info": (_int, [_vp, _sz, _P(ctypes.c_uint32), _P(PlaneLayout), _P(ctypes.c_uint8), _P(ctypes.c_uint8)]),
+    "mjx_batch_copy_planes": (_int, [_vp, _sz, _vp, _sz]),
     "mjx_batch_create_resize": (_int, [_vp, _P(ScanDesc), _sz, _P(Opts), _P(OutputDesc), _P(ResizeDesc), _P(_vp), _P(_int)]),
     "mjx_decode_batch_resize": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(OutputDesc), _P(ResizeDesc), _P(_int), _P(_vp)]),
     "mjx_resize_plan": (_int, [_P(ScanDesc), _P(Opts), _P(ResizeDesc), _sz, _P(ctypes.c_uint8), _P(Rect), _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
@@ -321,6 +338,58 @@ class Output:
         return _NP_DTYPES[self.dtype]
 
 
+class Planes:
+    """YCbCr output (mjx.h: mjx_planes): the pictures of a call leave as their component planes -- Y, Cb, Cr at their own sampling,
+    no upsampling and no colour conversion; a uint8 4:2:0 picture is an I420 frame, with interleave=True NV12.  dtype "uint8" /
+    "float16" / "float32" (or DTYPE_*); a float element is fmaf(float(u8), scale[c], bias[c]) with c the COMPONENT; mean / std (of
+    values in [0, 1], per component) become scale = 1 / (255 std) and bias = -mean / std as in Output.
+    dst: None -- the library owns the planes, dense and back to back -- or per input a list of (device pointer, row_pitch) per plane
+    with the planes' (width, height) per component: ([(ptr, pitch), ...], [(w, h), ...]); pitches in elements."""
+
+    def __init__(self, dtype="uint8", interleave=False, mean=None, std=None, scale=None, bias=None, dst=None):
+        names = {"uint8": DTYPE_U8, "u8": DTYPE_U8, "float16": DTYPE_F16, "f16": DTYPE_F16, "float32": DTYPE_F32, "f32": DTYPE_F32}
+        self.dtype = names[dtype] if isinstance(dtype, str) else int(dtype)
+        self.interleave = bool(interleave)
+        if (mean is not None or std is not None) and (scale is not None or bias is not None):
+            raise MjxError(ERR_INVALID_ARG, "mean / std or scale / bias, not both")
+        three = lambda v, d: [float(d)] * 3 if v is None else ([float(v)] * 3 if np.isscalar(v) else [float(x) for x in v])
+        if mean is not None or std is not None:
+            m, sd = np.array(three(mean, 0.0), np.float64), np.array(three(std, 1.0), np.float64)
+            sc, bi = 1.0 / (255.0 * sd), -m / sd
+        else:
+            sc, bi = np.array(three(scale, 1.0), np.float64), np.array(three(bias, 0.0), np.float64)
+        if len(sc) != 3 or len(bi) != 3:
+            raise MjxError(ERR_INVALID_ARG, "one value per component")
+        self.scale, self.bias = sc.astype(np.float32), bi.astype(np.float32)
+        self.dst = dst
+
+    def desc(self):
+        """-> the ctypes mjx_planes (it keeps its dst array alive)."""
+        d = PlanesDesc(self.dtype, int(self.interleave))
+        for c in range(3):
+            d.scale[c], d.bias[c] = float(self.scale[c]), float(self.bias[c])
+        if self.dst is not None:
+            arr = (PlaneLayout * max(len(self.dst), 1))()
+            for i, (planes, sizes) in enumerate(self.dst):
+                for c, (ptr, pitch) in enumerate(planes):
+                    arr[i].dev[c] = int(ptr) or None
+                    arr[i].row_pitch[c] = int(pitch)
+                for c, (w, h) in enumerate(sizes):
+                    arr[i].width[c], arr[i].height[c] = int(w), int(h)
+            d._arr = arr
+            d.dst = ctypes.cast(arr, _P(PlaneLayout))
+            d.n_dst = len(self.dst)
+        return d
+
+    def numpy_dtype(self):
+        return _NP_DTYPES[self.dtype]
+
+
+def _planes_ref(planes):
+    d = planes.desc() if isinstance(planes, Planes) else planes
+    return d, ctypes.byref(d)
+
+
 class Resize:
     """Resize on the device (mjx.h: mjx_resize): every picture of the call leaves at width x height, resampled from its decoded
     rectangle with the triangle filter of torch.nn.functional.interpolate(mode="bilinear", align_corners=False,
@@ -466,6 +535,16 @@ class ParsedScan:
         _check(lib().mjx_output_layout(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(lay), ctypes.byref(nb)), "mjx_output_layout")
         return dict(width=lay.width, height=lay.height, row_pitch=lay.row_pitch, plane_pitch=lay.plane_pitch, bytes=nb.value, dev=lay.dev or 0)
 
+    def planes_layout(self, planes, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD, pixels=None, strict_ref=False):
+        """mjx_planes_layout (host only) -> dict(nplanes, width, height, row_pitch, dev -- a list of three each --, bytes): the planes a
+        decode of this picture as input i of a call with this Planes would write; pitches in elements, sizes in samples."""
+        o = _opts(layout=layout, scale=scale, rois=roi, pixels=pixels, strict_ref=strict_ref)
+        keep, ref = _planes_ref(planes)
+        lay, np_, nb = PlaneLayout(), ctypes.c_uint32(), _sz()
+        _check(lib().mjx_planes_layout(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(lay), ctypes.byref(np_), ctypes.byref(nb)), "mjx_planes_layout")
+        return dict(nplanes=np_.value, width=list(lay.width), height=list(lay.height), row_pitch=list(lay.row_pitch),
+                    dev=[v or 0 for v in lay.dev], bytes=nb.value)
+
     def resize_plan(self, resize, roi=None, scale=1, i=0, layout=LAYOUT_STANDARD, pixels=None):
         """mjx_resize_plan (host only) -> dict(scale, rect=(x, y, w, h) at that scale, taps_x, taps_y): what a resized decode of this
         picture with this Resize takes; roi in full-size coordinates with auto_scale, else in the scaled picture's."""
@@ -532,7 +611,7 @@ class Batch:
     """Device-resident batch: inputs uploaded at construction, ``decode()`` only enqueues kernels."""
 
     def __init__(self, ctx, scans=None, strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0,
-                 _handle=None, scale=1, rois=None, output=None, resize=None, orient=None, datas=None, pixels=None):
+                 _handle=None, scale=1, rois=None, output=None, resize=None, orient=None, datas=None, pixels=None, planes=None):
         """scale: 1, 2, 4 or 8 -- every picture decoded at 1/scale (info(), rgb(), rgb_device() and bytes() then speak of the
         scaled picture; tile() keeps the scale).
         rois: one (x, y, w, h) for every picture, or a list with one per picture (None or (0, 0, 0, 0): the whole picture), in the
@@ -547,7 +626,9 @@ class Batch:
         picture, info(), output_info() and output() speak of it, roi(i) and rect(i) of the stored picture.  Parsed scans hold no
         EXIF segment: with Orient(exif=True) pass the files' bytes as `datas`, and the tags are read from them here.
         pixels: "libjpeg" (PIXELS_LIBJPEG) -- the pictures libjpeg-based decoders give: rounded samples, fancy chroma upsampling,
-        integer colour tables (STANDARD layout at full size only); everything above composes with it; tile() keeps it."""
+        integer colour tables (STANDARD layout at full size only); everything above composes with it; tile() keeps it.
+        planes: a Planes -- the pictures leave as their component planes (planes(i), plane_info(i)); scale, rois and pixels apply,
+        output, resize and orient do not go with it; tile() keeps it."""
         self.ctx = ctx
         self.h = _vp()
         if _handle is not None:
@@ -561,7 +642,12 @@ class Batch:
         st = (_int * max(n, 1))()
         o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois, pixels=pixels)
         keep, ref = _out_ref(output)
-        if orient is not None:
+        if planes is not None:
+            if output is not None or resize is not None or orient is not None:
+                raise MjxError(ERR_INVALID_ARG, "planes go without output, resize and orient")
+            keep_pl, pl_ref = _planes_ref(planes)
+            _check(lib().mjx_batch_create_planes(ctx.h, arr, n, ctypes.byref(o), pl_ref, ctypes.byref(self.h), st), "mjx_batch_create_planes")
+        elif orient is not None:
             if orient.exif:
                 if datas is None or len(datas) != n:
                     raise MjxError(ERR_INVALID_ARG, "Orient(exif=True) needs the files' bytes: datas")
@@ -653,6 +739,30 @@ class Batch:
         out = np.empty(shape, _NP_DTYPES[inf["dtype"]])
         _check(lib().mjx_batch_copy_output(self.h, i, out.ctypes.data_as(_vp), out.nbytes), "mjx_batch_copy_output")
         return out
+
+    def plane_info(self, i):
+        """mjx_batch_plane_info -> dict(nplanes, dev, row_pitch, width, height -- lists of three --, dtype, interleave)."""
+        lay, np_, dt, il = PlaneLayout(), ctypes.c_uint32(), ctypes.c_uint8(), ctypes.c_uint8()
+        _check(lib().mjx_batch_plane_info(self.h, i, ctypes.byref(np_), ctypes.byref(lay), ctypes.byref(dt), ctypes.byref(il)), "mjx_batch_plane_info")
+        return dict(nplanes=np_.value, dev=[v or 0 for v in lay.dev], row_pitch=list(lay.row_pitch), width=list(lay.width), height=list(lay.height),
+                    dtype=dt.value, interleave=bool(il.value))
+
+    def planes(self, i):
+        """Picture i's library-owned planes as a tuple of ndarrays of the planes' dtype: (Y,), (Y, Cb, Cr), each [h_c, w_c], or with
+        interleaved chroma (Y, CbCr) with CbCr [h, w, 2]."""
+        inf = self.plane_info(i)
+        dt = np.dtype(_NP_DTYPES[inf["dtype"]])
+        shapes = [(inf["height"][c], inf["width"][c]) for c in range(inf["nplanes"])]
+        if inf["interleave"]:
+            shapes[1] = shapes[1] + (2,)
+        counts = [int(np.prod(sh)) for sh in shapes]
+        buf = np.empty(sum(counts), dt)
+        _check(lib().mjx_batch_copy_planes(self.h, i, buf.ctypes.data_as(_vp), buf.nbytes), "mjx_batch_copy_planes")
+        out, at = [], 0
+        for sh, cnt in zip(shapes, counts):
+            out.append(buf[at:at + cnt].reshape(sh))
+            at += cnt
+        return tuple(out)
 
     def rgb_device(self, i):
         p, n = _vp(), _sz()
@@ -895,11 +1005,12 @@ class JPEGImage:
 
 
 def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False, scale=1, rois=None,
-                 output=None, chunk_images=0, resize=None, orient=None, pixels=None):
+                 output=None, chunk_images=0, resize=None, orient=None, pixels=None, planes=None):
     """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale, rois, pixels: see Batch.
     device_destuff: the host copies the entropy-coded bytes as they are; de-stuffing, restart markers and the scan's length
     are found on the GPU.  output: an Output (mjx_decode_batch_out) -- see Batch.  resize: a Resize (mjx_decode_batch_resize).  orient: an Orient
-    (mjx_decode_batch_orient): the files' EXIF orientation and / or a code per file on top."""
+    (mjx_decode_batch_orient): the files' EXIF orientation and / or a code per file on top.  planes: a Planes (mjx_decode_batch_planes) --
+    the pictures leave as their component planes; output, resize and orient do not go with it."""
     n = len(datas)
     arr = (ctypes.c_char_p * max(n, 1))(*[bytes(d) for d in datas])
     lens = (_sz * max(n, 1))(*[len(d) for d in datas])
@@ -907,6 +1018,12 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
     h = _vp()
     o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels)
+    if planes is not None:
+        if output is not None or resize is not None or orient is not None:
+            raise MjxError(ERR_INVALID_ARG, "planes go without output, resize and orient")
+        keep_pl, pl_ref = _planes_ref(planes)
+        _check(lib().mjx_decode_batch_planes(ctx.h, arr, lens, n, ctypes.byref(o), int(threads), pl_ref, st, ctypes.byref(h)), "mjx_decode_batch_planes")
+        return Batch(ctx, _handle=h), list(st)[:n]
     if orient is not None:
         keep, ref = _out_ref(output)
         keep_rs, rs_ref = _rs_ref(resize)
@@ -1000,6 +1117,48 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
     else:
         rs = None
     batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt, resize=rs, orient=orient, pixels=pixels)
+    batch.close()
+    return status
+
+
+def decode_planes_into(ctx, datas, y, cb=None, cr=None, cbcr=None, scale=1, rois=None, mean=None, std=None, threads=0, device_destuff=None, pixels=None):
+    """Decodes the files' component planes straight into torch tensors on the context's device: decode_planes_into(ctx, datas, y, cb,
+    cr) with y N x Hy x Wy, cb and cr N x Hc x Wc, or decode_planes_into(ctx, datas, y, cbcr=t) with t N x Hc x Wc x 2 (NV12's second
+    plane); one-component files take y alone.  All pictures of the call have one size and layout; tensors are of one dtype (uint8,
+    float16, float32); the innermost dimension is dense, rows may be padded and the pictures of a tensor must not overlap.  Float
+    tensors take (v / 255 - mean) / std per COMPONENT.  torch's current stream is synchronised before the call and the planes are
+    complete when this returns.  -> the per-picture statuses."""
+    import torch
+    n = len(datas)
+    if cbcr is not None and (cb is not None or cr is not None):
+        raise MjxError(ERR_INVALID_ARG, "cb and cr, or cbcr")
+    tensors = [y] + ([cbcr] if cbcr is not None else [t for t in (cb, cr) if t is not None])
+    if (cb is None) != (cr is None):
+        raise MjxError(ERR_INVALID_ARG, "cb and cr go together")
+    names = {torch.uint8: DTYPE_U8, torch.float16: DTYPE_F16, torch.float32: DTYPE_F32}
+    per_plane, sizes = [], []
+    for k, t in enumerate(tensors):
+        pair = cbcr is not None and k == 1
+        if not isinstance(t, torch.Tensor) or t.dim() != (4 if pair else 3) or t.shape[0] != n or (pair and t.shape[3] != 2):
+            raise MjxError(ERR_INVALID_ARG, "plane %d: a tensor of %d planes" % (k, n))
+        if t.dtype not in names or t.dtype != y.dtype:
+            raise MjxError(ERR_INVALID_ARG, "plane %d: dtype %s" % (k, t.dtype))
+        if t.device.type != "cuda" or t.device.index != ctx.device:
+            raise MjxError(ERR_INVALID_ARG, "plane %d lies on %s, not on the context's device %d" % (k, t.device, ctx.device))
+        st = t.stride()
+        h, w = int(t.shape[1]), int(t.shape[2])
+        row = 2 * w if pair else w
+        ok = (st[3] == 1 and st[2] == 2) if pair else st[2] == 1
+        if not ok or st[1] < row or (n > 1 and st[0] < (h - 1) * st[1] + row):
+            raise MjxError(ERR_INVALID_ARG, "plane %d: stride %s -- the innermost dimension is dense, rows at least a row apart, pictures apart" % (k, tuple(st)))
+        per_plane.append((t.data_ptr(), st[0] * t.element_size(), st[1]))
+        sizes.append((w, h))
+    if cbcr is not None:
+        sizes.append(sizes[1])
+    dst = [([(ptr + i * step, pitch) for ptr, step, pitch in per_plane], sizes) for i in range(n)]
+    fmt = Planes(names[y.dtype], interleave=cbcr is not None, mean=mean, std=std, dst=dst)
+    torch.cuda.current_stream(y.device).synchronize()
+    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, planes=fmt)
     batch.close()
     return status
 
@@ -1144,6 +1303,15 @@ def orient_plan(data, code, resize=None, roi=None, scale=1):
     scan = ParsedScan(data)
     try:
         return scan.orient_plan(code, resize=resize, roi=roi, scale=scale)
+    finally:
+        scan.close()
+
+
+def planes_layout(data, planes, i=0, roi=None, scale=1, pixels=None):
+    """Host only: the planes a decode of this file as input i with this Planes would write -> see ParsedScan.planes_layout."""
+    scan = ParsedScan(data)
+    try:
+        return scan.planes_layout(planes, i=i, roi=roi, scale=scale, pixels=pixels)
     finally:
         scan.close()
 

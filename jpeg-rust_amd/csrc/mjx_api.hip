@@ -131,6 +131,11 @@ struct ImageInfo {
     bool out_on = false, cropped = false;
     uint32_t out_dtype = 0, out_planar = 0, out_bgr = 0, out_channels = 3;
     uint64_t out_dev = 0, out_row_pitch = 0, out_plane_pitch = 0, out_span = 0;
+    // YCbCr output (mjx_planes): the picture's planes as the planner laid them out (ImagePlan::ycc_*); out_on is set as well, so that
+    // every accessor of a picture with an output description treats the picture as one
+    bool ycc_on = false;
+    uint32_t ycc_il = 0, ycc_w[3] = {0, 0, 0}, ycc_h[3] = {0, 0, 0};
+    uint64_t ycc_dev[3] = {0, 0, 0}, ycc_off[3] = {0, 0, 0}, ycc_pitch[3] = {0, 0, 0};
     // resize on the device: width x height above is the target; the intermediate is src_w x src_h (the rectangle at roi_x, roi_y of
     // the full_w x full_h picture at `scale`) and lies at DevImage::rgb_off; rgb_off here is the output's place in the pool
     bool rs_on = false;
@@ -170,6 +175,7 @@ struct Chunk {
     uint32_t max_dc_roi_wgs = 0;   // ... and of k_dc_color_roi for its largest rectangle
     uint32_t max_dc_out_wgs = 0;   // ... and of k_dc_color_out for its largest picture with an output description
     uint32_t max_dc_luma_wgs = 0;  // ... and of k_dc_color_luma for its largest luminance picture
+    uint32_t max_dc_ycc_wgs = 0;   // ... and of k_dc_color_ycc for the picture with the most plane samples
     uint32_t max_lj_luma_tiles = 0;                   // luminance pictures: workgroups of k_upsample_luma, k_orient_luma and k_resize_luma (0: none)
     uint32_t max_or_luma_tiles = 0, max_rso_luma_tiles = 0;
     uint32_t max_or_tiles = 0, max_rso_tiles = 0;     // orientation on the device: workgroups of k_orient_out for the chunk's largest oriented picture, of k_resize_orient for its largest target (0: none)
@@ -481,7 +487,7 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
     d.valid = 1;
     d.nseg = p.nseg;
     d.restart_mcus = p.restart_mcus;
-    d.mode = (!p.lj && p.ncomp == 3 && p.h[0] == 2 && p.v[0] == 2 && p.h[1] == 1 && p.v[1] == 1 && p.h[2] == 1 && p.v[2] == 1) ? 1 : 0;
+    d.mode = (!p.lj && !p.ycc_on && p.ncomp == 3 && p.h[0] == 2 && p.v[0] == 2 && p.h[1] == 1 && p.v[1] == 1 && p.h[2] == 1 && p.v[2] == 1) ? 1 : 0;
     d.scale = p.scale;
     d.out_w = p.out_w;
     d.out_h = p.out_h;
@@ -529,6 +535,15 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
             d.mode = d.mode % kRoiMode + kLumaMode;
             d.rs_on = 0;
             d.or_on = !p.rs_on ? 0u : p.or_copy ? 3u : 4u;
+        }
+    }
+    // YCbCr output: the forms that write the component planes as the picture (4:2:0 takes the generic tile, above)
+    if (p.ycc_on) {
+        d.mode = d.mode % kRoiMode + kYccMode;
+        d.ycc_on = 1; d.ycc_il = p.ycc_il; d.ycc_round = p.ycc_round;
+        for (uint32_t c = 0; c < 3; c++) {
+            d.ycc_x0[c] = p.ycc_x0[c]; d.ycc_y0[c] = p.ycc_y0[c]; d.ycc_w[c] = p.ycc_w[c]; d.ycc_h[c] = p.ycc_h[c];
+            d.ycc_dev[c] = p.ycc_dev[c]; d.ycc_off[c] = p.ycc_off[c]; d.ycc_pitch[c] = p.ycc_pitch[c];
         }
     }
     // libjpeg's pixels: one plane form for every sampling layout (4:2:0 takes the generic tile), whatever the picture leaves as --
@@ -652,6 +667,11 @@ void plan_chunks(mjx_batch *b)
                 if (d.nseg > 1) c.max_restart_segs = std::max(c.max_restart_segs, d.nseg);
                 if (d.mode == 5) c.max_dc_wgs = std::max<uint32_t>(c.max_dc_wgs, uint32_t((uint64_t(d.out_w) * d.out_h + 255) / 256));
                 if (d.mode == 5 + kOutMode) c.max_dc_out_wgs = std::max<uint32_t>(c.max_dc_out_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
+                if (d.mode == 5 + kYccMode) {
+                    uint64_t samples = 0;
+                    for (uint32_t q = 0; q < d.ncomp; q++) samples += uint64_t(d.ycc_w[q]) * d.ycc_h[q];
+                    c.max_dc_ycc_wgs = std::max<uint32_t>(c.max_dc_ycc_wgs, uint32_t((samples + 255) / 256));
+                }
                 if (d.mode == 5 + kLumaMode) c.max_dc_luma_wgs = std::max<uint32_t>(c.max_dc_luma_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
                 if (d.or_on == 3 && d.role != 1) c.max_or_luma_tiles = std::max<uint32_t>(c.max_or_luma_tiles, orient_tiles(d.rs_w, d.rs_h));
                 if (d.or_on == 4 && d.role != 1) c.max_rso_luma_tiles = std::max<uint32_t>(c.max_rso_luma_tiles, resize_tiles(d.rs_w, d.rs_h));
@@ -978,6 +998,7 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
         if (c.max_dc_roi_wgs) launch_dc_color(sp, c.max_dc_roi_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true);
         if (c.max_dc_out_wgs) launch_dc_color(sp, c.max_dc_out_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true, true);
         if (c.max_dc_luma_wgs) launch_dc_color_luma(sp, c.max_dc_luma_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags);
+        if (c.max_dc_ycc_wgs) launch_dc_color_ycc(sp, c.max_dc_ycc_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags);
         prof_end(b, sp);
         if (c.max_lj_tiles) {          // libjpeg's pixels: the chunk's component planes -> its pictures (or the intermediates of the passes below)
             prof_begin(b, MJX_K_RESIZE, sp);
@@ -1364,6 +1385,15 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 inf.rgb_bytes = uint64_t(p.rs_w) * p.rs_h * p.out_channels;
             }
             inf.rgb_bytes *= p.out_dtype == MJX_DTYPE_U8 ? 1u : p.out_dtype == MJX_DTYPE_F16 ? 2u : 4u;      // (the bytes written)
+            if (p.ycc_on) {                                                  // (component planes: the samples of every plane)
+                inf.ycc_on = true;
+                inf.ycc_il = p.ycc_il;
+                inf.rgb_bytes = p.ycc_written;
+                for (uint32_t c = 0; c < 3; c++) {
+                    inf.ycc_w[c] = p.ycc_w[c]; inf.ycc_h[c] = p.ycc_h[c];
+                    inf.ycc_dev[c] = p.ycc_dev[c]; inf.ycc_off[c] = p.ycc_off[c]; inf.ycc_pitch[c] = p.ycc_pitch[c];
+                }
+            }
             rgb_pool += p.out_dev ? 0 : align_up(inf.out_span, 256);
         } else
         rgb_pool += align_up(inf.rgb_bytes, 256);
@@ -1910,15 +1940,16 @@ static uint32_t orient_code(const mjx_orient *orient, size_t i, const uint8_t *j
 // an orientation always comes with an output description: without one, interleaved u8 R,G,B, library-owned (as a resize)
 static const mjx_output kPackedOutput = {MJX_DTYPE_U8, 0, 0, {1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}, nullptr, 0};
 
-extern "C" int mjx_batch_create_orient(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_output *fmt,
-                                       const mjx_resize *rs, const mjx_orient *orient, mjx_batch **out, int *status)
+// (pl: the call's plane description -- mjx_batch_create_planes, which has no output description, resize or orientation -- or null)
+static int batch_create_impl(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_output *fmt,
+                             const mjx_resize *rs, const mjx_orient *orient, const mjx_planes *pl, mjx_batch **out, int *status)
 {
     return guarded([&]() -> int {
     if (!ctx || !out || (!descs && n)) return MJX_ERR_INVALID_ARG;
     *out = nullptr;
     mjx_opts o{};
     if (opts) o = *opts;
-    if (!rois_fit(o, n) || !output_fits(fmt, n) || !orient_fits(orient, n)) return MJX_ERR_INVALID_ARG;
+    if (!rois_fit(o, n) || !output_fits(fmt, n) || !orient_fits(orient, n) || (pl && !planes_fit(pl, n))) return MJX_ERR_INVALID_ARG;
     if (orient && orient->from_exif) return MJX_ERR_INVALID_ARG;       // (descriptors carry no file bytes: mjx_exif_orientation, then `extra`)
     if (orient && !fmt) fmt = &kPackedOutput;
     const mjx_scan_desc *dd = descs;
@@ -1928,6 +1959,7 @@ extern "C" int mjx_batch_create_orient(mjx_ctx *ctx, const mjx_scan_desc *descs,
     const auto tp0 = std::chrono::steady_clock::now();
     for (size_t i = 0; i < n; i++) {
         plan_input_for(dd[i], opts_for_input(o, n, i), fmt, rs, i, plans, orient_code(orient, i, nullptr, 0));      // (rois[i], dst[i] and extra[i] go with input i: a multi-scan file's picture plan takes them)
+        if (pl) plan_planes_of_input(plans, pl, i);
         plan_of[i] = plans.size() - 1;
     }
     if (std::getenv("MJX_TIMING"))
@@ -1935,6 +1967,53 @@ extern "C" int mjx_batch_create_orient(mjx_ctx *ctx, const mjx_scan_desc *descs,
     (void)plan_of;
     if (rs && rs->auto_scale) o.scale_denom = 1;                // (the pictures' own scales are in their plans)
     return build_batch(ctx, plans, o, nullptr, 1, out, status);
+    });
+}
+
+extern "C" int mjx_batch_create_orient(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_output *fmt,
+                                       const mjx_resize *rs, const mjx_orient *orient, mjx_batch **out, int *status)
+{
+    return batch_create_impl(ctx, descs, n, opts, fmt, rs, orient, nullptr, out, status);
+}
+
+// mjx_batch_create with a plane description (mjx_planes): the pictures leave as their component planes.
+extern "C" int mjx_batch_create_planes(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_planes *pl,
+                                       mjx_batch **out, int *status)
+{
+    if (!pl) { if (out) *out = nullptr; return MJX_ERR_INVALID_ARG; }
+    return batch_create_impl(ctx, descs, n, opts, nullptr, nullptr, nullptr, pl, out, status);
+}
+
+// Host-only: the planes a decode of this picture as input i would write -- plan_planes' own numbers.
+extern "C" int mjx_planes_layout(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_planes *pl, size_t i, mjx_plane_layout *layout,
+                                 uint32_t *nplanes, size_t *bytes)
+{
+    return guarded([&]() -> int {
+    if (!desc || !pl) return MJX_ERR_INVALID_ARG;
+    mjx_opts o{};
+    if (opts) o = *opts;
+    if (!rois_fit(o, 1)) return MJX_ERR_INVALID_ARG;
+    if (pl->dst ? i >= pl->n_dst : pl->n_dst != 0) return MJX_ERR_INVALID_ARG;
+    std::vector<ImagePlan> plans;
+    plan_input(*desc, o, plans);
+    plan_planes_of_input(plans, pl, i);
+    const ImagePlan &p = plans.back();
+    if (p.status != MJX_OK) return p.status;
+    const uint64_t esz = p.out_dtype == MJX_DTYPE_U8 ? 1u : p.out_dtype == MJX_DTYPE_F16 ? 2u : 4u;
+    const uint32_t np = p.ycc_il ? 2u : p.ncomp;
+    uint64_t total = 0;
+    if (layout) std::memset(layout, 0, sizeof *layout);
+    for (uint32_t c = 0; c < p.ncomp; c++) {
+        if (layout) {
+            layout->width[c] = p.ycc_w[c]; layout->height[c] = p.ycc_h[c];
+            layout->row_pitch[c] = c < np ? p.ycc_pitch[c] : 0;
+            layout->dev[c] = reinterpret_cast<void *>(uintptr_t(c < np ? p.ycc_dev[c] : 0));
+        }
+        if (c < np) total += ((uint64_t(p.ycc_h[c]) - 1) * p.ycc_pitch[c] + uint64_t(p.ycc_w[c]) * (p.ycc_il && c == 1 ? 2u : 1u)) * esz;
+    }
+    if (nplanes) *nplanes = np;
+    if (bytes) *bytes = size_t(total);
+    return MJX_OK;
     });
 }
 
@@ -2179,6 +2258,16 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
             p.orient = src->himages[k].or_on ? src->himages[k].orient : 1u;
             p.or_copy = src->himages[k].or_on == 1 || src->himages[k].or_on == 3;
             p.rs_w = src->himages[k].rs_w; p.rs_h = src->himages[k].rs_h; p.rs_aa = src->himages[k].rs_aa;
+            if (fi.ycc_on) {                                                          // (... and its plane description)
+                const DevImage &sd = src->himages[k];
+                p.ycc_on = true;
+                p.ycc_il = sd.ycc_il; p.ycc_round = sd.ycc_round;
+                p.ycc_written = fi.rgb_bytes;
+                for (uint32_t c = 0; c < 3; c++) {
+                    p.ycc_x0[c] = sd.ycc_x0[c]; p.ycc_y0[c] = sd.ycc_y0[c]; p.ycc_w[c] = sd.ycc_w[c]; p.ycc_h[c] = sd.ycc_h[c];
+                    p.ycc_dev[c] = 0; p.ycc_off[c] = sd.ycc_off[c]; p.ycc_pitch[c] = sd.ycc_pitch[c];
+                }
+            }
         }
         p.roi_x = d.roi_x; p.roi_y = d.roi_y; p.roi_w = d.roi_w; p.roi_h = d.roi_h;
         p.roi_mr0 = d.roi_mr0; p.roi_mr1 = d.roi_mr1; p.roi_mc0 = d.roi_mc0; p.roi_mc1 = d.roi_mc1;
@@ -2537,6 +2626,32 @@ extern "C" int mjx_batch_output_info(const mjx_batch *b, size_t iu, mjx_dst *lay
     return MJX_OK;
 }
 
+// The planes of picture i of a batch with a plane description: how many there are (1, 3, or 2 with interleaved chroma), where they
+// lie, their pitches and sizes; a batch without one: MJX_ERR_INVALID_ARG.
+extern "C" int mjx_batch_plane_info(const mjx_batch *b, size_t iu, uint32_t *nplanes, mjx_plane_layout *layout, uint8_t *dtype, uint8_t *interleave)
+{
+    if (b && !b->parts.empty()) { mjx_batch *pb; size_t pi; return route(b, iu, pb, pi) ? mjx_batch_plane_info(pb, pi, nplanes, layout, dtype, interleave) : MJX_ERR_INVALID_ARG; }
+    size_t i;
+    if (!visible_index(b, iu, i)) return MJX_ERR_INVALID_ARG;
+    const ImageInfo &inf = b->info[i];
+    if (layout) std::memset(layout, 0, sizeof *layout);
+    if (nplanes) *nplanes = 0;
+    if (inf.status != MJX_OK) return inf.status;
+    if (!inf.ycc_on) return MJX_ERR_INVALID_ARG;
+    const uint32_t nc = b->himages[i].ncomp, np = inf.ycc_il ? 2u : nc;
+    if (nplanes) *nplanes = np;
+    if (dtype) *dtype = uint8_t(inf.out_dtype);
+    if (interleave) *interleave = uint8_t(inf.ycc_il);
+    if (layout)
+        for (uint32_t c = 0; c < nc; c++) {
+            layout->width[c] = inf.ycc_w[c]; layout->height[c] = inf.ycc_h[c];
+            if (c >= np) continue;
+            layout->row_pitch[c] = inf.ycc_pitch[c];
+            layout->dev[c] = inf.ycc_dev[c] ? reinterpret_cast<void *>(uintptr_t(inf.ycc_dev[c])) : b->d_rgb + inf.rgb_off + inf.ycc_off[c];
+        }
+    return MJX_OK;
+}
+
 extern "C" int mjx_batch_output_channels(mjx_batch *b, size_t iu, uint8_t *channels)
 {
     if (b && !b->parts.empty()) { mjx_batch *pb; size_t pi; return route(b, iu, pb, pi) ? mjx_batch_output_channels(pb, pi, channels) : MJX_ERR_INVALID_ARG; }
@@ -2601,6 +2716,23 @@ extern "C" int mjx_batch_copy_output(mjx_batch *b, size_t iu, void *host, size_t
     const ImageInfo &inf = b->info[i];
     if (inf.status != MJX_OK) return inf.status;
     if (!inf.out_on || inf.out_dev || cap_bytes < inf.out_span) return MJX_ERR_INVALID_ARG;
+    HIPOK(hipSetDevice(b->ctx->device));
+    { const int rcs = sync_streams(b); if (rcs != MJX_OK) return rcs; }
+    return copy_from_device(b->ctx, host, b->d_rgb + inf.rgb_off, size_t(inf.out_span));
+    });
+}
+
+// Copy picture i's library-owned planes to host memory, dense, back to back (what mjx_planes_layout's *bytes counts); cap_bytes smaller
+// than that, caller-owned planes or a batch without a plane description: MJX_ERR_INVALID_ARG.
+extern "C" int mjx_batch_copy_planes(mjx_batch *b, size_t iu, void *host, size_t cap_bytes)
+{
+    if (b && !b->parts.empty()) { mjx_batch *pb; size_t pi; return route(b, iu, pb, pi) ? mjx_batch_copy_planes(pb, pi, host, cap_bytes) : MJX_ERR_INVALID_ARG; }
+    return guarded([&]() -> int {
+    size_t i;
+    if (!visible_index(b, iu, i) || !host) return MJX_ERR_INVALID_ARG;
+    const ImageInfo &inf = b->info[i];
+    if (inf.status != MJX_OK) return inf.status;
+    if (!inf.ycc_on || inf.out_dev || cap_bytes < inf.out_span) return MJX_ERR_INVALID_ARG;
     HIPOK(hipSetDevice(b->ctx->device));
     { const int rcs = sync_streams(b); if (rcs != MJX_OK) return rcs; }
     return copy_from_device(b->ctx, host, b->d_rgb + inf.rgb_off, size_t(inf.out_span));
@@ -2910,7 +3042,7 @@ unsigned usable_processors()
 // (fmt: the call's output description, or null -- mjx_decode_batch_out; dst[i] goes with file i wherever its group falls)
 static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
                              unsigned threads, const mjx_output *fmt, const mjx_resize *rs, const mjx_orient *orient, uint8_t **rgb_dev, int *status,
-                             mjx_batch **out)
+                             mjx_batch **out, const mjx_planes *pl = nullptr /* mjx_decode_batch_planes: the plane description; dst[i] goes with file i */)
 {
     return guarded([&]() -> int {
     if (!ctx || !out || ((!jpegs || !lens) && n)) return MJX_ERR_INVALID_ARG;
@@ -2918,7 +3050,7 @@ static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const si
     std::lock_guard<std::mutex> serial(ctx->batch_mu);        // the pinned arena is shared state of the context
     mjx_opts o{};
     if (opts) o = *opts;
-    if (!rois_fit(o, n) || !output_fits(fmt, n) || !orient_fits(orient, n)) return MJX_ERR_INVALID_ARG;
+    if (!rois_fit(o, n) || !output_fits(fmt, n) || !orient_fits(orient, n) || (pl && !planes_fit(pl, n))) return MJX_ERR_INVALID_ARG;
     if (orient && !fmt) fmt = &kPackedOutput;
     const bool timing = std::getenv("MJX_TIMING") != nullptr;
     const auto t_begin = std::chrono::steady_clock::now();
@@ -3051,6 +3183,7 @@ static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const si
             try {
                 // geometry + decode tables, also on the worker (rois[i], dst[i], the resize and the orientation -- the file's tag is read here -- go with file i)
                 plan_input_for(descs[i], opts_for_input(o, n, i), fmt, rs, i, file_plans[i], orient_code(orient, i, jpegs[i], lens[i]));
+                if (pl) plan_planes_of_input(file_plans[i], pl, i);
             } catch (...) {
                 file_plans[i].clear();
             }
@@ -3153,6 +3286,15 @@ extern "C" int mjx_decode_batch_orient(mjx_ctx *ctx, const uint8_t *const *jpegs
 {
     if (!ctx) { if (out) *out = nullptr; return MJX_ERR_DEVICE; }      // (as mjx_decode_batch_out: no device, no CPU path)
     return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, fmt, rs, orient, nullptr, status, out);
+}
+
+// mjx_decode_batch with a plane description; dst[i] follows file i through the groups of the pipelined call, as in mjx_decode_batch_out.
+extern "C" int mjx_decode_batch_planes(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
+                                       unsigned threads, const mjx_planes *pl, int *status, mjx_batch **out)
+{
+    if (!ctx) { if (out) *out = nullptr; return MJX_ERR_DEVICE; }      // (as mjx_decode_batch_out: no device, no CPU path)
+    if (!pl) { if (out) *out = nullptr; return MJX_ERR_INVALID_ARG; }
+    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, nullptr, nullptr, nullptr, nullptr, status, out, pl);
 }
 
 // ---- one-shot surface ------------------------------------------------------------------------------

@@ -4,7 +4,8 @@
 // fancy chroma upsampling and libjpeg's integer colour tables, mjx_opts.pixels = MJX_PIXELS_LIBJPEG)
 // Writes the same ASCII P3 file ("P3\n{w} {h}\n255\n" then "r g b\n" per pixel, main.rs:35-39), buffered; --p6 writes
 // binary PPM instead.  --luma: the luminance picture (MJX_OUTPUT_CHANNELS = 1) through the batch API, written as binary PGM (P5); chroma
-// is never transformed.  Exit code = MJX_* status.
+// is never transformed.  --ycc: the component planes at their own sampling (mjx_planes), written back to back as one raw file -- Y,
+// Cb, Cr: I420 order for a 4:2:0 file --; --nv12: Y, then Cb and Cr interleaved.  Both print the planes' sizes.  Exit code = MJX_* status.
 #include "jpeg.hpp"
 
 #include <cstdio>
@@ -45,18 +46,58 @@ static int write_luma(const std::vector<uint8_t> &bytes, const mjx_opts &opts, c
     return MJX_OK;
 }
 
+// --ycc / --nv12: the one file through mjx_decode_batch_planes, library-owned uint8 planes, copied out dense
+static int write_planes(const std::vector<uint8_t> &bytes, const mjx_opts &opts, const char *path, bool nv12)
+{
+    mjx_ctx *ctx = nullptr;
+    int rc = mjx_ctx_create(0, &ctx);
+    if (rc != MJX_OK) { std::fprintf(stderr, "decode failed: %s (%d)\n", mjx_strerror(rc), rc); return rc; }
+    mjx_planes fmt{};
+    fmt.dtype = MJX_DTYPE_U8;
+    fmt.interleave_chroma = nv12 ? 1 : 0;
+    const uint8_t *ptr = bytes.data();
+    const size_t len = bytes.size();
+    int status = MJX_OK;
+    mjx_batch *b = nullptr;
+    rc = mjx_decode_batch_planes(ctx, &ptr, &len, 1, &opts, 1, &fmt, &status, &b);
+    if (rc == MJX_OK) rc = status;
+    uint32_t nplanes = 0;
+    uint8_t il = 0;
+    mjx_plane_layout lay{};
+    std::vector<uint8_t> pix;
+    if (rc == MJX_OK) rc = mjx_batch_plane_info(b, 0, &nplanes, &lay, nullptr, &il);
+    if (rc == MJX_OK) {
+        size_t total = 0;
+        for (uint32_t c = 0; c < nplanes; c++) total += size_t(lay.width[c]) * lay.height[c] * (il && c == 1 ? 2u : 1u);
+        pix.resize(total);
+        rc = mjx_batch_copy_planes(b, 0, pix.data(), pix.size());
+    }
+    if (b) mjx_batch_free(b);
+    mjx_ctx_destroy(ctx);
+    if (rc != MJX_OK) { std::fprintf(stderr, "decode failed: %s (%d)\n", mjx_strerror(rc), rc); return rc; }
+    std::FILE *o = std::fopen(path, "wb");
+    if (!o) { std::perror(path); return MJX_ERR_INVALID_ARG; }
+    std::fwrite(pix.data(), 1, pix.size(), o);
+    std::fclose(o);
+    for (uint32_t c = 0; c < nplanes; c++)
+        std::printf("plane %u: %ux%u%s\n", c, lay.width[c], lay.height[c], il && c == 1 ? " pairs Cb,Cr" : "");
+    return MJX_OK;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s <input.jpeg> <output.ppm> [--p6] [--strict] [--ref-compat] [--scale N] [--crop X,Y,W,H] [--libjpeg-pixels] [--luma]\n", argv[0]);   // main.rs:26-28 expect()
+        std::fprintf(stderr, "usage: %s <input.jpeg> <output.ppm> [--p6] [--strict] [--ref-compat] [--scale N] [--crop X,Y,W,H] [--libjpeg-pixels] [--luma] [--ycc] [--nv12]\n", argv[0]);   // main.rs:26-28 expect()
         return MJX_ERR_INVALID_ARG;
     }
-    bool p6 = false, luma = false;
+    bool p6 = false, luma = false, ycc = false, nv12 = false;
     mjx_opts opts{};
     mjx_rect crop{0, 0, 0, 0};
     for (int i = 3; i < argc; i++) {
         if (!std::strcmp(argv[i], "--p6")) p6 = true;
         else if (!std::strcmp(argv[i], "--luma")) luma = true;
+        else if (!std::strcmp(argv[i], "--ycc")) ycc = true;
+        else if (!std::strcmp(argv[i], "--nv12")) nv12 = true;
         else if (!std::strcmp(argv[i], "--strict")) opts.strict_ref = 1;
         else if (!std::strcmp(argv[i], "--ref-compat")) opts.layout = MJX_LAYOUT_REF_COMPAT;
         else if (!std::strcmp(argv[i], "--libjpeg-pixels")) opts.pixels = MJX_PIXELS_LIBJPEG;
@@ -81,6 +122,7 @@ int main(int argc, char **argv)
     while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) bytes.insert(bytes.end(), buf, buf + n);
     std::fclose(f);
     if (luma) return write_luma(bytes, opts, argv[2]);
+    if (ycc || nv12) return write_planes(bytes, opts, argv[2], nv12);
     jpeg::JPEGImage image;
     const jpeg::JPEGImage::Result r = jpeg::JPEGImage::parse(bytes, image, &opts);   // main.rs:31
     if (!r.ok()) { std::fprintf(stderr, "decode failed: %s (%d)\n", r.message.c_str(), r.code); return r.code; }

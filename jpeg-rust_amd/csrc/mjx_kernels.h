@@ -136,11 +136,37 @@ struct DevImage {
     // rgb_off, and the three-channel passes leave the picture alone.  With libjpeg's pixels lj_on stays 0 and lj_luma = 1: stage B's
     // plane form as it is, k_upsample_luma reads component 0's plane.
     uint32_t out_ch, lj_luma;
+    // YCbCr output (mjx_planes; ycc_on, mode kYccMode + m): the picture leaves as its component planes at their own sampling.  Plane c
+    // is the ycc_w[c] x ycc_h[c] samples from (ycc_x0[c], ycc_y0[c]) of component c's plane at the picture's scale (plane_span of the
+    // rectangle roi_*), rows of ycc_pitch[c] elements of out_dtype at ycc_dev[c] (caller-owned memory) or, ycc_dev[c] == 0, at byte
+    // rgb_off + ycc_off[c] of the batch's pool; a float element is fmaf(float(u8), out_scale[c], out_bias[c]), c the COMPONENT.
+    // ycc_il = 1: Cb and Cr share plane 1, element (X, Y) as the pair Cb, Cr at Y ycc_pitch[1] + 2 X (ycc_dev[2] / ycc_off[2] are
+    // not used).  ycc_round = 1 (libjpeg's pixels): the sample is rounded, not truncated.
+    uint32_t ycc_on, ycc_il, ycc_round;
+    uint32_t ycc_x0[3], ycc_y0[3], ycc_w[3], ycc_h[3];
+    uint64_t ycc_dev[3], ycc_off[3], ycc_pitch[3];
 };
 constexpr uint32_t kRoiMode = 8;
 constexpr uint32_t kOutMode = 16;      // + m (0, 1, 3, 4; 5: k_dc_color_out): the forms for pictures with an output description
 constexpr uint32_t kPlaneMode = 24;    // + 0: the form that writes component planes (libjpeg's pixels; 4:2:0 takes the generic form too)
 constexpr uint32_t kLumaMode = 32;     // + m (0, 1, 3, 4; 5: k_dc_color_luma): the forms for luminance pictures -- a bit each in a 64-bit mode mask
+constexpr uint32_t kYccMode = 40;      // + m (0, 3, 4; 5: k_dc_color_ycc): the forms that write component planes as the picture (4:2:0 takes the generic form)
+
+// YCbCr output: the samples of component c -- factors (hc, vc) of maxima (hmax, vmax) -- that the rectangle (x, y, w, h) of the
+// out_w x out_h picture covers: columns floor(x hc / hmax) .. ceil((x + w) hc / hmax), rows likewise.  These are the samples the
+// packed decode of the rectangle reads from the component (box replication: pixel X takes sample floor(X hc / hmax)); the whole
+// picture's plane is ceil(out_w hc / hmax) x ceil(out_h vc / vmax).  The planner (plan_planes) and k_dc_color_ycc run this routine;
+// stage B's plane forms clip to what the planner put into DevImage::ycc_* with it.
+struct PlaneSpan { uint32_t x0, y0, w, h; };
+MJX_HD PlaneSpan plane_span(uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t hc, uint32_t vc, uint32_t hmax, uint32_t vmax)
+{
+    PlaneSpan s;
+    s.x0 = x * hc / hmax;
+    s.y0 = y * vc / vmax;
+    s.w = ((x + w) * hc + hmax - 1u) / hmax - s.x0;
+    s.h = ((y + h) * vc + vmax - 1u) / vmax - s.y0;
+    return s;
+}
 
 // Region-of-interest decode: does tile t -- T consecutive MCUs in raster order, so it may wrap into the next MCU row -- hold an MCU
 // of the MCU rows r0 .. r1 and the MCU columns c0 .. c1?  Arithmetic on uniform values only: stage B decides per tile without a
@@ -730,7 +756,8 @@ void launch_dc_scan(hipStream_t st, uint32_t max_segs, uint32_t nimg, const DevI
                     bool fault = false /* test knob: a workgroup never publishes */);
 // (max_tiles: the chunk's largest count of tiles a picture's workgroups walk -- DevImage::roi_ntiles; mode_mask bits kRoiMode + m:
 // pictures with a rectangle, which take the forms k_idct_color<kRoiMode + m, ...>; bits kOutMode + m: pictures with an output
-// description, k_idct_color<kOutMode + m, ...>; bits kLumaMode + m: luminance pictures, k_idct_color<kLumaMode + m, ...>)
+// description, k_idct_color<kOutMode + m, ...>; bits kLumaMode + m: luminance pictures, k_idct_color<kLumaMode + m, ...>; bits
+// kYccMode + m: pictures that leave as component planes, k_idct_color<kYccMode + m, ...>)
 void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t lds, const DevImage *images,
                        const uint32_t *entries, const uint32_t *tile_eoff, const int32_t *dcbuf, const float *qmult,
                        uint8_t *rgb, uint64_t mode_mask, unsigned long long *planes, const uint32_t *img_flags,
@@ -751,6 +778,9 @@ void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, cons
 // ... luminance pictures (mode 5 + kLumaMode): one lane per pixel of the rectangle, component 0's DC value alone
 void launch_dc_color_luma(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
                           const float *qmult, uint8_t *rgb, const uint32_t *img_flags);
+// ... YCbCr output (mode 5 + kYccMode): one lane per sample of each plane, the components' DC values alone
+void launch_dc_color_ycc(hipStream_t st, uint32_t max_sample_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
+                         const float *qmult, uint8_t *rgb, const uint32_t *img_flags);
 // resize on the device: one workgroup per tile of the target (resize_tiles) and picture with DevImage::rs_on, behind stage B
 void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
 // orientation on the device, behind stage B like the resize: one workgroup per tile of D (orient_tiles) and picture with or_on == 1

@@ -3573,6 +3573,168 @@ __device__ __forceinline__ void planes_store(const DevImage &im, const float *ti
     }
 }
 
+// ---- YCbCr output (mjx_planes; k_idct_color<kYccMode + m, ...>; DevImage::ycc_*) -------------------------------------------------
+// One element of a plane: byte value `u` through the dtype's table (DT: MJX_DTYPE_*, a template argument -- chosen once per tile).
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+// A plane's address comes out of the descriptor as an integer, so the compiler cannot know its address space and would store through
+// FLAT instructions: those count on lgkmcnt as well as vmcnt, and every wait for an LDS read behind them -- the next row's samples --
+// would wait for the stores too.  The planes lie in device memory: say so, and the stores are global_store, counted on vmcnt alone.
+template <typename T>
+__device__ __forceinline__ __attribute__((address_space(1))) T *ycc_global(uint8_t *d)
+{
+    return (__attribute__((address_space(1))) T *)(uintptr_t(d));
+}
+template <int DT>
+__device__ __forceinline__ void ycc_store1(uint8_t *d, uint32_t u, float sc, float bi)
+{
+    if constexpr (DT == 0) __builtin_nontemporal_store(uint8_t(u), ycc_global<uint8_t>(d));
+    else if constexpr (DT == 1) __builtin_nontemporal_store(uint16_t(half_bits(__builtin_fmaf(float(u), sc, bi))), ycc_global<uint16_t>(d));
+    else __builtin_nontemporal_store(__builtin_fmaf(float(u), sc, bi), ycc_global<float>(d));
+}
+// CNT consecutive elements of one plane row -- byte values u[0 .. CNT), of which [k0, k1) lie inside the plane; d: where element k0 goes.
+// Even elements take (sc0, bi0), odd ones (sc1, bi1): the two are one component's, or Cb's and Cr's of an interleaved chroma plane.
+// A whole run at a 4-byte aligned address leaves in stores of up to 16 bytes, a cut or misaligned one as predicated elements; all
+// register indices are constants.  Nothing is written outside [k0, k1).
+template <int DT, int CNT>
+__device__ __forceinline__ void ycc_store_run(uint8_t *d, const uint32_t (&u)[CNT], uint32_t k0, uint32_t k1, float sc0, float bi0, float sc1, float bi1)
+{
+    constexpr uint32_t ESZ = DT == 0 ? 1u : DT == 1 ? 2u : 4u;
+    constexpr uint32_t NW = CNT * ESZ / 4u;                // dwords of a whole run (0: two bytes)
+    if (k0 == 0u && k1 == uint32_t(CNT) && (uintptr_t(d) & (NW ? 3u : 1u)) == 0) {
+        if constexpr (NW == 0) {
+            __builtin_nontemporal_store(uint16_t(u[0] | (u[1] << 8)), ycc_global<uint16_t>(d));
+        } else {
+            uint32_t w[NW];
+#pragma unroll
+            for (uint32_t j = 0; j < NW; j++) {
+                if constexpr (DT == 0) w[j] = u[4 * j] | (u[4 * j + 1] << 8) | (u[4 * j + 2] << 16) | (u[4 * j + 3] << 24);
+                else if constexpr (DT == 1) w[j] = half_bits(__builtin_fmaf(float(u[2 * j]), sc0, bi0)) | (half_bits(__builtin_fmaf(float(u[2 * j + 1]), sc1, bi1)) << 16);
+                else w[j] = __builtin_bit_cast(uint32_t, __builtin_fmaf(float(u[j]), (j & 1u) ? sc1 : sc0, (j & 1u) ? bi1 : bi0));
+            }
+            if constexpr (NW == 1) __builtin_nontemporal_store(w[0], ycc_global<uint32_t>(d));
+            else if constexpr (NW == 2) {
+                u32x2_a4 v; v.x = w[0]; v.y = w[1];
+                __builtin_nontemporal_store(v, ycc_global<u32x2_a4>(d));
+            } else {
+#pragma unroll
+                for (uint32_t j = 0; j < NW; j += 4) {
+                    u32x4_a4 v; v.x = w[j]; v.y = w[j + 1]; v.z = w[j + 2]; v.w = w[j + 3];
+                    __builtin_nontemporal_store(v, ycc_global<u32x4_a4>(d + j * 4u));
+                }
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < uint32_t(CNT); k++)
+        if (k >= k0 && k < k1) ycc_store1<DT>(d + (k - k0) * ESZ, u[k], (k & 1u) ? sc1 : sc0, (k & 1u) ? bi1 : bi0);
+}
+// the N samples of row r of a block (N x N floats at the head of its tile row) as bytes: pack_u8's truncating, saturating store of the
+// sample, level shift (and, libjpeg's pixels, the rounding half) included -- they sit on the DC term
+template <uint32_t N>
+__device__ __forceinline__ void ycc_row_bytes(const float *p, uint32_t *u)
+{
+    if constexpr (N == 2) {
+        const float2 v = *reinterpret_cast<const float2 *>(p);
+        u[0] = pack_u8(v.x, 0, 0u); u[1] = pack_u8(v.y, 0, 0u);
+    } else {
+#pragma unroll
+        for (uint32_t q = 0; q < N / 4; q++) {
+            const float4 v = *reinterpret_cast<const float4 *>(p + 4 * q);
+            u[4 * q] = pack_u8(v.x, 0, 0u); u[4 * q + 1] = pack_u8(v.y, 0, 0u); u[4 * q + 2] = pack_u8(v.z, 0, 0u); u[4 * q + 3] = pack_u8(v.w, 0, 0u);
+        }
+    }
+}
+// What phase 3 needs of one plane, staged in LDS once per workgroup (ycc_plane_l): read from the descriptor in HBM inside the tile loop,
+// every field would be a load behind the previous component's stores -- a wait for it drains those stores --, and held in scalar
+// registers across phases 1 and 2 the three planes would not fit beside the tile loop's own state.
+struct YccPlaneL {
+    uint64_t base, pitch;           // first element of the plane, elements between rows
+    uint32_t x0, y0, w, h;          // the plane's rectangle in the component's plane
+    float sc0, bi0, sc1, bi1;       // the dtype's table: the component's, and (an interleaved chroma plane) Cr's for the odd elements
+    uint32_t hc, vc, first, cr_at;  // sampling factors, first block inside the MCU, floats from a Cb block to its Cr block (pair) or 0
+    uint32_t pair, skip, dt, pad_;  // pair: Cb, Cr interleaved; skip: Cr, written with Cb; dt: MJX_DTYPE_*
+};
+__device__ __forceinline__ YccPlaneL ycc_plane_l(const DevImage &im, uint8_t *rgb_pool, uint32_t c)
+{
+    YccPlaneL p;
+    const bool il = im.ycc_il != 0u && im.ncomp == 3u;
+    p.base = uint64_t(uintptr_t(im.ycc_dev[c] ? reinterpret_cast<uint8_t *>(uintptr_t(im.ycc_dev[c])) : rgb_pool + im.rgb_off + im.ycc_off[c]));
+    p.pitch = im.ycc_pitch[c];
+    p.x0 = im.ycc_x0[c]; p.y0 = im.ycc_y0[c]; p.w = im.ycc_w[c]; p.h = im.ycc_h[c];
+    p.pair = il && c == 1u ? 1u : 0u;
+    p.skip = il && c == 2u ? 1u : 0u;
+    p.sc0 = im.out_scale[c]; p.bi0 = im.out_bias[c];
+    p.sc1 = p.pair ? im.out_scale[2] : p.sc0; p.bi1 = p.pair ? im.out_bias[2] : p.bi0;
+    p.hc = im.ch[c]; p.vc = im.cv[c]; p.first = im.cfirst[c];
+    p.cr_at = p.pair ? (uint32_t(im.cfirst[2]) - uint32_t(im.cfirst[1])) * uint32_t(kPixStride) : 0u;
+    p.dt = im.out_dtype; p.pad_ = 0u;
+    return p;
+}
+// Phase 3 of the forms that write component planes as the picture (k_idct_color<kYccMode + m, ...>).  N: samples per block side
+// (8, 4, 2).  Per component the lanes of the workgroup are laid over the tile's blocks of one block row of the MCUs, block column
+// fastest: lane -> (MCU t, block column bx) is fixed for the component (T hc is a power of two that divides 256), the lanes left over
+// take further sample rows, and the loop advances by rows.  Adjacent lanes so hold adjacent blocks of the SAME sample row: a wave's
+// store instruction covers runs of 64 N consecutive samples of a plane row (planes_store's lanes lie a row stride apart).  Each
+// block row is clipped to the plane's rectangle; a block row fully inside leaves in wide stores.  With interleaved chroma the lane
+// of a Cb block row also reads the Cr block's and writes the 2 N elements Cb, Cr, Cb, Cr ...  Nothing is loaded from HBM here.
+template <uint32_t N, int DT>
+__device__ __forceinline__ void planes_out_store_t(const YccPlaneL *pl, uint32_t ncomp, uint32_t log2T, const float *tile, uint32_t m0, uint32_t nm,
+                                                   uint32_t bpm, uint32_t mcux)
+{
+    constexpr uint32_t ESZ = DT == 0 ? 1u : DT == 1 ? 2u : 4u;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t my0 = m0 / mcux, mx0 = m0 - my0 * mcux;
+    for (uint32_t c = 0; c < ncomp; c++) {
+        const YccPlaneL p = pl[c];
+        // (the same words in every lane: the loop bounds and the pair / skip choice go back to scalar registers)
+        const uint32_t hc = __builtin_amdgcn_readfirstlane(p.hc), vc = __builtin_amdgcn_readfirstlane(p.vc);
+        const bool pair = __builtin_amdgcn_readfirstlane(p.pair) != 0u;
+        if (__builtin_amdgcn_readfirstlane(p.skip)) continue;
+        const uint32_t lh = hc >> 1, lper = log2T + lh;
+        const uint32_t rem = tid & ((1u << lper) - 1u), t = rem >> lh, bx = rem & (hc - 1u);
+        if (t >= nm) continue;
+        uint32_t mx = mx0 + t, my = my0;
+        if (mx >= mcux) { const uint32_t q = mx / mcux; my += q; mx -= q * mcux; }
+        const uint32_t Xp = (mx * hc + bx) * N;
+        const uint32_t lo = max(Xp, p.x0), hi = min(Xp + N, p.x0 + p.w);
+        if (lo >= hi) continue;
+        const uint32_t k0 = lo - Xp, k1 = hi - Xp;
+        uint8_t *base = reinterpret_cast<uint8_t *>(uintptr_t(p.base));
+        const uint32_t blk0 = t * bpm + p.first + bx;
+        const uint32_t rstep = 256u >> lper;
+        for (uint32_t by = 0; by < vc; by++) {
+            const float *blk = tile + (blk0 + by * hc) * kPixStride;
+            for (uint32_t r = tid >> lper; r < N; r += rstep) {
+                const uint32_t Yp = (my * vc + by) * N + r;
+                if (Yp < p.y0 || Yp - p.y0 >= p.h) continue;
+                const uint64_t row = uint64_t(Yp - p.y0) * p.pitch;
+                if (pair) {
+                    uint32_t a[N], b[N], u[2 * N];
+                    ycc_row_bytes<N>(blk + r * N, a);
+                    ycc_row_bytes<N>(blk + p.cr_at + r * N, b);
+#pragma unroll
+                    for (uint32_t k = 0; k < N; k++) { u[2 * k] = a[k]; u[2 * k + 1] = b[k]; }
+                    ycc_store_run<DT, int(2 * N)>(base + (row + uint64_t(lo - p.x0) * 2u) * ESZ, u, 2u * k0, 2u * k1, p.sc0, p.bi0, p.sc1, p.bi1);
+                } else {
+                    uint32_t u[N];
+                    ycc_row_bytes<N>(blk + r * N, u);
+                    ycc_store_run<DT, int(N)>(base + (row + (lo - p.x0)) * ESZ, u, k0, k1, p.sc0, p.bi0, p.sc1, p.bi1);
+                }
+            }
+        }
+    }
+}
+template <uint32_t N>
+__device__ __forceinline__ void planes_out_store(const YccPlaneL *pl, uint32_t ncomp, uint32_t log2T, const float *tile, uint32_t m0, uint32_t nm,
+                                                 uint32_t bpm, uint32_t mcux)
+{
+    const uint32_t dt = pl[0].dt;               // (uniform: one of three bodies per tile, no format branch inside the loops)
+    if (dt == 0u) planes_out_store_t<N, 0>(pl, ncomp, log2T, tile, m0, nm, bpm, mcux);
+    else if (dt == 1u) planes_out_store_t<N, 1>(pl, ncomp, log2T, tile, m0, nm, bpm, mcux);
+    else planes_out_store_t<N, 2>(pl, ncomp, log2T, tile, m0, nm, bpm, mcux);
+}
+
 // ---- REF_COMPAT placement (MODE 2) ---------------------------------------------------------------------------
 // Reproduces decoder.rs:259-312 + fill_block_in_array (:347-379) bug for bug: the component's blocks
 // are taken in decode order as a raster counter, get_indices maps the counter to a block position with formulas
@@ -3810,6 +3972,10 @@ __device__ __forceinline__ void pixels_scaled_luma(const GenShape &g, const floa
 //        k_upsample_color makes the picture
 //   OUT  output formats (MODE_ = MODE + kOutMode, the mode of a picture with an output description): the ROI form -- a picture without a
 //        rectangle is its own whole rectangle --, phase 3 writing the picture's format (store4_out, DevImage::out_*)
+//   YCC  YCbCr output (MODE_ = MODE + kYccMode, MODE 0, 3, 4; mjx_planes): the ROI form with one difference in phases 1-2 -- every
+//        component's DC term takes the level shift, as PLANES --, phase 3 storing every component's samples as the picture's planes,
+//        clipped to their true sizes and the rectangle, in the planes' dtype and pitches (planes_out_store; the planes' descriptors
+//        are staged in LDS once per workgroup, so phase 3 loads nothing from HBM)
 //   LUMA  luminance output (MODE_ = MODE + kLumaMode, MJX_OUTPUT_CHANNELS == 1): the OUT form with three differences -- an entry whose
 //        block is not component 0's goes to the padding word, as dropped positions do at reduced scale; the DC term and phase 2 run on
 //        luminance blocks only; phase 3 does no colour arithmetic and stores one element per pixel (store4_luma).  The tile keeps the
@@ -3822,12 +3988,14 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                                                      uint8_t *__restrict__ rgb, unsigned long long *__restrict__ planes,
                                                      const uint32_t *__restrict__ img_flags, uint32_t tiles_per_wg)
 {
-    constexpr bool LUMA = MODE_ >= int(kLumaMode);            // luminance output: the cropped form, component 0 alone
-    constexpr bool PLANES = !LUMA && MODE_ >= int(kPlaneMode);// libjpeg's pixels: the cropped form again, phase 3 storing component planes
-    constexpr bool OUT = !LUMA && !PLANES && MODE_ >= int(kOutMode);   // output formats: the cropped form, the picture its own whole rectangle without one
+    constexpr bool YCC = MODE_ >= int(kYccMode);              // YCbCr output: the cropped form, phase 3 storing the component planes as the picture
+    constexpr bool LUMA = !YCC && MODE_ >= int(kLumaMode);    // luminance output: the cropped form, component 0 alone
+    constexpr bool PLANES = !YCC && !LUMA && MODE_ >= int(kPlaneMode);// libjpeg's pixels: the cropped form again, phase 3 storing component planes
+    constexpr bool OUT = !YCC && !LUMA && !PLANES && MODE_ >= int(kOutMode);   // output formats: the cropped form, the picture its own whole rectangle without one
     constexpr bool ROI = MODE_ >= int(kRoiMode);
-    constexpr int MODE = MODE_ - (LUMA ? int(kLumaMode) : PLANES ? int(kPlaneMode) : OUT ? int(kOutMode) : ROI ? int(kRoiMode) : 0);
+    constexpr int MODE = MODE_ - (YCC ? int(kYccMode) : LUMA ? int(kLumaMode) : PLANES ? int(kPlaneMode) : OUT ? int(kOutMode) : ROI ? int(kRoiMode) : 0);
     static_assert(!PLANES || MODE == 0, "the planes are written by the generic form");
+    static_assert(!YCC || MODE == 0 || MODE == 3 || MODE == 4, "component planes: the generic form and its scaled siblings");
     static_assert(!ROI || MODE != 2, "REF_COMPAT has no rectangles");
     // (its own symbol: dynamic LDS arrays of one name share their alignment, and the entropy kernels ask for 2 KiB)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_px[];
@@ -3867,6 +4035,13 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     OutFmt ofmt{};
     if constexpr (OUT) ofmt = out_fmt(im, rgb);
     if constexpr (LUMA) ofmt = luma_fmt(im, rgb);
+    // YCbCr output: the planes' descriptors go to LDS once (a lane each; the barrier behind the offsets' fetch below publishes them)
+    const YccPlaneL *ycc_pl = nullptr;
+    if constexpr (YCC) {
+        __shared__ YccPlaneL s_ycc[3];
+        if (threadIdx.x < im.ncomp) s_ycc[threadIdx.x] = ycc_plane_l(im, rgb, threadIdx.x);
+        ycc_pl = s_ycc;
+    }
     constexpr bool SKIP = ROI && SRC != 2;
     auto wanted_from = [&](uint32_t t) {          // the first tile at or behind t that the rectangle wants (uniform)
         if constexpr (SKIP)
@@ -3954,6 +4129,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     float my_dc_qm = qmult[im.qm_off + my_comp * 64];
     float my_dc_add = (MODE != 2 && my_comp == 0) ? 128.0f : 0.0f;
     if constexpr (PLANES) my_dc_add = 128.5f;         // (every component's level shift and the rounding: the store truncates, planes_store)
+    if constexpr (YCC) my_dc_add = im.ycc_round ? 128.5f : 128.0f;      // (every component's level shift; libjpeg's pixels: and the rounding)
     float *tile_f = reinterpret_cast<float *>(smem_px);
     GenShape gshape{};
     if (MODE == 0 || SCALED) gshape = gen_shape(im);
@@ -4122,11 +4298,13 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
         } else if (MODE == 2) {
             place_ref(im, tile_f, tile * tile_blocks, nblk, planes);
         } else if constexpr (SCALED) {
-            if constexpr (LUMA) pixels_scaled_luma<scaled_n<MODE>()>(gshape, tile_f, m0, nm, roi, ofmt);
+            if constexpr (YCC) planes_out_store<scaled_n<MODE>()>(ycc_pl, gshape.ncomp, log2T, tile_f, m0, nm, bpm, mcux);
+            else if constexpr (LUMA) pixels_scaled_luma<scaled_n<MODE>()>(gshape, tile_f, m0, nm, roi, ofmt);
             else if constexpr (OUT) pixels_scaled<scaled_n<MODE>(), true, true>(gshape, tile_f, m0, nm, nullptr, false, roi, &ofmt);
             else pixels_scaled<scaled_n<MODE>(), ROI>(gshape, tile_f, m0, nm, out_img, aligned, roi);
         } else {
-            if constexpr (LUMA) pixels_generic_luma(gshape, tile_f, m0, nm, roi, ofmt);
+            if constexpr (YCC) planes_out_store<8u>(ycc_pl, gshape.ncomp, log2T, tile_f, m0, nm, bpm, mcux);
+            else if constexpr (LUMA) pixels_generic_luma(gshape, tile_f, m0, nm, roi, ofmt);
             else if constexpr (PLANES) planes_store(im, tile_f, m0, nblk, bpm, mcux, reinterpret_cast<uint8_t *>(planes + im.plane_off));
             else if constexpr (OUT) pixels_generic_out(gshape, tile_f, m0, nm, roi, ofmt);
             else if constexpr (ROI) pixels_generic_roi(gshape, tile_f, m0, nm, out_img, aligned, roi);
@@ -4246,6 +4424,50 @@ extern "C" __global__ __launch_bounds__(256) void k_dc_color_luma(const DevImage
     const float s0 = float(dc) * qmult[im.qm_off] + 128.0f;
     const OutFmt f = luma_fmt(im, rgb);
     out_store1(f, uint64_t(row) * f.row_pitch + col, pack_u8(s0, 0, 0) & 0xffu, f.scale[0], f.bias[0]);
+}
+
+// YCbCr output at 1/8 (k_dc_color_ycc, mode 5 + kYccMode): one lane per sample of each plane -- a block gives one sample, its DC value
+// through dc_color_body's expression with the level shift on every component, pack_u8's store, one element through the dtype's table.
+extern "C" __global__ __launch_bounds__(256) void k_dc_color_ycc(const DevImage *__restrict__ images, const int32_t *__restrict__ dcbuf,
+                                                                  const float *__restrict__ qmult, uint8_t *__restrict__ rgb,
+                                                                  const uint32_t *__restrict__ img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    if (!im.valid || im.mode != 5u + kYccMode || img_flags[im.status_idx]) return;
+    uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    uint32_t c = 0;
+    for (; c < im.ncomp; c++) {
+        const uint64_t n = uint64_t(im.ycc_w[c]) * im.ycc_h[c];
+        if (i < n) break;
+        i -= n;
+    }
+    if (c >= im.ncomp) return;
+    const uint32_t pw = im.ycc_w[c];
+    const uint32_t j = uint32_t(i);                  // (inside one plane: below 2^32, a 32-bit division)
+    const uint32_t row = j / pw, col = j - row * pw;
+    const uint32_t Xp = col + im.ycc_x0[c], Yp = row + im.ycc_y0[c];
+    const uint32_t hc = im.ch[c], vc = im.cv[c];
+    const uint32_t mx = Xp / hc, my = Yp / vc, bx = Xp - mx * hc, by = Yp - my * vc;
+    const uint32_t k = im.cfirst[c] + by * hc + bx;
+    int32_t dc = 0;
+    if (im.planar) {
+        PlanarDc d{};
+        planar_dc_slot(images, im, blockIdx.y, k, d);
+        if (mx * d.rx + d.r0x < d.lx && my * d.ry + d.r0y < d.ly) dc = dcbuf[d.base + (my * d.ky + mx * d.kx + d.k0)];
+    } else {
+        dc = dcbuf[im.coef_off + (uint64_t(my) * im.mcux + mx) * im.bpm + k];
+    }
+    const float s = float(dc) * qmult[im.qm_off + c * 64u] + 128.0f;
+    const uint32_t u = pack_u8(s, 0, 0u);
+    const bool pair = im.ycc_il != 0u && c >= 1u;                        // Cb and Cr share plane 1: element 2 X (+ 1 for Cr)
+    const uint32_t pc = pair ? 1u : c;
+    uint8_t *base = im.ycc_dev[pc] ? reinterpret_cast<uint8_t *>(uintptr_t(im.ycc_dev[pc])) : rgb + im.rgb_off + im.ycc_off[pc];
+    const uint64_t at = uint64_t(row) * im.ycc_pitch[pc] + (pair ? uint64_t(col) * 2u + (c - 1u) : uint64_t(col));
+    const uint32_t dt = im.out_dtype;
+    const float sc = im.out_scale[c], bi = im.out_bias[c];
+    if (dt == 0u) ycc_store1<0>(base + at, u, sc, bi);
+    else if (dt == 1u) ycc_store1<1>(base + at * 2u, u, sc, bi);
+    else ycc_store1<2>(base + at * 4u, u, sc, bi);
 }
 
 // ---- resize on the device (mjx_resize; DevImage::rs_*) -------------------------------------------------------------------------
@@ -4648,7 +4870,9 @@ int configure_kernels(size_t huff_lds, size_t idct_lds)
                              MJX_ROI_FORMS(kOutMode - kRoiMode + 3), MJX_ROI_FORMS(kOutMode - kRoiMode + 4),
                              MJX_ROI_FORMS(kPlaneMode - kRoiMode + 0),                                               // (libjpeg's pixels: the plane form)
                              MJX_ROI_FORMS(kLumaMode - kRoiMode + 0), MJX_ROI_FORMS(kLumaMode - kRoiMode + 1),      // (luminance output, kLumaMode + m)
-                             MJX_ROI_FORMS(kLumaMode - kRoiMode + 3), MJX_ROI_FORMS(kLumaMode - kRoiMode + 4)};
+                             MJX_ROI_FORMS(kLumaMode - kRoiMode + 3), MJX_ROI_FORMS(kLumaMode - kRoiMode + 4),
+                             MJX_ROI_FORMS(kYccMode - kRoiMode + 0), MJX_ROI_FORMS(kYccMode - kRoiMode + 3),        // (YCbCr output, kYccMode + m)
+                             MJX_ROI_FORMS(kYccMode - kRoiMode + 4)};
 #undef MJX_ROI_FORMS
         for (const void *f : fns)
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(idct_lds));
@@ -4862,6 +5086,10 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
     MJX_IDCT_ROI(kLumaMode - kRoiMode + 1)
     MJX_IDCT_ROI(kLumaMode - kRoiMode + 3)
     MJX_IDCT_ROI(kLumaMode - kRoiMode + 4)
+    // ... and pictures that leave as component planes (mode + kYccMode) the forms that write those
+    MJX_IDCT_ROI(kYccMode - kRoiMode + 0)
+    MJX_IDCT_ROI(kYccMode - kRoiMode + 3)
+    MJX_IDCT_ROI(kYccMode - kRoiMode + 4)
 #undef MJX_IDCT_ROI
 }
 
@@ -4921,6 +5149,13 @@ void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, cons
     if (out) hipLaunchKernelGGL(k_dc_color_out, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
     else if (roi) hipLaunchKernelGGL(k_dc_color_roi, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
     else hipLaunchKernelGGL(k_dc_color, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
+}
+
+void launch_dc_color_ycc(hipStream_t st, uint32_t max_sample_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
+                         const float *qmult, uint8_t *rgb, const uint32_t *img_flags)
+{
+    if (max_sample_wgs == 0 || nimg == 0) return;
+    hipLaunchKernelGGL(k_dc_color_ycc, dim3(max_sample_wgs, nimg), dim3(256), 0, st, images, dcbuf, qmult, rgb, img_flags);
 }
 
 void launch_dc_color_luma(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,

@@ -531,6 +531,91 @@ int plan_output_of_input(std::vector<ImagePlan> &plans, const mjx_output *out, s
     return rc;
 }
 
+bool planes_fit(const mjx_planes *pl, size_t n)
+{
+    if (!pl) return false;
+    if (!pl->dst) return pl->n_dst == 0;
+    return pl->n_dst == n;
+}
+
+int plan_planes(ImagePlan &p, const mjx_planes *pl, size_t i)
+{
+    p.ycc_on = false;
+    if (!pl || p.status != MJX_OK) return p.status;
+    auto fail = [&]() { p.status = MJX_ERR_INVALID_ARG; return p.status; };
+    if (pl->dtype > MJX_DTYPE_F32 || p.layout == MJX_LAYOUT_REF_COMPAT) return fail();
+    const uint32_t nc = p.ncomp;
+    const bool il = pl->interleave_chroma != 0 && nc == 3;            // (a one-component file has one plane: the flag has no meaning)
+    if (il && (p.h[1] != p.h[2] || p.v[1] != p.v[2])) return fail();
+    const uint64_t esz = pl->dtype == MJX_DTYPE_U8 ? 1u : pl->dtype == MJX_DTYPE_F16 ? 2u : 4u;
+    for (uint32_t c = 0; c < nc; c++) {
+        if (pl->dtype != MJX_DTYPE_U8 && !(std::isfinite(pl->scale[c]) && std::isfinite(pl->bias[c]))) return fail();
+        p.out_scale[c] = pl->dtype == MJX_DTYPE_U8 ? 1.f : pl->scale[c];
+        p.out_bias[c] = pl->dtype == MJX_DTYPE_U8 ? 0.f : pl->bias[c];
+    }
+    // libjpeg's pixels: the planes in front of that option's upsampling -- no filter, so no reach: the rectangle's own tiles, and the
+    // generic plane form with the rounding half on the DC term instead of k_upsample_color's pass
+    if (p.lj) {
+        const uint32_t pw = 8 * p.hmax, ph = 8 * p.vmax;
+        p.roi_mc0 = p.roi_x / pw; p.roi_mc1 = (p.roi_x + p.roi_w - 1) / pw;
+        p.roi_mr0 = p.roi_y / ph; p.roi_mr1 = (p.roi_y + p.roi_h - 1) / ph;
+        p.lj = false;
+        p.ycc_round = 1;
+    }
+    uint64_t off = 0, first = 0, last = 0;
+    p.ycc_written = 0;
+    const uint32_t nplanes = il ? 2u : nc;
+    for (uint32_t c = 0; c < nc; c++) {
+        const PlaneSpan s = plane_span(p.roi_x, p.roi_y, p.roi_w, p.roi_h, p.h[c], p.v[c], p.hmax, p.vmax);
+        p.ycc_x0[c] = s.x0; p.ycc_y0[c] = s.y0; p.ycc_w[c] = s.w; p.ycc_h[c] = s.h;
+        p.ycc_written += uint64_t(s.w) * s.h * esz;
+        p.ycc_dev[c] = 0; p.ycc_off[c] = 0; p.ycc_pitch[c] = 0;
+        if (c >= nplanes) continue;                                    // (Cr rides in plane 1)
+        const uint64_t row_min = uint64_t(s.w) * (il && c == 1 ? 2u : 1u);
+        uint64_t pitch = row_min;
+        if (pl->dst) {
+            const mjx_plane_layout &d = pl->dst[i];
+            if (d.width[c] != s.w || d.height[c] != s.h || d.row_pitch[c] < row_min || d.row_pitch[c] > (uint64_t(1) << 40)) return fail();
+            if (!d.dev[c] || (uint64_t(uintptr_t(d.dev[c])) & (esz - 1))) return fail();
+            pitch = d.row_pitch[c];
+            p.ycc_dev[c] = uint64_t(uintptr_t(d.dev[c]));
+        } else {
+            p.ycc_off[c] = off;
+        }
+        p.ycc_pitch[c] = pitch;
+        const uint64_t span = ((uint64_t(s.h) - 1) * pitch + row_min) * esz;
+        const uint64_t at = pl->dst ? p.ycc_dev[c] : off;
+        if (c == 0) first = at;
+        last = std::max(last, at + span);
+        off += span;
+    }
+    p.ycc_on = true;
+    p.ycc_il = il ? 1u : 0u;
+    p.out_on = true;
+    p.out_channels = 3;
+    p.out_dtype = pl->dtype;
+    p.out_planar = 1; p.out_bgr = 0;
+    p.out_dev = p.ycc_dev[0];
+    p.out_row_pitch = p.ycc_pitch[0]; p.out_plane_pitch = 0;
+    p.out_bytes = last > first ? last - first : ((uint64_t(p.ycc_h[0]) - 1) * p.ycc_pitch[0] + p.ycc_w[0]) * esz;
+    return p.status;
+}
+
+int plan_planes_of_input(std::vector<ImagePlan> &plans, const mjx_planes *pl, size_t i)
+{
+    ImagePlan &p = plans.back();
+    const bool was_ok = p.status == MJX_OK;
+    const size_t nparts = p.role == 2 ? p.nparts : 0;
+    const int rc = plan_planes(p, pl, i);
+    if (was_ok && rc != MJX_OK && nparts && plans.size() > nparts) {       // one status for the whole picture, as plan_output_of_input
+        ImagePlan pic;
+        pic.status = rc;
+        plans.resize(plans.size() - 1 - nparts);
+        plans.push_back(pic);
+    }
+    return rc;
+}
+
 // one status for the whole input: a multi-scan picture that is refused takes its scans' plans with it
 static void fail_input(std::vector<ImagePlan> &plans, size_t first, int rc)
 {

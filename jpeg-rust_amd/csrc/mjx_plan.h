@@ -55,6 +55,16 @@ struct ImagePlan {
     uint32_t out_channels = 3;                     // 1: luminance -- one element per pixel, rows of out_row_pitch, no planes (scale[0], bias[0])
     float out_scale[3] = {1.f, 1.f, 1.f}, out_bias[3] = {0.f, 0.f, 0.f};
     uint64_t out_dev = 0, out_row_pitch = 0, out_plane_pitch = 0, out_bytes = 0;
+    // YCbCr output (mjx_planes, plan_planes): the picture leaves as its component planes.  out_on, out_dtype, out_scale / out_bias (by
+    // COMPONENT), out_dev (plane 0's, 0: library-owned) and out_bytes (the span from plane 0's first byte to the last plane's end)
+    // above are set as for any output description; plane c is ycc_w[c] x ycc_h[c] samples from (ycc_x0[c], ycc_y0[c]) of the
+    // component's plane (plane_span of the rectangle), rows of ycc_pitch[c] elements at ycc_dev[c] or, library-owned, ycc_off[c]
+    // bytes behind plane 0's first.  ycc_il: Cb and Cr share plane 1 as pairs.  ycc_round: libjpeg's pixels (rounded samples).
+    // ycc_written: the bytes stage B writes (the pitches' padding not counted).
+    bool ycc_on = false;
+    uint32_t ycc_il = 0, ycc_round = 0;
+    uint32_t ycc_x0[3] = {0, 0, 0}, ycc_y0[3] = {0, 0, 0}, ycc_w[3] = {0, 0, 0}, ycc_h[3] = {0, 0, 0};
+    uint64_t ycc_dev[3] = {0, 0, 0}, ycc_off[3] = {0, 0, 0}, ycc_pitch[3] = {0, 0, 0}, ycc_written = 0;
     // resize on the device (mjx_resize, plan_resize): the picture is planned as the packed (cropped) picture roi_w x roi_h at `scale`
     // -- the intermediate -- and leaves as rs_w x rs_h elements per channel: out_* above then describe the TARGET picture, and
     // stage B keeps its packed forms (fill_dev_image).
@@ -129,6 +139,13 @@ int plan_output(ImagePlan &p, const mjx_output *out, size_t i);
 // ... applied to the plans of one input as plan_input left them (the last is the picture's): a multi-scan picture that is refused
 // takes its scans' plans with it, so that nothing of the file is uploaded or decoded.
 int plan_output_of_input(std::vector<ImagePlan> &plans, const mjx_output *out, size_t i);
+
+// YCbCr output: does pl->dst / n_dst fit a call of n inputs, and the one place that knows the rules of a picture's planes -- sizes
+// (plane_span, mjx_kernels.h), offsets of dense library-owned planes or dst[i]'s pointers and pitches after checking them -- or fails
+// the picture with MJX_ERR_INVALID_ARG.  mjx_planes_layout reports what it finds here.  plan_planes_of_input: as plan_output_of_input.
+bool planes_fit(const mjx_planes *pl, size_t n);
+int plan_planes(ImagePlan &p, const mjx_planes *pl, size_t i);
+int plan_planes_of_input(std::vector<ImagePlan> &plans, const mjx_planes *pl, size_t i);
 
 // Resize on the device.  resize_opts: the options input i is planned with under `rs` -- the call's own (auto_scale 0), or the scale
 // and the rectangle at that scale the auto-scale rule picks for a picture of width x height (`rect` is the storage the options
