@@ -116,6 +116,21 @@ pub struct mjx_resize {
     pub auto_scale: u8,
 }
 
+/// MJX_RESIZE_FILTER_OFFSET: the filter kind of a resize description is byte 10 of mjx_resize, the byte behind `auto_scale`
+/// (0: the triangle, 1: bicubic, 2: nearest).  Start from a zeroed value (std::mem::zeroed) and set it on the value the call is given.
+pub const MJX_RESIZE_FILTER_OFFSET: usize = 10;
+pub const MJX_FILTER_TRIANGLE: u8 = 0;
+pub const MJX_FILTER_BICUBIC: u8 = 1;
+pub const MJX_FILTER_NEAREST: u8 = 2;
+impl mjx_resize {
+    pub fn filter(&self) -> u8 {
+        unsafe { *(self as *const mjx_resize as *const u8).add(MJX_RESIZE_FILTER_OFFSET) }
+    }
+    pub fn set_filter(&mut self, filter: u8) {
+        unsafe { *(self as *mut mjx_resize as *mut u8).add(MJX_RESIZE_FILTER_OFFSET) = filter }
+    }
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct mjx_opts {
@@ -252,6 +267,8 @@ extern "C" {
                            rect: *mut mjx_rect, taps_x: *mut u32, taps_y: *mut u32) -> c_int;
     pub fn mjx_resize_weights(n_in: u32, n_out: u32, antialias: c_int, x: u32, first: *mut u32, weights: *mut f32, cap: usize,
                               count: *mut usize) -> c_int;
+    pub fn mjx_resize_filter_weights(n_in: u32, n_out: u32, filter: c_int, antialias: c_int, x: u32, first: *mut u32, weights: *mut f32,
+                                     cap: usize, count: *mut usize) -> c_int;
     pub fn mjx_exif_orientation(jpeg: *const u8, len: usize, code: *mut u8) -> c_int;
     pub fn mjx_orient_compose(first: u8, then: u8) -> u8;
     pub fn mjx_batch_create_orient(ctx: *mut mjx_ctx, descs: *const mjx_scan_desc, n: usize, opts: *const mjx_opts, out: *const mjx_output,

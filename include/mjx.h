@@ -268,6 +268,36 @@ typedef struct mjx_resize {
     uint8_t antialias;        /* 1: the filter widens with the ratio when shrinking (fs = max(1, r)); 0: two taps */
     uint8_t auto_scale;       /* 1: the library picks the DCT-domain scale per picture; rois are in full-size coordinates */
 } mjx_resize;
+/* The filter kind of a resize description: byte 10 of mjx_resize, one of the two bytes behind `auto_scale` that the declared members
+ * leave unused (the struct's members, size and offsets are as they were; a zero-filled struct means what it meant).  An lvalue:
+ * MJX_RESIZE_FILTER(&rs) = MJX_FILTER_BICUBIC.  Fill the struct with zeros first (memset, = {0} on a static, value-initialisation
+ * in C++) and set the kind on the object the call is given: a member-wise copy of the struct need not carry the byte.  A value
+ * above MJX_FILTER_NEAREST gives the picture MJX_ERR_INVALID_ARG (mjx_resize_plan reports it). */
+#define MJX_RESIZE_FILTER_OFFSET 10
+#define MJX_RESIZE_FILTER(rs) (((uint8_t *)(rs))[MJX_RESIZE_FILTER_OFFSET])
+#define MJX_FILTER_TRIANGLE 0   /* the rule above, bit for bit */
+#define MJX_FILTER_BICUBIC  1   /* torch's two bicubic rules, picked by `antialias` */
+#define MJX_FILTER_NEAREST  2   /* torch's nearest-exact / Pillow's NEAREST; `antialias` is ignored */
+/* The other two kinds keep the notation of the rule above -- per axis n_in -> n_out, r = n_in / n_out, c = (X + 0.5) r, coordinates
+ * in exact integer arithmetic -- and everything around it: crop, then resize; auto_scale, rectangles, output formats, caller-owned
+ * memory, orientation, luminance, MJX_PIXELS_LIBJPEG, mjx_batch_tile and the pipelined calls.  The cubic kernel with parameter a:
+ *   k_a(x) = ((a + 2)|x| - (a + 3)) x^2 + 1 for |x| < 1,  a (((|x| - 5)|x| + 8)|x| - 4) for 1 <= |x| < 2,  else 0.
+ * Bicubic, antialias = 1 (torch mode="bicubic", antialias=True; Pillow's BICUBIC): a = -0.5, fs = max(1, r),
+ *   lo = max(0, floor(c - 2 fs + 0.5)),  hi = min(n_in, floor(c + 2 fs + 0.5)),
+ *   w_j = k_a((j + 0.5 - c) / fs) for j in [lo, hi), divided by their sum
+ * (the window is clipped at the rectangle's edge and renormalised, as the triangle is).
+ * Bicubic, antialias = 0 (torch mode="bicubic", antialias=False, align_corners=False): a = -0.75, s = c - 0.5, q = floor(s) (may
+ * be -1), t = s - q; the four taps q - 1 .. q + 2 with the weights k_a(1 + t), k_a(t), k_a(1 - t), k_a(2 - t).  A tap outside
+ * [0, n_in) reads the edge sample: its weight is added to the edge sample's, and nothing is renormalised.  This filter does NOT
+ * widen when shrinking -- it is torch's behaviour: a picture shrunk by more than about two aliases; ask for antialias = 1 then.
+ * Nearest: the one tap j = floor((2X + 1) n_in / (2 n_out)) with weight 1.
+ * The weights are evaluated in float32 from the whole-number distance of a tap (the Horner forms above: distances 0, 1 and 2 give
+ * exactly 1, 0 and 0).  The sample v = sum_y sum_x wy wx I[y][x][ch] and the element are as above: U8 rint of v clamped to
+ * [0, 255] -- bicubic weights are signed, v over- and undershoots, and the clamp acts on both sides --, F32 fmaf(v, scale[c],
+ * bias[c]) on the unrounded and UNCLAMPED v (as torch's float path), F16 that float rounded to nearest even.  With nearest every
+ * element is mjx_output's table applied to the byte picked, bit for bit; with any kind a target of the rectangle's own size is
+ * that table applied to the packed decode, bit for bit.  Not built: Lanczos (its weights need sin(pi x) from one host-and-device
+ * routine that gives exact zeros at whole distances: an argument-reduced form of its own); modes that pad (letterbox). */
 
 /* ---- orientation on the device: EXIF orientation, with per-picture flips on top -----------------------------------------
  * A camera file stores its pixels as the sensor saw them and names, in EXIF tag 0x0112, one of eight ways to turn them upright.
@@ -468,6 +498,12 @@ int mjx_resize_plan(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_r
  * (at most cap are written; *count is the window's length either way).  n_in, n_out in 1 .. 2^24, X < n_out. */
 int mjx_resize_weights(uint32_t n_in, uint32_t n_out, int antialias, uint32_t X, uint32_t *first, float *weights, size_t cap,
                        size_t *count);
+/* mjx_resize_weights with the filter kind (MJX_FILTER_*; the routines the bicubic and nearest kernels run: resize_taps,
+ * mjx_kernels.h); filter 0 is mjx_resize_weights itself.  Bicubic with antialias = 0 returns the folded weights over the clipped
+ * window -- a tap outside [0, n_in) added to the edge sample's --, so *first + *count <= n_in as for every kind.  An unknown filter:
+ * MJX_ERR_INVALID_ARG. */
+int mjx_resize_filter_weights(uint32_t n_in, uint32_t n_out, int filter, int antialias, uint32_t X, uint32_t *first, float *weights,
+                              size_t cap, size_t *count);
 /* Host-only: MJX_PIXELS_LIBJPEG's upsampling and colour step on the CPU -- the routines k_upsample_color itself runs (lj_strip8 /
  * lj_color, mjx_kernels.h).  ncomp (1 or 3) dense planes of cw[c] x ch[c] samples, upsampled by rh[c], rv[c] (each 1 or 2); rgb receives
  * the rectangle's rect->w x rect->h pixels, packed R,G,B.  The rectangle must lie inside every upsampled plane (cw[c] rh[c] x

@@ -91,6 +91,15 @@ class PlanesDesc(ctypes.Structure):
 class ResizeDesc(ctypes.Structure):
     """mjx_resize: the one target size of a call's pictures (see Resize)."""
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("antialias", ctypes.c_uint8), ("auto_scale", ctypes.c_uint8)]
+    FILTER_OFFSET = 10                  # MJX_RESIZE_FILTER_OFFSET: the filter kind lives in the byte behind auto_scale
+
+    @property
+    def filter(self):
+        return ctypes.c_uint8.from_address(ctypes.addressof(self) + self.FILTER_OFFSET).value
+
+    @filter.setter
+    def filter(self, v):
+        ctypes.c_uint8.from_address(ctypes.addressof(self) + self.FILTER_OFFSET).value = int(v)
 
 
 class OrientDesc(ctypes.Structure):
@@ -99,6 +108,17 @@ class OrientDesc(ctypes.Structure):
 
 
 DTYPE_U8, DTYPE_F16, DTYPE_F32 = 0, 1, 2
+FILTER_TRIANGLE, FILTER_BICUBIC, FILTER_NEAREST = 0, 1, 2
+FILTERS = {"bilinear": FILTER_TRIANGLE, "bicubic": FILTER_BICUBIC, "nearest": FILTER_NEAREST}
+
+
+def _filter_code(filter):
+    """A filter's name (or its MJX_FILTER_* code) -> the code."""
+    if isinstance(filter, str):
+        if filter not in FILTERS:
+            raise MjxError(ERR_INVALID_ARG, "filter %r (one of %s)" % (filter, ", ".join(sorted(FILTERS))))
+        return FILTERS[filter]
+    return int(filter)
 _NP_DTYPES = {DTYPE_U8: np.uint8, DTYPE_F16: np.float16, DTYPE_F32: np.float32}
 
 
@@ -154,6 +174,7 @@ SYMBOLS = {
     "mjx_decode_batch_resize": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(OutputDesc), _P(ResizeDesc), _P(_int), _P(_vp)]),
     "mjx_resize_plan": (_int, [_P(ScanDesc), _P(Opts), _P(ResizeDesc), _sz, _P(ctypes.c_uint8), _P(Rect), _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
     "mjx_resize_weights": (_int, [ctypes.c_uint32, ctypes.c_uint32, _int, ctypes.c_uint32, _P(ctypes.c_uint32), _P(ctypes.c_float), _sz, _P(_sz)]),
+    "mjx_resize_filter_weights": (_int, [ctypes.c_uint32, ctypes.c_uint32, _int, _int, ctypes.c_uint32, _P(ctypes.c_uint32), _P(ctypes.c_float), _sz, _P(_sz)]),
     "mjx_upsample_color_host": (_int, [_P(_P(ctypes.c_uint8)), _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(ctypes.c_uint8), _P(ctypes.c_uint8), ctypes.c_uint32,
                                        _P(Rect), _P(ctypes.c_uint8)]),
     "mjx_upsample_luma_host": (_int, [_P(ctypes.c_uint8), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8, _P(Rect), _P(ctypes.c_uint8)]),
@@ -392,19 +413,29 @@ def _planes_ref(planes):
 
 class Resize:
     """Resize on the device (mjx.h: mjx_resize): every picture of the call leaves at width x height, resampled from its decoded
-    rectangle with the triangle filter of torch.nn.functional.interpolate(mode="bilinear", align_corners=False,
-    antialias=antialias).  auto_scale: the library picks the DCT-domain scale (1, 1/2, 1/4, 1/8) per picture so that the filter
+    rectangle with the filter of torch.nn.functional.interpolate(mode=filter, align_corners=False, antialias=antialias) --
+    filter "bilinear" (the triangle), "bicubic" (torch's two rules: a = -0.5, widening with the ratio, with antialias, which is also
+    Pillow's BICUBIC; a = -0.75 and four taps without, which does not widen when shrinking) or "nearest" (torch's nearest-exact,
+    Pillow's NEAREST; antialias is ignored).  auto_scale: the library picks the DCT-domain scale (1, 1/2, 1/4, 1/8) per picture so that the filter
     never has to shrink by more than it must; rois are then in FULL-SIZE coordinates and scale must be 1.  Without it the call's
     scale and rois apply as in any call."""
 
-    def __init__(self, width, height, antialias=True, auto_scale=True):
+    def __init__(self, width, height, antialias=True, auto_scale=True, filter="bilinear"):
         self.width, self.height = int(width), int(height)
         self.antialias, self.auto_scale = bool(antialias), bool(auto_scale)
+        self.filter = filter
+        _filter_code(filter)
         if not (0 <= self.width <= 0xffffffff and 0 <= self.height <= 0xffffffff):
             raise MjxError(ERR_INVALID_ARG, "resize to %d x %d" % (self.width, self.height))
 
     def desc(self):
-        return ResizeDesc(self.width, self.height, int(self.antialias), int(self.auto_scale))
+        d = ResizeDesc(self.width, self.height, int(self.antialias), int(self.auto_scale))
+        d.filter = _filter_code(self.filter)
+        return d
+
+    def sized(self, width, height):
+        """This description at another target size: everything else, the filter included, is kept."""
+        return Resize(width, height, self.antialias, self.auto_scale, self.filter)
 
 
 def _rs_ref(resize):
@@ -452,9 +483,17 @@ def orient_compose(first, then):
     return c
 
 
-def resize_weights(n_in, n_out, antialias, X):
-    """mjx_resize_weights (host only; the routine the resize kernel runs) -> (first input index, float32 weights of the window)."""
+def resize_weights(n_in, n_out, antialias, X, filter="bilinear"):
+    """mjx_resize_weights / mjx_resize_filter_weights (host only; the routine the resize kernel runs) -> (first input index, float32
+    weights of the window); filter as Resize's."""
     first, cnt = ctypes.c_uint32(), _sz()
+    f = _filter_code(filter)
+    if f != FILTER_TRIANGLE:
+        args = (int(n_in), int(n_out), f, int(bool(antialias)), int(X), ctypes.byref(first))
+        _check(lib().mjx_resize_filter_weights(*args, None, 0, ctypes.byref(cnt)), "mjx_resize_filter_weights")
+        w = np.zeros(max(cnt.value, 1), np.float32)
+        _check(lib().mjx_resize_filter_weights(*args, w.ctypes.data_as(_P(ctypes.c_float)), cnt.value, ctypes.byref(cnt)), "mjx_resize_filter_weights")
+        return first.value, w[:cnt.value]
     _check(lib().mjx_resize_weights(int(n_in), int(n_out), int(bool(antialias)), int(X), ctypes.byref(first), None, 0, ctypes.byref(cnt)), "mjx_resize_weights")
     w = np.zeros(max(cnt.value, 1), np.float32)
     _check(lib().mjx_resize_weights(int(n_in), int(n_out), int(bool(antialias)), int(X), ctypes.byref(first),
@@ -1056,7 +1095,7 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
     N x 1 x H x 1 needs the keyword -- with padded rows; mean / std are then scalars or have one element.
     torch's current stream is synchronised before the call (the library writes on streams of its
     own) and the batch is complete when this returns.  -> the per-picture statuses.
-    resize: True, or a Resize (its antialias and auto_scale; a size, if it names one, must be the tensor's) -- the pictures, of any
+    resize: True, or a Resize (its antialias, auto_scale and filter; a size, if it names one, must be the tensor's) -- the pictures, of any
     size, are resampled on the device to the tensor's H x W (see Resize); None: every picture must be H x W as it is.
     orient: an Orient -- the pictures are turned on the device (see Orient); H x W and rois speak of the turned pictures.
     pixels: "libjpeg" -- see Batch."""
@@ -1111,7 +1150,7 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
     fmt = Output(names[out.dtype], planar=bool(planar), bgr=bgr, mean=mean, std=std, dst=dst, channels=channels)
     torch.cuda.current_stream(out.device).synchronize()
     if resize is not None and resize is not False:
-        rs = Resize(w, h) if resize is True else Resize(w, h, resize.antialias, resize.auto_scale)
+        rs = Resize(w, h) if resize is True else resize.sized(w, h)
         if resize is not True and (resize.width or resize.height) and (resize.width, resize.height) != (w, h):
             raise MjxError(ERR_INVALID_ARG, "resize to %d x %d into a tensor of %d x %d" % (resize.width, resize.height, w, h))
     else:

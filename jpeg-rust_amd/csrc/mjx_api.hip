@@ -177,9 +177,10 @@ struct Chunk {
     uint32_t max_dc_luma_wgs = 0;  // ... and of k_dc_color_luma for its largest luminance picture
     uint32_t max_dc_ycc_wgs = 0;   // ... and of k_dc_color_ycc for the picture with the most plane samples
     uint32_t max_lj_luma_tiles = 0;                   // luminance pictures: workgroups of k_upsample_luma, k_orient_luma and k_resize_luma (0: none)
-    uint32_t max_or_luma_tiles = 0, max_rso_luma_tiles = 0;
-    uint32_t max_or_tiles = 0, max_rso_tiles = 0;     // orientation on the device: workgroups of k_orient_out for the chunk's largest oriented picture, of k_resize_orient for its largest target (0: none)
-    uint32_t max_rs_tiles = 0;     // resize on the device: workgroups of k_resize_out for the chunk's largest target (0: no picture is resized)
+    uint32_t max_or_luma_tiles = 0, max_rso_luma_tiles[kFilterCount] = {0, 0, 0};
+    uint32_t max_or_tiles = 0, max_rso_tiles[kFilterCount] = {0, 0, 0};     // orientation on the device: workgroups of k_orient_out for the chunk's largest oriented picture, of k_resize_orient for its largest target (0: none)
+    uint32_t max_rs_tiles[kFilterCount] = {0, 0, 0};     // resize on the device: workgroups of k_resize_out for the chunk's largest target (0: no picture is resized)
+                                   // (the resize forms per filter kind, DevImage::rs_filter: a kind no picture of the chunk has launches nothing)
     uint32_t max_b_tiles = 0;      // tiles the workgroups of stage B walk in the chunk's largest picture: all its tiles, or those of its
                                    // rectangle's MCU rows (DevImage::roi_ntiles) -- max_tiles without rectangles
     uint32_t min_sub_bits = 0xffffffffu;   // shortest subsequence length among its scans (chunk_fix_passes)
@@ -522,7 +523,7 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
         d.rs_on = p.rs_on && p.orient == 1 ? 1u : 0u;
         d.orient = p.orient;                                     // (an oriented picture is k_orient_out's or k_resize_orient's)
         d.or_on = !p.rs_on || p.orient == 1 ? 0u : p.or_copy ? 1u : 2u;
-        d.rs_w = p.rs_w; d.rs_h = p.rs_h; d.rs_aa = p.rs_aa;
+        d.rs_w = p.rs_w; d.rs_h = p.rs_h; d.rs_aa = p.rs_aa; d.rs_filter = p.rs_filter;
         d.out_dev = p.out_dev;
         d.out_row_pitch = p.out_row_pitch; d.out_plane_pitch = p.out_plane_pitch;
         d.out_dtype = p.out_dtype; d.out_planar = p.out_planar; d.out_bgr = p.out_bgr;
@@ -674,10 +675,10 @@ void plan_chunks(mjx_batch *b)
                 }
                 if (d.mode == 5 + kLumaMode) c.max_dc_luma_wgs = std::max<uint32_t>(c.max_dc_luma_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
                 if (d.or_on == 3 && d.role != 1) c.max_or_luma_tiles = std::max<uint32_t>(c.max_or_luma_tiles, orient_tiles(d.rs_w, d.rs_h));
-                if (d.or_on == 4 && d.role != 1) c.max_rso_luma_tiles = std::max<uint32_t>(c.max_rso_luma_tiles, resize_tiles(d.rs_w, d.rs_h));
-                if (d.rs_on && d.role != 1) c.max_rs_tiles = std::max<uint32_t>(c.max_rs_tiles, resize_tiles(d.rs_w, d.rs_h));
+                if (d.or_on == 4 && d.role != 1) c.max_rso_luma_tiles[d.rs_filter] = std::max<uint32_t>(c.max_rso_luma_tiles[d.rs_filter], resize_tiles(d.rs_w, d.rs_h));
+                if (d.rs_on && d.role != 1) c.max_rs_tiles[d.rs_filter] = std::max<uint32_t>(c.max_rs_tiles[d.rs_filter], resize_tiles(d.rs_w, d.rs_h));
                 if (d.or_on == 1 && d.role != 1) c.max_or_tiles = std::max<uint32_t>(c.max_or_tiles, orient_tiles(d.rs_w, d.rs_h));
-                if (d.or_on == 2 && d.role != 1) c.max_rso_tiles = std::max<uint32_t>(c.max_rso_tiles, resize_tiles(d.rs_w, d.rs_h));
+                if (d.or_on == 2 && d.role != 1) c.max_rso_tiles[d.rs_filter] = std::max<uint32_t>(c.max_rso_tiles[d.rs_filter], resize_tiles(d.rs_w, d.rs_h));
                 if (d.mode == 5 + kRoiMode) c.max_dc_roi_wgs = std::max<uint32_t>(c.max_dc_roi_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
                 if (d.mode == 2) {
                     d.plane_off = c.plane_words;
@@ -1010,9 +1011,9 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
             launch_upsample_color(sp, c.max_lj_luma_tiles, nimg, imgs, reinterpret_cast<const uint8_t *>(SCR(d_planes)), b->d_rgb, b->d_img_flags, true);
             prof_end(b, sp);
         }
-        if (c.max_rs_tiles) {          // resize on the device: the chunk's intermediates -> the target pictures, behind its stage B
+        for (uint32_t f = 0; f < kFilterCount; f++) if (c.max_rs_tiles[f]) {   // resize on the device: the chunk's intermediates -> the target pictures, behind its stage B
             prof_begin(b, MJX_K_RESIZE, sp);
-            launch_resize_out(sp, c.max_rs_tiles, nimg, imgs, b->d_rgb, b->d_img_flags);
+            launch_resize_out(sp, c.max_rs_tiles[f], nimg, imgs, b->d_rgb, b->d_img_flags, f);
             prof_end(b, sp);
         }
         if (c.max_or_tiles) {          // orientation on the device, the same class: the pass behind stage B that brings a picture to the form it leaves in
@@ -1020,9 +1021,9 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
             launch_orient_out(sp, c.max_or_tiles, nimg, imgs, b->d_rgb, b->d_img_flags);
             prof_end(b, sp);
         }
-        if (c.max_rso_tiles) {
+        for (uint32_t f = 0; f < kFilterCount; f++) if (c.max_rso_tiles[f]) {
             prof_begin(b, MJX_K_RESIZE, sp);
-            launch_resize_orient(sp, c.max_rso_tiles, nimg, imgs, b->d_rgb, b->d_img_flags);
+            launch_resize_orient(sp, c.max_rso_tiles[f], nimg, imgs, b->d_rgb, b->d_img_flags, false, f);
             prof_end(b, sp);
         }
         if (c.max_or_luma_tiles) {     // the same passes for luminance pictures: one-byte intermediates, one element per pixel
@@ -1030,9 +1031,9 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
             launch_orient_out(sp, c.max_or_luma_tiles, nimg, imgs, b->d_rgb, b->d_img_flags, true);
             prof_end(b, sp);
         }
-        if (c.max_rso_luma_tiles) {
+        for (uint32_t f = 0; f < kFilterCount; f++) if (c.max_rso_luma_tiles[f]) {
             prof_begin(b, MJX_K_RESIZE, sp);
-            launch_resize_orient(sp, c.max_rso_luma_tiles, nimg, imgs, b->d_rgb, b->d_img_flags, true);
+            launch_resize_orient(sp, c.max_rso_luma_tiles[f], nimg, imgs, b->d_rgb, b->d_img_flags, true, f);
             prof_end(b, sp);
         }
         if (sp != st) {
@@ -2107,7 +2108,11 @@ extern "C" int mjx_resize_plan(const mjx_scan_desc *desc, const mjx_opts *opts, 
     if (rect) *rect = mjx_rect{p.roi_x, p.roi_y, p.roi_w, p.roi_h};
     auto taps = [&](uint32_t n_in, uint32_t n_out) {
         uint32_t t = 0;
-        for (uint32_t X = 0; X < n_out; X++) { const ResizeAxis a = resize_window(n_in, n_out, p.rs_aa != 0, X); t = std::max(t, a.hi - a.lo); }
+        for (uint32_t X = 0; X < n_out; X++) {
+            if (p.rs_filter == kFilterBicubic) { const ResizeTaps a = resize_taps_window<kFilterBicubic>(n_in, n_out, p.rs_aa != 0, X); t = std::max(t, a.hi - a.lo); }
+            else if (p.rs_filter == kFilterNearest) t = 1;
+            else { const ResizeAxis a = resize_window(n_in, n_out, p.rs_aa != 0, X); t = std::max(t, a.hi - a.lo); }
+        }
         return t;
     };
     if (taps_x) *taps_x = taps(p.roi_w, p.rs_w);
@@ -2125,6 +2130,28 @@ extern "C" int mjx_resize_weights(uint32_t n_in, uint32_t n_out, int antialias, 
     if (first) *first = a.lo;
     if (count) *count = a.hi - a.lo;
     for (uint32_t j = a.lo; j < a.hi && weights && size_t(j - a.lo) < cap; j++) weights[j - a.lo] = float(resize_num(a, j)) / a.sum;
+    return MJX_OK;
+}
+
+// ... of any filter kind (resize_taps, the routine the bicubic and nearest kernels run): the window's weights with the folded
+// border taps of the no-antialias bicubic added in, divided by the sum the kernel divides by
+template <uint32_t FILTER>
+static void resize_filter_weights(uint32_t n_in, uint32_t n_out, bool aa, uint32_t X, uint32_t *first, float *weights, size_t cap, size_t *count)
+{
+    const ResizeTaps a = resize_taps<FILTER>(n_in, n_out, aa, X);
+    if (first) *first = a.lo;
+    if (count) *count = a.hi - a.lo;
+    int32_t t = a.t_lo;
+    for (uint32_t j = a.lo; j < a.hi && weights && size_t(j - a.lo) < cap; j++, t += a.step) weights[j - a.lo] = resize_tap_at<FILTER>(a, j, t) / a.sum;
+}
+extern "C" int mjx_resize_filter_weights(uint32_t n_in, uint32_t n_out, int filter, int antialias, uint32_t X, uint32_t *first, float *weights,
+                                         size_t cap, size_t *count)
+{
+    if (filter == int(kFilterTriangle)) return mjx_resize_weights(n_in, n_out, antialias, X, first, weights, cap, count);
+    if (filter < 0 || filter >= int(kFilterCount)) return MJX_ERR_INVALID_ARG;
+    if (!n_in || !n_out || n_in > kResizeMaxDim || n_out > kResizeMaxDim || X >= n_out) return MJX_ERR_INVALID_ARG;
+    if (filter == int(kFilterBicubic)) resize_filter_weights<kFilterBicubic>(n_in, n_out, antialias != 0, X, first, weights, cap, count);
+    else resize_filter_weights<kFilterNearest>(n_in, n_out, false, X, first, weights, cap, count);
     return MJX_OK;
 }
 
@@ -2257,7 +2284,7 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
             p.rs_on = src->himages[k].rs_on != 0 || src->himages[k].or_on != 0;       // (... and its resize and orientation)
             p.orient = src->himages[k].or_on ? src->himages[k].orient : 1u;
             p.or_copy = src->himages[k].or_on == 1 || src->himages[k].or_on == 3;
-            p.rs_w = src->himages[k].rs_w; p.rs_h = src->himages[k].rs_h; p.rs_aa = src->himages[k].rs_aa;
+            p.rs_w = src->himages[k].rs_w; p.rs_h = src->himages[k].rs_h; p.rs_aa = src->himages[k].rs_aa; p.rs_filter = src->himages[k].rs_filter;
             if (fi.ycc_on) {                                                          // (... and its plane description)
                 const DevImage &sd = src->himages[k];
                 p.ycc_on = true;

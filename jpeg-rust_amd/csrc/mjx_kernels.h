@@ -113,8 +113,10 @@ struct DevImage {
     // resize on the device (mjx_resize; rs_on): stage B writes the picture as a packed (cropped) one -- roi_w x roi_h x 3 bytes at
     // rgb_off, mode below kOutMode -- and k_resize_out resamples that to rs_w x rs_h elements per channel in the format out_* above
     // describe, at out_dev or, out_dev == 0, at byte rs_off of the batch's picture pool.
+    // rs_filter: the filter kind (MJX_RESIZE_FILTER: 0 triangle, 1 bicubic, 2 nearest), also of k_resize_orient's and k_resize_luma's pictures
     uint32_t rs_on, rs_w, rs_h, rs_aa;
     uint64_t rs_off;
+    uint32_t rs_filter;
     // orientation on the device (mjx_orient; or_on): the picture that leaves is orient_c(S), S the packed intermediate above, c =
     // orient (an EXIF code 2 .. 8; a picture whose code is 1 has or_on = 0 and is planned as if there were no orientation).
     // or_on = 1: k_orient_out copies S to rs_w x rs_h = the oriented size, element by element through the formats' table, to out_dev
@@ -413,6 +415,105 @@ MJX_HD ResizeAxis resize_axis(uint32_t n_in, uint32_t n_out, bool antialias, uin
     uint64_t sum = 0;       // (a whole number; 65535 -> 1 passes 2^32)
     for (uint32_t j = a.lo; j < a.hi; j++) sum += resize_num(a, j);
     a.sum = float(sum);
+    return a;
+}
+
+// ---- the filter kinds beside the triangle (mjx_resize's filter byte: MJX_FILTER_BICUBIC, MJX_FILTER_NEAREST) ----------------------
+// The positions are the triangle's: c = q + rem / (2 n_out) in lowest terms, tap j at t_j / (2 n_out), its distance in units of the
+// filter's scale x = |t_j| / 2F (F as above; F = n_out whenever the filter does not widen).  What differs is the support and the weight:
+//   bicubic, antialias:  a = -0.5,  taps with x < 2: [floor(c - 2 fs + 1/2), floor(c + 2 fs + 1/2)), clipped to [0, n_in) and divided
+//                        by their sum
+//   bicubic, no antialias: a = -0.75, F = n_out, the four taps floor(c - 1/2) - 1 ... + 2 (the same window formula at fs = 1);
+//                        a tap outside [0, n_in) reads the edge sample, so its weight is ADDED to tap 0's (fold_lo) or tap
+//                        n_in - 1's (fold_hi) and the divisor is 1: nothing is renormalised
+//   nearest:             the one tap q, weight 1
+// The weight is evaluated in float32 from the quotient x = float(|t_j|) / float(2F) by the Horner forms of resize_cubic: x = 0, 1
+// and 2 give exactly 1, 0 and 0, so equal sizes (t_j = 2 (j - X), 2F = 2) leave the tap j = X alone with weight 1 and sum 1.
+// Explicit fmaf everywhere: host and device round alike whatever the compiler would contract.
+// The kernels (resize_body), mjx_resize_filter_weights and mjx_resize_plan run these routines.
+constexpr uint32_t kFilterTriangle = 0, kFilterBicubic = 1, kFilterNearest = 2, kFilterCount = 3;
+MJX_HD float resize_cubic(float x, float a)      // k_a(x), x >= 0
+{
+    if (x < 1.0f) return __builtin_fmaf(__builtin_fmaf(a + 2.0f, x, -(a + 3.0f)), x * x, 1.0f);
+    if (x < 2.0f) return a * __builtin_fmaf(__builtin_fmaf(x - 5.0f, x, 8.0f), x, -4.0f);
+    return 0.0f;
+}
+struct ResizeTaps {
+    uint32_t lo, hi;        // taps [lo, hi), inside [0, n_in)
+    uint32_t last;          // n_in - 1
+    int32_t t_lo;           // t_j at j = lo; t_(j+1) = t_j + step
+    int32_t step;           // 2 n_out
+    int32_t full;           // 2 F
+    float a;                // the cubic's parameter
+    float fold_lo, fold_hi; // no antialias: the weights of the taps below 0 / at and above n_in (else 0)
+    float sum;              // the divisor: the float32 sum of the window's weights in ascending order, or 1 where nothing is renormalised
+};
+// the unfolded weight of a tap from its t (any tap: 0 outside the support)
+template <uint32_t FILTER>
+MJX_HD float resize_tap(int32_t t, int32_t step, int32_t full, float a)
+{
+    if constexpr (FILTER == kFilterNearest) return 2 * int64_t(t) > -int64_t(step) && 2 * int64_t(t) <= int64_t(step) ? 1.0f : 0.0f;   // (t_q = n_out - rem, rem in [0, 2 n_out))
+    else { const int32_t m = t < 0 ? -t : t; return resize_cubic(float(m) / float(full), a); }
+}
+// the weight tap j of the window has in the sum: its own and what folds onto it
+template <uint32_t FILTER>
+MJX_HD float resize_tap_at(const ResizeTaps &a, uint32_t j, int32_t t)
+{
+    float w = resize_tap<FILTER>(t, a.step, a.full, a.a);
+    if constexpr (FILTER == kFilterBicubic) {
+        if (j == 0u) w += a.fold_lo;
+        if (j == a.last) w += a.fold_hi;
+    }
+    return w;
+}
+// the window, the first tap's offset and the folded weights, without the sum
+template <uint32_t FILTER>
+MJX_HD ResizeTaps resize_taps_window(uint32_t n_in, uint32_t n_out, bool antialias, uint32_t X)
+{
+    static_assert(FILTER == kFilterBicubic || FILTER == kFilterNearest, "the triangle is resize_window's");
+    ResizeTaps a;
+    uint32_t g = n_in, g2 = n_out;
+    while (g2) { const uint32_t r = g % g2; g = g2; g2 = r; }
+    const uint64_t ni = n_in / g, no = n_out / g;
+    const uint64_t num = (2ull * X + 1ull) * ni, den = 2ull * no;
+    const uint64_t q = num / den, rem = num - q * den;
+    const uint64_t F = FILTER == kFilterBicubic && antialias && ni > no ? ni : no;
+    a.last = n_in - 1u;
+    a.step = int32_t(den);
+    a.full = int32_t(2 * F);
+    a.a = antialias ? -0.5f : -0.75f;
+    a.fold_lo = a.fold_hi = 0.0f;
+    a.sum = 1.0f;
+    if constexpr (FILTER == kFilterNearest) {
+        a.lo = uint32_t(q); a.hi = a.lo + 1u;            // (q <= n_in - 1: (2X + 1) n_in < 2 n_out n_in)
+        a.t_lo = int32_t(int64_t(no) - int64_t(rem));
+        return a;
+    }
+    // floor((num + no -+ 4F) / den): the first tap and one past the last, before clipping
+    const int64_t lo_num = int64_t(num) + int64_t(no) - int64_t(4 * F);
+    const int64_t lo_raw = lo_num >= 0 ? lo_num / int64_t(den) : -((-lo_num + int64_t(den) - 1) / int64_t(den));
+    const int64_t hi_raw = int64_t((num + no + 4 * F) / den);
+    a.lo = lo_raw > 0 ? uint32_t(lo_raw) : 0u;
+    a.hi = hi_raw < int64_t(n_in) ? uint32_t(hi_raw) : n_in;
+    a.t_lo = int32_t((2 * (int64_t(a.lo) - int64_t(q)) + 1) * int64_t(no) - int64_t(rem));
+    if (!antialias) {                                    // (four taps: at most two on either side)
+        for (int64_t j = lo_raw; j < 0; j++)
+            a.fold_lo += resize_tap<FILTER>(int32_t((2 * (j - int64_t(q)) + 1) * int64_t(no) - int64_t(rem)), a.step, a.full, a.a);
+        for (int64_t j = int64_t(n_in); j < hi_raw; j++)
+            a.fold_hi += resize_tap<FILTER>(int32_t((2 * (j - int64_t(q)) + 1) * int64_t(no) - int64_t(rem)), a.step, a.full, a.a);
+    }
+    return a;
+}
+template <uint32_t FILTER>
+MJX_HD ResizeTaps resize_taps(uint32_t n_in, uint32_t n_out, bool antialias, uint32_t X)
+{
+    ResizeTaps a = resize_taps_window<FILTER>(n_in, n_out, antialias, X);
+    if (FILTER == kFilterBicubic && antialias) {
+        float sum = 0.0f;
+        int32_t t = a.t_lo;
+        for (uint32_t j = a.lo; j < a.hi; j++, t += a.step) sum += resize_tap<FILTER>(t, a.step, a.full, a.a);
+        a.sum = sum;
+    }
     return a;
 }
 
@@ -782,12 +883,15 @@ void launch_dc_color_luma(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg,
 void launch_dc_color_ycc(hipStream_t st, uint32_t max_sample_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
                          const float *qmult, uint8_t *rgb, const uint32_t *img_flags);
 // resize on the device: one workgroup per tile of the target (resize_tiles) and picture with DevImage::rs_on, behind stage B
-void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
+// (filter: the kind of the pictures the launch is for -- kFilterTriangle, kFilterBicubic, kFilterNearest; the others are passed over)
+void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags,
+                       uint32_t filter = 0);
 // orientation on the device, behind stage B like the resize: one workgroup per tile of D (orient_tiles) and picture with or_on == 1
 // (k_orient_out), or per tile of the target (resize_tiles) and picture with or_on == 2 (k_resize_orient)
 // luma: the one-channel forms for luminance pictures -- or_on == 3 (k_orient_luma), or_on == 4 (k_resize_luma, any code, 1 included)
 void launch_orient_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma = false);
-void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma = false);
+void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma = false,
+                          uint32_t filter = 0);
 // libjpeg's pixels, behind stage B: one workgroup per tile of the rectangle (lj_tiles) and picture with DevImage::lj_on
 void launch_upsample_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
                            const uint32_t *img_flags, bool luma = false /* k_upsample_luma: pictures with DevImage::lj_luma */);

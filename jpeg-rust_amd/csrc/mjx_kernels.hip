@@ -4499,12 +4499,17 @@ __device__ __forceinline__ void out_store1f(const OutFmt &f, uint64_t at, float 
 // ORIENT (k_resize_orient): the filter runs on D = orient_c(I), I the intermediate -- w_in and h_in are D's axes and the horizontal
 // pass reaches D(j, row) through orient_map's base and strides; the identity form (k_resize_out) keeps its own addressing.
 // CH: the channels of the intermediate and of the target -- 3, or 1 for a luminance picture (always the ORIENT form: or_on == 4, any code)
-template <bool ORIENT, int CH = 3>
+// FILTER: the filter kind (DevImage::rs_filter; a kernel passes over the pictures of another kind).  The triangle keeps its whole-number
+// numerators; bicubic and nearest (resize_taps, mjx_kernels.h) weigh in float32 -- signed weights, so the sums over- and undershoot
+// and out_store1f's clamp works on both sides -- and add the folded border weights of the no-antialias form at a window's first and
+// last sample; one division by (sum x)(sum y) at the end as before (1 where nothing is renormalised).  Nearest runs the same two
+// passes with one tap each: its sample is the byte itself, so every format is mjx_output's table bit for bit.
+template <bool ORIENT, int CH = 3, uint32_t FILTER = kFilterTriangle>
 __device__ __forceinline__ void resize_body(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
 {
     const DevImage &im = images[blockIdx.y];
     static_assert(CH == 3 || (CH == 1 && ORIENT), "the luminance form is the oriented one");
-    if (!im.valid || (CH == 1 ? im.or_on != 4u : ORIENT ? im.or_on != 2u : !im.rs_on) || img_flags[im.status_idx]) return;
+    if (!im.valid || (CH == 1 ? im.or_on != 4u : ORIENT ? im.or_on != 2u : !im.rs_on) || im.rs_filter != FILTER || img_flags[im.status_idx]) return;
     const bool swaps = ORIENT && orient_swaps(im.orient);
     const uint32_t W = im.rs_w, H = im.rs_h, w_in = swaps ? im.roi_h : im.roi_w, h_in = swaps ? im.roi_w : im.roi_h;
     int64_t o_base = 0, o_sx = 0, o_sy = 0;                // bytes
@@ -4521,16 +4526,27 @@ __device__ __forceinline__ void resize_body(const DevImage *__restrict__ images,
     const uint32_t lx = threadIdx.x & (kRsTileW - 1), ly = threadIdx.x / kRsTileW;       // (ly: the wave)
     const uint32_t X = tile_x * kRsTileW + lx, Y0 = tile_y * kRsTileH;
     // (a lane past the right or bottom edge works on the last column / row -- the barriers stay uniform -- and stores nothing)
-    const ResizeAxis ax = resize_axis(w_in, W, aa, X < W ? X : W - 1u);
+    constexpr bool TRI = FILTER == kFilterTriangle, FOLD = FILTER == kFilterBicubic;
+    constexpr uint32_t FT = TRI ? kFilterBicubic : FILTER;       // (names a routine the triangle's branches never call)
+    using Axis = std::conditional_t<TRI, ResizeAxis, ResizeTaps>;
+    Axis ax;
+    if constexpr (TRI) ax = resize_axis(w_in, W, aa, X < W ? X : W - 1u);
+    else ax = resize_taps<FT>(w_in, W, aa, X < W ? X : W - 1u);
     const uint32_t Y1 = (Y0 + kRsTileH < H ? Y0 + kRsTileH : H) - 1u;
-    const uint32_t row_lo = resize_window(h_in, H, aa, Y0).lo, row_hi = resize_window(h_in, H, aa, Y1).hi;
+    uint32_t row_lo, row_hi;
+    if constexpr (TRI) { row_lo = resize_window(h_in, H, aa, Y0).lo; row_hi = resize_window(h_in, H, aa, Y1).hi; }
+    else { row_lo = resize_taps_window<FT>(h_in, H, aa, Y0).lo; row_hi = resize_taps_window<FT>(h_in, H, aa, Y1).hi; }
     int32_t ty[kRsRows];            // numerator offset t of the lane's output row k at the source row the loop stands at
     float sy[kRsRows], acc[kRsRows][CH];
+    [[maybe_unused]] float fy_lo[kRsRows], fy_hi[kRsRows];      // FOLD: what row 0 / row h_in - 1 carries on top of its own weight
     int32_t ystep = 0, yfull = 0;
+    [[maybe_unused]] float ya = 0.0f;
 #pragma unroll
     for (uint32_t k = 0; k < kRsRows; k++) {
         const uint32_t Y = Y0 + ly + 4u * k;
-        const ResizeAxis a = resize_axis(h_in, H, aa, Y < H ? Y : H - 1u);
+        Axis a;
+        if constexpr (TRI) a = resize_axis(h_in, H, aa, Y < H ? Y : H - 1u);
+        else { a = resize_taps<FT>(h_in, H, aa, Y < H ? Y : H - 1u); ya = a.a; fy_lo[k] = a.fold_lo; fy_hi[k] = a.fold_hi; }
         ty[k] = a.t_lo - int32_t(a.lo - row_lo) * a.step;
         sy[k] = a.sum;
         ystep = a.step; yfull = a.full;
@@ -4546,8 +4562,11 @@ __device__ __forceinline__ void resize_body(const DevImage *__restrict__ images,
         }
         int32_t t = ax.t_lo;
         for (uint32_t j = ax.lo; j < ax.hi; j++, t += ax.step) {
-            const int32_t m = t < 0 ? -t : t;
-            const float wn = m < ax.full ? float(ax.full - m) : 0.0f;
+            float wn;
+            if constexpr (TRI) {
+                const int32_t m = t < 0 ? -t : t;
+                wn = m < ax.full ? float(ax.full - m) : 0.0f;
+            } else wn = resize_tap_at<FT>(ax, j, t);
 #pragma unroll
             for (uint32_t k = 0; k < kRsRows; k++) {
                 const uint32_t row = r0 + ly + 4u * k;
@@ -4571,8 +4590,17 @@ __device__ __forceinline__ void resize_body(const DevImage *__restrict__ images,
             for (int c = 0; c < CH; c++) v[c] = s_h[rr][c][lx];
 #pragma unroll
             for (uint32_t k = 0; k < kRsRows; k++) {
-                const int32_t m = ty[k] < 0 ? -ty[k] : ty[k];
-                const float wn = m < yfull ? float(yfull - m) : 0.0f;
+                float wn;
+                if constexpr (TRI) {
+                    const int32_t m = ty[k] < 0 ? -ty[k] : ty[k];
+                    wn = m < yfull ? float(yfull - m) : 0.0f;
+                } else {
+                    wn = resize_tap<FT>(ty[k], ystep, yfull, ya);
+                    if constexpr (FOLD) {
+                        if (r0 + rr == 0u) wn += fy_lo[k];
+                        if (r0 + rr == h_in - 1u) wn += fy_hi[k];
+                    }
+                }
                 ty[k] += ystep;
 #pragma unroll
                 for (int c = 0; c < CH; c++) acc[k][c] = __builtin_fmaf(wn, v[c], acc[k][c]);
@@ -4617,6 +4645,26 @@ extern "C" __global__ __launch_bounds__(256) void k_resize_luma(const DevImage *
 {
     resize_body<true, 1>(images, rgb, img_flags);
 }
+// ... with the bicubic and the nearest filter (mjx_resize's filter byte): launched only for a chunk that holds such a picture
+#define MJX_RESIZE_KERNELS(suffix, filter)                                                                                                  \
+extern "C" __global__ __launch_bounds__(256) void k_resize_out_##suffix(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,    \
+                                                                         const uint32_t *__restrict__ img_flags)                           \
+{                                                                                                                                           \
+    resize_body<false, 3, filter>(images, rgb, img_flags);                                                                                  \
+}                                                                                                                                           \
+extern "C" __global__ __launch_bounds__(256) void k_resize_orient_##suffix(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb, \
+                                                                            const uint32_t *__restrict__ img_flags)                        \
+{                                                                                                                                           \
+    resize_body<true, 3, filter>(images, rgb, img_flags);                                                                                   \
+}                                                                                                                                           \
+extern "C" __global__ __launch_bounds__(256) void k_resize_luma_##suffix(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,   \
+                                                                          const uint32_t *__restrict__ img_flags)                          \
+{                                                                                                                                           \
+    resize_body<true, 1, filter>(images, rgb, img_flags);                                                                                   \
+}
+MJX_RESIZE_KERNELS(cubic, kFilterBicubic)
+MJX_RESIZE_KERNELS(nearest, kFilterNearest)
+#undef MJX_RESIZE_KERNELS
 
 // ---- orientation on the device (mjx_orient; DevImage::or_on == 1): an oriented picture that is not resized --------------------
 // Stage B has written the picture as a packed (cropped) one, S: roi_h x roi_w x 3 bytes at rgb_off.  A workgroup owns a tile of
@@ -5119,19 +5167,23 @@ void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, con
     hipLaunchKernelGGL(k_ref_color, dim3(max_pixel_wgs, nimg), dim3(256), 0, st, images, planes, rgb, img_flags);
 }
 
-void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags)
+void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, uint32_t filter)
 {
-    hipLaunchKernelGGL(k_resize_out, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
+    hipLaunchKernelGGL(filter == kFilterBicubic ? k_resize_out_cubic : filter == kFilterNearest ? k_resize_out_nearest : k_resize_out,
+                       dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
 }
 void launch_orient_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma)
 {
     if (luma) hipLaunchKernelGGL(k_orient_luma, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
     else hipLaunchKernelGGL(k_orient_out, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
 }
-void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma)
+void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma,
+                          uint32_t filter)
 {
-    if (luma) hipLaunchKernelGGL(k_resize_luma, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
-    else hipLaunchKernelGGL(k_resize_orient, dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
+    if (luma) hipLaunchKernelGGL(filter == kFilterBicubic ? k_resize_luma_cubic : filter == kFilterNearest ? k_resize_luma_nearest : k_resize_luma,
+                                 dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
+    else hipLaunchKernelGGL(filter == kFilterBicubic ? k_resize_orient_cubic : filter == kFilterNearest ? k_resize_orient_nearest : k_resize_orient,
+                            dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
 }
 
 void launch_upsample_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,

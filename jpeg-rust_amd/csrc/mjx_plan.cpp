@@ -683,6 +683,8 @@ void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_ou
         }
         if (orient_swaps(code)) std::swap(rs_s.width, rs_s.height);
     }
+    // (the filter byte is read from the caller's object: rs_s is a member-wise copy and need not carry it)
+    if (rs && MJX_RESIZE_FILTER(rs) >= kFilterCount) rc = MJX_ERR_INVALID_ARG;
     if (rs && rc == MJX_OK) {
         const mjx_opts in = eff;
         rc = resize_opts(d.width, d.height, in, rs_s, eff, rect);
@@ -694,10 +696,10 @@ void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_ou
     ImagePlan &p = plans.back();
     p.rs_on = true;
     p.orient = code;
-    if (rs) { p.rs_w = rs->width; p.rs_h = rs->height; p.rs_aa = rs->antialias ? 1u : 0u; }
+    if (rs) { p.rs_w = rs->width; p.rs_h = rs->height; p.rs_aa = rs->antialias ? 1u : 0u; p.rs_filter = MJX_RESIZE_FILTER(rs); }
     else {
         p.or_copy = true;
-        p.rs_w = orient_swaps(code) ? p.roi_h : p.roi_w; p.rs_h = orient_swaps(code) ? p.roi_w : p.roi_h; p.rs_aa = 0;
+        p.rs_w = orient_swaps(code) ? p.roi_h : p.roi_w; p.rs_h = orient_swaps(code) ? p.roi_w : p.roi_h; p.rs_aa = 0; p.rs_filter = 0;
     }
     static const mjx_output packed = {MJX_DTYPE_U8, 0, 0, {1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}, nullptr, 0};
     plan_output_of_input(plans, out ? out : &packed, i);

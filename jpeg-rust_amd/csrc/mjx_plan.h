@@ -70,6 +70,7 @@ struct ImagePlan {
     // stage B keeps its packed forms (fill_dev_image).
     bool rs_on = false;
     uint32_t rs_w = 0, rs_h = 0, rs_aa = 0;
+    uint32_t rs_filter = 0;                // MJX_RESIZE_FILTER of the description: 0 triangle, 1 bicubic, 2 nearest
     // orientation on the device (mjx_orient, plan_input_for): orient = the EXIF code 2 .. 8 of a picture that leaves as orient_c(S), S
     // the packed intermediate as above (rs_on is set either way: the pool, the output's rules and the accessors are the resize's).
     // or_copy: there is no resize, rs_w x rs_h is the oriented size of roi_w x roi_h and k_orient_out copies.  Code 1 leaves no trace.

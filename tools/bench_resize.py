@@ -4,11 +4,11 @@
 The batch of bench.py -- 2048 synthetic 3840x2160 4:2:0 q75 pictures, 64 unique ones -- with one seeded random-resized-crop
 rectangle per picture (area 8 .. 100 % of the picture, aspect 3/4 .. 4/3), every picture to 224 x 224 planar float16, ImageNet
 mean / std, in ONE caller-owned 2048 x 3 x 224 x 224 tensor:
-  a_auto    Resize(224, 224, antialias, auto_scale=True): the library picks the DCT-domain scale per picture
+  a_auto    Resize(224, 224, antialias, auto_scale=True, filter=--filter): the library picks the DCT-domain scale per picture
   b_scale1  the same with auto_scale=False at scale 1: the resize kernel filters the full-size rectangle
   c_torch   today's route: the same rectangles decoded packed at scale 1, then per picture
-            torch.nn.functional.interpolate(mode="bilinear", antialias=True) and the normalisation into the tensor, timed to a
-            device synchronise
+            torch.nn.functional.interpolate(mode=--filter, antialias=True) and the normalisation into the tensor, timed to a
+            device synchronise ("nearest" is torch's "nearest-exact")
 Caller-owned destinations cannot be tiled, so every variant builds its batch from the 2048 inputs themselves (the 64 scans, each
 named 32 times).  The variants take turns inside every repeat.
 
@@ -16,6 +16,7 @@ Per variant: ms per step (every repeat, best, median), per-class kernel ms per s
 k_resize_out), the bytes written, the scales auto_scale chose.  One JSON object on the last line.
 
     python tools/bench_resize.py [--steps 5] [--warmup 1] [--repeats 3] [--images 2048] [--variants a_auto,b_scale1,c_torch]
+                                 [--filter bilinear|bicubic|nearest]
 """
 import argparse
 import json
@@ -60,6 +61,7 @@ def main():
     ap.add_argument("--quality", type=int, default=75)
     ap.add_argument("--side", type=int, default=224)
     ap.add_argument("--variants", default="a_auto,b_scale1,c_torch")
+    ap.add_argument("--filter", default="bilinear", choices=("bilinear", "bicubic", "nearest"))
     args = ap.parse_args()
     import torch                         # (first: libmjx.so must find torch's HIP runtime already loaded, as in bench.py)
     import torch.nn.functional as F
@@ -104,12 +106,15 @@ def main():
 
                 def convert():
                     for i in range(n):
-                        x = F.interpolate(views[i].to(torch.float32), size=(side, side), mode="bilinear", align_corners=False, antialias=True)
+                        if args.filter == "nearest":
+                            x = F.interpolate(views[i].to(torch.float32), size=(side, side), mode="nearest-exact")
+                        else:
+                            x = F.interpolate(views[i].to(torch.float32), size=(side, side), mode=args.filter, align_corners=False, antialias=True)
                         tensor[i:i + 1].copy_(torch.addcmul(bi_t, x, sc_t))
             else:
                 fmt = mjx.Output("float16", planar=True, mean=MEAN, std=STD,
                                  dst=[(tensor.data_ptr() + 2 * per * i, side, side, side, side * side) for i in range(n)])
-                b = mjx.Batch(ctx, inputs, rois=rects, output=fmt, resize=mjx.Resize(side, side, antialias=True, auto_scale=(v == "a_auto")))
+                b = mjx.Batch(ctx, inputs, rois=rects, output=fmt, resize=mjx.Resize(side, side, antialias=True, auto_scale=(v == "a_auto"), filter=args.filter))
                 assert all(x == mjx.OK for x in b.create_status)
                 if v not in scales:
                     got = [b.scale(i) for i in range(n)]
@@ -142,7 +147,7 @@ def main():
             finally:
                 b.close()
                 del tensor
-    out = {"images": n, "unique": args.unique, "picture": "%dx%d 4:2:0 q%d" % (W, H, args.quality), "target": side, "steps": args.steps,
+    out = {"filter": args.filter, "images": n, "unique": args.unique, "picture": "%dx%d 4:2:0 q%d" % (W, H, args.quality), "target": side, "steps": args.steps,
            "repeats": args.repeats, "variants": {}}
     for v in names:
         best = min(runs[v], key=lambda x: x["ms_per_step"])
