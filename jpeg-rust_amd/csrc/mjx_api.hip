@@ -155,6 +155,18 @@ struct ImageInfo {
     bool planar = false;           // role 2: read without the gather (no stream of its own: mjx_batch_copy_coefs has nothing to expand)
 };
 
+// The passes behind stage B that bring a picture to the form it leaves in, in the order run_chunk launches them
+enum PostPass : uint32_t {
+    kPassUpsample,          // libjpeg's pixels: the chunk's component planes -> its pictures (or the intermediates of the passes below)
+    kPassUpsampleLuma,      // ... luminance pictures: component 0's plane alone
+    kPassResize,            // resize on the device: the intermediates -> the target pictures (per filter kind)
+    kPassOrient,            // orientation on the device: k_orient_out copies
+    kPassResizeOrient,      // ... k_resize_orient resamples (per filter kind)
+    kPassOrientLuma,        // the same two for luminance pictures: one-byte intermediates, one element per pixel
+    kPassResizeLuma,
+    kPostPasses
+};
+
 struct Chunk {
     size_t first = 0, count = 0;
     uint32_t nsub = 0;             // subsequences in the chunk
@@ -166,21 +178,14 @@ struct Chunk {
     uint32_t loop_participants = 0;     // > 0: the merge rounds run as one launch (k_huff_merge_loop) with this many workgroups
     uint32_t lut2_cap = 0;         // entries of the largest second table set (pair parts, the counting passes)
     uint32_t max_wg = 0, merge_wgs = 0, max_tiles = 0, lut_cap = 0, max_tile_blocks = 0, layout_mask = 0, max_segs = 0, bpm_mask = 0, max_restart_segs = 0;
-    uint64_t mode_mask = 0;        // bit m: the chunk holds a picture of stage-B mode m (kLumaMode + m lies above bit 31)
+    uint64_t mode_mask = 0;        // bit m: the chunk holds a picture of DevImage::mode m (the sinks from kSinkLuma on lie above bit 31)
     uint64_t plane_words = 0;      // REF_COMPAT scratch of the chunk
     uint32_t max_pixel_wgs = 0;
     uint64_t lj_words = 0;         // libjpeg's pixels: the component planes of the chunk's pictures, in the same scratch (a call is one or the other)
-    uint32_t max_lj_tiles = 0;     // ... and the workgroups of k_upsample_color for its largest rectangle (0: no such picture)
-    uint32_t max_dc_wgs = 0;       // scaled decode at 1/8: workgroups of k_dc_color for the chunk's largest picture
-    uint32_t max_dc_roi_wgs = 0;   // ... and of k_dc_color_roi for its largest rectangle
-    uint32_t max_dc_out_wgs = 0;   // ... and of k_dc_color_out for its largest picture with an output description
-    uint32_t max_dc_luma_wgs = 0;  // ... and of k_dc_color_luma for its largest luminance picture
-    uint32_t max_dc_ycc_wgs = 0;   // ... and of k_dc_color_ycc for the picture with the most plane samples
-    uint32_t max_lj_luma_tiles = 0;                   // luminance pictures: workgroups of k_upsample_luma, k_orient_luma and k_resize_luma (0: none)
-    uint32_t max_or_luma_tiles = 0, max_rso_luma_tiles[kFilterCount] = {0, 0, 0};
-    uint32_t max_or_tiles = 0, max_rso_tiles[kFilterCount] = {0, 0, 0};     // orientation on the device: workgroups of k_orient_out for the chunk's largest oriented picture, of k_resize_orient for its largest target (0: none)
-    uint32_t max_rs_tiles[kFilterCount] = {0, 0, 0};     // resize on the device: workgroups of k_resize_out for the chunk's largest target (0: no picture is resized)
-                                   // (the resize forms per filter kind, DevImage::rs_filter: a kind no picture of the chunk has launches nothing)
+    uint32_t max_dc_wgs[kStageBSinks] = {};   // scaled decode at 1/8: per sink, the workgroups of its k_dc_color* kernel for the chunk's largest
+                                   // picture -- a lane per pixel written, per plane sample for kSinkYcc (kSinkPlanes has no 1/8)
+    uint32_t max_pass_tiles[kPostPasses][kFilterCount] = {};   // the passes behind stage B: workgroups for the chunk's largest picture of each pass
+                                   // and filter kind (DevImage::rs_filter; [0] for the passes that have no filter); 0: launches nothing
     uint32_t max_b_tiles = 0;      // tiles the workgroups of stage B walk in the chunk's largest picture: all its tiles, or those of its
                                    // rectangle's MCU rows (DevImage::roi_ntiles) -- max_tiles without rectangles
     uint32_t min_sub_bits = 0xffffffffu;   // shortest subsequence length among its scans (chunk_fix_passes)
@@ -488,72 +493,51 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
     d.valid = 1;
     d.nseg = p.nseg;
     d.restart_mcus = p.restart_mcus;
-    d.mode = (!p.lj && !p.ycc_on && p.ncomp == 3 && p.h[0] == 2 && p.v[0] == 2 && p.h[1] == 1 && p.v[1] == 1 && p.h[2] == 1 && p.v[2] == 1) ? 1 : 0;
+    const StageBChoice sb = stage_b_choice(p);          // what stage B and the passes behind it do with the picture: decided there alone
+    d.mode = sb.mode;
+    d.rs_on = sb.rs_on; d.or_on = sb.or_on; d.out_ch = sb.out_ch;
+    d.lj_on = sb.lj_on; d.lj_luma = sb.lj_luma; d.lj_out = sb.lj_out;
     d.scale = p.scale;
     d.out_w = p.out_w;
     d.out_h = p.out_h;
-    if (p.scale > 1) d.mode = p.scale == 2 ? 3 : p.scale == 4 ? 4 : 5;      // scaled decode: the generic tile (a power of two) below
-    uint32_t t = (d.mode == 1 && p.layout != MJX_LAYOUT_REF_COMPAT) ? tile_mcus_420() : tile_mcus(p.bpm, p.hmax), l2 = 0;
+    uint32_t t = sb.tile_420 ? tile_mcus_420() : tile_mcus(p.bpm, p.hmax), l2 = 0;
     while ((1u << (l2 + 1)) <= t) l2++;
-    if (!(d.mode == 1 && p.layout != MJX_LAYOUT_REF_COMPAT)) t = 1u << l2;      // (the generic pixel phase needs a power of two)
+    if (!sb.tile_420) t = 1u << l2;      // (the generic pixel phase needs a power of two)
     d.log2_tile = l2;
     d.tile_mcus = t;
     d.tile_blocks = t * p.bpm;
     if (p.layout == MJX_LAYOUT_REF_COMPAT) {
-        d.mode = 2;
         for (uint32_t c = 0; c < 3; c++) { d.ref_xf[c] = uint8_t(p.ref_xf[c]); d.ref_yf[c] = uint8_t(p.ref_yf[c]); }
         d.nbx = p.nbx;
         d.nby = p.nby;
     }
     // region-of-interest decode: the rectangle, and the tiles from the one that holds its first MCU to the one that holds its last
-    // (stage B walks these and passes over those among them that hold none of its MCU columns, roi_tile_wanted)
+    // (stage B walks these and passes over those among them that hold none of its MCU columns, roi_tile_wanted); a picture
+    // without a rectangle is its own whole rectangle: every tile
     d.roi_x = p.roi_x; d.roi_y = p.roi_y; d.roi_w = p.roi_w; d.roi_h = p.roi_h;
     d.roi_mr0 = p.roi_mr0; d.roi_mr1 = p.roi_mr1; d.roi_mc0 = p.roi_mc0; d.roi_mc1 = p.roi_mc1;
     d.roi_tile0 = 0;
     d.roi_ntiles = (p.nmcu + t - 1) / t;
     if (p.cropped) {
-        d.mode += kRoiMode;
         d.roi_tile0 = (p.roi_mr0 * p.mcux + p.roi_mc0) / t;
         d.roi_ntiles = (p.roi_mr1 * p.mcux + p.roi_mc1) / t - d.roi_tile0 + 1;
     }
-    // output formats: the forms built on the cropped ones (a picture without a rectangle is its own whole rectangle: every tile above)
-    // (a resized picture keeps the packed forms: its description is k_resize_out's, behind stage B)
-    if (p.out_on) {
-        if (!p.rs_on) d.mode = d.mode % kRoiMode + kOutMode;
-        d.rs_on = p.rs_on && p.orient == 1 ? 1u : 0u;
-        d.orient = p.orient;                                     // (an oriented picture is k_orient_out's or k_resize_orient's)
-        d.or_on = !p.rs_on || p.orient == 1 ? 0u : p.or_copy ? 1u : 2u;
+    if (p.out_on) {          // the output description: stage B's (kSinkOut, kSinkLuma), k_upsample_color's or that of the pass behind them
+        d.orient = p.orient;
         d.rs_w = p.rs_w; d.rs_h = p.rs_h; d.rs_aa = p.rs_aa; d.rs_filter = p.rs_filter;
         d.out_dev = p.out_dev;
         d.out_row_pitch = p.out_row_pitch; d.out_plane_pitch = p.out_plane_pitch;
         d.out_dtype = p.out_dtype; d.out_planar = p.out_planar; d.out_bgr = p.out_bgr;
         for (uint32_t c = 0; c < 3; c++) { d.out_scale[c] = p.out_scale[c]; d.out_bias[c] = p.out_bias[c]; }
-        // luminance: stage B's forms for component 0 alone, whatever follows -- a resized or oriented picture's intermediate is the packed
-        // one-channel picture, which these forms write as well (luma_fmt), and the one-channel passes take it from there (or_on 3, 4:
-        // the three-channel passes pass over the picture)
-        if (p.out_channels == 1) {
-            d.out_ch = 1;
-            d.mode = d.mode % kRoiMode + kLumaMode;
-            d.rs_on = 0;
-            d.or_on = !p.rs_on ? 0u : p.or_copy ? 3u : 4u;
-        }
     }
-    // YCbCr output: the forms that write the component planes as the picture (4:2:0 takes the generic tile, above)
     if (p.ycc_on) {
-        d.mode = d.mode % kRoiMode + kYccMode;
         d.ycc_on = 1; d.ycc_il = p.ycc_il; d.ycc_round = p.ycc_round;
         for (uint32_t c = 0; c < 3; c++) {
             d.ycc_x0[c] = p.ycc_x0[c]; d.ycc_y0[c] = p.ycc_y0[c]; d.ycc_w[c] = p.ycc_w[c]; d.ycc_h[c] = p.ycc_h[c];
             d.ycc_dev[c] = p.ycc_dev[c]; d.ycc_off[c] = p.ycc_off[c]; d.ycc_pitch[c] = p.ycc_pitch[c];
         }
     }
-    // libjpeg's pixels: one plane form for every sampling layout (4:2:0 takes the generic tile), whatever the picture leaves as --
-    // k_upsample_color writes the packed picture (also a resize's or an orientation's intermediate) or the output format
-    if (p.lj) {
-        d.mode = kPlaneMode;
-        d.lj_on = p.out_on && p.out_channels == 1 ? 0u : 1u;       // (a luminance picture is k_upsample_luma's: component 0's plane alone)
-        d.lj_luma = d.lj_on ? 0u : 1u;
-        d.lj_out = p.out_on && !p.rs_on ? 1u : 0u;
+    if (p.lj) {              // libjpeg's pixels: where stage B puts component c's plane in the chunk's scratch
         uint64_t off = 0;
         for (uint32_t c = 0; c < p.ncomp; c++) {
             d.lj_stride[c] = p.mcux * 8 * p.h[c];
@@ -564,7 +548,6 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
     d.role = p.role;
     d.wg_lanes = p.wg_lanes;
     if (p.role == 1) {                // a scan of a multi-scan file: no stage B; one tile offset per block for the gather (build_batch: or segment cuts, seg_S)
-        d.mode = 7;
         d.log2_tile = 0;
         d.tile_mcus = 1;
         d.tile_blocks = 1;
@@ -666,21 +649,24 @@ void plan_chunks(mjx_batch *b)
                 if (d.role != 1) c.layout_mask |= d.planar ? 4u : d.ent_rows ? 2u : 1u;
                 c.bpm_mask |= 1u << d.bpm;
                 if (d.nseg > 1) c.max_restart_segs = std::max(c.max_restart_segs, d.nseg);
-                if (d.mode == 5) c.max_dc_wgs = std::max<uint32_t>(c.max_dc_wgs, uint32_t((uint64_t(d.out_w) * d.out_h + 255) / 256));
-                if (d.mode == 5 + kOutMode) c.max_dc_out_wgs = std::max<uint32_t>(c.max_dc_out_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
-                if (d.mode == 5 + kYccMode) {
-                    uint64_t samples = 0;
-                    for (uint32_t q = 0; q < d.ncomp; q++) samples += uint64_t(d.ycc_w[q]) * d.ycc_h[q];
-                    c.max_dc_ycc_wgs = std::max<uint32_t>(c.max_dc_ycc_wgs, uint32_t((samples + 255) / 256));
+                if (form_of(d.mode) == kFormEighth) {
+                    const StageBSink sink = sink_of(d.mode);
+                    uint64_t lanes = sink == kSinkPacked ? uint64_t(d.out_w) * d.out_h : uint64_t(d.roi_w) * d.roi_h;
+                    if (sink == kSinkYcc) {
+                        lanes = 0;
+                        for (uint32_t q = 0; q < d.ncomp; q++) lanes += uint64_t(d.ycc_w[q]) * d.ycc_h[q];
+                    }
+                    c.max_dc_wgs[sink] = std::max<uint32_t>(c.max_dc_wgs[sink], uint32_t((lanes + 255) / 256));
                 }
-                if (d.mode == 5 + kLumaMode) c.max_dc_luma_wgs = std::max<uint32_t>(c.max_dc_luma_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
-                if (d.or_on == 3 && d.role != 1) c.max_or_luma_tiles = std::max<uint32_t>(c.max_or_luma_tiles, orient_tiles(d.rs_w, d.rs_h));
-                if (d.or_on == 4 && d.role != 1) c.max_rso_luma_tiles[d.rs_filter] = std::max<uint32_t>(c.max_rso_luma_tiles[d.rs_filter], resize_tiles(d.rs_w, d.rs_h));
-                if (d.rs_on && d.role != 1) c.max_rs_tiles[d.rs_filter] = std::max<uint32_t>(c.max_rs_tiles[d.rs_filter], resize_tiles(d.rs_w, d.rs_h));
-                if (d.or_on == 1 && d.role != 1) c.max_or_tiles = std::max<uint32_t>(c.max_or_tiles, orient_tiles(d.rs_w, d.rs_h));
-                if (d.or_on == 2 && d.role != 1) c.max_rso_tiles[d.rs_filter] = std::max<uint32_t>(c.max_rso_tiles[d.rs_filter], resize_tiles(d.rs_w, d.rs_h));
-                if (d.mode == 5 + kRoiMode) c.max_dc_roi_wgs = std::max<uint32_t>(c.max_dc_roi_wgs, uint32_t((uint64_t(d.roi_w) * d.roi_h + 255) / 256));
-                if (d.mode == 2) {
+                auto pass = [&c](PostPass k, uint32_t f, uint32_t tiles) { c.max_pass_tiles[k][f] = std::max(c.max_pass_tiles[k][f], tiles); };
+                if (d.role != 1) {
+                    if (d.rs_on) pass(kPassResize, d.rs_filter, resize_tiles(d.rs_w, d.rs_h));
+                    if (d.or_on == kOrCopy) pass(kPassOrient, 0, orient_tiles(d.rs_w, d.rs_h));
+                    if (d.or_on == kOrResize) pass(kPassResizeOrient, d.rs_filter, resize_tiles(d.rs_w, d.rs_h));
+                    if (d.or_on == kOrCopyLuma) pass(kPassOrientLuma, 0, orient_tiles(d.rs_w, d.rs_h));
+                    if (d.or_on == kOrResizeLuma) pass(kPassResizeLuma, d.rs_filter, resize_tiles(d.rs_w, d.rs_h));
+                }
+                if (d.mode == stage_b_mode(kFormRefCompat, kSinkPacked)) {
                     d.plane_off = c.plane_words;
                     c.plane_words += uint64_t(d.width) * d.height * d.ncomp;
                     c.max_pixel_wgs = std::max<uint32_t>(c.max_pixel_wgs, uint32_t((uint64_t(d.width) * d.height + 255) / 256));
@@ -688,8 +674,7 @@ void plan_chunks(mjx_batch *b)
                 if ((d.lj_on || d.lj_luma) && d.role != 1) {        // (the planes span the MCU grid: whole 64-byte block rows, so every plane starts on a multiple of 8)
                     d.plane_off = c.lj_words;
                     c.lj_words += (d.lj_off[d.ncomp - 1] + uint64_t(d.lj_stride[d.ncomp - 1]) * d.mcuy * 8 * d.cv[d.ncomp - 1]) / 8;
-                    if (d.lj_luma) c.max_lj_luma_tiles = std::max<uint32_t>(c.max_lj_luma_tiles, lj_tiles(d.roi_x, d.roi_w, d.roi_h));
-                    else c.max_lj_tiles = std::max<uint32_t>(c.max_lj_tiles, lj_tiles(d.roi_x, d.roi_w, d.roi_h));
+                    pass(d.lj_luma ? kPassUpsampleLuma : kPassUpsample, 0, lj_tiles(d.roi_x, d.roi_w, d.roi_h));
                 }
                 c.max_segs = std::max<uint32_t>(c.max_segs, (d.nmcu + kDcSegMcus - 1) / kDcSegMcus);
             }
@@ -995,47 +980,28 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
         launch_idct_color(sp, c.max_b_tiles, nimg, b->idct_lds + b->ctx->idct_lds_pad, imgs, SCR(d_entries), SCR(d_tile_eoff), dcb, b->d_qm, b->d_rgb, c.mode_mask, SCR(d_planes), b->d_img_flags,
                           c.scan_bytes > uint64_t(c.tiles) * (1400u * tile_mcus_420() / 32u), c.layout_mask);
         if (c.plane_words) launch_ref_color(sp, c.max_pixel_wgs, nimg, imgs, SCR(d_planes), b->d_rgb, b->d_img_flags);
-        if (c.max_dc_wgs) launch_dc_color(sp, c.max_dc_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags);
-        if (c.max_dc_roi_wgs) launch_dc_color(sp, c.max_dc_roi_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true);
-        if (c.max_dc_out_wgs) launch_dc_color(sp, c.max_dc_out_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, true, true);
-        if (c.max_dc_luma_wgs) launch_dc_color_luma(sp, c.max_dc_luma_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags);
-        if (c.max_dc_ycc_wgs) launch_dc_color_ycc(sp, c.max_dc_ycc_wgs, nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags);
+        for (uint32_t s = 0; s < kStageBSinks; s++) {       // scaled decode at 1/8: every sink's own kernel
+            if (!c.max_dc_wgs[s]) continue;
+            if (s == kSinkLuma) launch_dc_color_luma(sp, c.max_dc_wgs[s], nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags);
+            else if (s == kSinkYcc) launch_dc_color_ycc(sp, c.max_dc_wgs[s], nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags);
+            else launch_dc_color(sp, c.max_dc_wgs[s], nimg, imgs, dcb, b->d_qm, b->d_rgb, b->d_img_flags, s != kSinkPacked, s == kSinkOut);
+        }
         prof_end(b, sp);
-        if (c.max_lj_tiles) {          // libjpeg's pixels: the chunk's component planes -> its pictures (or the intermediates of the passes below)
-            prof_begin(b, MJX_K_RESIZE, sp);
-            launch_upsample_color(sp, c.max_lj_tiles, nimg, imgs, reinterpret_cast<const uint8_t *>(SCR(d_planes)), b->d_rgb, b->d_img_flags);
-            prof_end(b, sp);
-        }
-        if (c.max_lj_luma_tiles) {     // ... luminance pictures: component 0's plane alone
-            prof_begin(b, MJX_K_RESIZE, sp);
-            launch_upsample_color(sp, c.max_lj_luma_tiles, nimg, imgs, reinterpret_cast<const uint8_t *>(SCR(d_planes)), b->d_rgb, b->d_img_flags, true);
-            prof_end(b, sp);
-        }
-        for (uint32_t f = 0; f < kFilterCount; f++) if (c.max_rs_tiles[f]) {   // resize on the device: the chunk's intermediates -> the target pictures, behind its stage B
-            prof_begin(b, MJX_K_RESIZE, sp);
-            launch_resize_out(sp, c.max_rs_tiles[f], nimg, imgs, b->d_rgb, b->d_img_flags, f);
-            prof_end(b, sp);
-        }
-        if (c.max_or_tiles) {          // orientation on the device, the same class: the pass behind stage B that brings a picture to the form it leaves in
-            prof_begin(b, MJX_K_RESIZE, sp);
-            launch_orient_out(sp, c.max_or_tiles, nimg, imgs, b->d_rgb, b->d_img_flags);
-            prof_end(b, sp);
-        }
-        for (uint32_t f = 0; f < kFilterCount; f++) if (c.max_rso_tiles[f]) {
-            prof_begin(b, MJX_K_RESIZE, sp);
-            launch_resize_orient(sp, c.max_rso_tiles[f], nimg, imgs, b->d_rgb, b->d_img_flags, false, f);
-            prof_end(b, sp);
-        }
-        if (c.max_or_luma_tiles) {     // the same passes for luminance pictures: one-byte intermediates, one element per pixel
-            prof_begin(b, MJX_K_RESIZE, sp);
-            launch_orient_out(sp, c.max_or_luma_tiles, nimg, imgs, b->d_rgb, b->d_img_flags, true);
-            prof_end(b, sp);
-        }
-        for (uint32_t f = 0; f < kFilterCount; f++) if (c.max_rso_luma_tiles[f]) {
-            prof_begin(b, MJX_K_RESIZE, sp);
-            launch_resize_orient(sp, c.max_rso_luma_tiles[f], nimg, imgs, b->d_rgb, b->d_img_flags, true, f);
-            prof_end(b, sp);
-        }
+        for (uint32_t k = 0; k < kPostPasses; k++)          // the passes behind stage B, each for the filter kinds the chunk's pictures have
+            for (uint32_t f = 0; f < kFilterCount; f++) {
+                const uint32_t tiles = c.max_pass_tiles[k][f];
+                if (!tiles) continue;
+                prof_begin(b, MJX_K_RESIZE, sp);
+                switch (k) {
+                case kPassUpsample: case kPassUpsampleLuma:
+                    launch_upsample_color(sp, tiles, nimg, imgs, reinterpret_cast<const uint8_t *>(SCR(d_planes)), b->d_rgb, b->d_img_flags, k == kPassUpsampleLuma);
+                    break;
+                case kPassResize: launch_resize_out(sp, tiles, nimg, imgs, b->d_rgb, b->d_img_flags, f); break;
+                case kPassOrient: case kPassOrientLuma: launch_orient_out(sp, tiles, nimg, imgs, b->d_rgb, b->d_img_flags, k == kPassOrientLuma); break;
+                default: launch_resize_orient(sp, tiles, nimg, imgs, b->d_rgb, b->d_img_flags, k == kPassResizeLuma, f); break;
+                }
+                prof_end(b, sp);
+            }
         if (sp != st) {
             HIPOK(hipEventRecord(b->ev_pixels[set], sp));
             b->pixels_recorded[set] = true;
@@ -2283,7 +2249,7 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
             for (uint32_t c = 0; c < 3; c++) { p.out_scale[c] = src->himages[k].out_scale[c]; p.out_bias[c] = src->himages[k].out_bias[c]; }
             p.rs_on = src->himages[k].rs_on != 0 || src->himages[k].or_on != 0;       // (... and its resize and orientation)
             p.orient = src->himages[k].or_on ? src->himages[k].orient : 1u;
-            p.or_copy = src->himages[k].or_on == 1 || src->himages[k].or_on == 3;
+            p.or_copy = src->himages[k].or_on == kOrCopy || src->himages[k].or_on == kOrCopyLuma;
             p.rs_w = src->himages[k].rs_w; p.rs_h = src->himages[k].rs_h; p.rs_aa = src->himages[k].rs_aa; p.rs_filter = src->himages[k].rs_filter;
             if (fi.ycc_on) {                                                          // (... and its plane description)
                 const DevImage &sd = src->himages[k];

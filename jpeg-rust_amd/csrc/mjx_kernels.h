@@ -36,17 +36,17 @@ struct DevImage {
     uint32_t ncomp, bpm, hmax, vmax;
     uint32_t valid;         // 0: skip (error at plan time)
     uint32_t status_idx;    // index into the batch-wide device status array
-    uint32_t log2_tile;     // stage-B tile = 1 << log2_tile MCUs (modes 0 and 2; mode 1: floor(log2(tile_mcus)), unused)
-    uint32_t tile_mcus;     // MCUs per stage-B tile (mode 1: tile_mcus_420(), which need not be a power of two)
-    uint32_t mode;          // stage-B specialisation: 0 generic, 1 = 4:2:0 (Y 2x2, Cb 1x1, Cr 1x1), 2 = REF_COMPAT placement
-                            // (3, 4, 5: scaled decode, below; 7: a scan of a multi-scan file, no stage B; + kRoiMode: the same
-                            // form for a picture with a rectangle -- the forms for whole pictures leave those alone)
+    uint32_t log2_tile;     // stage-B tile = 1 << log2_tile MCUs (kForm420: floor(log2(tile_mcus)), unused)
+    uint32_t tile_mcus;     // MCUs per stage-B tile (kForm420: tile_mcus_420(), which need not be a power of two)
+    uint32_t mode;          // stage-B specialisation: stage_b_mode(form, sink) = form | sink << 3 (StageBForm, StageBSink below) -- what
+                            // stage B computes and how the picture leaves it.  Every kernel form compares the whole number, so the
+                            // forms of one sink leave the pictures of every other alone.
     uint32_t tile_off;      // index of the image's first tile offset in the tile_eoff array
     uint32_t tile_blocks;   // blocks per stage-B tile = tile_mcus * bpm  (<= 256)
     uint8_t blk_comp[kMaxBlocksPerMcu], blk_bx[kMaxBlocksPerMcu], blk_by[kMaxBlocksPerMcu];
     uint8_t ch[4], cv[4];   // sampling factors per component
     uint8_t cfirst[4];      // first block position of each component inside the MCU
-    // REF_COMPAT layout only (mode 2): decoder.rs:239-250 replication factors, block grid, f32 plane scratch
+    // REF_COMPAT layout only (kFormRefCompat): decoder.rs:239-250 replication factors, block grid, f32 plane scratch
     uint8_t ref_xf[4], ref_yf[4];
     uint32_t nbx, nby;
     uint64_t plane_off;     // 64-bit words into the plane scratch (ncomp planes of width*height words)
@@ -92,17 +92,17 @@ struct DevImage {
     uint32_t emit;
     uint32_t emit_head;         // groups of head room in front of the first decode's entries (kEmitHeadGroups; tests shrink it)
     // scaled decode (mjx_opts.scale_denom): 1, 2, 4 or 8; the picture written is out_w x out_h = ceil(width / scale) x
-    // ceil(height / scale).  Modes 3 (1/2) and 4 (1/4) run k_idct_color with a 4- or 2-point inverse DCT on the low corner of
-    // each block, mode 5 (1/8) runs k_dc_color on the DC values alone; qm_off then points at the reduced multipliers.
+    // ceil(height / scale).  kFormHalf and kFormQuarter run k_idct_color with a 4- or 2-point inverse DCT on the low corner of
+    // each block, kFormEighth runs k_dc_color on the DC values alone; qm_off then points at the reduced multipliers.
     uint32_t scale, out_w, out_h;
-    // region-of-interest decode (mjx_opts.rois; mode >= kRoiMode): the rectangle in the coordinates of the out_w x out_h picture
+    // region-of-interest decode (mjx_opts.rois; kSinkCropped and every sink above it): the rectangle in the coordinates of the out_w x out_h picture
     // -- the picture written is roi_w x roi_h, rgb_off its first byte --, the MCU rows and columns that touch it, and the tiles
     // that can: roi_ntiles tiles from roi_tile0 on hold the MCU rows roi_mr0 .. roi_mr1 (roi_tile_wanted says which of them also
     // hold one of the columns).  Without a rectangle: 0, 0, out_w, out_h and all the picture's tiles.
     uint32_t roi_x, roi_y, roi_w, roi_h;
     uint32_t roi_mr0, roi_mr1, roi_mc0, roi_mc1;
     uint32_t roi_tile0, roi_ntiles;
-    // output formats (mjx_output; mode >= kOutMode): the picture leaves as 3 x H x W or H x W x 3 elements of u8 / f16 / f32 in the
+    // output formats (mjx_output; kSinkOut): the picture leaves as 3 x H x W or H x W x 3 elements of u8 / f16 / f32 in the
     // channel order asked for, a float element as fmaf(float(u8), out_scale[c], out_bias[c]) with c the OUTPUT channel.  The first
     // element lies at out_dev (caller-owned memory) or, out_dev == 0, at byte rgb_off of the batch's picture pool; pitches count
     // elements.  Such a picture is its own whole rectangle unless it has one (roi_* above say which either way).
@@ -111,19 +111,19 @@ struct DevImage {
     uint32_t out_dtype, out_planar, out_bgr;
     float out_scale[3], out_bias[3];
     // resize on the device (mjx_resize; rs_on): stage B writes the picture as a packed (cropped) one -- roi_w x roi_h x 3 bytes at
-    // rgb_off, mode below kOutMode -- and k_resize_out resamples that to rs_w x rs_h elements per channel in the format out_* above
+    // rgb_off, kSinkPacked or kSinkCropped -- and k_resize_out resamples that to rs_w x rs_h elements per channel in the format out_* above
     // describe, at out_dev or, out_dev == 0, at byte rs_off of the batch's picture pool.
     // rs_filter: the filter kind (MJX_RESIZE_FILTER: 0 triangle, 1 bicubic, 2 nearest), also of k_resize_orient's and k_resize_luma's pictures
     uint32_t rs_on, rs_w, rs_h, rs_aa;
     uint64_t rs_off;
     uint32_t rs_filter;
     // orientation on the device (mjx_orient; or_on): the picture that leaves is orient_c(S), S the packed intermediate above, c =
-    // orient (an EXIF code 2 .. 8; a picture whose code is 1 has or_on = 0 and is planned as if there were no orientation).
-    // or_on = 1: k_orient_out copies S to rs_w x rs_h = the oriented size, element by element through the formats' table, to out_dev
-    // or byte rs_off of the pool; or_on = 2: k_resize_orient resamples orient_c(S) to rs_w x rs_h (rs_on stays 0: k_resize_out
+    // orient (an EXIF code 2 .. 8; a picture whose code is 1 has or_on = kOrNone and is planned as if there were no orientation).
+    // kOrCopy: k_orient_out copies S to rs_w x rs_h = the oriented size, element by element through the formats' table, to out_dev
+    // or byte rs_off of the pool; kOrResize: k_resize_orient resamples orient_c(S) to rs_w x rs_h (rs_on stays 0: k_resize_out
     // passes over the picture).
     uint32_t orient, or_on;
-    // libjpeg's pixels (mjx_opts.pixels = MJX_PIXELS_LIBJPEG; lj_on, mode kPlaneMode): stage B stores the rounded samples of component c
+    // libjpeg's pixels (mjx_opts.pixels = MJX_PIXELS_LIBJPEG; lj_on, kSinkPlanes): stage B stores the rounded samples of component c
     // as a uint8 plane over the whole MCU grid -- rows of lj_stride[c] = mcux * 8 * ch[c] bytes, mcuy * 8 * cv[c] of them -- at byte
     // plane_off * 8 + lj_off[c] of the chunk's plane scratch, and k_upsample_color makes the picture of them: the packed picture at
     // rgb_off (what a resize or an orientation then works on) or, lj_out = 1, the output format out_* describe.  roi_m* and
@@ -131,14 +131,14 @@ struct DevImage {
     uint32_t lj_on, lj_out;
     uint32_t lj_stride[3];
     uint64_t lj_off[3];
-    // luminance output (MJX_OUTPUT_CHANNELS == 1; out_ch = 1, mode kLumaMode + m): the picture leaves as roi_w x roi_h elements, one per
+    // luminance output (MJX_OUTPUT_CHANNELS == 1; out_ch = 1, kSinkLuma): the picture leaves as roi_w x roi_h elements, one per
     // pixel, rows of out_row_pitch elements at out_dev or byte rgb_off of the pool, a float element as fmaf(float(L), out_scale[0],
-    // out_bias[0]).  Stage B transforms the luminance blocks only.  A resized or oriented luminance picture has rs_on = 0 and or_on = 3
-    // (k_orient_luma copies) or 4 (k_resize_luma resamples orient_c(S), c = 1 included): stage B then writes S as roi_w x roi_h BYTES at
+    // out_bias[0]).  Stage B transforms the luminance blocks only.  A resized or oriented luminance picture has rs_on = 0 and or_on = kOrCopyLuma
+    // (k_orient_luma copies) or kOrResizeLuma (k_resize_luma resamples orient_c(S), c = 1 included): stage B then writes S as roi_w x roi_h BYTES at
     // rgb_off, and the three-channel passes leave the picture alone.  With libjpeg's pixels lj_on stays 0 and lj_luma = 1: stage B's
     // plane form as it is, k_upsample_luma reads component 0's plane.
     uint32_t out_ch, lj_luma;
-    // YCbCr output (mjx_planes; ycc_on, mode kYccMode + m): the picture leaves as its component planes at their own sampling.  Plane c
+    // YCbCr output (mjx_planes; ycc_on, kSinkYcc): the picture leaves as its component planes at their own sampling.  Plane c
     // is the ycc_w[c] x ycc_h[c] samples from (ycc_x0[c], ycc_y0[c]) of component c's plane at the picture's scale (plane_span of the
     // rectangle roi_*), rows of ycc_pitch[c] elements of out_dtype at ycc_dev[c] (caller-owned memory) or, ycc_dev[c] == 0, at byte
     // rgb_off + ycc_off[c] of the batch's pool; a float element is fmaf(float(u8), out_scale[c], out_bias[c]), c the COMPONENT.
@@ -148,11 +148,63 @@ struct DevImage {
     uint32_t ycc_x0[3], ycc_y0[3], ycc_w[3], ycc_h[3];
     uint64_t ycc_dev[3], ycc_off[3], ycc_pitch[3];
 };
-constexpr uint32_t kRoiMode = 8;
-constexpr uint32_t kOutMode = 16;      // + m (0, 1, 3, 4; 5: k_dc_color_out): the forms for pictures with an output description
-constexpr uint32_t kPlaneMode = 24;    // + 0: the form that writes component planes (libjpeg's pixels; 4:2:0 takes the generic form too)
-constexpr uint32_t kLumaMode = 32;     // + m (0, 1, 3, 4; 5: k_dc_color_luma): the forms for luminance pictures -- a bit each in a 64-bit mode mask
-constexpr uint32_t kYccMode = 40;      // + m (0, 3, 4; 5: k_dc_color_ycc): the forms that write component planes as the picture (4:2:0 takes the generic form)
+// DevImage::mode.  The form: what stage B computes per tile.
+enum StageBForm : uint32_t {
+    kFormGeneric = 0,       // any sampling layout
+    kForm420 = 1,           // Y 2x2, Cb 1x1, Cr 1x1 on the 4:2:0 kernel's own tile (tile_mcus_420)
+    kFormRefCompat = 2,     // any sampling layout, REF_COMPAT placement into the plane scratch (k_ref_color finishes the picture)
+    kFormHalf = 3,          // scaled decode at 1/2: the 4-point transform on each block's low corner
+    kFormQuarter = 4,       // ... at 1/4: the 2-point transform
+    kFormEighth = 5,        // ... at 1/8: the DC values alone (the k_dc_color* kernels, not k_idct_color)
+    kFormScan = 7,          // a scan of a multi-scan file (role 1): no stage B
+};
+// The sink: how the picture leaves stage B.  Every sink but kSinkPacked walks the tiles of the picture's rectangle only.
+enum StageBSink : uint32_t {
+    kSinkPacked = 0,        // the whole picture, packed R,G,B bytes
+    kSinkCropped = 1,       // the rectangle's pixels, packed R,G,B bytes (also the intermediate of a resize or an orientation)
+    kSinkOut = 2,           // the picture's output description (DevImage::out_*)
+    kSinkPlanes = 3,        // libjpeg's pixels: rounded component planes in the chunk's scratch, kFormGeneric only (k_upsample_color follows)
+    kSinkLuma = 4,          // luminance: component 0 alone, one element per pixel
+    kSinkYcc = 5,           // YCbCr output: the component planes as the picture (4:2:0 takes kFormGeneric)
+};
+constexpr uint32_t kStageBSinks = 6;
+MJX_HD constexpr uint32_t stage_b_mode(uint32_t form, uint32_t sink) { return form | sink << 3; }
+MJX_HD constexpr StageBForm form_of(uint32_t mode) { return StageBForm(mode & 7u); }
+MJX_HD constexpr StageBSink sink_of(uint32_t mode) { return StageBSink(mode >> 3); }
+
+// Every instantiation of k_idct_color, in the order launch_idct_color launches them: X(form, sink, PF, SRC, layout bit, density).
+// PF / SRC: the kernel's prefetch depth and stream source (0 linear, 1 quad-interleaved, 2 the scans of a multi-scan picture); layout
+// bit: the bit of a chunk's layout_mask that holds pictures of that source; density: which of a chunk's two kinds of linear stream
+// the instantiation is for (kAnyDensity: both).  configure_kernels and launch_idct_color are generated from this list and nothing
+// else names an instantiation: a mode that is not here has no kernel.
+enum StageBDensity : uint32_t { kAnyDensity = 0, kSparse = 1, kDense = 2 };
+#define MJX_STAGE_B_SOURCES(X, F, S) X(F, S, kPrefetch, 0, 1u, kAnyDensity) X(F, S, 8, 1, 2u, kAnyDensity) X(F, S, 8, 2, 4u, kAnyDensity)
+#define MJX_STAGE_B_KERNELS(X)                                                                                                       \
+    MJX_STAGE_B_SOURCES(X, kFormGeneric, kSinkPacked)                                                                                \
+    X(kForm420, kSinkPacked, kPrefetchDense, 0, 1u, kDense) X(kForm420, kSinkPacked, kPrefetch, 0, 1u, kSparse)                      \
+    X(kForm420, kSinkPacked, 16, 1, 2u, kDense) X(kForm420, kSinkPacked, 8, 1, 2u, kSparse) X(kForm420, kSinkPacked, 8, 2, 4u, kAnyDensity) \
+    X(kFormRefCompat, kSinkPacked, kPrefetch, 0, 1u, kAnyDensity) X(kFormRefCompat, kSinkPacked, 8, 1, 2u, kAnyDensity)              \
+    MJX_STAGE_B_SOURCES(X, kFormHalf, kSinkPacked) MJX_STAGE_B_SOURCES(X, kFormQuarter, kSinkPacked)                                 \
+    MJX_STAGE_B_SOURCES(X, kFormGeneric, kSinkCropped) MJX_STAGE_B_SOURCES(X, kForm420, kSinkCropped)                                \
+    MJX_STAGE_B_SOURCES(X, kFormHalf, kSinkCropped) MJX_STAGE_B_SOURCES(X, kFormQuarter, kSinkCropped)                               \
+    MJX_STAGE_B_SOURCES(X, kFormGeneric, kSinkOut) MJX_STAGE_B_SOURCES(X, kForm420, kSinkOut)                                        \
+    MJX_STAGE_B_SOURCES(X, kFormHalf, kSinkOut) MJX_STAGE_B_SOURCES(X, kFormQuarter, kSinkOut)                                       \
+    MJX_STAGE_B_SOURCES(X, kFormGeneric, kSinkPlanes)                                                                                \
+    MJX_STAGE_B_SOURCES(X, kFormGeneric, kSinkLuma) MJX_STAGE_B_SOURCES(X, kForm420, kSinkLuma)                                      \
+    MJX_STAGE_B_SOURCES(X, kFormHalf, kSinkLuma) MJX_STAGE_B_SOURCES(X, kFormQuarter, kSinkLuma)                                     \
+    MJX_STAGE_B_SOURCES(X, kFormGeneric, kSinkYcc) MJX_STAGE_B_SOURCES(X, kFormHalf, kSinkYcc) MJX_STAGE_B_SOURCES(X, kFormQuarter, kSinkYcc)
+#define MJX_STAGE_B_COUNT(F, S, PF, SRC, LAYOUT, DENSITY) +1
+static_assert(0 MJX_STAGE_B_KERNELS(MJX_STAGE_B_COUNT) == 64, "16 packed kernels + 48 of the other sinks (DESIGN.md s3.2)");
+#undef MJX_STAGE_B_COUNT
+
+// DevImage::or_on: the pass behind stage B that brings an oriented (or resized, one-channel) picture to the form it leaves in
+enum OrientPass : uint32_t {
+    kOrNone = 0,
+    kOrCopy = 1,            // k_orient_out copies the packed intermediate
+    kOrResize = 2,          // k_resize_orient resamples it
+    kOrCopyLuma = 3,        // k_orient_luma: the one-byte intermediate of a luminance picture
+    kOrResizeLuma = 4,      // k_resize_luma (any orientation code, 1 included)
+};
 
 // YCbCr output: the samples of component c -- factors (hc, vc) of maxima (hmax, vmax) -- that the rectangle (x, y, w, h) of the
 // out_w x out_h picture covers: columns floor(x hc / hmax) .. ceil((x + w) hc / hmax), rows likewise.  These are the samples the
@@ -785,7 +837,7 @@ inline uint32_t tile_mcus(uint32_t bpm, uint32_t hmax)
 }
 
 
-uint32_t tile_mcus_420();       // MCUs per stage-B tile of the 4:2:0 kernel (mode 1)
+uint32_t tile_mcus_420();       // MCUs per stage-B tile of the 4:2:0 kernel (kForm420)
 
 // ---- launchers (mjx_kernels.hip); all asynchronous on `st` ---------------------------------------------
 #if defined(__HIPCC__) || defined(MJX_WITH_HIP_RUNTIME)
@@ -855,10 +907,8 @@ void launch_dc_scan(hipStream_t st, uint32_t max_segs, uint32_t nimg, const DevI
                     uint32_t *segflag = nullptr, uint32_t gen = 0,
                     uint32_t *fail = nullptr /* device word, set when the one-pass kernel gave up waiting */, uint32_t spin_limit = 1u << 20,
                     bool fault = false /* test knob: a workgroup never publishes */);
-// (max_tiles: the chunk's largest count of tiles a picture's workgroups walk -- DevImage::roi_ntiles; mode_mask bits kRoiMode + m:
-// pictures with a rectangle, which take the forms k_idct_color<kRoiMode + m, ...>; bits kOutMode + m: pictures with an output
-// description, k_idct_color<kOutMode + m, ...>; bits kLumaMode + m: luminance pictures, k_idct_color<kLumaMode + m, ...>; bits
-// kYccMode + m: pictures that leave as component planes, k_idct_color<kYccMode + m, ...>)
+// (max_tiles: the chunk's largest count of tiles a picture's workgroups walk -- DevImage::roi_ntiles; mode_mask bit m: the chunk holds
+// a picture of DevImage::mode m; each entry of MJX_STAGE_B_KERNELS whose mode, layout bit and density are present is launched)
 void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t lds, const DevImage *images,
                        const uint32_t *entries, const uint32_t *tile_eoff, const int32_t *dcbuf, const float *qmult,
                        uint8_t *rgb, uint64_t mode_mask, unsigned long long *planes, const uint32_t *img_flags,
@@ -871,24 +921,24 @@ void launch_rgb_compare(hipStream_t st, uint32_t npairs, uint64_t max_bytes, con
                         unsigned long long *ndiff);
 void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images,
                       const unsigned long long *planes, uint8_t *rgb, const uint32_t *img_flags);
-// scaled decode at 1/8 (mode 5): one lane per output pixel from the blocks' DC values; max_pixel_wgs = the chunk's largest
+// scaled decode at 1/8 (kFormEighth): one lane per output pixel from the blocks' DC values; max_pixel_wgs = the chunk's largest
 // ceil(out_w * out_h / 256)
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
                      const float *qmult, uint8_t *rgb, const uint32_t *img_flags, bool roi = false /* the form for pictures with a rectangle */,
-                     bool out = false /* the form for pictures with an output description (mode 5 + kOutMode) */);
-// ... luminance pictures (mode 5 + kLumaMode): one lane per pixel of the rectangle, component 0's DC value alone
+                     bool out = false /* the form for pictures with an output description (kFormEighth, kSinkOut) */);
+// ... luminance pictures (kFormEighth, kSinkLuma): one lane per pixel of the rectangle, component 0's DC value alone
 void launch_dc_color_luma(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
                           const float *qmult, uint8_t *rgb, const uint32_t *img_flags);
-// ... YCbCr output (mode 5 + kYccMode): one lane per sample of each plane, the components' DC values alone
+// ... YCbCr output (kFormEighth, kSinkYcc): one lane per sample of each plane, the components' DC values alone
 void launch_dc_color_ycc(hipStream_t st, uint32_t max_sample_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,
                          const float *qmult, uint8_t *rgb, const uint32_t *img_flags);
 // resize on the device: one workgroup per tile of the target (resize_tiles) and picture with DevImage::rs_on, behind stage B
 // (filter: the kind of the pictures the launch is for -- kFilterTriangle, kFilterBicubic, kFilterNearest; the others are passed over)
 void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags,
                        uint32_t filter = 0);
-// orientation on the device, behind stage B like the resize: one workgroup per tile of D (orient_tiles) and picture with or_on == 1
-// (k_orient_out), or per tile of the target (resize_tiles) and picture with or_on == 2 (k_resize_orient)
-// luma: the one-channel forms for luminance pictures -- or_on == 3 (k_orient_luma), or_on == 4 (k_resize_luma, any code, 1 included)
+// orientation on the device, behind stage B like the resize: one workgroup per tile of D (orient_tiles) and picture with or_on == kOrCopy
+// (k_orient_out), or per tile of the target (resize_tiles) and picture with or_on == kOrResize (k_resize_orient)
+// luma: the one-channel forms for luminance pictures -- kOrCopyLuma (k_orient_luma), kOrResizeLuma (k_resize_luma, any code, 1 included)
 void launch_orient_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma = false);
 void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma = false,
                           uint32_t filter = 0);

@@ -2746,7 +2746,7 @@ __device__ __forceinline__ void store4_out(const OutFmt &f, const Roi &r, uint32
     }
 }
 
-// ---- luminance output (MJX_OUTPUT_CHANNELS == 1; k_idct_color<kLumaMode + m, ...>; DevImage::out_ch) ----------------------------------
+// ---- luminance output (MJX_OUTPUT_CHANNELS == 1; k_idct_color's kSinkLuma forms; DevImage::out_ch) ----------------------------------
 // Four luminance samples -> four bytes: pack4's conversions (v_cvt_pk_u8_f32 under round-toward-zero, saturating) on the samples
 // themselves -- the byte pack4 writes into all three channels of a pixel whose chroma terms are zero (y + 0 is y).  One opaque asm
 // block, as pack4: no float arithmetic can move inside it, and the mode is nearest-even again when it ends.
@@ -2765,7 +2765,7 @@ __device__ __forceinline__ uint32_t pack4_luma(float y0, float y1, float y2, flo
                  : "v"(y0), "v"(y1), "v"(y2), "v"(y3));
     return o;
 }
-// Where a luminance picture's elements go: its output format, or -- a resized or oriented picture (or_on 3, 4) -- the intermediate,
+// Where a luminance picture's elements go: its output format, or -- a resized or oriented picture (or_on kOrCopyLuma, kOrResizeLuma) -- the intermediate,
 // roi_w x roi_h bytes at rgb_off of the pool.
 __device__ __forceinline__ OutFmt luma_fmt(const DevImage &im, uint8_t *rgb_pool)
 {
@@ -3379,7 +3379,7 @@ __device__ __forceinline__ void pixels_420(uint32_t width, uint32_t height, uint
     }
 }
 
-// Phase 3 for 4:2:0 with an output description (k_idct_color<kOutMode + 1, ...>): pixels_420's ROI form -- the same lane -> strip mapping,
+// Phase 3 for 4:2:0 with an output description (k_idct_color<kForm420 | kSinkOut, ...>): pixels_420's ROI form -- the same lane -> strip mapping,
 // the same reads and the same packed additions, so the bytes are the packed picture's -- with ONE store site: the rows of the
 // lane's strip are walked by a loop that is not unrolled (store4_out is a few hundred instructions of uniform branches; eight
 // copies of it cost the kernel its third wave per SIMD), each row reading its own samples.
@@ -3418,7 +3418,7 @@ __device__ __forceinline__ void pixels_420_out(uint32_t width, uint32_t height, 
     }
 }
 
-// Phase 3 for 4:2:0, luminance output (k_idct_color<kLumaMode + 1, ...>): pixels_420_out's lane -> strip mapping and row loop; a row is
+// Phase 3 for 4:2:0, luminance output (k_idct_color<kForm420 | kSinkLuma, ...>): pixels_420_out's lane -> strip mapping and row loop; a row is
 // one 16-byte read of the lane's four luminance samples, their four conversions and one store site.  The chroma rows of the tile are
 // never read (nor written: the scatter drops their entries and phase 2 passes over their lanes).
 __device__ __forceinline__ void pixels_420_luma(uint32_t width, uint32_t height, uint32_t mcux, const float *tile, uint32_t m0,
@@ -3491,7 +3491,7 @@ __device__ __forceinline__ void pixels_generic_t(const GenShape &g, const float 
         else store4(dst, pack4(p), aligned, npix);
     }
 }
-// ... luminance output (k_idct_color<kLumaMode + 0, ...>): pixels_generic_t's walk, component 0 alone (upsampled by box replication
+// ... luminance output (k_idct_color<kFormGeneric | kSinkLuma, ...>): pixels_generic_t's walk, component 0 alone (upsampled by box replication
 // where it is not the most finely sampled component, as load4 does for any component)
 __device__ __forceinline__ void pixels_generic_luma(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm, const Roi &roi, const OutFmt &of)
 {
@@ -3542,7 +3542,7 @@ __device__ __forceinline__ void pixels_generic(const GenShape &g, const float *t
     }
 }
 
-// Phase 3 of the form that writes component planes (k_idct_color<kPlaneMode, ...>, libjpeg's pixels): the tile's samples leave as
+// Phase 3 of the form that writes component planes (k_idct_color<kFormGeneric | kSinkPlanes, ...>, libjpeg's pixels): the tile's samples leave as
 // bytes clamp(floor(f + 128.5), 0, 255) -- the 128.5 sits on the DC term, pack_u8 floors and saturates --, a lane per row of a
 // block (eight samples, one 8-byte store), into the picture's planes.  These span the whole MCU grid, so nothing is clipped here:
 // k_upsample_color reads only what lies inside the components' true sizes.
@@ -3573,7 +3573,7 @@ __device__ __forceinline__ void planes_store(const DevImage &im, const float *ti
     }
 }
 
-// ---- YCbCr output (mjx_planes; k_idct_color<kYccMode + m, ...>; DevImage::ycc_*) -------------------------------------------------
+// ---- YCbCr output (mjx_planes; k_idct_color's kSinkYcc forms; DevImage::ycc_*) -------------------------------------------------
 // One element of a plane: byte value `u` through the dtype's table (DT: MJX_DTYPE_*, a template argument -- chosen once per tile).
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 // A plane's address comes out of the descriptor as an integer, so the compiler cannot know its address space and would store through
@@ -3671,7 +3671,7 @@ __device__ __forceinline__ YccPlaneL ycc_plane_l(const DevImage &im, uint8_t *rg
     p.dt = im.out_dtype; p.pad_ = 0u;
     return p;
 }
-// Phase 3 of the forms that write component planes as the picture (k_idct_color<kYccMode + m, ...>).  N: samples per block side
+// Phase 3 of the forms that write component planes as the picture (k_idct_color's kSinkYcc forms).  N: samples per block side
 // (8, 4, 2).  Per component the lanes of the workgroup are laid over the tile's blocks of one block row of the MCUs, block column
 // fastest: lane -> (MCU t, block column bx) is fixed for the component (T hc is a power of two that divides 256), the lanes left over
 // take further sample rows, and the loop advances by rows.  Adjacent lanes so hold adjacent blocks of the SAME sample row: a wave's
@@ -3805,7 +3805,7 @@ extern "C" __global__ __launch_bounds__(256) void k_ref_color(const DevImage *im
                                                                uint8_t *rgb, const uint32_t *img_flags)
 {
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || im.mode != 2 || img_flags[im.status_idx]) return;
+    if (!im.valid || im.mode != stage_b_mode(kFormRefCompat, kSinkPacked) || img_flags[im.status_idx]) return;
     const size_t len = size_t(im.width) * im.height;
     const size_t i = size_t(blockIdx.x) * 256 + threadIdx.x;
     if (i >= len) return;
@@ -3925,7 +3925,7 @@ __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *ti
     }
 }
 
-// ... luminance output (k_idct_color<kLumaMode + 3 / 4, ...>): pixels_scaled's walk, component 0 alone
+// ... luminance output (k_idct_color<kFormHalf / kFormQuarter | kSinkLuma, ...>): pixels_scaled's walk, component 0 alone
 template <uint32_t N>
 __device__ __forceinline__ void pixels_scaled_luma(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm, const Roi &roi, const OutFmt &of)
 {
@@ -3959,24 +3959,25 @@ __device__ __forceinline__ void pixels_scaled_luma(const GenShape &g, const floa
 //            then issue the loads of the next tile
 //   phase 2  one lane = one 8x8 block: float AAN inverse DCT in registers (transform.rs:55-87 up to rounding)
 //   phase 3  chroma replication + YCbCr->RGB + packed stores
+//   MODE_ = stage_b_mode(MODE, sink) (DevImage::mode, mjx_kernels.h): MODE the form above, the sink one of the following
 //   SRC  where the entries come from: 0 the picture's linear stream, 1 its quad-interleaved stream, 2 the linear streams of the scans of
 //        a multi-scan picture (planar, above)
-//   ROI  region-of-interest decode (MODE_ = MODE + kRoiMode, the mode of a picture with a rectangle): the workgroups walk only the tiles that
+//   ROI  region-of-interest decode (kSinkCropped, the sink of a picture with a rectangle; true for every sink above it too): the workgroups walk only the tiles that
 //        can touch the rectangle's MCU rows (DevImage::roi_tile0, roi_ntiles) and, among them, only those that hold one of its MCU
 //        columns (roi_tile_wanted: uniform arithmetic, no memory access) -- a tile that is passed over issues no stream fetch, no DC
 //        load, no scatter, no transform and no barrier, and the prefetch chain runs from one wanted tile to the next.  The planar
 //        form (its segment lists are prepared two tiles ahead in a ring of three) walks every tile of the row band.  Phase 3 writes
 //        the rectangle's pixels only (store4_roi); the 4:2:0 form takes plain reads there, so `clean` stays false.
-//   PLANES  libjpeg's pixels (MODE_ = kPlaneMode, every sampling layout): the ROI form over the tiles of the rectangle grown by the
+//   PLANES  libjpeg's pixels (kSinkPlanes, kFormGeneric for every sampling layout): the ROI form over the tiles of the rectangle grown by the
 //        upsampling filter's reach (the planner's roi_m*), phase 3 storing every component's rounded samples as bytes (planes_store);
 //        k_upsample_color makes the picture
-//   OUT  output formats (MODE_ = MODE + kOutMode, the mode of a picture with an output description): the ROI form -- a picture without a
+//   OUT  output formats (kSinkOut, the sink of a picture with an output description): the ROI form -- a picture without a
 //        rectangle is its own whole rectangle --, phase 3 writing the picture's format (store4_out, DevImage::out_*)
-//   YCC  YCbCr output (MODE_ = MODE + kYccMode, MODE 0, 3, 4; mjx_planes): the ROI form with one difference in phases 1-2 -- every
+//   YCC  YCbCr output (kSinkYcc, MODE 0, 3, 4; mjx_planes): the ROI form with one difference in phases 1-2 -- every
 //        component's DC term takes the level shift, as PLANES --, phase 3 storing every component's samples as the picture's planes,
 //        clipped to their true sizes and the rectangle, in the planes' dtype and pitches (planes_out_store; the planes' descriptors
 //        are staged in LDS once per workgroup, so phase 3 loads nothing from HBM)
-//   LUMA  luminance output (MODE_ = MODE + kLumaMode, MJX_OUTPUT_CHANNELS == 1): the OUT form with three differences -- an entry whose
+//   LUMA  luminance output (kSinkLuma, MJX_OUTPUT_CHANNELS == 1): the OUT form with three differences -- an entry whose
 //        block is not component 0's goes to the padding word, as dropped positions do at reduced scale; the DC term and phase 2 run on
 //        luminance blocks only; phase 3 does no colour arithmetic and stores one element per pixel (store4_luma).  The tile keeps the
 //        colour forms' layout (a row per block of the MCU): the chroma rows are cleared with the rest and never touched again.
@@ -3988,15 +3989,17 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                                                      uint8_t *__restrict__ rgb, unsigned long long *__restrict__ planes,
                                                      const uint32_t *__restrict__ img_flags, uint32_t tiles_per_wg)
 {
-    constexpr bool YCC = MODE_ >= int(kYccMode);              // YCbCr output: the cropped form, phase 3 storing the component planes as the picture
-    constexpr bool LUMA = !YCC && MODE_ >= int(kLumaMode);    // luminance output: the cropped form, component 0 alone
-    constexpr bool PLANES = !YCC && !LUMA && MODE_ >= int(kPlaneMode);// libjpeg's pixels: the cropped form again, phase 3 storing component planes
-    constexpr bool OUT = !YCC && !LUMA && !PLANES && MODE_ >= int(kOutMode);   // output formats: the cropped form, the picture its own whole rectangle without one
-    constexpr bool ROI = MODE_ >= int(kRoiMode);
-    constexpr int MODE = MODE_ - (YCC ? int(kYccMode) : LUMA ? int(kLumaMode) : PLANES ? int(kPlaneMode) : OUT ? int(kOutMode) : ROI ? int(kRoiMode) : 0);
-    static_assert(!PLANES || MODE == 0, "the planes are written by the generic form");
-    static_assert(!YCC || MODE == 0 || MODE == 3 || MODE == 4, "component planes: the generic form and its scaled siblings");
-    static_assert(!ROI || MODE != 2, "REF_COMPAT has no rectangles");
+    constexpr int MODE = int(form_of(uint32_t(MODE_)));
+    constexpr StageBSink SINK = sink_of(uint32_t(MODE_));
+    constexpr bool YCC = SINK == kSinkYcc;                    // YCbCr output: the cropped form, phase 3 storing the component planes as the picture
+    constexpr bool LUMA = SINK == kSinkLuma;                  // luminance output: the cropped form, component 0 alone
+    constexpr bool PLANES = SINK == kSinkPlanes;              // libjpeg's pixels: the cropped form again, phase 3 storing component planes
+    constexpr bool OUT = SINK == kSinkOut;                    // output formats: the cropped form, the picture its own whole rectangle without one
+    constexpr bool ROI = SINK != kSinkPacked;                 // every sink but the packed whole picture walks and writes a rectangle
+    static_assert(uint32_t(MODE_) == stage_b_mode(MODE, SINK) && SINK < kStageBSinks && MODE <= int(kFormQuarter), "a mode of MJX_STAGE_B_KERNELS");
+    static_assert(!PLANES || MODE == int(kFormGeneric), "the planes are written by the generic form");
+    static_assert(!YCC || MODE == int(kFormGeneric) || MODE == int(kFormHalf) || MODE == int(kFormQuarter), "component planes: the generic form and its scaled siblings");
+    static_assert(!ROI || MODE != int(kFormRefCompat), "REF_COMPAT has no rectangles");
     // (its own symbol: dynamic LDS arrays of one name share their alignment, and the entropy kernels ask for 2 KiB)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_px[];
     __shared__ float s_qm[3 * 64];
@@ -4326,15 +4329,15 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
 // coefficient stream, only the blocks' DC values.  One lane per output pixel: at 1/8 an MCU is an hmax x vmax patch of the output,
 // and pixel (X, Y) takes block (X h / hmax, Y v / vmax) of each component's plane (box replication, as pixels_scaled).
 // Multi-scan pictures read without the gather keep their DC values in their scans' regions (planar_dc_slot, as stage B finds them).
-// ROI (k_dc_color_roi, mode 5 + kRoiMode): one lane per pixel of the rectangle.
-// OUT (k_dc_color_out, mode 5 + kOutMode): the ROI form writing the picture's output format, one element at a time.
+// ROI (k_dc_color_roi, kFormEighth | kSinkCropped): one lane per pixel of the rectangle.
+// OUT (k_dc_color_out, kFormEighth | kSinkOut): the ROI form writing the picture's output format, one element at a time.
 template <bool ROI, bool OUT = false>
 __device__ __forceinline__ void dc_color_body(const DevImage *__restrict__ images, const int32_t *__restrict__ dcbuf,
                                               const float *__restrict__ qmult, uint8_t *__restrict__ rgb,
                                               const uint32_t *__restrict__ img_flags)
 {
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || im.mode != 5u + (OUT ? kOutMode : ROI ? kRoiMode : 0u) || img_flags[im.status_idx]) return;
+    if (!im.valid || im.mode != stage_b_mode(kFormEighth, OUT ? kSinkOut : ROI ? kSinkCropped : kSinkPacked) || img_flags[im.status_idx]) return;
     const uint32_t ow = ROI ? im.roi_w : im.out_w, oh = ROI ? im.roi_h : im.out_h;
     const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
     if (i >= uint64_t(ow) * oh) return;
@@ -4396,14 +4399,14 @@ extern "C" __global__ __launch_bounds__(256) void k_dc_color_out(const DevImage 
     dc_color_body<true, true>(images, dcbuf, qmult, rgb, img_flags);
 }
 
-// Luminance output at 1/8 (k_dc_color_luma, mode 5 + kLumaMode): one lane per pixel of the rectangle from component 0's DC value alone --
+// Luminance output at 1/8 (k_dc_color_luma, kFormEighth | kSinkLuma): one lane per pixel of the rectangle from component 0's DC value alone --
 // dc_color_body's sample and its store (pack_u8), one element through the formats' table.
 extern "C" __global__ __launch_bounds__(256) void k_dc_color_luma(const DevImage *__restrict__ images, const int32_t *__restrict__ dcbuf,
                                                                    const float *__restrict__ qmult, uint8_t *__restrict__ rgb,
                                                                    const uint32_t *__restrict__ img_flags)
 {
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || im.mode != 5u + kLumaMode || img_flags[im.status_idx]) return;
+    if (!im.valid || im.mode != stage_b_mode(kFormEighth, kSinkLuma) || img_flags[im.status_idx]) return;
     const uint32_t ow = im.roi_w, oh = im.roi_h;
     const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
     if (i >= uint64_t(ow) * oh) return;
@@ -4426,14 +4429,14 @@ extern "C" __global__ __launch_bounds__(256) void k_dc_color_luma(const DevImage
     out_store1(f, uint64_t(row) * f.row_pitch + col, pack_u8(s0, 0, 0) & 0xffu, f.scale[0], f.bias[0]);
 }
 
-// YCbCr output at 1/8 (k_dc_color_ycc, mode 5 + kYccMode): one lane per sample of each plane -- a block gives one sample, its DC value
+// YCbCr output at 1/8 (k_dc_color_ycc, kFormEighth | kSinkYcc): one lane per sample of each plane -- a block gives one sample, its DC value
 // through dc_color_body's expression with the level shift on every component, pack_u8's store, one element through the dtype's table.
 extern "C" __global__ __launch_bounds__(256) void k_dc_color_ycc(const DevImage *__restrict__ images, const int32_t *__restrict__ dcbuf,
                                                                   const float *__restrict__ qmult, uint8_t *__restrict__ rgb,
                                                                   const uint32_t *__restrict__ img_flags)
 {
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || im.mode != 5u + kYccMode || img_flags[im.status_idx]) return;
+    if (!im.valid || im.mode != stage_b_mode(kFormEighth, kSinkYcc) || img_flags[im.status_idx]) return;
     uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
     uint32_t c = 0;
     for (; c < im.ncomp; c++) {
@@ -4498,7 +4501,7 @@ __device__ __forceinline__ void out_store1f(const OutFmt &f, uint64_t at, float 
 }
 // ORIENT (k_resize_orient): the filter runs on D = orient_c(I), I the intermediate -- w_in and h_in are D's axes and the horizontal
 // pass reaches D(j, row) through orient_map's base and strides; the identity form (k_resize_out) keeps its own addressing.
-// CH: the channels of the intermediate and of the target -- 3, or 1 for a luminance picture (always the ORIENT form: or_on == 4, any code)
+// CH: the channels of the intermediate and of the target -- 3, or 1 for a luminance picture (always the ORIENT form: or_on == kOrResizeLuma, any code)
 // FILTER: the filter kind (DevImage::rs_filter; a kernel passes over the pictures of another kind).  The triangle keeps its whole-number
 // numerators; bicubic and nearest (resize_taps, mjx_kernels.h) weigh in float32 -- signed weights, so the sums over- and undershoot
 // and out_store1f's clamp works on both sides -- and add the folded border weights of the no-antialias form at a window's first and
@@ -4509,7 +4512,7 @@ __device__ __forceinline__ void resize_body(const DevImage *__restrict__ images,
 {
     const DevImage &im = images[blockIdx.y];
     static_assert(CH == 3 || (CH == 1 && ORIENT), "the luminance form is the oriented one");
-    if (!im.valid || (CH == 1 ? im.or_on != 4u : ORIENT ? im.or_on != 2u : !im.rs_on) || im.rs_filter != FILTER || img_flags[im.status_idx]) return;
+    if (!im.valid || (CH == 1 ? im.or_on != kOrResizeLuma : ORIENT ? im.or_on != kOrResize : !im.rs_on) || im.rs_filter != FILTER || img_flags[im.status_idx]) return;
     const bool swaps = ORIENT && orient_swaps(im.orient);
     const uint32_t W = im.rs_w, H = im.rs_h, w_in = swaps ? im.roi_h : im.roi_w, h_in = swaps ? im.roi_w : im.roi_h;
     int64_t o_base = 0, o_sx = 0, o_sy = 0;                // bytes
@@ -4639,7 +4642,7 @@ extern "C" __global__ __launch_bounds__(256) void k_resize_orient(const DevImage
 {
     resize_body<true>(images, rgb, img_flags);
 }
-// ... of a luminance picture (or_on == 4): the intermediate is roi_w x roi_h bytes, the target one element per pixel
+// ... of a luminance picture (or_on == kOrResizeLuma): the intermediate is roi_w x roi_h bytes, the target one element per pixel
 extern "C" __global__ __launch_bounds__(256) void k_resize_luma(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,
                                                                  const uint32_t *__restrict__ img_flags)
 {
@@ -4666,7 +4669,7 @@ MJX_RESIZE_KERNELS(cubic, kFilterBicubic)
 MJX_RESIZE_KERNELS(nearest, kFilterNearest)
 #undef MJX_RESIZE_KERNELS
 
-// ---- orientation on the device (mjx_orient; DevImage::or_on == 1): an oriented picture that is not resized --------------------
+// ---- orientation on the device (mjx_orient; DevImage::or_on == kOrCopy): an oriented picture that is not resized --------------------
 // Stage B has written the picture as a packed (cropped) one, S: roi_h x roi_w x 3 bytes at rgb_off.  A workgroup owns a tile of
 // kOrientTile x kOrientTile pixels of D = orient_c(S).  The tile of S that holds the same pixels (orient_rect_to_stored; at most
 // 64 x 64 as well) is read along S's rows -- a wave per row, consecutive lanes consecutive bytes; the rows are 3 w bytes and not
@@ -4680,14 +4683,14 @@ MJX_RESIZE_KERNELS(nearest, kFilterNearest)
 // form serves all eight codes.
 constexpr uint32_t kOrientRowBytes = kOrientTile * 3u + 4u;
 static_assert((kOrientRowBytes / 4u) % 2u == 1u, "k_orient_out: an odd number of words per LDS row");
-// CH: 3, or 1 for a luminance picture (or_on == 3; rows of 17 words, odd as well)
+// CH: 3, or 1 for a luminance picture (or_on == kOrCopyLuma; rows of 17 words, odd as well)
 template <int CH>
 __device__ __forceinline__ void orient_body(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
 {
     constexpr uint32_t kRowBytes = kOrientTile * uint32_t(CH) + 4u;
     static_assert((kRowBytes / 4u) % 2u == 1u, "an odd number of words per LDS row");
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || im.or_on != (CH == 1 ? 3u : 1u) || img_flags[im.status_idx]) return;
+    if (!im.valid || im.or_on != (CH == 1 ? kOrCopyLuma : kOrCopy) || img_flags[im.status_idx]) return;
     const uint32_t code = im.orient, w = im.roi_w, h = im.roi_h;
     const bool swaps = orient_swaps(code), fu = orient_flips_u(code), fv = orient_flips_v(code);
     const uint32_t W = swaps ? h : w, H = swaps ? w : h;
@@ -4904,24 +4907,9 @@ int configure_kernels(size_t huff_lds, size_t idct_lds)
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_huff_prefix), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
     }
     if (e == hipSuccess && idct_lds > 64 * 1024) {
-        const void *fns[] = {reinterpret_cast<const void *>(k_idct_color<0, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<0, 8, 1>),
-                             reinterpret_cast<const void *>(k_idct_color<1, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<1, kPrefetchDense, 0>),
-                             reinterpret_cast<const void *>(k_idct_color<1, 8, 1>), reinterpret_cast<const void *>(k_idct_color<1, 16, 1>),
-                             reinterpret_cast<const void *>(k_idct_color<2, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<2, 8, 1>),
-                             reinterpret_cast<const void *>(k_idct_color<0, 8, 2>), reinterpret_cast<const void *>(k_idct_color<1, 8, 2>),
-                             reinterpret_cast<const void *>(k_idct_color<3, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<3, 8, 1>),
-                             reinterpret_cast<const void *>(k_idct_color<3, 8, 2>), reinterpret_cast<const void *>(k_idct_color<4, kPrefetch, 0>),
-                             reinterpret_cast<const void *>(k_idct_color<4, 8, 1>), reinterpret_cast<const void *>(k_idct_color<4, 8, 2>),
-#define MJX_ROI_FORMS(M) reinterpret_cast<const void *>(k_idct_color<kRoiMode + M, kPrefetch, 0>), reinterpret_cast<const void *>(k_idct_color<kRoiMode + M, 8, 1>), reinterpret_cast<const void *>(k_idct_color<kRoiMode + M, 8, 2>)
-                             MJX_ROI_FORMS(0), MJX_ROI_FORMS(1), MJX_ROI_FORMS(3), MJX_ROI_FORMS(4),
-                             MJX_ROI_FORMS(kOutMode - kRoiMode + 0), MJX_ROI_FORMS(kOutMode - kRoiMode + 1),        // (the output formats' forms, kOutMode + m)
-                             MJX_ROI_FORMS(kOutMode - kRoiMode + 3), MJX_ROI_FORMS(kOutMode - kRoiMode + 4),
-                             MJX_ROI_FORMS(kPlaneMode - kRoiMode + 0),                                               // (libjpeg's pixels: the plane form)
-                             MJX_ROI_FORMS(kLumaMode - kRoiMode + 0), MJX_ROI_FORMS(kLumaMode - kRoiMode + 1),      // (luminance output, kLumaMode + m)
-                             MJX_ROI_FORMS(kLumaMode - kRoiMode + 3), MJX_ROI_FORMS(kLumaMode - kRoiMode + 4),
-                             MJX_ROI_FORMS(kYccMode - kRoiMode + 0), MJX_ROI_FORMS(kYccMode - kRoiMode + 3),        // (YCbCr output, kYccMode + m)
-                             MJX_ROI_FORMS(kYccMode - kRoiMode + 4)};
-#undef MJX_ROI_FORMS
+#define MJX_STAGE_B_FN(F, S, PF, SRC, LAYOUT, DENSITY) reinterpret_cast<const void *>(k_idct_color<stage_b_mode(F, S), PF, SRC>),
+        const void *fns[] = {MJX_STAGE_B_KERNELS(MJX_STAGE_B_FN)};
+#undef MJX_STAGE_B_FN
         for (const void *f : fns)
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(idct_lds));
     }
@@ -5074,71 +5062,17 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
     const uint32_t gx = (max_tiles + tpw - 1) / tpw;
     // (layout_mask: bit 0 = the chunk has pictures with a linear stream, bit 1 = with a quad-interleaved one, bit 2 = multi-scan
     // pictures read straight from their scans' streams; a kernel form leaves the other kinds' pictures alone)
-#define MJX_IDCT(M, P, Q) hipLaunchKernelGGL((k_idct_color<M, P, Q>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw)
-    if (mode_mask & 1u) {
-        if (layout_mask & 1u) MJX_IDCT(0, kPrefetch, 0);
-        if (layout_mask & 2u) MJX_IDCT(0, 8, 1);
-        if (layout_mask & 4u) MJX_IDCT(0, 8, 2);
-    }
-    if (mode_mask & 2u) {
-        // (linear streams that are dense -- more than ~2048 entries per tile: quality 90 and up -- take the form that prefetches
-        // twelve words per lane instead of eight: 18.2 -> 17.2 ms per 2048 4K pictures at quality 90; at quality 75 the four
-        // extra loads per lane and tile cost 0.15 ms)
-        if (layout_mask & 1u) {
-            if (dense) MJX_IDCT(1, kPrefetchDense, 0);
-            else MJX_IDCT(1, kPrefetch, 0);
-        }
-        // (quad-interleaved streams: one round of 256 groups prefetched, two for dense streams -- 20.2 -> ... ms at quality 90)
-        if (layout_mask & 2u) {
-            if (dense) MJX_IDCT(1, 16, 1);
-            else MJX_IDCT(1, 8, 1);
-        }
-        if (layout_mask & 4u) MJX_IDCT(1, 8, 2);
-    }
-    if (mode_mask & 4u) {
-        if (layout_mask & 1u) MJX_IDCT(2, kPrefetch, 0);
-        if (layout_mask & 2u) MJX_IDCT(2, 8, 1);
-    }
-    // scaled decode at 1/2 (mode 3) and 1/4 (mode 4); 1/8 is launch_dc_color's
-    if (mode_mask & 8u) {
-        if (layout_mask & 1u) MJX_IDCT(3, kPrefetch, 0);
-        if (layout_mask & 2u) MJX_IDCT(3, 8, 1);
-        if (layout_mask & 4u) MJX_IDCT(3, 8, 2);
-    }
-    if (mode_mask & 16u) {
-        if (layout_mask & 1u) MJX_IDCT(4, kPrefetch, 0);
-        if (layout_mask & 2u) MJX_IDCT(4, 8, 1);
-        if (layout_mask & 4u) MJX_IDCT(4, 8, 2);
-    }
-#undef MJX_IDCT
-    // region-of-interest decode: pictures with a rectangle (mode + kRoiMode) take the forms that skip tiles and crop
-    // ... and pictures with an output description (mode + kOutMode) the forms that write it
-#define MJX_IDCT_ROI(M_)                                                                                                                  \
-    if (mode_mask & (uint64_t(1) << (kRoiMode + M_))) {                                                                                            \
-        constexpr int M = (M_) % int(kRoiMode);                                                                                           \
-        if (layout_mask & 1u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M_, kPrefetch, 0>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw); \
-        if (layout_mask & 2u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M_, 8, 1>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw);         \
-        if (layout_mask & 4u) hipLaunchKernelGGL((k_idct_color<kRoiMode + M_, 8, 2>), dim3(gx, nimg), dim3(M == 1 ? kLanes420 : 256u), lds, st, images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw);         \
-    }
-    MJX_IDCT_ROI(0)
-    MJX_IDCT_ROI(1)
-    MJX_IDCT_ROI(3)
-    MJX_IDCT_ROI(4)
-    MJX_IDCT_ROI(kOutMode - kRoiMode + 0)
-    MJX_IDCT_ROI(kOutMode - kRoiMode + 1)
-    MJX_IDCT_ROI(kOutMode - kRoiMode + 3)
-    MJX_IDCT_ROI(kOutMode - kRoiMode + 4)
-    MJX_IDCT_ROI(kPlaneMode - kRoiMode + 0)
-    // ... and luminance pictures (mode + kLumaMode) the forms that transform and write component 0 alone
-    MJX_IDCT_ROI(kLumaMode - kRoiMode + 0)
-    MJX_IDCT_ROI(kLumaMode - kRoiMode + 1)
-    MJX_IDCT_ROI(kLumaMode - kRoiMode + 3)
-    MJX_IDCT_ROI(kLumaMode - kRoiMode + 4)
-    // ... and pictures that leave as component planes (mode + kYccMode) the forms that write those
-    MJX_IDCT_ROI(kYccMode - kRoiMode + 0)
-    MJX_IDCT_ROI(kYccMode - kRoiMode + 3)
-    MJX_IDCT_ROI(kYccMode - kRoiMode + 4)
-#undef MJX_IDCT_ROI
+    // The 4:2:0 form has two instantiations each for linear and quad-interleaved streams.  Dense linear streams -- more than ~2048
+    // entries per tile: quality 90 and up -- take the one that prefetches twelve words per lane instead of eight: 18.2 -> 17.2 ms
+    // per 2048 4K pictures at quality 90; at quality 75 the four extra loads per lane and tile cost 0.15 ms.  Quad-interleaved
+    // streams: one round of 256 groups prefetched, two for dense streams.  (1/8 scale is launch_dc_color's.)
+    const StageBDensity density = dense ? kDense : kSparse;
+#define MJX_STAGE_B_LAUNCH(F, S, PF, SRC, LAYOUT, DENSITY)                                                                                    \
+    if ((mode_mask >> stage_b_mode(F, S) & 1u) && (layout_mask & LAYOUT) && (DENSITY == kAnyDensity || DENSITY == density))                   \
+        hipLaunchKernelGGL((k_idct_color<stage_b_mode(F, S), PF, SRC>), dim3(gx, nimg), dim3(F == kForm420 ? kLanes420 : 256u), lds, st,     \
+                           images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw);
+    MJX_STAGE_B_KERNELS(MJX_STAGE_B_LAUNCH)
+#undef MJX_STAGE_B_LAUNCH
 }
 
 void launch_planar_gather(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint32_t *entries,

@@ -452,6 +452,40 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     return p.status;
 }
 
+StageBChoice stage_b_choice(const ImagePlan &p)
+{
+    const bool luma = p.out_on && p.out_channels == 1;
+    // The form, first match: libjpeg's pixels have the generic form alone, whatever else the plan says; REF_COMPAT placement; a
+    // scale; Y 2x2 + Cb 1x1 + Cr 1x1 on the 4:2:0 kernel, unless the picture leaves as component planes (no 4:2:0 plane form).
+    const bool s420 = p.ncomp == 3 && p.h[0] == 2 && p.v[0] == 2 && p.h[1] == 1 && p.v[1] == 1 && p.h[2] == 1 && p.v[2] == 1;
+    const StageBForm form = p.lj ? kFormGeneric
+                          : p.layout == MJX_LAYOUT_REF_COMPAT ? kFormRefCompat
+                          : p.scale > 1 ? (p.scale == 2 ? kFormHalf : p.scale == 4 ? kFormQuarter : kFormEighth)
+                          : s420 && !p.ycc_on ? kForm420 : kFormGeneric;
+    // The sink, by precedence: (1) libjpeg's planes -- k_upsample_color then writes whatever the picture leaves as; (2) the
+    // component planes as the picture; (3) luminance, also as the one-byte intermediate of a resize or an orientation; (4) an output
+    // description with no resize behind it -- a resized picture's description is the resize's, stage B writes the packed
+    // intermediate; (5) a rectangle; (6) the packed whole picture.  (This is the order in which the features' overwrites of the
+    // mode used to follow one another, last writer first; tests/golden/stage_b_choice.npz holds what those gave.)
+    const StageBSink sink = p.lj ? kSinkPlanes : p.ycc_on ? kSinkYcc : luma ? kSinkLuma : p.out_on && !p.rs_on ? kSinkOut
+                          : p.cropped ? kSinkCropped : kSinkPacked;
+    StageBChoice c;
+    // (0) ahead of them all: a scan of a multi-scan file has no stage B.  Its tile geometry is still that of `form`.
+    c.mode = p.role == 1 ? stage_b_mode(kFormScan, kSinkPacked) : stage_b_mode(form, sink);
+    c.tile_420 = form == kForm420;
+    // the passes behind stage B: a colour picture is k_resize_out's (rs_on) without an orientation, else k_orient_out's or
+    // k_resize_orient's; a luminance picture is always one of the one-channel passes', orientation code 1 included
+    const bool pass = p.out_on && p.rs_on;
+    c.rs_on = pass && !luma && p.orient == 1 ? 1u : 0u;
+    c.or_on = !pass ? kOrNone : luma ? (p.or_copy ? kOrCopyLuma : kOrResizeLuma)
+            : p.orient == 1 ? kOrNone : p.or_copy ? kOrCopy : kOrResize;
+    c.out_ch = luma ? 1u : 0u;
+    c.lj_luma = p.lj && luma ? 1u : 0u;                      // (a luminance picture is k_upsample_luma's: component 0's plane alone)
+    c.lj_on = p.lj && !luma ? 1u : 0u;
+    c.lj_out = p.lj && p.out_on && !p.rs_on ? 1u : 0u;
+    return c;
+}
+
 bool rois_fit(const mjx_opts &opts, size_t n)
 {
     if (!opts.rois) return opts.n_rois == 0;

@@ -109,6 +109,14 @@ struct ImagePlan {
     uint32_t src_part[3] = {0, 0, 0}, src_comp[3] = {0, 0, 0};   // ... which of them carries component c, as its n-th component
 };
 
+// What stage B and the passes behind it do with a planned picture: DevImage's fields of the same names (mjx_kernels.h), decided
+// here and nowhere else.  tile_420: the picture's tile is the 4:2:0 kernel's (tile_mcus_420) and not the generic power of two.
+struct StageBChoice {
+    uint32_t mode, rs_on, or_on, out_ch, lj_on, lj_luma, lj_out;
+    bool tile_420;
+};
+StageBChoice stage_b_choice(const ImagePlan &p);
+
 // decoder.rs:259-288 get_indices: raster counter (x, y) of a component's blocks -> block position (bug-for-bug, Q3).
 // Returns false where the reference's usize arithmetic underflows (panic).
 bool ref_get_indices(long x, long y, long max_x, long x_factor, long y_factor, long max_x_factor, long max_y_factor,

@@ -716,6 +716,30 @@ extern "C" int emul_plan_parts(const uint8_t *jpeg, size_t len, int *out /* [cap
     mjx_free_scan(&d);
     return n;
 }
+// stage_b_choice on n plans that hold nothing but its inputs: rows of {lj, ycc_on, out_on, rs_on, out_channels, cropped, scale, layout,
+// sampling is 4:2:0, role, orient, or_copy} -> rows of {mode, rs_on, or_on, out_ch, lj_on, lj_luma, lj_out, tile_420}
+extern "C" void emul_stage_b_choice(const uint32_t *in /* [n][12] */, int n, uint8_t *out /* [n][8] */)
+{
+    for (int i = 0; i < n; i++, in += 12, out += 8) {
+        ImagePlan p;
+        p.lj = in[0] != 0; p.ycc_on = in[1] != 0; p.out_on = in[2] != 0; p.rs_on = in[3] != 0; p.out_channels = in[4];
+        p.cropped = in[5] != 0; p.scale = in[6]; p.layout = in[7]; p.role = in[9]; p.orient = in[10]; p.or_copy = in[11] != 0;
+        p.ncomp = 3;
+        if (in[8]) p.h[0] = p.v[0] = p.hmax = p.vmax = 2;
+        const StageBChoice c = stage_b_choice(p);
+        const uint32_t o[8] = {c.mode, c.rs_on, c.or_on, c.out_ch, c.lj_on, c.lj_luma, c.lj_out, c.tile_420 ? 1u : 0u};
+        for (int k = 0; k < 8; k++) out[k] = uint8_t(o[k]);
+    }
+}
+// the modes of the entries of MJX_STAGE_B_KERNELS (mjx_kernels.h), in the list's order; returns their count
+extern "C" int emul_stage_b_kernel_modes(uint32_t *out, int cap)
+{
+    int n = 0;
+#define EMUL_MODE(F, S, PF, SRC, LAYOUT, DENSITY) if (n < cap) out[n] = stage_b_mode(F, S); n++;
+    MJX_STAGE_B_KERNELS(EMUL_MODE)
+#undef EMUL_MODE
+    return n;
+}
 
 // ---- decode tables as the host builds them (tests/test_huffman_tables.py walks them over every 16-bit window) ------------------------
 // build_decode_table on one DHT table (vals: 256 bytes) -> entries written, or the negative status

@@ -2,6 +2,7 @@
 entropy routine through the CPU emulation of the GPU algorithm (tests/emul), the synthetic generator."""
 import ctypes
 import io
+import itertools
 import os
 import re
 import sys
@@ -711,6 +712,34 @@ def test_planner_shares_tables_and_fills_workgroups(mjx, emul_lib):
                                             ((256, 256, 75), (1024, 1024), (40, 128)), ((96, 64, 75), (1024, 1024), (1, 16))):
         (p,) = parts(mjx.synth_jpeg(w, h, "420", q, seed=5))
         assert lo <= p[5] <= hi and p[5] % 256 == 0 and nlo <= p[6] <= nhi, (w, h, p)
+
+
+def test_stage_b_choice_is_the_recorded_cascade(emul_lib):
+    """stage_b_choice (mjx_plan.cpp) decides DevImage::mode = form | sink << 3 and the six fields that go with it, by a precedence
+    that is written down there.  Before it, fill_dev_image reached the same numbers by overwriting the mode feature after feature;
+    tests/golden/stage_b_choice.npz holds what that cascade gave on the full product of its inputs -- 12288 rows in the order of
+    itertools.product below, columns mode, rs_on, or_on, out_ch, lj_on, lj_luma, lj_out and whether the tile is the 4:2:0
+    kernel's -- and every row must be equal, those no front door reaches included.
+    Then: the mode splits into a form and a sink and back; and every mode stage B is launched for (not a scan's, not 1/8 scale,
+    which is the k_dc_color kernels') has a kernel in MJX_STAGE_B_KERNELS -- all but REF_COMPAT placement with a sink other than
+    the packed picture, which the planner refuses (plan_image, plan_output, plan_planes, resize_opts: MJX_ERR_INVALID_ARG)."""
+    rows = np.array(list(itertools.product((0, 1), (0, 1), (0, 1), (0, 1), (1, 3), (0, 1), (1, 2, 4, 8), (0, 1), (0, 1), (0, 1, 2),
+                                           (1, 6), (0, 1))), np.uint32)         # (layout: MJX_LAYOUT_STANDARD 0, REF_COMPAT 1)
+    want = np.load(os.path.join(ROOT, "tests", "golden", "stage_b_choice.npz"))["choice"]
+    assert rows.shape == (12288, 12) and want.shape == (12288, 8) and want.dtype == np.uint8
+    got = np.zeros_like(want)
+    emul_lib.emul_stage_b_choice(rows.ctypes.data_as(ctypes.c_void_p), len(rows), got.ctypes.data_as(ctypes.c_void_p))
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    assert bad.size == 0, (bad.size, rows[bad[:5]].tolist(), got[bad[:5]].tolist(), want[bad[:5]].tolist())
+    modes = want[:, 0].astype(np.int64)
+    form, sink = modes & 7, modes >> 3
+    assert np.array_equal(form | sink << 3, modes) and set(form.tolist()) <= {0, 1, 2, 3, 4, 5, 7} and sink.max() <= 5
+    listed = (ctypes.c_uint32 * 128)()
+    n = emul_lib.emul_stage_b_kernel_modes(listed, 128)
+    assert n == 64
+    launched = set(modes[(rows[:, 9] != 1) & (form < 5)].tolist())
+    assert launched - set(listed[:n]) == {2 | s << 3 for s in (1, 2, 4, 5)}
+    assert set(listed[:n]) <= launched                                         # (and no kernel that no plan asks for)
 
 
 def test_emulated_rounds_keep_two_decodes_per_subsequence(mjx, orc, emul, monkeypatch):

@@ -32,8 +32,8 @@ Which kernel instantiation each GPU test reaches, and why (planner rules: mjx_ap
   test_scaled[*-2|4]                    scale 2, 4                               k_idct_color<3 | 4, kPrefetch | 8, 0 | 1>
   test_scaled[*-8]                      scale 8                                  k_dc_color
   test_ref_compat                       REF_COMPAT, 4:4:4 320 x 216 and grey     k_idct_color<2, ...> + k_ref_color (pack_u8)
-  test_roi_and_formats[*-1]             unaligned rectangles / an Output         k_idct_color<kRoiMode + 0|1>, <kOutMode + 0|1>
-  test_roi_and_formats[*-2|4|8]                                                  <kRoiMode + 3|4>, <kOutMode + 3|4>, k_dc_color_roi,
+  test_roi_and_formats[*-1]             unaligned rectangles / an Output         k_idct_color, forms 0|1 of kSinkCropped, kSinkOut
+  test_roi_and_formats[*-2|4|8]                                                  forms 3|4 of the same sinks, k_dc_color_roi,
                                                                                  k_dc_color_out
 Every test asserts T0 (b.coefs(i) == the blocks written) wherever the batch keeps coefficients, so a pixel failure is stage B's.
 """

@@ -3,7 +3,7 @@
 
 The batch of bench.py -- 2048 synthetic 3840x2160 4:2:0 q75 pictures, 64 unique ones -- decoded whole at scales 1, 1/2 and 1/8 as
   rgb       packed R,G,B without an output description: the parent's path, the yardstick of the same run
-  luma_u8   luminance, uint8 (k_idct_color<kLumaMode + m>, k_dc_color_luma at 1/8)
+  luma_u8   luminance, uint8 (k_idct_color's kSinkLuma forms, k_dc_color_luma at 1/8)
   luma_f32  luminance, float32 normalised
 Every variant builds a base batch of the unique pictures once and tiles it per repeat (only one large batch is resident at a
 time); the variants take turns inside every repeat.  Per variant: ms per step (every repeat, best, median), per-class kernel ms per

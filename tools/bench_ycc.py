@@ -3,8 +3,8 @@
 
 The batch of bench.py -- 2048 synthetic 3840x2160 4:2:0 q75 pictures, 64 unique ones -- decoded whole at scales 1 and 1/8 as
   rgb        packed R,G,B without an output description: the default path, the yardstick of the same run
-  luma_u8    luminance, uint8 (k_idct_color<kLumaMode + m>, k_dc_color_luma at 1/8)
-  ycc_u8     component planes, uint8: I420 (k_idct_color<kYccMode + m>, k_dc_color_ycc at 1/8)
+  luma_u8    luminance, uint8 (k_idct_color's kSinkLuma forms, k_dc_color_luma at 1/8)
+  ycc_u8     component planes, uint8: I420 (k_idct_color's kSinkYcc forms, k_dc_color_ycc at 1/8)
   ycc_nv12   component planes, uint8, Cb and Cr interleaved
   ycc_f32    component planes, float32 normalised per component
 Every variant builds a base batch of the unique pictures once and tiles it per repeat (only one large batch is resident at a
