@@ -149,6 +149,19 @@ pub struct mjx_opts {
     pub n_rois: u32,
 }
 
+/// byte 10 of mjx_opts, a padding byte behind scale_denom: MJX_COLOR_* (include/mjx.h: MJX_OPTS_COLOR)
+pub const MJX_OPTS_COLOR_OFFSET: usize = 10;
+
+impl mjx_opts {
+    /// MJX_COLOR_*: 0 components by position (grey, or Y, Cb, Cr), 1 the file's own colour model -- RGB, CMYK and YCCK files decode to R,G,B
+    pub fn color(&self) -> u8 {
+        unsafe { *(self as *const mjx_opts as *const u8).add(MJX_OPTS_COLOR_OFFSET) }
+    }
+    pub fn set_color(&mut self, color: u8) {
+        unsafe { *(self as *mut mjx_opts as *mut u8).add(MJX_OPTS_COLOR_OFFSET) = color }
+    }
+}
+
 impl Default for mjx_opts {
     fn default() -> Self {
         mjx_opts { strict_ref: 0, layout: 0, keep_coefs: 0, device_destuff: 0, chunk_images: 0, pixels: 0, scale_denom: 0, rois: std::ptr::null(), n_rois: 0 }
@@ -207,6 +220,29 @@ pub struct mjx_scan_desc {
     pub n_parts: u8,
     pub parts: *const mjx_scan_part,
     pub owner_: *mut c_void,
+    /// MJX_COLOR_FILE: the fourth component of a four-component scan, and MJX_MODEL_* as mjx_parse decided it (appended)
+    pub comp_fourth: mjx_comp,
+    pub model: u8,
+}
+
+pub const MJX_COLOR_POSITIONAL: u8 = 0;
+pub const MJX_COLOR_FILE: u8 = 1;
+pub const MJX_MODEL_GREY: u8 = 0;
+pub const MJX_MODEL_YCBCR: u8 = 1;
+pub const MJX_MODEL_RGB: u8 = 2;
+pub const MJX_MODEL_CMYK: u8 = 3;
+pub const MJX_MODEL_YCCK: u8 = 4;
+
+/// what mjx_color_model found in a file (include/mjx.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mjx_color_info {
+    pub model: u8,
+    pub ncomp: u8,
+    pub jfif: u8,
+    pub adobe: u8,
+    pub adobe_transform: u8,
+    pub ids: [u8; 4],
 }
 
 #[repr(C)]
@@ -271,6 +307,9 @@ extern "C" {
                                      cap: usize, count: *mut usize) -> c_int;
     pub fn mjx_exif_orientation(jpeg: *const u8, len: usize, code: *mut u8) -> c_int;
     pub fn mjx_orient_compose(first: u8, then: u8) -> u8;
+    pub fn mjx_color_model(jpeg: *const u8, len: usize, out: *mut mjx_color_info) -> c_int;
+    pub fn mjx_ink_mul(a: u8, k: u8) -> u8;
+    pub fn mjx_batch_image_color(b: *const mjx_batch, i: usize, model: *mut u8) -> c_int;
     pub fn mjx_batch_create_orient(ctx: *mut mjx_ctx, descs: *const mjx_scan_desc, n: usize, opts: *const mjx_opts, out: *const mjx_output,
                                    rs: *const mjx_resize, orient: *const mjx_orient, b: *mut *mut mjx_batch, status: *mut c_int) -> c_int;
     pub fn mjx_decode_batch_orient(ctx: *mut mjx_ctx, jpegs: *const *const u8, lens: *const usize, n: usize, opts: *const mjx_opts,

@@ -48,7 +48,7 @@ enum {
                                      * behind the last block needed do not count.  MJX_ERR_TRUNCATED wins where both hold. */
     MJX_ERR_REF_PANIC = 5,          /* other input on which the reference panics (asserts, bad DQT precision ...) */
     MJX_ERR_DEVICE = 6,             /* HIP error / no device / kernels missing */
-    MJX_ERR_UNSUPPORTED_FORMAT = 7, /* non-baseline SOF, ncomp not in {1,3} (decoder.rs:328-330), sampling > 2 */
+    MJX_ERR_UNSUPPORTED_FORMAT = 7, /* non-baseline SOF, ncomp not in {1,3} (decoder.rs:328-330; {1,3,4} with MJX_COLOR_FILE), sampling > 2 */
     MJX_ERR_NO_SCAN = 8,            /* EOF without SOS: the reference returns image_data() == None */
     MJX_ERR_INVALID_ARG = 9,
     MJX_ERR_NOMEM = 10,
@@ -63,6 +63,20 @@ enum {
 enum {
     MJX_PIXELS_REFERENCE = 0, /* box chroma replication, float colour conversion, truncating store (the reference's pixels) */
     MJX_PIXELS_LIBJPEG = 1    /* rounded samples, fancy (triangle) chroma upsampling, libjpeg's integer colour tables */
+};
+
+enum {
+    MJX_COLOR_POSITIONAL = 0, /* one component, or three that are Y, Cb, Cr by position (the reference's rule); four are refused */
+    MJX_COLOR_FILE = 1        /* the file says what its components are: MJX_OPTS_COLOR */
+};
+
+/* What the components of a file are (mjx_color_model, mjx_batch_image_color, mjx_scan_desc.model). */
+enum {
+    MJX_MODEL_GREY = 0,   /* one component */
+    MJX_MODEL_YCBCR = 1,  /* Y, Cb, Cr */
+    MJX_MODEL_RGB = 2,    /* R, G, B stored as they are */
+    MJX_MODEL_CMYK = 3,   /* C, M, Y, K in Adobe's convention: the stored value is the amount of light */
+    MJX_MODEL_YCCK = 4    /* CMYK whose first three components went through the YCbCr transform */
 };
 
 enum mjx_destuff {
@@ -132,6 +146,32 @@ typedef struct mjx_opts {
                              mjx_plan_tiles: rois[0]); n, the call's number of inputs: rois[i] belongs to input i.  Anything else,
                              or rois == NULL with n_rois != 0, fails the call with MJX_ERR_INVALID_ARG. */
 } mjx_opts;
+
+/* The colour option of a call: byte 10 of mjx_opts, one of the padding bytes behind `scale_denom` that the declared members leave unused
+ * (the struct's members, size and offsets are as they were; a zero-filled struct means what it meant).  An lvalue:
+ * MJX_OPTS_COLOR(&opts) = MJX_COLOR_FILE.  Fill the struct with zeros first (memset, = {0} on a static, value-initialisation in C++)
+ * and set the byte on the object the call is given: a member-wise copy of the struct need not carry it.
+ * MJX_COLOR_*: where the meaning of a file's components comes from.  MJX_COLOR_POSITIONAL (0): one component is grey, three are Y, Cb,
+ * Cr whatever the file says, four are MJX_ERR_UNSUPPORTED_FORMAT -- bit for bit the decode of every earlier version.  MJX_COLOR_FILE
+ * (1): libjpeg's default_decompress_parms, decided on the host (mjx_color_model).  One component: grey.  Three: a JFIF APP0 segment
+ * seen: YCbCr; else an Adobe APP14 segment seen: transform 0 RGB, anything else YCbCr; else the component ids 'R','G','B': RGB; else
+ * YCbCr.  Four: an Adobe segment with a transform other than 0: YCCK; transform 0 or no Adobe segment: CMYK.  An APP14 segment counts
+ * when its payload is at least 12 bytes and begins with "Adobe"; the transform is payload byte 11; JFIF is an APP0 whose payload
+ * begins "JFIF\0"; the last such segment in front of the first SOS counts.  The pixels: s_c is the byte of component c at a pixel --
+ * box-replicated, level-shifted, truncated and saturated exactly as the packed decode of a one-component file that carries c's blocks
+ * stores it.  RGB: R,G,B = s_0, s_1, s_2.  CMYK: R = mul(s_0, s_3), G = mul(s_1, s_3), B = mul(s_2, s_3), mul(a, k) = (a k + 127) /
+ * 255 in integers (mjx_ink_mul): samples are taken in Adobe's convention, stored value = amount of light, with or without an APP14
+ * segment, as Pillow takes them. YCCK: (r, g, b) = the default colour step on components 0 .. 2, truncated to bytes; the
+ * writer took that transform of the complemented samples, so s_0 = 255 - r (libjpeg's ycck_cmyk_convert: C = MAXJSAMPLE - R), and
+ * R = mul(255 - r, s_3), likewise G, B -- the picture libjpeg and Pillow give for an Adobe transform 2 file.  YCbCr and grey pictures are byte for byte those of MJX_COLOR_POSITIONAL.  A frame of four components must
+ * be one interleaved scan of at most 10 blocks per MCU (T.81's limit), else MJX_ERR_UNSUPPORTED_FORMAT; restart intervals are fine.
+ * Scales, rectangles, output formats, caller memory, resize, orientation and the pipelined calls compose: a picture leaves stage B as
+ * R,G,B.  Refused per picture with MJX_ERR_UNSUPPORTED_FORMAT, the others of the call unaffected -- the follow-ups: an RGB, CMYK or
+ * YCCK picture with luminance output (MJX_OUTPUT_CHANNELS == 1: component 0 of such a file is not a luminance), with a plane
+ * description, or with MJX_PIXELS_LIBJPEG.  strict_ref or MJX_LAYOUT_REF_COMPAT together with MJX_COLOR_FILE: MJX_ERR_INVALID_ARG for
+ * the picture (the reference has one rule). Anything but 0 and 1: MJX_ERR_INVALID_ARG. */
+#define MJX_OPTS_COLOR_OFFSET 10
+#define MJX_OPTS_COLOR(opts) (((uint8_t *)(opts))[MJX_OPTS_COLOR_OFFSET])
 
 /* ---- output formats: what a picture leaves as, and where -------------------------------------------------------------
  * Without an output description a picture is packed R,G,B uint8 in the batch's own memory.  With one (mjx_batch_create_out,
@@ -359,7 +399,7 @@ typedef struct mjx_scan_desc {
                                       scan_is_stuffed */
     size_t scan_len;
     uint16_t width, height;        /* .dimensions() decoder.rs:66 */
-    uint8_t ncomp;                 /* 1 or 3 */
+    uint8_t ncomp;                 /* 1 or 3; 4 with MJX_COLOR_FILE (the fourth component is comp_fourth, at the struct's end) */
     mjx_comp comp[3];              /* scan order (decoder.rs:141-150) */
     uint16_t qt[4][64];            /* zig-zag (file) order as in DQT, jpeg/mod.rs:236-256; .quantization_table() */
     uint8_t qt_present;            /* bit i = slot i defined */
@@ -381,6 +421,12 @@ typedef struct mjx_scan_desc {
     uint8_t n_parts;
     const mjx_scan_part *parts;
     void *owner_;                  /* internal: storage behind `scan` / `parts` when filled by mjx_parse */
+    /* MJX_COLOR_FILE (appended: every offset above is as before).  comp_fourth: the fourth component of a four-component scan, scan
+       order, behind comp[0 .. 2].  model: MJX_MODEL_* as mjx_parse decided it with MJX_COLOR_FILE; with MJX_COLOR_POSITIONAL -- and
+       in a zero-filled struct a caller fills by hand -- MJX_MODEL_GREY (0), which for three components means Y, Cb, Cr by
+       position.  A four-component description needs MJX_MODEL_CMYK or MJX_MODEL_YCCK. */
+    mjx_comp comp_fourth;
+    uint8_t model;
 } mjx_scan_desc;
 
 /* ---- outer surface ------------------------------------------------------------------------ */
@@ -400,6 +446,22 @@ void mjx_free_scan(mjx_scan_desc *desc);
  * segment, a file that ends inside it -- gives *code = 1 and MJX_OK; nothing outside [jpeg, jpeg + len) is read.  Only NULL arguments
  * are an error.  mjx_parse is not involved (it skips APP1; with strict_ref it still refuses it). */
 int mjx_exif_orientation(const uint8_t *jpeg, size_t len, uint8_t *code);
+/* Host-only: what the components of a file are under MJX_COLOR_FILE (MJX_OPTS_COLOR has the rule).  Walks the markers up to the first
+ * SOS, notes JFIF APP0 and Adobe APP14 segments and the first SOF's component ids.  A file without a frame of 1, 3 or 4 components in
+ * front of its first SOS, or one that ends inside a segment, gives MJX_ERR_UNSUPPORTED_FORMAT (out is zero-filled); nothing outside
+ * [jpeg, jpeg + len) is read.  mjx_parse with MJX_COLOR_FILE decides with the same routine. */
+typedef struct mjx_color_info {
+    uint8_t model;            /* MJX_MODEL_* */
+    uint8_t ncomp;            /* components of the frame */
+    uint8_t jfif;             /* 1: a JFIF APP0 segment was seen */
+    uint8_t adobe;            /* 1: an Adobe APP14 segment was seen */
+    uint8_t adobe_transform;  /* its transform byte (0 without one) */
+    uint8_t ids[4];           /* the frame's component ids, frame order */
+} mjx_color_info;
+int mjx_color_model(const uint8_t *jpeg, size_t len, mjx_color_info *out);
+/* mul(a, k) = (a k + 127) / 255 of MJX_OPTS_COLOR: the routine the kernels run (ink_mul, mjx_kernels.h).  Equal to Pillow's
+ * CMYK -> RGB conversion on all 65 536 pairs. */
+uint8_t mjx_ink_mul(uint8_t a, uint8_t k);
 /* The one code that does what `first` followed by `then` does; 0 when either lies outside 1 .. 8. */
 uint8_t mjx_orient_compose(uint8_t first, uint8_t then);
 
@@ -548,6 +610,8 @@ int mjx_batch_image_info(const mjx_batch *b, size_t i, uint32_t *width, uint32_t
 int mjx_batch_image_roi(const mjx_batch *b, size_t i, uint32_t *x, uint32_t *y, uint32_t *full_width, uint32_t *full_height);
 /* the DCT-domain scale picture i was decoded at (1, 2, 4 or 8): the call's, or the one auto_scale picked */
 int mjx_batch_image_scale(const mjx_batch *b, size_t i, uint8_t *scale_denom);
+/* the colour model of picture i (MJX_MODEL_*; with MJX_COLOR_POSITIONAL grey for one component, YCbCr for three) */
+int mjx_batch_image_color(const mjx_batch *b, size_t i, uint8_t *model);
 /* the orientation code picture i left with (1 .. 8: the file's tag followed by extra[i]; 1 for any batch without an orientation) */
 int mjx_batch_image_orientation(const mjx_batch *b, size_t i, uint8_t *code);
 /* a resized batch: the rectangle R picture i's intermediate covers, in the coordinates of the picture at its scale

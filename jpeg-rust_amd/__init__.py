@@ -30,6 +30,9 @@ OK, ERR_TRUNCATED, ERR_UNSUPPORTED_MARKER, ERR_DRI_UNSUPPORTED, ERR_BAD_HUFFMAN,
     ERR_UNSUPPORTED_FORMAT, ERR_NO_SCAN, ERR_INVALID_ARG, ERR_NOMEM, ERR_MISSING_TABLE = range(12)
 LAYOUT_STANDARD, LAYOUT_REF_COMPAT = 0, 1
 PIXELS_REFERENCE, PIXELS_LIBJPEG = 0, 1
+COLOR_POSITIONAL, COLOR_FILE = 0, 1
+MODEL_GREY, MODEL_YCBCR, MODEL_RGB, MODEL_CMYK, MODEL_YCCK = range(5)
+MODEL_NAMES = ["grey", "ycbcr", "rgb", "cmyk", "ycck"]
 ABI_VERSION = 2                  # mjx.h: MJX_ABI_VERSION, the layout the structures below mirror (mjx_version() prints the library's)
 STAGE_ENTROPY, STAGE_PIXELS, STAGE_ALL = 1, 2, 3
 KERNEL_NAMES = ["gather", "huff_sync", "huff_fix", "huff_scan", "huff_write", "dc_scan", "idct_color", "upload", "huff_emit", "huff_prefix", "resize"]
@@ -52,6 +55,18 @@ class Opts(ctypes.Structure):
     _fields_ = [("strict_ref", ctypes.c_uint8), ("layout", ctypes.c_uint8), ("keep_coefs", ctypes.c_uint8),
                 ("device_destuff", ctypes.c_uint8), ("chunk_images", ctypes.c_uint32), ("pixels", ctypes.c_uint8),
                 ("scale_denom", ctypes.c_uint8), ("rois", ctypes.POINTER(Rect)), ("n_rois", ctypes.c_uint32)]
+
+
+def _opts_color(self):
+    return ctypes.c_uint8.from_address(ctypes.addressof(self) + Opts.COLOR_OFFSET).value
+
+
+def _opts_set_color(self, v):
+    ctypes.c_uint8.from_address(ctypes.addressof(self) + Opts.COLOR_OFFSET).value = int(v)
+
+
+Opts.COLOR_OFFSET = 10                  # MJX_OPTS_COLOR_OFFSET: the colour option lives in a padding byte behind scale_denom
+Opts.color = property(_opts_color, _opts_set_color)
 
 
 class Dst(ctypes.Structure):
@@ -143,7 +158,14 @@ class ScanDesc(ctypes.Structure):
                 ("dc", HuffTab * 4), ("ac", HuffTab * 4), ("dc_present", ctypes.c_uint8),
                 ("ac_present", ctypes.c_uint8), ("scan_is_stuffed", ctypes.c_uint8), ("restart_interval", ctypes.c_uint16),
                 ("n_restart", ctypes.c_uint32), ("restart_offsets", ctypes.POINTER(ctypes.c_uint32)),
-                ("n_parts", ctypes.c_uint8), ("parts", ctypes.POINTER(ScanPart)), ("owner_", ctypes.c_void_p)]
+                ("n_parts", ctypes.c_uint8), ("parts", ctypes.POINTER(ScanPart)), ("owner_", ctypes.c_void_p),
+                ("comp_fourth", Comp), ("model", ctypes.c_uint8)]
+
+
+class ColorInfo(ctypes.Structure):
+    """mjx_color_info: what mjx_color_model found in a file."""
+    _fields_ = [("model", ctypes.c_uint8), ("ncomp", ctypes.c_uint8), ("jfif", ctypes.c_uint8), ("adobe", ctypes.c_uint8),
+                ("adobe_transform", ctypes.c_uint8), ("ids", ctypes.c_uint8 * 4)]
 
 
 class Image(ctypes.Structure):
@@ -180,6 +202,9 @@ SYMBOLS = {
     "mjx_upsample_luma_host": (_int, [_P(ctypes.c_uint8), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8, _P(Rect), _P(ctypes.c_uint8)]),
     "mjx_exif_orientation": (_int, [ctypes.c_char_p, _sz, _P(ctypes.c_uint8)]),
     "mjx_orient_compose": (ctypes.c_uint8, [ctypes.c_uint8, ctypes.c_uint8]),
+    "mjx_color_model": (_int, [ctypes.c_char_p, _sz, _P(ColorInfo)]),
+    "mjx_ink_mul": (ctypes.c_uint8, [ctypes.c_uint8, ctypes.c_uint8]),
+    "mjx_batch_image_color": (_int, [_vp, _sz, _P(ctypes.c_uint8)]),
     "mjx_batch_create_orient": (_int, [_vp, _P(ScanDesc), _sz, _P(Opts), _P(OutputDesc), _P(ResizeDesc), _P(OrientDesc), _P(_vp), _P(_int)]),
     "mjx_decode_batch_orient": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(OutputDesc), _P(ResizeDesc), _P(OrientDesc), _P(_int), _P(_vp)]),
     "mjx_orient_plan": (_int, [_P(ScanDesc), _P(Opts), _P(ResizeDesc), ctypes.c_uint8, _sz, _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(Rect), _P(ctypes.c_uint8)]),
@@ -286,16 +311,30 @@ def _pixels(pixels):
     return int(pixels)
 
 
-def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0, device_destuff=False, scale=1, rois=None, pixels=None):
+def _color(color):
+    """None / "positional" / COLOR_POSITIONAL, or "file" / COLOR_FILE (mjx.h: mjx_opts.color)."""
+    names = {None: COLOR_POSITIONAL, "positional": COLOR_POSITIONAL, "file": COLOR_FILE}
+    if color is None or isinstance(color, str):
+        if color not in names:
+            raise MjxError(ERR_INVALID_ARG, "color=%r" % (color,))
+        return names[color]
+    if not 0 <= int(color) <= 255:
+        raise MjxError(ERR_INVALID_ARG, "color=%r" % (color,))
+    return int(color)
+
+
+def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0, device_destuff=False, scale=1, rois=None, pixels=None, color=None):
     """device_destuff: True = on the GPU, False = on the host, None = the library's choice (mjx.h: MJX_DESTUFF_*).
     scale: 1, 2, 4 or 8 -- the picture decoded at 1/scale in the DCT domain (mjx.h: mjx_opts.scale_denom).
     rois: see _rects (mjx.h: mjx_opts.rois, n_rois); the Opts returned keeps the array alive.
-    pixels: see _pixels -- "libjpeg": rounded samples, fancy chroma upsampling and libjpeg's integer colour tables."""
+    pixels: see _pixels -- "libjpeg": rounded samples, fancy chroma upsampling and libjpeg's integer colour tables.
+    color: see _color -- "file": the colour model comes from the file (RGB, CMYK and YCCK files decode to R,G,B)."""
     dd = DESTUFF_AUTO if device_destuff is None else (DESTUFF_DEVICE if device_destuff else DESTUFF_HOST)
     scale = int(scale)
     if not 0 <= scale <= 255:
         raise MjxError(ERR_INVALID_ARG, "scale=%d" % scale)
     o = Opts(int(bool(strict_ref)), int(layout), int(bool(keep_coefs)), dd, int(chunk_images), _pixels(pixels), scale)
+    o.color = _color(color)
     arr = _rects(rois)
     if arr is not None:
         o._rects = arr                      # (the library borrows the array for the duration of the call)
@@ -542,42 +581,43 @@ def _out_ref(output):
 class ParsedScan:
     """Owns one mjx_scan_desc filled by mjx_parse (reference: the state JPEGImage::parse hands to JPEGDecoder)."""
 
-    def __init__(self, data, strict_ref=False, device_destuff=False):
+    def __init__(self, data, strict_ref=False, device_destuff=False, color=None):
+        """color: "file" -- four-component files parse, and desc.model says what the components are (see Batch)."""
         self.desc = ScanDesc()
         self._owned = False
-        o = _opts(strict_ref=strict_ref, device_destuff=device_destuff)
+        o = _opts(strict_ref=strict_ref, device_destuff=device_destuff, color=color)
         _check(lib().mjx_parse(bytes(data), len(data), ctypes.byref(o), ctypes.byref(self.desc)), "mjx_parse")
         self._owned = True
 
     def scan_bytes(self):
         return ctypes.string_at(self.desc.scan, self.desc.scan_len)
 
-    def validate(self, layout=LAYOUT_STANDARD, strict_ref=False, scale=1, roi=None, pixels=None):
+    def validate(self, layout=LAYOUT_STANDARD, strict_ref=False, scale=1, roi=None, pixels=None, color=None):
         """Status mjx_batch_create would give this image (host only).  roi: (x, y, w, h) in the scaled picture's coordinates."""
-        o = _opts(layout=layout, strict_ref=strict_ref, scale=scale, rois=roi, pixels=pixels)
+        o = _opts(layout=layout, strict_ref=strict_ref, scale=scale, rois=roi, pixels=pixels, color=color)
         return int(lib().mjx_validate(ctypes.byref(self.desc), ctypes.byref(o)))
 
-    def plan_tiles(self, roi=None, scale=1, pixels=None):
+    def plan_tiles(self, roi=None, scale=1, pixels=None, color=None):
         """mjx_plan_tiles (host only) -> dict(tiles_read, tiles_total, tile_mcus): the stage-B tiles a decode with this rectangle
         fetches and transforms, of the picture's tiles, and the MCUs a tile holds."""
-        o = _opts(scale=scale, rois=roi, pixels=pixels)
+        o = _opts(scale=scale, rois=roi, pixels=pixels, color=color)
         rd, tot, t = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
         _check(lib().mjx_plan_tiles(ctypes.byref(self.desc), ctypes.byref(o), ctypes.byref(rd), ctypes.byref(tot), ctypes.byref(t)), "mjx_plan_tiles")
         return dict(tiles_read=rd.value, tiles_total=tot.value, tile_mcus=t.value)
 
-    def output_layout(self, output=None, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD):
+    def output_layout(self, output=None, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD, color=None):
         """mjx_output_layout (host only) -> dict(width, height, row_pitch, plane_pitch, bytes, dev): what a decode of this picture
         as input i of a call with this Output would write; pitches in elements, bytes from the first element to the last."""
-        o = _opts(layout=layout, scale=scale, rois=roi)
+        o = _opts(layout=layout, scale=scale, rois=roi, color=color)
         keep, ref = _out_ref(output)
         lay, nb = Dst(), _sz()
         _check(lib().mjx_output_layout(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(lay), ctypes.byref(nb)), "mjx_output_layout")
         return dict(width=lay.width, height=lay.height, row_pitch=lay.row_pitch, plane_pitch=lay.plane_pitch, bytes=nb.value, dev=lay.dev or 0)
 
-    def planes_layout(self, planes, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD, pixels=None, strict_ref=False):
+    def planes_layout(self, planes, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD, pixels=None, strict_ref=False, color=None):
         """mjx_planes_layout (host only) -> dict(nplanes, width, height, row_pitch, dev -- a list of three each --, bytes): the planes a
         decode of this picture as input i of a call with this Planes would write; pitches in elements, sizes in samples."""
-        o = _opts(layout=layout, scale=scale, rois=roi, pixels=pixels, strict_ref=strict_ref)
+        o = _opts(layout=layout, scale=scale, rois=roi, pixels=pixels, strict_ref=strict_ref, color=color)
         keep, ref = _planes_ref(planes)
         lay, np_, nb = PlaneLayout(), ctypes.c_uint32(), _sz()
         _check(lib().mjx_planes_layout(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(lay), ctypes.byref(np_), ctypes.byref(nb)), "mjx_planes_layout")
@@ -650,7 +690,7 @@ class Batch:
     """Device-resident batch: inputs uploaded at construction, ``decode()`` only enqueues kernels."""
 
     def __init__(self, ctx, scans=None, strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0,
-                 _handle=None, scale=1, rois=None, output=None, resize=None, orient=None, datas=None, pixels=None, planes=None):
+                 _handle=None, scale=1, rois=None, output=None, resize=None, orient=None, datas=None, pixels=None, planes=None, color=None):
         """scale: 1, 2, 4 or 8 -- every picture decoded at 1/scale (info(), rgb(), rgb_device() and bytes() then speak of the
         scaled picture; tile() keeps the scale).
         rois: one (x, y, w, h) for every picture, or a list with one per picture (None or (0, 0, 0, 0): the whole picture), in the
@@ -667,7 +707,11 @@ class Batch:
         pixels: "libjpeg" (PIXELS_LIBJPEG) -- the pictures libjpeg-based decoders give: rounded samples, fancy chroma upsampling,
         integer colour tables (STANDARD layout at full size only); everything above composes with it; tile() keeps it.
         planes: a Planes -- the pictures leave as their component planes (planes(i), plane_info(i)); scale, rois and pixels apply,
-        output, resize and orient do not go with it; tile() keeps it."""
+        output, resize and orient do not go with it; tile() keeps it.
+        color: "file" (COLOR_FILE) -- what a file's components are comes from the file (JFIF / Adobe segments, component ids:
+        mjx.h, mjx_opts.color): RGB, CMYK and YCCK files decode to R,G,B (color_model(i) says which a picture was); the scans must
+        have been parsed with color="file" too.  Luminance output, planes and pixels="libjpeg" refuse such pictures
+        (ERR_UNSUPPORTED_FORMAT); YCbCr and grey pictures are unchanged.  Default: three components are Y, Cb, Cr by position."""
         self.ctx = ctx
         self.h = _vp()
         if _handle is not None:
@@ -679,7 +723,7 @@ class Batch:
             ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(s.desc if isinstance(s, ParsedScan) else s),
                            ctypes.sizeof(ScanDesc))
         st = (_int * max(n, 1))()
-        o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois, pixels=pixels)
+        o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois, pixels=pixels, color=color)
         keep, ref = _out_ref(output)
         if planes is not None:
             if output is not None or resize is not None or orient is not None:
@@ -737,6 +781,12 @@ class Batch:
         """The DCT-domain scale picture i was decoded at: the call's, or the one Resize(auto_scale=True) picked."""
         v = ctypes.c_uint8()
         lib().mjx_batch_image_scale(self.h, i, ctypes.byref(v))
+        return v.value
+
+    def color_model(self, i):
+        """The colour model of picture i: MODEL_GREY, MODEL_YCBCR, MODEL_RGB, MODEL_CMYK or MODEL_YCCK (MODEL_NAMES)."""
+        v = ctypes.c_uint8(0)
+        lib().mjx_batch_image_color(self.h, i, ctypes.byref(v))
         return v.value
 
     def orientation(self, i):
@@ -1010,14 +1060,14 @@ class JPEGImage:
         self._w, self._h, self._rgb = width, height, rgb
 
     @staticmethod
-    def parse(data, strict_ref=False, layout=LAYOUT_STANDARD, ctx=None, scale=1, roi=None, pixels=None):
+    def parse(data, strict_ref=False, layout=LAYOUT_STANDARD, ctx=None, scale=1, roi=None, pixels=None, color=None):
         """scale: 1, 2, 4 or 8 -- the picture at 1/scale (width() and height() are the scaled picture's).
         roi: (x, y, w, h) of the scaled picture -- only that rectangle is produced (width() and height() are its).
-        pixels: "libjpeg" -- see Batch."""
+        pixels: "libjpeg", color: "file" -- see Batch."""
         ctx = ctx or default_context()
-        scan = ParsedScan(data, strict_ref=strict_ref)
+        scan = ParsedScan(data, strict_ref=strict_ref, color=color)
         try:
-            b = Batch(ctx, [scan], strict_ref=strict_ref, layout=layout, scale=scale, rois=roi, pixels=pixels)
+            b = Batch(ctx, [scan], strict_ref=strict_ref, layout=layout, scale=scale, rois=roi, pixels=pixels, color=color)
             try:
                 if b.create_status[0] != OK:
                     raise MjxError(b.create_status[0])
@@ -1044,8 +1094,8 @@ class JPEGImage:
 
 
 def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False, scale=1, rois=None,
-                 output=None, chunk_images=0, resize=None, orient=None, pixels=None, planes=None):
-    """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale, rois, pixels: see Batch.
+                 output=None, chunk_images=0, resize=None, orient=None, pixels=None, planes=None, color=None):
+    """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale, rois, pixels, color: see Batch.
     device_destuff: the host copies the entropy-coded bytes as they are; de-stuffing, restart markers and the scan's length
     are found on the GPU.  output: an Output (mjx_decode_batch_out) -- see Batch.  resize: a Resize (mjx_decode_batch_resize).  orient: an Orient
     (mjx_decode_batch_orient): the files' EXIF orientation and / or a code per file on top.  planes: a Planes (mjx_decode_batch_planes) --
@@ -1056,7 +1106,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     st = (_int * max(n, 1))()
     ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
     h = _vp()
-    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels)
+    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, color=color)
     if planes is not None:
         if output is not None or resize is not None or orient is not None:
             raise MjxError(ERR_INVALID_ARG, "planes go without output, resize and orient")
@@ -1083,7 +1133,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
 
 
 def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=False, threads=0, device_destuff=None, planar=None, resize=None,
-                orient=None, pixels=None):
+                orient=None, pixels=None, color=None):
     """Decodes the files straight into a torch tensor on the context's device: N x 3 x H x W (planar) or N x H x W x 3, of uint8,
     float16 or float32; picture i -- at 1/scale, its rectangle rois[i] -- must be H x W.  Float tensors take (v / 255 - mean) / std
     per OUTPUT channel (see Output); bgr: channel 0 is blue.  The pointers and pitches come from data_ptr() and stride(): the
@@ -1098,7 +1148,7 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
     resize: True, or a Resize (its antialias, auto_scale and filter; a size, if it names one, must be the tensor's) -- the pictures, of any
     size, are resampled on the device to the tensor's H x W (see Resize); None: every picture must be H x W as it is.
     orient: an Orient -- the pictures are turned on the device (see Orient); H x W and rois speak of the turned pictures.
-    pixels: "libjpeg" -- see Batch."""
+    pixels: "libjpeg", color: "file" -- see Batch."""
     import torch
     n = len(datas)
     if not isinstance(out, torch.Tensor) or out.dim() != 4 or out.shape[0] != n:
@@ -1155,7 +1205,7 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
             raise MjxError(ERR_INVALID_ARG, "resize to %d x %d into a tensor of %d x %d" % (resize.width, resize.height, w, h))
     else:
         rs = None
-    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt, resize=rs, orient=orient, pixels=pixels)
+    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt, resize=rs, orient=orient, pixels=pixels, color=color)
     batch.close()
     return status
 
@@ -1221,9 +1271,9 @@ class Pool:
     def set_deal(self, round_robin):
         _check(lib().mjx_pool_set_deal(self.h, 1 if round_robin else 0), "mjx_pool_set_deal")
 
-    def decode_batch(self, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads_per_device=0, device_destuff=None, scale=1, rois=None, pixels=None):
+    def decode_batch(self, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads_per_device=0, device_destuff=None, scale=1, rois=None, pixels=None, color=None):
         """-> PoolResult; .slot_of[i], .status[i], .rgb(i), .rc (the call's return code: a failed slot fails its own files only).
-        scale, rois, pixels: see Batch (a file's rectangle follows it to its slot)."""
+        scale, rois, pixels, color: see Batch (a file's rectangle follows it to its slot)."""
         n = len(datas)
         arr = (ctypes.c_char_p * max(n, 1))(*[bytes(d) for d in datas])
         lens = (_sz * max(n, 1))(*[len(d) for d in datas])
@@ -1231,7 +1281,7 @@ class Pool:
         slots = (_int * max(n, 1))()
         ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
         h = _vp()
-        o = _opts(strict_ref, layout, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels)
+        o = _opts(strict_ref, layout, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, color=color)
         rc = lib().mjx_pool_decode_batch(self.h, arr, lens, n, ctypes.byref(o), int(threads_per_device), slots, ptrs, st, ctypes.byref(h))
         if not h:
             _check(rc, "mjx_pool_decode_batch")
@@ -1319,11 +1369,11 @@ class PoolResult:
             pass
 
 
-def plan_tiles(data, roi=None, scale=1, pixels=None):
+def plan_tiles(data, roi=None, scale=1, pixels=None, color=None):
     """Host only: the stage-B tiles a decode of this file with this rectangle and scale reads -> see ParsedScan.plan_tiles."""
-    scan = ParsedScan(data)
+    scan = ParsedScan(data, color=color)
     try:
-        return scan.plan_tiles(roi=roi, scale=scale, pixels=pixels)
+        return scan.plan_tiles(roi=roi, scale=scale, pixels=pixels, color=color)
     finally:
         scan.close()
 
@@ -1364,11 +1414,25 @@ def output_layout(data, output=None, i=0, roi=None, scale=1):
         scan.close()
 
 
-def decode(data, strict_ref=False, layout=LAYOUT_STANDARD, scale=1, roi=None, pixels=None):
+def color_model(data):
+    """mjx_color_model (host only) -> dict(model -- MODEL_*, name, ncomp, jfif, adobe, adobe_transform, ids): what the components of
+    the file are when a call takes the file's word for it (color="file")."""
+    ci = ColorInfo()
+    _check(lib().mjx_color_model(bytes(data), len(data), ctypes.byref(ci)), "mjx_color_model")
+    return dict(model=ci.model, name=MODEL_NAMES[ci.model], ncomp=ci.ncomp, jfif=bool(ci.jfif), adobe=bool(ci.adobe),
+                adobe_transform=ci.adobe_transform, ids=list(ci.ids)[:ci.ncomp])
+
+
+def ink_mul(a, k):
+    """mjx_ink_mul: (a k + 127) // 255, the routine the kernels multiply a sample by K with (CMYK, YCCK)."""
+    return int(lib().mjx_ink_mul(int(a), int(k)))
+
+
+def decode(data, strict_ref=False, layout=LAYOUT_STANDARD, scale=1, roi=None, pixels=None, color=None):
     """One-shot C entry point mjx_decode (parse + GPU decode + copy back) -> ndarray [H, W, 3] uint8.  scale: see Batch.
     roi: (x, y, w, h) of the scaled picture -- the array is that rectangle, [h, w, 3]."""
     img = Image()
-    o = _opts(strict_ref, layout, scale=scale, rois=roi, pixels=pixels)
+    o = _opts(strict_ref, layout, scale=scale, rois=roi, pixels=pixels, color=color)
     _check(lib().mjx_decode(bytes(data), len(data), ctypes.byref(o), ctypes.byref(img)), "mjx_decode")
     try:
         return np.ctypeslib.as_array(img.rgb, (img.height, img.width, 3)).copy()

@@ -110,17 +110,19 @@ public:
     };
     // JPEGImage::parse, src/jpeg/mod.rs:202.  scale_denom (2, 4, 8; 0 = whatever opts says): scaled decode, mjx_opts.scale_denom.
     // roi (null = whatever opts says): only that rectangle of the (scaled) picture is produced, mjx_opts.rois; width() and
-    // height() are then the rectangle's.
+    // height() are then the rectangle's.  color_from_file: the file says what its components are (MJX_OPTS_COLOR = MJX_COLOR_FILE):
+    // RGB, CMYK and YCCK files decode to R,G,B; false: whatever opts says (by default three components are Y, Cb, Cr by position).
     static Result parse(const std::vector<uint8_t> &vec, JPEGImage &image, const mjx_opts *opts = nullptr, unsigned scale_denom = 0,
-                        const mjx_rect *roi = nullptr)
+                        const mjx_rect *roi = nullptr, bool color_from_file = false)
     {
         mjx_image img{0, 0, nullptr};
         Result r;
         mjx_opts o{};
-        if (opts) o = *opts;
+        if (opts) { o = *opts; MJX_OPTS_COLOR(&o) = MJX_OPTS_COLOR(opts); }      // (the colour option is a byte outside the members)
+        if (color_from_file) MJX_OPTS_COLOR(&o) = MJX_COLOR_FILE;
         if (scale_denom) o.scale_denom = uint8_t(scale_denom > 255 ? 255 : scale_denom);
         if (roi) { o.rois = roi; o.n_rois = 1; }
-        r.code = mjx_decode(vec.data(), vec.size(), (opts || scale_denom || roi) ? &o : nullptr, &img);
+        r.code = mjx_decode(vec.data(), vec.size(), (opts || scale_denom || roi || color_from_file) ? &o : nullptr, &img);
         r.message = mjx_strerror(r.code);
         if (!r.ok()) return r;
         image.dimensions_ = {uint16_t(img.width), uint16_t(img.height)};
@@ -129,6 +131,14 @@ public:
             image.image_data_[i] = Pixel(img.rgb[3 * i], img.rgb[3 * i + 1], img.rgb[3 * i + 2]);
         image.has_data_ = true;
         mjx_free_image(&img);
+        return r;
+    }
+    // What the components of a file are when a call takes the file's word for it: mjx_color_model (host only).
+    static Result color_model(const std::vector<uint8_t> &vec, mjx_color_info &info)
+    {
+        Result r;
+        r.code = mjx_color_model(vec.data(), vec.size(), &info);
+        r.message = mjx_strerror(r.code);
         return r;
     }
     size_t width() const { return dimensions_.first; }                          // mod.rs:467

@@ -122,6 +122,7 @@ namespace {
 
 struct ImageInfo {
     int status = MJX_OK;
+    uint32_t model = MJX_MODEL_GREY;                        // MJX_MODEL_* (mjx_batch_image_color)
     uint32_t width = 0, height = 0, bpm = 0, nmcu = 0;      // (width x height: the picture written -- scaled, cropped)
     uint32_t roi_x = 0, roi_y = 0, full_w = 0, full_h = 0;  // where it lies in the uncropped out_w x out_h picture (mjx_batch_image_roi)
     uint64_t nblocks = 0;
@@ -565,8 +566,12 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
     std::memcpy(d.blk_comp, p.blk_comp, sizeof d.blk_comp);
     std::memcpy(d.blk_bx, p.blk_bx, sizeof d.blk_bx);
     std::memcpy(d.blk_by, p.blk_by, sizeof d.blk_by);
+    // colour models (MJX_COLOR_FILE): positional for grey and YCbCr, which so run the pixel phase they always ran
+    d.model = p.model >= MJX_MODEL_RGB ? p.model : uint32_t(kModelPositional);
+    static_assert(uint32_t(kModelRgb) == MJX_MODEL_RGB && uint32_t(kModelCmyk) == MJX_MODEL_CMYK && uint32_t(kModelYcck) == MJX_MODEL_YCCK, "ColorModel mirrors MJX_MODEL_*");
+    d.dc_shape = p.ncomp == 4 ? kDcShape4 + p.bpm : p.bpm;
     uint32_t first = 0;
-    for (uint32_t c = 0; c < 3; c++) {
+    for (uint32_t c = 0; c < 4; c++) {
         d.ch[c] = uint8_t(c < p.ncomp ? p.h[c] : 1);
         d.cv[c] = uint8_t(c < p.ncomp ? p.v[c] : 1);
         d.cfirst[c] = uint8_t(first);
@@ -647,7 +652,7 @@ void plan_chunks(mjx_batch *b)
                 c.lut2_cap = std::max<uint32_t>(c.lut2_cap, d.lut2_n);
                 c.mode_mask |= uint64_t(1) << d.mode;
                 if (d.role != 1) c.layout_mask |= d.planar ? 4u : d.ent_rows ? 2u : 1u;
-                c.bpm_mask |= 1u << d.bpm;
+                c.bpm_mask |= d.ncomp == 4 ? 1u << 31 : 1u << d.bpm;      // (bit 31: four components, launch_dc_scan)
                 if (d.nseg > 1) c.max_restart_segs = std::max(c.max_restart_segs, d.nseg);
                 if (form_of(d.mode) == kFormEighth) {
                     const StageBSink sink = sink_of(d.mode);
@@ -703,6 +708,9 @@ int allocate_work_buffers(mjx_batch *b, DevArena &ar)
     uint32_t max_tiles_arr = 1, total_tiles_arr = 0;
     uint32_t lut_cap = 8, lut2_cap = 8, max_tile_blocks = 1;
     size_t max_segsum = 1;
+    // (segment sums: three words per segment; a batch with four-component pictures keeps four more behind them, launch_dc_scan)
+    size_t seg_words = 3;
+    for (const Chunk &c : b->chunks) if (c.bpm_mask >> 31) seg_words = 7;
     for (const Chunk &c : b->chunks) {
         lut2_cap = std::max(lut2_cap, c.lut2_cap);
         max_segsum = std::max<size_t>(max_segsum, size_t(c.max_segs) * c.count);
@@ -732,7 +740,7 @@ int allocate_work_buffers(mjx_batch *b, DevArena &ar)
     b->max_chunk_images = uint32_t(max_imgs);
     ar.take(&b->d_pull, max_imgs * kMaxFix * sizeof(uint32_t));
     ar.take(&b->d_items, size_t(max_nsub) * 6 * sizeof(uint32_t));
-    ar.take(&b->d_segsum, max_segsum * 3 * sizeof(int32_t));
+    ar.take(&b->d_segsum, max_segsum * seg_words * sizeof(int32_t));
     {
         uint64_t max_planes = 0;
         for (const Chunk &c : b->chunks) max_planes = std::max({max_planes, c.plane_words, c.lj_words});
@@ -765,7 +773,7 @@ int allocate_work_buffers(mjx_batch *b, DevArena &ar)
         ar.take(&a.d_esub, size_t(max_nsub) * sizeof(EmitSub));
         ar.take(&a.d_pull, max_imgs * kMaxFix * sizeof(uint32_t));
         ar.take(&a.d_items, size_t(max_nsub) * 6 * sizeof(uint32_t));
-        ar.take(&a.d_segsum, max_segsum * 3 * sizeof(int32_t));
+        ar.take(&a.d_segsum, max_segsum * seg_words * sizeof(int32_t));
         uint64_t max_planes = 0;
         for (const Chunk &c : b->chunks) max_planes = std::max({max_planes, c.plane_words, c.lj_words});
         if (max_planes) ar.take(&a.d_planes, size_t(max_planes) * 8);
@@ -794,7 +802,7 @@ int allocate_work_buffers(mjx_batch *b, DevArena &ar)
             {b->d_ebase, size_t(max_nsub) * sizeof(uint32_t)},                    // 3
             {b->d_cps, cps_bytes},                                                // 4
             {b->d_items, size_t(max_nsub) * 6 * sizeof(uint32_t)},                // 5
-            {b->d_segsum, max_segsum * 3 * sizeof(int32_t)},                      // 6
+            {b->d_segsum, max_segsum * seg_words * sizeof(int32_t)},                      // 6
             {b->d_entries, size_t(b->opts.keep_coefs ? std::max<uint64_t>(total_entries, 4) : max_entries) * 4 + 64},      // 7
             {b->d_tile_eoff, size_t(b->opts.keep_coefs ? std::max<uint32_t>(total_tiles_arr, 1) : max_tiles_arr) * 4 + 16},   // 8
             {b->d_dc, size_t(coef_blocks) * sizeof(int32_t) + 64},                // 9
@@ -1170,6 +1178,12 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
     auto layout_nsub = [](const ImagePlan &p) { return p.nsub_layout ? p.nsub_layout : p.himg.nsub; };
     b->has_stuffed = any_stuffed && !src;
     std::vector<char> lut_first(nu, 1);                     // 0: the image shares an earlier image's tables
+    // the dequant-multiplier pool: 192 floats per unique picture, 192 more for the reduced transforms, and -- behind both halves, so
+    // that pictures of up to three components keep their slots -- 2 x 64 per four-component picture for its fourth component
+    std::vector<size_t> qm_tail(nu, 0);
+    size_t qm_floats = std::max<size_t>(nu, 1) * 384;
+    for (size_t k = 0; k < nu; k++)
+        if (plans[k].status == MJX_OK && plans[k].ncomp == 4) { qm_tail[k] = qm_floats; qm_floats += 128; }
     std::unordered_multimap<uint64_t, size_t> lut_seen;
     b->h_segs.clear();
     for (size_t k = 0; k < nu; k++) {
@@ -1235,6 +1249,8 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
         d.lut2_n = lut_n[k] - p.lut_plain_n;
         d.qm_off = uint32_t(k * 192);
         if (p.scale > 1) d.qm_off = uint32_t((nu + k) * 192);       // (the reduced transforms' multipliers: the second half of the pool)
+        if (p.ncomp == 4) d.qm3_off = uint32_t(qm_tail[k] + (p.scale > 1 ? 64 : 0));      // (a fourth component's: behind both halves)
+        inf.model = p.model;
         d.seg_off = seg_off[k];
         inf.width = p.roi_w; inf.height = p.roi_h; inf.bpm = p.bpm; inf.nmcu = p.nmcu;      // (the picture written: scaled decode, rectangle)
         inf.roi_x = p.roi_x; inf.roi_y = p.roi_y; inf.full_w = p.out_w; inf.full_h = p.out_h;
@@ -1479,7 +1495,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 // the small pools first, back to back: they go up in one transfer from one host block (meta_*)
                 ar.take(&b->d_images, std::max<size_t>(n, 1) * sizeof(DevImage));
                 ar.take(&b->d_lut, std::max<size_t>(lut_pool, 8) * sizeof(LutEntry));
-                ar.take(&b->d_qm, std::max<size_t>(nu, 1) * 384 * sizeof(float));      // (the multipliers, then those of the reduced transforms)
+                ar.take(&b->d_qm, qm_floats * sizeof(float));      // (the multipliers, then those of the reduced transforms)
                 ar.take(&b->d_segs, std::max<size_t>(b->h_segs.size(), 2) * sizeof(uint32_t));
                 ar.take(&b->d_ii, std::max<size_t>(ii.size(), 1) * sizeof(InterleaveImg));
                 // per-image words the kernels expect to be zero: inside the block, so that its one transfer clears them (three
@@ -1550,7 +1566,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
             for (size_t rep = 0; rep < times; rep++)
                 HIPOK(hipMemcpyAsync(b->d_scan + rep * scan_pool, src->d_scan, scan_pool, hipMemcpyDeviceToDevice, up));
             HIPOK(hipMemcpyAsync(b->d_lut, src->d_lut, std::max<size_t>(lut_pool, 8) * sizeof(LutEntry), hipMemcpyDeviceToDevice, up));
-            HIPOK(hipMemcpyAsync(b->d_qm, src->d_qm, std::max<size_t>(nu, 1) * 384 * sizeof(float), hipMemcpyDeviceToDevice, up));
+            HIPOK(hipMemcpyAsync(b->d_qm, src->d_qm, qm_floats * sizeof(float), hipMemcpyDeviceToDevice, up));
         } else {
             const bool timing = std::getenv("MJX_TIMING") != nullptr;
             auto now = [] { return std::chrono::steady_clock::now(); };
@@ -1576,7 +1592,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 h_qm = reinterpret_cast<float *>(mirror(b->d_qm));
             } else {
                 b->h_lut.assign(std::max<size_t>(lut_pool, 8), 0);
-                b->h_qm.assign(std::max<size_t>(nu, 1) * 384, 0.f);
+                b->h_qm.assign(qm_floats, 0.f);
                 h_lut = b->h_lut.data();
                 h_qm = b->h_qm.data();
             }
@@ -1584,8 +1600,12 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 const ImagePlan &p = plans[k];
                 if (p.status != MJX_OK) continue;
                 if (lut_first[k]) std::memcpy(h_lut + lut_off[k], p.lut.data(), p.lut.size() * sizeof(LutEntry));
-                std::memcpy(h_qm + k * 192, p.qmult, sizeof p.qmult);
-                std::memcpy(h_qm + (nu + k) * 192, p.qmult_scaled, sizeof p.qmult_scaled);
+                std::memcpy(h_qm + k * 192, p.qmult, 192 * sizeof(float));
+                std::memcpy(h_qm + (nu + k) * 192, p.qmult_scaled, 192 * sizeof(float));
+                if (p.ncomp == 4) {
+                    std::memcpy(h_qm + qm_tail[k], p.qmult[3], 64 * sizeof(float));
+                    std::memcpy(h_qm + qm_tail[k] + 64, p.qmult_scaled[3], 64 * sizeof(float));
+                }
             }
             if (!meta_block) {
                 HIPOK(hipMemcpyAsync(b->d_lut, b->h_lut.data(), b->h_lut.size() * sizeof(LutEntry), hipMemcpyHostToDevice, up));
@@ -2265,7 +2285,8 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
         p.roi_x = d.roi_x; p.roi_y = d.roi_y; p.roi_w = d.roi_w; p.roi_h = d.roi_h;
         p.roi_mr0 = d.roi_mr0; p.roi_mr1 = d.roi_mr1; p.roi_mc0 = d.roi_mc0; p.roi_mc1 = d.roi_mc1;
         p.mcux = d.mcux; p.mcuy = d.mcuy; p.nmcu = d.nmcu;
-        for (uint32_t c = 0; c < 3; c++) { p.h[c] = d.ch[c]; p.v[c] = d.cv[c]; }
+        for (uint32_t c = 0; c < 4; c++) { p.h[c] = d.ch[c]; p.v[c] = d.cv[c]; }
+        p.model = src->info[k].model;                                                 // (... and its colour model)
         std::memcpy(p.blk_comp, d.blk_comp, sizeof p.blk_comp);
         std::memcpy(p.blk_bx, d.blk_bx, sizeof p.blk_bx);
         std::memcpy(p.blk_by, d.blk_by, sizeof p.blk_by);
@@ -2564,6 +2585,16 @@ extern "C" int mjx_batch_image_scale(const mjx_batch *b, size_t iu, uint8_t *sca
     if (!visible_index(b, iu, i)) return MJX_ERR_INVALID_ARG;
     const ImageInfo &inf = b->info[i];
     if (scale_denom) *scale_denom = uint8_t(inf.scale ? inf.scale : 1u);
+    return inf.status;
+}
+
+extern "C" int mjx_batch_image_color(const mjx_batch *b, size_t iu, uint8_t *model)
+{
+    if (b && !b->parts.empty()) { mjx_batch *pb; size_t pi; return route(b, iu, pb, pi) ? mjx_batch_image_color(pb, pi, model) : MJX_ERR_INVALID_ARG; }
+    size_t i;
+    if (!visible_index(b, iu, i)) return MJX_ERR_INVALID_ARG;
+    const ImageInfo &inf = b->info[i];
+    if (model) *model = uint8_t(inf.model);
     return inf.status;
 }
 

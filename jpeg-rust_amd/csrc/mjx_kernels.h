@@ -31,7 +31,7 @@ struct DevImage {
     uint32_t lut_n;         // entries (multiple of 4)
     uint32_t lut2_off, lut2_n;   // the set with pair parts (counting passes: k_huff_spec, merge rounds), HuffImage::tabs_pair
     uint32_t sub_off;       // index of subsequence 0 in the per-subsequence arrays
-    uint32_t qm_off;        // floats into the dequant-multiplier pool (3 x 64 per image)
+    uint32_t qm_off;        // floats into the dequant-multiplier pool (3 x 64 per image; a fourth component's: qm3_off)
     uint32_t width, height, mcux, mcuy, nmcu;
     uint32_t ncomp, bpm, hmax, vmax;
     uint32_t valid;         // 0: skip (error at plan time)
@@ -147,7 +147,24 @@ struct DevImage {
     uint32_t ycc_on, ycc_il, ycc_round;
     uint32_t ycc_x0[3], ycc_y0[3], ycc_w[3], ycc_h[3];
     uint64_t ycc_dev[3], ycc_off[3], ycc_pitch[3];
+    // colour models (mjx_opts.color = MJX_COLOR_FILE; ColorModel below).  model: what the pixel phase does with the components' samples;
+    // 0 (kModelPositional) is the decode of every picture planned without the option: one component grey, three Y, Cb, Cr.
+    // qm3_off: floats into the dequant-multiplier pool of the FOURTH component's 64 multipliers (components 0 .. 2 stay at qm_off).
+    // dc_shape: what the DC-prediction kernels choose by -- bpm for a picture of up to three components, kDcShape4 + bpm for one of
+    // four, which so never takes a kernel that carries three running sums.
+    uint32_t model, qm3_off, dc_shape;
 };
+// DevImage::model
+enum ColorModel : uint32_t {
+    kModelPositional = 0,   // grey, or Y, Cb, Cr by position: the pixel phase as it has always been
+    kModelRgb = 2,          // three components stored as R, G, B: no arithmetic
+    kModelCmyk = 3,         // four components, Adobe's convention: R,G,B = ink_mul(s_c, s_3)
+    kModelYcck = 4,         // the colour step on components 0 .. 2, its bytes complemented (C = 255 - R), then ink_mul with s_3
+};
+constexpr uint32_t kDcShape4 = 16;       // DevImage::dc_shape of a four-component picture = kDcShape4 + bpm (bpm <= 10)
+// mul(a, k) of mjx_opts.color: (a k + 127) / 255 in integers -- the host (mjx_ink_mul) and the pixel phase run this routine; the
+// division by a constant is a multiplication and a shift, exact for every a, k < 256.
+MJX_HD uint32_t ink_mul(uint32_t a, uint32_t k) { return (a * k + 127u) / 255u; }
 // DevImage::mode.  The form: what stage B computes per tile.
 enum StageBForm : uint32_t {
     kFormGeneric = 0,       // any sampling layout

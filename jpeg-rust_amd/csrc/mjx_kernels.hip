@@ -2078,13 +2078,17 @@ __device__ __forceinline__ void wg_reduce3(int32_t v[3], int32_t (*s_w)[3], int3
 }
 
 constexpr uint32_t kDcFastShapes = (1u << 1) | (1u << 3) | (1u << 4) | (1u << 6);     // blocks per MCU with a fast kernel
+// The kernels choose by DevImage::dc_shape, not by bpm: a four-component picture (kDcShape4 + bpm) has the bpm of some three-component
+// layout -- 1x1x4 that of 4:2:2, (2,1),(1,1),(1,1),(2,1) that of 4:2:0 -- and must take neither a fast shape nor the generic kernels
+// here, which carry three running sums; it takes k_dc_sums4 / k_dc_apply4 / k_dc_restart4 below.
+constexpr uint32_t kDcNotGeneric3 = kDcFastShapes | (~0u << kDcShape4);            // shapes k_dc_sums / k_dc_apply leave alone
 extern "C" __global__ __launch_bounds__(256) void k_dc_sums(const DevImage *images, const int16_t *dcd,
                                                              int32_t *segsum, uint32_t max_segs, const uint32_t *img_flags)
 {
     __shared__ int32_t s_w[4][3];
     const DevImage &im = images[blockIdx.y];
     const uint32_t m0 = blockIdx.x * kDcSegMcus;
-    if (!im.valid || m0 >= im.nmcu || img_flags[im.status_idx] || ((kDcFastShapes >> im.bpm) & 1u) || im.nseg > 1) return;
+    if (!im.valid || m0 >= im.nmcu || img_flags[im.status_idx] || ((kDcNotGeneric3 >> im.dc_shape) & 1u) || im.nseg > 1) return;
     const uint32_t bpm = im.bpm, tid = threadIdx.x;
     const uint32_t nv = (min(uint32_t(kDcSegMcus), im.nmcu - m0)) * bpm;
     const int16_t *dc = dcd + im.coef_off + size_t(m0) * bpm;
@@ -2109,7 +2113,7 @@ extern "C" __global__ __launch_bounds__(256) void k_dc_apply(const DevImage *ima
     __shared__ int32_t s_wsum[4][3];
     const DevImage &im = images[blockIdx.y];
     const uint32_t seg0 = blockIdx.x * kDcSegMcus;
-    if (!im.valid || seg0 >= im.nmcu || img_flags[im.status_idx] || ((kDcFastShapes >> im.bpm) & 1u) || im.nseg > 1) return;
+    if (!im.valid || seg0 >= im.nmcu || img_flags[im.status_idx] || ((kDcNotGeneric3 >> im.dc_shape) & 1u) || im.nseg > 1) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, bpm = im.bpm;
     const uint32_t seg1 = min(im.nmcu, seg0 + kDcSegMcus);
     int32_t *dc = dcbuf + im.coef_off;
@@ -2226,7 +2230,7 @@ __global__ __launch_bounds__(256) void k_dc_sums_t(const DevImage *images, const
     __shared__ int32_t s_w[4][3];
     const DevImage &im = images[blockIdx.y];
     const uint32_t seg0 = blockIdx.x * kDcSegMcus;
-    if (!im.valid || im.bpm != BPM || seg0 >= im.nmcu || img_flags[im.status_idx] || im.nseg > 1) return;
+    if (!im.valid || im.dc_shape != BPM || seg0 >= im.nmcu || img_flags[im.status_idx] || im.nseg > 1) return;
     const uint32_t seg1 = min(im.nmcu, seg0 + kDcSegMcus);
     int32_t v[kDcLaneMcus * BPM];
     int32_t *p;
@@ -2254,7 +2258,7 @@ __global__ __launch_bounds__(256) void k_dc_apply_t(const DevImage *images, cons
     __shared__ int32_t s_wsum[4][3];
     const DevImage &im = images[blockIdx.y];
     const uint32_t seg0 = blockIdx.x * kDcSegMcus;
-    if (!im.valid || im.bpm != BPM || seg0 >= im.nmcu || img_flags[im.status_idx] || im.nseg > 1) return;
+    if (!im.valid || im.dc_shape != BPM || seg0 >= im.nmcu || img_flags[im.status_idx] || im.nseg > 1) return;
     const uint32_t seg1 = min(im.nmcu, seg0 + kDcSegMcus);
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int32_t v[kDcLaneMcus * BPM];
@@ -2345,7 +2349,7 @@ __global__ __launch_bounds__(256) void k_dc_scan_t(const DevImage *images, const
     const uint32_t img = picture_of_slot(blockIdx.x, gridDim.x), seg = blockIdx.y;         // (the image is the fast dimension, see above)
     const DevImage &im = images[img];
     const uint32_t seg0 = seg * kDcSegMcus;
-    if (!im.valid || im.bpm != BPM || seg0 >= im.nmcu || img_flags[im.status_idx] || im.nseg > 1) return;
+    if (!im.valid || im.dc_shape != BPM || seg0 >= im.nmcu || img_flags[im.status_idx] || im.nseg > 1) return;
     const uint32_t seg1 = min(im.nmcu, seg0 + kDcSegMcus);
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int32_t v[kDcLaneMcus * BPM];
@@ -2440,7 +2444,7 @@ extern "C" __global__ __launch_bounds__(256) void k_dc_restart(const DevImage *i
                                                                 const uint32_t *img_flags)
 {
     const DevImage &im = images[blockIdx.y];
-    if (!im.valid || im.nseg <= 1 || img_flags[im.status_idx]) return;
+    if (!im.valid || im.nseg <= 1 || im.dc_shape >= kDcShape4 || img_flags[im.status_idx]) return;
     const uint32_t g = blockIdx.x * 256 + threadIdx.x;
     if (g >= im.nseg) return;
     const uint32_t seg_blocks = im.restart_mcus * im.bpm, b0 = g * seg_blocks;
@@ -2461,6 +2465,151 @@ extern "C" __global__ __launch_bounds__(256) void k_dc_restart(const DevImage *i
             p0 = c == 0 ? r : p0;
             p1 = c == 1 ? r : p1;
             p2 = c == 2 ? r : p2;
+            j = j + 1 == im.bpm ? 0 : j + 1;
+        }
+    }
+}
+
+// ---- four components (mjx_opts.color = MJX_COLOR_FILE: CMYK, YCCK) -----------------------------------------------------------------
+// The generic kernels above with four running sums: k_dc_sums4 / k_dc_apply4 for a picture without restart intervals, k_dc_restart4
+// with them.  They take the pictures whose dc_shape says four components and no others; their segment sums lie four to a segment in
+// a region of their own behind the three-component kernels' (launch_dc_scan).  No fast shapes: these pictures are rare.
+__device__ __forceinline__ int32_t dc_pick4(uint32_t c, const int32_t b[4])
+{
+    return c == 0 ? b[0] : (c == 1 ? b[1] : (c == 2 ? b[2] : b[3]));
+}
+__device__ __forceinline__ void dc_put4(uint32_t c, int32_t r, int32_t b[4])
+{
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) b[k] = c == k ? r : b[k];
+}
+extern "C" __global__ __launch_bounds__(256) void k_dc_sums4(const DevImage *images, const int16_t *dcd,
+                                                              int32_t *segsum, uint32_t max_segs, const uint32_t *img_flags)
+{
+    __shared__ int32_t s_w[4][4];
+    const DevImage &im = images[blockIdx.y];
+    const uint32_t m0 = blockIdx.x * kDcSegMcus;
+    if (!im.valid || m0 >= im.nmcu || img_flags[im.status_idx] || im.dc_shape < kDcShape4 || im.nseg > 1) return;
+    const uint32_t bpm = im.bpm, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t nv = (min(uint32_t(kDcSegMcus), im.nmcu - m0)) * bpm;
+    const int16_t *dc = dcd + im.coef_off + size_t(m0) * bpm;
+    int32_t sum[4] = {0, 0, 0, 0};
+    for (uint32_t i = tid; i < nv; i += 256) {
+        const int32_t v = dc[i];
+        const uint32_t c = im.blk_comp[i % bpm];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) sum[k] += c == k ? v : 0;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) sum[c] += __shfl_xor(sum[c], d);
+    if (lane == 0) { s_w[wave][0] = sum[0]; s_w[wave][1] = sum[1]; s_w[wave][2] = sum[2]; s_w[wave][3] = sum[3]; }
+    __syncthreads();
+    if (tid < 4) segsum[(size_t(blockIdx.y) * max_segs + blockIdx.x) * 4 + tid] = s_w[0][tid] + s_w[1][tid] + s_w[2][tid] + s_w[3][tid];
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_dc_apply4(const DevImage *images, const int16_t *dcd, int32_t *dcbuf,
+                                                               const int32_t *segsum, uint32_t max_segs,
+                                                               const uint32_t *img_flags)
+{
+    __shared__ int32_t s_dc[256 * kMaxBlocksPerMcu];
+    __shared__ int32_t s_wsum[4][4];
+    const DevImage &im = images[blockIdx.y];
+    const uint32_t seg0 = blockIdx.x * kDcSegMcus;
+    if (!im.valid || seg0 >= im.nmcu || img_flags[im.status_idx] || im.dc_shape < kDcShape4 || im.nseg > 1) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, bpm = im.bpm;
+    const uint32_t seg1 = min(im.nmcu, seg0 + kDcSegMcus);
+    int32_t *dc = dcbuf + im.coef_off;
+    const int16_t *dd = dcd + im.coef_off;
+    int32_t carry[4] = {0, 0, 0, 0};
+    for (uint32_t sgi = 0; sgi < blockIdx.x; sgi++) {
+        const int32_t *p = segsum + (size_t(blockIdx.y) * max_segs + sgi) * 4;
+        carry[0] += p[0]; carry[1] += p[1]; carry[2] += p[2]; carry[3] += p[3];
+    }
+    uint32_t comp[kMaxBlocksPerMcu];
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxBlocksPerMcu; j++) comp[j] = im.blk_comp[j];
+    for (uint32_t m0 = seg0; m0 < seg1; m0 += 256) {
+        const uint32_t nm = min(256u, seg1 - m0), nv = nm * bpm;
+        for (uint32_t i = tid; i < nv; i += 256) s_dc[i] = dd[size_t(m0) * bpm + i];
+        __syncthreads();
+        int32_t sum[4] = {0, 0, 0, 0};
+        if (tid < nm) {
+#pragma unroll
+            for (uint32_t j = 0; j < kMaxBlocksPerMcu; j++) {
+                if (j < bpm) {
+                    const int32_t v = s_dc[tid * bpm + j];
+#pragma unroll
+                    for (uint32_t k = 0; k < 4; k++) sum[k] += comp[j] == k ? v : 0;
+                }
+            }
+        }
+        int32_t incl[4] = {sum[0], sum[1], sum[2], sum[3]};
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const int32_t o = __shfl_up(incl[c], d);
+                if (lane >= uint32_t(d)) incl[c] += o;
+            }
+        }
+        if (lane == 63) { s_wsum[wave][0] = incl[0]; s_wsum[wave][1] = incl[1]; s_wsum[wave][2] = incl[2]; s_wsum[wave][3] = incl[3]; }
+        __syncthreads();
+        int32_t base[4];
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            base[c] = carry[c];
+            int32_t total = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < 4; w++) {
+                const int32_t v = s_wsum[w][c];
+                base[c] += w < wave ? v : 0;
+                total += v;
+            }
+            base[c] += incl[c] - sum[c];
+            carry[c] += total;
+        }
+        if (tid < nm) {
+#pragma unroll
+            for (uint32_t j = 0; j < kMaxBlocksPerMcu; j++) {
+                if (j < bpm) {
+                    const uint32_t c = comp[j];
+                    const int32_t r = dc_pick4(c, base) + s_dc[tid * bpm + j];
+                    s_dc[tid * bpm + j] = r;
+                    dc_put4(c, r, base);
+                }
+            }
+        }
+        __syncthreads();
+        for (uint32_t i = tid; i < nv; i += 256) dc[size_t(m0) * bpm + i] = s_dc[i];
+        __syncthreads();
+    }
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_dc_restart4(const DevImage *images, const int16_t *dcd, int32_t *dcbuf,
+                                                                 const uint32_t *img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    if (!im.valid || im.nseg <= 1 || im.dc_shape < kDcShape4 || img_flags[im.status_idx]) return;
+    const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= im.nseg) return;
+    const uint32_t seg_blocks = im.restart_mcus * im.bpm, b0 = g * seg_blocks;
+    const uint32_t b1 = min(b0 + seg_blocks, im.himg.total_blocks);
+    int32_t *dc = dcbuf + im.coef_off;
+    const int16_t *dd = dcd + im.coef_off;
+    int32_t pred[4] = {0, 0, 0, 0};
+    uint32_t j = 0;
+    for (uint32_t b = b0; b < b1; b += 8) {                                // eight loads in flight, then the serial part
+        int32_t v[8];
+#pragma unroll
+        for (uint32_t q = 0; q < 8; q++) v[q] = b + q < b1 ? int32_t(dd[b + q]) : 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 8; q++) {
+            const uint32_t c = im.blk_comp[j];
+            const int32_t r = dc_pick4(c, pred) + v[q];
+            if (b + q < b1) dc[b + q] = r;
+            dc_put4(c, r, pred);
             j = j + 1 == im.bpm ? 0 : j + 1;
         }
     }
@@ -2765,6 +2914,41 @@ __device__ __forceinline__ uint32_t pack4_luma(float y0, float y1, float y2, flo
                  : "v"(y0), "v"(y1), "v"(y2), "v"(y3));
     return o;
 }
+// ---- colour models (mjx_opts.color = MJX_COLOR_FILE; DevImage::model) -----------------------------------------------------------------
+// The twelve bytes of four pixels times their four K bytes: byte i of the packed pixels belongs to pixel i / 3.  ink_mul
+// (mjx_kernels.h) is integer arithmetic -- the division by 255 a multiplication and a shift --, so the device and the host agree on
+// every pair.
+__device__ __forceinline__ Rgb4 ink4(const Rgb4 &w, uint32_t kb)
+{
+    const uint32_t in[3] = {w.a, w.b, w.c};
+    uint32_t out[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t i = 0; i < 12; i++) {
+        const uint32_t a = (in[i >> 2] >> ((i & 3u) * 8u)) & 0xffu, k = (kb >> ((i / 3u) * 8u)) & 0xffu;
+        out[i >> 2] |= ink_mul(a, k) << ((i & 3u) * 8u);
+    }
+    return Rgb4{out[0], out[1], out[2]};
+}
+// Four pixels of a picture whose model is not the positional one, from the samples of its three or four components (each with its
+// level shift: the DC term carries it, k_idct_color): RGB passes them through, YCCK runs the colour step on the first three and
+// complements its bytes, and CMYK and YCCK multiply the bytes by K's (kb: its four bytes, packed by the caller before it loads the other components, so that the
+// fourth costs no registers).  `model` is uniform.
+__device__ __forceinline__ Rgb4 model_pixels4(uint32_t model, const float a[4], const float b[4], const float c[4], uint32_t kb)
+{
+    Rgb p[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (model == kModelYcck) p[k] = ycc_to_rgb(a[k], chroma_terms(b[k], c[k]));
+        else p[k] = Rgb{a[k], b[k], c[k]};
+    }
+    Rgb4 w = pack4(p);
+    // (YCCK: the colour step gives back what the writer took the inks from, C = 255 - R as libjpeg's ycck_cmyk_convert has it; on a
+    // byte that is its complement)
+    if (model == kModelYcck) w = Rgb4{~w.a, ~w.b, ~w.c};
+    if (model != kModelRgb) w = ink4(w, kb);
+    return w;
+}
+
 // Where a luminance picture's elements go: its output format, or -- a resized or oriented picture (or_on kOrCopyLuma, kOrResizeLuma) -- the intermediate,
 // roi_w x roi_h bytes at rgb_off of the pool.
 __device__ __forceinline__ OutFmt luma_fmt(const DevImage &im, uint8_t *rgb_pool)
@@ -3209,14 +3393,15 @@ __device__ __forceinline__ void idct_row_inplace(float *rowf)
 // anything) -- the pixel phase of a 4:2:2 tile took 30.7 k cycles per wave where the 4:2:0 form takes 9.1 k for twice the pixels
 // (round 5, tools/stamp_stage_b.py).
 struct GenShape {
-    uint32_t xsh[3], ysh[3];         // log2 of the replication of component c's samples
-    uint32_t first[3], ch[3];        // its first block inside the MCU, its blocks per MCU row
+    uint32_t xsh[4], ysh[4];         // log2 of the replication of component c's samples
+    uint32_t first[4], ch[4];        // its first block inside the MCU, its blocks per MCU row
     uint32_t ncomp, bpm, hmax, vmax, log2_tile, width, height, mcux;
+    uint32_t model;                  // DevImage::model (ColorModel): 0 for every picture planned without MJX_COLOR_FILE
 };
 __device__ __forceinline__ GenShape gen_shape(const DevImage &im)
 {
     GenShape g;
-    for (uint32_t c = 0; c < 3; c++) {
+    for (uint32_t c = 0; c < 4; c++) {
         g.xsh[c] = im.hmax > im.ch[c] ? 1 : 0;
         g.ysh[c] = im.vmax > im.cv[c] ? 1 : 0;
         g.first[c] = im.cfirst[c];
@@ -3224,6 +3409,7 @@ __device__ __forceinline__ GenShape gen_shape(const DevImage &im)
     }
     g.ncomp = im.ncomp; g.bpm = im.bpm; g.hmax = im.hmax; g.vmax = im.vmax; g.log2_tile = im.log2_tile;
     g.width = im.width; g.height = im.height; g.mcux = im.mcux;
+    g.model = im.model;
     return g;
 }
 __device__ __forceinline__ void load4(const float *tile, const GenShape &g, uint32_t mcu_blk0, uint32_t c,
@@ -3449,12 +3635,15 @@ __device__ __forceinline__ void pixels_420_luma(uint32_t width, uint32_t height,
 // INTERIOR: every MCU of the tile lies in one MCU row and fully inside the picture, rows are 4-byte aligned -- no bounds, plain 12-byte stores
 // ROI: the picture written is the rectangle `roi` of this one (as pixels_420)
 // OUT: (a ROI form) the rectangle leaves in the picture's output format (store4_out)
-template <bool INTERIOR, bool COLOUR, bool ROI = false, bool OUT = false>
+// MODEL: (a COLOUR form with bounds) the picture may have one of the colour models of MJX_COLOR_FILE (g.model != 0: RGB, CMYK, YCCK) --
+//   a uniform branch beside the colour step, the pixels from model_pixels4; one form for both, so that no store site is there twice
+template <bool INTERIOR, bool COLOUR, bool ROI = false, bool OUT = false, bool MODEL = false>
 __device__ __forceinline__ void pixels_generic_t(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm,
                                                  uint8_t *out_img, bool aligned, const Roi &roi = Roi{}, const OutFmt *of = nullptr)
 {
     static_assert(!OUT || ROI, "the output formats are built on the cropped forms");
     static_assert(!ROI || !INTERIOR, "strips of a cropped picture are cut at the rectangle's edges");
+    static_assert(!MODEL || (COLOUR && !INTERIOR), "the colour models ride on the colour form with bounds");
     const uint32_t tid = threadIdx.x, bpm = g.bpm;
     const uint32_t lstrips = g.hmax == 2 ? 2u : 1u;          // log2 of the 4-pixel strips per MCU row (2*hmax)
     const uint32_t R = (1u << g.log2_tile) << lstrips;       // strips per pixel row of the tile (power of two <= 256)
@@ -3474,21 +3663,35 @@ __device__ __forceinline__ void pixels_generic_t(const GenShape &g, const float 
         if (!INTERIOR && my * rows + r >= g.height) break;
         if (ROI && (my * rows + r < roi.y || my * rows + r >= roi.y + roi.h)) continue;
         float yv[4], cbv[4], crv[4];
-        load4(tile, g, t * bpm, 0, sx * 4, r, yv);
-        Rgb p[4];
-        if (COLOUR) {
+        Rgb4 w;
+        if (MODEL && g.model) {
+            uint32_t kb = 0;
+            if (g.model != kModelRgb) {        // (K's bytes first: packed before the other components are loaded)
+                load4(tile, g, t * bpm, 3, sx * 4, r, yv);
+                kb = pack4_luma(yv[0], yv[1], yv[2], yv[3]);
+            }
+            load4(tile, g, t * bpm, 0, sx * 4, r, yv);
             load4(tile, g, t * bpm, 1, sx * 4, r, cbv);
             load4(tile, g, t * bpm, 2, sx * 4, r, crv);
-#pragma unroll
-            for (int k = 0; k < 4; k++) p[k] = ycc_to_rgb(yv[k], chroma_terms(cbv[k], crv[k]));
+            w = model_pixels4(g.model, yv, cbv, crv, kb);
         } else {
+            load4(tile, g, t * bpm, 0, sx * 4, r, yv);
+            Rgb p[4];
+            if (COLOUR) {
+                load4(tile, g, t * bpm, 1, sx * 4, r, cbv);
+                load4(tile, g, t * bpm, 2, sx * 4, r, crv);
 #pragma unroll
-            for (int k = 0; k < 4; k++) p[k].r = p[k].g = p[k].b = yv[k];                          // decoder.rs:318-325 (+128 is in the samples)
+                for (int k = 0; k < 4; k++) p[k] = ycc_to_rgb(yv[k], chroma_terms(cbv[k], crv[k]));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; k++) p[k].r = p[k].g = p[k].b = yv[k];                          // decoder.rs:318-325 (+128 is in the samples)
+            }
+            w = pack4(p);
         }
-        if (OUT) store4_out(*of, roi, px, my * rows + r, pack4(p), npix);
-        else if (ROI) store4_roi(out_img, roi, px, my * rows + r, pack4(p), npix);
-        else if (INTERIOR) store_rgb4(dst, pack4(p));
-        else store4(dst, pack4(p), aligned, npix);
+        if (OUT) store4_out(*of, roi, px, my * rows + r, w, npix);
+        else if (ROI) store4_roi(out_img, roi, px, my * rows + r, w, npix);
+        else if (INTERIOR) store_rgb4(dst, w);
+        else store4(dst, w, aligned, npix);
     }
 }
 // ... luminance output (k_idct_color<kFormGeneric | kSinkLuma, ...>): pixels_generic_t's walk, component 0 alone (upsampled by box replication
@@ -3520,12 +3723,12 @@ __device__ __forceinline__ void pixels_generic_luma(const GenShape &g, const flo
 __device__ __forceinline__ void pixels_generic_roi(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm,
                                                    uint8_t *out_img, bool aligned, const Roi &roi)
 {
-    if (g.ncomp == 3) pixels_generic_t<false, true, true>(g, tile, m0, nm, out_img, aligned, roi);
+    if (g.ncomp >= 3) pixels_generic_t<false, true, true, false, true>(g, tile, m0, nm, out_img, aligned, roi);
     else pixels_generic_t<false, false, true>(g, tile, m0, nm, out_img, aligned, roi);
 }
 __device__ __forceinline__ void pixels_generic_out(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm, const Roi &roi, const OutFmt &of)
 {
-    if (g.ncomp == 3) pixels_generic_t<false, true, true, true>(g, tile, m0, nm, nullptr, false, roi, &of);
+    if (g.ncomp >= 3) pixels_generic_t<false, true, true, true, true>(g, tile, m0, nm, nullptr, false, roi, &of);
     else pixels_generic_t<false, false, true, true>(g, tile, m0, nm, nullptr, false, roi, &of);
 }
 __device__ __forceinline__ void pixels_generic(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm,
@@ -3533,9 +3736,9 @@ __device__ __forceinline__ void pixels_generic(const GenShape &g, const float *t
 {
     const uint32_t T = 1u << g.log2_tile, my0 = m0 / g.mcux, mx0 = m0 - my0 * g.mcux;
     const bool interior = aligned && nm == T && mx0 + T <= g.mcux && (mx0 + T) * 8 * g.hmax <= g.width && (my0 + 1) * 8 * g.vmax <= g.height;
-    if (g.ncomp == 3) {
-        if (interior) pixels_generic_t<true, true>(g, tile, m0, nm, out_img, aligned);
-        else pixels_generic_t<false, true>(g, tile, m0, nm, out_img, aligned);
+    if (g.ncomp >= 3) {            // (a picture with a colour model of MJX_COLOR_FILE has no interior form: the one with bounds does both)
+        if (interior && !g.model) pixels_generic_t<true, true>(g, tile, m0, nm, out_img, aligned);
+        else pixels_generic_t<false, true, false, false, true>(g, tile, m0, nm, out_img, aligned);
     } else {
         if (interior) pixels_generic_t<true, false>(g, tile, m0, nm, out_img, aligned);
         else pixels_generic_t<false, false>(g, tile, m0, nm, out_img, aligned);
@@ -3903,6 +4106,16 @@ __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *ti
         if (ROI && (Y < roi.y || Y >= roi.y + roi.h || X + SW <= roi.x || X >= roi.x + roi.w)) continue;
         const uint32_t npix = min(SW, g.width - X);
         float s[3][4];
+        uint32_t kb = 0;
+        if (g.ncomp == 4u) {               // (K's bytes first: packed before the other components are loaded)
+            const uint32_t ys = r >> g.ysh[3], bro = g.first[3] + (ys / N) * g.ch[3];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                const uint32_t xs = min(sx * SW + k, PW - 1u) >> g.xsh[3];
+                s[0][k] = tile[(t * g.bpm + bro + xs / N) * kPixStride + (ys % N) * N + xs % N];
+            }
+            kb = pack4_luma(s[0][0], s[0][1], s[0][2], s[0][3]);
+        }
 #pragma unroll
         for (uint32_t c = 0; c < 3; c++) {
             if (c >= g.ncomp) break;
@@ -3913,15 +4126,21 @@ __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *ti
                 s[c][k] = tile[(t * g.bpm + bro + xs / N) * kPixStride + (ys % N) * N + xs % N];
             }
         }
-        Rgb p[4];
+        Rgb4 w;
+        if (g.model) {
+            w = model_pixels4(g.model, s[0], s[1], s[2], kb);
+        } else {
+            Rgb p[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (g.ncomp == 3) p[k] = ycc_to_rgb(s[0][k], chroma_terms(s[1][k], s[2][k]));
-            else p[k].r = p[k].g = p[k].b = s[0][k];
+            for (int k = 0; k < 4; k++) {
+                if (g.ncomp == 3) p[k] = ycc_to_rgb(s[0][k], chroma_terms(s[1][k], s[2][k]));
+                else p[k].r = p[k].g = p[k].b = s[0][k];
+            }
+            w = pack4(p);
         }
-        if (OUT) store4_out(*of, roi, X, Y, pack4(p), npix);
-        else if (ROI) store4_roi(out_img, roi, X, Y, pack4(p), npix);
-        else store4(out_img + (size_t(Y) * g.width + X) * 3, pack4(p), al, npix);
+        if (OUT) store4_out(*of, roi, X, Y, w, npix);
+        else if (ROI) store4_roi(out_img, roi, X, Y, w, npix);
+        else store4(out_img + (size_t(Y) * g.width + X) * 3, w, al, npix);
     }
 }
 
@@ -4002,7 +4221,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     static_assert(!ROI || MODE != int(kFormRefCompat), "REF_COMPAT has no rectangles");
     // (its own symbol: dynamic LDS arrays of one name share their alignment, and the entropy kernels ask for 2 KiB)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_px[];
-    __shared__ float s_qm[3 * 64];
+    __shared__ float s_qm[(MODE == 1 ? 3 : 4) * 64];      // (a fourth component's multipliers: never in the 4:2:0 form)
     __shared__ uint8_t s_nat[64];
     __shared__ uint8_t s_comp[MODE == 1 ? 4 : 256];     // (4:2:0: the component comes from arithmetic on the block index)
     // per tile of the workgroup (+ sentinel).  Linear stream: s_eoff = the tile's first entry.  Quad-interleaved stream (QUAD):
@@ -4119,6 +4338,9 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     else if constexpr (PLANAR) tile_fetch_planar<LANES, PF>(psrc, s_ptile[tile0 % 3u], dcbuf, pdc, tile0 * T, pr0, pa0, nmcu, mcux, cur);
     else tile_fetch<LANES, PF>(src, s_eoff + (tile_first - tile0), dcs, tile_first, tile_blocks, total_blocks, cur);
     for (uint32_t i = tid; i < 192; i += LANES) s_qm[i] = qmult[im.qm_off + i];
+    if constexpr (!M420) {
+        if (im.ncomp == 4u && tid < 64u) s_qm[192u + tid] = qmult[im.qm3_off + tid];
+    }
     if (tid < 64) {
         constexpr uint8_t ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
@@ -4129,8 +4351,14 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     if (!M420 && tid < tile_blocks) s_comp[tid] = im.blk_comp[tid % bpm];
     // the lane's own block slot (tid) has the same component in every tile (a tile is whole MCUs): its DC multiplier and level shift
     const uint32_t my_comp = im.blk_comp[tid % bpm];
-    float my_dc_qm = qmult[im.qm_off + my_comp * 64];
+    float my_dc_qm = qmult[(!M420 && my_comp == 3u) ? im.qm3_off : im.qm_off + my_comp * 64];
     float my_dc_add = (MODE != 2 && my_comp == 0) ? 128.0f : 0.0f;
+    // the colour models of MJX_COLOR_FILE (the sinks that write R,G,B): every component that leaves as a byte of its own takes the
+    // level shift -- all of RGB's and CMYK's, Y and K of YCCK (its Cb and Cr enter the colour step as they are)
+    if constexpr ((MODE == 0 || MODE >= 3) && (SINK == kSinkPacked || SINK == kSinkCropped || SINK == kSinkOut)) {
+        const uint32_t model = im.model;
+        if (model == kModelRgb || model == kModelCmyk || (model == kModelYcck && my_comp == 3u)) my_dc_add = 128.0f;
+    }
     if constexpr (PLANES) my_dc_add = 128.5f;         // (every component's level shift and the rounding: the store truncates, planes_store)
     if constexpr (YCC) my_dc_add = im.ycc_round ? 128.5f : 128.0f;      // (every component's level shift; libjpeg's pixels: and the rounding)
     float *tile_f = reinterpret_cast<float *>(smem_px);
@@ -4345,9 +4573,10 @@ __device__ __forceinline__ void dc_color_body(const DevImage *__restrict__ image
     if constexpr (ROI) { X += im.roi_x; Y += im.roi_y; }
     const uint32_t hmax = im.hmax, vmax = im.vmax;
     const uint32_t mx = X / hmax, my = Y / vmax, lx = X - mx * hmax, ly = Y - my * vmax;
-    float s[3] = {0.f, 0.f, 0.f};
+    const uint32_t model = im.model;
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (uint32_t c = 0; c < 3; c++) {
+    for (uint32_t c = 0; c < 4; c++) {
         if (c >= im.ncomp) break;
         const uint32_t bx = hmax > im.ch[c] ? lx >> 1 : lx, by = vmax > im.cv[c] ? ly >> 1 : ly;
         const uint32_t k = im.cfirst[c] + by * im.ch[c] + bx;
@@ -4359,12 +4588,20 @@ __device__ __forceinline__ void dc_color_body(const DevImage *__restrict__ image
         } else {
             dc = dcbuf[im.coef_off + (uint64_t(my) * im.mcux + mx) * im.bpm + k];
         }
-        s[c] = float(dc) * qmult[im.qm_off + c * 64u] + (c == 0 ? 128.0f : 0.0f);
+        // (the level shift: component 0 -- and, with a colour model of MJX_COLOR_FILE, every component that leaves as a byte of its own)
+        const bool shift = c == 0 || model == kModelRgb || model == kModelCmyk || (model == kModelYcck && c == 3u);
+        s[c] = float(dc) * qmult[c == 3u ? im.qm3_off : im.qm_off + c * 64u] + (shift ? 128.0f : 0.0f);
     }
     Rgb p;
-    if (im.ncomp == 3) p = ycc_to_rgb(s[0], chroma_terms(s[1], s[2]));
+    if (model == kModelRgb || model == kModelCmyk) p = Rgb{s[0], s[1], s[2]};
+    else if (im.ncomp >= 3) p = ycc_to_rgb(s[0], chroma_terms(s[1], s[2]));
     else p.r = p.g = p.b = s[0];
-    const uint32_t word = pack_u8(p.b, 2, pack_u8(p.g, 1, pack_u8(p.r, 0, 0)));
+    uint32_t word = pack_u8(p.b, 2, pack_u8(p.g, 1, pack_u8(p.r, 0, 0)));
+    if (model == kModelCmyk || model == kModelYcck) {
+        const uint32_t kb = pack_u8(s[3], 0, 0) & 0xffu;
+        if (model == kModelYcck) word = ~word & 0xffffffu;            // (C = 255 - R, as model_pixels4)
+        word = ink_mul(word & 0xffu, kb) | ink_mul((word >> 8) & 0xffu, kb) << 8 | ink_mul((word >> 16) & 0xffu, kb) << 16;
+    }
     if constexpr (OUT) {
         const OutFmt f = out_fmt(im, rgb);
         const uint32_t col = X - im.roi_x;
@@ -5028,6 +5265,16 @@ void launch_dc_scan(hipStream_t st, uint32_t max_segs, uint32_t nimg, const DevI
                     uint32_t *segflag, uint32_t gen, uint32_t *fail, uint32_t spin_limit, bool fault)
 {
     const dim3 grid(max_segs, nimg), wg(256);
+    // (bit 31 of bpm_mask: the chunk holds four-component pictures -- their kernels, their own region of segment sums behind the
+    // three-component kernels' max_segs x nimg x 3 words)
+    const bool four = (bpm_mask >> 31) != 0;
+    bpm_mask &= 0x7fffffffu;
+    if (four) {
+        int32_t *segsum4 = segsum + size_t(3) * max_segs * nimg;
+        hipLaunchKernelGGL(k_dc_sums4, grid, wg, 0, st, images, dcd, segsum4, max_segs, img_flags);
+        hipLaunchKernelGGL(k_dc_apply4, grid, wg, 0, st, images, dcd, dcbuf, segsum4, max_segs, img_flags);
+        if (max_restart_segs) hipLaunchKernelGGL(k_dc_restart4, dim3((max_restart_segs + 255) / 256, nimg), wg, 0, st, images, dcd, dcbuf, img_flags);
+    }
     if (segflag) {          // the common MCU shapes in one pass (k_dc_scan_t); segflag == nullptr: two passes as before
         const dim3 grid(nimg, max_segs);
         if (bpm_mask & (1u << 1)) hipLaunchKernelGGL(k_dc_scan_t<1>, grid, wg, 0, st, images, dcd, dcbuf, segflag, max_segs, img_flags, gen, fail, spin_limit, fault ? 1u : 0u);

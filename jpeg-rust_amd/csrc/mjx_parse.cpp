@@ -6,6 +6,7 @@
 // JPEGDecoder::scan_header does (src/jpeg/decoder.rs:113-152), and de-stuffs the entropy-coded
 // segment to end-of-file (mod.rs:371-385).  The reference's panics become status codes.
 #include "mjx.h"
+#include "mjx_kernels.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -57,7 +58,25 @@ struct ParserState {
     uint8_t *lent = nullptr;
     size_t lent_cap = 0;
     mjx_scan_desc *d;
+    // MJX_COLOR_FILE: the JFIF and Adobe segments seen so far
+    bool color_file = false, jfif = false, adobe = false;
+    uint8_t adobe_transform = 0;
 };
+
+// libjpeg's default_decompress_parms (mjx.h: mjx_opts.color): what the components of a frame are
+uint8_t decide_model(unsigned ncomp, bool jfif, bool adobe, uint8_t transform, const uint8_t *ids)
+{
+    if (ncomp == 1) return MJX_MODEL_GREY;
+    if (ncomp == 3) {
+        if (jfif) return MJX_MODEL_YCBCR;
+        if (adobe) return transform == 0 ? MJX_MODEL_RGB : MJX_MODEL_YCBCR;
+        return ids[0] == 'R' && ids[1] == 'G' && ids[2] == 'B' ? MJX_MODEL_RGB : MJX_MODEL_YCBCR;
+    }
+    return adobe && transform != 0 ? MJX_MODEL_YCCK : MJX_MODEL_CMYK;
+}
+// An APP0 payload that names JFIF; an APP14 payload that is Adobe's (at least 12 bytes, the transform is byte 11)
+bool is_jfif(const uint8_t *p, size_t n) { return n >= 5 && std::memcmp(p, "JFIF\0", 5) == 0; }
+bool is_adobe(const uint8_t *p, size_t n) { return n >= 12 && std::memcmp(p, "Adobe", 5) == 0; }
 
 // Marker classes of bytes_to_marker, mod.rs:157-181.
 enum class Seg { SOI_EOI, DQT, SOF0, DHT, SOS, DRI, APP0, APP12_14, COM, OTHER_SKIPPABLE, OTHER_STANDALONE, OTHER_SOF };
@@ -234,6 +253,11 @@ void finish_parts(ParserState &st)
     d->scan_len = 0;
     d->n_parts = uint8_t(n);
     d->parts = parts;
+    if (st.color_file) {
+        uint8_t ids[4] = {0, 0, 0, 0};
+        for (size_t c = 0; c < st.frame.size() && c < 4; c++) ids[c] = st.frame[c].id;
+        d->model = decide_model(unsigned(st.frame.size()), st.jfif, st.adobe, st.adobe_transform, ids);
+    }
     d->owner_ = buf;
 }
 
@@ -258,7 +282,7 @@ size_t read_sos(const ByteView &f, size_t pos, ParserState &st, bool strict, boo
         for (unsigned q = 0; q < n; q++) sel[q] = ScanCompSel{sc[q].id, sc[q].td, sc[q].ta};
         return read_part(f, i, sel, n, st);
     }
-    if (n != 1 && n != 3) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};          // decoder.rs:328-330 panic!("asd")
+    if (n != 1 && n != 3 && !(n == 4 && st.color_file)) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};          // decoder.rs:328-330 panic!("asd")
 
     d->width = uint16_t(st.width);
     d->height = uint16_t(st.height);
@@ -267,7 +291,12 @@ size_t read_sos(const ByteView &f, size_t pos, ParserState &st, bool strict, boo
         const FrameComp *fc = nullptr;
         for (const FrameComp &cand : st.frame) if (cand.id == sc[c].id) { fc = &cand; break; }
         if (!fc) throw ParseError{MJX_ERR_REF_PANIC};   // decoder.rs:128-138 inserts 0xff factors; decode then panics
-        d->comp[c] = mjx_comp{sc[c].id, fc->h, fc->v, fc->tq, sc[c].td, sc[c].ta};
+        (c < 3 ? d->comp[c] : d->comp_fourth) = mjx_comp{sc[c].id, fc->h, fc->v, fc->tq, sc[c].td, sc[c].ta};
+    }
+    if (st.color_file) {
+        uint8_t ids[4] = {0, 0, 0, 0};
+        for (unsigned c = 0; c < n; c++) ids[c] = sc[c].id;
+        d->model = decide_model(n, st.jfif, st.adobe, st.adobe_transform, ids);
     }
 
     // everything after the SOS header, FF00 -> FF, markers (EOI...) kept verbatim -- except RSTn when a restart
@@ -332,6 +361,7 @@ void walk(const uint8_t *jpeg, size_t len, const mjx_opts &opts, mjx_scan_desc *
     const bool strict = opts.strict_ref != 0;
     ParserState st;
     st.d = out;
+    st.color_file = MJX_OPTS_COLOR(&opts) == MJX_COLOR_FILE && !strict;
     st.lent = lent;
     st.lent_cap = lent_cap;
     size_t i = 0;
@@ -373,9 +403,14 @@ void walk(const uint8_t *jpeg, size_t len, const mjx_opts &opts, mjx_scan_desc *
         case Seg::APP0:                                                            // :429-443 absolute offsets up to vec[15]
             (void)f.span(i, 6);
             if (strict && len < 16) throw ParseError{MJX_ERR_TRUNCATED};
+            if (st.color_file && body <= len - i && is_jfif(jpeg + i, body)) st.jfif = true;
             break;
         case Seg::APP12_14:
             if (strict) throw ParseError{MJX_ERR_UNSUPPORTED_MARKER};             // :445-450
+            if (st.color_file && m == 0xee && i <= len && body <= len - i && is_adobe(jpeg + i, body)) {
+                st.adobe = true;
+                st.adobe_transform = jpeg[i + 11];
+            }
             break;
         case Seg::COM: (void)f.span(i, body); break;                              // :223-228
         default: break;
@@ -405,6 +440,7 @@ int mjx::parse_into(const uint8_t *jpeg, size_t len, const mjx_opts *opts, mjx_s
     if (!out || (!jpeg && len)) return MJX_ERR_INVALID_ARG;
     mjx_opts o{};
     if (opts) o = *opts;
+    if (MJX_OPTS_COLOR(&o) > MJX_COLOR_FILE) { std::memset(out, 0, sizeof *out); return MJX_ERR_INVALID_ARG; }
     std::memset(out, 0, sizeof *out);
     try {
         walk(jpeg, len, o, out, storage, cap);
@@ -466,6 +502,43 @@ extern "C" int mjx_exif_orientation(const uint8_t *jpeg, size_t len, uint8_t *co
     }
     return MJX_OK;
 }
+
+// What the components of a file are (mjx_opts.color): a walk of its own, in the manner of mjx_exif_orientation -- every read is
+// checked against the file; the decision is decide_model's, as in mjx_parse.
+extern "C" int mjx_color_model(const uint8_t *jpeg, size_t len, mjx_color_info *out)
+{
+    if (!jpeg || !out) return MJX_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    bool jfif = false, adobe = false;
+    uint8_t transform = 0;
+    size_t i = 0;
+    while (i < len && len - i >= 2) {
+        if (jpeg[i] != 0xff) break;
+        const uint8_t m = jpeg[i + 1];
+        if (m == 0xff) { i++; continue; }                                          // fill byte
+        if (m == 0xd8 || m == 0x01 || (m >= 0xd0 && m <= 0xd7)) { i += 2; continue; }   // stand-alone markers
+        if (m == 0xd9 || m == 0xda || len - i < 4) break;                          // EOI, the first SOS, or no room for a length
+        const size_t seglen = size_t(jpeg[i + 2]) << 8 | jpeg[i + 3], body = i + 4;
+        if (seglen < 2 || seglen - 2 > len - body) break;                          // (the file ends inside the segment)
+        const size_t n = seglen - 2;
+        const uint8_t *p = jpeg + body;
+        if (m == 0xe0 && is_jfif(p, n)) jfif = true;
+        if (m == 0xee && is_adobe(p, n)) { adobe = true; transform = p[11]; }
+        if (m >= 0xc0 && m <= 0xcf && m != 0xc4 && m != 0xc8 && m != 0xcc && !out->ncomp) {      // the first frame header
+            const unsigned nc = n >= 6 ? p[5] : 0u;
+            if ((nc != 1 && nc != 3 && nc != 4) || n < 6 + 3 * size_t(nc)) break;
+            out->ncomp = uint8_t(nc);
+            for (unsigned c = 0; c < nc; c++) out->ids[c] = p[6 + 3 * c];
+        }
+        i = body + n;
+    }
+    if (!out->ncomp) { std::memset(out, 0, sizeof *out); return MJX_ERR_UNSUPPORTED_FORMAT; }
+    out->jfif = jfif; out->adobe = adobe; out->adobe_transform = adobe ? transform : 0;
+    out->model = decide_model(out->ncomp, jfif, adobe, transform, out->ids);
+    return MJX_OK;
+}
+
+extern "C" uint8_t mjx_ink_mul(uint8_t a, uint8_t k) { return uint8_t(mjx::ink_mul(a, k)); }
 
 extern "C" void mjx_free_scan(mjx_scan_desc *desc)
 {

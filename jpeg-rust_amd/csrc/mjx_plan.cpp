@@ -186,6 +186,11 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     if (opts.pixels > MJX_PIXELS_LIBJPEG) return fail(MJX_ERR_INVALID_ARG);
     const bool lj = opts.pixels == MJX_PIXELS_LIBJPEG && !scan_part;
     if (lj && (scale != 1 || opts.layout == MJX_LAYOUT_REF_COMPAT || opts.strict_ref)) return fail(MJX_ERR_INVALID_ARG);
+    // the file's own colour model: STANDARD layout without strict_ref only (the reference has one rule)
+    if (MJX_OPTS_COLOR(&opts) > MJX_COLOR_FILE) return fail(MJX_ERR_INVALID_ARG);
+    const bool color_file = MJX_OPTS_COLOR(&opts) == MJX_COLOR_FILE;
+    if (color_file && (opts.layout == MJX_LAYOUT_REF_COMPAT || opts.strict_ref)) return fail(MJX_ERR_INVALID_ARG);
+    const bool four = color_file && !scan_part && d.ncomp == 4;
     const bool gather = d.n_parts != 0;            // the picture of a multi-scan file: geometry only, no scan of its own
     if (gather) {
         if (!d.parts || d.n_parts < 2 || d.n_parts > 3 || d.ncomp != 3) return fail(MJX_ERR_UNSUPPORTED_FORMAT);
@@ -193,7 +198,17 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     } else if (!d.scan) {
         return fail(MJX_ERR_INVALID_ARG);
     }
-    if (d.ncomp != 1 && d.ncomp != 3 && !(scan_part && d.ncomp == 2)) return fail(MJX_ERR_UNSUPPORTED_FORMAT);     // decoder.rs:328-330
+    if (d.ncomp != 1 && d.ncomp != 3 && !(scan_part && d.ncomp == 2) && !(four && !gather)) return fail(MJX_ERR_UNSUPPORTED_FORMAT);     // decoder.rs:328-330
+    // what the components are: by position unless the call takes the file's word for it
+    p.model = d.ncomp == 1 ? MJX_MODEL_GREY : MJX_MODEL_YCBCR;
+    if (color_file && !scan_part && d.ncomp == 3 && d.model == MJX_MODEL_RGB) p.model = MJX_MODEL_RGB;
+    else if (color_file && !scan_part && d.ncomp == 3 && d.model > MJX_MODEL_RGB) return fail(MJX_ERR_INVALID_ARG);
+    if (four) {
+        if (d.model != MJX_MODEL_CMYK && d.model != MJX_MODEL_YCCK) return fail(MJX_ERR_INVALID_ARG);
+        p.model = d.model;
+    }
+    const bool other_model = p.model >= MJX_MODEL_RGB;
+    if (other_model && lj) return fail(MJX_ERR_UNSUPPORTED_FORMAT);        // (libjpeg's pixels of these models: not built)
     if (d.width == 0 || d.height == 0) return fail(MJX_ERR_REF_PANIC);             // x_factor division by zero
     // huffman.rs:127-128 preloads data[0..4] and panics on a shorter scan; the bug-compatible modes keep that.  Otherwise a
     // short scan (a flat 8x8 grey picture has one byte of entropy data) is decoded: past its end the lanes read the 0xAA
@@ -209,8 +224,9 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     p.scan = d.scan;
     p.scan_len = d.scan_len;
     p.stuffed = d.scan_is_stuffed != 0 && !gather;
+    auto comp_of = [&d](uint32_t c) -> const mjx_comp & { return c < 3 ? d.comp[c] : d.comp_fourth; };
     for (uint32_t c = 0; c < p.ncomp; c++) {
-        const mjx_comp &k = d.comp[c];
+        const mjx_comp &k = comp_of(c);
         if (k.h < 1 || k.h > 2 || k.v < 1 || k.v > 2) return fail(MJX_ERR_UNSUPPORTED_FORMAT);   // mod.rs:275-277
         if (k.tq > 3 || !(d.qt_present & (1u << k.tq))) return fail(MJX_ERR_MISSING_TABLE);      // decoder.rs:222-225
         if (!gather && (k.td > 3 || !(d.dc_present & (1u << k.td)))) return fail(MJX_ERR_MISSING_TABLE);      // decoder.rs:158-160
@@ -230,6 +246,11 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     for (uint32_t c = 0; c < p.ncomp; c++)
         if (p.hmax % p.h[c] || p.vmax % p.v[c]) return fail(MJX_ERR_UNSUPPORTED_FORMAT);
     p.bpm = 0;
+    if (four) {            // T.81 B.2.3: an interleaved MCU holds at most 10 blocks
+        uint32_t blocks = 0;
+        for (uint32_t c = 0; c < p.ncomp; c++) blocks += p.h[c] * p.v[c];
+        if (blocks > 10) return fail(MJX_ERR_UNSUPPORTED_FORMAT);
+    }
     for (uint32_t c = 0; c < p.ncomp; c++)
         for (uint32_t by = 0; by < p.v[c]; by++)
             for (uint32_t bx = 0; bx < p.h[c]; bx++) {
@@ -320,16 +341,16 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
             return std::memcmp(x.bits, y.bits, sizeof x.bits) == 0 && std::memcmp(x.vals, y.vals, std::min(n, sizeof x.vals)) == 0;
         };
         for (uint32_t c = 0; c < p.ncomp; c++) {
-            const mjx_comp &k = d.comp[c];
+            const mjx_comp &k = comp_of(c);
             for (uint32_t e = 0; e < c && dcb[k.td] < 0; e++)
-                if (same_table(d.dc[d.comp[e].td], d.dc[k.td])) dcb[k.td] = dcb[d.comp[e].td];
+                if (same_table(d.dc[comp_of(e).td], d.dc[k.td])) dcb[k.td] = dcb[comp_of(e).td];
             if (dcb[k.td] < 0) {
                 const int b = add_table(d.dc[k.td], true);
                 if (b < 0) return b;
                 dcb[k.td] = b;
             }
             for (uint32_t e = 0; e < c && acb[k.ta] < 0; e++)
-                if (same_table(d.ac[d.comp[e].ta], d.ac[k.ta])) acb[k.ta] = acb[d.comp[e].ta];
+                if (same_table(d.ac[comp_of(e).ta], d.ac[k.ta])) acb[k.ta] = acb[comp_of(e).ta];
             if (acb[k.ta] < 0) {
                 const int b = add_table(d.ac[k.ta], false);
                 if (b < 0) return b;
@@ -367,7 +388,7 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     // (see ImagePlan::emit_fits: a 1-bit DC code and a 2-bit entry -- a 1-bit code for an AC symbol of size 1 --, per component)
     p.emit_fits = true;
     for (uint32_t c = 0; c < p.ncomp; c++) {
-        const mjx_hufftab &dc = d.dc[d.comp[c].td], &ac = d.ac[d.comp[c].ta];
+        const mjx_hufftab &dc = d.dc[comp_of(c).td], &ac = d.ac[comp_of(c).ta];
         uint32_t dc_min = 0, entry_min = 0xffffu, v = 0;
         for (uint32_t l = 1; l <= 16 && !dc_min; l++) if (dc.bits[l - 1]) dc_min = l;
         for (uint32_t l = 1; l <= 16; l++)
@@ -377,7 +398,7 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     }
     std::memset(&p.himg, 0, sizeof p.himg);
     for (uint32_t b = 0; b < p.bpm; b++) {
-        const mjx_comp &k = d.comp[p.blk_comp[b]];
+        const mjx_comp &k = comp_of(p.blk_comp[b]);
         p.himg.btab[b].tabs = uint32_t(dc_base[k.td]) * uint32_t(sizeof(LutEntry)) | (uint32_t(ac_base[k.ta]) * uint32_t(sizeof(LutEntry)) << 16);
         p.himg.btab[b].next = b + 1 == p.bpm ? 0 : b + 1;
         p.himg.tabs_pair[b] = uint32_t(dc_base2[k.td]) * uint32_t(sizeof(LutEntry)) | (uint32_t(ac_base2[k.ta]) * uint32_t(sizeof(LutEntry)) << 16);
@@ -457,7 +478,7 @@ StageBChoice stage_b_choice(const ImagePlan &p)
     const bool luma = p.out_on && p.out_channels == 1;
     // The form, first match: libjpeg's pixels have the generic form alone, whatever else the plan says; REF_COMPAT placement; a
     // scale; Y 2x2 + Cb 1x1 + Cr 1x1 on the 4:2:0 kernel, unless the picture leaves as component planes (no 4:2:0 plane form).
-    const bool s420 = p.ncomp == 3 && p.h[0] == 2 && p.v[0] == 2 && p.h[1] == 1 && p.v[1] == 1 && p.h[2] == 1 && p.v[2] == 1;
+    const bool s420 = p.ncomp == 3 && p.model < MJX_MODEL_RGB && p.h[0] == 2 && p.v[0] == 2 && p.h[1] == 1 && p.v[1] == 1 && p.h[2] == 1 && p.v[2] == 1;
     const StageBForm form = p.lj ? kFormGeneric
                           : p.layout == MJX_LAYOUT_REF_COMPAT ? kFormRefCompat
                           : p.scale > 1 ? (p.scale == 2 ? kFormHalf : p.scale == 4 ? kFormQuarter : kFormEighth)
@@ -520,6 +541,7 @@ int plan_output(ImagePlan &p, const mjx_output *out, size_t i)
     const uint8_t channels = reinterpret_cast<const uint8_t *>(out)[MJX_OUTPUT_CHANNELS_OFFSET];       // (the byte behind bgr, mjx.h)
     if (channels != 0 && channels != 1 && channels != 3) return fail();
     const bool luma = channels == 1;                                  // luminance: H x W elements, one plane whatever `planar` says
+    if (luma && p.model >= MJX_MODEL_RGB) { p.status = MJX_ERR_UNSUPPORTED_FORMAT; return p.status; }      // (component 0 of such a file is no luminance: not built)
     const uint64_t esz = out->dtype == MJX_DTYPE_U8 ? 1u : out->dtype == MJX_DTYPE_F16 ? 2u : 4u;
     const bool planar = out->planar != 0 && !luma;
     for (int c = 0; c < (luma ? 1 : 3); c++) {
@@ -578,6 +600,7 @@ int plan_planes(ImagePlan &p, const mjx_planes *pl, size_t i)
     if (!pl || p.status != MJX_OK) return p.status;
     auto fail = [&]() { p.status = MJX_ERR_INVALID_ARG; return p.status; };
     if (pl->dtype > MJX_DTYPE_F32 || p.layout == MJX_LAYOUT_REF_COMPAT) return fail();
+    if (p.model >= MJX_MODEL_RGB) { p.status = MJX_ERR_UNSUPPORTED_FORMAT; return p.status; }      // (the planes of an RGB, CMYK or YCCK file: not built)
     const uint32_t nc = p.ncomp;
     const bool il = pl->interleave_chroma != 0 && nc == 3;            // (a one-component file has one plane: the flag has no meaning)
     if (il && (p.h[1] != p.h[2] || p.v[1] != p.v[2])) return fail();

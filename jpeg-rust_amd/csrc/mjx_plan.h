@@ -15,8 +15,11 @@ struct ImagePlan {
     int status = MJX_OK;
     uint32_t width = 0, height = 0;
     uint32_t ncomp = 0;
-    uint32_t h[3] = {1, 1, 1}, v[3] = {1, 1, 1};   // effective sampling factors (scan order)
-    uint32_t tq[3] = {0, 0, 0};
+    uint32_t h[4] = {1, 1, 1, 1}, v[4] = {1, 1, 1, 1};   // effective sampling factors (scan order)
+    uint32_t tq[4] = {0, 0, 0, 0};
+    // colour model (mjx_opts.color): MJX_MODEL_* -- grey for one component and YCbCr for three unless the call asks for the file's own
+    // model (MJX_COLOR_FILE) and the description carries RGB, CMYK or YCCK.  A fourth component exists for the last two only.
+    uint32_t model = MJX_MODEL_GREY;
     uint32_t hmax = 1, vmax = 1;
     uint32_t bpm = 0;                              // blocks per MCU
     uint32_t mcux = 0, mcuy = 0;                   // MCU grid of the standard layout
@@ -36,11 +39,11 @@ struct ImagePlan {
     // or entry a block of j entries takes 2 j + 2 bits at least.  false: the tables are of that kind; the picture takes the
     // two-pass kernels, in this batch and in every batch tiled from it.
     bool emit_fits = true;
-    float qmult[3][64];                            // per component, zig-zag order: q[k] * idct prescale
+    float qmult[4][64];                            // per component, zig-zag order: q[k] * idct prescale
     // scaled decode (mjx_opts.scale_denom): 1, 2, 4 or 8, the output size ceil(width / scale) x ceil(height / scale), and the
     // multipliers of the reduced transforms (zig-zag order: q[k] * C(u) C(v) / 4 inside the low N x N corner, 0 outside)
     uint32_t scale = 1, out_w = 0, out_h = 0;
-    float qmult_scaled[3][64];
+    float qmult_scaled[4][64];
     // region-of-interest decode (mjx_opts.rois): the rectangle in the coordinates of the out_w x out_h picture -- the whole of it
     // without one -- and the MCU rows and columns that touch it.  The picture written is roi_w x roi_h.  A multi-scan file's
     // rectangle belongs to its role-2 plan, not to its scans.
