@@ -45,7 +45,14 @@ enum {
                                      * picture needs, the next 16 bits begin with no code of the block's table (or the DC symbol
                                      * is above 15).  The decode goes on -- such a pattern takes one bit and stands for a symbol of
                                      * run 0, size 0 -- but the picture's coefficients and pixels are not handed out.  Patterns
-                                     * behind the last block needed do not count.  MJX_ERR_TRUNCATED wins where both hold. */
+                                     * behind the last block needed do not count.  MJX_ERR_TRUNCATED wins where both hold.
+                                     * Also the status of a picture whose decode tables do not fit: the tables of a scan's distinct
+                                     * DC and AC slots -- 2 KiB per DC table, 4 KiB per AC table, and their second-level tables -- are
+                                     * addressed with 15 bits, so a set above 32 767 bytes is refused by the planner, the other
+                                     * pictures of the call unaffected.  Three pairs of any shape fit (largest seen 23 696 bytes), and
+                                     * so do four Annex K-style or optimised pairs (under 28 KiB; the largest set of the test shapes
+                                     * is 31 584 bytes); four pairs that each spread codes of 10 to 16 bits over every prefix they
+                                     * can (34 880 bytes) do not, valid though the file is. */
     MJX_ERR_REF_PANIC = 5,          /* other input on which the reference panics (asserts, bad DQT precision ...) */
     MJX_ERR_DEVICE = 6,             /* HIP error / no device / kernels missing */
     MJX_ERR_UNSUPPORTED_FORMAT = 7, /* non-baseline SOF, ncomp not in {1,3} (decoder.rs:328-330; {1,3,4} with MJX_COLOR_FILE), sampling > 2 */

@@ -53,22 +53,74 @@ class ColorFile:
         self.__dict__.update(kw)
 
 
-def color_jpeg(width, height, hv, ids=None, head=(), quality=75, seed=0, restart=None, noise=4.0, k_swing=0.0):
+def _slots(nc, tq, huff):
+    """the DQT slot and the (DC slot, AC slot) pair of each component; default: Adobe's 0, 1, 1, 0 for all three"""
+    slot = [0, 1, 1, 0][:nc]
+    tq = list(slot) if tq is None else [int(t) for t in tq]
+    huff = [(s, s) for s in slot] if huff is None else [(int(d), int(a)) for d, a in huff]
+    assert len(tq) == nc and len(huff) == nc and all(0 <= t < 4 for t in tq) and all(0 <= d < 4 and 0 <= a < 4 for d, a in huff)
+    return slot, tq, huff
+
+
+def color_from_blocks(blocks_per_component, hv, mcux, mcuy, qts, tq, tables, huff, head=(), width=None, height=None, restart=None, ids=None):
+    """jpegwriter.jpeg_from_blocks for three or four components with tables of the caller's choosing: a baseline file in one interleaved
+    scan whose blocks carry exactly the coefficients given.  blocks_per_component[c]: int [mcux mcuy h v, 64] in decode order (MCU-major,
+    v x h inside the MCU), zig-zag, absolute DC, before dequantisation.  qts: {slot: 64 zig-zag entries}, up to four; a table with an
+    entry above 255 is written with 16-bit entries, the others with 8-bit ones.  tq[c]: component c's DQT slot.  tables: {(class, slot):
+    (bits, vals)}, up to four pairs; huff[c] = (DC slot, AC slot).  head: segments behind SOI; width, height: the frame's (default the
+    whole MCU grid; smaller values clip the last MCUs); restart=n: DRI n, RSTn every n MCUs.  -> ColorFile"""
+    hv = [tuple(x) for x in hv]
+    nc = len(hv)
+    assert nc in (3, 4) and len(blocks_per_component) == nc
+    slot, tq, huff = _slots(nc, tq, huff)
+    hmax, vmax = max(h for h, _ in hv), max(v for _, v in hv)
+    width = mcux * 8 * hmax if width is None else width
+    height = mcuy * 8 * vmax if height is None else height
+    assert -(-width // (8 * hmax)) == mcux and -(-height // (8 * vmax)) == mcuy, (width, height, mcux, mcuy)
+    per_mcu = [h * v for h, v in hv]
+    bpm = sum(per_mcu)
+    blocks = [np.asarray(b, np.int64) for b in blocks_per_component]
+    assert all(b.shape == (mcux * mcuy * k, 64) for b, k in zip(blocks, per_mcu)), [b.shape for b in blocks]
+    qts = {int(s): [int(v) for v in q] for s, q in qts.items()}
+    assert len(qts) <= 4 and all(t in qts for t in tq) and all(1 <= v <= 65535 for q in qts.values() for v in q)
+    dhts = {(int(cls), int(s)): (list(t[0]), list(t[1])) for (cls, s), t in tables.items()}
+    assert all((0, d) in dhts and (1, a) in dhts for d, a in huff)
+    order = np.concatenate([b.reshape(mcux * mcuy, k, 64) for b, k in zip(blocks, per_mcu)], axis=1).reshape(-1, 64)
+    owner = [c for c, k in enumerate(per_mcu) for _ in range(k)] * (mcux * mcuy)
+    dc = {c: jw.huff_codes(*dhts[(0, huff[c][0])]) for c in range(nc)}
+    ac = {c: jw.huff_codes(*dhts[(1, huff[c][1])]) for c in range(nc)}
+    ent = jw.encode_scan_np(order, owner, dc, ac, restart_blocks=(restart or 0) * bpm)
+    ids = list(ids) if ids is not None else list(range(1, nc + 1))
+    comps = [(ids[c], h, v, tq[c], huff[c][0], huff[c][1]) for c, (h, v) in enumerate(hv)]
+    wide = {s for s, q in qts.items() if max(q) > 255}
+    data = with_head(jw.write_jpeg(width, height, comps, qts, dhts, ent, qt16=wide, restart_interval=restart or 0), *head)
+    plain = tq == slot and huff == [(s, s) for s in slot]
+    return ColorFile(data=data, hv=hv, blocks=blocks, qts=[qts[t] for t in tq], tables=dhts, slot=slot if plain else list(huff), tq=tq,
+                     huff=huff, qt_slots=qts, width=width, height=height, mcux=mcux, mcuy=mcuy, hmax=hmax, vmax=vmax, bpm=bpm, order=order,
+                     owner=owner, codes=(dc, ac), entropy=ent, restart=restart or 0, head=tuple(head))
+
+
+def color_jpeg(width, height, hv, ids=None, head=(), quality=75, seed=0, restart=None, noise=4.0, k_swing=0.0, tq=None, huff=None,
+               qts=None, tables=None):
     """A baseline file of len(hv) in (3, 4) components in one interleaved scan, written from float64 DCT coefficients: smooth plane
-    waves plus gaussian noise per component at its own resolution over the whole MCU grid.  Components 0 and 3 code with the
+    waves plus gaussian noise per component at its own resolution over the whole MCU grid.  By default components 0 and 3 code with the
     luminance tables and DQT (slot 0), 1 and 2 with the chrominance ones (slot 1), as Adobe's writer does.  ids: the component ids
     (default 1, 2, ...); head: segments to put behind SOI (app0(), app14(t)).  k_swing: the last component gets a checkerboard of
-    +- k_swing per 8 x 8 block on top, so that its DC differences are large and of both signs.  restart=n: DRI n, RSTn every n MCUs."""
+    +- k_swing per 8 x 8 block on top, so that its DC differences are large and of both signs.  restart=n: DRI n, RSTn every n MCUs.
+    tq: a DQT slot per component; huff: a (DC slot, AC slot) pair per component; qts: {slot: table}, up to four, 8-bit or 16-bit
+    (default: the Annex K tables at `quality` on slots 0 and 1); tables: {(class, slot): (bits, vals)}, up to four pairs (default: the
+    Annex K tables on slots 0 and 1)."""
     rng = np.random.default_rng(seed)
     hv = [tuple(x) for x in hv]
     nc = len(hv)
     assert nc in (3, 4)
     hmax, vmax = max(h for h, _ in hv), max(v for _, v in hv)
     mcux, mcuy = -(-width // (8 * hmax)), -(-height // (8 * vmax))
-    slot = [0, 1, 1, 0][:nc]
-    qt = {0: jw.quality_table(jw.ANNEX_K_LUMA, quality), 1: jw.quality_table(jw.ANNEX_K_CHROMA, quality)}
-    ak = jw._annex_k_tables()
-    dhts = {(cls, s): ak[(cls, s)] for s in (0, 1) for cls in (0, 1)}
+    _, tq, huff = _slots(nc, tq, huff)
+    qt = {0: jw.quality_table(jw.ANNEX_K_LUMA, quality), 1: jw.quality_table(jw.ANNEX_K_CHROMA, quality)} if qts is None else dict(qts)
+    if tables is None:
+        ak = jw._annex_k_tables()
+        tables = {(cls, s): ak[(cls, s)] for s in (0, 1) for cls in (0, 1)}
     blocks = []
     for c, (h, v) in enumerate(hv):
         ph, pw = mcuy * v * 8, mcux * h * 8
@@ -81,20 +133,9 @@ def color_jpeg(width, height, hv, ids=None, head=(), quality=75, seed=0, restart
         if k_swing and c == nc - 1:
             p += k_swing * (1.0 - 2.0 * (((yy // 8) + (xx // 8)) % 2))
         p = np.clip(p, -128.0, 127.0)
-        b = jw.fdct_quantise(p, qt[slot[c]])
+        b = jw.fdct_quantise(p, qt[tq[c]])
         blocks.append(b.reshape(mcuy, v, mcux, h, 64).transpose(0, 2, 1, 3, 4).reshape(-1, 64))
-    per_mcu = [h * v for h, v in hv]
-    bpm = sum(per_mcu)
-    order = np.concatenate([b.reshape(mcux * mcuy, k, 64) for b, k in zip(blocks, per_mcu)], axis=1).reshape(-1, 64)
-    owner = [c for c, k in enumerate(per_mcu) for _ in range(k)] * (mcux * mcuy)
-    dc = {c: jw.huff_codes(*dhts[(0, slot[c])]) for c in range(nc)}
-    ac = {c: jw.huff_codes(*dhts[(1, slot[c])]) for c in range(nc)}
-    ent = jw.encode_scan_np(order, owner, dc, ac, restart_blocks=(restart or 0) * bpm)
-    ids = list(ids) if ids is not None else list(range(1, nc + 1))
-    comps = [(ids[c], h, v, slot[c], slot[c], slot[c]) for c, (h, v) in enumerate(hv)]
-    data = with_head(jw.write_jpeg(width, height, comps, qt, dhts, ent, restart_interval=restart or 0), *head)
-    return ColorFile(data=data, hv=hv, blocks=blocks, qts=[qt[s] for s in slot], tables=dhts, slot=slot, width=width, height=height,
-                     mcux=mcux, mcuy=mcuy, hmax=hmax, vmax=vmax, bpm=bpm, order=order, owner=owner, codes=(dc, ac), entropy=ent)
+    return color_from_blocks(blocks, hv, mcux, mcuy, qt, tq, tables, huff, head, width, height, restart, ids)
 
 
 def cut_in_last_mcu(cf, keep=2):
@@ -114,7 +155,7 @@ def component_twin(cf, c):
     raster = cf.blocks[c].reshape(cf.mcuy, cf.mcux, v, h, 64).transpose(0, 2, 1, 3, 4).reshape(-1, 64)
     td, ta = cf.slot[c] if isinstance(cf.slot[c], tuple) else (cf.slot[c], cf.slot[c])
     tables = {(0, 0): cf.tables[(0, td)], (1, 0): cf.tables[(1, ta)]}
-    return jw.jpeg_from_blocks(raster, [(1, 1)], cf.mcux * h, cf.mcuy * v, [cf.qts[c]], tables)
+    return jw.jpeg_from_blocks(raster, [(1, 1)], cf.mcux * h, cf.mcuy * v, [cf.qts[c]], tables, qt16=max(cf.qts[c]) > 255)
 
 
 def ycc_twin(cf):
@@ -122,6 +163,11 @@ def ycc_twin(cf):
     its packed decode is the (r, g, b) a YCCK picture multiplies by K."""
     hv = cf.hv[:3]
     assert max(h for h, _ in hv) == cf.hmax and max(v for _, v in hv) == cf.vmax
+    if isinstance(cf.slot[0], tuple) and getattr(cf, "qt_slots", None) is not None:
+        # (tables of the file's own choosing: each component keeps its DQT slot and its pair of Huffman slots)
+        return color_from_blocks(cf.blocks[:3], hv, cf.mcux, cf.mcuy, {t: cf.qt_slots[t] for t in set(cf.tq[:3])}, cf.tq[:3],
+                                 {(cls, s): cf.tables[(cls, s)] for d, a in cf.huff[:3] for cls, s in ((0, d), (1, a))}, cf.huff[:3],
+                                 width=cf.width, height=cf.height).data
     per_mcu = [h * v for h, v in hv]
     n = cf.mcux * cf.mcuy
     order = np.concatenate([cf.blocks[c].reshape(n, per_mcu[c], 64) for c in range(3)], axis=1).reshape(-1, 64)

@@ -111,11 +111,13 @@ extern "C" int emul_decode_coefs(const uint8_t *jpeg, size_t len, int layout, in
 {
     return emul_decode_coefs_sub(jpeg, len, layout, mode, 0, out, cap_blocks, nblocks, stats);
 }
-extern "C" int emul_decode_coefs_sub(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, int16_t *out,
-                                     size_t cap_blocks, size_t *nblocks, int *stats /* [8] */)
+// (..._color: the same with mjx_opts.color = `color` (MJX_COLOR_*): MJX_COLOR_FILE admits four-component files)
+extern "C" int emul_decode_coefs_sub_color(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, int16_t *out,
+                                           size_t cap_blocks, size_t *nblocks, int *stats /* [8] */, int color)
 {
     mjx_opts opts{};
     opts.layout = uint8_t(layout);
+    MJX_OPTS_COLOR(&opts) = uint8_t(color);
     mjx_scan_desc d;
     int rc = mjx_parse(jpeg, len, &opts, &d);
     if (rc) return rc;
@@ -347,7 +349,7 @@ extern "C" int emul_decode_coefs_sub(const uint8_t *jpeg, size_t len, int layout
             }
             if (!bad && (std::memcmp(out2.data(), out, nb * 64 * sizeof(int16_t)) != 0 || dcb2 != dcb)) bad = 10;
         }
-        int32_t pred[3] = {0, 0, 0};
+        int32_t pred[4] = {0, 0, 0, 0};            // (a fourth component with MJX_COLOR_FILE)
         for (size_t b = 0; b < nb; b++) {
             const int c = plan.blk_comp[b % plan.bpm];
             pred[c] += dcb[b];
@@ -361,6 +363,11 @@ extern "C" int emul_decode_coefs_sub(const uint8_t *jpeg, size_t len, int layout
     mjx_free_scan(&d);
     if (nb > cap_blocks) return MJX_ERR_NOMEM;
     return truncated ? MJX_ERR_TRUNCATED : bad ? MJX_ERR_BAD_HUFFMAN : MJX_OK;      // (as mjx_batch_wait: truncated wins)
+}
+extern "C" int emul_decode_coefs_sub(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, int16_t *out,
+                                     size_t cap_blocks, size_t *nblocks, int *stats /* [8] */)
+{
+    return emul_decode_coefs_sub_color(jpeg, len, layout, mode, sub_base_bits, out, cap_blocks, nblocks, stats, MJX_COLOR_POSITIONAL);
 }
 
 // ---- single decode (round 5): the counting pass emits ------------------------------------------------------------------
@@ -437,12 +444,14 @@ extern "C" int emul_single_decode_cp(const uint8_t *jpeg, size_t len, int layout
 //   lane's entry was right, everything it decoded stays; 0xffffffff: nothing stays)   [2] position of a later one the sink keeps   [3] how many
 // and behind the last subsequence's a row {bits per subsequence, subsequences, bits between checkpoints, warm-up bits}.
 // A lane with [0] < [1] has spent "the first one" on a code that does not count: what k_huff_prefix decides on is the last one.
-extern "C" int emul_single_decode_lanes(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, unsigned warm_bits,
-                                        unsigned headroom_groups, unsigned cp_bits, int16_t *out, size_t cap_blocks, size_t *nblocks, int *stats /* [8] */,
-                                        uint32_t *lanes, size_t lanes_cap)
+// (..._color: the same with mjx_opts.color = `color`, as emul_decode_coefs_sub_color)
+extern "C" int emul_single_decode_lanes_color(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, unsigned warm_bits,
+                                              unsigned headroom_groups, unsigned cp_bits, int16_t *out, size_t cap_blocks, size_t *nblocks, int *stats /* [8] */,
+                                              uint32_t *lanes, size_t lanes_cap, int color)
 {
     mjx_opts opts{};
     opts.layout = uint8_t(layout);
+    MJX_OPTS_COLOR(&opts) = uint8_t(color);
     mjx_scan_desc d;
     int rc = mjx_parse(jpeg, len, &opts, &d);
     if (rc) return rc;
@@ -662,7 +671,7 @@ extern "C" int emul_single_decode_lanes(const uint8_t *jpeg, size_t len, int lay
                 }
             }
         }
-        int32_t pred[3] = {0, 0, 0};
+        int32_t pred[4] = {0, 0, 0, 0};            // (a fourth component with MJX_COLOR_FILE)
         for (size_t b = 0; b < nb; b++) {
             const int c = plan.blk_comp[b % plan.bpm];
             pred[c] += dcb[b];
@@ -676,6 +685,20 @@ extern "C" int emul_single_decode_lanes(const uint8_t *jpeg, size_t len, int lay
     mjx_free_scan(&d);
     if (nb > cap_blocks) return MJX_ERR_NOMEM;
     return truncated ? MJX_ERR_TRUNCATED : (bad || huff_bad) ? MJX_ERR_BAD_HUFFMAN : MJX_OK;      // (as mjx_batch_wait: truncated wins)
+}
+extern "C" int emul_single_decode_lanes(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, unsigned warm_bits,
+                                        unsigned headroom_groups, unsigned cp_bits, int16_t *out, size_t cap_blocks, size_t *nblocks, int *stats /* [8] */,
+                                        uint32_t *lanes, size_t lanes_cap)
+{
+    return emul_single_decode_lanes_color(jpeg, len, layout, mode, sub_base_bits, warm_bits, headroom_groups, cp_bits, out, cap_blocks, nblocks, stats,
+                                          lanes, lanes_cap, MJX_COLOR_POSITIONAL);
+}
+extern "C" int emul_single_decode_cp_color(const uint8_t *jpeg, size_t len, int layout, int mode, unsigned sub_base_bits, unsigned warm_bits,
+                                           unsigned headroom_groups, unsigned cp_bits, int16_t *out, size_t cap_blocks, size_t *nblocks, int *stats /* [8] */,
+                                           int color)
+{
+    return emul_single_decode_lanes_color(jpeg, len, layout, mode, sub_base_bits, warm_bits, headroom_groups, cp_bits, out, cap_blocks, nblocks, stats,
+                                          nullptr, 0, color);
 }
 
 // ---- round 5: multi-scan pictures read without the gather, and what the planner decides per scan ------------------------------------
@@ -696,9 +719,10 @@ extern "C" int emul_planar_cuts(unsigned scan_mcux, unsigned scan_mcuy, unsigned
     return n;
 }
 // plan_input on a file: per plan {role, part_idx, ncomp, bpm, himg.bpm (the decoder's block-in-MCU period), sub_bits, nsub, status}
-extern "C" int emul_plan_parts(const uint8_t *jpeg, size_t len, int *out /* [cap][8] */, int cap)
+extern "C" int emul_plan_parts_color(const uint8_t *jpeg, size_t len, int *out /* [cap][8] */, int cap, int color)
 {
     mjx_opts opts{};
+    MJX_OPTS_COLOR(&opts) = uint8_t(color);
     mjx_scan_desc d;
     const int rc = mjx_parse(jpeg, len, &opts, &d);
     if (rc) return -rc;
@@ -715,6 +739,10 @@ extern "C" int emul_plan_parts(const uint8_t *jpeg, size_t len, int *out /* [cap
     }
     mjx_free_scan(&d);
     return n;
+}
+extern "C" int emul_plan_parts(const uint8_t *jpeg, size_t len, int *out /* [cap][8] */, int cap)
+{
+    return emul_plan_parts_color(jpeg, len, out, cap, MJX_COLOR_POSITIONAL);
 }
 // stage_b_choice on n plans that hold nothing but its inputs: rows of {lj, ycc_on, out_on, rs_on, out_channels, cropped, scale, layout,
 // sampling is 4:2:0, role, orient, or_copy} -> rows of {mode, rs_on, or_on, out_ch, lj_on, lj_luma, lj_out, tile_420}
@@ -749,9 +777,11 @@ extern "C" int emul_build_table(const uint8_t *bits, const uint8_t *vals, int is
 }
 // plan_image on a file: out = {entries of the plain table set, entries of the set with pair parts, blocks per MCU, BlockTab::tabs per
 // block of the MCU [12], ImagePlan::emit_fits}; returns the plan's status
-extern "C" int emul_table_set(const uint8_t *jpeg, size_t len, uint32_t *out /* [16] */)
+// (with mjx_opts.color = `color`; the status of a file the parser or the planner refuses comes back as it is)
+extern "C" int emul_table_set_color(const uint8_t *jpeg, size_t len, uint32_t *out /* [16] */, int color)
 {
     mjx_opts opts{};
+    MJX_OPTS_COLOR(&opts) = uint8_t(color);
     mjx_scan_desc d;
     int rc = mjx_parse(jpeg, len, &opts, &d);
     if (rc) return rc;
@@ -766,6 +796,10 @@ extern "C" int emul_table_set(const uint8_t *jpeg, size_t len, uint32_t *out /* 
     }
     mjx_free_scan(&d);
     return rc;
+}
+extern "C" int emul_table_set(const uint8_t *jpeg, size_t len, uint32_t *out /* [16] */)
+{
+    return emul_table_set_color(jpeg, len, out, MJX_COLOR_POSITIONAL);
 }
 
 // ---- device-side de-stuffing and marker scan (tests/test_destuff_boundaries.py) ------------------------------------------------------

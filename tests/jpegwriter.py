@@ -112,10 +112,11 @@ def encode_blocks(blocks, comp_of_block, dc_codes, ac_codes):
 def write_jpeg(width, height, comps, qts, dhts, entropy, qt16=False, restart_interval=0):
     """comps: [(id, h, v, tq, td, ta)] in frame = scan order; qts: {slot: 64 values in zig-zag (file) order};
     dhts: {(class, slot): (bits, vals)}; entropy: the stuffed entropy-coded segment (with its RSTn markers);
-    restart_interval: > 0 writes a DRI segment in front of the scan."""
+    qt16: every table with 16-bit entries, or the set of slots whose tables have them; restart_interval: > 0 writes a DRI segment in
+    front of the scan."""
     out = bytearray(b"\xff\xd8")
     for slot, q in sorted(qts.items()):
-        if qt16:
+        if (slot in qt16) if isinstance(qt16, (set, frozenset)) else qt16:
             out += b"\xff\xdb" + struct.pack(">H", 2 + 129) + bytes([0x10 | slot]) + b"".join(struct.pack(">H", int(v)) for v in q)
         else:
             out += b"\xff\xdb" + struct.pack(">H", 2 + 65) + bytes([slot]) + bytes(int(v) for v in q)

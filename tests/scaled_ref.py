@@ -160,6 +160,113 @@ def rgb_interval(data, scale, K, dec=None):
     return lo, hi
 
 
+# ---- RGB, CMYK and YCCK files (mjx.h: MJX_OPTS_COLOR) ------------------------------------------------------------------------------
+def _color_file(cf_or_data):
+    """a colorwriter.ColorFile as it is; a file's bytes (one interleaved baseline scan without restart intervals) read back into one"""
+    if isinstance(cf_or_data, (bytes, bytearray)):
+        import colorwriter
+        return colorwriter.read_baseline(bytes(cf_or_data))
+    return cf_or_data
+
+
+def component_samples(cf, c, scale, qt=None):
+    """-> (sample, magnitude) of component c under every output pixel of the picture at 1/scale, float64 [ceil(H/s), ceil(W/s)]: the
+    sample without a level shift (planes()'s transform on the blocks written, box replication), and S_c = sum |coef q| / 8 over the
+    corner of the sample's block.  qt: the table to dequantise with (default the component's own)."""
+    n = 8 // scale
+    M = _basis(n)
+    hc, vc = cf.hv[c]
+    deq = np.asarray(cf.blocks[c], np.float64) * np.asarray(cf.qts[c] if qt is None else qt, np.float64)[None, :]
+    nat = np.zeros_like(deq)
+    nat[:, ZIGZAG] = deq
+    F = nat.reshape(-1, 8, 8)[:, :n, :n]
+    S = 0.25 * np.einsum("yv,bvu,xu->byx", M, F, M)
+    A = np.broadcast_to((np.abs(F).sum(axis=(1, 2)) / 8.0)[:, None, None], S.shape)
+    ow, oh = -(-cf.width // scale), -(-cf.height // scale)
+    ys, xs = (np.arange(oh) * vc // cf.vmax)[:, None], (np.arange(ow) * hc // cf.hmax)[None, :]
+    grid = lambda p: p.reshape(cf.mcuy, cf.mcux, vc, hc, n, n).transpose(0, 2, 4, 1, 3, 5).reshape(cf.mcuy * vc * n, cf.mcux * hc * n)[ys, xs]
+    return grid(S), grid(A)
+
+
+def byte_interval(sample, mag, K):
+    """-> (lo, hi) uint8 of a component that leaves as a byte of its own: the sample + 128 moved by K half-ulps of its magnitude
+    S_c + 128 and truncated, as rgb_interval does for grey; a block with nothing inside the corner is exactly 128."""
+    w, m = sample + 128.0, mag + 128.0
+    d = K * 2.0 ** -24 * m
+    lo, hi = trunc_u8(w - d), trunc_u8(w + d)
+    lo[mag == 0.0], hi[mag == 0.0] = 128, 128
+    return lo, hi
+
+
+def ink_mul(a, k):
+    """(a k + 127) // 255 on uint8 arrays (mjx.h: mjx_ink_mul)"""
+    return ((a.astype(np.uint32) * k.astype(np.uint32) + 127) // 255).astype(np.uint8)
+
+
+def ycc_part(cf):
+    """(the three-component file of components 0 .. 2, a stand-in for its decode) -- what rgb_f64 and rgb_interval take"""
+    import types
+    import colorwriter
+    return colorwriter.ycc_twin(cf), types.SimpleNamespace(coefs=[np.asarray(b) for b in cf.blocks[:3]], mcus=cf.mcux * cf.mcuy)
+
+
+def model_interval(cf_or_data, model, scale, K):
+    """-> (lo, hi), uint8 [ceil(H/s), ceil(W/s), 3]: the bytes a float32 decoder of an "rgb", "cmyk" or "ycck" file may produce at
+    1/scale.  Per component the float64 sample under every output pixel, + 128 on every component that leaves as a byte of its own,
+    moved by K half-ulps of S_c + 128 and truncated (byte_interval).  RGB: the three intervals.  CMYK: [mul(lo_c, lo_K), mul(hi_c,
+    hi_K)] -- ink_mul is non-decreasing in both arguments.  YCCK: rgb_interval of the three-component part, complemented (the ends
+    swap), then the same product with K's interval."""
+    cf = _color_file(cf_or_data)
+    assert model in ("rgb", "cmyk", "ycck") and len(cf.hv) == (3 if model == "rgb" else 4)
+    if model == "ycck":
+        data3, dec3 = ycc_part(cf)
+        rlo, rhi = rgb_interval(data3, scale, K, dec3)
+        lo3, hi3 = 255 - rhi, 255 - rlo
+    else:
+        iv = [byte_interval(*component_samples(cf, c, scale), K) for c in range(3)]
+        lo3, hi3 = np.stack([a for a, _ in iv], axis=2), np.stack([b for _, b in iv], axis=2)
+    if model == "rgb":
+        return lo3, hi3
+    klo, khi = byte_interval(*component_samples(cf, 3, scale), K)
+    return ink_mul(lo3, klo[:, :, None]), ink_mul(hi3, khi[:, :, None])
+
+
+def model_bytes(cf_or_data, model, scale, plant=None):
+    """-> the float64 picture of the file at 1/scale, uint8 [ceil(H/s), ceil(W/s), 3] (model_interval with K = 0, but for the samples
+    that are exactly whole).  plant: one error on purpose, for the tests that show the inputs tell it from the truth --
+      "k_table0"        K dequantised with component 0's table          "k_table0_scaled"  the same at scales 2, 4, 8 only
+      "mul_no_127"      mul(a, k) = a k / 255 without the + 127          "ycck_no_complement"  R = mul(r, K) instead of mul(255 - r, K)
+      "k_no_128"        K without its + 128                              "swap_1_3"  components 1 and 3 take each other's place"""
+    cf = _color_file(cf_or_data)
+    assert plant in (None, "k_table0", "k_table0_scaled", "mul_no_127", "ycck_no_complement", "k_no_128", "swap_1_3")
+    order = [0, 3, 2, 1] if plant == "swap_1_3" else [0, 1, 2, 3]
+
+    def byte_of(c, shift=128.0, qt=None):
+        """component c's byte where the picture has component `order[c]`'s place: its own sampling, its own table"""
+        return to_u8(component_samples(cf, c, scale, qt)[0] + shift)
+    if model == "ycck":
+        assert plant != "swap_1_3" or cf.hv[1] == cf.hv[3]
+        data3, dec3 = ycc_part(cf)
+        if plant == "swap_1_3":                     # (K's blocks in Cb's place and the other way round: the same sampling)
+            import types
+            swapped = types.SimpleNamespace(**cf.__dict__)
+            swapped.blocks = [cf.blocks[k] for k in order]
+            swapped.qts = [cf.qts[k] for k in order]
+            return model_bytes(swapped, model, scale)
+        three = to_u8(rgb_f64(data3, scale, dec3))
+        if plant != "ycck_no_complement":
+            three = 255 - three
+    else:
+        three = np.stack([byte_of(order[c]) for c in range(3)], axis=2)
+    if model == "rgb":
+        return three
+    kq = cf.qts[0] if plant == "k_table0" or (plant == "k_table0_scaled" and scale > 1) else None
+    k = byte_of(order[3], 0.0 if plant == "k_no_128" else 128.0, kq)[:, :, None]
+    if plant == "mul_no_127":
+        return ((three.astype(np.uint32) * k.astype(np.uint32)) // 255).astype(np.uint8)
+    return ink_mul(three, k)
+
+
 def box_mean(rgb, s):
     """s x s box mean of a full-size picture (edge boxes: what they cover) -> float64 [ceil(H/s), ceil(W/s), 3]"""
     h, w, _ = rgb.shape

@@ -77,15 +77,18 @@ def _cc(nat):
 
 
 def _limits(ncomp):
-    """peak excursion allowed per component so that R, G and B stay inside 0..255 around mid-grey"""
-    return [120.0] if ncomp == 1 else [60.0, 30.0 / 1.772, 30.0 / 1.402]
+    """peak excursion allowed per component so that R, G and B stay inside 0..255 around mid-grey (a fourth component, K, is a byte
+    of its own: half the range of a single one, so that two excursions in one block still fit)"""
+    return [120.0] if ncomp == 1 else [60.0, 30.0 / 1.772, 30.0 / 1.402, 60.0][:ncomp]
 
 
 def _tables_q(Q, ncomp):
-    """Q everywhere on luminance; chroma: Q on every other position and a neighbour of Q on the rest, the other way round on Cr"""
+    """Q everywhere on luminance; chroma: Q on every other position and a neighbour of Q on the rest, the other way round on Cr; a
+    fourth component: a factor of two or more away from Q at every position (3 for Q = 1, else Q // 2 -- odd for the Q in use,
+    1, 255 and 65535)"""
     alt = 2 if Q == 1 else Q - 1
     k = np.arange(64)
-    return [np.full(64, Q), np.where(k % 2 == 0, Q, alt), np.where(k % 2 == 1, Q, alt)][:ncomp]
+    return [np.full(64, Q), np.where(k % 2 == 0, Q, alt), np.where(k % 2 == 1, Q, alt), np.full(64, 3 if Q == 1 else Q // 2)][:ncomp]
 
 
 def _in_range_amp(limit, q, k):
@@ -220,7 +223,7 @@ def _generate(variant, per_mcu, mcus):
         return _gen_sat_dense(int(variant.rsplit("q", 1)[1]), per_mcu, mcus, rng)
     if variant == "sat_chroma":
         return _gen_sat_chroma(per_mcu, mcus, rng)
-    return _gen_over({"q1": (1, 1, 1), "q3": (3, 2, 1)}[arg], per_mcu, mcus, rng)
+    return _gen_over({"q1": (1, 1, 1, 3), "q3": (3, 2, 1, 5)}[arg], per_mcu, mcus, rng)
 
 
 def _huffman(kind):
