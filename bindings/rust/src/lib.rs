@@ -73,6 +73,22 @@ impl mjx_output {
     }
 }
 
+/// MJX_OUTPUT_PAD_OFFSET: the pad colour of MJX_FIT_CONTAIN is bytes 28, 29 and 30 of mjx_output, the gap between `bias` and `dst`,
+/// one byte per OUTPUT channel (luminance: byte 0).  A zeroed value pads with black.  Set it on the value the call is given.
+pub const MJX_OUTPUT_PAD_OFFSET: usize = 28;
+impl mjx_output {
+    pub fn pad(&self) -> [u8; 3] {
+        let p = unsafe { (self as *const mjx_output as *const u8).add(MJX_OUTPUT_PAD_OFFSET) };
+        unsafe { [*p, *p.add(1), *p.add(2)] }
+    }
+    pub fn set_pad(&mut self, pad: [u8; 3]) {
+        let p = unsafe { (self as *mut mjx_output as *mut u8).add(MJX_OUTPUT_PAD_OFFSET) };
+        for c in 0..3 {
+            unsafe { *p.add(c) = pad[c] }
+        }
+    }
+}
+
 /// Orientation on the device: the file's EXIF orientation and / or one code 1..8 per input on top (include/mjx.h: mjx_orient).
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -128,6 +144,21 @@ impl mjx_resize {
     }
     pub fn set_filter(&mut self, filter: u8) {
         unsafe { *(self as *mut mjx_resize as *mut u8).add(MJX_RESIZE_FILTER_OFFSET) = filter }
+    }
+}
+
+/// MJX_RESIZE_FIT_OFFSET: the fit mode of a resize description is byte 11 of mjx_resize, the struct's last byte (0: stretch, 1: cover
+/// -- centre-crop --, 2: contain -- letterbox, padded with mjx_output's pad colour).  Set it on the value the call is given.
+pub const MJX_RESIZE_FIT_OFFSET: usize = 11;
+pub const MJX_FIT_STRETCH: u8 = 0;
+pub const MJX_FIT_COVER: u8 = 1;
+pub const MJX_FIT_CONTAIN: u8 = 2;
+impl mjx_resize {
+    pub fn fit(&self) -> u8 {
+        unsafe { *(self as *const mjx_resize as *const u8).add(MJX_RESIZE_FIT_OFFSET) }
+    }
+    pub fn set_fit(&mut self, fit: u8) {
+        unsafe { *(self as *mut mjx_resize as *mut u8).add(MJX_RESIZE_FIT_OFFSET) = fit }
     }
 }
 
@@ -320,6 +351,9 @@ extern "C" {
     pub fn mjx_batch_image_orientation(b: *const mjx_batch, i: usize, code: *mut u8) -> c_int;
     pub fn mjx_batch_image_scale(b: *const mjx_batch, i: usize, scale_denom: *mut u8) -> c_int;
     pub fn mjx_batch_resize_rect(b: *const mjx_batch, i: usize, rect: *mut mjx_rect) -> c_int;
+    pub fn mjx_batch_fit_rect(b: *const mjx_batch, i: usize, inner: *mut mjx_rect) -> c_int;
+    pub fn mjx_resize_fit_plan(desc: *const mjx_scan_desc, opts: *const mjx_opts, out: *const mjx_output, rs: *const mjx_resize,
+                               orient_code: u8, i: usize, inner: *mut mjx_rect, asked: *mut mjx_rect, scale_denom: *mut u8) -> c_int;
     pub fn mjx_batch_tile(ctx: *mut mjx_ctx, src: *const mjx_batch, times: usize, out: *mut *mut mjx_batch) -> c_int;
     pub fn mjx_batch_free(b: *mut mjx_batch);
     pub fn mjx_batch_decode(b: *mut mjx_batch, stages: c_uint) -> c_int;

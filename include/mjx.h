@@ -344,7 +344,52 @@ typedef struct mjx_resize {
  * bias[c]) on the unrounded and UNCLAMPED v (as torch's float path), F16 that float rounded to nearest even.  With nearest every
  * element is mjx_output's table applied to the byte picked, bit for bit; with any kind a target of the rectangle's own size is
  * that table applied to the packed decode, bit for bit.  Not built: Lanczos (its weights need sin(pi x) from one host-and-device
- * routine that gives exact zeros at whole distances: an argument-reduced form of its own); modes that pad (letterbox). */
+ * routine that gives exact zeros at whole distances: an argument-reduced form of its own). */
+
+/* The fit mode of a resize description: byte 11 of mjx_resize, the last byte the declared members leave unused (the struct's members,
+ * size and offsets are as they were; a zero-filled struct means what it meant).  An lvalue: MJX_RESIZE_FIT(&rs) = MJX_FIT_CONTAIN.
+ * Fill the struct with zeros first and set the mode on the object the call is given, as for the filter byte: a member-wise copy need
+ * not carry it.  A value above MJX_FIT_CONTAIN gives the picture MJX_ERR_INVALID_ARG (the plan functions report it).  Every entry
+ * point that takes a resize description carries the mode: mjx_batch_create_resize, mjx_decode_batch_resize, mjx_batch_create_orient,
+ * mjx_decode_batch_orient, mjx_resize_plan, mjx_orient_plan. */
+#define MJX_RESIZE_FIT_OFFSET 11
+#define MJX_RESIZE_FIT(rs) (((uint8_t *)(rs))[MJX_RESIZE_FIT_OFFSET])
+#define MJX_FIT_STRETCH 0       /* the rectangle is stretched to the target: the rule above, bit for bit */
+#define MJX_FIT_COVER   1       /* centre-crop: the largest centred part of the rectangle with the target's aspect fills the target */
+#define MJX_FIT_CONTAIN 2       /* letterbox: the rectangle fits inside the target, the rest is the pad colour */
+/* The pad colour of MJX_FIT_CONTAIN: bytes 28, 29 and 30 of mjx_output, the alignment gap between `bias` and `dst` (size, members and
+ * offsets as they were; a zero-filled struct pads with black).  MJX_OUTPUT_PAD(&out)[c] = value, c the OUTPUT channel as for scale
+ * and bias -- bgr does not reorder the three bytes; luminance output uses byte 0 only.  A padded element is the format's table
+ * applied to that byte, exactly what a decoded pixel of that value would become: U8 the byte, F32 fmaf((float)byte, scale[c],
+ * bias[c]), F16 that value rounded to nearest even.  out == NULL pads with black; with mean / std black is what Pad(fill=0) before
+ * Normalize gives, and the mean colour's bytes give about 0 after normalisation.  The bytes are ignored unless the mode is
+ * MJX_FIT_CONTAIN.  Set them on the object the call is given. */
+#define MJX_OUTPUT_PAD_OFFSET 28
+#define MJX_OUTPUT_PAD(out) ((uint8_t *)(out) + MJX_OUTPUT_PAD_OFFSET)
+/* The rule (fit_rule, mjx_kernels.h: the planner and mjx_resize_fit_plan run this one routine).  Per picture
+ * A = (x, y, w, h) is the rectangle the call asks for -- rois[i] or the whole picture -- in the coordinates of the picture that
+ * leaves (D, after orientation): full size with auto_scale, else at the call's scale.  The target is W x H in D's axes.  Products are
+ * 64-bit, round(a / b) = (2a + b) / (2b) in integers, the other divisions floor.
+ * MJX_FIT_COVER takes the largest centred part A' of A with the target's aspect:
+ *   w H > h W:  w' = clamp(round(h W / H), 1, w),  x' = x + (w - w') / 2,  h and y unchanged;
+ *   w H < h W:  h' = clamp(round(w H / W), 1, h),  y' = y + (h - h') / 2,  w and x unchanged;   else A' = A.
+ * The picture is then planned exactly as the stretch call with rois[i] = A': orientation mapping, auto_scale with its outward
+ * rounding, tiles read and filter taps are that call's, and the output is byte for byte that call's.
+ * MJX_FIT_CONTAIN computes the inner size and origin:
+ *   w H > h W:  iw = W,  ih = clamp(round(h W / w), 1, H);   w H < h W:  ih = H,  iw = clamp(round(w H / h), 1, W);   else iw = W, ih = H;
+ *   ox = (W - iw) / 2,  oy = (H - ih) / 2.
+ * The inner rectangle (ox, oy, iw, ih) of the target is exactly what the stretch call with target iw x ih and rois[i] = A writes --
+ * with auto_scale the scale is chosen against iw x ih -- bit for bit in every format; every other element of the target is the pad
+ * element (k_fit_pad writes the border, behind stage B like the resize).  Only one axis is ever padded.
+ * Everything else is the resize's: dst[i].width / height are the target's, mjx_batch_image_info and mjx_batch_output_info speak of
+ * the W x H picture, mjx_batch_resize_rect, mjx_batch_image_roi and mjx_batch_image_scale of what was decoded, rgb_bytes counts the
+ * whole target, mjx_orient_plan's out_w x out_h are the target (its rectangle and scale, and all of mjx_resize_plan, are the rewritten
+ * stretch call's), mjx_batch_tile carries mode and pad along; a picture whose status is not MJX_OK has nothing written, border
+ * included; the refusals (MJX_LAYOUT_REF_COMPAT, auto_scale with a scale, planes) are unchanged.
+ * Mapping a source coordinate to the output (boxes, key points): with (asked, inner) from mjx_resize_fit_plan, a point (px, py) of D
+ * in asked's coordinates lies at  inner.x + (px - asked.x) inner.w / asked.w,  inner.y + (py - asked.y) inner.h / asked.h  of the
+ * target (pixel centres: add 0.5 before and take it off after).
+ * Not built: per-picture target sizes, a fractional crop ratio, pad modes other than a constant colour, fit modes for planes. */
 
 /* ---- orientation on the device: EXIF orientation, with per-picture flips on top -----------------------------------------
  * A camera file stores its pixels as the sensor saw them and names, in EXIF tag 0x0112, one of eight ways to turn them upright.
@@ -562,6 +607,12 @@ int mjx_batch_create_resize(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, 
  * number of taps of an output column / row (what the resize kernel's loops run to).  Returns the picture's status. */
 int mjx_resize_plan(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_resize *rs, size_t i, uint8_t *scale_denom,
                     mjx_rect *rect, uint32_t *taps_x, uint32_t *taps_y);
+/* Host-only, the planner's own rule (fit_rule): picture `desc` as input i of a call with these options, this output description (its
+ * pad bytes are not looked at; NULL is fine), this resize and the resolved orientation code -- *inner: the inner rectangle in the
+ * target (the whole target for MJX_FIT_STRETCH and MJX_FIT_COVER); *asked: A' for MJX_FIT_COVER and A otherwise, in D's coordinates at
+ * full size (auto_scale) or at the call's scale; *scale_denom: the scale the picture is decoded at.  Returns the picture's status. */
+int mjx_resize_fit_plan(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_output *out, const mjx_resize *rs, uint8_t orient_code,
+                        size_t i, mjx_rect *inner, mjx_rect *asked, uint8_t *scale_denom);
 /* Host-only: the filter of one output coordinate X of an axis n_in -> n_out -- the routine the resize kernel itself runs
  * (resize_axis / resize_weight, mjx_kernels.h).  *first: the first tap's input index, weights[0 .. *count): the normalised weights
  * (at most cap are written; *count is the window's length either way).  n_in, n_out in 1 .. 2^24, X < n_out. */
@@ -624,6 +675,9 @@ int mjx_batch_image_orientation(const mjx_batch *b, size_t i, uint8_t *code);
 /* a resized batch: the rectangle R picture i's intermediate covers, in the coordinates of the picture at its scale
  * (mjx_batch_image_roi: that picture's size); any other batch: the picture's own rectangle */
 int mjx_batch_resize_rect(const mjx_batch *b, size_t i, mjx_rect *rect);
+/* a resized batch: the inner rectangle of picture i in its target -- the part the picture fills; (0, 0, W, H) for MJX_FIT_STRETCH and
+ * MJX_FIT_COVER, the letterboxed part for MJX_FIT_CONTAIN; (0, 0, 0, 0) for a batch without a resize */
+int mjx_batch_fit_rect(const mjx_batch *b, size_t i, mjx_rect *inner);
 /* device pointer + byte size of image i's packed RGB (valid until mjx_batch_free) */
 int mjx_batch_rgb_device(const mjx_batch *b, size_t i, void **dev_ptr, size_t *bytes);
 /* copy image i's RGB to host memory (width*height*3 bytes) */

@@ -90,6 +90,18 @@ class OutputDesc(ctypes.Structure):
     def channels(self, v):
         ctypes.c_uint8.from_address(ctypes.addressof(self) + self.CHANNELS_OFFSET).value = int(v)
 
+    PAD_OFFSET = 28                     # MJX_OUTPUT_PAD_OFFSET: the pad colour lives in the three bytes in front of dst
+
+    @property
+    def pad(self):
+        return tuple((ctypes.c_uint8 * 3).from_address(ctypes.addressof(self) + self.PAD_OFFSET))
+
+    @pad.setter
+    def pad(self, v):
+        b = (ctypes.c_uint8 * 3).from_address(ctypes.addressof(self) + self.PAD_OFFSET)
+        for c in range(3):
+            b[c] = int(v[c])
+
 
 class PlaneLayout(ctypes.Structure):
     """mjx_plane_layout: the planes of one picture; pitches in elements, width / height in samples of the component."""
@@ -116,6 +128,16 @@ class ResizeDesc(ctypes.Structure):
     def filter(self, v):
         ctypes.c_uint8.from_address(ctypes.addressof(self) + self.FILTER_OFFSET).value = int(v)
 
+    FIT_OFFSET = 11                     # MJX_RESIZE_FIT_OFFSET: the fit mode lives in the struct's last byte
+
+    @property
+    def fit(self):
+        return ctypes.c_uint8.from_address(ctypes.addressof(self) + self.FIT_OFFSET).value
+
+    @fit.setter
+    def fit(self, v):
+        ctypes.c_uint8.from_address(ctypes.addressof(self) + self.FIT_OFFSET).value = int(v)
+
 
 class OrientDesc(ctypes.Structure):
     """mjx_orient: where a picture's orientation code comes from (see Orient)."""
@@ -134,6 +156,29 @@ def _filter_code(filter):
             raise MjxError(ERR_INVALID_ARG, "filter %r (one of %s)" % (filter, ", ".join(sorted(FILTERS))))
         return FILTERS[filter]
     return int(filter)
+
+
+FIT_STRETCH, FIT_COVER, FIT_CONTAIN = 0, 1, 2
+FITS = {"stretch": FIT_STRETCH, "cover": FIT_COVER, "contain": FIT_CONTAIN}
+
+
+def _fit_code(fit):
+    """A fit mode's name (or its MJX_FIT_* code) -> the code."""
+    if isinstance(fit, str):
+        if fit not in FITS:
+            raise MjxError(ERR_INVALID_ARG, "fit %r (one of %s)" % (fit, ", ".join(sorted(FITS))))
+        return FITS[fit]
+    return int(fit)
+
+
+def _pad_bytes(pad):
+    """A pad colour -- one value or three, 0 .. 255 -- -> three ints."""
+    v = [pad] * 3 if np.isscalar(pad) else list(pad)
+    if len(v) == 1:
+        v = v * 3
+    if len(v) != 3 or any(int(x) != x or not 0 <= int(x) <= 255 for x in v):
+        raise MjxError(ERR_INVALID_ARG, "pad=%r (one value or three, 0 .. 255)" % (pad,))
+    return tuple(int(x) for x in v)
 _NP_DTYPES = {DTYPE_U8: np.uint8, DTYPE_F16: np.float16, DTYPE_F32: np.float32}
 
 
@@ -211,6 +256,8 @@ SYMBOLS = {
     "mjx_batch_image_orientation": (_int, [_vp, _sz, _P(ctypes.c_uint8)]),
     "mjx_batch_image_scale": (_int, [_vp, _sz, _P(ctypes.c_uint8)]),
     "mjx_batch_resize_rect": (_int, [_vp, _sz, _P(Rect)]),
+    "mjx_batch_fit_rect": (_int, [_vp, _sz, _P(Rect)]),
+    "mjx_resize_fit_plan": (_int, [_P(ScanDesc), _P(Opts), _P(OutputDesc), _P(ResizeDesc), ctypes.c_uint8, _sz, _P(Rect), _P(Rect), _P(ctypes.c_uint8)]),
     "mjx_decode_batch": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(_P(ctypes.c_uint8)), _P(_int), _P(_vp)]),
     "mjx_free_image": (None, [_P(Image)]),
     "mjx_ctx_create": (_int, [_int, _P(_vp)]),
@@ -351,15 +398,20 @@ class Output:
     dst: None -- the library owns the output, dense -- or one (device pointer, width, height, row_pitch, plane_pitch) per input,
     pitches in elements.
     channels: 3, or 1 for luminance -- H x W elements, one per pixel (H x W x 1 and 1 x H x W are the same memory; planar only says
-    which shape Batch.output gives; bgr has no meaning); mean / std / scale / bias are then one value (a scalar or one element)."""
+    which shape Batch.output gives; bgr has no meaning); mean / std / scale / bias are then one value (a scalar or one element).
+    pad: the colour of the border of Resize(fit="contain"), one value or three of 0 .. 255 by OUTPUT channel (bgr does not reorder
+    them; luminance uses the first).  A padded element is what a decoded pixel of that value would become: the byte, or
+    fmaf(float(byte), scale[c], bias[c]).  0 is black -- Pad(fill=0) before Normalize; the mean colour's bytes give about 0 after
+    normalisation.  Ignored by every other fit mode."""
 
-    def __init__(self, dtype="uint8", planar=False, bgr=False, mean=None, std=None, scale=None, bias=None, dst=None, channels=3):
+    def __init__(self, dtype="uint8", planar=False, bgr=False, mean=None, std=None, scale=None, bias=None, dst=None, channels=3, pad=0):
         names = {"uint8": DTYPE_U8, "u8": DTYPE_U8, "float16": DTYPE_F16, "f16": DTYPE_F16, "float32": DTYPE_F32, "f32": DTYPE_F32}
         self.dtype = names[dtype] if isinstance(dtype, str) else int(dtype)
         self.planar, self.bgr = bool(planar), bool(bgr)
         self.channels = int(channels)
         if not 0 <= self.channels <= 255:
             raise MjxError(ERR_INVALID_ARG, "channels=%r" % (channels,))
+        self.pad = _pad_bytes(pad)
         if (mean is not None or std is not None) and (scale is not None or bias is not None):
             raise MjxError(ERR_INVALID_ARG, "mean / std or scale / bias, not both")
         def three(v, d):
@@ -383,6 +435,7 @@ class Output:
         """-> the ctypes mjx_output (it keeps its dst array alive)."""
         d = OutputDesc(self.dtype, int(self.planar), int(self.bgr))
         d.channels = self.channels
+        d.pad = self.pad
         for c in range(3):
             d.scale[c], d.bias[c] = float(self.scale[c]), float(self.bias[c])
         if self.dst is not None:
@@ -457,24 +510,33 @@ class Resize:
     Pillow's BICUBIC; a = -0.75 and four taps without, which does not widen when shrinking) or "nearest" (torch's nearest-exact,
     Pillow's NEAREST; antialias is ignored).  auto_scale: the library picks the DCT-domain scale (1, 1/2, 1/4, 1/8) per picture so that the filter
     never has to shrink by more than it must; rois are then in FULL-SIZE coordinates and scale must be 1.  Without it the call's
-    scale and rois apply as in any call."""
+    scale and rois apply as in any call.
+    fit: "stretch" -- the rectangle is stretched to the target --, "cover" -- centre-crop: the largest centred part of the rectangle
+    with the target's aspect fills the target, byte for byte the stretch call on that part -- or "contain" -- letterbox: the rectangle
+    is resized to fit inside the target, centred, and the rest is Output's pad colour (mjx.h has the rule in integers).
+    Mapping a source coordinate to the output: with p = ParsedScan.fit_plan(resize, ...), a point (px, py) of the oriented picture, in
+    the coordinates p["asked"] is given in, lies at inner.x + (px - asked.x) * inner.w / asked.w, inner.y + (py - asked.y) * inner.h /
+    asked.h of the target; Batch.fit_rect(i) gives the inner rectangle of a picture of a batch."""
 
-    def __init__(self, width, height, antialias=True, auto_scale=True, filter="bilinear"):
+    def __init__(self, width, height, antialias=True, auto_scale=True, filter="bilinear", fit="stretch"):
         self.width, self.height = int(width), int(height)
         self.antialias, self.auto_scale = bool(antialias), bool(auto_scale)
         self.filter = filter
         _filter_code(filter)
+        self.fit = fit
+        _fit_code(fit)
         if not (0 <= self.width <= 0xffffffff and 0 <= self.height <= 0xffffffff):
             raise MjxError(ERR_INVALID_ARG, "resize to %d x %d" % (self.width, self.height))
 
     def desc(self):
         d = ResizeDesc(self.width, self.height, int(self.antialias), int(self.auto_scale))
         d.filter = _filter_code(self.filter)
+        d.fit = _fit_code(self.fit)
         return d
 
     def sized(self, width, height):
-        """This description at another target size: everything else, the filter included, is kept."""
-        return Resize(width, height, self.antialias, self.auto_scale, self.filter)
+        """This description at another target size: everything else, the filter and the fit mode included, is kept."""
+        return Resize(width, height, self.antialias, self.auto_scale, self.filter, self.fit)
 
 
 def _rs_ref(resize):
@@ -632,6 +694,20 @@ class ParsedScan:
         s, r, tx, ty = ctypes.c_uint8(), Rect(), ctypes.c_uint32(), ctypes.c_uint32()
         _check(lib().mjx_resize_plan(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(s), ctypes.byref(r), ctypes.byref(tx), ctypes.byref(ty)), "mjx_resize_plan")
         return dict(scale=s.value, rect=(r.x, r.y, r.w, r.h), taps_x=tx.value, taps_y=ty.value)
+
+    def fit_plan(self, resize, output=None, code=1, roi=None, scale=1, i=0, layout=LAYOUT_STANDARD):
+        """mjx_resize_fit_plan (host only) -> dict(inner=(x, y, w, h), asked=(x, y, w, h), scale): the inner rectangle of the target this
+        picture fills under this Resize's fit mode (the whole target unless the mode is "contain"), the rectangle asked for -- roi or the
+        whole picture, for "cover" its centred part -- in the coordinates of the oriented picture (full size with auto_scale, else at the
+        call's scale), and the scale the picture is decoded at.  A source point (px, py) in asked's coordinates lies at
+        inner.x + (px - asked.x) * inner.w / asked.w, inner.y + (py - asked.y) * inner.h / asked.h of the output."""
+        o = _opts(layout=layout, scale=scale, rois=roi)
+        keep, ref = _rs_ref(resize)
+        keep_o, oref = _out_ref(output)
+        inner, asked, s = Rect(), Rect(), ctypes.c_uint8()
+        _check(lib().mjx_resize_fit_plan(ctypes.byref(self.desc), ctypes.byref(o), oref, ref, int(code), int(i), ctypes.byref(inner),
+                                         ctypes.byref(asked), ctypes.byref(s)), "mjx_resize_fit_plan")
+        return dict(inner=(inner.x, inner.y, inner.w, inner.h), asked=(asked.x, asked.y, asked.w, asked.h), scale=s.value)
 
     def orient_plan(self, code, resize=None, roi=None, scale=1, i=0, layout=LAYOUT_STANDARD):
         """mjx_orient_plan (host only) -> dict(width, height, stored_rect=(x, y, w, h), scale): the picture that leaves when this one is
@@ -799,6 +875,14 @@ class Batch:
         """(x, y, w, h) of what was decoded for picture i, in the coordinates of the picture at scale(i) (roi(i): its size)."""
         r = Rect()
         lib().mjx_batch_resize_rect(self.h, i, ctypes.byref(r))
+        return (r.x, r.y, r.w, r.h)
+
+    def fit_rect(self, i):
+        """mjx_batch_fit_rect -> (x, y, w, h): the inner rectangle of picture i's target, the part the picture fills -- the whole target
+        for Resize(fit="stretch") and "cover", the letterboxed part for "contain"; zeros for a batch without a resize.  With
+        ParsedScan.fit_plan's `asked` a source point maps to inner.x + (px - asked.x) * inner.w / asked.w, likewise in y."""
+        r = Rect()
+        lib().mjx_batch_fit_rect(self.h, i, ctypes.byref(r))
         return (r.x, r.y, r.w, r.h)
 
     def rgb(self, i):
@@ -1133,7 +1217,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
 
 
 def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=False, threads=0, device_destuff=None, planar=None, resize=None,
-                orient=None, pixels=None, color=None):
+                orient=None, pixels=None, color=None, pad=0):
     """Decodes the files straight into a torch tensor on the context's device: N x 3 x H x W (planar) or N x H x W x 3, of uint8,
     float16 or float32; picture i -- at 1/scale, its rectangle rois[i] -- must be H x W.  Float tensors take (v / 255 - mean) / std
     per OUTPUT channel (see Output); bgr: channel 0 is blue.  The pointers and pitches come from data_ptr() and stride(): the
@@ -1145,7 +1229,8 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
     N x 1 x H x 1 needs the keyword -- with padded rows; mean / std are then scalars or have one element.
     torch's current stream is synchronised before the call (the library writes on streams of its
     own) and the batch is complete when this returns.  -> the per-picture statuses.
-    resize: True, or a Resize (its antialias, auto_scale and filter; a size, if it names one, must be the tensor's) -- the pictures, of any
+    pad: the border colour of resize=Resize(fit="contain") (Output's pad: one value or three of 0 .. 255, by OUTPUT channel).
+    resize: True, or a Resize (its antialias, auto_scale, filter and fit mode; a size, if it names one, must be the tensor's) -- the pictures, of any
     size, are resampled on the device to the tensor's H x W (see Resize); None: every picture must be H x W as it is.
     orient: an Orient -- the pictures are turned on the device (see Orient); H x W and rois speak of the turned pictures.
     pixels: "libjpeg", color: "file" -- see Batch."""
@@ -1197,7 +1282,7 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
         raise MjxError(ERR_INVALID_ARG, "out.stride() %s: neither 3 x H x W nor H x W x 3 with a dense innermost dimension, or the pictures overlap" % (tuple(out.stride()),))
     esz = out.element_size()
     dst = [(out.data_ptr() + i * sn * esz, w, h, row_pitch, plane_pitch) for i in range(n)]
-    fmt = Output(names[out.dtype], planar=bool(planar), bgr=bgr, mean=mean, std=std, dst=dst, channels=channels)
+    fmt = Output(names[out.dtype], planar=bool(planar), bgr=bgr, mean=mean, std=std, dst=dst, channels=channels, pad=pad)
     torch.cuda.current_stream(out.device).synchronize()
     if resize is not None and resize is not False:
         rs = Resize(w, h) if resize is True else resize.sized(w, h)

@@ -141,6 +141,7 @@ struct ImageInfo {
     // the full_w x full_h picture at `scale`) and lies at DevImage::rgb_off; rgb_off here is the output's place in the pool
     bool rs_on = false;
     uint32_t scale = 1, src_w = 0, src_h = 0;
+    uint32_t fit_x = 0, fit_y = 0, fit_w = 0, fit_h = 0;    // ... and the inner rectangle of the target the picture fills (mjx_batch_fit_rect; zeros without a resize)
     uint32_t orient = 1;           // orientation on the device: the picture that leaves is orient_c of the intermediate (rs_on is set for c != 1)
     uint64_t coef_off = 0;         // blocks, inside the per-block arrays of its chunk (or of the batch with keep_coefs)
     uint64_t ent_off = 0, ent_cap = 0;   // region of the compact coefficient stream (entries)
@@ -187,6 +188,7 @@ struct Chunk {
                                    // picture -- a lane per pixel written, per plane sample for kSinkYcc (kSinkPlanes has no 1/8)
     uint32_t max_pass_tiles[kPostPasses][kFilterCount] = {};   // the passes behind stage B: workgroups for the chunk's largest picture of each pass
                                    // and filter kind (DevImage::rs_filter; [0] for the passes that have no filter); 0: launches nothing
+    uint32_t max_fit_wgs = 0;      // fit modes: workgroups of k_fit_pad for the chunk's largest letterboxed picture (DevImage::fit_on); 0: no launch
     uint32_t max_b_tiles = 0;      // tiles the workgroups of stage B walk in the chunk's largest picture: all its tiles, or those of its
                                    // rectangle's MCU rows (DevImage::roi_ntiles) -- max_tiles without rectangles
     uint32_t min_sub_bits = 0xffffffffu;   // shortest subsequence length among its scans (chunk_fix_passes)
@@ -484,6 +486,14 @@ bool planar_ok(bool planar_direct, bool keep_coefs, const std::vector<ImagePlan>
     return (T & (T - 1)) == 0 && kinds >= 1 && kinds <= kPlanarKinds && pieces <= 2 && pieces * kinds <= kPlanarSegs;
 }
 
+// fit modes: bytes from the target's first element to the inner rectangle's (fit_oy rows and fit_ox pixels at the format's pitches)
+uint64_t fit_origin_bytes(const ImagePlan &p)
+{
+    const uint64_t esz = p.out_dtype == MJX_DTYPE_U8 ? 1u : p.out_dtype == MJX_DTYPE_F16 ? 2u : 4u;
+    const uint64_t per_pixel = p.out_channels == 1 || p.out_planar ? 1u : 3u;
+    return (uint64_t(p.fit_oy) * p.out_row_pitch + uint64_t(p.fit_ox) * per_pixel) * esz;
+}
+
 // Fills the DevImage of image i from its plan (offsets are assigned by the caller).
 void fill_dev_image(const ImagePlan &p, DevImage &d)
 {
@@ -530,6 +540,12 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
         d.out_row_pitch = p.out_row_pitch; d.out_plane_pitch = p.out_plane_pitch;
         d.out_dtype = p.out_dtype; d.out_planar = p.out_planar; d.out_bgr = p.out_bgr;
         for (uint32_t c = 0; c < 3; c++) { d.out_scale[c] = p.out_scale[c]; d.out_bias[c] = p.out_bias[c]; }
+        // fit modes: the target, and for MJX_FIT_CONTAIN the inner rectangle's origin -- the resize pass writes from there on (a
+        // caller-owned destination here, the pool's rs_off where build_batch assigns it) -- and the border for k_fit_pad
+        d.fit_w = p.fit_w; d.fit_h = p.fit_h; d.fit_ox = p.fit_ox; d.fit_oy = p.fit_oy;
+        d.fit_pad = uint32_t(p.pad[0]) | uint32_t(p.pad[1]) << 8 | uint32_t(p.pad[2]) << 16;
+        d.fit_on = p.rs_on && p.fit_mode == kFitContain && (p.rs_w != p.fit_w || p.rs_h != p.fit_h) ? 1u : 0u;
+        if (p.out_dev) d.out_dev += fit_origin_bytes(p);
     }
     if (p.ycc_on) {
         d.ycc_on = 1; d.ycc_il = p.ycc_il; d.ycc_round = p.ycc_round;
@@ -670,6 +686,7 @@ void plan_chunks(mjx_batch *b)
                     if (d.or_on == kOrResize) pass(kPassResizeOrient, d.rs_filter, resize_tiles(d.rs_w, d.rs_h));
                     if (d.or_on == kOrCopyLuma) pass(kPassOrientLuma, 0, orient_tiles(d.rs_w, d.rs_h));
                     if (d.or_on == kOrResizeLuma) pass(kPassResizeLuma, d.rs_filter, resize_tiles(d.rs_w, d.rs_h));
+                    if (d.fit_on) c.max_fit_wgs = std::max(c.max_fit_wgs, fit_pad_wgs(d.out_ch != 1 && d.out_planar ? 3u : 1u, d.fit_h));
                 }
                 if (d.mode == stage_b_mode(kFormRefCompat, kSinkPacked)) {
                     d.plane_off = c.plane_words;
@@ -1010,6 +1027,11 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
                 }
                 prof_end(b, sp);
             }
+        if (c.max_fit_wgs) {                                // fit modes: the borders of the chunk's letterboxed pictures
+            prof_begin(b, MJX_K_RESIZE, sp);
+            launch_fit_pad(sp, c.max_fit_wgs, nimg, imgs, b->d_rgb, b->d_img_flags);
+            prof_end(b, sp);
+        }
         if (sp != st) {
             HIPOK(hipEventRecord(b->ev_pixels[set], sp));
             b->pixels_recorded[set] = true;
@@ -1362,10 +1384,11 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 inf.rs_on = true;
                 inf.orient = p.orient;
                 inf.src_w = p.roi_w; inf.src_h = p.roi_h;
-                inf.width = p.rs_w; inf.height = p.rs_h;
+                inf.width = p.fit_w; inf.height = p.fit_h;                       // (the picture that leaves: the whole target)
+                if (!p.or_copy) { inf.fit_x = p.fit_ox; inf.fit_y = p.fit_oy; inf.fit_w = p.rs_w; inf.fit_h = p.rs_h; }
                 inf.rgb_off = rgb_pool;
-                d.rs_off = rgb_pool;
-                inf.rgb_bytes = uint64_t(p.rs_w) * p.rs_h * p.out_channels;
+                d.rs_off = rgb_pool + fit_origin_bytes(p);                       // (MJX_FIT_CONTAIN: the resize pass starts at the inner rectangle)
+                inf.rgb_bytes = uint64_t(p.fit_w) * p.fit_h * p.out_channels;
             }
             inf.rgb_bytes *= p.out_dtype == MJX_DTYPE_U8 ? 1u : p.out_dtype == MJX_DTYPE_F16 ? 2u : 4u;      // (the bytes written)
             if (p.ycc_on) {                                                  // (component planes: the samples of every plane)
@@ -2107,6 +2130,31 @@ extern "C" int mjx_resize_plan(const mjx_scan_desc *desc, const mjx_opts *opts, 
     });
 }
 
+// Host-only: the fit rule as the planner applied it (plan_input_for, fit_rule) -- the inner rectangle of the target, the rectangle
+// asked for (MJX_FIT_COVER: the centred part) in D's coordinates, and the scale the picture is decoded at.
+extern "C" int mjx_resize_fit_plan(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_output *fmt, const mjx_resize *rs, uint8_t code,
+                                   size_t i, mjx_rect *inner, mjx_rect *asked, uint8_t *scale_denom)
+{
+    return guarded([&]() -> int {
+    if (!desc || !rs) return MJX_ERR_INVALID_ARG;
+    mjx_opts o{};
+    if (opts) o = *opts;
+    if (!o.rois ? o.n_rois != 0 : (o.n_rois == 0 || (o.n_rois > 1 && i >= o.n_rois))) return MJX_ERR_INVALID_ARG;
+    if (o.rois) { if (o.n_rois > 1) o.rois += i; o.n_rois = 1; }
+    mjx_output f;                                      // (the format's own rules count; a caller's destinations are not looked at)
+    std::memcpy(&f, fmt ? fmt : &kPackedOutput, sizeof f);      // (... with the bytes the declared members leave unused: channels, pad)
+    f.dst = nullptr; f.n_dst = 0;
+    std::vector<ImagePlan> plans;
+    plan_input_for(*desc, o, &f, rs, 0, plans, code);
+    const ImagePlan &p = plans.back();
+    if (p.status != MJX_OK) return p.status;
+    if (inner) *inner = mjx_rect{p.fit_ox, p.fit_oy, p.rs_w, p.rs_h};
+    if (asked) *asked = mjx_rect{p.fit_ax, p.fit_ay, p.fit_aw, p.fit_ah};
+    if (scale_denom) *scale_denom = uint8_t(p.scale);
+    return MJX_OK;
+    });
+}
+
 // Host-only: one output coordinate's filter from the kernel's own routine.
 extern "C" int mjx_resize_weights(uint32_t n_in, uint32_t n_out, int antialias, uint32_t X, uint32_t *first, float *weights, size_t cap,
                                   size_t *count)
@@ -2219,8 +2267,8 @@ extern "C" int mjx_orient_plan(const mjx_scan_desc *desc, const mjx_opts *opts, 
     plan_input_for(*desc, o, &kPackedOutput, rs, 0, plans, code);
     const ImagePlan &p = plans.back();
     if (p.status != MJX_OK) return p.status;
-    if (out_w) *out_w = p.rs_on ? p.rs_w : p.roi_w;
-    if (out_h) *out_h = p.rs_on ? p.rs_h : p.roi_h;
+    if (out_w) *out_w = p.rs_on ? p.fit_w : p.roi_w;
+    if (out_h) *out_h = p.rs_on ? p.fit_h : p.roi_h;
     if (stored_rect) *stored_rect = mjx_rect{p.roi_x, p.roi_y, p.roi_w, p.roi_h};
     if (scale_denom) *scale_denom = uint8_t(p.scale);
     return MJX_OK;
@@ -2271,6 +2319,12 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
             p.orient = src->himages[k].or_on ? src->himages[k].orient : 1u;
             p.or_copy = src->himages[k].or_on == kOrCopy || src->himages[k].or_on == kOrCopyLuma;
             p.rs_w = src->himages[k].rs_w; p.rs_h = src->himages[k].rs_h; p.rs_aa = src->himages[k].rs_aa; p.rs_filter = src->himages[k].rs_filter;
+            {                                                                         // (... and its fit mode and pad colour)
+                const DevImage &sd = src->himages[k];
+                p.fit_w = sd.fit_w; p.fit_h = sd.fit_h; p.fit_ox = sd.fit_ox; p.fit_oy = sd.fit_oy;
+                p.fit_mode = sd.fit_on ? kFitContain : kFitStretch;                   // (without a border the mode leaves no trace)
+                for (uint32_t c = 0; c < 3; c++) p.pad[c] = uint8_t(sd.fit_pad >> (8 * c));
+            }
             if (fi.ycc_on) {                                                          // (... and its plane description)
                 const DevImage &sd = src->himages[k];
                 p.ycc_on = true;
@@ -2615,6 +2669,16 @@ extern "C" int mjx_batch_resize_rect(const mjx_batch *b, size_t iu, mjx_rect *re
     if (!visible_index(b, iu, i)) return MJX_ERR_INVALID_ARG;
     const ImageInfo &inf = b->info[i];
     if (rect) *rect = mjx_rect{inf.roi_x, inf.roi_y, inf.src_w, inf.src_h};
+    return inf.status;
+}
+
+extern "C" int mjx_batch_fit_rect(const mjx_batch *b, size_t iu, mjx_rect *inner)
+{
+    if (b && !b->parts.empty()) { mjx_batch *pb; size_t pi; return route(b, iu, pb, pi) ? mjx_batch_fit_rect(pb, pi, inner) : MJX_ERR_INVALID_ARG; }
+    size_t i;
+    if (!visible_index(b, iu, i)) return MJX_ERR_INVALID_ARG;
+    const ImageInfo &inf = b->info[i];
+    if (inner) *inner = mjx_rect{inf.fit_x, inf.fit_y, inf.fit_w, inf.fit_h};
     return inf.status;
 }
 

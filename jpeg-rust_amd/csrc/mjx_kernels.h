@@ -153,6 +153,12 @@ struct DevImage {
     // dc_shape: what the DC-prediction kernels choose by -- bpm for a picture of up to three components, kDcShape4 + bpm for one of
     // four, which so never takes a kernel that carries three running sums.
     uint32_t model, qm3_off, dc_shape;
+    // fit modes (mjx_resize's fit byte).  MJX_FIT_COVER leaves no trace: its rectangle is the planner's.  MJX_FIT_CONTAIN: the picture
+    // that leaves is fit_w x fit_h elements per channel at the pitches above; the resize pass writes its rs_w x rs_h into the inner
+    // rectangle at (fit_ox, fit_oy) -- out_dev and rs_off above are already moved there by fit_oy rows and fit_ox pixels -- and,
+    // fit_on = 1 (there is a border), k_fit_pad writes every other element: the format's table applied to fit_pad's byte c
+    // (bits 8 c .. 8 c + 7, c the OUTPUT channel).  Without the mode fit_w x fit_h = rs_w x rs_h, the origin is 0 and fit_on = 0.
+    uint32_t fit_on, fit_w, fit_h, fit_ox, fit_oy, fit_pad;
 };
 // DevImage::model
 enum ColorModel : uint32_t {
@@ -486,6 +492,40 @@ MJX_HD ResizeAxis resize_axis(uint32_t n_in, uint32_t n_out, bool antialias, uin
     a.sum = float(sum);
     return a;
 }
+
+// ---- fit modes (mjx_resize's fit byte: MJX_FIT_COVER, MJX_FIT_CONTAIN; the rule of mjx.h) ------------------------------------------
+// A = (x, y, w, h): the rectangle asked for, in the coordinates of the picture that leaves; W x H: the target.  COVER rewrites A to its
+// largest centred part with the target's aspect (a: A', inner: the whole target); CONTAIN keeps A and gives the inner rectangle of the
+// target the picture fills.  64-bit products, round(a / b) = (2a + b) / (2b).  w, h, W, H >= 1, all <= kResizeMaxDim.
+// The planner (plan_input_for), mjx_resize_fit_plan and the tests' ctypes call run this one routine.
+constexpr uint32_t kFitStretch = 0, kFitCover = 1, kFitContain = 2, kFitCount = 3;
+struct FitRect { uint32_t x, y, w, h; };
+struct FitPlan { FitRect a, inner; };
+MJX_HD uint32_t fit_round_clamp(uint64_t num, uint64_t den, uint32_t hi)      // clamp(round(num / den), 1, hi)
+{
+    const uint64_t q = (2 * num + den) / (2 * den);
+    return q < 1 ? 1u : q > hi ? hi : uint32_t(q);
+}
+MJX_HD FitPlan fit_rule(uint32_t mode, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t W, uint32_t H)
+{
+    FitPlan f;
+    f.a = FitRect{x, y, w, h};
+    f.inner = FitRect{0, 0, W, H};
+    const uint64_t wH = uint64_t(w) * H, hW = uint64_t(h) * W;
+    if (mode == kFitCover) {
+        if (wH > hW) { f.a.w = fit_round_clamp(hW, H, w); f.a.x = x + (w - f.a.w) / 2; }
+        else if (wH < hW) { f.a.h = fit_round_clamp(wH, W, h); f.a.y = y + (h - f.a.h) / 2; }
+    } else if (mode == kFitContain) {
+        if (wH > hW) f.inner.h = fit_round_clamp(hW, w, H);
+        else if (wH < hW) f.inner.w = fit_round_clamp(wH, h, W);
+        f.inner.x = (W - f.inner.w) / 2;
+        f.inner.y = (H - f.inner.h) / 2;
+    }
+    return f;
+}
+// k_fit_pad: a workgroup owns kFitPadRows rows of the target (of every plane behind one another), a wave every fourth of them
+constexpr uint32_t kFitPadRows = 16;
+MJX_HD uint32_t fit_pad_wgs(uint32_t planes, uint32_t H) { return uint32_t((uint64_t(planes) * H + kFitPadRows - 1) / kFitPadRows); }
 
 // ---- the filter kinds beside the triangle (mjx_resize's filter byte: MJX_FILTER_BICUBIC, MJX_FILTER_NEAREST) ----------------------
 // The positions are the triangle's: c = q + rem / (2 n_out) in lowest terms, tap j at t_j / (2 n_out), its distance in units of the
@@ -959,6 +999,9 @@ void launch_resize_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const 
 void launch_orient_out(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma = false);
 void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags, bool luma = false,
                           uint32_t filter = 0);
+// fit modes: the border of every picture with DevImage::fit_on (MJX_FIT_CONTAIN), behind stage B on the resize's stream; max_wgs = the
+// chunk's largest fit_pad_wgs
+void launch_fit_pad(hipStream_t st, uint32_t max_wgs, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
 // libjpeg's pixels, behind stage B: one workgroup per tile of the rectangle (lj_tiles) and picture with DevImage::lj_on
 void launch_upsample_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
                            const uint32_t *img_flags, bool luma = false /* k_upsample_luma: pictures with DevImage::lj_luma */);

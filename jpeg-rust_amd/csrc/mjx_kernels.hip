@@ -4987,6 +4987,86 @@ extern "C" __global__ __launch_bounds__(256) void k_orient_luma(const DevImage *
     orient_body<1>(images, rgb, img_flags);
 }
 
+// ---- fit modes (mjx_resize's fit byte; DevImage::fit_on): the border of a letterboxed picture ------------------------------------
+// MJX_FIT_CONTAIN: the resize pass has written -- or will write: the two touch disjoint elements, so their order does not matter --
+// its rs_w x rs_h picture into the inner rectangle at (fit_ox, fit_oy) of the fit_w x fit_h target; this kernel writes every other
+// element of the target.  The target is taken as rows of `rowlen` elements: 3 fit_w of an interleaved picture, fit_w of a plane (the
+// three planes' rows behind one another) or of a luminance picture.  A row above or below the inner rectangle is one run [0, rowlen); a
+// row that crosses it is the two runs [0, k fit_ox) and [k (fit_ox + rs_w), rowlen), k the elements per pixel -- only one axis is ever
+// padded, so one of the two kinds is empty, but nothing here relies on that.  A workgroup owns kFitPadRows rows, a wave every fourth
+// of them.  The pad element of channel c -- the format's table applied to the pad byte, out_store1's arithmetic -- is computed once per
+// workgroup, by lanes 0 .. 2 into LDS.  A run leaves as non-temporal 16-byte stores from its first 16-byte boundary on, a lane a vector,
+// with element stores for the head in front of that boundary and the tail behind the last whole vector; a run too short for a vector
+// is all head.  An interleaved row repeats a three-element pattern: a vector is built from its first element's index mod 3.
+// Nothing is written outside [0, rowlen) of a row or outside the fit_h rows (pitched caller memory has the caller's bytes there), and
+// nothing at all for a picture with a device status.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void fit_pad_run(uint8_t *row, uint32_t s, uint32_t e, uint32_t lg, bool il, uint32_t ch, const uint32_t *pv, uint32_t lane)
+{
+    if (s >= e) return;
+    const uint32_t epv = 16u >> lg;                                        // elements per vector
+    const uint32_t mis = uint32_t(uintptr_t(row + (uint64_t(s) << lg)) & 15u);
+    const uint32_t head = mis ? (16u - mis) >> lg : 0u;                    // (an element's address is a multiple of its size)
+    const uint32_t a0 = e - s < head ? e : s + head;
+    const uint32_t nvec = (e - a0) / epv, t0 = a0 + nvec * epv;
+    auto pick = [&](uint32_t c) { return c == 0u ? pv[0] : c == 1u ? pv[1] : pv[2]; };       // (constant indices: no scratch)
+    auto elem = [&](uint32_t j) {
+        const uint32_t v = pick(il ? j % 3u : ch);
+        if (lg == 0u) __builtin_nontemporal_store(uint8_t(v), row + j);
+        else if (lg == 1u) __builtin_nontemporal_store(uint16_t(v), reinterpret_cast<uint16_t *>(row) + j);
+        else __builtin_nontemporal_store(v, reinterpret_cast<uint32_t *>(row) + j);
+    };
+    for (uint32_t j = s + lane; j < a0; j += 64u) elem(j);
+    for (uint32_t j = t0 + lane; j < e; j += 64u) elem(j);
+    const uint32_t epw = 4u >> lg, bits = 8u << lg;                        // elements per 32-bit word, bits per element
+    for (uint32_t v = lane; v < nvec; v += 64u) {
+        const uint32_t j = a0 + v * epv;
+        uint32_t ph = il ? j % 3u : ch;
+        uint32_t w[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) {
+            uint32_t word = 0;
+            for (uint32_t q = 0; q < epw; q++) {
+                word |= pick(ph) << (q * bits);                             // (bits == 32: epw == 1, the shift is 0)
+                if (il) ph = ph == 2u ? 0u : ph + 1u;
+            }
+            w[k] = word;
+        }
+        __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4 *>(row + (uint64_t(j) << lg)));
+    }
+}
+extern "C" __global__ __launch_bounds__(256) void k_fit_pad(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb,
+                                                             const uint32_t *__restrict__ img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    if (!im.valid || !im.fit_on || img_flags[im.status_idx]) return;
+    const bool luma = im.out_ch == 1u, planar = !luma && im.out_planar != 0u, il = !luma && !planar;
+    const uint32_t W = im.fit_w, H = im.fit_h, k = il ? 3u : 1u, planes = planar ? 3u : 1u;
+    const uint32_t nrows = planes * H;                                      // (H <= 2^24)
+    if (blockIdx.x * kFitPadRows >= nrows) return;
+    const uint32_t lg = im.out_dtype == 0u ? 0u : im.out_dtype == 1u ? 1u : 2u;
+    __shared__ uint32_t s_pv[3];
+    if (threadIdx.x < 3u) {
+        const uint32_t c = threadIdx.x, byte = (im.fit_pad >> (8u * c)) & 0xffu;
+        const float e = __builtin_fmaf(float(byte), im.out_scale[c], im.out_bias[c]);
+        s_pv[c] = lg == 0u ? byte : lg == 1u ? half_bits(e) : __builtin_bit_cast(uint32_t, e);
+    }
+    __syncthreads();
+    const uint32_t pv[3] = {s_pv[0], s_pv[1], s_pv[2]};
+    // the target's first element: the resize's origin (out_dev or byte rs_off of the pool) less the inner rectangle's offset
+    uint8_t *inner = im.out_dev ? reinterpret_cast<uint8_t *>(uintptr_t(im.out_dev)) : rgb + im.rs_off;
+    uint8_t *base = inner - ((uint64_t(im.fit_oy) * im.out_row_pitch + uint64_t(im.fit_ox) * k) << lg);
+    const uint32_t rowlen = W * k, in0 = im.fit_ox * k, in1 = (im.fit_ox + im.rs_w) * k;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t r = blockIdx.x * kFitPadRows + wave; r < min(nrows, (blockIdx.x + 1u) * kFitPadRows); r += 4u) {
+        const uint32_t p = r / H, y = r - p * H;
+        uint8_t *row = base + ((uint64_t(p) * im.out_plane_pitch + uint64_t(y) * im.out_row_pitch) << lg);
+        const bool crosses = y >= im.fit_oy && y - im.fit_oy < im.rs_h;
+        fit_pad_run(row, 0u, crosses ? in0 : rowlen, lg, il, p, pv, lane);
+        if (crosses) fit_pad_run(row, in1, rowlen, lg, il, p, pv, lane);
+    }
+}
+
 // ---- libjpeg's pixels (mjx_opts.pixels; DevImage::lj_on): component planes -> the picture ------------------------------------------
 // Behind stage B's plane form.  A workgroup owns kLjTileW x kLjTileH pixels of the picture's rectangle, a wave a row at a time (four
 // rows each), a lane kLjStrip = 8 adjacent pixels: per component one or two aligned 8-byte reads, or an aligned 4-byte read and two
@@ -5365,6 +5445,12 @@ void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, con
                                  dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
     else hipLaunchKernelGGL(filter == kFilterBicubic ? k_resize_orient_cubic : filter == kFilterNearest ? k_resize_orient_nearest : k_resize_orient,
                             dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
+}
+
+void launch_fit_pad(hipStream_t st, uint32_t max_wgs, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags)
+{
+    if (max_wgs == 0 || nimg == 0) return;
+    hipLaunchKernelGGL(k_fit_pad, dim3(max_wgs, nimg), dim3(256), 0, st, images, rgb, img_flags);
 }
 
 void launch_upsample_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,

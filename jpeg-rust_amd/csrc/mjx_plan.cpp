@@ -549,7 +549,9 @@ int plan_output(ImagePlan &p, const mjx_output *out, size_t i)
         p.out_scale[c] = out->dtype == MJX_DTYPE_U8 ? 1.f : out->scale[c];
         p.out_bias[c] = out->dtype == MJX_DTYPE_U8 ? 0.f : out->bias[c];
     }
-    const uint64_t w = p.rs_on ? p.rs_w : p.roi_w, h = p.rs_on ? p.rs_h : p.roi_h, row_min = planar || luma ? w : 3 * w;      // (a resized picture: the target)
+    const uint64_t w = p.rs_on ? p.fit_w : p.roi_w, h = p.rs_on ? p.fit_h : p.roi_h, row_min = planar || luma ? w : 3 * w;      // (a resized picture: the target)
+    for (int c = 0; c < 3; c++)                                          // (the pad colour: the three bytes in front of dst, mjx.h; MJX_FIT_CONTAIN only)
+        p.pad[c] = p.rs_on && p.fit_mode == kFitContain ? reinterpret_cast<const uint8_t *>(out)[MJX_OUTPUT_PAD_OFFSET + c] : uint8_t(0);
     p.out_row_pitch = row_min;
     p.out_plane_pitch = planar ? h * w : 0;
     if (out->dst) {
@@ -684,7 +686,7 @@ static void fail_input(std::vector<ImagePlan> &plans, size_t first, int rc)
 
 int resize_opts(uint32_t width, uint32_t height, const mjx_opts &opts_i, const mjx_resize &rs, mjx_opts &eff, mjx_rect &rect)
 {
-    eff = opts_i;
+    std::memcpy(&eff, &opts_i, sizeof eff);                                // (byte for byte, as above)
     if (!rs.width || !rs.height || rs.width > kResizeMaxDim || rs.height > kResizeMaxDim) return MJX_ERR_INVALID_ARG;
     if (opts_i.layout == MJX_LAYOUT_REF_COMPAT) return MJX_ERR_INVALID_ARG;
     if (!rs.auto_scale) return MJX_OK;
@@ -719,18 +721,46 @@ void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_ou
         return;
     }
     const size_t first = plans.size();
-    mjx_opts eff = opts_i;
-    mjx_rect rect{0, 0, 0, 0}, stored{0, 0, 0, 0};
+    mjx_rect rect{0, 0, 0, 0}, stored{0, 0, 0, 0}, cover{0, 0, 0, 0};
     int rc = MJX_OK;
     mjx_resize rs_s{};                                                     // the resize in S's axes
     if (rs) rs_s = *rs;
+    // fit modes (the byte is read from the caller's object, as the filter byte below).  A: the rectangle asked for, in D's coordinates at
+    // the scale it is given in.  MJX_FIT_COVER: the picture is the stretch call's with rois[0] = A' -- everything below sees that
+    // rectangle; MJX_FIT_CONTAIN: the stretch call's with the target iw x ih, moved to (ox, oy) of the target once it is planned.  A
+    // rectangle or a target the checks below refuse is left to them.
+    const uint32_t fit = rs ? MJX_RESIZE_FIT(rs) : kFitStretch;
+    FitPlan fp{};
+    bool fit_known = false;
+    mjx_opts opts_f;                                                       // (byte for byte: the colour option lives outside the declared members)
+    std::memcpy(&opts_f, &opts_i, sizeof opts_f);
+    if (rs && fit < kFitCount && rs->width && rs->height && rs->width <= kResizeMaxDim && rs->height <= kResizeMaxDim) {
+        const uint32_t s = rs->auto_scale ? 1u : opts_i.scale_denom > 1 ? opts_i.scale_denom : 1u;
+        const uint32_t w = (d.width + s - 1) / s, h = (d.height + s - 1) / s;
+        const bool sw = orient_valid(code) && orient_swaps(code);
+        const uint32_t dw = sw ? h : w, dh = sw ? w : h;
+        mjx_rect a{0, 0, dw, dh};
+        const bool given = opts_i.rois && opts_i.n_rois && (opts_i.rois[0].w || opts_i.rois[0].h);
+        if (given) a = opts_i.rois[0];
+        if ((s == 1 || s == 2 || s == 4 || s == 8) && a.w && a.h && a.x < dw && a.y < dh && a.w <= dw - a.x && a.h <= dh - a.y) {
+            fp = fit_rule(fit, a.x, a.y, a.w, a.h, rs->width, rs->height);
+            fit_known = true;
+            if (fit == kFitCover && (fp.a.w != a.w || fp.a.h != a.h)) {
+                cover = mjx_rect{fp.a.x, fp.a.y, fp.a.w, fp.a.h};
+                opts_f.rois = &cover; opts_f.n_rois = 1;
+            }
+            if (fit == kFitContain) { rs_s.width = fp.inner.w; rs_s.height = fp.inner.h; }
+        }
+    }
+    mjx_opts eff;
+    std::memcpy(&eff, &opts_f, sizeof eff);
     if (code != 1) {
         // orientation: the rectangle is D's; back to S at the scale it is given in (full size with auto_scale)
-        const uint32_t s = rs && rs->auto_scale ? 1u : opts_i.scale_denom > 1 ? opts_i.scale_denom : 1u;
+        const uint32_t s = rs && rs->auto_scale ? 1u : opts_f.scale_denom > 1 ? opts_f.scale_denom : 1u;
         const uint32_t w = (d.width + s - 1) / s, h = (d.height + s - 1) / s;
-        if (!orient_valid(code) || opts_i.layout == MJX_LAYOUT_REF_COMPAT) rc = MJX_ERR_INVALID_ARG;
-        else if (w && h && (s == 1 || s == 2 || s == 4 || s == 8) && opts_i.rois && opts_i.n_rois && (opts_i.rois[0].w || opts_i.rois[0].h)) {
-            const mjx_rect &r = opts_i.rois[0];
+        if (!orient_valid(code) || opts_f.layout == MJX_LAYOUT_REF_COMPAT) rc = MJX_ERR_INVALID_ARG;
+        else if (w && h && (s == 1 || s == 2 || s == 4 || s == 8) && opts_f.rois && opts_f.n_rois && (opts_f.rois[0].w || opts_f.rois[0].h)) {
+            const mjx_rect &r = opts_f.rois[0];
             const OrientMap m = orient_map(code, w, h);
             if (!r.w || !r.h || r.x >= m.dw || r.y >= m.dh || r.w > m.dw - r.x || r.h > m.dh - r.y) rc = MJX_ERR_INVALID_ARG;
             else {
@@ -741,9 +771,10 @@ void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_ou
         if (orient_swaps(code)) std::swap(rs_s.width, rs_s.height);
     }
     // (the filter byte is read from the caller's object: rs_s is a member-wise copy and need not carry it)
-    if (rs && MJX_RESIZE_FILTER(rs) >= kFilterCount) rc = MJX_ERR_INVALID_ARG;
+    if (rs && (MJX_RESIZE_FILTER(rs) >= kFilterCount || fit >= kFitCount)) rc = MJX_ERR_INVALID_ARG;
     if (rs && rc == MJX_OK) {
-        const mjx_opts in = eff;
+        mjx_opts in;
+        std::memcpy(&in, &eff, sizeof in);
         rc = resize_opts(d.width, d.height, in, rs_s, eff, rect);
     }
     if (rc != MJX_OK && code != 1) { eff.rois = nullptr; eff.n_rois = 0; }  // (the rectangle is D's: the picture's own fault, which comes first, is found on the whole picture)
@@ -757,6 +788,12 @@ void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_ou
     else {
         p.or_copy = true;
         p.rs_w = orient_swaps(code) ? p.roi_h : p.roi_w; p.rs_h = orient_swaps(code) ? p.roi_w : p.roi_h; p.rs_aa = 0; p.rs_filter = 0;
+    }
+    p.fit_mode = fit;
+    p.fit_w = p.rs_w; p.fit_h = p.rs_h;                                    // the picture that leaves: what plan_output lays out
+    if (fit_known) {
+        p.fit_ax = fp.a.x; p.fit_ay = fp.a.y; p.fit_aw = fp.a.w; p.fit_ah = fp.a.h;
+        if (fit == kFitContain) { p.rs_w = fp.inner.w; p.rs_h = fp.inner.h; p.fit_ox = fp.inner.x; p.fit_oy = fp.inner.y; }
     }
     static const mjx_output packed = {MJX_DTYPE_U8, 0, 0, {1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}, nullptr, 0};
     plan_output_of_input(plans, out ? out : &packed, i);

@@ -74,6 +74,14 @@ struct ImagePlan {
     bool rs_on = false;
     uint32_t rs_w = 0, rs_h = 0, rs_aa = 0;
     uint32_t rs_filter = 0;                // MJX_RESIZE_FILTER of the description: 0 triangle, 1 bicubic, 2 nearest
+    // fit modes (MJX_RESIZE_FIT of the description, fit_rule): fit_w x fit_h is the picture that leaves -- rs_w x rs_h unless the mode
+    // is MJX_FIT_CONTAIN, where rs_w x rs_h is the inner rectangle at (fit_ox, fit_oy) of the fit_w x fit_h target and out_* describe
+    // the target.  pad: the three pad bytes of the output description, by OUTPUT channel (read for MJX_FIT_CONTAIN only).  MJX_FIT_COVER
+    // only rewrites the rectangle the picture is planned with.  fit_ax .. fit_ah: the rectangle asked for (A' for MJX_FIT_COVER) in the
+    // coordinates of the picture that leaves, as mjx_resize_fit_plan reports it.
+    uint32_t fit_mode = 0, fit_w = 0, fit_h = 0, fit_ox = 0, fit_oy = 0;
+    uint32_t fit_ax = 0, fit_ay = 0, fit_aw = 0, fit_ah = 0;
+    uint8_t pad[3] = {0, 0, 0};
     // orientation on the device (mjx_orient, plan_input_for): orient = the EXIF code 2 .. 8 of a picture that leaves as orient_c(S), S
     // the packed intermediate as above (rs_on is set either way: the pool, the output's rules and the accessors are the resize's).
     // or_copy: there is no resize, rs_w x rs_h is the oriented size of roi_w x roi_h and k_orient_out copies.  Code 1 leaves no trace.

@@ -12,11 +12,17 @@ mean / std, in ONE caller-owned 2048 x 3 x 224 x 224 tensor:
 Caller-owned destinations cannot be tiled, so every variant builds its batch from the 2048 inputs themselves (the 64 scans, each
 named 32 times).  The variants take turns inside every repeat.
 
+--fit: the fit mode of the library's variants (mjx_resize's fit byte) -- stretch, cover (centre-crop) or contain (letterbox, padded
+with the mean colour's bytes); a comma-separated list runs every mode of it for a_auto and b_scale1, the modes taking turns inside
+every repeat like the variants (a result is then named variant:mode).  With contain in the list the tool also times, in every
+repeat, a hipMemsetAsync of the batch's whole output tensor on the null stream to a device synchronise (memset_ms_all) and writes
+the comparison the mode is held to beside the figures: every contain step <= the stretch step of the same repeat + that memset.
+
 Per variant: ms per step (every repeat, best, median), per-class kernel ms per step (idct_color is stage B, resize is
 k_resize_out), the bytes written, the scales auto_scale chose.  One JSON object on the last line.
 
     python tools/bench_resize.py [--steps 5] [--warmup 1] [--repeats 3] [--images 2048] [--variants a_auto,b_scale1,c_torch]
-                                 [--filter bilinear|bicubic|nearest]
+                                 [--filter bilinear|bicubic|nearest] [--fit stretch,cover,contain]
 """
 import argparse
 import json
@@ -62,7 +68,10 @@ def main():
     ap.add_argument("--side", type=int, default=224)
     ap.add_argument("--variants", default="a_auto,b_scale1,c_torch")
     ap.add_argument("--filter", default="bilinear", choices=("bilinear", "bicubic", "nearest"))
+    ap.add_argument("--fit", default="stretch", help="stretch, cover, contain, or a comma-separated list of them")
     args = ap.parse_args()
+    fits = [f for f in args.fit.split(",") if f]
+    assert fits and all(f in ("stretch", "cover", "contain") for f in fits), "--fit: stretch, cover, contain"
     import torch                         # (first: libmjx.so must find torch's HIP runtime already loaded, as in bench.py)
     import torch.nn.functional as F
     import __graft_entry__ as ge
@@ -75,7 +84,11 @@ def main():
     reps = max(1, args.images // args.unique)
     n = reps * args.unique
     rects = random_resized_crops(n, W, H, seed=224)
-    names = [v for v in args.variants.split(",") if v]
+    base_names = [v for v in args.variants.split(",") if v]
+    # (a library variant per fit mode: the plain name for a single mode, variant:mode for a list)
+    names = [v if v == "c_torch" or len(fits) == 1 else "%s:%s" % (v, f) for v in base_names for f in (fits if v != "c_torch" else fits[:1])]
+    fit_of = {(v if v == "c_torch" or len(fits) == 1 else "%s:%s" % (v, f)): f for v in base_names for f in (fits if v != "c_torch" else fits[:1])}
+    pad = tuple(int(round(255 * m)) for m in MEAN)
     dev = torch.device("cuda", 0)
     ctx = mjx.Context(0, profiling=True, throughput_plan=True)
     scans = [mjx.ParsedScan(d) for d in datas]
@@ -84,8 +97,26 @@ def main():
     bi_t = torch.tensor([-m / s for m, s in zip(MEAN, STD)], dtype=torch.float32, device=dev).view(1, 3, 1, 1)
     runs = {v: [] for v in names}
     scales = {}
+    memset_ms = []
+    import ctypes
+    hip = mjx.lib()                      # (the HIP runtime the library itself is linked against)
+    hip.hipMemsetAsync.restype = hip.hipDeviceSynchronize.restype = ctypes.c_int
+    hip.hipMemsetAsync.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    hip.hipDeviceSynchronize.argtypes = []
     for r in range(args.repeats):
         order = names[r % len(names):] + names[:r % len(names)]
+        if "contain" in fits:            # the second term of contain's bar: clearing the batch's whole output, this repeat
+            tensor = torch.empty((n, 3, side, side), dtype=torch.float16, device=dev)
+            torch.cuda.synchronize()
+            nbytes = tensor.numel() * 2
+            assert hip.hipMemsetAsync(tensor.data_ptr(), 0, nbytes, None) == 0 and hip.hipDeviceSynchronize() == 0      # (warm)
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                assert hip.hipMemsetAsync(tensor.data_ptr(), 0, nbytes, None) == 0
+            assert hip.hipDeviceSynchronize() == 0
+            memset_ms.append(round(1e3 * (time.perf_counter() - t0) / args.steps, 4))
+            print("memset    repeat %d: %.3f ms per step (%d bytes)" % (r, memset_ms[-1], nbytes), flush=True)
+            del tensor
         for v in order:
             tensor = torch.empty((n, 3, side, side), dtype=torch.float16, device=dev)
             torch.cuda.synchronize()
@@ -112,9 +143,9 @@ def main():
                             x = F.interpolate(views[i].to(torch.float32), size=(side, side), mode=args.filter, align_corners=False, antialias=True)
                         tensor[i:i + 1].copy_(torch.addcmul(bi_t, x, sc_t))
             else:
-                fmt = mjx.Output("float16", planar=True, mean=MEAN, std=STD,
+                fmt = mjx.Output("float16", planar=True, mean=MEAN, std=STD, pad=pad,
                                  dst=[(tensor.data_ptr() + 2 * per * i, side, side, side, side * side) for i in range(n)])
-                b = mjx.Batch(ctx, inputs, rois=rects, output=fmt, resize=mjx.Resize(side, side, antialias=True, auto_scale=(v == "a_auto"), filter=args.filter))
+                b = mjx.Batch(ctx, inputs, rois=rects, output=fmt, resize=mjx.Resize(side, side, antialias=True, auto_scale=v.startswith("a_auto"), filter=args.filter, fit=fit_of[v]))
                 assert all(x == mjx.OK for x in b.create_status)
                 if v not in scales:
                     got = [b.scale(i) for i in range(n)]
@@ -147,7 +178,7 @@ def main():
             finally:
                 b.close()
                 del tensor
-    out = {"filter": args.filter, "images": n, "unique": args.unique, "picture": "%dx%d 4:2:0 q%d" % (W, H, args.quality), "target": side, "steps": args.steps,
+    out = {"filter": args.filter, "fit": fits, "images": n, "unique": args.unique, "picture": "%dx%d 4:2:0 q%d" % (W, H, args.quality), "target": side, "steps": args.steps,
            "repeats": args.repeats, "variants": {}}
     for v in names:
         best = min(runs[v], key=lambda x: x["ms_per_step"])
@@ -158,6 +189,14 @@ def main():
                               "stage_b_ms_all": [x["kernel_ms_per_step"].get("idct_color", 0.0) for x in runs[v]],
                               "resize_ms_all": [x["kernel_ms_per_step"].get("resize", 0.0) for x in runs[v]],
                               "bytes_written": best["bytes_written"], "scales": scales.get(v)}
+    if "contain" in fits:
+        out["memset_ms_all"] = memset_ms
+        for v in base_names:
+            if v == "c_torch" or "stretch" not in fits:
+                continue
+            st, co = out["variants"]["%s:stretch" % v]["all_ms_per_step"], out["variants"]["%s:contain" % v]["all_ms_per_step"]
+            out["contain_bar_%s" % v] = {"stretch_plus_memset": [round(a + m, 4) for a, m in zip(st, memset_ms)], "contain": co,
+                                         "every_repeat_within": all(c <= a + m for c, a, m in zip(co, st, memset_ms))}
     if "a_auto" in names and "c_torch" in names:
         out["bar1_every_repeat_of_a_below_the_best_of_c"] = max(out["variants"]["a_auto"]["all_ms_per_step"]) < out["variants"]["c_torch"]["ms_per_step_best"]
     for s in scans:
