@@ -55,7 +55,8 @@ enum {
                                      * can (34 880 bytes) do not, valid though the file is. */
     MJX_ERR_REF_PANIC = 5,          /* other input on which the reference panics (asserts, bad DQT precision ...) */
     MJX_ERR_DEVICE = 6,             /* HIP error / no device / kernels missing */
-    MJX_ERR_UNSUPPORTED_FORMAT = 7, /* non-baseline SOF, ncomp not in {1,3} (decoder.rs:328-330; {1,3,4} with MJX_COLOR_FILE), sampling > 2 */
+    MJX_ERR_UNSUPPORTED_FORMAT = 7, /* non-baseline SOF, ncomp not in {1,3} (decoder.rs:328-330; {1,3,4} with MJX_COLOR_FILE), a sampling factor other than 1, 2 or 4,
+                                       more than 12 blocks per MCU (10 with four components) */
     MJX_ERR_NO_SCAN = 8,            /* EOF without SOS: the reference returns image_data() == None */
     MJX_ERR_INVALID_ARG = 9,
     MJX_ERR_NOMEM = 10,
@@ -119,6 +120,9 @@ typedef struct mjx_opts {
                                (2, 2) t[i] = 3 near[i] + far[i] (near: the chroma row under the output row, far: the one above it for
                                       even output rows, below for odd), out[2i] = (3 t[i] + t[i-1] + 8) >> 4,
                                       out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4;
+                             a component with a ratio of 4 in EITHER direction is replicated in both, out[X][Y] = s[X / rh][Y / rv]
+                             (jdsample.c's int_upsample: libjpeg has no triangle filter at ratio 4, and picks replication for the
+                             whole component even where its other ratio is 2);
                              (no fall-back to replication for planes of one or two columns).  Colour is jdcolor.c's, FIX(x) =
                              int(x 65536 + 0.5), cb = Cb - 128, cr = Cr - 128: R = clamp(Y + ((FIX(1.40200) cr + 32768) >> 16)),
                              B = clamp(Y + ((FIX(1.77200) cb + 32768) >> 16)), G = clamp(Y + ((-FIX(0.34414) cb + 32768
@@ -423,6 +427,13 @@ typedef struct mjx_orient {
 } mjx_orient;
 
 /* ---- inner seam: what jpeg/mod.rs:388-415 hands to JPEGDecoder -------------------------- */
+/* Sampling factors: h and v are each 1, 2 or 4 -- 4:4:4, 4:2:2, 4:2:0, 4:4:0, 4:1:1 (Y 4x1), 4:1:0 (Y 4x2), their vertical forms and
+ * every mixed layout.  Three components: at most 12 blocks per MCU (sum of h v; T.81 B.2.3 says 10, files with 11 and 12 exist);
+ * four components (MJX_COLOR_FILE): at most 10; one component: any of the factors, the scan is non-interleaved and decodes as
+ * h = v = 1 in the STANDARD layout.  An MCU covers 8 hmax x 8 vmax pixels, up to 32 x 32; pixel (X, Y) takes sample
+ * (floor(X h / hmax), floor(Y v / vmax)) of each component (box replication).  A factor of 3, or above 4, is
+ * MJX_ERR_UNSUPPORTED_FORMAT: strips per MCU row and replication by shifts need powers of two, and the pixel forms hold 32 x 32.
+ * The reference asserts 1 or 2 (mod.rs:275-277): strict_ref and MJX_LAYOUT_REF_COMPAT answer a 4 with MJX_ERR_REF_PANIC. */
 typedef struct mjx_comp {          /* decoder.rs:39-52 JPEGDecoderComponentFields */
     uint8_t id, h, v, tq, td, ta;
 } mjx_comp;
@@ -625,13 +636,13 @@ int mjx_resize_weights(uint32_t n_in, uint32_t n_out, int antialias, uint32_t X,
 int mjx_resize_filter_weights(uint32_t n_in, uint32_t n_out, int filter, int antialias, uint32_t X, uint32_t *first, float *weights,
                               size_t cap, size_t *count);
 /* Host-only: MJX_PIXELS_LIBJPEG's upsampling and colour step on the CPU -- the routines k_upsample_color itself runs (lj_strip8 /
- * lj_color, mjx_kernels.h).  ncomp (1 or 3) dense planes of cw[c] x ch[c] samples, upsampled by rh[c], rv[c] (each 1 or 2); rgb receives
+ * lj_color, mjx_kernels.h).  ncomp (1 or 3) dense planes of cw[c] x ch[c] samples, upsampled by rh[c], rv[c] (each 1, 2 or 4); rgb receives
  * the rectangle's rect->w x rect->h pixels, packed R,G,B.  The rectangle must lie inside every upsampled plane (cw[c] rh[c] x
  * ch[c] rv[c]); the plane of an odd picture is one sample short of the picture's size, which the rule allows. */
 int mjx_upsample_color_host(const uint8_t *const *planes, const uint32_t *cw, const uint32_t *ch, const uint8_t *rh, const uint8_t *rv,
                             uint32_t ncomp, const mjx_rect *rect, uint8_t *rgb);
 /* Host-only: MJX_PIXELS_LIBJPEG's luminance picture (MJX_OUTPUT_CHANNELS == 1) on the CPU -- the routine k_upsample_luma itself runs
- * (lj_luma8, mjx_kernels.h).  One dense plane of cw x ch samples, upsampled by rh, rv (each 1 or 2; 1, 1: the plane itself); out receives
+ * (lj_luma8, mjx_kernels.h).  One dense plane of cw x ch samples, upsampled by rh, rv (each 1, 2 or 4; 1, 1: the plane itself); out receives
  * the rectangle's rect->w x rect->h bytes.  The rectangle must lie inside the upsampled plane. */
 int mjx_upsample_luma_host(const uint8_t *plane, uint32_t cw, uint32_t ch, uint8_t rh, uint8_t rv, const mjx_rect *rect, uint8_t *out);
 

@@ -36,7 +36,7 @@ MODEL_NAMES = ["grey", "ycbcr", "rgb", "cmyk", "ycck"]
 ABI_VERSION = 2                  # mjx.h: MJX_ABI_VERSION, the layout the structures below mirror (mjx_version() prints the library's)
 STAGE_ENTROPY, STAGE_PIXELS, STAGE_ALL = 1, 2, 3
 KERNEL_NAMES = ["gather", "huff_sync", "huff_fix", "huff_scan", "huff_write", "dc_scan", "idct_color", "upload", "huff_emit", "huff_prefix", "resize"]
-SUBSAMPLING = {"444": 0, "422": 1, "420": 2, "gray": 3, "440": 4}
+SUBSAMPLING = {"444": 0, "422": 1, "420": 2, "gray": 3, "440": 4, "411": 5, "410": 6}
 
 
 class MjxError(RuntimeError):
@@ -604,7 +604,7 @@ def resize_weights(n_in, n_out, antialias, X, filter="bilinear"):
 
 def upsample_color_host(planes, rh, rv, rect):
     """mjx_upsample_color_host (host only; the routines k_upsample_color runs): one or three uint8 planes [ch, cw], their upsampling
-    ratios rh[c], rv[c] (1 or 2) and a rectangle (x, y, w, h) of the upsampled picture -> ndarray [h, w, 3] uint8, the "libjpeg"
+    ratios rh[c], rv[c] (1, 2 or 4) and a rectangle (x, y, w, h) of the upsampled picture -> ndarray [h, w, 3] uint8, the "libjpeg"
     pixels of that rectangle."""
     n = len(planes)
     pl = [np.ascontiguousarray(q, np.uint8) for q in planes]
@@ -621,7 +621,7 @@ def upsample_color_host(planes, rh, rv, rect):
 
 
 def upsample_luma_host(plane, rh, rv, rect):
-    """mjx_upsample_luma_host (host only; the routine k_upsample_luma runs): one uint8 plane [ch, cw], its upsampling ratios (1 or 2)
+    """mjx_upsample_luma_host (host only; the routine k_upsample_luma runs): one uint8 plane [ch, cw], its upsampling ratios (1, 2 or 4)
     and a rectangle (x, y, w, h) of the upsampled plane -> ndarray [h, w] uint8, the "libjpeg" luminance of that rectangle."""
     pl = np.ascontiguousarray(plane, np.uint8)
     x, y, w, h = (int(v) for v in rect)

@@ -2201,7 +2201,7 @@ extern "C" int mjx_upsample_color_host(const uint8_t *const *planes, const uint3
     std::vector<std::vector<uint64_t>> store(ncomp);
     LjPlane pl[3];
     for (uint32_t c = 0; c < ncomp; c++) {
-        if (!planes[c] || !cw[c] || !ch[c] || cw[c] > kResizeMaxDim || ch[c] > kResizeMaxDim || rh[c] < 1 || rh[c] > 2 || rv[c] < 1 || rv[c] > 2) return MJX_ERR_INVALID_ARG;
+        if (!planes[c] || !cw[c] || !ch[c] || cw[c] > kResizeMaxDim || ch[c] > kResizeMaxDim || !sampling_factor_ok(rh[c]) || !sampling_factor_ok(rv[c])) return MJX_ERR_INVALID_ARG;
         if ((rect->x + rect->w - 1) / rh[c] >= cw[c] || (rect->y + rect->h - 1) / rv[c] >= ch[c]) return MJX_ERR_INVALID_ARG;
         const uint32_t stride = (cw[c] + 7u) & ~7u;
         store[c].assign(size_t(stride) / 8 * ch[c], 0xa5a5a5a5a5a5a5a5ull);
@@ -2230,7 +2230,7 @@ extern "C" int mjx_upsample_luma_host(const uint8_t *plane, uint32_t cw, uint32_
 {
     return guarded([&]() -> int {
     if (!plane || !rect || !out || !rect->w || !rect->h || !cw || !ch || cw > kResizeMaxDim || ch > kResizeMaxDim) return MJX_ERR_INVALID_ARG;
-    if (rh < 1 || rh > 2 || rv < 1 || rv > 2) return MJX_ERR_INVALID_ARG;
+    if (!sampling_factor_ok(rh) || !sampling_factor_ok(rv)) return MJX_ERR_INVALID_ARG;
     if (rect->x > kResizeMaxDim || rect->y > kResizeMaxDim || rect->w > kResizeMaxDim || rect->h > kResizeMaxDim) return MJX_ERR_INVALID_ARG;
     if ((rect->x + rect->w - 1) / rh >= cw || (rect->y + rect->h - 1) / rv >= ch) return MJX_ERR_INVALID_ARG;
     const uint32_t stride = (cw + 7u) & ~7u;

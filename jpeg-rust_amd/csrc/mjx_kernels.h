@@ -229,6 +229,12 @@ enum OrientPass : uint32_t {
     kOrResizeLuma = 4,      // k_resize_luma (any orientation code, 1 included)
 };
 
+// Sampling factors: 1, 2 or 4 in each direction (include/mjx.h).  Strips per MCU row, lane -> (MCU, strip) and the replication of a
+// subsampled component are all shifts, so a factor -- and with it every ratio hmax / h_c -- is a power of two; ratio_shift is its
+// log2, 0, 1 or 2 (hmax a multiple of hc: the planner checks).
+MJX_HD constexpr bool sampling_factor_ok(uint32_t f) { return f == 1u || f == 2u || f == 4u; }
+MJX_HD constexpr uint32_t ratio_shift(uint32_t fmax, uint32_t fc) { return fmax >= 4u * fc ? 2u : fmax >= 2u * fc ? 1u : 0u; }
+
 // YCbCr output: the samples of component c -- factors (hc, vc) of maxima (hmax, vmax) -- that the rectangle (x, y, w, h) of the
 // out_w x out_h picture covers: columns floor(x hc / hmax) .. ceil((x + w) hc / hmax), rows likewise.  These are the samples the
 // packed decode of the rectangle reads from the component (box replication: pixel X takes sample floor(X hc / hmax)); the whole
@@ -311,7 +317,7 @@ MJX_HD uint32_t orient_tiles(uint32_t w, uint32_t h) { return ((w + kOrientTile 
 // ---- libjpeg's pixels (mjx_opts.pixels = MJX_PIXELS_LIBJPEG): fancy upsampling and jdcolor.c's integer colour step ---------------
 // A component plane: cw x ch samples in rows of `stride` bytes; s and stride are multiples of 8 and stride >= cw rounded up to 8, so
 // that the aligned 4- and 8-byte reads below stay inside a row (what they bring in from behind cw is never used: indices clamp to
-// the plane's edge).  rh, rv: the upsampling ratios, 1 or 2.  k_upsample_color and the host (mjx_upsample_color_host) run these
+// the plane's edge).  rh, rv: the upsampling ratios, 1, 2 or 4.  k_upsample_color and the host (mjx_upsample_color_host) run these
 // routines; a lane makes 8 adjacent pixels of one output row.
 struct LjPlane { const uint8_t *s; uint32_t stride, cw, ch, rh, rv; };
 constexpr uint32_t kLjStrip = 8;                               // pixels a lane makes
@@ -353,8 +359,26 @@ MJX_UNROLL
 //   (1, 1) the sample; (2, 1) out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2; (1, 2) the same down the
 //   columns, bias 1 for the upper output row and 2 for the lower; (2, 2) t[i] = 3 near[i] + far[i], out[2i] = (3 t[i] + t[i-1] + 8) >> 4,
 //   out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4 -- jdsample.c's h2v1 / h2v2 fancy upsampling with edge replication.
+// A component with a ratio of 4 in EITHER direction is replicated in both -- out[k] = s[(X0 + k) / rh] of row Y / rv, jdsample.c's
+// int_upsample, which libjpeg picks for every ratio pair that is not one of the four above; there is no triangle filter at ratio 4.
 MJX_HD void lj_strip8(const LjPlane &p, uint32_t X0, uint32_t Y, int32_t out[8])
 {
+    if (p.rh == 4u || p.rv == 4u) {
+        const uint8_t *row = p.s + size_t(Y >> ratio_shift(p.rv, 1u)) * p.stride;
+        if (p.rh == 1u) {
+            lj_row8(row, X0, out);
+        } else if (p.rh == 2u) {
+            const uint32_t a = lj_ld32(row + (X0 >> 1));                   // (X0 / 2 is a multiple of 4: inside the row)
+MJX_UNROLL
+            for (uint32_t k = 0; k < 8; k++) out[k] = int32_t((a >> (8 * (k >> 1))) & 0xffu);
+        } else {
+            const uint32_t i = X0 >> 2;                                    // (a multiple of 2, below cw; the row holds a multiple of 8)
+            const int32_t s0 = int32_t(row[i]), s1 = int32_t(row[i + 1u]);
+MJX_UNROLL
+            for (uint32_t k = 0; k < 8; k++) out[k] = k < 4 ? s0 : s1;
+        }
+        return;
+    }
     const uint32_t j = p.rv == 2u ? Y >> 1 : Y;
     uint32_t jf = j;                                               // the far row: above for even output rows, below for odd, clamped
     if (p.rv == 2u) jf = (Y & 1u) ? (j + 1u < p.ch ? j + 1u : j) : (j ? j - 1u : 0u);

@@ -3387,7 +3387,7 @@ __device__ __forceinline__ void idct_row_inplace(float *rowf)
 
 // Reads 4 horizontally adjacent samples of one component for the pixel strip starting at MCU-local (x, y);
 // replicates when the component is subsampled (box replication: the reference never interpolates).
-// Sampling ratios are 1 or 2 (jpeg/mod.rs:275-277), so the divisions are shifts.
+// Sampling ratios are 1, 2 or 4 (the reference stops at 2, jpeg/mod.rs:275-277), so the divisions are shifts.
 // What the generic pixel phase needs of the picture's sampling layout, read ONCE per workgroup into registers: read through the
 // descriptor inside the row loop, every field was fetched again after every store to the picture (a byte pointer may alias
 // anything) -- the pixel phase of a 4:2:2 tile took 30.7 k cycles per wave where the 4:2:0 form takes 9.1 k for twice the pixels
@@ -3402,8 +3402,8 @@ __device__ __forceinline__ GenShape gen_shape(const DevImage &im)
 {
     GenShape g;
     for (uint32_t c = 0; c < 4; c++) {
-        g.xsh[c] = im.hmax > im.ch[c] ? 1 : 0;
-        g.ysh[c] = im.vmax > im.cv[c] ? 1 : 0;
+        g.xsh[c] = ratio_shift(im.hmax, im.ch[c]);
+        g.ysh[c] = ratio_shift(im.vmax, im.cv[c]);
         g.first[c] = im.cfirst[c];
         g.ch[c] = im.ch[c];
     }
@@ -3421,9 +3421,12 @@ __device__ __forceinline__ void load4(const float *tile, const GenShape &g, uint
     if (!g.xsh[c]) {
         const float4 v = *reinterpret_cast<const float4 *>(p);
         out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
-    } else {
+    } else if (g.xsh[c] == 1u) {
         const float2 v = *reinterpret_cast<const float2 *>(p);
         out[0] = v.x; out[1] = v.x; out[2] = v.y; out[3] = v.y;
+    } else {                               // ratio 4: one sample serves the strip (the four lanes that share a word read one address: a broadcast)
+        const float v = *p;
+        out[0] = v; out[1] = v; out[2] = v; out[3] = v;
     }
 }
 
@@ -3645,7 +3648,7 @@ __device__ __forceinline__ void pixels_generic_t(const GenShape &g, const float 
     static_assert(!ROI || !INTERIOR, "strips of a cropped picture are cut at the rectangle's edges");
     static_assert(!MODEL || (COLOUR && !INTERIOR), "the colour models ride on the colour form with bounds");
     const uint32_t tid = threadIdx.x, bpm = g.bpm;
-    const uint32_t lstrips = g.hmax == 2 ? 2u : 1u;          // log2 of the 4-pixel strips per MCU row (2*hmax)
+    const uint32_t lstrips = g.hmax == 4 ? 3u : g.hmax == 2 ? 2u : 1u;          // log2 of the 4-pixel strips per MCU row (2*hmax)
     const uint32_t R = (1u << g.log2_tile) << lstrips;       // strips per pixel row of the tile (power of two <= 256)
     const uint32_t q = tid & (R - 1);
     const uint32_t t = q >> lstrips, sx = q & ((1u << lstrips) - 1);
@@ -3699,7 +3702,7 @@ __device__ __forceinline__ void pixels_generic_t(const GenShape &g, const float 
 __device__ __forceinline__ void pixels_generic_luma(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm, const Roi &roi, const OutFmt &of)
 {
     const uint32_t tid = threadIdx.x, bpm = g.bpm;
-    const uint32_t lstrips = g.hmax == 2 ? 2u : 1u;
+    const uint32_t lstrips = g.hmax == 4 ? 3u : g.hmax == 2 ? 2u : 1u;
     const uint32_t R = (1u << g.log2_tile) << lstrips;
     const uint32_t q = tid & (R - 1);
     const uint32_t t = q >> lstrips, sx = q & ((1u << lstrips) - 1);
@@ -4095,7 +4098,7 @@ __device__ __forceinline__ void pixels_scaled(const GenShape &g, const float *ti
 {
     static_assert(!OUT || ROI, "the output formats are built on the cropped forms");
     const uint32_t PW = N * g.hmax, PH = N * g.vmax, SW = PW < 4u ? PW : 4u;
-    const uint32_t lspr = PW / SW == 2u ? 1u : 0u, lph = 31u - __builtin_clz(PH);
+    const uint32_t lspr = PW / SW == 4u ? 2u : PW / SW == 2u ? 1u : 0u, lph = 31u - __builtin_clz(PH);        // (PW = N hmax reaches 16: 1, 2 or 4 strips per patch row)
     const uint32_t items = nm << (lph + lspr);
     const bool al = aligned && SW == 4u;
     for (uint32_t i = threadIdx.x; i < items; i += 256u) {
@@ -4149,7 +4152,7 @@ template <uint32_t N>
 __device__ __forceinline__ void pixels_scaled_luma(const GenShape &g, const float *tile, uint32_t m0, uint32_t nm, const Roi &roi, const OutFmt &of)
 {
     const uint32_t PW = N * g.hmax, PH = N * g.vmax, SW = PW < 4u ? PW : 4u;
-    const uint32_t lspr = PW / SW == 2u ? 1u : 0u, lph = 31u - __builtin_clz(PH);
+    const uint32_t lspr = PW / SW == 4u ? 2u : PW / SW == 2u ? 1u : 0u, lph = 31u - __builtin_clz(PH);        // (PW = N hmax reaches 16: 1, 2 or 4 strips per patch row)
     const uint32_t items = nm << (lph + lspr);
     for (uint32_t i = threadIdx.x; i < items; i += 256u) {
         const uint32_t t = i >> (lph + lspr), r = (i >> lspr) & (PH - 1u), sx = i & ((1u << lspr) - 1u);
@@ -4578,7 +4581,7 @@ __device__ __forceinline__ void dc_color_body(const DevImage *__restrict__ image
 #pragma unroll
     for (uint32_t c = 0; c < 4; c++) {
         if (c >= im.ncomp) break;
-        const uint32_t bx = hmax > im.ch[c] ? lx >> 1 : lx, by = vmax > im.cv[c] ? ly >> 1 : ly;
+        const uint32_t bx = lx >> ratio_shift(hmax, im.ch[c]), by = ly >> ratio_shift(vmax, im.cv[c]);
         const uint32_t k = im.cfirst[c] + by * im.ch[c] + bx;
         int32_t dc = 0;
         if (im.planar) {
@@ -4651,7 +4654,7 @@ extern "C" __global__ __launch_bounds__(256) void k_dc_color_luma(const DevImage
     const uint32_t X = col + im.roi_x, Y = row + im.roi_y;
     const uint32_t hmax = im.hmax, vmax = im.vmax;
     const uint32_t mx = X / hmax, my = Y / vmax, lx = X - mx * hmax, ly = Y - my * vmax;
-    const uint32_t bx = hmax > im.ch[0] ? lx >> 1 : lx, by = vmax > im.cv[0] ? ly >> 1 : ly;
+    const uint32_t bx = lx >> ratio_shift(hmax, im.ch[0]), by = ly >> ratio_shift(vmax, im.cv[0]);
     const uint32_t k = im.cfirst[0] + by * im.ch[0] + bx;
     int32_t dc = 0;
     if (im.planar) {

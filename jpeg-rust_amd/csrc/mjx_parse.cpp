@@ -126,8 +126,10 @@ void read_sof0(const ByteView &f, size_t pos, ParserState &st, bool strict)     
     size_t idx = pos + 6;
     for (unsigned c = 0; c < n; c++, idx += 3) {
         FrameComp fc{f.at(idx), uint8_t(f.at(idx + 1) >> 4), uint8_t(f.at(idx + 1) & 15), f.at(idx + 2)};
-        if (fc.h < 1 || fc.h > 2 || fc.v < 1 || fc.v > 2)                        // asserts :275-277
-            throw ParseError{strict ? MJX_ERR_REF_PANIC : MJX_ERR_UNSUPPORTED_FORMAT};
+        // the reference asserts 1 or 2 (:275-277); the library takes 1, 2 and 4 (include/mjx.h: powers of two up to 4)
+        const bool ref_ok = fc.h >= 1 && fc.h <= 2 && fc.v >= 1 && fc.v <= 2;
+        if (strict && !ref_ok) throw ParseError{MJX_ERR_REF_PANIC};
+        if (!mjx::sampling_factor_ok(fc.h) || !mjx::sampling_factor_ok(fc.v)) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};
         st.frame.push_back(fc);
     }
     st.have_frame = true;

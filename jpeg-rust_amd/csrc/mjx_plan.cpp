@@ -227,7 +227,10 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     auto comp_of = [&d](uint32_t c) -> const mjx_comp & { return c < 3 ? d.comp[c] : d.comp_fourth; };
     for (uint32_t c = 0; c < p.ncomp; c++) {
         const mjx_comp &k = comp_of(c);
-        if (k.h < 1 || k.h > 2 || k.v < 1 || k.v > 2) return fail(MJX_ERR_UNSUPPORTED_FORMAT);   // mod.rs:275-277
+        // factors of 1, 2 and 4 (a 3 or anything above 4: not a power of two, or beyond the 32 x 32 MCU the pixel forms hold); the
+        // reference asserts 1 or 2 (mod.rs:275-277), so its own modes answer a 4 as it does
+        if (!sampling_factor_ok(k.h) || !sampling_factor_ok(k.v)) return fail(MJX_ERR_UNSUPPORTED_FORMAT);
+        if ((k.h > 2 || k.v > 2) && (opts.layout == MJX_LAYOUT_REF_COMPAT || opts.strict_ref)) return fail(MJX_ERR_REF_PANIC);
         if (k.tq > 3 || !(d.qt_present & (1u << k.tq))) return fail(MJX_ERR_MISSING_TABLE);      // decoder.rs:222-225
         if (!gather && (k.td > 3 || !(d.dc_present & (1u << k.td)))) return fail(MJX_ERR_MISSING_TABLE);      // decoder.rs:158-160
         if (!gather && (k.ta > 3 || !(d.ac_present & (1u << k.ta)))) return fail(MJX_ERR_MISSING_TABLE);      // decoder.rs:154-156
@@ -246,10 +249,10 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     for (uint32_t c = 0; c < p.ncomp; c++)
         if (p.hmax % p.h[c] || p.vmax % p.v[c]) return fail(MJX_ERR_UNSUPPORTED_FORMAT);
     p.bpm = 0;
-    if (four) {            // T.81 B.2.3: an interleaved MCU holds at most 10 blocks
+    {                      // T.81 B.2.3: an interleaved MCU holds at most 10 blocks; three components may fill the per-MCU tables (12)
         uint32_t blocks = 0;
         for (uint32_t c = 0; c < p.ncomp; c++) blocks += p.h[c] * p.v[c];
-        if (blocks > 10) return fail(MJX_ERR_UNSUPPORTED_FORMAT);
+        if (blocks > (four ? 10u : uint32_t(kMaxBlocksPerMcu))) return fail(MJX_ERR_UNSUPPORTED_FORMAT);
     }
     for (uint32_t c = 0; c < p.ncomp; c++)
         for (uint32_t by = 0; by < p.v[c]; by++)

@@ -210,7 +210,7 @@ static void encode_block(bitw *b, const int16_t zz[64], int *pred, const henc *d
 
 static void put16(uint8_t **p, unsigned v) { *(*p)++ = (uint8_t)(v >> 8); *(*p)++ = (uint8_t)v; }
 
-/* subsampling: 0 = 4:4:4, 1 = 4:2:2 (Y 2x1), 2 = 4:2:0 (Y 2x2), 3 = greyscale, 4 = 4:4:0 (Y 1x2).
+/* subsampling: 0 = 4:4:4, 1 = 4:2:2 (Y 2x1), 2 = 4:2:0 (Y 2x2), 3 = greyscale, 4 = 4:4:0 (Y 1x2), 5 = 4:1:1 (Y 4x1), 6 = 4:1:0 (Y 4x2).
  * flags: MJXS_DQT16 = write the quantisation tables with 16-bit precision (Pq = 1, jpeg/mod.rs:245-256) and do not
  *        clamp their values at 255 (low qualities then give values up to 99 * 50 = 4950, like libjpeg without force_baseline).
  * Returns bytes written, or 0 if `cap` is too small. */
@@ -220,8 +220,8 @@ size_t mjxs_encode_ex(const uint8_t *rgb, int w, int h, int subsampling, int qua
     if (!dct_ready) dct_init();
     if (w < 1 || h < 1 || w > 65535 || h > 65535 || cap < 1024) return 0;
     const int ncomp = subsampling == 3 ? 1 : 3;
-    const int hy = (subsampling == 1 || subsampling == 2) ? 2 : 1;
-    const int vy = (subsampling == 2 || subsampling == 4) ? 2 : 1;
+    const int hy = (subsampling == 5 || subsampling == 6) ? 4 : (subsampling == 1 || subsampling == 2) ? 2 : 1;
+    const int vy = (subsampling == 2 || subsampling == 4 || subsampling == 6) ? 2 : 1;
     if (quality < 1) quality = 1;
     if (quality > 100) quality = 100;
     const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
