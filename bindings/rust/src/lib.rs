@@ -183,7 +183,17 @@ pub struct mjx_opts {
 /// byte 10 of mjx_opts, a padding byte behind scale_denom: MJX_COLOR_* (include/mjx.h: MJX_OPTS_COLOR)
 pub const MJX_OPTS_COLOR_OFFSET: usize = 10;
 
+/// byte 11 of mjx_opts, the next padding byte: 1 accepts progressive (SOF2) files (include/mjx.h: MJX_OPTS_PROGRESSIVE)
+pub const MJX_OPTS_PROGRESSIVE_OFFSET: usize = 11;
+
 impl mjx_opts {
+    /// 0: progressive files are refused as before; 1: SOF2 frames of one or three components decode on the device
+    pub fn progressive(&self) -> u8 {
+        unsafe { *(self as *const mjx_opts as *const u8).add(MJX_OPTS_PROGRESSIVE_OFFSET) }
+    }
+    pub fn set_progressive(&mut self, on: u8) {
+        unsafe { *(self as *mut mjx_opts as *mut u8).add(MJX_OPTS_PROGRESSIVE_OFFSET) = on }
+    }
     /// MJX_COLOR_*: 0 components by position (grey, or Y, Cb, Cr), 1 the file's own colour model -- RGB, CMYK and YCCK files decode to R,G,B
     pub fn color(&self) -> u8 {
         unsafe { *(self as *const mjx_opts as *const u8).add(MJX_OPTS_COLOR_OFFSET) }
@@ -254,6 +264,18 @@ pub struct mjx_scan_desc {
     /// MJX_COLOR_FILE: the fourth component of a four-component scan, and MJX_MODEL_* as mjx_parse decided it (appended)
     pub comp_fourth: mjx_comp,
     pub model: u8,
+    /// MJX_OPTS_PROGRESSIVE: null for a baseline file, else Ss, Se, Ah, Al of every part (appended)
+    pub prog: *const mjx_scan_prog,
+}
+
+/// one scan of a progressive file (include/mjx.h: mjx_scan_desc.prog)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mjx_scan_prog {
+    pub ss: u8,
+    pub se: u8,
+    pub ah: u8,
+    pub al: u8,
 }
 
 pub const MJX_COLOR_POSITIONAL: u8 = 0;

@@ -184,6 +184,29 @@ typedef struct mjx_opts {
 #define MJX_OPTS_COLOR_OFFSET 10
 #define MJX_OPTS_COLOR(opts) (((uint8_t *)(opts))[MJX_OPTS_COLOR_OFFSET])
 
+/* The progressive option of a call: byte 11 of mjx_opts, the next padding byte behind MJX_OPTS_COLOR (the struct's members, size and
+ * offsets are as they were; a zero-filled struct means what it meant).  An lvalue: MJX_OPTS_PROGRESSIVE(&opts) = 1.  Fill the struct
+ * with zeros first and set the byte on the object the call is given: a member-wise copy of the struct need not carry it.
+ * 0: everything as in every earlier version, bit for bit -- a progressive frame (SOF2) is MJX_ERR_UNSUPPORTED_FORMAT.  1: SOF2 frames of
+ * 8-bit precision with one or three components are accepted (four: MJX_ERR_UNSUPPORTED_FORMAT), in every sampling layout the baseline
+ * path takes, with the colour model as for baseline files (MJX_COLOR_FILE included); baseline files decode as they always did.
+ * Anything but 0 and 1: MJX_ERR_INVALID_ARG.  Together with strict_ref or MJX_LAYOUT_REF_COMPAT: MJX_ERR_INVALID_ARG for the picture.
+ * The scans (at most 255, else MJX_ERR_UNSUPPORTED_FORMAT) follow T.81 G.1.1.1 and libjpeg's coef_bits rule, any violation is
+ * MJX_ERR_UNSUPPORTED_FORMAT: a DC scan has Ss = Se = 0 and may interleave components; an AC scan has one component and 1 <= Ss <= Se
+ * <= 63; Al <= 13; the first scan of a (component, coefficient) has Ah = 0, every later one Ah = the previous Al and Al = Ah - 1; an AC
+ * scan needs the component's first DC scan in front of it; a component without a first DC scan is refused.  A progression that stops
+ * early (low bits or bands never sent) is valid and decodes to what was sent, as libjpeg does.  DHT and DRI are those in force at
+ * each SOS, a component's DQT the one in force at the first scan that carries it; a slot defined only later is MJX_ERR_MISSING_TABLE.
+ * The host de-stuffs the scans and cuts them at their restart markers (device_destuff does not apply, as for multi-scan files).
+ * On the device one lane decodes one restart interval of one scan serially (T.81 G.2) into a dense coefficient store; scans that
+ * touch no common (component, coefficient) run side by side (levels).  The store is then compacted into the coefficient stream stage
+ * B reads, so scales, rectangles, output formats, caller memory, luminance, planes, resize, orientation, MJX_PIXELS_LIBJPEG,
+ * keep_coefs and mjx_batch_tile compose as for a gathered multi-scan picture.  Statuses: a lane that runs out of bits before its
+ * interval's blocks are complete gives MJX_ERR_TRUNCATED, which wins; a bit pattern that matches no code, or an end-of-band run longer
+ * than the blocks left, MJX_ERR_BAD_HUFFMAN; such a picture hands out neither pixels nor coefficients, the others are unaffected. */
+#define MJX_OPTS_PROGRESSIVE_OFFSET 11
+#define MJX_OPTS_PROGRESSIVE(opts) (((uint8_t *)(opts))[MJX_OPTS_PROGRESSIVE_OFFSET])
+
 /* ---- output formats: what a picture leaves as, and where -------------------------------------------------------------
  * Without an output description a picture is packed R,G,B uint8 in the batch's own memory.  With one (mjx_batch_create_out,
  * mjx_decode_batch_out) stage B writes, in its one pass over the pixels, H x W x 3 or 3 x H x W elements of uint8, float16 or
@@ -457,6 +480,9 @@ typedef struct mjx_scan_part {
     mjx_hufftab dc[3], ac[3];      /* per component of the scan: the tables it selects, as defined when the SOS was read */
 } mjx_scan_part;
 
+/* One scan of a progressive file (mjx_scan_desc.prog): spectral selection Ss .. Se, successive approximation Ah, Al (T.81 G.1.1.1) */
+typedef struct mjx_scan_prog { uint8_t ss, se, ah, al; } mjx_scan_prog;
+
 typedef struct mjx_scan_desc {
     const uint8_t *scan;           /* bytes after the SOS header to end of file, de-stuffed (jpeg/mod.rs:371-385) unless
                                       scan_is_stuffed */
@@ -490,6 +516,12 @@ typedef struct mjx_scan_desc {
        position.  A four-component description needs MJX_MODEL_CMYK or MJX_MODEL_YCCK. */
     mjx_comp comp_fourth;
     uint8_t model;
+    /* MJX_OPTS_PROGRESSIVE (appended: every offset above is as before).  NULL: a baseline file -- every hand-filled or zero-filled
+       description means what it meant.  Else the file is progressive (SOF2): prog[k] holds Ss, Se, Ah, Al of parts[k], n_parts is 1 ..
+       255, ncomp 1 or 3, a part's ncomp is 1 .. 3 (an interleaved DC scan), its dc[q] counts for a first DC scan and its ac[0] for an
+       AC scan, its restart interval counts MCUs (interleaved) or blocks of the component's own grid.  mjx_validate applies the rules of
+       MJX_OPTS_PROGRESSIVE to a hand-filled description. */
+    const mjx_scan_prog *prog;
 } mjx_scan_desc;
 
 /* ---- outer surface ------------------------------------------------------------------------ */

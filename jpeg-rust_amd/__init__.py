@@ -69,6 +69,18 @@ Opts.COLOR_OFFSET = 10                  # MJX_OPTS_COLOR_OFFSET: the colour opti
 Opts.color = property(_opts_color, _opts_set_color)
 
 
+def _opts_progressive(self):
+    return ctypes.c_uint8.from_address(ctypes.addressof(self) + Opts.PROGRESSIVE_OFFSET).value
+
+
+def _opts_set_progressive(self, v):
+    ctypes.c_uint8.from_address(ctypes.addressof(self) + Opts.PROGRESSIVE_OFFSET).value = int(v)
+
+
+Opts.PROGRESSIVE_OFFSET = 11            # MJX_OPTS_PROGRESSIVE_OFFSET: the next padding byte
+Opts.progressive = property(_opts_progressive, _opts_set_progressive)
+
+
 class Dst(ctypes.Structure):
     """mjx_dst: caller-owned device memory for one picture; pitches in elements."""
     _fields_ = [("dev", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
@@ -196,6 +208,11 @@ class ScanPart(ctypes.Structure):
                 ("restart_offsets", ctypes.POINTER(ctypes.c_uint32)), ("dc", HuffTab * 3), ("ac", HuffTab * 3)]
 
 
+class ScanProg(ctypes.Structure):
+    """mjx_scan_prog: Ss, Se, Ah, Al of one scan of a progressive file."""
+    _fields_ = [(n, ctypes.c_uint8) for n in ("ss", "se", "ah", "al")]
+
+
 class ScanDesc(ctypes.Structure):
     _fields_ = [("scan", ctypes.POINTER(ctypes.c_uint8)), ("scan_len", ctypes.c_size_t),
                 ("width", ctypes.c_uint16), ("height", ctypes.c_uint16), ("ncomp", ctypes.c_uint8),
@@ -204,7 +221,7 @@ class ScanDesc(ctypes.Structure):
                 ("ac_present", ctypes.c_uint8), ("scan_is_stuffed", ctypes.c_uint8), ("restart_interval", ctypes.c_uint16),
                 ("n_restart", ctypes.c_uint32), ("restart_offsets", ctypes.POINTER(ctypes.c_uint32)),
                 ("n_parts", ctypes.c_uint8), ("parts", ctypes.POINTER(ScanPart)), ("owner_", ctypes.c_void_p),
-                ("comp_fourth", Comp), ("model", ctypes.c_uint8)]
+                ("comp_fourth", Comp), ("model", ctypes.c_uint8), ("prog", ctypes.POINTER(ScanProg))]
 
 
 class ColorInfo(ctypes.Structure):
@@ -370,18 +387,20 @@ def _color(color):
     return int(color)
 
 
-def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0, device_destuff=False, scale=1, rois=None, pixels=None, color=None):
+def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0, device_destuff=False, scale=1, rois=None, pixels=None, color=None, progressive=False):
     """device_destuff: True = on the GPU, False = on the host, None = the library's choice (mjx.h: MJX_DESTUFF_*).
     scale: 1, 2, 4 or 8 -- the picture decoded at 1/scale in the DCT domain (mjx.h: mjx_opts.scale_denom).
     rois: see _rects (mjx.h: mjx_opts.rois, n_rois); the Opts returned keeps the array alive.
     pixels: see _pixels -- "libjpeg": rounded samples, fancy chroma upsampling and libjpeg's integer colour tables.
-    color: see _color -- "file": the colour model comes from the file (RGB, CMYK and YCCK files decode to R,G,B)."""
+    color: see _color -- "file": the colour model comes from the file (RGB, CMYK and YCCK files decode to R,G,B).
+    progressive: True -- progressive files (SOF2) are accepted (mjx.h: MJX_OPTS_PROGRESSIVE); an integer is passed through as it is."""
     dd = DESTUFF_AUTO if device_destuff is None else (DESTUFF_DEVICE if device_destuff else DESTUFF_HOST)
     scale = int(scale)
     if not 0 <= scale <= 255:
         raise MjxError(ERR_INVALID_ARG, "scale=%d" % scale)
     o = Opts(int(bool(strict_ref)), int(layout), int(bool(keep_coefs)), dd, int(chunk_images), _pixels(pixels), scale)
     o.color = _color(color)
+    o.progressive = int(progressive) if not isinstance(progressive, bool) and 0 <= int(progressive) <= 255 else int(bool(progressive))
     arr = _rects(rois)
     if arr is not None:
         o._rects = arr                      # (the library borrows the array for the duration of the call)
@@ -643,43 +662,43 @@ def _out_ref(output):
 class ParsedScan:
     """Owns one mjx_scan_desc filled by mjx_parse (reference: the state JPEGImage::parse hands to JPEGDecoder)."""
 
-    def __init__(self, data, strict_ref=False, device_destuff=False, color=None):
+    def __init__(self, data, strict_ref=False, device_destuff=False, color=None, progressive=False):
         """color: "file" -- four-component files parse, and desc.model says what the components are (see Batch)."""
         self.desc = ScanDesc()
         self._owned = False
-        o = _opts(strict_ref=strict_ref, device_destuff=device_destuff, color=color)
+        o = _opts(strict_ref=strict_ref, device_destuff=device_destuff, color=color, progressive=progressive)
         _check(lib().mjx_parse(bytes(data), len(data), ctypes.byref(o), ctypes.byref(self.desc)), "mjx_parse")
         self._owned = True
 
     def scan_bytes(self):
         return ctypes.string_at(self.desc.scan, self.desc.scan_len)
 
-    def validate(self, layout=LAYOUT_STANDARD, strict_ref=False, scale=1, roi=None, pixels=None, color=None):
+    def validate(self, layout=LAYOUT_STANDARD, strict_ref=False, scale=1, roi=None, pixels=None, color=None, progressive=False):
         """Status mjx_batch_create would give this image (host only).  roi: (x, y, w, h) in the scaled picture's coordinates."""
-        o = _opts(layout=layout, strict_ref=strict_ref, scale=scale, rois=roi, pixels=pixels, color=color)
+        o = _opts(layout=layout, strict_ref=strict_ref, scale=scale, rois=roi, pixels=pixels, color=color, progressive=progressive)
         return int(lib().mjx_validate(ctypes.byref(self.desc), ctypes.byref(o)))
 
-    def plan_tiles(self, roi=None, scale=1, pixels=None, color=None):
+    def plan_tiles(self, roi=None, scale=1, pixels=None, color=None, progressive=False):
         """mjx_plan_tiles (host only) -> dict(tiles_read, tiles_total, tile_mcus): the stage-B tiles a decode with this rectangle
         fetches and transforms, of the picture's tiles, and the MCUs a tile holds."""
-        o = _opts(scale=scale, rois=roi, pixels=pixels, color=color)
+        o = _opts(scale=scale, rois=roi, pixels=pixels, color=color, progressive=progressive)
         rd, tot, t = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
         _check(lib().mjx_plan_tiles(ctypes.byref(self.desc), ctypes.byref(o), ctypes.byref(rd), ctypes.byref(tot), ctypes.byref(t)), "mjx_plan_tiles")
         return dict(tiles_read=rd.value, tiles_total=tot.value, tile_mcus=t.value)
 
-    def output_layout(self, output=None, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD, color=None):
+    def output_layout(self, output=None, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD, color=None, progressive=False):
         """mjx_output_layout (host only) -> dict(width, height, row_pitch, plane_pitch, bytes, dev): what a decode of this picture
         as input i of a call with this Output would write; pitches in elements, bytes from the first element to the last."""
-        o = _opts(layout=layout, scale=scale, rois=roi, color=color)
+        o = _opts(layout=layout, scale=scale, rois=roi, color=color, progressive=progressive)
         keep, ref = _out_ref(output)
         lay, nb = Dst(), _sz()
         _check(lib().mjx_output_layout(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(lay), ctypes.byref(nb)), "mjx_output_layout")
         return dict(width=lay.width, height=lay.height, row_pitch=lay.row_pitch, plane_pitch=lay.plane_pitch, bytes=nb.value, dev=lay.dev or 0)
 
-    def planes_layout(self, planes, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD, pixels=None, strict_ref=False, color=None):
+    def planes_layout(self, planes, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD, pixels=None, strict_ref=False, color=None, progressive=False):
         """mjx_planes_layout (host only) -> dict(nplanes, width, height, row_pitch, dev -- a list of three each --, bytes): the planes a
         decode of this picture as input i of a call with this Planes would write; pitches in elements, sizes in samples."""
-        o = _opts(layout=layout, scale=scale, rois=roi, pixels=pixels, strict_ref=strict_ref, color=color)
+        o = _opts(layout=layout, scale=scale, rois=roi, pixels=pixels, strict_ref=strict_ref, color=color, progressive=progressive)
         keep, ref = _planes_ref(planes)
         lay, np_, nb = PlaneLayout(), ctypes.c_uint32(), _sz()
         _check(lib().mjx_planes_layout(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(lay), ctypes.byref(np_), ctypes.byref(nb)), "mjx_planes_layout")
@@ -766,7 +785,7 @@ class Batch:
     """Device-resident batch: inputs uploaded at construction, ``decode()`` only enqueues kernels."""
 
     def __init__(self, ctx, scans=None, strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0,
-                 _handle=None, scale=1, rois=None, output=None, resize=None, orient=None, datas=None, pixels=None, planes=None, color=None):
+                 _handle=None, scale=1, rois=None, output=None, resize=None, orient=None, datas=None, pixels=None, planes=None, color=None, progressive=False):
         """scale: 1, 2, 4 or 8 -- every picture decoded at 1/scale (info(), rgb(), rgb_device() and bytes() then speak of the
         scaled picture; tile() keeps the scale).
         rois: one (x, y, w, h) for every picture, or a list with one per picture (None or (0, 0, 0, 0): the whole picture), in the
@@ -799,7 +818,7 @@ class Batch:
             ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(s.desc if isinstance(s, ParsedScan) else s),
                            ctypes.sizeof(ScanDesc))
         st = (_int * max(n, 1))()
-        o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois, pixels=pixels, color=color)
+        o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois, pixels=pixels, color=color, progressive=progressive)
         keep, ref = _out_ref(output)
         if planes is not None:
             if output is not None or resize is not None or orient is not None:
@@ -1144,14 +1163,14 @@ class JPEGImage:
         self._w, self._h, self._rgb = width, height, rgb
 
     @staticmethod
-    def parse(data, strict_ref=False, layout=LAYOUT_STANDARD, ctx=None, scale=1, roi=None, pixels=None, color=None):
+    def parse(data, strict_ref=False, layout=LAYOUT_STANDARD, ctx=None, scale=1, roi=None, pixels=None, color=None, progressive=False):
         """scale: 1, 2, 4 or 8 -- the picture at 1/scale (width() and height() are the scaled picture's).
         roi: (x, y, w, h) of the scaled picture -- only that rectangle is produced (width() and height() are its).
         pixels: "libjpeg", color: "file" -- see Batch."""
         ctx = ctx or default_context()
-        scan = ParsedScan(data, strict_ref=strict_ref, color=color)
+        scan = ParsedScan(data, strict_ref=strict_ref, color=color, progressive=progressive)
         try:
-            b = Batch(ctx, [scan], strict_ref=strict_ref, layout=layout, scale=scale, rois=roi, pixels=pixels, color=color)
+            b = Batch(ctx, [scan], strict_ref=strict_ref, layout=layout, scale=scale, rois=roi, pixels=pixels, color=color, progressive=progressive)
             try:
                 if b.create_status[0] != OK:
                     raise MjxError(b.create_status[0])
@@ -1178,7 +1197,7 @@ class JPEGImage:
 
 
 def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False, scale=1, rois=None,
-                 output=None, chunk_images=0, resize=None, orient=None, pixels=None, planes=None, color=None):
+                 output=None, chunk_images=0, resize=None, orient=None, pixels=None, planes=None, color=None, progressive=False):
     """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale, rois, pixels, color: see Batch.
     device_destuff: the host copies the entropy-coded bytes as they are; de-stuffing, restart markers and the scan's length
     are found on the GPU.  output: an Output (mjx_decode_batch_out) -- see Batch.  resize: a Resize (mjx_decode_batch_resize).  orient: an Orient
@@ -1190,7 +1209,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     st = (_int * max(n, 1))()
     ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
     h = _vp()
-    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, color=color)
+    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, color=color, progressive=progressive)
     if planes is not None:
         if output is not None or resize is not None or orient is not None:
             raise MjxError(ERR_INVALID_ARG, "planes go without output, resize and orient")
@@ -1217,7 +1236,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
 
 
 def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=False, threads=0, device_destuff=None, planar=None, resize=None,
-                orient=None, pixels=None, color=None, pad=0):
+                orient=None, pixels=None, color=None, progressive=False, pad=0):
     """Decodes the files straight into a torch tensor on the context's device: N x 3 x H x W (planar) or N x H x W x 3, of uint8,
     float16 or float32; picture i -- at 1/scale, its rectangle rois[i] -- must be H x W.  Float tensors take (v / 255 - mean) / std
     per OUTPUT channel (see Output); bgr: channel 0 is blue.  The pointers and pitches come from data_ptr() and stride(): the
@@ -1290,7 +1309,7 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
             raise MjxError(ERR_INVALID_ARG, "resize to %d x %d into a tensor of %d x %d" % (resize.width, resize.height, w, h))
     else:
         rs = None
-    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt, resize=rs, orient=orient, pixels=pixels, color=color)
+    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt, resize=rs, orient=orient, pixels=pixels, color=color, progressive=progressive)
     batch.close()
     return status
 
@@ -1356,7 +1375,7 @@ class Pool:
     def set_deal(self, round_robin):
         _check(lib().mjx_pool_set_deal(self.h, 1 if round_robin else 0), "mjx_pool_set_deal")
 
-    def decode_batch(self, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads_per_device=0, device_destuff=None, scale=1, rois=None, pixels=None, color=None):
+    def decode_batch(self, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads_per_device=0, device_destuff=None, scale=1, rois=None, pixels=None, color=None, progressive=False):
         """-> PoolResult; .slot_of[i], .status[i], .rgb(i), .rc (the call's return code: a failed slot fails its own files only).
         scale, rois, pixels, color: see Batch (a file's rectangle follows it to its slot)."""
         n = len(datas)
@@ -1366,7 +1385,7 @@ class Pool:
         slots = (_int * max(n, 1))()
         ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
         h = _vp()
-        o = _opts(strict_ref, layout, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, color=color)
+        o = _opts(strict_ref, layout, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, color=color, progressive=progressive)
         rc = lib().mjx_pool_decode_batch(self.h, arr, lens, n, ctypes.byref(o), int(threads_per_device), slots, ptrs, st, ctypes.byref(h))
         if not h:
             _check(rc, "mjx_pool_decode_batch")
@@ -1454,11 +1473,11 @@ class PoolResult:
             pass
 
 
-def plan_tiles(data, roi=None, scale=1, pixels=None, color=None):
+def plan_tiles(data, roi=None, scale=1, pixels=None, color=None, progressive=False):
     """Host only: the stage-B tiles a decode of this file with this rectangle and scale reads -> see ParsedScan.plan_tiles."""
-    scan = ParsedScan(data, color=color)
+    scan = ParsedScan(data, color=color, progressive=progressive)
     try:
-        return scan.plan_tiles(roi=roi, scale=scale, pixels=pixels, color=color)
+        return scan.plan_tiles(roi=roi, scale=scale, pixels=pixels, color=color, progressive=progressive)
     finally:
         scan.close()
 
@@ -1513,11 +1532,11 @@ def ink_mul(a, k):
     return int(lib().mjx_ink_mul(int(a), int(k)))
 
 
-def decode(data, strict_ref=False, layout=LAYOUT_STANDARD, scale=1, roi=None, pixels=None, color=None):
+def decode(data, strict_ref=False, layout=LAYOUT_STANDARD, scale=1, roi=None, pixels=None, color=None, progressive=False):
     """One-shot C entry point mjx_decode (parse + GPU decode + copy back) -> ndarray [H, W, 3] uint8.  scale: see Batch.
     roi: (x, y, w, h) of the scaled picture -- the array is that rectangle, [h, w, 3]."""
     img = Image()
-    o = _opts(strict_ref, layout, scale=scale, rois=roi, pixels=pixels, color=color)
+    o = _opts(strict_ref, layout, scale=scale, rois=roi, pixels=pixels, color=color, progressive=progressive)
     _check(lib().mjx_decode(bytes(data), len(data), ctypes.byref(o), ctypes.byref(img)), "mjx_decode")
     try:
         return np.ctypeslib.as_array(img.rgb, (img.height, img.width, 3)).copy()

@@ -4,6 +4,7 @@
     synth/libmjx_synth.so synthetic baseline-JPEG generator           (gcc)
     ../oracle/libmjx_oracle.so  CPU oracle, test infrastructure only  (make, gcc)
     ../tests/emul/libhuff_emul.so CPU emulation of the entropy algorithm, test infrastructure only (g++)
+    ../tests/emul/libprog_emul.so CPU emulation of the progressive path, test infrastructure only (g++)
 """
 import contextlib
 import fcntl
@@ -18,7 +19,7 @@ CSRC = os.path.join(PKG, "csrc")
 
 HIP_SOURCES = ["mjx_kernels.hip", "mjx_api.hip"]
 CXX_SOURCES = ["mjx_parse.cpp", "mjx_lut.cpp", "mjx_plan.cpp", "mjx_pool.cpp"]
-HEADERS = ["mjx_huff.h", "mjx_kernels.h", "mjx_plan.h", os.path.join(ROOT, "include", "mjx.h")]
+HEADERS = ["mjx_huff.h", "mjx_kernels.h", "mjx_plan.h", "mjx_prog.h", os.path.join(ROOT, "include", "mjx.h")]
 
 
 def _newer(target, sources):
@@ -118,6 +119,13 @@ def build_emul(force=False):
     if os.path.exists(src) and (force or _newer(out, deps)):
         _link(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
                "-o", out, src] + [os.path.join(CSRC, s) for s in host_only], out)
+    # the progressive path's emulation: mjx_prog.h's lane routine and its count / copy rule, run serially (tests/emul/prog_emul.cpp)
+    psrc = os.path.join(d, "prog_emul.cpp")
+    pout = os.path.join(d, "libprog_emul.so")
+    pdeps = [psrc] + [os.path.join(CSRC, s) for s in host_only + ["mjx_huff.h", "mjx_kernels.h", "mjx_plan.h", "mjx_prog.h"]]
+    if os.path.exists(psrc) and (force or _newer(pout, pdeps)):
+        _link(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
+               "-o", pout, psrc] + [os.path.join(CSRC, s) for s in host_only], pout)
     return out
 
 

@@ -10,6 +10,7 @@
 #include "mjx.h"
 #include "mjx_kernels.h"
 #include "mjx_plan.h"
+#include "mjx_prog.h"
 
 #include <algorithm>
 #include <atomic>
@@ -155,6 +156,8 @@ struct ImageInfo {
     uint32_t role = 0;             // 0 ordinary picture; multi-scan files: 1 = one scan (internal), 2 = the picture
     uint32_t nparts = 0;           // role 2: scans in front of it
     bool planar = false;           // role 2: read without the gather (no stream of its own: mjx_batch_copy_coefs has nothing to expand)
+    bool prog = false;             // role 2: a progressive picture (MJX_OPTS_PROGRESSIVE): its flags are kProgShort / kProgBad
+    uint64_t store_elems = 0;      // ... and its planes in the chunk's dense store (int16 elements)
 };
 
 // The passes behind stage B that bring a picture to the form it leaves in, in the order run_chunk launches them
@@ -198,6 +201,10 @@ struct Chunk {
     bool has_gather = false;       // holds multi-scan pictures (k_planar_gather runs)
     bool has_copy = false;         // ... some of which are gathered into a stream of their own (the others are read from their scans' streams)
     bool has_emit = false, has_spec = false;   // holds pictures whose first decode emits (k_huff_emit ...) / pictures of the two-pass path
+    // progressive pictures: the chunk's dense store (int16 elements), and per level the lanes of k_prog_scan (first, count) in the batch's array
+    bool has_prog = false;
+    uint64_t store_elems = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> prog_levels;
 };
 
 // All device buffers of a batch come out of ONE allocation: the layout code runs twice, first measuring, then handing out
@@ -279,6 +286,23 @@ struct mjx_batch {
     // handed to the caller is then only a directory of the groups' batches
     std::vector<mjx_batch *> parts;
     std::vector<std::pair<uint32_t, uint32_t>> part_index;     // caller's picture -> (part, picture inside the part)
+    // progressive pictures (MJX_OPTS_PROGRESSIVE): their scans' bytes, the lanes and pictures of k_prog_scan, and the dense store --
+    // one per scratch set, sized for the largest chunk.  Allocations of their own: a batch without such a picture has none of this.
+    struct ProgKeep {                   // per unique picture: what mjx_batch_tile rebuilds a progressive picture's plan from
+        std::vector<uint8_t> bytes;     // (its scans, one behind the other: the caller's descriptions are only borrowed)
+        std::vector<ProgScanPlan> pscans;
+        uint32_t levels = 0;
+        uint64_t prog_bytes = 0, ac_bytes = 0;
+    };
+    std::vector<ProgKeep> prog_keep;
+    std::vector<uint8_t> h_prog_bytes;
+    std::vector<ProgLane> h_prog_lanes;
+    std::vector<ProgPic> h_prog_pics;
+    uint8_t *d_prog_bytes = nullptr;
+    ProgLane *d_prog_lanes = nullptr;
+    ProgPic *d_prog_pics = nullptr;
+    int16_t *d_prog_store[2] = {nullptr, nullptr};
+    uint64_t prog_store_bytes = 0;
     LutEntry *d_lut = nullptr;
     float *d_qm = nullptr;
     uint32_t *d_segs = nullptr;         // restart segments of the unique images: (first subsequence, first bit) pairs
@@ -422,6 +446,10 @@ void release(mjx_batch *b)
     if (!b) return;
     for (mjx_batch *part : b->parts) release(part);
     if (b->ctx) (void)hipSetDevice(b->ctx->device);
+    if (b->d_prog_bytes) (void)hipFree(b->d_prog_bytes);
+    if (b->d_prog_lanes) (void)hipFree(b->d_prog_lanes);
+    if (b->d_prog_pics) (void)hipFree(b->d_prog_pics);
+    for (int k = 0; k < 2; k++) if (b->d_prog_store[k]) (void)hipFree(b->d_prog_store[k]);
     if (b->uploaded) (void)hipEventDestroy(b->uploaded);
     if (b->copied) (void)hipEventDestroy(b->copied);
     for (int k = 0; k < 2; k++) {
@@ -563,6 +591,7 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
         }
     }
     d.role = p.role;
+    d.prog = p.prog ? 1u : 0u;
     d.wg_lanes = p.wg_lanes;
     if (p.role == 1) {                // a scan of a multi-scan file: no stage B; one tile offset per block for the gather (build_batch: or segment cuts, seg_S)
         d.log2_tile = 0;
@@ -619,6 +648,7 @@ void plan_chunks(mjx_batch *b)
         if (total_scan >= (uint64_t(256) << 20)) scan_target = std::min(scan_target, total_scan - total_scan / 4);      // (128 4K pictures, 138 MB: 2.34 ms in one chunk, 2.43 in two)
     }
     const uint64_t kMaxChunkEntries = (uint64_t(32) << 30) / 4;          // 32 GiB of stream capacity per chunk (24 before the columns got their head room, round 5)
+    const uint64_t kMaxChunkStore = uint64_t(4) << 30;                   // int16 elements: 8 GiB of dense store per chunk (320 progressive 4K 4:2:0 pictures)
     b->chunks.clear();
     uint64_t coef_running = 0, ent_running = 0;
     uint32_t tile_running = 0;
@@ -633,8 +663,10 @@ void plan_chunks(mjx_batch *b)
             if (i >= n) break;
             const ImageInfo &inf = b->info[i];
             // (the scans of a multi-scan file and their picture stay in one chunk: only a group's first image may open one)
-            const bool head = inf.role == 0 || (inf.role == 1 && (i == 0 || b->info[i - 1].role != 1));
+            // (a progressive picture has no scans in front of it: it is a group of its own)
+            const bool head = inf.role == 0 || inf.prog || (inf.role == 1 && (i == 0 || b->info[i - 1].role != 1));
             if (head && c.count >= per_chunk) break;
+            if (head && c.count > 0 && inf.store_elems && c.store_elems + inf.store_elems > kMaxChunkStore) break;      // (progressive pictures: the dense store closes a chunk too)
             if (head && c.count > 0 && (c.entries + inf.ent_cap > kMaxChunkEntries || c.scan_bytes >= scan_target || c.nsub >= (uint64_t(1) << 22))) break;
             DevImage &d = b->himages[i];
             if (inf.status == MJX_OK) {
@@ -662,7 +694,8 @@ void plan_chunks(mjx_batch *b)
                     c.max_b_tiles = std::max<uint32_t>(c.max_b_tiles, d.roi_ntiles);
                     c.max_tile_blocks = std::max<uint32_t>(c.max_tile_blocks, T * d.bpm);
                 }
-                if (d.role == 2) { c.has_gather = true; if (!d.planar) c.has_copy = true; }
+                if (d.role == 2 && !d.prog) { c.has_gather = true; if (!d.planar) c.has_copy = true; }
+                if (d.prog) { c.has_prog = true; c.store_elems += inf.store_elems; }
                 if (d.emit) c.has_emit = true; else if (d.role != 2) c.has_spec = true;
                 c.lut_cap = std::max<uint32_t>(c.lut_cap, d.lut_n);
                 c.lut2_cap = std::max<uint32_t>(c.lut2_cap, d.lut2_n);
@@ -887,7 +920,7 @@ enum { PH_SYNC = 1, PH_FIX = 2, PH_TAIL = 4, PH_ENTROPY_ALL = 7 };
 int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned phases = PH_ENTROPY_ALL, bool force_first = false)
 {
     const Chunk &c = b->chunks[ci];
-    if (c.count == 0 || c.nsub == 0) return MJX_OK;
+    if (c.count == 0 || (c.nsub == 0 && !c.has_prog)) return MJX_OK;
     // Two streams (the default): the entropy stage of every chunk runs on `stream`, stage B on `stream2`, chained by events --
     // so the pixel kernel of chunk k (HBM stores, LDS) always shares the device with the entropy kernels of chunk k+1
     // (instruction issue, latency) instead of two kernels of one kind meeting by chance.  Odd chunks use the second set of
@@ -987,6 +1020,20 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
         if (c.has_gather) {
             prof_begin(b, MJX_K_GATHER, st);
             launch_planar_gather(st, c.max_tiles, nimg, imgs, SCR(d_entries), SCR(d_tile_eoff), dcb, b->d_img_flags, c.has_copy);
+            prof_end(b, st);
+        }
+        // (The lanes only OR into their picture's word of img_flags and nothing clears it between decodes of a batch: a lane's flags
+        // are a function of the scan's bytes alone, so every decode of the batch sets the same bits.  Whoever makes them depend on
+        // anything else must clear the words of the chunk's progressive pictures here, in front of the first level.)
+        if (c.has_prog) {       // progressive pictures: the store is cleared, the scans decode level by level, the store becomes the stream
+            int16_t *store = b->d_prog_store[set];
+            HIPOK(hipMemsetAsync(store, 0, size_t(c.store_elems) * sizeof(int16_t), st));
+            prof_begin(b, MJX_K_HUFF_WRITE, st);
+            for (const auto &lv : c.prog_levels)
+                launch_prog_scan(st, lv.second, b->d_prog_lanes + lv.first, b->d_prog_pics, imgs, b->d_prog_bytes, b->d_lut, store, b->d_img_flags);
+            prof_end(b, st);
+            prof_begin(b, MJX_K_GATHER, st);
+            launch_prog_compact(st, c.max_tiles, nimg, imgs, b->d_prog_pics, store, SCR(d_entries), SCR(d_tile_eoff), dcb, b->d_img_flags, b->d_status);
             prof_end(b, st);
         }
     }
@@ -1269,6 +1316,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
         d.lut_n = p.lut_plain_n;
         d.lut2_off = lut_off[k] + p.lut_plain_n;
         d.lut2_n = lut_n[k] - p.lut_plain_n;
+        if (p.prog) d.lut_n = d.lut2_n = 0;      // (its tables are read where they lie, from lut_off on: no entropy workgroup stages them)
         d.qm_off = uint32_t(k * 192);
         if (p.scale > 1) d.qm_off = uint32_t((nu + k) * 192);       // (the reduced transforms' multipliers: the second half of the pool)
         if (p.ncomp == 4) d.qm3_off = uint32_t(qm_tail[k] + (p.scale > 1 ? 64 : 0));      // (a fourth component's: behind both halves)
@@ -1362,10 +1410,16 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
             inf.nparts = p.nparts;
             inf.ent_cap = 8;
             for (uint32_t k = 1; k <= p.nparts && !inf.planar; k++) inf.ent_cap += b->info[i - k].ent_cap;
+            // a progressive picture: a non-zero AC costs at least two bits of some AC scan -- 4 entries per AC-scan byte
+            if (p.prog) {
+                inf.prog = true;
+                inf.ent_cap = 8 + std::min<uint64_t>(p.prog_ac_bytes * 4, inf.nblocks * 63);
+                for (uint32_t q = 0; q < p.ncomp; q++) inf.store_elems += uint64_t(p.mcux) * p.h[q] * p.mcuy * p.v[q] * 64u;
+            }
         }
         inf.ent_cap = (inf.ent_cap + 31) / 32 * 32;        // regions start on whole 128-byte lines (rows of the quad-interleaved stream)
         d.ent_cap = uint32_t(std::min<uint64_t>(inf.ent_cap, 0xffffffffu));
-        inf.scan_len = p.scan_len;
+        inf.scan_len = p.prog ? p.prog_bytes : p.scan_len;
         inf.rgb_off = rgb_pool;
         inf.rgb_bytes = p.role == 1 ? 0 : uint64_t(p.roi_w) * p.roi_h * 3;     // (a scan of a multi-scan file has no picture)
         inf.cropped = p.cropped;
@@ -1403,7 +1457,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
             rgb_pool += p.out_dev ? 0 : align_up(inf.out_span, 256);
         } else
         rgb_pool += align_up(inf.rgb_bytes, 256);
-        b->scan_bytes += p.scan_len;
+        b->scan_bytes += inf.scan_len;
         b->rgb_bytes += inf.rgb_bytes;
         if (p.role != 1) {
             b->coef_bytes += inf.nblocks * 128;
@@ -1415,6 +1469,44 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
     b->rgb_pool_bytes = rgb_pool;
     b->lut_pool_entries = lut_pool;
     plan_chunks(b);
+    for (size_t k = 0; k < nu; k++) {
+        const ImagePlan &p = plans[k];
+        if (p.status != MJX_OK || !p.prog) continue;
+        if (b->prog_keep.empty()) b->prog_keep.resize(nu);
+        mjx_batch::ProgKeep &keep = b->prog_keep[k];
+        keep.pscans = p.pscans;
+        keep.levels = p.prog_levels; keep.prog_bytes = p.prog_bytes; keep.ac_bytes = p.prog_ac_bytes;
+        size_t total = 0;
+        for (const ProgScanPlan &sc : p.pscans) total += sc.cuts.back();
+        keep.bytes.reserve(total + 1);                    // (no reallocation below: the scans' pointers stay valid)
+        for (ProgScanPlan &sc : keep.pscans) {
+            const size_t at = keep.bytes.size();
+            if (sc.cuts.back()) keep.bytes.insert(keep.bytes.end(), sc.scan, sc.scan + sc.cuts.back());
+            sc.scan = keep.bytes.data() + at;
+        }
+    }
+    // progressive pictures: every chunk's dense store (a plane of 64-coefficient blocks per component over the MCU-padded grid) and
+    // the lanes of its levels, one per (scan, restart interval), with the scans' bytes one behind the other
+    std::vector<uint64_t> prog_bytes_at(nu, kProgAppend);     // (the copies of a unique picture share one copy of its scans' bytes)
+    for (Chunk &c : b->chunks) {
+        if (!c.has_prog) continue;
+        std::vector<std::vector<ProgLane>> levels;
+        c.store_elems = 0;                   // (laid out again below, picture by picture, to the same total)
+        for (size_t i = c.first; i < c.first + c.count; i++) {
+            const ImagePlan &p = plans[i % nu];
+            if (p.status != MJX_OK || !p.prog) continue;
+            DevImage &d = b->himages[i];
+            d.prog_pic = uint32_t(b->h_prog_pics.size());
+            ProgPic pic;
+            c.store_elems = prog_layout(p, c.store_elems, uint32_t(i - c.first), d.prog_pic, pic, levels, b->h_prog_bytes, &prog_bytes_at[i % nu]);
+            b->h_prog_pics.push_back(pic);
+        }
+        for (const std::vector<ProgLane> &lv : levels) {
+            c.prog_levels.emplace_back(uint32_t(b->h_prog_lanes.size()), uint32_t(lv.size()));
+            b->h_prog_lanes.insert(b->h_prog_lanes.end(), lv.begin(), lv.end());
+        }
+        b->prog_store_bytes = std::max<uint64_t>(b->prog_store_bytes, c.store_elems * sizeof(int16_t));
+    }
     if (pinned_words && std::max<size_t>(b->chunks.size(), 1) * kMisWords <= pinned_cap) {    // lent by the caller (mjx_decode_batch)
         b->h_mismatch = pinned_words;
         b->h_mismatch_owned = false;
@@ -1773,6 +1865,23 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                     std::fprintf(stderr, "[mjx] interleave %.2f ms\n", ms(t2, now()));
                 }
             }
+        }
+        if (b->prog_store_bytes) {          // progressive pictures: their pools, allocations of their own (the stores are cleared per decode)
+            b->h_prog_bytes.resize(b->h_prog_bytes.size() + 16, 0);
+            void *q = nullptr;
+            if (hipMalloc(&q, b->h_prog_bytes.size()) != hipSuccess) { (void)hipGetLastError(); return MJX_ERR_NOMEM; }
+            b->d_prog_bytes = static_cast<uint8_t *>(q);
+            if (hipMalloc(&q, std::max<size_t>(b->h_prog_lanes.size(), 1) * sizeof(ProgLane)) != hipSuccess) { (void)hipGetLastError(); return MJX_ERR_NOMEM; }
+            b->d_prog_lanes = static_cast<ProgLane *>(q);
+            if (hipMalloc(&q, b->h_prog_pics.size() * sizeof(ProgPic)) != hipSuccess) { (void)hipGetLastError(); return MJX_ERR_NOMEM; }
+            b->d_prog_pics = static_cast<ProgPic *>(q);
+            for (int k = 0; k < (b->dual ? 2 : 1); k++) {
+                if (hipMalloc(&q, size_t(b->prog_store_bytes) + 256) != hipSuccess) { (void)hipGetLastError(); return MJX_ERR_NOMEM; }
+                b->d_prog_store[k] = static_cast<int16_t *>(q);
+            }
+            HIPOK(hipMemcpyAsync(b->d_prog_bytes, b->h_prog_bytes.data(), b->h_prog_bytes.size(), hipMemcpyHostToDevice, up));
+            if (!b->h_prog_lanes.empty()) HIPOK(hipMemcpyAsync(b->d_prog_lanes, b->h_prog_lanes.data(), b->h_prog_lanes.size() * sizeof(ProgLane), hipMemcpyHostToDevice, up));
+            HIPOK(hipMemcpyAsync(b->d_prog_pics, b->h_prog_pics.data(), b->h_prog_pics.size() * sizeof(ProgPic), hipMemcpyHostToDevice, up));
         }
         if (async_upload) {
             // the caller goes on (parsing and uploading the next group of files) while the DMA engine works; the decode
@@ -2368,6 +2477,13 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
         p.scan = nullptr;
         p.scan_len = src->info[k].scan_len;
         p.emit_fits = src->info[k].emit_fits;             // (a picture too dense for the emitting pass stays off it in every copy)
+        if (src->info[k].prog && !src->prog_keep.empty()) {      // (a progressive picture: its scans as the source kept them; its tables stay on the device)
+            const mjx_batch::ProgKeep &keep = src->prog_keep[k % src->prog_keep.size()];
+            p.prog = true;
+            p.pscans = keep.pscans;
+            p.prog_levels = keep.levels; p.prog_bytes = keep.prog_bytes; p.prog_ac_bytes = keep.ac_bytes;
+            p.scan_len = 0;
+        }
     }
     return build_batch(ctx, plans, src->opts, src, times, out, nullptr);
     });
@@ -2562,7 +2678,8 @@ extern "C" int mjx_batch_wait(mjx_batch *b)
     }
     for (size_t i = 0; i < dev.size(); i++) {
         if (b->info[i].status != MJX_OK) continue;
-        if (flags[i]) b->info[i].status = MJX_ERR_TRUNCATED;           // scan ended before the last MCU
+        if (b->info[i].prog) { if (flags[i]) b->info[i].status = (flags[i] & kProgShort) ? MJX_ERR_TRUNCATED : MJX_ERR_BAD_HUFFMAN; }   // (a lane's flags, mjx_prog.h)
+        else if (flags[i]) b->info[i].status = MJX_ERR_TRUNCATED;      // scan ended before the last MCU
         else if (dev[i]) b->info[i].status = MJX_ERR_BAD_HUFFMAN;       // no code matched (huffman.rs:156/162)
     }
     for (size_t i = 0; i < dev.size(); i++) {                           // a multi-scan picture takes its scans' failures
@@ -2977,7 +3094,7 @@ extern "C" int mjx_batch_bytes(const mjx_batch *b, uint64_t *scan_bytes, uint64_
             std::vector<uint32_t> cnt(b->info.size());
             if (!cnt.empty()) HIPOK(hipMemcpy(cnt.data(), b->d_img_entries, cnt.size() * 4, hipMemcpyDeviceToHost));
             for (size_t i = 0; i < cnt.size(); i++)
-                if (b->info[i].status == MJX_OK) total += uint64_t(cnt[i]) * 4 + b->info[i].nblocks * 4;
+                if (b->info[i].status == MJX_OK) total += uint64_t(cnt[i]) * 4 + b->info[i].nblocks * 4 + b->info[i].store_elems * 2;      // (a progressive picture: its planes of the dense store)
         }
         *coef_bytes = total;
     }

@@ -159,6 +159,10 @@ struct DevImage {
     // fit_on = 1 (there is a border), k_fit_pad writes every other element: the format's table applied to fit_pad's byte c
     // (bits 8 c .. 8 c + 7, c the OUTPUT channel).  Without the mode fit_w x fit_h = rs_w x rs_h, the origin is 0 and fit_on = 0.
     uint32_t fit_on, fit_w, fit_h, fit_ox, fit_oy, fit_pad;
+    // progressive pictures (MJX_OPTS_PROGRESSIVE; prog = 1): a role-2 picture with no scans in front of it.  k_prog_scan's lanes fill
+    // the chunk's dense store, k_prog_count / _offsets / _copy build the stream from it (the k_planar_* kernels pass over the picture);
+    // prog_pic: its ProgPic (mjx_prog.h) in the batch's array.
+    uint32_t prog, prog_pic;
 };
 // DevImage::model
 enum ColorModel : uint32_t {
@@ -998,6 +1002,14 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
 // multi-scan pictures: component streams (raster order) -> the picture's stream in MCU order, tile offsets, DC values
 void launch_planar_gather(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint32_t *entries,
                           uint32_t *tile_eoff, int32_t *dcbuf, uint32_t *img_flags, bool copy);
+// progressive pictures: one lane per (scan, restart interval) of one level -- lanes [lane0, lane0 + nlanes) of the batch's array --
+// into the dense store; then the store -> the picture's stream in MCU order, tile offsets, DC values (k_prog_count / _offsets / _copy)
+struct ProgLane;
+struct ProgPic;
+void launch_prog_scan(hipStream_t st, uint32_t nlanes, const ProgLane *lanes, const ProgPic *pics, const DevImage *images,
+                      const uint8_t *bytes, const LutEntry *lut_pool, int16_t *store, uint32_t *img_flags);
+void launch_prog_compact(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const ProgPic *pics, const int16_t *store,
+                         uint32_t *entries, uint32_t *tile_eoff, int32_t *dcbuf, uint32_t *img_flags, int *status);
 void launch_rgb_compare(hipStream_t st, uint32_t npairs, uint64_t max_bytes, const RgbPair *pairs, uint32_t *maxdiff,
                         unsigned long long *ndiff);
 void launch_ref_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images,

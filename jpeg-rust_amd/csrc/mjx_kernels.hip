@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mjx_kernels.h"
+#include "mjx_prog.h"
 
 #include <algorithm>
 
@@ -1980,7 +1981,7 @@ extern "C" __global__ __launch_bounds__(256) void k_planar_count(const DevImage 
     const DevImage &im = images[img];
     const uint32_t T = im.tile_mcus;
     uint32_t bad;
-    if (!im.valid || im.role != 2 || im.planar || tile >= (im.nmcu + T - 1) / T || planar_flags(images, im, img, img_flags, bad)) return;
+    if (!im.valid || im.role != 2 || im.prog || im.planar || tile >= (im.nmcu + T - 1) / T || planar_flags(images, im, img, img_flags, bad)) return;
     const PlanarSlot p = planar_slot(images, im, img, tile, tile_eoff);
     uint32_t total;
     (void)wg_exclusive_scan(p.cnt, s_tmp, &total);
@@ -1993,7 +1994,7 @@ extern "C" __global__ __launch_bounds__(256) void k_planar_offsets(const DevImag
     __shared__ uint32_t s_tmp[4];
     const uint32_t img = blockIdx.x, tid = threadIdx.x;
     const DevImage &im = images[img];
-    if (!im.valid || im.role != 2) return;
+    if (!im.valid || im.role != 2 || im.prog) return;         // (a progressive picture is k_prog_offsets')
     uint32_t bad;
     if (planar_flags(images, im, img, img_flags, bad)) {          // a scan is short (or its chunk unconverged): no picture
         if (tid == 0) img_flags[im.status_idx] = bad;
@@ -2031,7 +2032,7 @@ extern "C" __global__ __launch_bounds__(256) void k_planar_copy(const DevImage *
     const uint32_t img = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
     const DevImage &im = images[img];
     const uint32_t T = im.tile_mcus;
-    if (!im.valid || im.role != 2 || im.planar || tile >= (im.nmcu + T - 1) / T || img_flags[im.status_idx]) return;
+    if (!im.valid || im.role != 2 || im.prog || im.planar || tile >= (im.nmcu + T - 1) / T || img_flags[im.status_idx]) return;
     const PlanarSlot p = planar_slot(images, im, img, tile, tile_eoff);
     uint32_t total;
     const uint32_t at = wg_exclusive_scan(p.cnt, s_tmp, &total);
@@ -2055,6 +2056,101 @@ extern "C" __global__ __launch_bounds__(256) void k_planar_copy(const DevImage *
         const uint32_t e = entries[s_src[lo] + (i - s_at[lo])];
         dst[i] = (e & 0x003fffffu) | (((tile * im.tile_blocks + lo) & 0xffu) << 22);
     }
+}
+
+// Progressive pictures (MJX_OPTS_PROGRESSIVE, mjx_prog.h).  k_prog_scan: plain 64-lane packing, a lane per (scan, restart interval)
+// of one level, the serial routine prog_lane on the scan's bytes and tables where they lie (no LDS); its flags go to the picture's
+// word of img_flags with an ordinary atomic.  One launch per level, in stream order: a scan only reads what earlier levels stored.
+extern "C" __global__ __launch_bounds__(64) void k_prog_scan(const ProgLane *lanes, uint32_t nlanes, const ProgPic *pics,
+                                                              const DevImage *images, const uint8_t *bytes, const LutEntry *lut_pool,
+                                                              int16_t *store, uint32_t *img_flags)
+{
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= nlanes) return;
+    const ProgLane &ln = lanes[i];
+    const DevImage &im = images[ln.img];
+    if (!im.valid || !im.prog) return;
+    const uint32_t flags = prog_lane(ln, pics[ln.pic], bytes, lut_pool + im.lut_off, store);
+    if (flags) atomicOr(img_flags + im.status_idx, flags);
+}
+
+// The dense store -> what k_huff_write + DC prediction leave behind for an interleaved picture (as the k_planar_* trio does for a
+// gathered multi-scan picture): one workgroup per stage-B tile, one lane per block slot.
+//   k_prog_count    the non-zero ACs of the slot's block (16-byte loads; a padding slot has none); the tile's total
+//   k_prog_offsets  one workgroup per picture: exclusive scan of the totals -> tile offsets; a picture whose entries would pass
+//                   ent_cap is flagged, not written
+//   k_prog_copy     a workgroup scan places the blocks' runs; entries in ascending (slot, position), DC values in MCU order
+__device__ __forceinline__ bool prog_tile_slot(const DevImage &im, const ProgPic &pic, uint32_t tile, ProgSlot &s)
+{
+    const uint32_t tid = threadIdx.x, m = tile * im.tile_mcus + tid / im.bpm, k = tid % im.bpm;
+    s.at = 0;
+    s.real = false;
+    if (tid >= im.tile_blocks || m >= im.nmcu) return false;
+    s = prog_slot(pic, m, im.blk_comp[k], im.blk_bx[k], im.blk_by[k]);
+    return true;
+}
+extern "C" __global__ __launch_bounds__(256) void k_prog_count(const DevImage *images, const ProgPic *pics, const int16_t *store,
+                                                                uint32_t *tile_eoff, const uint32_t *img_flags)
+{
+    __shared__ uint32_t s_tmp[4];
+    const DevImage &im = images[blockIdx.y];
+    const uint32_t tile = blockIdx.x, T = im.tile_mcus;
+    if (!im.valid || !im.prog || tile >= (im.nmcu + T - 1) / T || img_flags[im.status_idx]) return;
+    ProgSlot s;
+    const bool inside = prog_tile_slot(im, pics[im.prog_pic], tile, s);
+    const uint32_t cnt = inside && s.real ? prog_block_count(store + s.at) : 0u;
+    uint32_t total;
+    (void)wg_exclusive_scan(cnt, s_tmp, &total);
+    if (threadIdx.x == 0) (tile_eoff + im.tile_off)[tile + 1] = total;
+}
+extern "C" __global__ __launch_bounds__(256) void k_prog_offsets(const DevImage *images, uint32_t *tile_eoff, uint32_t *img_flags, int *status)
+{
+    __shared__ uint32_t s_tmp[4];
+    const uint32_t tid = threadIdx.x;
+    const DevImage &im = images[blockIdx.x];
+    if (!im.valid || !im.prog) return;
+    const uint32_t flags = img_flags[im.status_idx];
+    if (flags) {                                                  // (kProgShort wins: the host reads the flag word first)
+        if (tid == 0 && (flags & kProgBad)) status[im.status_idx] = 1;
+        return;
+    }
+    const uint32_t T = im.tile_mcus, ntiles = (im.nmcu + T - 1) / T;
+    uint32_t *eoff = tile_eoff + im.tile_off;
+    uint32_t run = 0;
+    bool over = false;
+    for (uint32_t t0 = 0; t0 < ntiles; t0 += kWgLanes) {
+        const uint32_t t = t0 + tid;
+        const uint32_t v = t < ntiles ? eoff[t + 1] : 0u;
+        uint32_t total;
+        const uint32_t ex = wg_exclusive_scan(v, s_tmp, &total);
+        if (t < ntiles) eoff[t + 1] = run + ex + v;
+        over = over || total > im.ent_cap - run;                  // (run <= ent_cap here)
+        if (over) break;                                          // (uniform: total and run are the workgroup's)
+        run += total;
+    }
+    if (tid == 0) {
+        eoff[0] = 0;
+        if (over) { img_flags[im.status_idx] = kProgBad; status[im.status_idx] = 1; }
+    }
+}
+extern "C" __global__ __launch_bounds__(256) void k_prog_copy(const DevImage *images, const ProgPic *pics, const int16_t *store,
+                                                               uint32_t *entries, const uint32_t *tile_eoff, int32_t *dcbuf,
+                                                               const uint32_t *img_flags)
+{
+    __shared__ uint32_t s_tmp[4];
+    const DevImage &im = images[blockIdx.y];
+    const uint32_t tile = blockIdx.x, T = im.tile_mcus, tid = threadIdx.x;
+    if (!im.valid || !im.prog || tile >= (im.nmcu + T - 1) / T || img_flags[im.status_idx]) return;
+    ProgSlot s;
+    const bool inside = prog_tile_slot(im, pics[im.prog_pic], tile, s);
+    const bool real = inside && s.real;
+    const uint32_t cnt = real ? prog_block_count(store + s.at) : 0u;
+    uint32_t total;
+    const uint32_t at = wg_exclusive_scan(cnt, s_tmp, &total);
+    if (inside) (dcbuf + im.coef_off)[tile * im.tile_blocks + tid] = real ? int32_t(store[s.at]) : 0;
+    const uint32_t t0 = (tile_eoff + im.tile_off)[tile];
+    // (k_prog_offsets flagged the picture when its total passed ent_cap, and the flag was read above: this is the second check)
+    if (real && cnt && uint64_t(t0) + at + cnt <= im.ent_cap) (void)prog_block_emit(store + s.at, (tile * im.tile_blocks + tid) & 0xffu, entries + im.ent_off + t0 + at);
 }
 
 // DC prediction (decoder.rs:173, 208-210: running sum per component, never reset) as a two-level prefix sum over
@@ -5405,6 +5501,19 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
 #undef MJX_STAGE_B_LAUNCH
 }
 
+void launch_prog_scan(hipStream_t st, uint32_t nlanes, const ProgLane *lanes, const ProgPic *pics, const DevImage *images,
+                      const uint8_t *bytes, const LutEntry *lut_pool, int16_t *store, uint32_t *img_flags)
+{
+    if (!nlanes) return;
+    hipLaunchKernelGGL(k_prog_scan, dim3((nlanes + 63u) / 64u), dim3(64), 0, st, lanes, nlanes, pics, images, bytes, lut_pool, store, img_flags);
+}
+void launch_prog_compact(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const ProgPic *pics, const int16_t *store,
+                         uint32_t *entries, uint32_t *tile_eoff, int32_t *dcbuf, uint32_t *img_flags, int *status)
+{
+    hipLaunchKernelGGL(k_prog_count, dim3(max_tiles, nimg), dim3(256), 0, st, images, pics, store, tile_eoff, img_flags);
+    hipLaunchKernelGGL(k_prog_offsets, dim3(nimg), dim3(256), 0, st, images, tile_eoff, img_flags, status);
+    hipLaunchKernelGGL(k_prog_copy, dim3(max_tiles, nimg), dim3(256), 0, st, images, pics, store, entries, tile_eoff, dcbuf, img_flags);
+}
 void launch_planar_gather(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, uint32_t *entries,
                           uint32_t *tile_eoff, int32_t *dcbuf, uint32_t *img_flags, bool copy)
 {

@@ -7,6 +7,7 @@
 // segment to end-of-file (mod.rs:371-385).  The reference's panics become status codes.
 #include "mjx.h"
 #include "mjx_kernels.h"
+#include "mjx_prog.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -52,7 +53,14 @@ struct ParserState {
         unsigned restart_interval = 0;
         mjx_hufftab dc[3], ac[3];
         uint16_t qt[3][64];            // each component's quantisation table, latched when the SOS was read
+        mjx_scan_prog prog{0, 0, 0, 0}; // progressive files: Ss, Se, Ah, Al of the scan
     };
+    // progressive files (MJX_OPTS_PROGRESSIVE; a SOF2 frame was read): what the scans so far sent of every coefficient
+    // (prog_scan_ok), and each component's quantisation table as its first scan latched it
+    bool accept_prog = false, progressive = false;
+    int8_t coef_bits[3][64];
+    bool qt_latched[3] = {false, false, false};
+    uint16_t prog_qt[3][64];
     std::vector<Part> parts;
     // storage lent by the caller for the de-stuffed scan (mjx_parse_into); null: the parser allocates
     uint8_t *lent = nullptr;
@@ -122,6 +130,7 @@ void read_sof0(const ByteView &f, size_t pos, ParserState &st, bool strict)     
     st.height = f.be16(pos + 1);
     st.width = f.be16(pos + 3);
     const unsigned n = f.at(pos + 5);
+    if (st.progressive && (f.at(pos) != 8 || (n != 1 && n != 3))) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};   // 8-bit, one or three components
     st.frame.clear();
     size_t idx = pos + 6;
     for (unsigned c = 0; c < n; c++, idx += 3) {
@@ -208,15 +217,78 @@ size_t read_part(const ByteView &f, size_t i, const ScanCompSel *sel, unsigned n
     return k;
 }
 
-// All scans of a multi-scan file are read: one block holds the parts array, the scans and the restart offsets.
+// One scan of a progressive file (T.81 G.1.1.1; the rule: prog_scan_ok): checked against the scans in front of it, its tables and
+// restart interval those in force now, its components' quantisation tables latched by the first scan that carries them.  The
+// entropy-coded segment is cut out like a multi-scan file's (read_part's loop).  Returns the offset of the marker behind it.
+size_t read_prog_part(const ByteView &f, size_t i, const ScanCompSel *sel, unsigned n, const mjx_scan_prog &pr, ParserState &st)
+{
+    const mjx_scan_desc *d = st.d;
+    if (st.parts.size() >= 255) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};          // (n_parts is a byte)
+    if (n < 1 || n > 3) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};
+    ParserState::Part part;
+    part.ncomp = uint8_t(n);
+    part.prog = pr;
+    for (unsigned q = 0; q < n; q++) {
+        int ci = -1;
+        for (size_t c = 0; c < st.frame.size(); c++) if (st.frame[c].id == sel[q].id) ci = int(c);
+        if (ci < 0 || sel[q].td > 3 || sel[q].ta > 3) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};
+        part.comp[q] = uint8_t(ci);
+    }
+    if (!mjx::prog_scan_ok(st.coef_bits, unsigned(st.frame.size()), n, part.comp, pr.ss, pr.se, pr.ah, pr.al)) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};
+    for (unsigned q = 0; q < n; q++) {
+        const unsigned ci = part.comp[q];
+        if (pr.ss == 0 && pr.ah == 0) {                       // a first DC scan: the only kind that reads a DC table
+            if (!((d->dc_present >> sel[q].td) & 1)) throw ParseError{MJX_ERR_MISSING_TABLE};
+            part.dc[q] = d->dc[sel[q].td];
+        }
+        if (pr.ss != 0) {
+            if (!((d->ac_present >> sel[q].ta) & 1)) throw ParseError{MJX_ERR_MISSING_TABLE};
+            part.ac[q] = d->ac[sel[q].ta];
+        }
+        if (!st.qt_latched[ci]) {
+            const unsigned tq = st.frame[ci].tq;
+            if (tq > 3 || !((d->qt_present >> tq) & 1)) throw ParseError{MJX_ERR_MISSING_TABLE};
+            std::memcpy(st.prog_qt[ci], d->qt[tq], sizeof st.prog_qt[ci]);
+            st.qt_latched[ci] = true;
+        }
+        part.td[q] = sel[q].td;
+        part.ta[q] = sel[q].ta;
+    }
+    part.restart_interval = st.restart_interval;
+    const size_t total = f.size();
+    size_t k = i;
+    while (k < total) {
+        const uint8_t b = f.at(k);
+        if (b != 0xff) { part.scan.push_back(b); k++; continue; }
+        if (k + 1 >= total) { part.scan.push_back(b); k++; break; }
+        const uint8_t m = f.at(k + 1);
+        if (m == 0x00) { part.scan.push_back(0xff); k += 2; continue; }
+        if (m == 0xff) { k++; continue; }
+        if ((m & 0xf8) == 0xd0 && part.restart_interval) {
+            part.rst.push_back(uint32_t(part.scan.size()));
+            k += 2;
+            continue;
+        }
+        break;
+    }
+    st.parts.push_back(std::move(part));
+    return k;
+}
+
+// All scans of a multi-scan file are read: one block holds the parts array, the scans and the restart offsets (and, for a
+// progressive file, the scans' Ss, Se, Ah, Al).
 void finish_parts(ParserState &st)
 {
     mjx_scan_desc *d = st.d;
     const size_t n = st.parts.size();
     size_t covered = 0;
     for (const ParserState::Part &p : st.parts) covered += p.ncomp;
+    if (st.progressive) {
+        for (size_t c = 0; c < st.frame.size(); c++) if (st.coef_bits[c][0] < 0) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};   // a component without a first DC scan
+    } else
     if (covered != st.frame.size() || st.frame.size() != 3) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};   // a component without a scan
     size_t bytes = (n * sizeof(mjx_scan_part) + 15) & ~size_t(15);
+    if (st.progressive) bytes += (n * sizeof(mjx_scan_prog) + 15) & ~size_t(15);
     for (const ParserState::Part &p : st.parts) bytes += ((p.scan.size() + 32 + 15) & ~size_t(15)) + ((p.rst.size() * 4 + 15) & ~size_t(15));
     uint8_t *buf = static_cast<uint8_t *>(std::malloc(bytes));
     if (!buf) throw ParseError{MJX_ERR_NOMEM};
@@ -230,7 +302,7 @@ void finish_parts(ParserState &st)
         for (unsigned q = 0; q < p.ncomp; q++) {                                  // component c: its latched table in slot c
             const FrameComp &fc = st.frame[p.comp[q]];
             d->comp[p.comp[q]] = mjx_comp{fc.id, fc.h, fc.v, p.comp[q], p.td[q], p.ta[q]};
-            std::memcpy(d->qt[p.comp[q]], p.qt[q], sizeof d->qt[0]);
+            std::memcpy(d->qt[p.comp[q]], st.progressive ? st.prog_qt[p.comp[q]] : p.qt[q], sizeof d->qt[0]);
         }
         mjx_scan_part &o = parts[k];
         std::memset(&o, 0, sizeof o);
@@ -251,6 +323,12 @@ void finish_parts(ParserState &st)
     }
     std::memset(d->qt[3], 0, sizeof d->qt[3]);
     d->qt_present = 7;
+    if (st.progressive) {
+        mjx_scan_prog *pr = reinterpret_cast<mjx_scan_prog *>(buf + off);
+        for (size_t k = 0; k < n; k++) pr[k] = st.parts[k].prog;
+        d->prog = pr;
+        if (st.frame.size() == 1) { d->qt_present = 1; std::memset(d->qt[1], 0, 2 * sizeof d->qt[1]); }
+    }
     d->scan = nullptr;
     d->scan_len = 0;
     d->n_parts = uint8_t(n);
@@ -273,8 +351,15 @@ size_t read_sos(const ByteView &f, size_t pos, ParserState &st, bool strict, boo
     size_t i = pos;
     for (unsigned c = 0; c < n; c++, i += 2) sc.push_back({f.at(i + 1), uint8_t(f.at(i + 2) >> 4), uint8_t(f.at(i + 2) & 15)});
     (void)f.at(i + 3);                                  // Ss, Se, AhAl are read (mod.rs:356-359) and ignored
+    const mjx_scan_prog pr{f.at(i + 1), f.at(i + 2), uint8_t(f.at(i + 3) >> 4), uint8_t(f.at(i + 3) & 15)};
     i += 4;
     if (!st.have_frame) throw ParseError{MJX_ERR_REF_PANIC};                     // mod.rs:388 unwrap
+    if (st.progressive) {                               // every scan of a progressive file is a part (MJX_OPTS_PROGRESSIVE)
+        if (n < 1 || n > 3) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};
+        ScanCompSel sel[3];
+        for (unsigned q = 0; q < n; q++) sel[q] = ScanCompSel{sc[q].id, sc[q].td, sc[q].ta};
+        return read_prog_part(f, i, sel, n, pr, st);
+    }
     // A scan that carries fewer components than the frame is one of several.  The reference decodes the
     // first one with the frame's sampling factors and stops (mod.rs:415-417); strict_ref keeps that.  Otherwise scans of
     // one component, or of two interleaved ones, are collected (read_part) until every component has been seen.
@@ -364,6 +449,8 @@ void walk(const uint8_t *jpeg, size_t len, const mjx_opts &opts, mjx_scan_desc *
     ParserState st;
     st.d = out;
     st.color_file = MJX_OPTS_COLOR(&opts) == MJX_COLOR_FILE && !strict;
+    st.accept_prog = MJX_OPTS_PROGRESSIVE(&opts) == 1 && !strict;
+    std::memset(st.coef_bits, -1, sizeof st.coef_bits);
     st.lent = lent;
     st.lent_cap = lent_cap;
     size_t i = 0;
@@ -380,7 +467,7 @@ void walk(const uint8_t *jpeg, size_t len, const mjx_opts &opts, mjx_scan_desc *
         }
         if (seg == Seg::OTHER_SKIPPABLE || seg == Seg::OTHER_STANDALONE || seg == Seg::OTHER_SOF) {
             if (strict) throw ParseError{MJX_ERR_UNSUPPORTED_MARKER};             // :456-462
-            if (seg == Seg::OTHER_SOF) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};
+            if (seg == Seg::OTHER_SOF && !(m == 0xc2 && st.accept_prog && !st.have_frame)) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};
             if (seg == Seg::OTHER_STANDALONE) { i += 2; continue; }
         }
         const unsigned seglen = f.be16(i + 2);
@@ -389,7 +476,12 @@ void walk(const uint8_t *jpeg, size_t len, const mjx_opts &opts, mjx_scan_desc *
         i += 4;
         switch (seg) {
         case Seg::DQT: read_dqt(f, i, body, out, strict); break;
-        case Seg::SOF0: read_sof0(f, i, st, strict); break;
+        case Seg::SOF0:
+            // (a frame header behind a progressive frame or its scans would replace the components the parts and coef_bits index)
+            if (st.progressive) throw ParseError{MJX_ERR_UNSUPPORTED_FORMAT};
+            read_sof0(f, i, st, strict);
+            break;
+        case Seg::OTHER_SOF: st.progressive = true; read_sof0(f, i, st, strict); break;      // SOF2 with the opt-in (every other frame kind was refused above)
         case Seg::DHT: read_dht(f, i, body, out); break;
         case Seg::SOS: {
             const size_t next = read_sos(f, i, st, strict, opts.device_destuff == MJX_DESTUFF_DEVICE);
@@ -442,7 +534,7 @@ int mjx::parse_into(const uint8_t *jpeg, size_t len, const mjx_opts *opts, mjx_s
     if (!out || (!jpeg && len)) return MJX_ERR_INVALID_ARG;
     mjx_opts o{};
     if (opts) o = *opts;
-    if (MJX_OPTS_COLOR(&o) > MJX_COLOR_FILE) { std::memset(out, 0, sizeof *out); return MJX_ERR_INVALID_ARG; }
+    if (MJX_OPTS_COLOR(&o) > MJX_COLOR_FILE || MJX_OPTS_PROGRESSIVE(&o) > 1) { std::memset(out, 0, sizeof *out); return MJX_ERR_INVALID_ARG; }
     std::memset(out, 0, sizeof *out);
     try {
         walk(jpeg, len, o, out, storage, cap);

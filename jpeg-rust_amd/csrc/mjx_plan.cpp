@@ -1,5 +1,6 @@
 // mjx_plan.cpp -- see mjx_plan.h.
 #include "mjx_plan.h"
+#include "mjx_prog.h"
 #include "mjx_kernels.h"
 
 #include <algorithm>
@@ -174,6 +175,116 @@ void replan_subsequences(ImagePlan &p, uint32_t base_bits, bool allow_long)
     p.himg.nsub = sub;
 }
 
+// The scans of a progressive picture (geometry already planned): the script's rule (prog_scan_ok), the distinct decode tables, the
+// restart intervals of every scan and the levels.
+static int plan_progressive(const mjx_scan_desc &d, ImagePlan &p)
+{
+    int8_t bits[3][64];
+    std::memset(bits, -1, sizeof bits);
+    p.prog = true;
+    p.lut.clear();
+    std::vector<std::pair<const mjx_hufftab *, uint32_t>> built[2];      // [is_dc]: table -> its first entry in p.lut
+    static thread_local LutEntry tmp[2 * kLutPrimarySize + 4096];
+    auto table = [&](const mjx_hufftab &t, bool is_dc, uint32_t *at) -> int {
+        size_t n = 0;
+        for (int i = 0; i < 16; i++) n += t.bits[i];
+        for (const auto &b : built[is_dc])
+            if (std::memcmp(b.first->bits, t.bits, 16) == 0 && std::memcmp(b.first->vals, t.vals, std::min(n, sizeof t.vals)) == 0) { *at = b.second; return 0; }
+        const int k = build_decode_table(t.bits, t.vals, is_dc, tmp, int(sizeof tmp / sizeof tmp[0]), false);
+        if (k < 0) return -k;
+        *at = uint32_t(p.lut.size());
+        built[is_dc].emplace_back(&t, *at);
+        p.lut.insert(p.lut.end(), tmp, tmp + k);
+        while (p.lut.size() % 4) p.lut.push_back(0);
+        return 0;
+    };
+    std::vector<uint32_t> lvl[3];                  // per component: the level of the last scan that touched coefficient k
+    for (uint32_t c = 0; c < 3; c++) lvl[c].assign(64, 0);
+    uint32_t dc_level[3] = {0, 0, 0};              // ... and of its first DC scan
+    for (uint32_t k = 0; k < d.n_parts; k++) {
+        const mjx_scan_part &part = d.parts[k];
+        const mjx_scan_prog &pr = d.prog[k];
+        if (!prog_scan_ok(bits, p.ncomp, part.ncomp, part.comp, pr.ss, pr.se, pr.ah, pr.al)) return MJX_ERR_UNSUPPORTED_FORMAT;
+        if (!part.scan && part.scan_len) return MJX_ERR_INVALID_ARG;
+        if (part.scan_len >= (size_t(1) << 28)) return MJX_ERR_UNSUPPORTED_FORMAT;
+        ProgScanPlan s;
+        s.ss = pr.ss; s.se = pr.se; s.ah = pr.ah; s.al = pr.al;
+        s.ncomp = part.ncomp;
+        s.scan = part.scan;
+        for (uint32_t q = 0; q < part.ncomp; q++) {
+            s.comp[q] = part.comp[q];
+            if (pr.ss == 0 && pr.ah == 0) { const int rc = table(part.dc[q], true, &s.tab[q]); if (rc) return rc; }
+            if (pr.ss != 0 && q == 0) { const int rc = table(part.ac[0], false, &s.tab[0]); if (rc) return rc; }
+            for (uint32_t z = pr.ss; z <= pr.se; z++) s.level = std::max(s.level, lvl[part.comp[q]][z] + 1);
+            // (an AC scan stands behind its component's first DC scan, G.1.1.1: it counts as touching it)
+            if (pr.ss != 0) s.level = std::max(s.level, dc_level[part.comp[q]] + 1);
+        }
+        for (uint32_t q = 0; q < part.ncomp; q++)
+            if (pr.ss == 0 && pr.ah == 0) dc_level[part.comp[q]] = s.level;
+        for (uint32_t q = 0; q < part.ncomp; q++)
+            for (uint32_t z = pr.ss; z <= pr.se; z++) lvl[part.comp[q]][z] = s.level;
+        p.prog_levels = std::max(p.prog_levels, s.level);
+        s.units = part.ncomp == 1 ? p.cbw[part.comp[0]] * p.cbh[part.comp[0]] : p.nmcu;
+        s.per_interval = part.restart_interval ? part.restart_interval : s.units;
+        const uint32_t nint = (s.units + s.per_interval - 1) / s.per_interval;
+        if (part.restart_interval && part.n_restart + 1 < nint) return MJX_ERR_TRUNCATED;       // fewer RSTn markers than intervals
+        if (part.n_restart && !part.restart_offsets) return MJX_ERR_INVALID_ARG;
+        s.cuts.push_back(0);
+        for (uint32_t g = 1; g < nint; g++) {
+            const uint32_t at = part.restart_offsets[g - 1];
+            if (at > part.scan_len || at < s.cuts.back()) return MJX_ERR_INVALID_ARG;
+            s.cuts.push_back(at);
+        }
+        // (markers beyond the last interval's: whatever lies behind the first of them is never looked at)
+        const size_t end = part.restart_interval && part.n_restart >= nint ? part.restart_offsets[nint - 1] : part.scan_len;
+        if (end > part.scan_len || end < s.cuts.back()) return MJX_ERR_INVALID_ARG;
+        s.cuts.push_back(uint32_t(end));
+        p.prog_bytes += part.scan_len;
+        if (pr.ss != 0) p.prog_ac_bytes += part.scan_len;
+        p.pscans.push_back(std::move(s));
+    }
+    for (uint32_t c = 0; c < p.ncomp; c++) if (bits[c][0] < 0) return MJX_ERR_UNSUPPORTED_FORMAT;      // a component without a first DC scan
+    p.lut_plain_n = uint32_t(p.lut.size());
+    return MJX_OK;
+}
+
+uint64_t prog_layout(const ImagePlan &p, uint64_t store0, uint32_t img, uint32_t pic_index, ProgPic &pic,
+                     std::vector<std::vector<ProgLane>> &levels, std::vector<uint8_t> &bytes, uint64_t *bytes_at)
+{
+    const bool append = !bytes_at || *bytes_at == kProgAppend;
+    uint64_t next = append ? bytes.size() : *bytes_at;
+    if (bytes_at) *bytes_at = next;
+    std::memset(&pic, 0, sizeof pic);
+    pic.ncomp = p.ncomp; pic.mcux = p.mcux; pic.mcuy = p.mcuy;
+    for (uint32_t q = 0; q < p.ncomp && q < 3; q++) {
+        pic.h[q] = p.h[q]; pic.v[q] = p.v[q];
+        pic.pbw[q] = p.mcux * p.h[q]; pic.pbh[q] = p.mcuy * p.v[q];
+        pic.cbw[q] = p.cbw[q]; pic.cbh[q] = p.cbh[q];
+        pic.plane[q] = store0;
+        store0 += uint64_t(pic.pbw[q]) * pic.pbh[q] * 64u;
+    }
+    for (const ProgScanPlan &sc : p.pscans) {
+        const uint64_t at = next;
+        next += sc.cuts.back();
+        if (append && sc.cuts.back()) bytes.insert(bytes.end(), sc.scan, sc.scan + sc.cuts.back());
+        if (levels.size() < sc.level) levels.resize(sc.level);
+        for (size_t g = 0; g + 1 < sc.cuts.size(); g++) {
+            ProgLane ln;
+            std::memset(&ln, 0, sizeof ln);
+            ln.byte_off = at + sc.cuts[g];
+            ln.nbytes = sc.cuts[g + 1] - sc.cuts[g];
+            ln.first = uint32_t(g) * sc.per_interval;
+            ln.count = std::min(sc.per_interval, sc.units - ln.first);
+            ln.img = img;
+            ln.pic = pic_index;
+            for (uint32_t q = 0; q < 3; q++) { ln.tab[q] = sc.tab[q]; ln.comp[q] = sc.comp[q]; }
+            ln.ss = sc.ss; ln.se = sc.se; ln.ah = sc.ah; ln.al = sc.al; ln.ncomp = sc.ncomp;
+            levels[sc.level - 1].push_back(ln);
+        }
+    }
+    return store0;
+}
+
 int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool scan_part)
 {
     p = ImagePlan{};
@@ -191,8 +302,14 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     const bool color_file = MJX_OPTS_COLOR(&opts) == MJX_COLOR_FILE;
     if (color_file && (opts.layout == MJX_LAYOUT_REF_COMPAT || opts.strict_ref)) return fail(MJX_ERR_INVALID_ARG);
     const bool four = color_file && !scan_part && d.ncomp == 4;
-    const bool gather = d.n_parts != 0;            // the picture of a multi-scan file: geometry only, no scan of its own
-    if (gather) {
+    if (MJX_OPTS_PROGRESSIVE(&opts) > 1) return fail(MJX_ERR_INVALID_ARG);
+    const bool prog = d.prog != nullptr && !scan_part;      // a progressive file: the opt-in, STANDARD layout without strict_ref
+    if (prog && (opts.layout == MJX_LAYOUT_REF_COMPAT || opts.strict_ref)) return fail(MJX_ERR_INVALID_ARG);
+    if (prog && MJX_OPTS_PROGRESSIVE(&opts) != 1) return fail(MJX_ERR_UNSUPPORTED_FORMAT);
+    const bool gather = d.n_parts != 0 || prog;    // the picture of a multi-scan file: geometry only, no scan of its own
+    if (prog) {
+        if (!d.parts || d.n_parts < 1 || (d.ncomp != 1 && d.ncomp != 3)) return fail(MJX_ERR_UNSUPPORTED_FORMAT);
+    } else if (gather) {
         if (!d.parts || d.n_parts < 2 || d.n_parts > 3 || d.ncomp != 3) return fail(MJX_ERR_UNSUPPORTED_FORMAT);
         if (opts.layout == MJX_LAYOUT_REF_COMPAT || opts.strict_ref) return fail(MJX_ERR_UNSUPPORTED_FORMAT);   // the reference stops after scan 1
     } else if (!d.scan) {
@@ -311,6 +428,10 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
             p.cbw[c] = ((p.width * p.h[c] + p.hmax - 1) / p.hmax + 7) / 8;
             p.cbh[c] = ((p.height * p.v[c] + p.vmax - 1) / p.vmax + 7) / 8;
         }
+    }
+    if (prog) {
+        const int rc = plan_progressive(d, p);
+        if (rc != MJX_OK) return fail(rc);
     }
     int dc_base[4] = {-1, -1, -1, -1}, ac_base[4] = {-1, -1, -1, -1};
     if (!gather) {
@@ -804,7 +925,7 @@ void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_ou
 
 void plan_input(const mjx_scan_desc &d, const mjx_opts &opts, std::vector<ImagePlan> &out)
 {
-    if (d.n_parts == 0) {
+    if (d.n_parts == 0 || d.prog) {           // (a progressive picture is one plan: its scans are no pictures of their own)
         out.emplace_back();
         plan_image(d, opts, out.back());
         return;

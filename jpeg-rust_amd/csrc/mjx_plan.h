@@ -11,6 +11,18 @@
 
 namespace mjx {
 
+// One scan of a progressive picture as the planner hands it to the batch (MJX_OPTS_PROGRESSIVE, mjx_prog.h)
+struct ProgScanPlan {
+    uint8_t ss = 0, se = 0, ah = 0, al = 0;
+    uint8_t ncomp = 0, comp[3] = {0, 0, 0};
+    uint32_t level = 1;                            // 1 + the largest level of an earlier scan that touches a common (component, coefficient);
+                                                   // an AC scan counts its component's first DC scan among them
+    uint32_t tab[3] = {0, 0, 0};                   // entries into ImagePlan::lut: the DC table per scan component, or the AC table in [0]
+    const uint8_t *scan = nullptr;                 // de-stuffed, restart markers taken out
+    uint32_t units = 0, per_interval = 0;          // MCUs (interleaved) or blocks of the component's own grid; units per restart interval
+    std::vector<uint32_t> cuts;                    // byte offsets of the intervals' starts, and the scan's length behind them
+};
+
 struct ImagePlan {
     int status = MJX_OK;
     uint32_t width = 0, height = 0;
@@ -118,6 +130,13 @@ struct ImagePlan {
     uint32_t nparts = 0;                               // role 2: scans in front of the picture; role 1: scans of its file
     uint32_t part_idx = 0;                             // role 1: which of them this is (the picture's plan lies nparts - part_idx plans behind)
     uint32_t src_part[3] = {0, 0, 0}, src_comp[3] = {0, 0, 0};   // ... which of them carries component c, as its n-th component
+    // Progressive pictures (MJX_OPTS_PROGRESSIVE): a role-2 picture with no plans in front of it (nparts = 0).  Its scans are decoded
+    // serially, a lane per restart interval, level by level into a dense store and compacted into the stream stage B reads.  `lut`
+    // holds the scans' distinct tables one behind the other, each as build_decode_table left it.
+    bool prog = false;
+    std::vector<ProgScanPlan> pscans;
+    uint32_t prog_levels = 0;
+    uint64_t prog_bytes = 0, prog_ac_bytes = 0;    // bytes of all scans / of the AC scans (a non-zero AC costs two bits of one at least)
 };
 
 // What stage B and the passes behind it do with a planned picture: DevImage's fields of the same names (mjx_kernels.h), decided
@@ -180,6 +199,18 @@ int plan_planes_of_input(std::vector<ImagePlan> &plans, const mjx_planes *pl, si
 int resize_opts(uint32_t width, uint32_t height, const mjx_opts &opts_i, const mjx_resize &rs, mjx_opts &eff, mjx_rect &rect);
 void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_output *out, const mjx_resize *rs, size_t i,
                     std::vector<ImagePlan> &plans, uint32_t code = 1);
+
+// A planned progressive picture as the device sees it (mjx_prog.h): its ProgPic, planes laid out from element `store0` of the chunk's
+// dense store on; its scans' bytes appended to `bytes`; one lane per (scan, restart interval) appended to levels[level - 1], for image
+// `img` of the chunk and entry `pic_index` of the picture array.  Returns the first store element behind the picture.  The batch
+// (mjx_api.hip) and the host emulation (tests/emul/prog_emul.cpp) both lay a picture out here.
+struct ProgPic;
+struct ProgLane;
+// bytes_at: null, or where the scans' bytes lie -- *bytes_at == kProgAppend appends them and notes the place, any other value says
+// that they are at that offset of `bytes` already (the copies of one picture in a tiled batch share one copy of its scans).
+constexpr uint64_t kProgAppend = ~uint64_t(0);
+uint64_t prog_layout(const ImagePlan &p, uint64_t store0, uint32_t img, uint32_t pic_index, ProgPic &pic,
+                     std::vector<std::vector<ProgLane>> &levels, std::vector<uint8_t> &bytes, uint64_t *bytes_at = nullptr);
 
 // mjx_parse.cpp: mjx_parse with caller-lent storage for the de-stuffed scan (see there)
 int parse_into(const uint8_t *jpeg, size_t len, const mjx_opts *opts, mjx_scan_desc *out, uint8_t *storage, size_t cap);
