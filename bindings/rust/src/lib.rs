@@ -347,6 +347,13 @@ extern "C" {
     pub fn mjx_batch_copy_planes(b: *mut mjx_batch, i: usize, host: *mut c_void, cap_bytes: usize) -> c_int;
     pub fn mjx_decode_batch_planes(ctx: *mut mjx_ctx, jpegs: *const *const u8, lens: *const usize, n: usize, opts: *const mjx_opts,
                                    threads: c_uint, planes: *const mjx_planes, status: *mut c_int, b: *mut *mut mjx_batch) -> c_int;
+    pub fn mjx_batch_create_planes_orient(ctx: *mut mjx_ctx, descs: *const mjx_scan_desc, n: usize, opts: *const mjx_opts, planes: *const mjx_planes,
+                                          rs: *const mjx_resize, orient: *const mjx_orient, b: *mut *mut mjx_batch, status: *mut c_int) -> c_int;
+    pub fn mjx_decode_batch_planes_orient(ctx: *mut mjx_ctx, jpegs: *const *const u8, lens: *const usize, n: usize, opts: *const mjx_opts,
+                                          threads: c_uint, planes: *const mjx_planes, rs: *const mjx_resize, orient: *const mjx_orient,
+                                          status: *mut c_int, b: *mut *mut mjx_batch) -> c_int;
+    pub fn mjx_planes_orient_layout(desc: *const mjx_scan_desc, opts: *const mjx_opts, planes: *const mjx_planes, rs: *const mjx_resize, code: u8,
+                                    i: usize, layout: *mut mjx_plane_layout, scale_denom: *mut u8, rect: *mut mjx_rect) -> c_int;
     pub fn mjx_batch_create_resize(ctx: *mut mjx_ctx, descs: *const mjx_scan_desc, n: usize, opts: *const mjx_opts, out: *const mjx_output,
                                    rs: *const mjx_resize, b: *mut *mut mjx_batch, status: *mut c_int) -> c_int;
     pub fn mjx_decode_batch_resize(ctx: *mut mjx_ctx, jpegs: *const *const u8, lens: *const usize, n: usize, opts: *const mjx_opts,

@@ -308,8 +308,44 @@ typedef struct mjx_planes {
  * from there to the last plane's end, mjx_batch_bytes' rgb_bytes counts the bytes written, mjx_batch_image_info, _image_roi and
  * _image_scale are as for a packed picture, mjx_batch_output_channels answers 3, mjx_batch_tile carries the description along
  * (library-owned output only), mjx_batch_copy_coefs is unchanged.
- * Not built: resize and orientation on planes (the entry points take neither); mjx_decode and the pool with planes; a dedicated
- * 4:2:0 plane form (4:2:0 takes the generic form); skipping anything in the entropy stage. */
+ * Not built: mjx_decode and the pool with planes; a dedicated 4:2:0 plane form (4:2:0 takes the generic form); skipping anything in
+ * the entropy stage.
+ *
+ * Planes with a resize and / or an orientation (mjx_batch_create_planes_orient, mjx_decode_batch_planes_orient; mjx_resize and
+ * mjx_orient are described below).  For picture i, c is the resolved orientation code (the file's tag with from_exif, then
+ * extra[i]), S the stored picture at the call's scale s, D = orient_c(S) the picture that leaves; rois[i] is in D's coordinates
+ * (full-size D with auto_scale), as for every oriented call.
+ * The intermediate.  The rectangle is mapped to S (orient_rect_to_stored); with auto_scale s is picked by the resize's rule on the
+ * picture-level rectangle and target, the target's axes swapped for codes 5 .. 8, exactly as for an oriented resized picture.  The
+ * picture is then planned as the library-owned, dense, uint8, non-interleaved plane decode at (s, R_S): stage B reads only the tiles
+ * that touch the rectangle, and its planes P_0 .. P_2 -- plane_span of R_S, as above -- lie in the batch's own memory.
+ * Without a resize plane k of the output is orient_c(P_k), the table of mjx_orient applied to the plane as a one-channel picture: for
+ * codes 5 .. 8 a plane's width and height swap, so a 4:2:2 file leaves with 4:4:0 planes.  Elements go through the dtype rule above,
+ * fmaf((float)u8, scale[k], bias[k]) by COMPONENT; a uint8 output is a permutation of the intermediate's bytes.  With
+ * interleave_chroma the pair at (X, Y) of plane 1 is (orient_c(P_1)[Y][X], orient_c(P_2)[Y][X]).
+ * With a resize to W x H (D's axes) component k's factors in D are (h_k, v_k) for codes 1 .. 4 and (v_k, h_k) for 5 .. 8, the maxima
+ * likewise, and the plane's target is W_k x H_k = ceil(W h'_k / hmax') x ceil(H v'_k / vmax') -- the whole-picture formula above for a
+ * W x H picture; a one-component file has one plane, W x H.  Output plane k is mjx_resize's rule applied to orient_c(P_k) as a
+ * one-channel picture, n_in -> n_out per axis being the oriented plane's size -> (W_k, H_k): the chosen filter and antialias, float32
+ * sums with whole-number numerators and one division, U8 rint clamped, F32 fmaf(v, scale[k], bias[k]) on the unrounded v, F16 that
+ * value rounded -- bit for bit what the luminance resize of the one-component file that carries component k's blocks gives for that
+ * rectangle and target.  A plane target equal to the oriented plane's own size is bit for bit the un-resized output, in every dtype.
+ * Siting: each plane is resampled over its OWN span.  Where the rectangle's edges are not multiples of hmax / h_k (vmax / v_k) the
+ * chroma span is the outward-rounded one of plane_span, a little wider than the luma span it belongs to: chroma then registers to
+ * luma within less than one chroma sample.  A rectangle aligned to the MCU's chroma grid has no such shift.
+ * Fit modes: MJX_FIT_COVER rewrites the rectangle before anything else, so the output is byte for byte the stretch call's on the
+ * rewritten rectangle; MJX_FIT_CONTAIN gives the picture MJX_ERR_INVALID_ARG (a pad per component plane is not built).
+ * MJX_PIXELS_LIBJPEG composes as it does with planes: full size only, rounded samples; with auto_scale every picture takes scale 1
+ * and its rectangle as given, as in any resize call with that option.
+ * rs == NULL and orient == NULL: the call plans, launches and writes exactly what mjx_batch_create_planes does; c == 1 without a
+ * resize is planned exactly as the planes call (no intermediate, no further launch).
+ * Per picture, MJX_ERR_INVALID_ARG (the others unaffected, nothing written): every refusal listed for mjx_planes, mjx_resize and
+ * mjx_orient; dst[i].width / height other than the LEAVING planes'; interleave_chroma with unequal chroma factors; MJX_FIT_CONTAIN.
+ * Whole-call failures are mjx_orient's and mjx_planes's own.
+ * Such a batch: mjx_batch_plane_info and mjx_batch_copy_planes speak of the leaving planes, mjx_batch_image_info of the leaving
+ * picture (D's rectangle, or W x H), mjx_batch_image_roi, mjx_batch_resize_rect and mjx_batch_image_scale of the intermediate in S's
+ * coordinates, mjx_batch_image_orientation gives c, mjx_batch_bytes' rgb_bytes counts the bytes written, mjx_batch_tile carries
+ * everything along (library-owned only).  Not built: MJX_FIT_CONTAIN on planes, per-picture targets, fusing the resize into stage B. */
 
 /* ---- resize on the device: every picture of a call leaves at one target size -------------------------------------------
  * With a resize description (mjx_batch_create_resize, mjx_decode_batch_resize) picture i is decoded as a packed picture at a
@@ -416,7 +452,7 @@ typedef struct mjx_resize {
  * Mapping a source coordinate to the output (boxes, key points): with (asked, inner) from mjx_resize_fit_plan, a point (px, py) of D
  * in asked's coordinates lies at  inner.x + (px - asked.x) inner.w / asked.w,  inner.y + (py - asked.y) inner.h / asked.h  of the
  * target (pixel centres: add 0.5 before and take it off after).
- * Not built: per-picture target sizes, a fractional crop ratio, pad modes other than a constant colour, fit modes for planes. */
+ * Not built: per-picture target sizes, a fractional crop ratio, pad modes other than a constant colour, contain for planes. */
 
 /* ---- orientation on the device: EXIF orientation, with per-picture flips on top -----------------------------------------
  * A camera file stores its pixels as the sensor saw them and names, in EXIF tag 0x0112, one of eight ways to turn them upright.
@@ -640,6 +676,19 @@ int mjx_batch_plane_info(const mjx_batch *b, size_t i, uint32_t *nplanes, mjx_pl
 /* Copy picture i's library-owned planes to host memory, dense, planes back to back, as mjx_planes_layout sizes them; cap_bytes
  * smaller than that, caller-owned planes or a batch without a plane description: MJX_ERR_INVALID_ARG. */
 int mjx_batch_copy_planes(mjx_batch *b, size_t i, void *host, size_t cap_bytes);
+/* mjx_batch_create_planes with a resize and / or an orientation description (planes with a resize and / or an orientation, above);
+ * rs == NULL and orient == NULL: mjx_batch_create_planes itself.  from_exif = 1 is MJX_ERR_INVALID_ARG for the call, as in
+ * mjx_batch_create_orient: descriptors carry no file bytes. */
+int mjx_batch_create_planes_orient(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_planes *planes,
+                                   const mjx_resize *rs, const mjx_orient *orient, mjx_batch **b, int *status);
+/* Host-only, from the planner itself (the routine the two calls above plan with): picture `desc` as input i of a call with these
+ * options (rois[i], or rois[0] when n_rois <= 1), this plane description, this resize (or NULL) and the resolved code `code` -- the
+ * LEAVING planes' sizes and pitches (library-owned planes are dense and back to back in plane order: the pitch is the row and
+ * layout->dev stays NULL; caller-owned: dst[i]'s own pitches and pointers), the scale the picture is decoded at and the rectangle of
+ * the stored picture its intermediate covers at that scale.  With rs == NULL and code == 1 the layout is mjx_planes_layout's member
+ * for member.  Returns the picture's status. */
+int mjx_planes_orient_layout(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_planes *planes, const mjx_resize *rs, uint8_t code,
+                             size_t i, mjx_plane_layout *layout, uint8_t *scale_denom, mjx_rect *rect);
 
 /* mjx_batch_create_out with a resize description (above); rs == NULL: mjx_batch_create_out itself.  out == NULL with a resize:
  * interleaved u8 R,G,B, library-owned. */
@@ -768,7 +817,7 @@ enum {
                              MJX_K_HUFF_SYNC and the decode of MJX_K_HUFF_WRITE */
     MJX_K_HUFF_PREFIX = 9,/* ... the prefixes of the subsequences whose entry state was wrong, and block words -> DC differences + tile offsets */
     MJX_K_RESIZE = 10,    /* the pass behind stage B that brings a picture to the form it leaves in: resize on the device (k_resize_out),
-                             orientation (k_orient_out, k_resize_orient), MJX_PIXELS_LIBJPEG's upsampling and colour step (k_upsample_color).  No launches
+                             orientation (k_orient_out, k_resize_orient), the same on planes (k_orient_planes, k_resize_planes), MJX_PIXELS_LIBJPEG's upsampling and colour step (k_upsample_color).  No launches
                              for a batch without a resized or oriented picture or that option */
     MJX_K_COUNT = 11
 };
@@ -813,6 +862,11 @@ int mjx_decode_batch_orient(mjx_ctx *ctx, const uint8_t *const *jpegs, const siz
  * MJX_ERR_INVALID_ARG. */
 int mjx_decode_batch_planes(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
                             unsigned threads, const mjx_planes *planes, int *status, mjx_batch **b);
+/* mjx_decode_batch_planes with a resize and / or an orientation description: dst[i], rois[i], the file's tag (from_exif: the worker
+ * that plans file i reads it) and extra[i] follow file i through the groups.  Both NULL: mjx_decode_batch_planes. */
+int mjx_decode_batch_planes_orient(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
+                                   unsigned threads, const mjx_planes *planes, const mjx_resize *rs, const mjx_orient *orient, int *status,
+                                   mjx_batch **b);
 
 /* ---- multi-GPU front: one context + one host thread + one work queue per device, no collective ----------
  * Pictures are independent (decoder.rs:162-343 touches only `self`), so a list of files shards over the GPUs of a node

@@ -254,6 +254,10 @@ SYMBOLS = {
     "mjx_planes_layout": (_int, [_P(ScanDesc), _P(Opts), _P(PlanesDesc), _sz, _P(PlaneLayout), _P(ctypes.c_uint32), _P(_sz)]),
     "mjx_batch_plane_info": (_int, [_vp, _sz, _P(ctypes.c_uint32), _P(PlaneLayout), _P(ctypes.c_uint8), _P(ctypes.c_uint8)]),
     "mjx_batch_copy_planes": (_int, [_vp, _sz, _vp, _sz]),
+    "mjx_batch_create_planes_orient": (_int, [_vp, _P(ScanDesc), _sz, _P(Opts), _P(PlanesDesc), _P(ResizeDesc), _P(OrientDesc), _P(_vp), _P(_int)]),
+    "mjx_decode_batch_planes_orient": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(PlanesDesc), _P(ResizeDesc), _P(OrientDesc),
+                                              _P(_int), _P(_vp)]),
+    "mjx_planes_orient_layout": (_int, [_P(ScanDesc), _P(Opts), _P(PlanesDesc), _P(ResizeDesc), ctypes.c_uint8, _sz, _P(PlaneLayout), _P(ctypes.c_uint8), _P(Rect)]),
     "mjx_batch_create_resize": (_int, [_vp, _P(ScanDesc), _sz, _P(Opts), _P(OutputDesc), _P(ResizeDesc), _P(_vp), _P(_int)]),
     "mjx_decode_batch_resize": (_int, [_vp, _P(ctypes.c_char_p), _P(_sz), _sz, _P(Opts), ctypes.c_uint, _P(OutputDesc), _P(ResizeDesc), _P(_int), _P(_vp)]),
     "mjx_resize_plan": (_int, [_P(ScanDesc), _P(Opts), _P(ResizeDesc), _sz, _P(ctypes.c_uint8), _P(Rect), _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
@@ -695,11 +699,28 @@ class ParsedScan:
         _check(lib().mjx_output_layout(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(lay), ctypes.byref(nb)), "mjx_output_layout")
         return dict(width=lay.width, height=lay.height, row_pitch=lay.row_pitch, plane_pitch=lay.plane_pitch, bytes=nb.value, dev=lay.dev or 0)
 
-    def planes_layout(self, planes, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD, pixels=None, strict_ref=False, color=None, progressive=False):
+    def planes_layout(self, planes, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD, pixels=None, strict_ref=False, color=None, progressive=False,
+                      resize=None, code=None):
         """mjx_planes_layout (host only) -> dict(nplanes, width, height, row_pitch, dev -- a list of three each --, bytes): the planes a
-        decode of this picture as input i of a call with this Planes would write; pitches in elements, sizes in samples."""
+        decode of this picture as input i of a call with this Planes would write; pitches in elements, sizes in samples.
+        resize (a Resize) and / or code (the resolved orientation, 1 .. 8): mjx_planes_orient_layout -- the planes that LEAVE such a
+        call (roi in the turned picture's coordinates, full size with auto_scale), and on top of the keys above `scale`, the scale the
+        picture is decoded at, and `rect` = (x, y, w, h), the rectangle of the stored picture its intermediate covers."""
         o = _opts(layout=layout, scale=scale, rois=roi, pixels=pixels, strict_ref=strict_ref, color=color, progressive=progressive)
         keep, ref = _planes_ref(planes)
+        if resize is not None or code is not None:
+            keep_rs, rs_ref = _rs_ref(resize)
+            lay, s, r = PlaneLayout(), ctypes.c_uint8(), Rect()
+            _check(lib().mjx_planes_orient_layout(ctypes.byref(self.desc), ctypes.byref(o), ref, rs_ref, 1 if code is None else int(code), int(i),
+                                                  ctypes.byref(lay), ctypes.byref(s), ctypes.byref(r)), "mjx_planes_orient_layout")
+            d = keep
+            ncomp = int(self.desc.ncomp)
+            il = bool(d.interleave_chroma) and ncomp == 3
+            nplanes = 1 if ncomp == 1 else 2 if il else 3
+            esz = (1, 2, 4)[d.dtype]
+            total = sum(((lay.height[c] - 1) * lay.row_pitch[c] + lay.width[c] * (2 if il and c == 1 else 1)) * esz for c in range(nplanes))
+            return dict(nplanes=nplanes, width=list(lay.width), height=list(lay.height), row_pitch=list(lay.row_pitch),
+                        dev=[v or 0 for v in lay.dev], bytes=total, scale=s.value, rect=(r.x, r.y, r.w, r.h))
         lay, np_, nb = PlaneLayout(), ctypes.c_uint32(), _sz()
         _check(lib().mjx_planes_layout(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(lay), ctypes.byref(np_), ctypes.byref(nb)), "mjx_planes_layout")
         return dict(nplanes=np_.value, width=list(lay.width), height=list(lay.height), row_pitch=list(lay.row_pitch),
@@ -802,7 +823,9 @@ class Batch:
         pixels: "libjpeg" (PIXELS_LIBJPEG) -- the pictures libjpeg-based decoders give: rounded samples, fancy chroma upsampling,
         integer colour tables (STANDARD layout at full size only); everything above composes with it; tile() keeps it.
         planes: a Planes -- the pictures leave as their component planes (planes(i), plane_info(i)); scale, rois and pixels apply,
-        output, resize and orient do not go with it; tile() keeps it.
+        output does not go with it; tile() keeps it.  With resize and / or orient (mjx_batch_create_planes_orient) every plane is
+        turned and resampled to its own share of the target: planes(i) and plane_info(i) give the planes that leave, info(i) the
+        picture that leaves, scale(i), roi(i) and rect(i) what was decoded for it, orientation(i) the code; fit="contain" is refused.
         color: "file" (COLOR_FILE) -- what a file's components are comes from the file (JFIF / Adobe segments, component ids:
         mjx.h, mjx_opts.color): RGB, CMYK and YCCK files decode to R,G,B (color_model(i) says which a picture was); the scans must
         have been parsed with color="file" too.  Luminance output, planes and pixels="libjpeg" refuse such pictures
@@ -820,9 +843,27 @@ class Batch:
         st = (_int * max(n, 1))()
         o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois, pixels=pixels, color=color, progressive=progressive)
         keep, ref = _out_ref(output)
-        if planes is not None:
-            if output is not None or resize is not None or orient is not None:
-                raise MjxError(ERR_INVALID_ARG, "planes go without output, resize and orient")
+        if planes is not None and (resize is not None or orient is not None):
+            if output is not None:
+                raise MjxError(ERR_INVALID_ARG, "planes go without output")
+            keep_pl, pl_ref = _planes_ref(planes)
+            keep_rs, rs_ref = _rs_ref(resize)
+            od_ref = None
+            if orient is not None:
+                if orient.exif:
+                    if datas is None or len(datas) != n:
+                        raise MjxError(ERR_INVALID_ARG, "Orient(exif=True) needs the files' bytes: datas")
+                    extra = orient.codes(n) or [1] * n
+                    if len(extra) != n:
+                        raise MjxError(ERR_INVALID_ARG, "Orient(extra=...): %d codes for %d pictures" % (len(extra), n))
+                    orient = Orient(False, [orient_compose(exif_orientation(d), e) if 1 <= e <= 8 else e for d, e in zip(datas, extra)])
+                keep_or, od = orient.desc(n, exif=False)
+                od_ref = ctypes.byref(od)
+            _check(lib().mjx_batch_create_planes_orient(ctx.h, arr, n, ctypes.byref(o), pl_ref, rs_ref, od_ref, ctypes.byref(self.h), st),
+                   "mjx_batch_create_planes_orient")
+        elif planes is not None:
+            if output is not None:
+                raise MjxError(ERR_INVALID_ARG, "planes go without output")
             keep_pl, pl_ref = _planes_ref(planes)
             _check(lib().mjx_batch_create_planes(ctx.h, arr, n, ctypes.byref(o), pl_ref, ctypes.byref(self.h), st), "mjx_batch_create_planes")
         elif orient is not None:
@@ -1202,7 +1243,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     device_destuff: the host copies the entropy-coded bytes as they are; de-stuffing, restart markers and the scan's length
     are found on the GPU.  output: an Output (mjx_decode_batch_out) -- see Batch.  resize: a Resize (mjx_decode_batch_resize).  orient: an Orient
     (mjx_decode_batch_orient): the files' EXIF orientation and / or a code per file on top.  planes: a Planes (mjx_decode_batch_planes) --
-    the pictures leave as their component planes; output, resize and orient do not go with it."""
+    the pictures leave as their component planes; output does not go with it, resize and orient do (mjx_decode_batch_planes_orient)."""
     n = len(datas)
     arr = (ctypes.c_char_p * max(n, 1))(*[bytes(d) for d in datas])
     lens = (_sz * max(n, 1))(*[len(d) for d in datas])
@@ -1211,9 +1252,15 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     h = _vp()
     o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, color=color, progressive=progressive)
     if planes is not None:
-        if output is not None or resize is not None or orient is not None:
-            raise MjxError(ERR_INVALID_ARG, "planes go without output, resize and orient")
+        if output is not None:
+            raise MjxError(ERR_INVALID_ARG, "planes go without output")
         keep_pl, pl_ref = _planes_ref(planes)
+        if resize is not None or orient is not None:
+            keep_rs, rs_ref = _rs_ref(resize)
+            keep_or, od = orient.desc(n) if orient is not None else (None, None)
+            _check(lib().mjx_decode_batch_planes_orient(ctx.h, arr, lens, n, ctypes.byref(o), int(threads), pl_ref, rs_ref,
+                                                        ctypes.byref(od) if od is not None else None, st, ctypes.byref(h)), "mjx_decode_batch_planes_orient")
+            return Batch(ctx, _handle=h), list(st)[:n]
         _check(lib().mjx_decode_batch_planes(ctx.h, arr, lens, n, ctypes.byref(o), int(threads), pl_ref, st, ctypes.byref(h)), "mjx_decode_batch_planes")
         return Batch(ctx, _handle=h), list(st)[:n]
     if orient is not None:
@@ -1314,13 +1361,18 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
     return status
 
 
-def decode_planes_into(ctx, datas, y, cb=None, cr=None, cbcr=None, scale=1, rois=None, mean=None, std=None, threads=0, device_destuff=None, pixels=None):
+def decode_planes_into(ctx, datas, y, cb=None, cr=None, cbcr=None, scale=1, rois=None, mean=None, std=None, threads=0, device_destuff=None, pixels=None,
+                       resize=None, orient=None):
     """Decodes the files' component planes straight into torch tensors on the context's device: decode_planes_into(ctx, datas, y, cb,
     cr) with y N x Hy x Wy, cb and cr N x Hc x Wc, or decode_planes_into(ctx, datas, y, cbcr=t) with t N x Hc x Wc x 2 (NV12's second
     plane); one-component files take y alone.  All pictures of the call have one size and layout; tensors are of one dtype (uint8,
     float16, float32); the innermost dimension is dense, rows may be padded and the pictures of a tensor must not overlap.  Float
     tensors take (v / 255 - mean) / std per COMPONENT.  torch's current stream is synchronised before the call and the planes are
-    complete when this returns.  -> the per-picture statuses."""
+    complete when this returns.  -> the per-picture statuses.
+    resize: True, or a Resize (its antialias, auto_scale, filter and fit mode; a size, if it names one, must be y's) -- the target is
+    y's H x W and the files may differ in size; they still share one sampling layout, since the tensors have one chroma size: a
+    picture of another layout gets ERR_INVALID_ARG and its slot is untouched.  orient: an Orient -- the planes are turned on the
+    device; the tensors' sizes and rois speak of the turned pictures."""
     import torch
     n = len(datas)
     if cbcr is not None and (cb is not None or cr is not None):
@@ -1351,7 +1403,14 @@ def decode_planes_into(ctx, datas, y, cb=None, cr=None, cbcr=None, scale=1, rois
     dst = [([(ptr + i * step, pitch) for ptr, step, pitch in per_plane], sizes) for i in range(n)]
     fmt = Planes(names[y.dtype], interleave=cbcr is not None, mean=mean, std=std, dst=dst)
     torch.cuda.current_stream(y.device).synchronize()
-    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, planes=fmt)
+    rs = None
+    if resize is not None and resize is not False:
+        w, h = sizes[0]
+        rs = Resize(w, h) if resize is True else resize.sized(w, h)
+        if resize is not True and (resize.width or resize.height) and (resize.width, resize.height) != (w, h):
+            raise MjxError(ERR_INVALID_ARG, "resize to %d x %d into a tensor of %d x %d" % (resize.width, resize.height, w, h))
+    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, planes=fmt,
+                                 resize=rs, orient=orient)
     batch.close()
     return status
 
@@ -1500,11 +1559,12 @@ def orient_plan(data, code, resize=None, roi=None, scale=1):
         scan.close()
 
 
-def planes_layout(data, planes, i=0, roi=None, scale=1, pixels=None):
-    """Host only: the planes a decode of this file as input i with this Planes would write -> see ParsedScan.planes_layout."""
+def planes_layout(data, planes, i=0, roi=None, scale=1, pixels=None, resize=None, code=None):
+    """Host only: the planes a decode of this file as input i with this Planes would write -> see ParsedScan.planes_layout (resize, code:
+    the planes that leave a call with a resize and / or an orientation)."""
     scan = ParsedScan(data)
     try:
-        return scan.planes_layout(planes, i=i, roi=roi, scale=scale, pixels=pixels)
+        return scan.planes_layout(planes, i=i, roi=roi, scale=scale, pixels=pixels, resize=resize, code=code)
     finally:
         scan.close()
 

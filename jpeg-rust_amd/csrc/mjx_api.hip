@@ -191,6 +191,8 @@ struct Chunk {
                                    // picture -- a lane per pixel written, per plane sample for kSinkYcc (kSinkPlanes has no 1/8)
     uint32_t max_pass_tiles[kPostPasses][kFilterCount] = {};   // the passes behind stage B: workgroups for the chunk's largest picture of each pass
                                    // and filter kind (DevImage::rs_filter; [0] for the passes that have no filter); 0: launches nothing
+    uint32_t max_plane_copy_tiles = 0, max_plane_resize_tiles[kFilterCount] = {};   // YCbCr planes with an orientation / a resize: workgroups of
+                                   // k_orient_planes / k_resize_planes (per filter kind) for the chunk's largest leaving plane; 0: no launch
     uint32_t max_fit_wgs = 0;      // fit modes: workgroups of k_fit_pad for the chunk's largest letterboxed picture (DevImage::fit_on); 0: no launch
     uint32_t max_b_tiles = 0;      // tiles the workgroups of stage B walk in the chunk's largest picture: all its tiles, or those of its
                                    // rectangle's MCU rows (DevImage::roi_ntiles) -- max_tiles without rectangles
@@ -303,6 +305,13 @@ struct mjx_batch {
     ProgPic *d_prog_pics = nullptr;
     int16_t *d_prog_store[2] = {nullptr, nullptr};
     uint64_t prog_store_bytes = 0;
+    // YCbCr planes with an orientation and / or a resize: one PlanePass per image beside himages (same index), an allocation of its
+    // own -- a batch without such a picture has none of this.  yp_keep: per unique picture, what mjx_batch_tile rebuilds the plan's
+    // leaving planes from (the device images describe the intermediate only).
+    std::vector<PlanePass> h_yp;
+    PlanePass *d_yp = nullptr;
+    struct PlaneKeep { ImagePlan yp; uint64_t mid_bytes = 0; };       // (yp: an empty plan that carries the yp_* fields alone)
+    std::vector<PlaneKeep> yp_keep;
     LutEntry *d_lut = nullptr;
     float *d_qm = nullptr;
     uint32_t *d_segs = nullptr;         // restart segments of the unique images: (first subsequence, first bit) pairs
@@ -449,6 +458,7 @@ void release(mjx_batch *b)
     if (b->d_prog_bytes) (void)hipFree(b->d_prog_bytes);
     if (b->d_prog_lanes) (void)hipFree(b->d_prog_lanes);
     if (b->d_prog_pics) (void)hipFree(b->d_prog_pics);
+    if (b->d_yp) (void)hipFree(b->d_yp);
     for (int k = 0; k < 2; k++) if (b->d_prog_store[k]) (void)hipFree(b->d_prog_store[k]);
     if (b->uploaded) (void)hipEventDestroy(b->uploaded);
     if (b->copied) (void)hipEventDestroy(b->copied);
@@ -720,6 +730,13 @@ void plan_chunks(mjx_batch *b)
                     if (d.or_on == kOrCopyLuma) pass(kPassOrientLuma, 0, orient_tiles(d.rs_w, d.rs_h));
                     if (d.or_on == kOrResizeLuma) pass(kPassResizeLuma, d.rs_filter, resize_tiles(d.rs_w, d.rs_h));
                     if (d.fit_on) c.max_fit_wgs = std::max(c.max_fit_wgs, fit_pad_wgs(d.out_ch != 1 && d.out_planar ? 3u : 1u, d.fit_h));
+                    if (!b->h_yp.empty() && b->h_yp[i].kind != kPlaneNone) {      // (the leaving planes: plane 0 need not be the largest)
+                        const PlanePass &yp = b->h_yp[i];
+                        for (uint32_t q = 0; q < yp.ncomp; q++) {
+                            if (yp.kind == kPlaneCopy) c.max_plane_copy_tiles = std::max(c.max_plane_copy_tiles, orient_tiles(yp.dw[q], yp.dh[q]));
+                            else c.max_plane_resize_tiles[yp.filter] = std::max(c.max_plane_resize_tiles[yp.filter], resize_tiles(yp.dw[q], yp.dh[q]));
+                        }
+                    }
                 }
                 if (d.mode == stage_b_mode(kFormRefCompat, kSinkPacked)) {
                     d.plane_off = c.plane_words;
@@ -1074,6 +1091,20 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
                 }
                 prof_end(b, sp);
             }
+        if (b->d_yp) {                                      // YCbCr planes with an orientation and / or a resize: the leaving planes
+            const PlanePass *passes = b->d_yp + c.first;
+            if (c.max_plane_copy_tiles) {
+                prof_begin(b, MJX_K_RESIZE, sp);
+                launch_orient_planes(sp, c.max_plane_copy_tiles, nimg, imgs, passes, b->d_rgb, b->d_img_flags);
+                prof_end(b, sp);
+            }
+            for (uint32_t f = 0; f < kFilterCount; f++) {
+                if (!c.max_plane_resize_tiles[f]) continue;
+                prof_begin(b, MJX_K_RESIZE, sp);
+                launch_resize_planes(sp, c.max_plane_resize_tiles[f], nimg, imgs, passes, b->d_rgb, b->d_img_flags, f);
+                prof_end(b, sp);
+            }
+        }
         if (c.max_fit_wgs) {                                // fit modes: the borders of the chunk's letterboxed pictures
             prof_begin(b, MJX_K_RESIZE, sp);
             launch_fit_pad(sp, c.max_fit_wgs, nimg, imgs, b->d_rgb, b->d_img_flags);
@@ -1455,6 +1486,45 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 }
             }
             rgb_pool += p.out_dev ? 0 : align_up(inf.out_span, 256);
+            if (p.ycc_on && p.yp_kind != kPlaneNone) {
+                // planes with an orientation and / or a resize: what was laid out above is the intermediate (always in the pool); the
+                // leaving planes lie behind it, or in the caller's memory, and the accessors speak of them
+                if (times > 1 && p.yp_dev[0]) return MJX_ERR_INVALID_ARG;    // (copies would share the destination)
+                if (b->h_yp.empty()) b->h_yp.assign(n, PlanePass{});
+                PlanePass &yp = b->h_yp[i];
+                yp.kind = p.yp_kind; yp.code = p.yp_code; yp.ncomp = p.ncomp; yp.il = p.yp_il; yp.dtype = p.yp_dtype;
+                yp.filter = p.yp_filter; yp.aa = p.yp_aa;
+                for (uint32_t c = 0; c < 3; c++) {
+                    yp.sw[c] = p.ycc_w[c]; yp.sh[c] = p.ycc_h[c]; yp.src_off[c] = d.rgb_off + p.ycc_off[c];
+                    yp.dw[c] = p.yp_w[c]; yp.dh[c] = p.yp_h[c];
+                    yp.dst_dev[c] = p.yp_dev[c]; yp.dst_off[c] = rgb_pool + p.yp_off[c]; yp.pitch[c] = p.yp_pitch[c];
+                    yp.scale[c] = p.yp_scale[c]; yp.bias[c] = p.yp_bias[c];
+                    inf.ycc_w[c] = p.yp_w[c]; inf.ycc_h[c] = p.yp_h[c];
+                    inf.ycc_dev[c] = p.yp_dev[c]; inf.ycc_off[c] = p.yp_off[c]; inf.ycc_pitch[c] = p.yp_pitch[c];
+                }
+                inf.ycc_il = p.yp_il;
+                inf.out_dtype = p.yp_dtype;
+                inf.out_dev = p.yp_dev[0]; inf.out_row_pitch = p.yp_pitch[0];
+                inf.out_span = p.yp_bytes;
+                inf.rgb_off = rgb_pool;
+                inf.rgb_bytes = p.yp_written;
+                inf.width = p.yp_out_w; inf.height = p.yp_out_h;             // (the picture that leaves)
+                inf.orient = p.yp_code;
+                rgb_pool += p.yp_dev[0] ? 0 : align_up(p.yp_bytes, 256);
+                if (b->yp_keep.empty()) b->yp_keep.resize(nu);
+                if (rep == 0) {
+                    mjx_batch::PlaneKeep &keep = b->yp_keep[k];
+                    keep.mid_bytes = p.out_bytes;
+                    ImagePlan &q = keep.yp;
+                    q.yp_kind = p.yp_kind; q.yp_code = p.yp_code; q.yp_il = p.yp_il; q.yp_dtype = p.yp_dtype; q.yp_filter = p.yp_filter; q.yp_aa = p.yp_aa;
+                    q.yp_out_w = p.yp_out_w; q.yp_out_h = p.yp_out_h; q.yp_bytes = p.yp_bytes; q.yp_written = p.yp_written;
+                    for (uint32_t c = 0; c < 3; c++) {
+                        q.yp_w[c] = p.yp_w[c]; q.yp_h[c] = p.yp_h[c]; q.yp_dev[c] = p.yp_dev[c]; q.yp_off[c] = p.yp_off[c]; q.yp_pitch[c] = p.yp_pitch[c];
+                        q.yp_scale[c] = p.yp_scale[c]; q.yp_bias[c] = p.yp_bias[c];
+                    }
+                    q.ycc_written = p.ycc_written;
+                }
+            }
         } else
         rgb_pool += align_up(inf.rgb_bytes, 256);
         b->scan_bytes += inf.scan_len;
@@ -1883,6 +1953,13 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
             if (!b->h_prog_lanes.empty()) HIPOK(hipMemcpyAsync(b->d_prog_lanes, b->h_prog_lanes.data(), b->h_prog_lanes.size() * sizeof(ProgLane), hipMemcpyHostToDevice, up));
             HIPOK(hipMemcpyAsync(b->d_prog_pics, b->h_prog_pics.data(), b->h_prog_pics.size() * sizeof(ProgPic), hipMemcpyHostToDevice, up));
         }
+        if (!b->h_yp.empty()) {             // planes with an orientation and / or a resize: the passes' descriptors, an allocation of their own
+            void *q = nullptr;
+            if (hipMalloc(&q, b->h_yp.size() * sizeof(PlanePass)) != hipSuccess) { (void)hipGetLastError(); return MJX_ERR_NOMEM; }
+            b->d_yp = static_cast<PlanePass *>(q);
+            // (a blocking copy: small, and complete on return whichever stream the decode later waits for)
+            HIPOK(hipMemcpy(b->d_yp, b->h_yp.data(), b->h_yp.size() * sizeof(PlanePass), hipMemcpyHostToDevice));
+        }
         if (async_upload) {
             // the caller goes on (parsing and uploading the next group of files) while the DMA engine works; the decode
             // streams wait for this event before their first kernel (run_chunk)
@@ -2070,15 +2147,14 @@ static int batch_create_impl(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n,
     if (opts) o = *opts;
     if (!rois_fit(o, n) || !output_fits(fmt, n) || !orient_fits(orient, n) || (pl && !planes_fit(pl, n))) return MJX_ERR_INVALID_ARG;
     if (orient && orient->from_exif) return MJX_ERR_INVALID_ARG;       // (descriptors carry no file bytes: mjx_exif_orientation, then `extra`)
-    if (orient && !fmt) fmt = &kPackedOutput;
+    if (orient && !fmt && !pl) fmt = &kPackedOutput;
     const mjx_scan_desc *dd = descs;
     std::vector<ImagePlan> plans;
     std::vector<size_t> plan_of(n);                    // input i -> its picture's plan (multi-scan files add plans in front)
     plans.reserve(n);
     const auto tp0 = std::chrono::steady_clock::now();
     for (size_t i = 0; i < n; i++) {
-        plan_input_for(dd[i], opts_for_input(o, n, i), fmt, rs, i, plans, orient_code(orient, i, nullptr, 0));      // (rois[i], dst[i] and extra[i] go with input i: a multi-scan file's picture plan takes them)
-        if (pl) plan_planes_of_input(plans, pl, i);
+        plan_input_for(dd[i], opts_for_input(o, n, i), fmt, rs, i, plans, orient_code(orient, i, nullptr, 0), pl);      // (rois[i], dst[i] and extra[i] go with input i: a multi-scan file's picture plan takes them)
         plan_of[i] = plans.size() - 1;
     }
     if (std::getenv("MJX_TIMING"))
@@ -2101,6 +2177,49 @@ extern "C" int mjx_batch_create_planes(mjx_ctx *ctx, const mjx_scan_desc *descs,
 {
     if (!pl) { if (out) *out = nullptr; return MJX_ERR_INVALID_ARG; }
     return batch_create_impl(ctx, descs, n, opts, nullptr, nullptr, nullptr, pl, out, status);
+}
+
+// mjx_batch_create_planes with a resize and / or an orientation description (both NULL: mjx_batch_create_planes itself).
+extern "C" int mjx_batch_create_planes_orient(mjx_ctx *ctx, const mjx_scan_desc *descs, size_t n, const mjx_opts *opts, const mjx_planes *pl,
+                                              const mjx_resize *rs, const mjx_orient *orient, mjx_batch **out, int *status)
+{
+    if (!pl) { if (out) *out = nullptr; return MJX_ERR_INVALID_ARG; }
+    return batch_create_impl(ctx, descs, n, opts, nullptr, rs, orient, pl, out, status);
+}
+
+// Host-only: the planes that leave when this picture is decoded as input i with this resize (or NULL) and the resolved code -- the
+// planner's own numbers (plan_input_for with a plane description), with the scale it picks and the stored rectangle of the intermediate.
+extern "C" int mjx_planes_orient_layout(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_planes *pl, const mjx_resize *rs, uint8_t code,
+                                        size_t i, mjx_plane_layout *layout, uint8_t *scale_denom, mjx_rect *rect)
+{
+    return guarded([&]() -> int {
+    if (!desc || !pl) return MJX_ERR_INVALID_ARG;
+    mjx_opts o{};
+    if (opts) o = *opts;
+    if (!o.rois ? o.n_rois != 0 : (o.n_rois == 0 || (o.n_rois > 1 && i >= o.n_rois))) return MJX_ERR_INVALID_ARG;
+    if (o.rois) { if (o.n_rois > 1) o.rois += i; o.n_rois = 1; }
+    if (pl->dst ? i >= pl->n_dst : pl->n_dst != 0) return MJX_ERR_INVALID_ARG;
+    if (opts) { MJX_OPTS_COLOR(&o) = MJX_OPTS_COLOR(opts); MJX_OPTS_PROGRESSIVE(&o) = MJX_OPTS_PROGRESSIVE(opts); }
+    std::vector<ImagePlan> plans;
+    plan_input_for(*desc, o, nullptr, rs, i, plans, code, pl);
+    const ImagePlan &p = plans.back();
+    if (p.status != MJX_OK) return p.status;
+    const bool pass = p.yp_kind != kPlaneNone;
+    const uint32_t il = pass ? p.yp_il : p.ycc_il, np = il ? 2u : p.ncomp;
+    if (layout) {
+        std::memset(layout, 0, sizeof *layout);
+        for (uint32_t c = 0; c < p.ncomp; c++) {
+            layout->width[c] = pass ? p.yp_w[c] : p.ycc_w[c]; layout->height[c] = pass ? p.yp_h[c] : p.ycc_h[c];
+            if (c >= np) continue;
+            // (library-owned planes are dense and back to back: the pitch is the row, dev stays NULL; caller-owned: dst[i]'s own)
+            layout->row_pitch[c] = pass ? p.yp_pitch[c] : p.ycc_pitch[c];
+            layout->dev[c] = reinterpret_cast<void *>(uintptr_t(pass ? p.yp_dev[c] : p.ycc_dev[c]));
+        }
+    }
+    if (scale_denom) *scale_denom = uint8_t(p.scale);
+    if (rect) *rect = mjx_rect{p.roi_x, p.roi_y, p.roi_w, p.roi_h};
+    return MJX_OK;
+    });
 }
 
 // Host-only: the planes a decode of this picture as input i would write -- plan_planes' own numbers.
@@ -2442,6 +2561,17 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
                 for (uint32_t c = 0; c < 3; c++) {
                     p.ycc_x0[c] = sd.ycc_x0[c]; p.ycc_y0[c] = sd.ycc_y0[c]; p.ycc_w[c] = sd.ycc_w[c]; p.ycc_h[c] = sd.ycc_h[c];
                     p.ycc_dev[c] = 0; p.ycc_off[c] = sd.ycc_off[c]; p.ycc_pitch[c] = sd.ycc_pitch[c];
+                }
+                if (k < src->yp_keep.size() && src->yp_keep[k].yp.yp_kind != kPlaneNone) {      // (... and its orientation and resize: the device image
+                    const mjx_batch::PlaneKeep &keep = src->yp_keep[k];                         // and these fields describe the intermediate again)
+                    const ImagePlan &q = keep.yp;
+                    p.out_dtype = MJX_DTYPE_U8; p.out_row_pitch = sd.ycc_pitch[0]; p.out_bytes = keep.mid_bytes; p.ycc_written = q.ycc_written;
+                    p.yp_kind = q.yp_kind; p.yp_code = q.yp_code; p.yp_il = q.yp_il; p.yp_dtype = q.yp_dtype; p.yp_filter = q.yp_filter; p.yp_aa = q.yp_aa;
+                    p.yp_out_w = q.yp_out_w; p.yp_out_h = q.yp_out_h; p.yp_bytes = q.yp_bytes; p.yp_written = q.yp_written;
+                    for (uint32_t c = 0; c < 3; c++) {
+                        p.yp_w[c] = q.yp_w[c]; p.yp_h[c] = q.yp_h[c]; p.yp_dev[c] = 0; p.yp_off[c] = q.yp_off[c]; p.yp_pitch[c] = q.yp_pitch[c];
+                        p.yp_scale[c] = q.yp_scale[c]; p.yp_bias[c] = q.yp_bias[c];
+                    }
                 }
             }
         }
@@ -3256,7 +3386,7 @@ static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const si
     mjx_opts o{};
     if (opts) o = *opts;
     if (!rois_fit(o, n) || !output_fits(fmt, n) || !orient_fits(orient, n) || (pl && !planes_fit(pl, n))) return MJX_ERR_INVALID_ARG;
-    if (orient && !fmt) fmt = &kPackedOutput;
+    if (orient && !fmt && !pl) fmt = &kPackedOutput;
     const bool timing = std::getenv("MJX_TIMING") != nullptr;
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
@@ -3387,8 +3517,7 @@ static int decode_batch_impl(mjx_ctx *ctx, const uint8_t *const *jpegs, const si
             if (rc != MJX_OK) std::memset(&descs[i], 0, sizeof descs[i]);
             try {
                 // geometry + decode tables, also on the worker (rois[i], dst[i], the resize and the orientation -- the file's tag is read here -- go with file i)
-                plan_input_for(descs[i], opts_for_input(o, n, i), fmt, rs, i, file_plans[i], orient_code(orient, i, jpegs[i], lens[i]));
-                if (pl) plan_planes_of_input(file_plans[i], pl, i);
+                plan_input_for(descs[i], opts_for_input(o, n, i), fmt, rs, i, file_plans[i], orient_code(orient, i, jpegs[i], lens[i]), pl);
             } catch (...) {
                 file_plans[i].clear();
             }
@@ -3500,6 +3629,17 @@ extern "C" int mjx_decode_batch_planes(mjx_ctx *ctx, const uint8_t *const *jpegs
     if (!ctx) { if (out) *out = nullptr; return MJX_ERR_DEVICE; }      // (as mjx_decode_batch_out: no device, no CPU path)
     if (!pl) { if (out) *out = nullptr; return MJX_ERR_INVALID_ARG; }
     return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, nullptr, nullptr, nullptr, nullptr, status, out, pl);
+}
+
+// mjx_decode_batch_planes with a resize and / or an orientation description; dst[i], rois[i], the file's tag and extra[i] follow file i
+// through the groups.  Both NULL: mjx_decode_batch_planes itself.
+extern "C" int mjx_decode_batch_planes_orient(mjx_ctx *ctx, const uint8_t *const *jpegs, const size_t *lens, size_t n, const mjx_opts *opts,
+                                              unsigned threads, const mjx_planes *pl, const mjx_resize *rs, const mjx_orient *orient, int *status,
+                                              mjx_batch **out)
+{
+    if (!ctx) { if (out) *out = nullptr; return MJX_ERR_DEVICE; }      // (as mjx_decode_batch_out: no device, no CPU path)
+    if (!pl) { if (out) *out = nullptr; return MJX_ERR_INVALID_ARG; }
+    return decode_batch_impl(ctx, jpegs, lens, n, opts, threads, nullptr, rs, orient, nullptr, status, out, pl);
 }
 
 // ---- one-shot surface ------------------------------------------------------------------------------

@@ -318,6 +318,32 @@ MJX_HD uint32_t orient_compose(uint32_t first, uint32_t then)
 constexpr uint32_t kOrientTile = 64;                        // k_orient_out: a workgroup owns kOrientTile x kOrientTile pixels of D
 MJX_HD uint32_t orient_tiles(uint32_t w, uint32_t h) { return ((w + kOrientTile - 1) / kOrientTile) * ((h + kOrientTile - 1) / kOrientTile); }
 
+// ---- YCbCr planes with an orientation and / or a resize (mjx_batch_create_planes_orient) -----------------------------------------
+// Stage B writes such a picture as the plain plane decode does -- dense uint8 planes P_0 .. P_2, not interleaved, in the batch's pool
+// (DevImage::ycc_*, kSinkYcc): the intermediate.  A pass behind it brings every plane to the form it leaves in: k_orient_planes
+// copies orient_c(P_k) through the dtype's table (kPlaneCopy), k_resize_planes resamples orient_c(P_k) to the plane's own target
+// (kPlaneResize; any code, 1 included).  What the pass needs of a picture is this descriptor, an array of its own beside the chunk's
+// DevImages (same index): no DevImage field, and with it no existing kernel, changes.  A job is one plane -- plane 0, plane 1 (with
+// il: Cb and Cr as pairs into the one plane), plane 2 (skipped with il) -- and rides in the grid's z dimension, so that every field a
+// workgroup reads is uniform and indexed by a uniform.
+enum PlanePassKind : uint32_t { kPlaneNone = 0, kPlaneCopy = 1, kPlaneResize = 2 };
+struct PlanePass {
+    uint32_t kind;              // PlanePassKind
+    uint32_t code;              // the orientation, an EXIF code 1 .. 8
+    uint32_t ncomp, il;         // planes of the intermediate (1 or 3); Cb and Cr leave interleaved in plane 1
+    uint32_t dtype;             // MJX_DTYPE_* of the leaving planes
+    uint32_t filter, aa;        // kPlaneResize: the filter kind and `antialias`
+    uint32_t pad_;
+    uint32_t sw[3], sh[3];      // the intermediate: plane k is sh[k] dense rows of sw[k] bytes at byte src_off[k] of the pool
+    uint32_t dw[3], dh[3];      // the leaving planes' sizes in samples (the interleaved plane 1 has 2 dw[1] elements per row)
+    uint64_t src_off[3];
+    uint64_t dst_dev[3];        // caller-owned memory, or 0: byte dst_off[k] of the pool
+    uint64_t dst_off[3];
+    uint64_t pitch[3];          // elements between rows of leaving plane k
+    float scale[3], bias[3];    // by COMPONENT: fmaf(value, scale[k], bias[k]) for the float dtypes
+};
+MJX_HD uint32_t plane_pass_jobs(uint32_t ncomp, uint32_t il) { return ncomp == 1u ? 1u : il ? 2u : 3u; }
+
 // ---- libjpeg's pixels (mjx_opts.pixels = MJX_PIXELS_LIBJPEG): fancy upsampling and jdcolor.c's integer colour step ---------------
 // A component plane: cw x ch samples in rows of `stride` bytes; s and stride are multiples of 8 and stride >= cw rounded up to 8, so
 // that the aligned 4- and 8-byte reads below stay inside a row (what they bring in from behind cw is never used: indices clamp to
@@ -1038,6 +1064,13 @@ void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, con
 // fit modes: the border of every picture with DevImage::fit_on (MJX_FIT_CONTAIN), behind stage B on the resize's stream; max_wgs = the
 // chunk's largest fit_pad_wgs
 void launch_fit_pad(hipStream_t st, uint32_t max_wgs, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags);
+// YCbCr planes with an orientation and / or a resize, behind stage B: one workgroup per tile (orient_tiles / resize_tiles of the
+// chunk's largest leaving plane), plane job (grid z: 3) and picture whose PlanePass::kind is kPlaneCopy (k_orient_planes) or
+// kPlaneResize with this filter kind (k_resize_planes, _cubic, _nearest); `passes` is the chunk's array, one entry per DevImage
+void launch_orient_planes(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const PlanePass *passes, uint8_t *rgb,
+                          const uint32_t *img_flags);
+void launch_resize_planes(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const PlanePass *passes, uint8_t *rgb,
+                          const uint32_t *img_flags, uint32_t filter);
 // libjpeg's pixels, behind stage B: one workgroup per tile of the rectangle (lj_tiles) and picture with DevImage::lj_on
 void launch_upsample_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
                            const uint32_t *img_flags, bool luma = false /* k_upsample_luma: pictures with DevImage::lj_luma */);

@@ -4843,24 +4843,74 @@ __device__ __forceinline__ void out_store1f(const OutFmt &f, uint64_t at, float 
 // and out_store1f's clamp works on both sides -- and add the folded border weights of the no-antialias form at a window's first and
 // last sample; one division by (sum x)(sum y) at the end as before (1 where nothing is renormalised).  Nearest runs the same two
 // passes with one tap each: its sample is the byte itself, so every format is mjx_output's table bit for bit.
-template <bool ORIENT, int CH = 3, uint32_t FILTER = kFilterTriangle>
-__device__ __forceinline__ void resize_body(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
+// PLANES (k_resize_planes): source and target are one plane of the picture, not the picture -- `pj` says which (the kernel has
+// checked that the picture is its own).  CH == 1: one plane; CH == 2: Cb and Cr of an interleaved chroma plane, two dense source
+// planes of one size whose tap windows are shared, the pair stored in one run.  Numerators, loops and the order of accumulation are
+// the luminance form's, channel by channel; the other instantiations compile as they did.
+struct PlaneJob {
+    const uint8_t *src[2];          // the dense source planes (src[1]: Cr of a pair)
+    uint8_t *dst;                   // first element of the leaving plane
+    uint64_t pitch;                 // elements between its rows
+    uint32_t sw, sh, W, H;          // the stored plane and the plane's target (the oriented plane's axes)
+    uint32_t code, aa, dtype;
+    float sc[2], bi[2];
+};
+template <int DT>
+__device__ __forceinline__ void plane_store_f(uint8_t *base, uint64_t at, float v, float sc, float bi)
+{
+    if constexpr (DT == 0) __builtin_nontemporal_store(uint8_t(uint32_t(__builtin_rintf(fminf(fmaxf(v, 0.0f), 255.0f)))), ycc_global<uint8_t>(base + at));
+    else if constexpr (DT == 1) __builtin_nontemporal_store(uint16_t(half_bits(__builtin_fmaf(v, sc, bi))), ycc_global<uint16_t>(base + at * 2u));
+    else __builtin_nontemporal_store(__builtin_fmaf(v, sc, bi), ycc_global<float>(base + at * 4u));
+}
+// ... the pair Cb, Cr at elements at, at + 1: one store where the address allows it
+template <int DT>
+__device__ __forceinline__ void plane_store_pair_f(uint8_t *base, uint64_t at, float v0, float v1, const float (&sc)[2], const float (&bi)[2])
+{
+    constexpr uint32_t ESZ = DT == 0 ? 1u : DT == 1 ? 2u : 4u;
+    uint8_t *d = base + at * ESZ;
+    if ((uintptr_t(d) & (DT == 0 ? 1u : 3u)) != 0) {
+        plane_store_f<DT>(base, at, v0, sc[0], bi[0]);
+        plane_store_f<DT>(base, at + 1u, v1, sc[1], bi[1]);
+    } else if constexpr (DT == 0) {
+        const uint32_t b0 = uint32_t(__builtin_rintf(fminf(fmaxf(v0, 0.0f), 255.0f))), b1 = uint32_t(__builtin_rintf(fminf(fmaxf(v1, 0.0f), 255.0f)));
+        __builtin_nontemporal_store(uint16_t(b0 | (b1 << 8)), ycc_global<uint16_t>(d));
+    } else if constexpr (DT == 1) {
+        __builtin_nontemporal_store(half_bits(__builtin_fmaf(v0, sc[0], bi[0])) | (half_bits(__builtin_fmaf(v1, sc[1], bi[1])) << 16), ycc_global<uint32_t>(d));
+    } else {
+        u32x2_a4 w;
+        w.x = __builtin_bit_cast(uint32_t, __builtin_fmaf(v0, sc[0], bi[0])); w.y = __builtin_bit_cast(uint32_t, __builtin_fmaf(v1, sc[1], bi[1]));
+        __builtin_nontemporal_store(w, ycc_global<u32x2_a4>(d));
+    }
+}
+template <bool ORIENT, int CH = 3, uint32_t FILTER = kFilterTriangle, bool PLANES = false>
+__device__ __forceinline__ void resize_body(const DevImage *__restrict__ images, uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags,
+                                            [[maybe_unused]] const PlaneJob *pj = nullptr)
 {
     const DevImage &im = images[blockIdx.y];
-    static_assert(CH == 3 || (CH == 1 && ORIENT), "the luminance form is the oriented one");
+    static_assert(PLANES ? ORIENT && (CH == 1 || CH == 2) : CH == 3 || (CH == 1 && ORIENT), "the luminance form is the oriented one; a plane job is one plane or a chroma pair");
+    if constexpr (!PLANES)
     if (!im.valid || (CH == 1 ? im.or_on != kOrResizeLuma : ORIENT ? im.or_on != kOrResize : !im.rs_on) || im.rs_filter != FILTER || img_flags[im.status_idx]) return;
-    const bool swaps = ORIENT && orient_swaps(im.orient);
-    const uint32_t W = im.rs_w, H = im.rs_h, w_in = swaps ? im.roi_h : im.roi_w, h_in = swaps ? im.roi_w : im.roi_h;
+    uint32_t code_, src_w_, src_h_, W_, H_;
+    if constexpr (PLANES) { code_ = pj->code; src_w_ = pj->sw; src_h_ = pj->sh; W_ = pj->W; H_ = pj->H; }
+    else { code_ = im.orient; src_w_ = im.roi_w; src_h_ = im.roi_h; W_ = im.rs_w; H_ = im.rs_h; }
+    const bool swaps = ORIENT && orient_swaps(code_);
+    const uint32_t W = W_, H = H_, w_in = swaps ? src_h_ : src_w_, h_in = swaps ? src_w_ : src_h_;
+    constexpr int SRC_CH = PLANES ? 1 : CH;                // bytes per sample position of a source plane
     int64_t o_base = 0, o_sx = 0, o_sy = 0;                // bytes
     if constexpr (ORIENT) {
-        const OrientMap om = orient_map(im.orient, im.roi_w, im.roi_h);
-        o_base = om.base * CH; o_sx = om.sx * CH; o_sy = om.sy * CH;
+        const OrientMap om = orient_map(code_, src_w_, src_h_);
+        o_base = om.base * SRC_CH; o_sx = om.sx * SRC_CH; o_sy = om.sy * SRC_CH;
     }
     const uint32_t tiles_x = (W + kRsTileW - 1) / kRsTileW, tiles_y = (H + kRsTileH - 1) / kRsTileH;
     if (blockIdx.x >= tiles_x * tiles_y) return;
     const uint32_t tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
-    const bool aa = im.rs_aa != 0;
-    const uint8_t *__restrict__ src = rgb + im.rgb_off;
+    bool aa_;
+    if constexpr (PLANES) aa_ = pj->aa != 0; else aa_ = im.rs_aa != 0;
+    const bool aa = aa_;
+    const uint8_t *__restrict__ src;
+    if constexpr (PLANES) src = pj->src[0]; else src = rgb + im.rgb_off;
+    [[maybe_unused]] const uint8_t *__restrict__ src1 = nullptr;
+    if constexpr (PLANES && CH == 2) src1 = pj->src[1];
     __shared__ float s_h[kRsSlab][CH][kRsTileW];
     const uint32_t lx = threadIdx.x & (kRsTileW - 1), ly = threadIdx.x / kRsTileW;       // (ly: the wave)
     const uint32_t X = tile_x * kRsTileW + lx, Y0 = tile_y * kRsTileH;
@@ -4910,9 +4960,15 @@ __device__ __forceinline__ void resize_body(const DevImage *__restrict__ images,
             for (uint32_t k = 0; k < kRsRows; k++) {
                 const uint32_t row = r0 + ly + 4u * k;
                 if (row < row_hi) {
+                    if constexpr (PLANES) {
+                        const int64_t at = o_base + int64_t(row) * o_sy + int64_t(j) * o_sx;
+                        h[k][0] = __builtin_fmaf(wn, float(src[at]), h[k][0]);
+                        if constexpr (CH == 2) h[k][1] = __builtin_fmaf(wn, float(src1[at]), h[k][1]);
+                    } else {
                     const uint8_t *p = ORIENT ? src + (o_base + int64_t(row) * o_sy + int64_t(j) * o_sx) : src + (uint64_t(row) * w_in + j) * uint32_t(CH);
 #pragma unroll
                     for (int c = 0; c < CH; c++) h[k][c] = __builtin_fmaf(wn, float(p[c]), h[k][c]);
+                    }
                 }
             }
         }
@@ -4948,6 +5004,28 @@ __device__ __forceinline__ void resize_body(const DevImage *__restrict__ images,
         __syncthreads();
     }
     if (X >= W) return;
+    if constexpr (PLANES) {
+        const uint32_t dt = pj->dtype;
+#pragma unroll
+        for (uint32_t k = 0; k < kRsRows; k++) {
+            const uint32_t Y = Y0 + ly + 4u * k;
+            if (Y >= H) continue;
+            const float norm = ax.sum * sy[k];
+            const uint64_t at = uint64_t(Y) * pj->pitch + uint64_t(X) * uint32_t(CH);
+            if constexpr (CH == 2) {
+                const float v0 = acc[k][0] / norm, v1 = acc[k][1] / norm;
+                if (dt == 0u) plane_store_pair_f<0>(pj->dst, at, v0, v1, pj->sc, pj->bi);
+                else if (dt == 1u) plane_store_pair_f<1>(pj->dst, at, v0, v1, pj->sc, pj->bi);
+                else plane_store_pair_f<2>(pj->dst, at, v0, v1, pj->sc, pj->bi);
+            } else {
+                const float v0 = acc[k][0] / norm;
+                if (dt == 0u) plane_store_f<0>(pj->dst, at, v0, pj->sc[0], pj->bi[0]);
+                else if (dt == 1u) plane_store_f<1>(pj->dst, at, v0, pj->sc[0], pj->bi[0]);
+                else plane_store_f<2>(pj->dst, at, v0, pj->sc[0], pj->bi[0]);
+            }
+        }
+        return;
+    }
     OutFmt f = out_fmt(im, rgb);
     if (!im.out_dev) f.base = rgb + im.rs_off;
 #pragma unroll
@@ -5004,6 +5082,51 @@ extern "C" __global__ __launch_bounds__(256) void k_resize_luma_##suffix(const D
 MJX_RESIZE_KERNELS(cubic, kFilterBicubic)
 MJX_RESIZE_KERNELS(nearest, kFilterNearest)
 #undef MJX_RESIZE_KERNELS
+
+// ---- YCbCr planes, resized (PlanePass::kind == kPlaneResize): k_resize_planes, _cubic, _nearest ------------------------------------
+// Stage B has written the picture's planes dense and uint8 into the pool (the plain plane decode: kSinkYcc); a workgroup owns a
+// tile of one leaving plane -- the plane is the grid's z -- and resamples orient_c(P_k) to the plane's own target with resize_body's
+// plane form: the luminance form's arithmetic on the plane as a one-channel picture.  With interleaved chroma job 1 is the pair: a
+// lane computes Cb and Cr of its output position from the two source planes (one window, two sums) and stores them side by side.
+// The descriptor's fields are uniform, indexed by the uniform job; the stores are global, non-temporal, 64 neighbouring elements
+// (128 of a pair) of a plane row per wave.
+template <uint32_t FILTER>
+__device__ __forceinline__ void resize_planes_body(const DevImage *__restrict__ images, const PlanePass *__restrict__ passes, uint8_t *__restrict__ rgb,
+                                                   const uint32_t *__restrict__ img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    const PlanePass &pp = passes[blockIdx.y];
+    if (!im.valid || pp.kind != kPlaneResize || pp.filter != FILTER || img_flags[im.status_idx]) return;
+    const uint32_t job = blockIdx.z;
+    if (job >= plane_pass_jobs(pp.ncomp, pp.il)) return;
+    const bool pair = pp.il != 0u && job == 1u;
+    PlaneJob pj;
+    pj.src[0] = rgb + pp.src_off[job];
+    pj.src[1] = rgb + pp.src_off[pair ? 2u : job];
+    pj.dst = pp.dst_dev[job] ? reinterpret_cast<uint8_t *>(uintptr_t(pp.dst_dev[job])) : rgb + pp.dst_off[job];
+    pj.pitch = pp.pitch[job];
+    pj.sw = pp.sw[job]; pj.sh = pp.sh[job]; pj.W = pp.dw[job]; pj.H = pp.dh[job];
+    pj.code = pp.code; pj.aa = pp.aa; pj.dtype = pp.dtype;
+    pj.sc[0] = pp.scale[job]; pj.bi[0] = pp.bias[job];
+    pj.sc[1] = pp.scale[pair ? 2u : job]; pj.bi[1] = pp.bias[pair ? 2u : job];
+    if (pair) resize_body<true, 2, FILTER, true>(images, rgb, img_flags, &pj);
+    else resize_body<true, 1, FILTER, true>(images, rgb, img_flags, &pj);
+}
+extern "C" __global__ __launch_bounds__(256) void k_resize_planes(const DevImage *__restrict__ images, const PlanePass *__restrict__ passes,
+                                                                   uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
+{
+    resize_planes_body<kFilterTriangle>(images, passes, rgb, img_flags);
+}
+extern "C" __global__ __launch_bounds__(256) void k_resize_planes_cubic(const DevImage *__restrict__ images, const PlanePass *__restrict__ passes,
+                                                                         uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
+{
+    resize_planes_body<kFilterBicubic>(images, passes, rgb, img_flags);
+}
+extern "C" __global__ __launch_bounds__(256) void k_resize_planes_nearest(const DevImage *__restrict__ images, const PlanePass *__restrict__ passes,
+                                                                           uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
+{
+    resize_planes_body<kFilterNearest>(images, passes, rgb, img_flags);
+}
 
 // ---- orientation on the device (mjx_orient; DevImage::or_on == kOrCopy): an oriented picture that is not resized --------------------
 // Stage B has written the picture as a packed (cropped) one, S: roi_h x roi_w x 3 bytes at rgb_off.  A workgroup owns a tile of
@@ -5084,6 +5207,78 @@ extern "C" __global__ __launch_bounds__(256) void k_orient_luma(const DevImage *
                                                                  const uint32_t *__restrict__ img_flags)
 {
     orient_body<1>(images, rgb, img_flags);
+}
+
+// ---- YCbCr planes, oriented and not resized (PlanePass::kind == kPlaneCopy): k_orient_planes ---------------------------------------
+// k_orient_out's plan for one byte per sample.  A workgroup owns a kOrientTile x kOrientTile tile of one leaving plane (the plane is
+// the grid's z); the tile of the stored plane that holds the same samples is read along the stored rows -- a wave per row,
+// consecutive lanes consecutive bytes -- into LDS rows of 68 bytes: 17 words, so the walk down a column of the tile that the codes
+// 5 .. 8 make puts the 32 lanes of a half wave on 32 different banks (a 64-byte row would put four rows on every pass of the banks).
+// An element is the planes' table applied to the byte (ycc_store1), stored global and non-temporal, 64 neighbouring elements of a
+// plane row per wave.  Interleaved chroma (job 1 with il): both source tiles are staged, and the lane that holds a Cb sample also
+// takes the Cr sample of the same place and stores the pair in one run (ycc_store_run), as planes_out_store does.
+constexpr uint32_t kOrientPlaneRow = kOrientTile + 4u;
+static_assert((kOrientPlaneRow / 4u) % 2u == 1u, "k_orient_planes: an odd number of words per LDS row");
+template <int DT>
+__device__ __forceinline__ void orient_planes_store(const uint8_t (*s_t)[kOrientTile][kOrientPlaneRow], bool pair, uint8_t *dst, uint64_t pitch,
+                                                    uint32_t X0, uint32_t Y0, uint32_t th, uint32_t sw, uint32_t sh, bool swaps, bool fu, bool fv,
+                                                    uint32_t lane, uint32_t wave, float sc0, float bi0, float sc1, float bi1)
+{
+    constexpr uint32_t ESZ = DT == 0 ? 1u : DT == 1 ? 2u : 4u;
+    const uint32_t X = X0 + lane;
+    for (uint32_t y = wave; y < th; y += 4u) {
+        const uint32_t ur = swaps ? y : lane, vr = swaps ? lane : y;
+        const uint32_t u = fu ? sw - 1u - ur : ur, v = fv ? sh - 1u - vr : vr;
+        const uint64_t row = uint64_t(Y0 + y) * pitch;
+        if (pair) {
+            const uint32_t e[2] = {s_t[0][v][u], s_t[1][v][u]};
+            ycc_store_run<DT, 2>(dst + (row + uint64_t(X) * 2u) * ESZ, e, 0u, 2u, sc0, bi0, sc1, bi1);
+        } else {
+            ycc_store1<DT>(dst + (row + X) * ESZ, s_t[0][v][u], sc0, bi0);
+        }
+    }
+}
+extern "C" __global__ __launch_bounds__(256) void k_orient_planes(const DevImage *__restrict__ images, const PlanePass *__restrict__ passes,
+                                                                   uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    const PlanePass &pp = passes[blockIdx.y];
+    if (!im.valid || pp.kind != kPlaneCopy || img_flags[im.status_idx]) return;
+    const uint32_t job = blockIdx.z;
+    if (job >= plane_pass_jobs(pp.ncomp, pp.il)) return;
+    const bool pair = pp.il != 0u && job == 1u;
+    const uint32_t code = pp.code, w = pp.sw[job], h = pp.sh[job];
+    const bool swaps = orient_swaps(code), fu = orient_flips_u(code), fv = orient_flips_v(code);
+    const uint32_t W = swaps ? h : w, H = swaps ? w : h;
+    const uint32_t tiles_x = (W + kOrientTile - 1) / kOrientTile, tiles_y = (H + kOrientTile - 1) / kOrientTile;
+    if (blockIdx.x >= tiles_x * tiles_y) return;
+    const uint32_t tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const uint32_t X0 = tile_x * kOrientTile, Y0 = tile_y * kOrientTile;
+    const uint32_t tw = W - X0 < kOrientTile ? W - X0 : kOrientTile, th = H - Y0 < kOrientTile ? H - Y0 : kOrientTile;
+    // the tile of the stored plane that holds the tile's samples, as in orient_body
+    const uint32_t sw = swaps ? th : tw, sh = swaps ? tw : th;
+    const uint32_t u0 = swaps ? Y0 : X0, v0 = swaps ? X0 : Y0;
+    const uint32_t sx0 = fu ? w - u0 - sw : u0, sy0 = fv ? h - v0 - sh : v0;
+    __shared__ uint8_t s_t[2][kOrientTile][kOrientPlaneRow];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t first = uint64_t(sy0) * w + sx0;
+    const uint8_t *__restrict__ src0 = rgb + pp.src_off[job] + first;
+    const uint8_t *__restrict__ src1 = rgb + pp.src_off[pair ? 2u : job] + first;
+    for (uint32_t r = wave; r < sh; r += 4u) {
+        if (lane < sw) {
+            s_t[0][r][lane] = src0[uint64_t(r) * w + lane];
+            if (pair) s_t[1][r][lane] = src1[uint64_t(r) * w + lane];
+        }
+    }
+    __syncthreads();
+    if (lane >= tw) return;
+    uint8_t *dst = pp.dst_dev[job] ? reinterpret_cast<uint8_t *>(uintptr_t(pp.dst_dev[job])) : rgb + pp.dst_off[job];
+    const uint64_t pitch = pp.pitch[job];
+    const float sc0 = pp.scale[job], bi0 = pp.bias[job], sc1 = pp.scale[pair ? 2u : job], bi1 = pp.bias[pair ? 2u : job];
+    const uint32_t dt = pp.dtype;
+    if (dt == 0u) orient_planes_store<0>(s_t, pair, dst, pitch, X0, Y0, th, sw, sh, swaps, fu, fv, lane, wave, sc0, bi0, sc1, bi1);
+    else if (dt == 1u) orient_planes_store<1>(s_t, pair, dst, pitch, X0, Y0, th, sw, sh, swaps, fu, fv, lane, wave, sc0, bi0, sc1, bi1);
+    else orient_planes_store<2>(s_t, pair, dst, pitch, X0, Y0, th, sw, sh, swaps, fu, fv, lane, wave, sc0, bi0, sc1, bi1);
 }
 
 // ---- fit modes (mjx_resize's fit byte; DevImage::fit_on): the border of a letterboxed picture ------------------------------------
@@ -5557,6 +5752,20 @@ void launch_resize_orient(hipStream_t st, uint32_t max_tiles, uint32_t nimg, con
                                  dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
     else hipLaunchKernelGGL(filter == kFilterBicubic ? k_resize_orient_cubic : filter == kFilterNearest ? k_resize_orient_nearest : k_resize_orient,
                             dim3(max_tiles, nimg), dim3(256), 0, st, images, rgb, img_flags);
+}
+
+void launch_orient_planes(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const PlanePass *passes, uint8_t *rgb,
+                          const uint32_t *img_flags)
+{
+    if (max_tiles == 0 || nimg == 0) return;
+    hipLaunchKernelGGL(k_orient_planes, dim3(max_tiles, nimg, 3), dim3(256), 0, st, images, passes, rgb, img_flags);
+}
+void launch_resize_planes(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const PlanePass *passes, uint8_t *rgb,
+                          const uint32_t *img_flags, uint32_t filter)
+{
+    if (max_tiles == 0 || nimg == 0) return;
+    hipLaunchKernelGGL(filter == kFilterBicubic ? k_resize_planes_cubic : filter == kFilterNearest ? k_resize_planes_nearest : k_resize_planes,
+                       dim3(max_tiles, nimg, 3), dim3(256), 0, st, images, passes, rgb, img_flags);
 }
 
 void launch_fit_pad(hipStream_t st, uint32_t max_wgs, uint32_t nimg, const DevImage *images, uint8_t *rgb, const uint32_t *img_flags)

@@ -836,12 +836,77 @@ int resize_opts(uint32_t width, uint32_t height, const mjx_opts &opts_i, const m
     return MJX_OK;
 }
 
+// YCbCr planes with an orientation and / or a resize: the input (planned at the stored rectangle and scale, plans.back()) becomes the
+// plain plane decode -- uint8, dense, not interleaved, library-owned: the intermediate -- and the planes that leave are laid out by
+// `pl`'s rules.  Without a resize plane k is orient_c(P_k): its sides swap for codes 5 .. 8.  With one, component k's factors in D are
+// (h_k, v_k) or, codes 5 .. 8, (v_k, h_k), the maxima likewise, and the plane's target is the whole-picture formula of a W x H
+// picture: ceil(W h'_k / hmax') x ceil(H v'_k / vmax').
+static void plan_planes_pass(std::vector<ImagePlan> &plans, size_t first, const mjx_planes *pl, const mjx_resize *rs, uint32_t code, size_t i)
+{
+    static const mjx_planes mid = {MJX_DTYPE_U8, 0, {1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}, nullptr, 0};
+    plan_output_of_input(plans, nullptr, i);
+    if (plan_planes_of_input(plans, &mid, i) != MJX_OK) return;
+    ImagePlan &p = plans.back();
+    const uint32_t nc = p.ncomp;
+    const bool il = pl->interleave_chroma != 0 && nc == 3;
+    bool bad = pl->dtype > MJX_DTYPE_F32 || (il && (p.h[1] != p.h[2] || p.v[1] != p.v[2]));
+    for (uint32_t c = 0; c < nc && !bad; c++)
+        bad = pl->dtype != MJX_DTYPE_U8 && !(std::isfinite(pl->scale[c]) && std::isfinite(pl->bias[c]));
+    const uint64_t esz = pl->dtype == MJX_DTYPE_U8 ? 1u : pl->dtype == MJX_DTYPE_F16 ? 2u : 4u;
+    const bool sw = orient_swaps(code);
+    const uint32_t nplanes = il ? 2u : nc;
+    uint64_t off = 0, first_at = 0, last = 0;
+    p.yp_written = 0;
+    for (uint32_t c = 0; c < nc && !bad; c++) {
+        uint32_t w = sw ? p.ycc_h[c] : p.ycc_w[c], h = sw ? p.ycc_w[c] : p.ycc_h[c];
+        if (rs) {
+            const uint64_t hc = sw ? p.v[c] : p.h[c], vc = sw ? p.h[c] : p.v[c], hm = sw ? p.vmax : p.hmax, vm = sw ? p.hmax : p.vmax;
+            w = uint32_t((uint64_t(rs->width) * hc + hm - 1) / hm);
+            h = uint32_t((uint64_t(rs->height) * vc + vm - 1) / vm);
+        }
+        p.yp_w[c] = w; p.yp_h[c] = h;
+        p.yp_scale[c] = pl->dtype == MJX_DTYPE_U8 ? 1.f : pl->scale[c];
+        p.yp_bias[c] = pl->dtype == MJX_DTYPE_U8 ? 0.f : pl->bias[c];
+        p.yp_written += uint64_t(w) * h * esz;
+        p.yp_dev[c] = 0; p.yp_off[c] = 0; p.yp_pitch[c] = 0;
+        if (c >= nplanes) continue;                                    // (Cr rides in plane 1)
+        const uint64_t row_min = uint64_t(w) * (il && c == 1 ? 2u : 1u);
+        uint64_t pitch = row_min;
+        if (pl->dst) {
+            const mjx_plane_layout &dl = pl->dst[i];
+            if (dl.width[c] != w || dl.height[c] != h || dl.row_pitch[c] < row_min || dl.row_pitch[c] > (uint64_t(1) << 40)) { bad = true; break; }
+            if (!dl.dev[c] || (uint64_t(uintptr_t(dl.dev[c])) & (esz - 1))) { bad = true; break; }
+            pitch = dl.row_pitch[c];
+            p.yp_dev[c] = uint64_t(uintptr_t(dl.dev[c]));
+        } else {
+            p.yp_off[c] = off;
+        }
+        p.yp_pitch[c] = pitch;
+        const uint64_t span = ((uint64_t(h) - 1) * pitch + row_min) * esz;
+        const uint64_t at = pl->dst ? p.yp_dev[c] : off;
+        if (c == 0) first_at = at;
+        last = std::max(last, at + span);
+        off += span;
+    }
+    if (bad) { fail_input(plans, first, MJX_ERR_INVALID_ARG); return; }
+    p.yp_kind = rs ? kPlaneResize : kPlaneCopy;
+    p.yp_code = code;
+    p.yp_il = il ? 1u : 0u;
+    p.yp_dtype = pl->dtype;
+    p.yp_filter = rs ? MJX_RESIZE_FILTER(rs) : 0u;
+    p.yp_aa = rs && rs->antialias ? 1u : 0u;
+    p.yp_out_w = rs ? rs->width : sw ? p.roi_h : p.roi_w;
+    p.yp_out_h = rs ? rs->height : sw ? p.roi_w : p.roi_h;
+    p.yp_bytes = last > first_at ? last - first_at : ((uint64_t(p.yp_h[0]) - 1) * p.yp_pitch[0] + p.yp_w[0]) * esz;
+}
+
 void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_output *out, const mjx_resize *rs, size_t i,
-                    std::vector<ImagePlan> &plans, uint32_t code)
+                    std::vector<ImagePlan> &plans, uint32_t code, const mjx_planes *pl)
 {
     if (!rs && code == 1) {
         plan_input(d, opts_i, plans);
-        plan_output_of_input(plans, out, i);
+        plan_output_of_input(plans, pl ? nullptr : out, i);
+        if (pl) plan_planes_of_input(plans, pl, i);
         return;
     }
     const size_t first = plans.size();
@@ -896,6 +961,7 @@ void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_ou
     }
     // (the filter byte is read from the caller's object: rs_s is a member-wise copy and need not carry it)
     if (rs && (MJX_RESIZE_FILTER(rs) >= kFilterCount || fit >= kFitCount)) rc = MJX_ERR_INVALID_ARG;
+    if (pl && fit == kFitContain) rc = MJX_ERR_INVALID_ARG;               // (a pad per component plane: not built)
     if (rs && rc == MJX_OK) {
         mjx_opts in;
         std::memcpy(&in, &eff, sizeof in);
@@ -905,6 +971,7 @@ void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_ou
     plan_input(d, eff, plans);
     if (plans.back().status != MJX_OK) return;
     if (rc != MJX_OK) { fail_input(plans, first, rc); return; }
+    if (pl) { plan_planes_pass(plans, first, pl, rs, code, i); return; }
     ImagePlan &p = plans.back();
     p.rs_on = true;
     p.orient = code;

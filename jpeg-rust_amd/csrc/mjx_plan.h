@@ -80,6 +80,16 @@ struct ImagePlan {
     uint32_t ycc_il = 0, ycc_round = 0;
     uint32_t ycc_x0[3] = {0, 0, 0}, ycc_y0[3] = {0, 0, 0}, ycc_w[3] = {0, 0, 0}, ycc_h[3] = {0, 0, 0};
     uint64_t ycc_dev[3] = {0, 0, 0}, ycc_off[3] = {0, 0, 0}, ycc_pitch[3] = {0, 0, 0}, ycc_written = 0;
+    // YCbCr planes with an orientation and / or a resize (plan_input_for with a plane description; PlanePass, mjx_kernels.h).  yp_kind
+    // != 0 (kPlaneCopy, kPlaneResize): ycc_* above, out_dtype (uint8) and out_bytes describe the INTERMEDIATE -- the plain plane decode
+    // of the stored rectangle, library-owned, dense, not interleaved -- and the fields here the planes that LEAVE: plane k is yp_w[k] x
+    // yp_h[k] samples of yp_dtype, rows of yp_pitch[k] elements at yp_dev[k] (caller-owned) or, yp_dev[k] == 0, yp_off[k] bytes behind
+    // the first leaving plane; yp_il: Cb and Cr share plane 1.  yp_bytes: the span from the first leaving plane's first byte to the
+    // last one's end; yp_written: the bytes written; yp_out_w x yp_out_h: the picture that leaves (D's rectangle, or the target).
+    uint32_t yp_kind = 0, yp_code = 1, yp_il = 0, yp_dtype = 0, yp_filter = 0, yp_aa = 0;
+    uint32_t yp_w[3] = {0, 0, 0}, yp_h[3] = {0, 0, 0}, yp_out_w = 0, yp_out_h = 0;
+    uint64_t yp_dev[3] = {0, 0, 0}, yp_off[3] = {0, 0, 0}, yp_pitch[3] = {0, 0, 0}, yp_bytes = 0, yp_written = 0;
+    float yp_scale[3] = {1.f, 1.f, 1.f}, yp_bias[3] = {0.f, 0.f, 0.f};
     // resize on the device (mjx_resize, plan_resize): the picture is planned as the packed (cropped) picture roi_w x roi_h at `scale`
     // -- the intermediate -- and leaves as rs_w x rs_h elements per channel: out_* above then describe the TARGET picture, and
     // stage B keeps its packed forms (fill_dev_image).
@@ -196,9 +206,13 @@ int plan_planes_of_input(std::vector<ImagePlan> &plans, const mjx_planes *pl, si
 // oriented picture D (full-size D with auto_scale), is mapped back to the stored picture S (orient_rect_to_stored) and the picture
 // is planned as the cropped packed picture there; with auto_scale the target's axes are swapped into S's for codes 5 .. 8 before the
 // scale is picked.  Anything else, a rectangle outside D, or REF_COMPAT: MJX_ERR_INVALID_ARG for the picture.
+// pl: the call's plane description (`out` is then not looked at).  Without a resize and with code 1 the picture is planned exactly as
+// mjx_batch_create_planes plans it (plan_input + plan_planes_of_input).  Otherwise the rectangle, the orientation mapping, the fit
+// rule and the scale are the ones above, the picture is planned as the plain uint8 plane decode at (s, R_S) -- the intermediate --
+// and the leaving planes (ImagePlan::yp_*) are laid out by pl's rules; MJX_FIT_CONTAIN is MJX_ERR_INVALID_ARG for the picture.
 int resize_opts(uint32_t width, uint32_t height, const mjx_opts &opts_i, const mjx_resize &rs, mjx_opts &eff, mjx_rect &rect);
 void plan_input_for(const mjx_scan_desc &d, const mjx_opts &opts_i, const mjx_output *out, const mjx_resize *rs, size_t i,
-                    std::vector<ImagePlan> &plans, uint32_t code = 1);
+                    std::vector<ImagePlan> &plans, uint32_t code = 1, const mjx_planes *pl = nullptr);
 
 // A planned progressive picture as the device sees it (mjx_prog.h): its ProgPic, planes laid out from element `store0` of the chunk's
 // dense store on; its scans' bytes appended to `bytes`; one lane per (scan, restart interval) appended to levels[level - 1], for image
