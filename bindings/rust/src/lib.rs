@@ -186,7 +186,23 @@ pub const MJX_OPTS_COLOR_OFFSET: usize = 10;
 /// byte 11 of mjx_opts, the next padding byte: 1 accepts progressive (SOF2) files (include/mjx.h: MJX_OPTS_PROGRESSIVE)
 pub const MJX_OPTS_PROGRESSIVE_OFFSET: usize = 11;
 
+/// byte 12 of mjx_opts, the next padding byte: MJX_IDCT_* (include/mjx.h: MJX_OPTS_IDCT)
+pub const MJX_OPTS_IDCT_OFFSET: usize = 12;
+/// stage B's float inverse DCT, as in every earlier version
+pub const MJX_IDCT_FLOAT: u8 = 0;
+/// libjpeg's integer slow inverse DCT: byte-exact libjpeg pixels; with pixels = 1 (MJX_PIXELS_LIBJPEG) only
+pub const MJX_IDCT_ISLOW: u8 = 1;
+/// or-ed into rh of mjx_upsample_color_host / mjx_upsample_luma_host: the component is replicated whatever its ratios
+pub const MJX_UPSAMPLE_REPLICATE: u8 = 0x80;
+
 impl mjx_opts {
+    /// MJX_IDCT_*: 0 the float inverse DCT, 1 libjpeg's integer slow one (the picture is then byte for byte libjpeg's)
+    pub fn idct(&self) -> u8 {
+        unsafe { *(self as *const mjx_opts as *const u8).add(MJX_OPTS_IDCT_OFFSET) }
+    }
+    pub fn set_idct(&mut self, idct: u8) {
+        unsafe { *(self as *mut mjx_opts as *mut u8).add(MJX_OPTS_IDCT_OFFSET) = idct }
+    }
     /// 0: progressive files are refused as before; 1: SOF2 frames of one or three components decode on the device
     pub fn progressive(&self) -> u8 {
         unsafe { *(self as *const mjx_opts as *const u8).add(MJX_OPTS_PROGRESSIVE_OFFSET) }
@@ -316,6 +332,8 @@ extern "C" {
     pub fn mjx_upsample_color_host(planes: *const *const u8, cw: *const u32, ch: *const u32, rh: *const u8, rv: *const u8, ncomp: u32,
                                    rect: *const mjx_rect, rgb: *mut u8) -> c_int;
     pub fn mjx_upsample_luma_host(plane: *const u8, cw: u32, ch: u32, rh: u8, rv: u8, rect: *const mjx_rect, out: *mut u8) -> c_int;
+    /// host only: MJX_IDCT_ISLOW's transform of one block, natural order (the lane routine stage B's integer sink runs)
+    pub fn mjx_idct_islow_host(coef: *const i16, q: *const u16, out: *mut u8) -> c_int;
     pub fn mjx_validate(desc: *const mjx_scan_desc, opts: *const mjx_opts) -> c_int;
     pub fn mjx_plan_tiles(desc: *const mjx_scan_desc, opts: *const mjx_opts, tiles_read: *mut u64, tiles_total: *mut u64,
                           tile_mcus: *mut u32) -> c_int;

@@ -207,6 +207,43 @@ typedef struct mjx_opts {
 #define MJX_OPTS_PROGRESSIVE_OFFSET 11
 #define MJX_OPTS_PROGRESSIVE(opts) (((uint8_t *)(opts))[MJX_OPTS_PROGRESSIVE_OFFSET])
 
+/* The inverse DCT of a call: byte 12 of mjx_opts, the next padding byte behind MJX_OPTS_PROGRESSIVE (the struct's members, size and
+ * offsets are as they were; a zero-filled struct means what it meant).  An lvalue: MJX_OPTS_IDCT(&opts) = MJX_IDCT_ISLOW.  Fill the
+ * struct with zeros first and set the byte on the object the call is given: a member-wise copy of the struct need not carry it.
+ * MJX_IDCT_FLOAT (0): stage B's float transform, everything as in every earlier version, bit for bit.  MJX_IDCT_ISLOW (1), with
+ * pixels == MJX_PIXELS_LIBJPEG only (without it: MJX_ERR_INVALID_ARG for the picture): libjpeg's integer slow inverse DCT
+ * (jidctint.c), so that the picture is byte for byte the one libjpeg and libjpeg-turbo give (Pillow, OpenCV, torchvision's CPU path),
+ * not the one up to 3 levels from it.  Anything but 0 and 1: MJX_ERR_INVALID_ARG.  Everything MJX_PIXELS_LIBJPEG refuses stays
+ * refused with the same status (scale_denom > 1, MJX_LAYOUT_REF_COMPAT, strict_ref: MJX_ERR_INVALID_ARG; RGB, CMYK and YCCK
+ * pictures: MJX_ERR_UNSUPPORTED_FORMAT); a plane description (mjx_planes) together with MJX_IDCT_ISLOW gives the picture
+ * MJX_ERR_UNSUPPORTED_FORMAT.
+ * The arithmetic, for one 8 x 8 block of one component.  All of it is in 32-bit two's-complement integers that wrap.
+ *   d[v][u] = coef[v][u] q[v][u], q the raw DQT entry (8 or 16 bits).
+ *   Pass 1 runs P with n = 11 on every column (over v), pass 2 the same P with n = 18 on every row of pass 1's output.
+ *   P takes d0 .. d7, FIX(x) = int(x 8192 + 0.5).  Even part:
+ *     z1 = (d2 + d6) FIX(0.541196100),  t2 = z1 - d6 FIX(1.847759065),  t3 = z1 + d2 FIX(0.765366865),
+ *     t0 = (d0 + d4) 8192,  t1 = (d0 - d4) 8192,  t10 = t0 + t3,  t13 = t0 - t3,  t11 = t1 + t2,  t12 = t1 - t2.
+ *   Odd part: a = d7, b = d5, c = d3, e = d1;  z1 = a + e,  z2 = b + c,  z3 = a + c,  z4 = b + e,  z5 = (z3 + z4) FIX(1.175875602);
+ *     a *= FIX(0.298631336),  b *= FIX(2.053119869),  c *= FIX(3.072711026),  e *= FIX(1.501321110);
+ *     z1 *= -FIX(0.899976223),  z2 *= -FIX(2.562915447),  z3 = z3 (-FIX(1.961570560)) + z5,  z4 = z4 (-FIX(0.390180644)) + z5;
+ *     a += z1 + z3,  b += z2 + z4,  c += z2 + z3,  e += z1 + z4.
+ *   Outputs: o0 = t10 + e, o7 = t10 - e, o1 = t11 + c, o6 = t11 - c, o2 = t12 + b, o5 = t12 - b, o3 = t13 + a, o4 = t13 - a, each
+ *   finished as (o + (1 << (n - 1))) >> n with an arithmetic shift.
+ *   The sample is s = clamp(x + 128, 0, 255), x pass 2's output: it saturates (libjpeg's C table wraps modulo 1024; the two agree
+ *   for every x in [-512, 511], and libjpeg-turbo's SIMD code saturates).  mjx_idct_islow_host runs exactly this on the CPU.
+ * Behind the transform the pipeline is MJX_PIXELS_LIBJPEG's with two changes: there is no rounding constant (the samples are
+ * integers already), and a component whose plane has at most two columns (ceil(W h / hmax) <= 2) and whose ratios (rh, rv) are
+ * (2, 1) or (2, 2) is replicated in both directions, out[X][Y] = s[X / rh][Y / rv] -- jdsample.c picks its triangle filters only for
+ * downsampled_width > 2; (1, 2) keeps its filter at every width.  Without MJX_IDCT_ISLOW MJX_PIXELS_LIBJPEG's own rule stands.
+ * Rectangles, output formats, caller memory, luminance, resize, orientation, mjx_batch_tile, the pool, mjx_decode, multi-scan,
+ * restart and progressive inputs compose as with MJX_PIXELS_LIBJPEG. */
+#define MJX_OPTS_IDCT_OFFSET 12
+#define MJX_OPTS_IDCT(opts) (((uint8_t *)(opts))[MJX_OPTS_IDCT_OFFSET])
+enum {
+    MJX_IDCT_FLOAT = 0,       /* stage B's float inverse DCT (every earlier version) */
+    MJX_IDCT_ISLOW = 1        /* libjpeg's integer slow inverse DCT: byte-exact libjpeg pixels, with MJX_PIXELS_LIBJPEG only */
+};
+
 /* ---- output formats: what a picture leaves as, and where -------------------------------------------------------------
  * Without an output description a picture is packed R,G,B uint8 in the batch's own memory.  With one (mjx_batch_create_out,
  * mjx_decode_batch_out) stage B writes, in its one pass over the pixels, H x W x 3 or 3 x H x W elements of uint8, float16 or
@@ -719,13 +756,20 @@ int mjx_resize_filter_weights(uint32_t n_in, uint32_t n_out, int filter, int ant
 /* Host-only: MJX_PIXELS_LIBJPEG's upsampling and colour step on the CPU -- the routines k_upsample_color itself runs (lj_strip8 /
  * lj_color, mjx_kernels.h).  ncomp (1 or 3) dense planes of cw[c] x ch[c] samples, upsampled by rh[c], rv[c] (each 1, 2 or 4); rgb receives
  * the rectangle's rect->w x rect->h pixels, packed R,G,B.  The rectangle must lie inside every upsampled plane (cw[c] rh[c] x
- * ch[c] rv[c]); the plane of an odd picture is one sample short of the picture's size, which the rule allows. */
+ * ch[c] rv[c]); the plane of an odd picture is one sample short of the picture's size, which the rule allows.
+ * MJX_UPSAMPLE_REPLICATE or-ed into rh[c] (the planner's flag for MJX_IDCT_ISLOW's planes of at most two columns): component c is
+ * replicated in both directions, out[X][Y] = s[X / rh][Y / rv], whatever its ratios. */
+#define MJX_UPSAMPLE_REPLICATE 0x80
 int mjx_upsample_color_host(const uint8_t *const *planes, const uint32_t *cw, const uint32_t *ch, const uint8_t *rh, const uint8_t *rv,
                             uint32_t ncomp, const mjx_rect *rect, uint8_t *rgb);
 /* Host-only: MJX_PIXELS_LIBJPEG's luminance picture (MJX_OUTPUT_CHANNELS == 1) on the CPU -- the routine k_upsample_luma itself runs
  * (lj_luma8, mjx_kernels.h).  One dense plane of cw x ch samples, upsampled by rh, rv (each 1, 2 or 4; 1, 1: the plane itself); out receives
- * the rectangle's rect->w x rect->h bytes.  The rectangle must lie inside the upsampled plane. */
+ * the rectangle's rect->w x rect->h bytes.  The rectangle must lie inside the upsampled plane.  MJX_UPSAMPLE_REPLICATE in rh: as above. */
 int mjx_upsample_luma_host(const uint8_t *plane, uint32_t cw, uint32_t ch, uint8_t rh, uint8_t rv, const mjx_rect *rect, uint8_t *out);
+/* Host-only: MJX_IDCT_ISLOW's transform of one block on the CPU -- the lane routine stage B's integer sink itself runs
+ * (idct_islow_inplace, mjx_kernels.h).  coef: the 64 coefficients, q: the 64 raw DQT entries, out: the 64 samples
+ * clamp(x + 128, 0, 255), all three in natural (row-major, [v][u]) order. */
+int mjx_idct_islow_host(const int16_t coef[64], const uint16_t q[64], uint8_t out[64]);
 
 /* mjx_batch_create_resize with an orientation description (above); orient == NULL: mjx_batch_create_resize itself.  Descriptors
  * carry no file bytes: from_exif = 1 is MJX_ERR_INVALID_ARG for the call -- read the tag with mjx_exif_orientation and pass it in

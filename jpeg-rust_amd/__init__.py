@@ -30,6 +30,8 @@ OK, ERR_TRUNCATED, ERR_UNSUPPORTED_MARKER, ERR_DRI_UNSUPPORTED, ERR_BAD_HUFFMAN,
     ERR_UNSUPPORTED_FORMAT, ERR_NO_SCAN, ERR_INVALID_ARG, ERR_NOMEM, ERR_MISSING_TABLE = range(12)
 LAYOUT_STANDARD, LAYOUT_REF_COMPAT = 0, 1
 PIXELS_REFERENCE, PIXELS_LIBJPEG = 0, 1
+IDCT_FLOAT, IDCT_ISLOW = 0, 1
+UPSAMPLE_REPLICATE = 0x80        # mjx.h: MJX_UPSAMPLE_REPLICATE, or-ed into rh of upsample_color_host / upsample_luma_host
 COLOR_POSITIONAL, COLOR_FILE = 0, 1
 MODEL_GREY, MODEL_YCBCR, MODEL_RGB, MODEL_CMYK, MODEL_YCCK = range(5)
 MODEL_NAMES = ["grey", "ycbcr", "rgb", "cmyk", "ycck"]
@@ -79,6 +81,18 @@ def _opts_set_progressive(self, v):
 
 Opts.PROGRESSIVE_OFFSET = 11            # MJX_OPTS_PROGRESSIVE_OFFSET: the next padding byte
 Opts.progressive = property(_opts_progressive, _opts_set_progressive)
+
+
+def _opts_idct(self):
+    return ctypes.c_uint8.from_address(ctypes.addressof(self) + Opts.IDCT_OFFSET).value
+
+
+def _opts_set_idct(self, v):
+    ctypes.c_uint8.from_address(ctypes.addressof(self) + Opts.IDCT_OFFSET).value = int(v)
+
+
+Opts.IDCT_OFFSET = 12                   # MJX_OPTS_IDCT_OFFSET: the next padding byte
+Opts.idct = property(_opts_idct, _opts_set_idct)
 
 
 class Dst(ctypes.Structure):
@@ -266,6 +280,7 @@ SYMBOLS = {
     "mjx_upsample_color_host": (_int, [_P(_P(ctypes.c_uint8)), _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(ctypes.c_uint8), _P(ctypes.c_uint8), ctypes.c_uint32,
                                        _P(Rect), _P(ctypes.c_uint8)]),
     "mjx_upsample_luma_host": (_int, [_P(ctypes.c_uint8), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8, _P(Rect), _P(ctypes.c_uint8)]),
+    "mjx_idct_islow_host": (_int, [_P(ctypes.c_int16), _P(ctypes.c_uint16), _P(ctypes.c_uint8)]),
     "mjx_exif_orientation": (_int, [ctypes.c_char_p, _sz, _P(ctypes.c_uint8)]),
     "mjx_orient_compose": (ctypes.c_uint8, [ctypes.c_uint8, ctypes.c_uint8]),
     "mjx_color_model": (_int, [ctypes.c_char_p, _sz, _P(ColorInfo)]),
@@ -368,8 +383,9 @@ def _rects(rois):
 
 
 def _pixels(pixels):
-    """None / "reference" / PIXELS_REFERENCE, or "libjpeg" / PIXELS_LIBJPEG (mjx.h: mjx_opts.pixels)."""
-    names = {None: PIXELS_REFERENCE, "reference": PIXELS_REFERENCE, "libjpeg": PIXELS_LIBJPEG}
+    """None / "reference" / PIXELS_REFERENCE, or "libjpeg" / PIXELS_LIBJPEG (mjx.h: mjx_opts.pixels); "libjpeg-exact": "libjpeg", and
+    _idct picks the integer inverse DCT with it."""
+    names = {None: PIXELS_REFERENCE, "reference": PIXELS_REFERENCE, "libjpeg": PIXELS_LIBJPEG, "libjpeg-exact": PIXELS_LIBJPEG}
     if pixels is None or isinstance(pixels, str):
         if pixels not in names:
             raise MjxError(ERR_INVALID_ARG, "pixels=%r" % (pixels,))
@@ -377,6 +393,18 @@ def _pixels(pixels):
     if not 0 <= int(pixels) <= 255:
         raise MjxError(ERR_INVALID_ARG, "pixels=%r" % (pixels,))
     return int(pixels)
+
+
+def _idct(idct, pixels=None):
+    """None / "float" / IDCT_FLOAT, or "islow" / IDCT_ISLOW (mjx.h: MJX_OPTS_IDCT); None with pixels="libjpeg-exact" is "islow"."""
+    names = {None: IDCT_ISLOW if pixels == "libjpeg-exact" else IDCT_FLOAT, "float": IDCT_FLOAT, "islow": IDCT_ISLOW}
+    if idct is None or isinstance(idct, str):
+        if idct not in names:
+            raise MjxError(ERR_INVALID_ARG, "idct=%r" % (idct,))
+        return names[idct]
+    if not 0 <= int(idct) <= 255:
+        raise MjxError(ERR_INVALID_ARG, "idct=%r" % (idct,))
+    return int(idct)
 
 
 def _color(color):
@@ -391,11 +419,13 @@ def _color(color):
     return int(color)
 
 
-def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0, device_destuff=False, scale=1, rois=None, pixels=None, color=None, progressive=False):
+def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0, device_destuff=False, scale=1, rois=None, pixels=None, color=None, progressive=False, idct=None):
     """device_destuff: True = on the GPU, False = on the host, None = the library's choice (mjx.h: MJX_DESTUFF_*).
     scale: 1, 2, 4 or 8 -- the picture decoded at 1/scale in the DCT domain (mjx.h: mjx_opts.scale_denom).
     rois: see _rects (mjx.h: mjx_opts.rois, n_rois); the Opts returned keeps the array alive.
     pixels: see _pixels -- "libjpeg": rounded samples, fancy chroma upsampling and libjpeg's integer colour tables.
+    idct: see _idct -- "islow": libjpeg's integer slow inverse DCT, with pixels="libjpeg" only: the picture is byte for byte libjpeg's
+    (mjx.h: MJX_OPTS_IDCT); pixels="libjpeg-exact" is shorthand for pixels="libjpeg", idct="islow".
     color: see _color -- "file": the colour model comes from the file (RGB, CMYK and YCCK files decode to R,G,B).
     progressive: True -- progressive files (SOF2) are accepted (mjx.h: MJX_OPTS_PROGRESSIVE); an integer is passed through as it is."""
     dd = DESTUFF_AUTO if device_destuff is None else (DESTUFF_DEVICE if device_destuff else DESTUFF_HOST)
@@ -404,6 +434,7 @@ def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_imag
         raise MjxError(ERR_INVALID_ARG, "scale=%d" % scale)
     o = Opts(int(bool(strict_ref)), int(layout), int(bool(keep_coefs)), dd, int(chunk_images), _pixels(pixels), scale)
     o.color = _color(color)
+    o.idct = _idct(idct, pixels)
     o.progressive = int(progressive) if not isinstance(progressive, bool) and 0 <= int(progressive) <= 255 else int(bool(progressive))
     arr = _rects(rois)
     if arr is not None:
@@ -655,6 +686,17 @@ def upsample_luma_host(plane, rh, rv, rect):
     return out[:h, :w]
 
 
+def idct_islow_host(coef, q):
+    """mjx_idct_islow_host (host only; the lane routine stage B's integer sink runs): one block's 64 coefficients (int16) and its 64
+    raw DQT entries (uint16), both [8, 8] in natural order -> ndarray [8, 8] uint8, the samples of idct="islow"."""
+    c = np.ascontiguousarray(coef, np.int16).reshape(64)
+    t = np.ascontiguousarray(q, np.uint16).reshape(64)
+    out = np.zeros(64, np.uint8)
+    _check(lib().mjx_idct_islow_host(c.ctypes.data_as(_P(ctypes.c_int16)), t.ctypes.data_as(_P(ctypes.c_uint16)),
+                                     out.ctypes.data_as(_P(ctypes.c_uint8))), "mjx_idct_islow_host")
+    return out.reshape(8, 8)
+
+
 def _out_ref(output):
     if output is None:
         return None, None
@@ -677,15 +719,15 @@ class ParsedScan:
     def scan_bytes(self):
         return ctypes.string_at(self.desc.scan, self.desc.scan_len)
 
-    def validate(self, layout=LAYOUT_STANDARD, strict_ref=False, scale=1, roi=None, pixels=None, color=None, progressive=False):
+    def validate(self, layout=LAYOUT_STANDARD, strict_ref=False, scale=1, roi=None, pixels=None, color=None, progressive=False, idct=None):
         """Status mjx_batch_create would give this image (host only).  roi: (x, y, w, h) in the scaled picture's coordinates."""
-        o = _opts(layout=layout, strict_ref=strict_ref, scale=scale, rois=roi, pixels=pixels, color=color, progressive=progressive)
+        o = _opts(layout=layout, strict_ref=strict_ref, scale=scale, rois=roi, pixels=pixels, idct=idct, color=color, progressive=progressive)
         return int(lib().mjx_validate(ctypes.byref(self.desc), ctypes.byref(o)))
 
-    def plan_tiles(self, roi=None, scale=1, pixels=None, color=None, progressive=False):
+    def plan_tiles(self, roi=None, scale=1, pixels=None, color=None, progressive=False, idct=None):
         """mjx_plan_tiles (host only) -> dict(tiles_read, tiles_total, tile_mcus): the stage-B tiles a decode with this rectangle
         fetches and transforms, of the picture's tiles, and the MCUs a tile holds."""
-        o = _opts(scale=scale, rois=roi, pixels=pixels, color=color, progressive=progressive)
+        o = _opts(scale=scale, rois=roi, pixels=pixels, idct=idct, color=color, progressive=progressive)
         rd, tot, t = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
         _check(lib().mjx_plan_tiles(ctypes.byref(self.desc), ctypes.byref(o), ctypes.byref(rd), ctypes.byref(tot), ctypes.byref(t)), "mjx_plan_tiles")
         return dict(tiles_read=rd.value, tiles_total=tot.value, tile_mcus=t.value)
@@ -700,13 +742,13 @@ class ParsedScan:
         return dict(width=lay.width, height=lay.height, row_pitch=lay.row_pitch, plane_pitch=lay.plane_pitch, bytes=nb.value, dev=lay.dev or 0)
 
     def planes_layout(self, planes, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD, pixels=None, strict_ref=False, color=None, progressive=False,
-                      resize=None, code=None):
+                      resize=None, code=None, idct=None):
         """mjx_planes_layout (host only) -> dict(nplanes, width, height, row_pitch, dev -- a list of three each --, bytes): the planes a
         decode of this picture as input i of a call with this Planes would write; pitches in elements, sizes in samples.
         resize (a Resize) and / or code (the resolved orientation, 1 .. 8): mjx_planes_orient_layout -- the planes that LEAVE such a
         call (roi in the turned picture's coordinates, full size with auto_scale), and on top of the keys above `scale`, the scale the
         picture is decoded at, and `rect` = (x, y, w, h), the rectangle of the stored picture its intermediate covers."""
-        o = _opts(layout=layout, scale=scale, rois=roi, pixels=pixels, strict_ref=strict_ref, color=color, progressive=progressive)
+        o = _opts(layout=layout, scale=scale, rois=roi, pixels=pixels, idct=idct, strict_ref=strict_ref, color=color, progressive=progressive)
         keep, ref = _planes_ref(planes)
         if resize is not None or code is not None:
             keep_rs, rs_ref = _rs_ref(resize)
@@ -726,10 +768,10 @@ class ParsedScan:
         return dict(nplanes=np_.value, width=list(lay.width), height=list(lay.height), row_pitch=list(lay.row_pitch),
                     dev=[v or 0 for v in lay.dev], bytes=nb.value)
 
-    def resize_plan(self, resize, roi=None, scale=1, i=0, layout=LAYOUT_STANDARD, pixels=None):
+    def resize_plan(self, resize, roi=None, scale=1, i=0, layout=LAYOUT_STANDARD, pixels=None, idct=None):
         """mjx_resize_plan (host only) -> dict(scale, rect=(x, y, w, h) at that scale, taps_x, taps_y): what a resized decode of this
         picture with this Resize takes; roi in full-size coordinates with auto_scale, else in the scaled picture's."""
-        o = _opts(layout=layout, scale=scale, rois=roi, pixels=pixels)
+        o = _opts(layout=layout, scale=scale, rois=roi, pixels=pixels, idct=idct)
         keep, ref = _rs_ref(resize)
         s, r, tx, ty = ctypes.c_uint8(), Rect(), ctypes.c_uint32(), ctypes.c_uint32()
         _check(lib().mjx_resize_plan(ctypes.byref(self.desc), ctypes.byref(o), ref, int(i), ctypes.byref(s), ctypes.byref(r), ctypes.byref(tx), ctypes.byref(ty)), "mjx_resize_plan")
@@ -806,7 +848,7 @@ class Batch:
     """Device-resident batch: inputs uploaded at construction, ``decode()`` only enqueues kernels."""
 
     def __init__(self, ctx, scans=None, strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_images=0,
-                 _handle=None, scale=1, rois=None, output=None, resize=None, orient=None, datas=None, pixels=None, planes=None, color=None, progressive=False):
+                 _handle=None, scale=1, rois=None, output=None, resize=None, orient=None, datas=None, pixels=None, planes=None, color=None, progressive=False, idct=None):
         """scale: 1, 2, 4 or 8 -- every picture decoded at 1/scale (info(), rgb(), rgb_device() and bytes() then speak of the
         scaled picture; tile() keeps the scale).
         rois: one (x, y, w, h) for every picture, or a list with one per picture (None or (0, 0, 0, 0): the whole picture), in the
@@ -841,7 +883,7 @@ class Batch:
             ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(s.desc if isinstance(s, ParsedScan) else s),
                            ctypes.sizeof(ScanDesc))
         st = (_int * max(n, 1))()
-        o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois, pixels=pixels, color=color, progressive=progressive)
+        o = _opts(strict_ref, layout, keep_coefs, chunk_images, scale=scale, rois=rois, pixels=pixels, idct=idct, color=color, progressive=progressive)
         keep, ref = _out_ref(output)
         if planes is not None and (resize is not None or orient is not None):
             if output is not None:
@@ -1204,14 +1246,14 @@ class JPEGImage:
         self._w, self._h, self._rgb = width, height, rgb
 
     @staticmethod
-    def parse(data, strict_ref=False, layout=LAYOUT_STANDARD, ctx=None, scale=1, roi=None, pixels=None, color=None, progressive=False):
+    def parse(data, strict_ref=False, layout=LAYOUT_STANDARD, ctx=None, scale=1, roi=None, pixels=None, color=None, progressive=False, idct=None):
         """scale: 1, 2, 4 or 8 -- the picture at 1/scale (width() and height() are the scaled picture's).
         roi: (x, y, w, h) of the scaled picture -- only that rectangle is produced (width() and height() are its).
         pixels: "libjpeg", color: "file" -- see Batch."""
         ctx = ctx or default_context()
         scan = ParsedScan(data, strict_ref=strict_ref, color=color, progressive=progressive)
         try:
-            b = Batch(ctx, [scan], strict_ref=strict_ref, layout=layout, scale=scale, rois=roi, pixels=pixels, color=color, progressive=progressive)
+            b = Batch(ctx, [scan], strict_ref=strict_ref, layout=layout, scale=scale, rois=roi, pixels=pixels, idct=idct, color=color, progressive=progressive)
             try:
                 if b.create_status[0] != OK:
                     raise MjxError(b.create_status[0])
@@ -1238,7 +1280,7 @@ class JPEGImage:
 
 
 def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0, device_destuff=None, keep_coefs=False, scale=1, rois=None,
-                 output=None, chunk_images=0, resize=None, orient=None, pixels=None, planes=None, color=None, progressive=False):
+                 output=None, chunk_images=0, resize=None, orient=None, pixels=None, planes=None, color=None, progressive=False, idct=None):
     """mjx_decode_batch: parse (host threads) + GPU decode of a list of files -> (Batch, [status per file]).  scale, rois, pixels, color: see Batch.
     device_destuff: the host copies the entropy-coded bytes as they are; de-stuffing, restart markers and the scan's length
     are found on the GPU.  output: an Output (mjx_decode_batch_out) -- see Batch.  resize: a Resize (mjx_decode_batch_resize).  orient: an Orient
@@ -1250,7 +1292,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
     st = (_int * max(n, 1))()
     ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
     h = _vp()
-    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, color=color, progressive=progressive)
+    o = _opts(strict_ref, layout, keep_coefs=keep_coefs, chunk_images=chunk_images, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, idct=idct, color=color, progressive=progressive)
     if planes is not None:
         if output is not None:
             raise MjxError(ERR_INVALID_ARG, "planes go without output")
@@ -1283,7 +1325,7 @@ def decode_batch(ctx, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads=0
 
 
 def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=False, threads=0, device_destuff=None, planar=None, resize=None,
-                orient=None, pixels=None, color=None, progressive=False, pad=0):
+                orient=None, pixels=None, color=None, progressive=False, pad=0, idct=None):
     """Decodes the files straight into a torch tensor on the context's device: N x 3 x H x W (planar) or N x H x W x 3, of uint8,
     float16 or float32; picture i -- at 1/scale, its rectangle rois[i] -- must be H x W.  Float tensors take (v / 255 - mean) / std
     per OUTPUT channel (see Output); bgr: channel 0 is blue.  The pointers and pitches come from data_ptr() and stride(): the
@@ -1356,13 +1398,13 @@ def decode_into(ctx, datas, out, scale=1, rois=None, mean=None, std=None, bgr=Fa
             raise MjxError(ERR_INVALID_ARG, "resize to %d x %d into a tensor of %d x %d" % (resize.width, resize.height, w, h))
     else:
         rs = None
-    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt, resize=rs, orient=orient, pixels=pixels, color=color, progressive=progressive)
+    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, output=fmt, resize=rs, orient=orient, pixels=pixels, idct=idct, color=color, progressive=progressive)
     batch.close()
     return status
 
 
 def decode_planes_into(ctx, datas, y, cb=None, cr=None, cbcr=None, scale=1, rois=None, mean=None, std=None, threads=0, device_destuff=None, pixels=None,
-                       resize=None, orient=None):
+                       resize=None, orient=None, idct=None):
     """Decodes the files' component planes straight into torch tensors on the context's device: decode_planes_into(ctx, datas, y, cb,
     cr) with y N x Hy x Wy, cb and cr N x Hc x Wc, or decode_planes_into(ctx, datas, y, cbcr=t) with t N x Hc x Wc x 2 (NV12's second
     plane); one-component files take y alone.  All pictures of the call have one size and layout; tensors are of one dtype (uint8,
@@ -1409,7 +1451,7 @@ def decode_planes_into(ctx, datas, y, cb=None, cr=None, cbcr=None, scale=1, rois
         rs = Resize(w, h) if resize is True else resize.sized(w, h)
         if resize is not True and (resize.width or resize.height) and (resize.width, resize.height) != (w, h):
             raise MjxError(ERR_INVALID_ARG, "resize to %d x %d into a tensor of %d x %d" % (resize.width, resize.height, w, h))
-    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, planes=fmt,
+    batch, status = decode_batch(ctx, datas, threads=threads, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, idct=idct, planes=fmt,
                                  resize=rs, orient=orient)
     batch.close()
     return status
@@ -1434,7 +1476,7 @@ class Pool:
     def set_deal(self, round_robin):
         _check(lib().mjx_pool_set_deal(self.h, 1 if round_robin else 0), "mjx_pool_set_deal")
 
-    def decode_batch(self, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads_per_device=0, device_destuff=None, scale=1, rois=None, pixels=None, color=None, progressive=False):
+    def decode_batch(self, datas, strict_ref=False, layout=LAYOUT_STANDARD, threads_per_device=0, device_destuff=None, scale=1, rois=None, pixels=None, color=None, progressive=False, idct=None):
         """-> PoolResult; .slot_of[i], .status[i], .rgb(i), .rc (the call's return code: a failed slot fails its own files only).
         scale, rois, pixels, color: see Batch (a file's rectangle follows it to its slot)."""
         n = len(datas)
@@ -1444,7 +1486,7 @@ class Pool:
         slots = (_int * max(n, 1))()
         ptrs = (_P(ctypes.c_uint8) * max(n, 1))()
         h = _vp()
-        o = _opts(strict_ref, layout, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, color=color, progressive=progressive)
+        o = _opts(strict_ref, layout, device_destuff=device_destuff, scale=scale, rois=rois, pixels=pixels, idct=idct, color=color, progressive=progressive)
         rc = lib().mjx_pool_decode_batch(self.h, arr, lens, n, ctypes.byref(o), int(threads_per_device), slots, ptrs, st, ctypes.byref(h))
         if not h:
             _check(rc, "mjx_pool_decode_batch")
@@ -1532,20 +1574,20 @@ class PoolResult:
             pass
 
 
-def plan_tiles(data, roi=None, scale=1, pixels=None, color=None, progressive=False):
+def plan_tiles(data, roi=None, scale=1, pixels=None, color=None, progressive=False, idct=None):
     """Host only: the stage-B tiles a decode of this file with this rectangle and scale reads -> see ParsedScan.plan_tiles."""
     scan = ParsedScan(data, color=color, progressive=progressive)
     try:
-        return scan.plan_tiles(roi=roi, scale=scale, pixels=pixels, color=color, progressive=progressive)
+        return scan.plan_tiles(roi=roi, scale=scale, pixels=pixels, idct=idct, color=color, progressive=progressive)
     finally:
         scan.close()
 
 
-def resize_plan(data, resize, roi=None, scale=1, pixels=None):
+def resize_plan(data, resize, roi=None, scale=1, pixels=None, idct=None):
     """Host only: the scale, rectangle and tap counts of a resized decode of this file -> see ParsedScan.resize_plan."""
     scan = ParsedScan(data)
     try:
-        return scan.resize_plan(resize, roi=roi, scale=scale, pixels=pixels)
+        return scan.resize_plan(resize, roi=roi, scale=scale, pixels=pixels, idct=idct)
     finally:
         scan.close()
 
@@ -1559,12 +1601,12 @@ def orient_plan(data, code, resize=None, roi=None, scale=1):
         scan.close()
 
 
-def planes_layout(data, planes, i=0, roi=None, scale=1, pixels=None, resize=None, code=None):
+def planes_layout(data, planes, i=0, roi=None, scale=1, pixels=None, resize=None, code=None, idct=None):
     """Host only: the planes a decode of this file as input i with this Planes would write -> see ParsedScan.planes_layout (resize, code:
     the planes that leave a call with a resize and / or an orientation)."""
     scan = ParsedScan(data)
     try:
-        return scan.planes_layout(planes, i=i, roi=roi, scale=scale, pixels=pixels, resize=resize, code=code)
+        return scan.planes_layout(planes, i=i, roi=roi, scale=scale, pixels=pixels, idct=idct, resize=resize, code=code)
     finally:
         scan.close()
 
@@ -1592,11 +1634,11 @@ def ink_mul(a, k):
     return int(lib().mjx_ink_mul(int(a), int(k)))
 
 
-def decode(data, strict_ref=False, layout=LAYOUT_STANDARD, scale=1, roi=None, pixels=None, color=None, progressive=False):
+def decode(data, strict_ref=False, layout=LAYOUT_STANDARD, scale=1, roi=None, pixels=None, color=None, progressive=False, idct=None):
     """One-shot C entry point mjx_decode (parse + GPU decode + copy back) -> ndarray [H, W, 3] uint8.  scale: see Batch.
     roi: (x, y, w, h) of the scaled picture -- the array is that rectangle, [h, w, 3]."""
     img = Image()
-    o = _opts(strict_ref, layout, scale=scale, rois=roi, pixels=pixels, color=color, progressive=progressive)
+    o = _opts(strict_ref, layout, scale=scale, rois=roi, pixels=pixels, idct=idct, color=color, progressive=progressive)
     _check(lib().mjx_decode(bytes(data), len(data), ctypes.byref(o), ctypes.byref(img)), "mjx_decode")
     try:
         return np.ctypeslib.as_array(img.rgb, (img.height, img.width, 3)).copy()

@@ -118,7 +118,7 @@ public:
         mjx_image img{0, 0, nullptr};
         Result r;
         mjx_opts o{};
-        if (opts) { o = *opts; MJX_OPTS_COLOR(&o) = MJX_OPTS_COLOR(opts); MJX_OPTS_PROGRESSIVE(&o) = MJX_OPTS_PROGRESSIVE(opts); }      // (the colour and progressive options are bytes outside the members)
+        if (opts) { o = *opts; MJX_OPTS_COLOR(&o) = MJX_OPTS_COLOR(opts); MJX_OPTS_PROGRESSIVE(&o) = MJX_OPTS_PROGRESSIVE(opts); MJX_OPTS_IDCT(&o) = MJX_OPTS_IDCT(opts); }      // (the colour, progressive and inverse-DCT options are bytes outside the members)
         if (color_from_file) MJX_OPTS_COLOR(&o) = MJX_COLOR_FILE;
         if (scale_denom) o.scale_denom = uint8_t(scale_denom > 255 ? 255 : scale_denom);
         if (roi) { o.rois = roi; o.n_rois = 1; }

@@ -164,6 +164,7 @@ struct ImageInfo {
 enum PostPass : uint32_t {
     kPassUpsample,          // libjpeg's pixels: the chunk's component planes -> its pictures (or the intermediates of the passes below)
     kPassUpsampleLuma,      // ... luminance pictures: component 0's plane alone
+    kPassUpsampleRep,       // ... the integer inverse DCT's pictures with a replicated component (DevImage::lj_rep), luminance or not
     kPassResize,            // resize on the device: the intermediates -> the target pictures (per filter kind)
     kPassOrient,            // orientation on the device: k_orient_out copies
     kPassResizeOrient,      // ... k_resize_orient resamples (per filter kind)
@@ -545,7 +546,7 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
     const StageBChoice sb = stage_b_choice(p);          // what stage B and the passes behind it do with the picture: decided there alone
     d.mode = sb.mode;
     d.rs_on = sb.rs_on; d.or_on = sb.or_on; d.out_ch = sb.out_ch;
-    d.lj_on = sb.lj_on; d.lj_luma = sb.lj_luma; d.lj_out = sb.lj_out;
+    d.lj_on = sb.lj_on; d.lj_luma = sb.lj_luma; d.lj_out = sb.lj_out; d.lj_rep = sb.lj_rep;
     d.scale = p.scale;
     d.out_w = p.out_w;
     d.out_h = p.out_h;
@@ -743,10 +744,10 @@ void plan_chunks(mjx_batch *b)
                     c.plane_words += uint64_t(d.width) * d.height * d.ncomp;
                     c.max_pixel_wgs = std::max<uint32_t>(c.max_pixel_wgs, uint32_t((uint64_t(d.width) * d.height + 255) / 256));
                 }
-                if ((d.lj_on || d.lj_luma) && d.role != 1) {        // (the planes span the MCU grid: whole 64-byte block rows, so every plane starts on a multiple of 8)
+                if ((d.lj_on || d.lj_luma || d.lj_rep) && d.role != 1) {        // (the planes span the MCU grid: whole 64-byte block rows, so every plane starts on a multiple of 8)
                     d.plane_off = c.lj_words;
                     c.lj_words += (d.lj_off[d.ncomp - 1] + uint64_t(d.lj_stride[d.ncomp - 1]) * d.mcuy * 8 * d.cv[d.ncomp - 1]) / 8;
-                    pass(d.lj_luma ? kPassUpsampleLuma : kPassUpsample, 0, lj_tiles(d.roi_x, d.roi_w, d.roi_h));
+                    pass(d.lj_rep ? kPassUpsampleRep : d.lj_luma ? kPassUpsampleLuma : kPassUpsample, 0, lj_tiles(d.roi_x, d.roi_w, d.roi_h));
                 }
                 c.max_segs = std::max<uint32_t>(c.max_segs, (d.nmcu + kDcSegMcus - 1) / kDcSegMcus);
             }
@@ -1084,6 +1085,9 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
                 switch (k) {
                 case kPassUpsample: case kPassUpsampleLuma:
                     launch_upsample_color(sp, tiles, nimg, imgs, reinterpret_cast<const uint8_t *>(SCR(d_planes)), b->d_rgb, b->d_img_flags, k == kPassUpsampleLuma);
+                    break;
+                case kPassUpsampleRep:
+                    launch_upsample_rep(sp, tiles, nimg, imgs, reinterpret_cast<const uint8_t *>(SCR(d_planes)), b->d_rgb, b->d_img_flags);
                     break;
                 case kPassResize: launch_resize_out(sp, tiles, nimg, imgs, b->d_rgb, b->d_img_flags, f); break;
                 case kPassOrient: case kPassOrientLuma: launch_orient_out(sp, tiles, nimg, imgs, b->d_rgb, b->d_img_flags, k == kPassOrientLuma); break;
@@ -1785,7 +1789,8 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
                 const ImagePlan &p = plans[k];
                 if (p.status != MJX_OK) continue;
                 if (lut_first[k]) std::memcpy(h_lut + lut_off[k], p.lut.data(), p.lut.size() * sizeof(LutEntry));
-                std::memcpy(h_qm + k * 192, p.qmult, 192 * sizeof(float));
+                if (p.islow) std::memcpy(h_qm + k * 192, p.qint, 192 * sizeof(uint32_t));      // (the integer inverse DCT: the raw DQT entries' bits in the float multipliers' place)
+                else std::memcpy(h_qm + k * 192, p.qmult, 192 * sizeof(float));
                 std::memcpy(h_qm + (nu + k) * 192, p.qmult_scaled, 192 * sizeof(float));
                 if (p.ncomp == 4) {
                     std::memcpy(h_qm + qm_tail[k], p.qmult[3], 64 * sizeof(float));
@@ -2199,7 +2204,7 @@ extern "C" int mjx_planes_orient_layout(const mjx_scan_desc *desc, const mjx_opt
     if (!o.rois ? o.n_rois != 0 : (o.n_rois == 0 || (o.n_rois > 1 && i >= o.n_rois))) return MJX_ERR_INVALID_ARG;
     if (o.rois) { if (o.n_rois > 1) o.rois += i; o.n_rois = 1; }
     if (pl->dst ? i >= pl->n_dst : pl->n_dst != 0) return MJX_ERR_INVALID_ARG;
-    if (opts) { MJX_OPTS_COLOR(&o) = MJX_OPTS_COLOR(opts); MJX_OPTS_PROGRESSIVE(&o) = MJX_OPTS_PROGRESSIVE(opts); }
+    if (opts) { MJX_OPTS_COLOR(&o) = MJX_OPTS_COLOR(opts); MJX_OPTS_PROGRESSIVE(&o) = MJX_OPTS_PROGRESSIVE(opts); MJX_OPTS_IDCT(&o) = MJX_OPTS_IDCT(opts); }
     std::vector<ImagePlan> plans;
     plan_input_for(*desc, o, nullptr, rs, i, plans, code, pl);
     const ImagePlan &p = plans.back();
@@ -2429,13 +2434,14 @@ extern "C" int mjx_upsample_color_host(const uint8_t *const *planes, const uint3
     std::vector<std::vector<uint64_t>> store(ncomp);
     LjPlane pl[3];
     for (uint32_t c = 0; c < ncomp; c++) {
-        if (!planes[c] || !cw[c] || !ch[c] || cw[c] > kResizeMaxDim || ch[c] > kResizeMaxDim || !sampling_factor_ok(rh[c]) || !sampling_factor_ok(rv[c])) return MJX_ERR_INVALID_ARG;
-        if ((rect->x + rect->w - 1) / rh[c] >= cw[c] || (rect->y + rect->h - 1) / rv[c] >= ch[c]) return MJX_ERR_INVALID_ARG;
+        const uint8_t rhc = rh[c] & uint8_t(~MJX_UPSAMPLE_REPLICATE);          // (the flag: the component is replicated whatever its ratios)
+        if (!planes[c] || !cw[c] || !ch[c] || cw[c] > kResizeMaxDim || ch[c] > kResizeMaxDim || !sampling_factor_ok(rhc) || !sampling_factor_ok(rv[c])) return MJX_ERR_INVALID_ARG;
+        if ((rect->x + rect->w - 1) / rhc >= cw[c] || (rect->y + rect->h - 1) / rv[c] >= ch[c]) return MJX_ERR_INVALID_ARG;
         const uint32_t stride = (cw[c] + 7u) & ~7u;
         store[c].assign(size_t(stride) / 8 * ch[c], 0xa5a5a5a5a5a5a5a5ull);
         uint8_t *dst = reinterpret_cast<uint8_t *>(store[c].data());
         for (uint32_t y = 0; y < ch[c]; y++) std::memcpy(dst + size_t(y) * stride, planes[c] + size_t(y) * cw[c], cw[c]);
-        pl[c] = LjPlane{dst, stride, cw[c], ch[c], rh[c], rv[c]};
+        pl[c] = LjPlane{dst, stride, cw[c], ch[c], rhc, rv[c], (rh[c] & MJX_UPSAMPLE_REPLICATE) ? 1u : 0u};
     }
     for (uint32_t c = ncomp; c < 3; c++) pl[c] = pl[0];
     for (uint32_t y = rect->y; y < rect->y + rect->h; y++)
@@ -2453,10 +2459,25 @@ extern "C" int mjx_upsample_color_host(const uint8_t *const *planes, const uint3
     });
 }
 
+// Host-only: libjpeg's integer slow inverse DCT of one block -- the lane routine stage B's integer sink runs (idct_islow_inplace).
+extern "C" int mjx_idct_islow_host(const int16_t coef[64], const uint16_t q[64], uint8_t out[64])
+{
+    return guarded([&]() -> int {
+    if (!coef || !q || !out) return MJX_ERR_INVALID_ARG;
+    alignas(16) uint32_t blk[64];
+    for (int k = 0; k < 64; k++) blk[k] = uint32_t(int32_t(coef[k])) * uint32_t(q[k]);
+    idct_islow_inplace(blk);
+    for (int k = 0; k < 64; k++) out[k] = uint8_t(islow_sample(blk[k]));
+    return MJX_OK;
+    });
+}
+
 // Host-only: the luminance picture of MJX_PIXELS_LIBJPEG on the CPU -- the routine k_upsample_luma itself runs (lj_luma8).
 extern "C" int mjx_upsample_luma_host(const uint8_t *plane, uint32_t cw, uint32_t ch, uint8_t rh, uint8_t rv, const mjx_rect *rect, uint8_t *out)
 {
     return guarded([&]() -> int {
+    const uint32_t rep = (rh & MJX_UPSAMPLE_REPLICATE) ? 1u : 0u;              // (the flag, as in mjx_upsample_color_host)
+    rh &= uint8_t(~MJX_UPSAMPLE_REPLICATE);
     if (!plane || !rect || !out || !rect->w || !rect->h || !cw || !ch || cw > kResizeMaxDim || ch > kResizeMaxDim) return MJX_ERR_INVALID_ARG;
     if (!sampling_factor_ok(rh) || !sampling_factor_ok(rv)) return MJX_ERR_INVALID_ARG;
     if (rect->x > kResizeMaxDim || rect->y > kResizeMaxDim || rect->w > kResizeMaxDim || rect->h > kResizeMaxDim) return MJX_ERR_INVALID_ARG;
@@ -2465,7 +2486,7 @@ extern "C" int mjx_upsample_luma_host(const uint8_t *plane, uint32_t cw, uint32_
     std::vector<uint64_t> store(size_t(stride) / 8 * ch, 0xa5a5a5a5a5a5a5a5ull);
     uint8_t *dst = reinterpret_cast<uint8_t *>(store.data());
     for (uint32_t y = 0; y < ch; y++) std::memcpy(dst + size_t(y) * stride, plane + size_t(y) * cw, cw);
-    const LjPlane pl{dst, stride, cw, ch, rh, rv};
+    const LjPlane pl{dst, stride, cw, ch, rh, rv, rep};
     for (uint32_t y = rect->y; y < rect->y + rect->h; y++)
         for (uint32_t X0 = rect->x & ~(kLjStrip - 1u); X0 < rect->x + rect->w; X0 += kLjStrip) {
             uint32_t w[2];
@@ -2535,7 +2556,9 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
         p.width = d.width; p.height = d.height; p.ncomp = d.ncomp; p.bpm = d.bpm; p.hmax = d.hmax; p.vmax = d.vmax;
         p.scale = d.scale ? d.scale : 1u; p.out_w = d.out_w; p.out_h = d.out_h;      // (the copies keep the source's scale)
         p.cropped = src->info[k].cropped;                                             // (... and its rectangle)
-        p.lj = src->himages[k].lj_on != 0 || src->himages[k].lj_luma != 0;                                            // (... and its pixels)
+        p.lj = src->himages[k].lj_on != 0 || src->himages[k].lj_luma != 0 || src->himages[k].lj_rep != 0;             // (... and its pixels)
+        p.islow = sink_of(src->himages[k].mode) == kSinkPlanesInt;                                                    // (... and its inverse DCT,
+        p.lj_rep = src->himages[k].lj_rep & 7u;                                                                       // whose replicated components keep their bits)
         if (src->info[k].out_on) {                                                    // (... and its output format)
             const ImageInfo &fi = src->info[k];
             p.out_on = true;
@@ -3694,10 +3717,10 @@ extern "C" void mjx_free_image(mjx_image *img)
 
 extern "C" const char *mjx_version(void)
 {
-    static char v[160];
+    static char v[200];
     static std::once_flag once;
     std::call_once(once, [] {
-        std::snprintf(v, sizeof v, "mjx 0.3 abi=%d gfx950 subseq_bits=%d..%d checkpoint_bits=%d lut_primary_bits=%d huff_wg_lanes=%d merge_wg_lanes=%d",
+        std::snprintf(v, sizeof v, "mjx 0.3 abi=%d gfx950 subseq_bits=%d..%d checkpoint_bits=%d lut_primary_bits=%d huff_wg_lanes=%d merge_wg_lanes=%d idct=float,islow",
                       MJX_ABI_VERSION, kSubseqBits, kSubseqBits * 5 / 4, kCpBits, kLutPrimaryBits, kHuffWg, kMergeWg);
     });
     return v;

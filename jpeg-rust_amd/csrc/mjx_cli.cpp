@@ -3,7 +3,8 @@
 // --crop: only that rectangle of the -- scaled -- picture is decoded and written, mjx_opts.rois; --libjpeg-pixels: rounded samples,
 // fancy chroma upsampling and libjpeg's integer colour tables, mjx_opts.pixels = MJX_PIXELS_LIBJPEG; --color-from-file: the file says
 // what its components are, MJX_OPTS_COLOR = MJX_COLOR_FILE -- RGB, CMYK and YCCK files are written as R,G,B; --progressive: progressive
-// files (SOF2) are accepted, MJX_OPTS_PROGRESSIVE = 1)
+// files (SOF2) are accepted, MJX_OPTS_PROGRESSIVE = 1; --islow: --libjpeg-pixels with libjpeg's integer inverse DCT, MJX_OPTS_IDCT =
+// MJX_IDCT_ISLOW -- byte for byte the picture libjpeg gives)
 // Writes the same ASCII P3 file ("P3\n{w} {h}\n255\n" then "r g b\n" per pixel, main.rs:35-39), buffered; --p6 writes
 // binary PPM instead.  --luma: the luminance picture (MJX_OUTPUT_CHANNELS = 1) through the batch API, written as binary PGM (P5); chroma
 // is never transformed.  --ycc: the component planes at their own sampling (mjx_planes), written back to back as one raw file -- Y,
@@ -89,7 +90,7 @@ static int write_planes(const std::vector<uint8_t> &bytes, const mjx_opts &opts,
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s <input.jpeg> <output.ppm> [--p6] [--strict] [--ref-compat] [--scale N] [--crop X,Y,W,H] [--libjpeg-pixels] [--color-from-file] [--progressive] [--luma] [--ycc] [--nv12]\n", argv[0]);   // main.rs:26-28 expect()
+        std::fprintf(stderr, "usage: %s <input.jpeg> <output.ppm> [--p6] [--strict] [--ref-compat] [--scale N] [--crop X,Y,W,H] [--libjpeg-pixels] [--islow] [--color-from-file] [--progressive] [--luma] [--ycc] [--nv12]\n", argv[0]);   // main.rs:26-28 expect()
         return MJX_ERR_INVALID_ARG;
     }
     bool p6 = false, luma = false, ycc = false, nv12 = false;
@@ -103,6 +104,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--strict")) opts.strict_ref = 1;
         else if (!std::strcmp(argv[i], "--ref-compat")) opts.layout = MJX_LAYOUT_REF_COMPAT;
         else if (!std::strcmp(argv[i], "--libjpeg-pixels")) opts.pixels = MJX_PIXELS_LIBJPEG;
+        else if (!std::strcmp(argv[i], "--islow")) { opts.pixels = MJX_PIXELS_LIBJPEG; MJX_OPTS_IDCT(&opts) = MJX_IDCT_ISLOW; }      // (implies --libjpeg-pixels)
         else if (!std::strcmp(argv[i], "--color-from-file")) MJX_OPTS_COLOR(&opts) = MJX_COLOR_FILE;
         else if (!std::strcmp(argv[i], "--progressive")) MJX_OPTS_PROGRESSIVE(&opts) = 1;
         else if (!std::strcmp(argv[i], "--scale")) {

@@ -163,7 +163,14 @@ struct DevImage {
     // the chunk's dense store, k_prog_count / _offsets / _copy build the stream from it (the k_planar_* kernels pass over the picture);
     // prog_pic: its ProgPic (mjx_prog.h) in the batch's array.
     uint32_t prog, prog_pic;
+    // libjpeg's integer inverse DCT (MJX_OPTS_IDCT = MJX_IDCT_ISLOW; kSinkPlanesInt): stage B's planes hold clamp(x + 128, 0, 255) of the
+    // integer transform, and qm_off points at the components' raw DQT entries (uint32, zig-zag order, 64 each) in the multiplier pool.
+    // lj_rep != 0: a picture with a component of at most two columns and ratios (2, 1) or (2, 2), which jdsample.c replicates --
+    // kLjRepOn | bit c per replicated component | kLjRepLuma for a luminance picture.  Such a picture has lj_on = lj_luma = 0 and is
+    // k_upsample_rep's; lj_out says where it leaves as for k_upsample_color.
+    uint32_t lj_rep;
 };
+constexpr uint32_t kLjRepOn = 16u, kLjRepLuma = 32u;
 // DevImage::model
 enum ColorModel : uint32_t {
     kModelPositional = 0,   // grey, or Y, Cb, Cr by position: the pixel phase as it has always been
@@ -193,8 +200,9 @@ enum StageBSink : uint32_t {
     kSinkPlanes = 3,        // libjpeg's pixels: rounded component planes in the chunk's scratch, kFormGeneric only (k_upsample_color follows)
     kSinkLuma = 4,          // luminance: component 0 alone, one element per pixel
     kSinkYcc = 5,           // YCbCr output: the component planes as the picture (4:2:0 takes kFormGeneric)
+    kSinkPlanesInt = 6,     // libjpeg's pixels with its integer inverse DCT (MJX_IDCT_ISLOW): kSinkPlanes on an int32 tile, kFormGeneric only
 };
-constexpr uint32_t kStageBSinks = 6;
+constexpr uint32_t kStageBSinks = 7;
 MJX_HD constexpr uint32_t stage_b_mode(uint32_t form, uint32_t sink) { return form | sink << 3; }
 MJX_HD constexpr StageBForm form_of(uint32_t mode) { return StageBForm(mode & 7u); }
 MJX_HD constexpr StageBSink sink_of(uint32_t mode) { return StageBSink(mode >> 3); }
@@ -220,8 +228,13 @@ enum StageBDensity : uint32_t { kAnyDensity = 0, kSparse = 1, kDense = 2 };
     MJX_STAGE_B_SOURCES(X, kFormGeneric, kSinkLuma) MJX_STAGE_B_SOURCES(X, kForm420, kSinkLuma)                                      \
     MJX_STAGE_B_SOURCES(X, kFormHalf, kSinkLuma) MJX_STAGE_B_SOURCES(X, kFormQuarter, kSinkLuma)                                     \
     MJX_STAGE_B_SOURCES(X, kFormGeneric, kSinkYcc) MJX_STAGE_B_SOURCES(X, kFormHalf, kSinkYcc) MJX_STAGE_B_SOURCES(X, kFormQuarter, kSinkYcc)
+// The forms of the integer inverse DCT (MJX_IDCT_ISLOW): a list of their own behind the one above, which stays what it was -- the
+// modes stage_b_choice gave before the option existed.  MJX_STAGE_B_ALL is what configure_kernels and launch_idct_color are generated from.
+#define MJX_STAGE_B_KERNELS_ISLOW(X) MJX_STAGE_B_SOURCES(X, kFormGeneric, kSinkPlanesInt)
+#define MJX_STAGE_B_ALL(X) MJX_STAGE_B_KERNELS(X) MJX_STAGE_B_KERNELS_ISLOW(X)
 #define MJX_STAGE_B_COUNT(F, S, PF, SRC, LAYOUT, DENSITY) +1
 static_assert(0 MJX_STAGE_B_KERNELS(MJX_STAGE_B_COUNT) == 64, "16 packed kernels + 48 of the other sinks (DESIGN.md s3.2)");
+static_assert(0 MJX_STAGE_B_KERNELS_ISLOW(MJX_STAGE_B_COUNT) == 3, "the integer inverse DCT: the generic form on the three stream sources");
 #undef MJX_STAGE_B_COUNT
 
 // DevImage::or_on: the pass behind stage B that brings an oriented (or resized, one-channel) picture to the form it leaves in
@@ -348,8 +361,9 @@ MJX_HD uint32_t plane_pass_jobs(uint32_t ncomp, uint32_t il) { return ncomp == 1
 // A component plane: cw x ch samples in rows of `stride` bytes; s and stride are multiples of 8 and stride >= cw rounded up to 8, so
 // that the aligned 4- and 8-byte reads below stay inside a row (what they bring in from behind cw is never used: indices clamp to
 // the plane's edge).  rh, rv: the upsampling ratios, 1, 2 or 4.  k_upsample_color and the host (mjx_upsample_color_host) run these
-// routines; a lane makes 8 adjacent pixels of one output row.
-struct LjPlane { const uint8_t *s; uint32_t stride, cw, ch, rh, rv; };
+// routines; a lane makes 8 adjacent pixels of one output row.  rep: the component is replicated whatever its ratios (MJX_IDCT_ISLOW's
+// planes of at most two columns; k_upsample_rep and the host set it, the other kernels leave it 0).
+struct LjPlane { const uint8_t *s; uint32_t stride, cw, ch, rh, rv; uint32_t rep = 0; };
 constexpr uint32_t kLjStrip = 8;                               // pixels a lane makes
 constexpr uint32_t kLjTileW = 64 * kLjStrip, kLjTileH = 16;    // the tile of a workgroup of k_upsample_color: a wave per row, four rows each
 MJX_HD uint32_t lj_tiles(uint32_t x, uint32_t w, uint32_t h)   // strips start on multiples of kLjStrip of the PICTURE (aligned plane reads)
@@ -391,9 +405,10 @@ MJX_UNROLL
 //   out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4 -- jdsample.c's h2v1 / h2v2 fancy upsampling with edge replication.
 // A component with a ratio of 4 in EITHER direction is replicated in both -- out[k] = s[(X0 + k) / rh] of row Y / rv, jdsample.c's
 // int_upsample, which libjpeg picks for every ratio pair that is not one of the four above; there is no triangle filter at ratio 4.
+// So is a component with p.rep set (MJX_IDCT_ISLOW: jdsample.c takes its triangle filters only for planes of more than two columns).
 MJX_HD void lj_strip8(const LjPlane &p, uint32_t X0, uint32_t Y, int32_t out[8])
 {
-    if (p.rh == 4u || p.rv == 4u) {
+    if (p.rh == 4u || p.rv == 4u || p.rep) {
         const uint8_t *row = p.s + size_t(Y >> ratio_shift(p.rv, 1u)) * p.stride;
         if (p.rh == 1u) {
             lj_row8(row, X0, out);
@@ -490,6 +505,88 @@ MJX_HD void lj_luma8(const LjPlane &p, uint32_t X0, uint32_t Y, uint32_t w[2])
     w[0] = w[1] = 0;
 MJX_UNROLL
     for (uint32_t k = 0; k < 8; k++) w[k >> 2] = lj_put_u8(float(y[k]), k & 3u, w[k >> 2]);
+}
+
+// ---- libjpeg's integer slow inverse DCT (MJX_OPTS_IDCT = MJX_IDCT_ISLOW; include/mjx.h states the contract) ---------------------
+// jidctint.c's jpeg_idct_islow on uint32_t, so that the wrap-around the contract asks for is defined behaviour on the host too; only
+// the descaling shift works on the value cast back to int32_t (arithmetic).  FIX(x) = int(x 8192 + 0.5).
+constexpr uint32_t kIslowBits = 13, kIslowPass1 = 2;       // CONST_BITS, PASS1_BITS: pass 1 descales by 11, pass 2 by 18
+MJX_HD uint32_t islow_descale(uint32_t x, uint32_t n) { return uint32_t(int32_t(x + (1u << (n - 1u))) >> n); }
+// P of the contract on d[0 .. 7], in place, descaled by n
+MJX_HD void islow_pass(uint32_t d[8], uint32_t n)
+{
+    constexpr uint32_t F0_298 = 2446u, F0_390 = 3196u, F0_541 = 4433u, F0_765 = 6270u, F0_899 = 7373u, F1_175 = 9633u, F1_501 = 12299u,
+                       F1_847 = 15137u, F1_961 = 16069u, F2_053 = 16819u, F2_562 = 20995u, F3_072 = 25172u;
+    uint32_t z1 = (d[2] + d[6]) * F0_541;
+    const uint32_t t2 = z1 - d[6] * F1_847, t3 = z1 + d[2] * F0_765;
+    const uint32_t t0 = (d[0] + d[4]) << kIslowBits, t1 = (d[0] - d[4]) << kIslowBits;
+    const uint32_t t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    uint32_t a = d[7], b = d[5], c = d[3], e = d[1];
+    z1 = a + e;
+    uint32_t z2 = b + c, z3 = a + c, z4 = b + e;
+    const uint32_t z5 = (z3 + z4) * F1_175;
+    a *= F0_298; b *= F2_053; c *= F3_072; e *= F1_501;
+    z1 *= 0u - F0_899; z2 *= 0u - F2_562;
+    z3 = z3 * (0u - F1_961) + z5;
+    z4 = z4 * (0u - F0_390) + z5;
+    a += z1 + z3; b += z2 + z4; c += z2 + z3; e += z1 + z4;
+    d[0] = islow_descale(t10 + e, n); d[7] = islow_descale(t10 - e, n);
+    d[1] = islow_descale(t11 + c, n); d[6] = islow_descale(t11 - c, n);
+    d[2] = islow_descale(t12 + b, n); d[5] = islow_descale(t12 - b, n);
+    d[3] = islow_descale(t13 + a, n); d[4] = islow_descale(t13 - a, n);
+}
+// four adjacent words of a block: one 16-byte access on the device (blk is 16-byte aligned there: a tile row of kPixStride words)
+struct IslowQuad { uint32_t x, y, z, w; };
+MJX_HD IslowQuad islow_ld4(const uint32_t *p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint4 v = *reinterpret_cast<const uint4 *>(p);
+    return IslowQuad{v.x, v.y, v.z, v.w};
+#else
+    return IslowQuad{p[0], p[1], p[2], p[3]};
+#endif
+}
+MJX_HD void islow_st4(uint32_t *p, uint32_t x, uint32_t y, uint32_t z, uint32_t w)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    *reinterpret_cast<uint4 *>(p) = make_uint4(x, y, z, w);
+#else
+    p[0] = x; p[1] = y; p[2] = z; p[3] = w;
+#endif
+}
+// One lane = one block: blk[v * 8 + u] = coef[v][u] q[v][u] on entry, pass 2's output x on exit (the sample is islow_sample(x)).  In
+// place, 16 bytes per access: a lane's blocks lie kPixStride = 17 x 16 bytes apart in the tile, an odd number of 16-byte units, so a
+// wave's quads fall on different banks.  The column pass takes four columns at a time (eight quads in, 32 values in registers, eight
+// quads out), the row pass one row (two quads).  libjpeg's shortcuts for all-zero AC columns give the same numbers and are left out.
+MJX_HD void idct_islow_inplace(uint32_t *blk)
+{
+MJX_UNROLL
+    for (uint32_t h = 0; h < 2u; h++) {                        // pass 1: columns 4 h .. 4 h + 3
+        uint32_t c[4][8];
+MJX_UNROLL
+        for (uint32_t v = 0; v < 8u; v++) {
+            const IslowQuad t = islow_ld4(blk + v * 8u + h * 4u);
+            c[0][v] = t.x; c[1][v] = t.y; c[2][v] = t.z; c[3][v] = t.w;
+        }
+MJX_UNROLL
+        for (uint32_t k = 0; k < 4u; k++) islow_pass(c[k], kIslowBits - kIslowPass1);
+MJX_UNROLL
+        for (uint32_t v = 0; v < 8u; v++) islow_st4(blk + v * 8u + h * 4u, c[0][v], c[1][v], c[2][v], c[3][v]);
+    }
+MJX_UNROLL
+    for (uint32_t v = 0; v < 8u; v++) {                        // pass 2: row v
+        const IslowQuad lo = islow_ld4(blk + v * 8u), hi = islow_ld4(blk + v * 8u + 4u);
+        uint32_t r[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        islow_pass(r, kIslowBits + kIslowPass1 + 3u);
+        islow_st4(blk + v * 8u, r[0], r[1], r[2], r[3]);
+        islow_st4(blk + v * 8u + 4u, r[4], r[5], r[6], r[7]);
+    }
+}
+// the sample of pass 2's output x: clamp(x + 128, 0, 255) -- it saturates (|x| < 2^14 after the shift by 18: the sum cannot wrap)
+MJX_HD uint32_t islow_sample(uint32_t x)
+{
+    const int32_t s = int32_t(x) + 128;
+    return uint32_t(s < 0 ? 0 : s > 255 ? 255 : s);
 }
 
 // ---- resize on the device (mjx_resize): the separable triangle filter, one axis -----------------------------------------------
@@ -1074,6 +1171,9 @@ void launch_resize_planes(hipStream_t st, uint32_t max_tiles, uint32_t nimg, con
 // libjpeg's pixels, behind stage B: one workgroup per tile of the rectangle (lj_tiles) and picture with DevImage::lj_on
 void launch_upsample_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
                            const uint32_t *img_flags, bool luma = false /* k_upsample_luma: pictures with DevImage::lj_luma */);
+// ... k_upsample_rep: pictures with DevImage::lj_rep (the integer inverse DCT's planes of at most two columns, replicated)
+void launch_upsample_rep(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
+                         const uint32_t *img_flags);
 #endif
 
 }   // namespace mjx

@@ -3238,20 +3238,21 @@ __device__ __forceinline__ uint32_t comp_of_block(uint32_t b, const uint8_t *s_c
     return s_comp[b];
 }
 
-template <int MODE, int N, bool LUMA = false>
+template <int MODE, int N, bool LUMA = false, bool INT = false>
 __device__ __forceinline__ void scatter_at(const uint32_t *ent, const uint32_t *b, uint32_t nblk, float *tile_f,
                                            const float *s_qm, const uint8_t *s_nat, const uint8_t *s_comp);
-template <int MODE, int N, bool LUMA = false>
+template <int MODE, int N, bool LUMA = false, bool INT = false>
 __device__ __forceinline__ void scatter_batch(const uint32_t *ent, uint32_t first_lo, uint32_t nblk, float *tile_f,
                                               const float *s_qm, const uint8_t *s_nat, const uint8_t *s_comp)
 {
     uint32_t b[N];
 #pragma unroll
     for (int k = 0; k < N; k++) b[k] = ((ent[k] >> 22) - first_lo) & 0xffu;
-    scatter_at<MODE, N, LUMA>(ent, b, nblk, tile_f, s_qm, s_nat, s_comp);
+    scatter_at<MODE, N, LUMA, INT>(ent, b, nblk, tile_f, s_qm, s_nat, s_comp);
 }
-// (b[k]: the block slot of entry k in the tile; anything >= nblk is dropped.  LUMA: so is an entry of a block that is not component 0's)
-template <int MODE, int N, bool LUMA>
+// (b[k]: the block slot of entry k in the tile; anything >= nblk is dropped.  LUMA: so is an entry of a block that is not component 0's.
+// INT, the integer inverse DCT's tile: s_qm holds the raw DQT entries as uint32 and the word stored is coefficient x entry, wrapping)
+template <int MODE, int N, bool LUMA, bool INT>
 __device__ __forceinline__ void scatter_at(const uint32_t *ent, const uint32_t *b, uint32_t nblk, float *tile_f,
                                            const float *s_qm, const uint8_t *s_nat, const uint8_t *s_comp)
 {
@@ -3277,7 +3278,8 @@ __device__ __forceinline__ void scatter_at(const uint32_t *ent, const uint32_t *
 #if defined(MJX_EXP_NO_SCATTER_STORE)  // (measurement build, garbage out: the scatter phase without its LDS stores)
         asm volatile("" :: "v"(at), "v"(float(int32_t(int16_t(ent[k] & 0xffffu))) * qm[k]));
 #else
-        *reinterpret_cast<float *>(base + at) = float(int32_t(int16_t(ent[k] & 0xffffu))) * qm[k];
+        if constexpr (INT) *reinterpret_cast<uint32_t *>(base + at) = uint32_t(int32_t(int16_t(ent[k] & 0xffffu))) * __float_as_uint(qm[k]);
+        else *reinterpret_cast<float *>(base + at) = float(int32_t(int16_t(ent[k] & 0xffffu))) * qm[k];
 #endif
     }
 }
@@ -3425,14 +3427,14 @@ __device__ __forceinline__ uint32_t planar_block(uint32_t e, uint32_t how, uint3
     const uint32_t l = how >> 24, fm = jb >> l;                   // its MCU of the picture, counted from the piece's first
     return min(((how >> 8) & 0xffu) + ((how >> 16) & 0xffu) + fm * bpm + (jb - (fm << l)), 255u);
 }
-template <int MODE, int N, bool LUMA = false>
+template <int MODE, int N, bool LUMA = false, bool INT = false>
 __device__ __forceinline__ void scatter_planar(const uint32_t *ent, const PlanarTile &t, uint32_t bpm, uint32_t nblk, float *tile_f,
                                                const float *s_qm, const uint8_t *s_nat, const uint8_t *s_comp)
 {
     uint32_t bs[N];
 #pragma unroll
     for (int k = 0; k < N; k++) bs[k] = planar_block(ent[k], __builtin_amdgcn_readfirstlane(t.rnd[k].how), bpm);
-    scatter_at<MODE, N, LUMA>(ent, bs, nblk, tile_f, s_qm, s_nat, s_comp);
+    scatter_at<MODE, N, LUMA, INT>(ent, bs, nblk, tile_f, s_qm, s_nat, s_comp);
 }
 
 // One lane = one 8x8 block: 16 x ds_read_b128 of its row, 8 row + 8 column transforms in registers, back to the row.
@@ -3848,6 +3850,8 @@ __device__ __forceinline__ void pixels_generic(const GenShape &g, const float *t
 // bytes clamp(floor(f + 128.5), 0, 255) -- the 128.5 sits on the DC term, pack_u8 floors and saturates --, a lane per row of a
 // block (eight samples, one 8-byte store), into the picture's planes.  These span the whole MCU grid, so nothing is clipped here:
 // k_upsample_color reads only what lies inside the components' true sizes.
+// INT (kSinkPlanesInt, the integer inverse DCT): the tile holds pass 2's int32 outputs, the byte is islow_sample's clamp(x + 128, 0, 255).
+template <bool INT = false>
 __device__ __forceinline__ void planes_store(const DevImage &im, const float *tile, uint32_t m0, uint32_t nblk, uint32_t bpm, uint32_t mcux,
                                              uint8_t *pl)
 {
@@ -3866,11 +3870,18 @@ __device__ __forceinline__ void planes_store(const DevImage &im, const float *ti
         }
         const uint32_t c = im.blk_comp[b];
         const uint32_t bx = mx * im.ch[c] + im.blk_bx[b], by = my * im.cv[c] + im.blk_by[b];
-        const float4 lo = *reinterpret_cast<const float4 *>(tile + blk * kPixStride + r * 8);
-        const float4 hi = *reinterpret_cast<const float4 *>(tile + blk * kPixStride + r * 8 + 4);
         uint2 w;
-        w.x = pack_u8(lo.w, 3, pack_u8(lo.z, 2, pack_u8(lo.y, 1, pack_u8(lo.x, 0, 0u))));
-        w.y = pack_u8(hi.w, 3, pack_u8(hi.z, 2, pack_u8(hi.y, 1, pack_u8(hi.x, 0, 0u))));
+        if constexpr (INT) {
+            const uint4 lo = *reinterpret_cast<const uint4 *>(tile + blk * kPixStride + r * 8);
+            const uint4 hi = *reinterpret_cast<const uint4 *>(tile + blk * kPixStride + r * 8 + 4);
+            w.x = islow_sample(lo.x) | islow_sample(lo.y) << 8 | islow_sample(lo.z) << 16 | islow_sample(lo.w) << 24;
+            w.y = islow_sample(hi.x) | islow_sample(hi.y) << 8 | islow_sample(hi.z) << 16 | islow_sample(hi.w) << 24;
+        } else {
+            const float4 lo = *reinterpret_cast<const float4 *>(tile + blk * kPixStride + r * 8);
+            const float4 hi = *reinterpret_cast<const float4 *>(tile + blk * kPixStride + r * 8 + 4);
+            w.x = pack_u8(lo.w, 3, pack_u8(lo.z, 2, pack_u8(lo.y, 1, pack_u8(lo.x, 0, 0u))));
+            w.y = pack_u8(hi.w, 3, pack_u8(hi.z, 2, pack_u8(hi.y, 1, pack_u8(hi.x, 0, 0u))));
+        }
         *reinterpret_cast<uint2 *>(pl + im.lj_off[c] + (size_t(by) * 8u + r) * im.lj_stride[c] + bx * 8u) = w;
     }
 }
@@ -4289,6 +4300,9 @@ __device__ __forceinline__ void pixels_scaled_luma(const GenShape &g, const floa
 //   PLANES  libjpeg's pixels (kSinkPlanes, kFormGeneric for every sampling layout): the ROI form over the tiles of the rectangle grown by the
 //        upsampling filter's reach (the planner's roi_m*), phase 3 storing every component's rounded samples as bytes (planes_store);
 //        k_upsample_color makes the picture
+//   PLANESI  ... with libjpeg's integer slow inverse DCT (kSinkPlanesInt, MJX_IDCT_ISLOW): PLANES with the tile held as int32 at the same
+//        stride -- phase 1 scatters coefficient x raw DQT entry in natural order (the scatter routines' INT flag), the DC term is dc x
+//        entry with no level shift, phase 2 is idct_islow_inplace (mjx_kernels.h, the routine the host runs), phase 3 planes_store<true>
 //   OUT  output formats (kSinkOut, the sink of a picture with an output description): the ROI form -- a picture without a
 //        rectangle is its own whole rectangle --, phase 3 writing the picture's format (store4_out, DevImage::out_*)
 //   YCC  YCbCr output (kSinkYcc, MODE 0, 3, 4; mjx_planes): the ROI form with one difference in phases 1-2 -- every
@@ -4312,10 +4326,11 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     constexpr bool YCC = SINK == kSinkYcc;                    // YCbCr output: the cropped form, phase 3 storing the component planes as the picture
     constexpr bool LUMA = SINK == kSinkLuma;                  // luminance output: the cropped form, component 0 alone
     constexpr bool PLANES = SINK == kSinkPlanes;              // libjpeg's pixels: the cropped form again, phase 3 storing component planes
+    constexpr bool PLANESI = SINK == kSinkPlanesInt;          // ... with libjpeg's integer inverse DCT: the tile holds int32, phases 1-3 in integers
     constexpr bool OUT = SINK == kSinkOut;                    // output formats: the cropped form, the picture its own whole rectangle without one
     constexpr bool ROI = SINK != kSinkPacked;                 // every sink but the packed whole picture walks and writes a rectangle
-    static_assert(uint32_t(MODE_) == stage_b_mode(MODE, SINK) && SINK < kStageBSinks && MODE <= int(kFormQuarter), "a mode of MJX_STAGE_B_KERNELS");
-    static_assert(!PLANES || MODE == int(kFormGeneric), "the planes are written by the generic form");
+    static_assert(uint32_t(MODE_) == stage_b_mode(MODE, SINK) && SINK < kStageBSinks && MODE <= int(kFormQuarter), "a mode of MJX_STAGE_B_ALL");
+    static_assert(!(PLANES || PLANESI) || MODE == int(kFormGeneric), "the planes are written by the generic form");
     static_assert(!YCC || MODE == int(kFormGeneric) || MODE == int(kFormHalf) || MODE == int(kFormQuarter), "component planes: the generic form and its scaled siblings");
     static_assert(!ROI || MODE != int(kFormRefCompat), "REF_COMPAT has no rectangles");
     // (its own symbol: dynamic LDS arrays of one name share their alignment, and the entropy kernels ask for 2 KiB)
@@ -4445,6 +4460,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
         if constexpr (SCALED) s_nat[tid] = uint8_t(scaled_slot(ZZ[tid], scaled_n<MODE>()));
+        else if constexpr (PLANESI) s_nat[tid] = ZZ[tid];   // (the integer transform works on the block in natural order)
         else s_nat[tid] = uint8_t(idct_slot(ZZ[tid]));      // zig-zag position -> where the inverse DCT expects the coefficient
     }
     if (!M420 && tid < tile_blocks) s_comp[tid] = im.blk_comp[tid % bpm];
@@ -4460,6 +4476,10 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     }
     if constexpr (PLANES) my_dc_add = 128.5f;         // (every component's level shift and the rounding: the store truncates, planes_store)
     if constexpr (YCC) my_dc_add = im.ycc_round ? 128.5f : 128.0f;      // (every component's level shift; libjpeg's pixels: and the rounding)
+    // (the integer transform: the pool holds the raw DQT entries as uint32 at qm_off -- the copy into s_qm above moves their bits --,
+    // and the DC term is dc x entry alone: the level shift is islow_sample's)
+    uint32_t my_dc_qi = 0u;
+    if constexpr (PLANESI) my_dc_qi = reinterpret_cast<const uint32_t *>(qmult)[im.qm_off + my_comp * 64];
     float *tile_f = reinterpret_cast<float *>(smem_px);
     GenShape gshape{};
     if (MODE == 0 || SCALED) gshape = gen_shape(im);
@@ -4471,6 +4491,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     // a vmcnt(0) that also drains the pixel stores of the tile before: the wait-count pass merges the loop's entry state into its
     // back edge.  Round 6: found in the ISA; it was a store drain per tile and wave right behind the pixel phase.)
     asm volatile("" : "+v"(my_dc_qm), "+v"(my_dc_add));
+    if constexpr (PLANESI) asm volatile("" : "+v"(my_dc_qi));
     if (!M420) asm volatile("" :: "v"(gshape.width));
 
 #ifdef MJX_STAMP_B
@@ -4528,9 +4549,9 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             if constexpr (PLANAR) {
                 // as many rounds as the tile has -- a uniform choice between a few batch sizes, as for the linear stream below
                 const PlanarTile &pt = s_ptile[tile % 3u];
-                if (__builtin_amdgcn_readfirstlane(pt.rnd[4].cnt) == 0) scatter_planar<MODE, 4, LUMA>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
-                else if (__builtin_amdgcn_readfirstlane(pt.rnd[6].cnt) == 0) scatter_planar<MODE, 6, LUMA>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
-                else scatter_planar<MODE, 8, LUMA>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
+                if (__builtin_amdgcn_readfirstlane(pt.rnd[4].cnt) == 0) scatter_planar<MODE, 4, LUMA, PLANESI>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
+                else if (__builtin_amdgcn_readfirstlane(pt.rnd[6].cnt) == 0) scatter_planar<MODE, 6, LUMA, PLANESI>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
+                else scatter_planar<MODE, 8, LUMA, PLANESI>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
                 // what the tile has beyond the prefetched rounds (dense streams)
                 for (uint32_t j = pt.rest_seg, r0 = pt.rest_rnd; j < kPlanarSegs; j++, r0 = 0) {
                     const uint32_t rel = s_kind[j >= nk ? j - nk : j].ent_rel + pt.start[j], len = pt.len[j], how = pt.how[j];
@@ -4538,7 +4559,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                         uint32_t e1[1], b1[1];
                         e1[0] = i0 + tid < len ? psrc[rel + i0 + tid] : 0u;
                         b1[0] = planar_block(e1[0], how, bpm);
-                        scatter_at<MODE, 1, LUMA>(e1, b1, nblk, tile_f, s_qm, s_nat, s_comp);
+                        scatter_at<MODE, 1, LUMA, PLANESI>(e1, b1, nblk, tile_f, s_qm, s_nat, s_comp);
                     }
                 }
             } else if constexpr (QUAD) {
@@ -4548,14 +4569,14 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                     if (cur.ncells > wave0 + LANES * r) {                                    // uniform over the wave
                         quad_mask(cur.ent[r], cur.k_lo[r], cur.k_hi[r]);
                         // (the labels of the group's entries + its subsequence's label offset = the blocks' indices in the picture, mod 256)
-                        scatter_batch<MODE, 8, LUMA>(cur.ent[r], first_lo - cur.lab[r], nblk, tile_f, s_qm, s_nat, s_comp);
+                        scatter_batch<MODE, 8, LUMA, PLANESI>(cur.ent[r], first_lo - cur.lab[r], nblk, tile_f, s_qm, s_nat, s_comp);
                     }
                 }
                 for (uint32_t h0 = LANES * QR; h0 < cur.ncells; h0 += LANES) {
                     uint32_t more[8], k_lo, k_hi, lab;
                     quad_load(src, qv, tile - tile0, h0 + tid, more, k_lo, k_hi, lab);
                     quad_mask(more, k_lo, k_hi);
-                    scatter_batch<MODE, 8, LUMA>(more, first_lo - lab, nblk, tile_f, s_qm, s_nat, s_comp);
+                    scatter_batch<MODE, 8, LUMA, PLANESI>(more, first_lo - lab, nblk, tile_f, s_qm, s_nat, s_comp);
                 }
             } else {
                 // The prefetched words the wave really has (a tile of the bench content holds ~1500 entries, 5.9 per lane; at quality
@@ -4564,10 +4585,10 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                 // fetched as 0: null entries.)
                 const uint32_t have = cur.e1 - cur.e0;
                 const uint32_t slots = have > wave0 ? (have - wave0 + LANES - 1) / LANES : 0u;      // uniform over the wave
-                if (slots <= 4) scatter_batch<MODE, 4, LUMA>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
-                else if (slots <= 6) scatter_batch<MODE, 6, LUMA>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
-                else if (slots <= 8 || PF == 8) scatter_batch<MODE, 8, LUMA>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
-                else if (PF > 8) scatter_batch<MODE, PF, LUMA>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                if (slots <= 4) scatter_batch<MODE, 4, LUMA, PLANESI>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                else if (slots <= 6) scatter_batch<MODE, 6, LUMA, PLANESI>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                else if (slots <= 8 || PF == 8) scatter_batch<MODE, 8, LUMA, PLANESI>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                else if (PF > 8) scatter_batch<MODE, PF, LUMA, PLANESI>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
                 for (uint32_t i0 = cur.e0 + LANES * PF; i0 < cur.e1; i0 += LANES * 4) {     // what a dense tile has beyond the prefetched words
                     uint32_t more[4];
 #pragma unroll
@@ -4575,14 +4596,16 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                         const uint32_t i = i0 + tid + LANES * k;
                         more[k] = i < cur.e1 ? src[i] : 0u;
                     }
-                    scatter_batch<MODE, 4, LUMA>(more, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                    scatter_batch<MODE, 4, LUMA, PLANESI>(more, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
                 }
             }
             // DC; luminance blocks also take the + 128 of decoder.rs:318-330 here (a constant on the DC term of the
             // prescaled transform is the same constant on all 64 samples); REF_COMPAT adds it per pixel in k_ref_color,
             // where samples no block covers must come out as 0 + 128
             MJX_SB(1);
-            if (tid < nblk && (!LUMA || my_comp == 0u)) tile_f[tid * kPixStride] = float(cur.dc) * my_dc_qm + my_dc_add;
+            if constexpr (PLANESI) {
+                if (tid < nblk) reinterpret_cast<uint32_t *>(tile_f)[tid * kPixStride] = uint32_t(cur.dc) * my_dc_qi;
+            } else if (tid < nblk && (!LUMA || my_comp == 0u)) tile_f[tid * kPixStride] = float(cur.dc) * my_dc_qm + my_dc_add;
         }
         if constexpr (PLANAR) {
             if (tile + 1 < tile1) tile_fetch_planar<LANES, PF>(psrc, s_ptile[(tile + 1) % 3u], dcbuf, pdc, (tile + 1) * T, pr1, pa1, nmcu, mcux, nxt);
@@ -4592,6 +4615,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
         MJX_SB(3);
         if constexpr (SCALED) {
             if (tid < nblk && (!LUMA || my_comp == 0u)) idct_scaled_inplace<scaled_n<MODE>()>(tile_f + tid * kPixStride);
+        } else if constexpr (PLANESI) {
+            if (tid < nblk) idct_islow_inplace(reinterpret_cast<uint32_t *>(tile_f) + tid * kPixStride);
         } else if (tid < nblk && (!LUMA || my_comp == 0u)) idct_row_inplace(tile_f + tid * kPixStride);
         MJX_SB(4);
         __syncthreads();
@@ -4636,6 +4661,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             if constexpr (YCC) planes_out_store<8u>(ycc_pl, gshape.ncomp, log2T, tile_f, m0, nm, bpm, mcux);
             else if constexpr (LUMA) pixels_generic_luma(gshape, tile_f, m0, nm, roi, ofmt);
             else if constexpr (PLANES) planes_store(im, tile_f, m0, nblk, bpm, mcux, reinterpret_cast<uint8_t *>(planes + im.plane_off));
+            else if constexpr (PLANESI) planes_store<true>(im, tile_f, m0, nblk, bpm, mcux, reinterpret_cast<uint8_t *>(planes + im.plane_off));
             else if constexpr (OUT) pixels_generic_out(gshape, tile_f, m0, nm, roi, ofmt);
             else if constexpr (ROI) pixels_generic_roi(gshape, tile_f, m0, nm, out_img, aligned, roi);
             else pixels_generic(gshape, tile_f, m0, nm, out_img, aligned);
@@ -5443,6 +5469,54 @@ __global__ __launch_bounds__(256) void k_upsample_luma(const DevImage *__restric
     }
 }
 
+// ... a picture of the integer inverse DCT with a component that jdsample.c replicates, a plane of at most two columns (DevImage::lj_rep;
+// such a picture is at most four pixels wide): the two kernels above in one, LjPlane::rep set per component -- lj_strip8's replication
+// path, the one a ratio of 4 takes.  A colour picture leaves through store4_roi / store4_out, a luminance picture through store4_luma.
+__global__ __launch_bounds__(256) void k_upsample_rep(const DevImage *__restrict__ images, const uint8_t *__restrict__ planes,
+                                                       uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    if (!im.valid || !im.lj_rep || im.role == 1u || img_flags[im.status_idx]) return;
+    const Roi roi{im.roi_x, im.roi_y, im.roi_w, im.roi_h};
+    const uint32_t xb = roi.x & ~(kLjStrip - 1u), tiles_x = (roi.x - xb + roi.w + kLjTileW - 1u) / kLjTileW;
+    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    if (ty * kLjTileH >= roi.h) return;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t px = xb + tx * kLjTileW + (tid & 63u) * kLjStrip;
+    if (px >= roi.x + roi.w) return;
+    const uint32_t width = im.width, height = im.height, ncomp = im.ncomp, hmax = im.hmax, vmax = im.vmax, rep = im.lj_rep;
+    const uint8_t *base = planes + im.plane_off * 8u;
+    LjPlane pl[3];
+#pragma unroll
+    for (uint32_t c = 0; c < 3; c++) {
+        const uint32_t k = c < ncomp ? c : 0u;
+        pl[c] = LjPlane{base + im.lj_off[k], im.lj_stride[k], (width * im.ch[k] + hmax - 1u) / hmax, (height * im.cv[k] + vmax - 1u) / vmax,
+                        hmax / im.ch[k], vmax / im.cv[k], rep >> k & 1u};
+    }
+    const bool luma = (rep & kLjRepLuma) != 0u, fmt = im.lj_out != 0u;
+    OutFmt of{};
+    if (luma) of = luma_fmt(im, rgb);
+    else if (fmt) of = out_fmt(im, rgb);
+    uint8_t *out_img = rgb + im.rgb_off;
+    uint32_t w[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll 1
+    for (uint32_t it = 0; it < 2u * (kLjTileH / 4u); it++) {
+        const uint32_t py = roi.y + ty * kLjTileH + (tid >> 6) + 4u * (it >> 1), half = it & 1u;
+        if (py >= roi.y + roi.h) break;
+        if (!half) {
+            if (luma) lj_luma8(pl[0], px, py, w);
+            else lj_pixels8(pl, ncomp, px, py, w);
+        }
+        const uint32_t x4 = px + 4u * half;
+        if (x4 >= width) continue;
+        const uint32_t npix = min(4u, width - x4);
+        if (luma) { store4_luma(of, roi, x4, py, half ? w[1] : w[0], npix); continue; }
+        const Rgb4 v = half ? Rgb4{w[3], w[4], w[5]} : Rgb4{w[0], w[1], w[2]};
+        if (fmt) store4_out(of, roi, x4, py, v, npix);
+        else store4_roi(out_img, roi, x4, py, v, npix);
+    }
+}
+
 // ---- verification helper: byte-wise comparison of decoded pictures on the device ------------------------------
 // (mjx_batch_compare_rgb: the parity gate of bench.py and the batch-scale tests compare tens of gigabytes of output
 // without copying them to the host.)  One workgroup per 16 KiB of a pair; per pair the largest absolute byte
@@ -5519,7 +5593,7 @@ int configure_kernels(size_t huff_lds, size_t idct_lds)
     }
     if (e == hipSuccess && idct_lds > 64 * 1024) {
 #define MJX_STAGE_B_FN(F, S, PF, SRC, LAYOUT, DENSITY) reinterpret_cast<const void *>(k_idct_color<stage_b_mode(F, S), PF, SRC>),
-        const void *fns[] = {MJX_STAGE_B_KERNELS(MJX_STAGE_B_FN)};
+        const void *fns[] = {MJX_STAGE_B_ALL(MJX_STAGE_B_FN)};
 #undef MJX_STAGE_B_FN
         for (const void *f : fns)
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(idct_lds));
@@ -5692,7 +5766,7 @@ void launch_idct_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, size_t
     if ((mode_mask >> stage_b_mode(F, S) & 1u) && (layout_mask & LAYOUT) && (DENSITY == kAnyDensity || DENSITY == density))                   \
         hipLaunchKernelGGL((k_idct_color<stage_b_mode(F, S), PF, SRC>), dim3(gx, nimg), dim3(F == kForm420 ? kLanes420 : 256u), lds, st,     \
                            images, entries, tile_eoff, dcbuf, qmult, rgb, planes, img_flags, tpw);
-    MJX_STAGE_B_KERNELS(MJX_STAGE_B_LAUNCH)
+    MJX_STAGE_B_ALL(MJX_STAGE_B_LAUNCH)
 #undef MJX_STAGE_B_LAUNCH
 }
 
@@ -5780,6 +5854,12 @@ void launch_upsample_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, co
     if (max_tiles == 0 || nimg == 0) return;
     if (luma) hipLaunchKernelGGL(k_upsample_luma, dim3(max_tiles, nimg), dim3(256), 0, st, images, planes, rgb, img_flags);
     else hipLaunchKernelGGL(k_upsample_color, dim3(max_tiles, nimg), dim3(256), 0, st, images, planes, rgb, img_flags);
+}
+void launch_upsample_rep(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
+                         const uint32_t *img_flags)
+{
+    if (max_tiles == 0 || nimg == 0) return;
+    hipLaunchKernelGGL(k_upsample_rep, dim3(max_tiles, nimg), dim3(256), 0, st, images, planes, rgb, img_flags);
 }
 
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,

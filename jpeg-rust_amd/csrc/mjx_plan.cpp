@@ -297,6 +297,10 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     if (opts.pixels > MJX_PIXELS_LIBJPEG) return fail(MJX_ERR_INVALID_ARG);
     const bool lj = opts.pixels == MJX_PIXELS_LIBJPEG && !scan_part;
     if (lj && (scale != 1 || opts.layout == MJX_LAYOUT_REF_COMPAT || opts.strict_ref)) return fail(MJX_ERR_INVALID_ARG);
+    // libjpeg's integer inverse DCT: with its pixels only
+    if (MJX_OPTS_IDCT(&opts) > MJX_IDCT_ISLOW) return fail(MJX_ERR_INVALID_ARG);
+    if (MJX_OPTS_IDCT(&opts) == MJX_IDCT_ISLOW && opts.pixels != MJX_PIXELS_LIBJPEG) return fail(MJX_ERR_INVALID_ARG);
+    const bool islow = lj && MJX_OPTS_IDCT(&opts) == MJX_IDCT_ISLOW;
     // the file's own colour model: STANDARD layout without strict_ref only (the reference has one rule)
     if (MJX_OPTS_COLOR(&opts) > MJX_COLOR_FILE) return fail(MJX_ERR_INVALID_ARG);
     const bool color_file = MJX_OPTS_COLOR(&opts) == MJX_COLOR_FILE;
@@ -400,6 +404,12 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
         p.roi_mc0 = x0 / pw; p.roi_mc1 = x1 / pw;
         p.roi_mr0 = y0 / ph; p.roi_mr1 = y1 / ph;
         p.lj = lj;
+        p.islow = islow;
+        // (jdsample.c takes its triangle filters for downsampled_width > 2 only: a narrower plane of ratios (2, 1) or (2, 2) is replicated)
+        for (uint32_t c = 0; islow && c < p.ncomp; c++) {
+            const uint32_t cw = (p.width * p.h[c] + p.hmax - 1) / p.hmax, rh = p.hmax / p.h[c], rv = p.vmax / p.v[c];
+            if (cw <= 2 && rh == 2 && (rv == 1 || rv == 2)) p.lj_rep |= 1u << c;
+        }
     }
     if (p.layout == MJX_LAYOUT_REF_COMPAT) {
         const uint64_t nb = uint64_t((p.width + 7) / 8) * ((p.height + 7) / 8);    // decoder.rs:164-166
@@ -583,6 +593,7 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
         for (int k = 0; k < 64; k++) {
             const int nat = kZigZag[k];
             p.qmult[c][k] = float(double(d.qt[p.tq[c]][k]) * aan[nat >> 3] * aan[nat & 7] / 8.0);
+            p.qint[c][k] = uint32_t(d.qt[p.tq[c]][k]);
         }
     // scaled decode: the N-point transforms of the kernels are plain cosine sums, C(u) C(v) / 4 goes here (N = 8 / scale)
     const uint32_t n = 8 / scale;
@@ -612,7 +623,7 @@ StageBChoice stage_b_choice(const ImagePlan &p)
     // description with no resize behind it -- a resized picture's description is the resize's, stage B writes the packed
     // intermediate; (5) a rectangle; (6) the packed whole picture.  (This is the order in which the features' overwrites of the
     // mode used to follow one another, last writer first; tests/golden/stage_b_choice.npz holds what those gave.)
-    const StageBSink sink = p.lj ? kSinkPlanes : p.ycc_on ? kSinkYcc : luma ? kSinkLuma : p.out_on && !p.rs_on ? kSinkOut
+    const StageBSink sink = p.lj ? (p.islow ? kSinkPlanesInt : kSinkPlanes) : p.ycc_on ? kSinkYcc : luma ? kSinkLuma : p.out_on && !p.rs_on ? kSinkOut
                           : p.cropped ? kSinkCropped : kSinkPacked;
     StageBChoice c;
     // (0) ahead of them all: a scan of a multi-scan file has no stage B.  Its tile geometry is still that of `form`.
@@ -625,8 +636,12 @@ StageBChoice stage_b_choice(const ImagePlan &p)
     c.or_on = !pass ? kOrNone : luma ? (p.or_copy ? kOrCopyLuma : kOrResizeLuma)
             : p.orient == 1 ? kOrNone : p.or_copy ? kOrCopy : kOrResize;
     c.out_ch = luma ? 1u : 0u;
-    c.lj_luma = p.lj && luma ? 1u : 0u;                      // (a luminance picture is k_upsample_luma's: component 0's plane alone)
-    c.lj_on = p.lj && !luma ? 1u : 0u;
+    // (the integer inverse DCT's pictures with a replicated component are k_upsample_rep's, luminance or not.  A luminance picture
+    // reads component 0 alone: only its own bit counts)
+    const uint32_t rep = !p.lj ? 0u : luma ? p.lj_rep & 1u : p.lj_rep;
+    c.lj_rep = rep ? kLjRepOn | rep | (luma ? kLjRepLuma : 0u) : 0u;
+    c.lj_luma = p.lj && luma && !rep ? 1u : 0u;              // (a luminance picture is k_upsample_luma's: component 0's plane alone)
+    c.lj_on = p.lj && !luma && !rep ? 1u : 0u;
     c.lj_out = p.lj && p.out_on && !p.rs_on ? 1u : 0u;
     return c;
 }
@@ -727,8 +742,9 @@ int plan_planes(ImagePlan &p, const mjx_planes *pl, size_t i)
     auto fail = [&]() { p.status = MJX_ERR_INVALID_ARG; return p.status; };
     if (pl->dtype > MJX_DTYPE_F32 || p.layout == MJX_LAYOUT_REF_COMPAT) return fail();
     if (p.model >= MJX_MODEL_RGB) { p.status = MJX_ERR_UNSUPPORTED_FORMAT; return p.status; }      // (the planes of an RGB, CMYK or YCCK file: not built)
+    if (p.islow) { p.status = MJX_ERR_UNSUPPORTED_FORMAT; return p.status; }      // (the integer inverse DCT's planes as the picture: not built)
     const uint32_t nc = p.ncomp;
-    const bool il = pl->interleave_chroma != 0 && nc == 3;            // (a one-component file has one plane: the flag has no meaning)
+    const bool il = pl->interleave_chroma != 0 && nc == 3;           // (a one-component file has one plane: the flag has no meaning)
     if (il && (p.h[1] != p.h[2] || p.v[1] != p.v[2])) return fail();
     const uint64_t esz = pl->dtype == MJX_DTYPE_U8 ? 1u : pl->dtype == MJX_DTYPE_F16 ? 2u : 4u;
     for (uint32_t c = 0; c < nc; c++) {

@@ -113,6 +113,13 @@ struct ImagePlan {
     // roi_m* above are then those of the rectangle grown by the upsampling filter's reach -- one sample of the most subsampled
     // component, hmax x vmax pixels, on each side, clipped to the picture: the tiles stage B must fill for the rectangle's pixels.
     bool lj = false;
+    // ... with libjpeg's integer slow inverse DCT (MJX_OPTS_IDCT = MJX_IDCT_ISLOW; kSinkPlanesInt): qint holds the components' raw DQT
+    // entries, zig-zag order, the table stage B multiplies by in place of qmult.  lj_rep: bit c -- component c's plane has at most two
+    // columns and ratios (2, 1) or (2, 2), so jdsample.c replicates it (its downsampled_width > 2 condition); such a picture is
+    // k_upsample_rep's.  Without the option both stay 0.
+    bool islow = false;
+    uint32_t lj_rep = 0;
+    uint32_t qint[4][64] = {};
     const uint8_t *scan = nullptr;
     size_t scan_len = 0;
     // The scan still holds FF00 pairs (and RSTn markers): it is de-stuffed on the device at upload (k_destuff_*), scan_len is
@@ -152,7 +159,7 @@ struct ImagePlan {
 // What stage B and the passes behind it do with a planned picture: DevImage's fields of the same names (mjx_kernels.h), decided
 // here and nowhere else.  tile_420: the picture's tile is the 4:2:0 kernel's (tile_mcus_420) and not the generic power of two.
 struct StageBChoice {
-    uint32_t mode, rs_on, or_on, out_ch, lj_on, lj_luma, lj_out;
+    uint32_t mode, rs_on, or_on, out_ch, lj_on, lj_luma, lj_out, lj_rep;
     bool tile_420;
 };
 StageBChoice stage_b_choice(const ImagePlan &p);

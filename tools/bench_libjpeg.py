@@ -4,14 +4,16 @@
 The batch of bench.py -- 2048 synthetic 3840x2160 4:2:0 q75 pictures, 64 unique ones -- decoded whole, packed RGB
   reference   the default pixels: stage B converts and stores the picture itself (the parent's path, measured in the same run)
   libjpeg     stage B stores component planes (about 1.5 bytes per pixel written and read again), k_upsample_color makes the picture
-Both build a base batch of the unique pictures once and tile it per repeat (only one large batch is resident at a time); the two
+  libjpeg-exact  (--islow) the same with libjpeg's integer slow inverse DCT in stage B (MJX_OPTS_IDCT = MJX_IDCT_ISLOW): the price of
+              byte-exact libjpeg pixels, against the float variant of the same run
+All build a base batch of the unique pictures once and tile it per repeat (only one large batch is resident at a time); the variants
 take turns inside every repeat and the figure is the best of the repeats.
 
 Per variant: ms per step (every repeat, best, median), per-class kernel ms per step -- idct_color is stage B, resize the class of the
 passes behind it, here k_upsample_color alone --, the bytes written and the device memory the batch took when it was built.
 One JSON object on the last line.
 
-    python tools/bench_libjpeg.py [--steps 5] [--warmup 1] [--repeats 3] [--images 2048]
+    python tools/bench_libjpeg.py [--steps 5] [--warmup 1] [--repeats 3] [--images 2048] [--islow]
 """
 import argparse
 import json
@@ -35,6 +37,7 @@ def main():
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--quality", type=int, default=75)
+    ap.add_argument("--islow", action="store_true", help="a third variant: libjpeg's pixels with its integer slow inverse DCT")
     args = ap.parse_args()
     import torch                         # (first: libmjx.so must find torch's HIP runtime already loaded, as in bench.py)
     import __graft_entry__ as ge
@@ -44,7 +47,7 @@ def main():
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as ex:
         datas = list(ex.map(lambda s: mjx.synth_jpeg(args.width, args.height, "420", args.quality, s), range(args.unique)))
-    names = ["reference", "libjpeg"]
+    names = ["reference", "libjpeg"] + (["libjpeg-exact"] if args.islow else [])
     reps = max(1, args.images // args.unique)
     n = reps * args.unique
     ctx = mjx.Context(0, profiling=True, throughput_plan=True)
@@ -54,7 +57,7 @@ def main():
         assert all(x == mjx.OK for x in bases[v].create_status), bases[v].create_status
     runs = {v: [] for v in names}
     for r in range(args.repeats):
-        for v in names[r % 2:] + names[:r % 2]:
+        for v in names[r % len(names):] + names[:r % len(names)]:
             free0 = free_device_bytes(mjx)
             b = bases[v].tile(reps)
             arena = max(0, free0 - free_device_bytes(mjx))
@@ -75,7 +78,7 @@ def main():
                 assert not bad, "pictures failed (%s): %s" % (v, bad[:8])
                 kms = {k: round(x[0] / args.steps, 4) for k, x in b.kernel_ms(reset=True).items() if x[1]}
                 runs[v].append({"ms_per_step": round(ms, 4), "kernel_ms_per_step": kms, "bytes_written": b.bytes()["rgb"], "arena_bytes": arena})
-                print("%-10s repeat %d: %.3f ms per step, stage B %.3f ms, k_upsample_color %.3f ms, arena %.2f GB"
+                print("%-13s repeat %d: %.3f ms per step, stage B %.3f ms, k_upsample_color %.3f ms, arena %.2f GB"
                       % (v, r, ms, kms.get("idct_color", 0.0), kms.get("resize", 0.0), arena / 1e9), flush=True)
             finally:
                 b.close()
@@ -90,6 +93,10 @@ def main():
                               "stage_b_ms_all": [x["kernel_ms_per_step"].get("idct_color", 0.0) for x in runs[v]],
                               "upsample_color_ms_all": [x["kernel_ms_per_step"].get("resize", 0.0) for x in runs[v]],
                               "bytes_written": best["bytes_written"], "arena_bytes": max(x["arena_bytes"] for x in runs[v])}
+    if args.islow:
+        f, x = out["variants"]["libjpeg"], out["variants"]["libjpeg-exact"]
+        out["islow_over_float"] = {"step": round(x["ms_per_step_best"] / f["ms_per_step_best"], 4),
+                                   "stage_b": round(x["kernel_ms_per_step"]["idct_color"] / f["kernel_ms_per_step"]["idct_color"], 4)}
     for b in bases.values():
         b.close()
     for s in scans:
