@@ -192,6 +192,9 @@ pub const MJX_OPTS_IDCT_OFFSET: usize = 12;
 pub const MJX_IDCT_FLOAT: u8 = 0;
 /// libjpeg's integer slow inverse DCT: byte-exact libjpeg pixels; with pixels = 1 (MJX_PIXELS_LIBJPEG) only
 pub const MJX_IDCT_ISLOW: u8 = 1;
+/// byte 13 of mjx_opts, the next padding byte: 1 with pixels = 1 and MJX_IDCT_ISLOW lets scale_denom 2, 4, 8 through as libjpeg's own
+/// reduced decode (include/mjx.h: MJX_OPTS_EXACT_SCALE); 0 keeps the refusal of a scale with these pixels
+pub const MJX_OPTS_EXACT_SCALE_OFFSET: usize = 13;
 /// or-ed into rh of mjx_upsample_color_host / mjx_upsample_luma_host: the component is replicated whatever its ratios
 pub const MJX_UPSAMPLE_REPLICATE: u8 = 0x80;
 
@@ -202,6 +205,13 @@ impl mjx_opts {
     }
     pub fn set_idct(&mut self, idct: u8) {
         unsafe { *(self as *mut mjx_opts as *mut u8).add(MJX_OPTS_IDCT_OFFSET) = idct }
+    }
+    /// MJX_OPTS_EXACT_SCALE: 1 = the exact pixels at scale_denom 2, 4, 8 are libjpeg's reduced decode; 0 = a scale with them is refused
+    pub fn exact_scale(&self) -> u8 {
+        unsafe { *(self as *const mjx_opts as *const u8).add(MJX_OPTS_EXACT_SCALE_OFFSET) }
+    }
+    pub fn set_exact_scale(&mut self, on: u8) {
+        unsafe { *(self as *mut mjx_opts as *mut u8).add(MJX_OPTS_EXACT_SCALE_OFFSET) = on }
     }
     /// 0: progressive files are refused as before; 1: SOF2 frames of one or three components decode on the device
     pub fn progressive(&self) -> u8 {
@@ -334,6 +344,11 @@ extern "C" {
     pub fn mjx_upsample_luma_host(plane: *const u8, cw: u32, ch: u32, rh: u8, rv: u8, rect: *const mjx_rect, out: *mut u8) -> c_int;
     /// host only: MJX_IDCT_ISLOW's transform of one block, natural order (the lane routine stage B's integer sink runs)
     pub fn mjx_idct_islow_host(coef: *const i16, q: *const u16, out: *mut u8) -> c_int;
+    /// host only: its reduced siblings at scale_denom 2, 4, 8 -- n = 8, 4, 2 or 1, the component's transform size; out: n x n samples
+    pub fn mjx_idct_reduced_host(coef: *const i16, q: *const u16, n: u32, out: *mut u8) -> c_int;
+    /// host only: the planner's geometry of MJX_IDCT_ISLOW's planes (transform size, plane samples, ratios, stride, replication per component)
+    pub fn mjx_plan_reduced(desc: *const mjx_scan_desc, opts: *const mjx_opts, ncomp: *mut u32, size: *mut u32, plane_w: *mut u32,
+                            plane_h: *mut u32, rh: *mut u32, rv: *mut u32, stride: *mut u32, replicated: *mut u32) -> c_int;
     pub fn mjx_validate(desc: *const mjx_scan_desc, opts: *const mjx_opts) -> c_int;
     pub fn mjx_plan_tiles(desc: *const mjx_scan_desc, opts: *const mjx_opts, tiles_read: *mut u64, tiles_total: *mut u64,
                           tile_mcus: *mut u32) -> c_int;

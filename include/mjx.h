@@ -128,7 +128,8 @@ typedef struct mjx_opts {
                              B = clamp(Y + ((FIX(1.77200) cb + 32768) >> 16)), G = clamp(Y + ((-FIX(0.34414) cb + 32768
                              - FIX(0.71414) cr) >> 16)); one component: R = G = B = s.  STANDARD layout at full size only:
                              MJX_LAYOUT_REF_COMPAT, strict_ref or scale_denom > 1 give the picture MJX_ERR_INVALID_ARG (a resize with
-                             auto_scale picks scale 1).  Rectangles, output formats, resize and orientation compose as with the
+                             auto_scale picks scale 1) -- a scale is accepted together with MJX_IDCT_ISLOW and MJX_OPTS_EXACT_SCALE
+                             only, see there.  Rectangles, output formats, resize and orientation compose as with the
                              default pixels: a rectangle is byte for byte the crop of the whole picture.  Anything but 0 and 1:
                              MJX_ERR_INVALID_ARG.  (The field stands in front of scale_denom, not at the struct's end: the struct's
                              size and the other fields' offsets are as before, scale_denom's moved by one byte -- callers are
@@ -214,9 +215,10 @@ typedef struct mjx_opts {
  * pixels == MJX_PIXELS_LIBJPEG only (without it: MJX_ERR_INVALID_ARG for the picture): libjpeg's integer slow inverse DCT
  * (jidctint.c), so that the picture is byte for byte the one libjpeg and libjpeg-turbo give (Pillow, OpenCV, torchvision's CPU path),
  * not the one up to 3 levels from it.  Anything but 0 and 1: MJX_ERR_INVALID_ARG.  Everything MJX_PIXELS_LIBJPEG refuses stays
- * refused with the same status (scale_denom > 1, MJX_LAYOUT_REF_COMPAT, strict_ref: MJX_ERR_INVALID_ARG; RGB, CMYK and YCCK
- * pictures: MJX_ERR_UNSUPPORTED_FORMAT); a plane description (mjx_planes) together with MJX_IDCT_ISLOW gives the picture
- * MJX_ERR_UNSUPPORTED_FORMAT.
+ * refused with the same status (MJX_LAYOUT_REF_COMPAT, strict_ref: MJX_ERR_INVALID_ARG; RGB, CMYK and YCCK pictures:
+ * MJX_ERR_UNSUPPORTED_FORMAT), scale_denom > 1 included (MJX_ERR_INVALID_ARG) unless the call also sets MJX_OPTS_EXACT_SCALE, which
+ * makes scale_denom 2, 4 and 8 libjpeg's own reduced decode (below); a plane description (mjx_planes) together with MJX_IDCT_ISLOW
+ * gives the picture MJX_ERR_UNSUPPORTED_FORMAT.
  * The arithmetic, for one 8 x 8 block of one component.  All of it is in 32-bit two's-complement integers that wrap.
  *   d[v][u] = coef[v][u] q[v][u], q the raw DQT entry (8 or 16 bits).
  *   Pass 1 runs P with n = 11 on every column (over v), pass 2 the same P with n = 18 on every row of pass 1's output.
@@ -236,7 +238,41 @@ typedef struct mjx_opts {
  * (2, 1) or (2, 2) is replicated in both directions, out[X][Y] = s[X / rh][Y / rv] -- jdsample.c picks its triangle filters only for
  * downsampled_width > 2; (1, 2) keeps its filter at every width.  Without MJX_IDCT_ISLOW MJX_PIXELS_LIBJPEG's own rule stands.
  * Rectangles, output formats, caller memory, luminance, resize, orientation, mjx_batch_tile, the pool, mjx_decode, multi-scan,
- * restart and progressive inputs compose as with MJX_PIXELS_LIBJPEG. */
+ * restart and progressive inputs compose as with MJX_PIXELS_LIBJPEG.
+ *
+ * At a reduced scale: MJX_PIXELS_LIBJPEG, MJX_IDCT_ISLOW, MJX_OPTS_EXACT_SCALE(&opts) = 1 (byte 13 of mjx_opts, the next padding byte:
+ * 0 keeps every earlier behaviour, the refusal of a scale with these pixels included; 1 without MJX_PIXELS_LIBJPEG and MJX_IDCT_ISLOW,
+ * or any other value: MJX_ERR_INVALID_ARG; with scale_denom 0 or 1 it changes nothing) and scale_denom = s in {2, 4, 8} give byte for
+ * byte the picture libjpeg gives with scale_denom = s (Pillow's draft() / thumbnail(), OpenCV's IMREAD_REDUCED_COLOR_*, torchvision's and DALI's libjpeg back ends).
+ * Let m = 8 / s.
+ *   1. The picture is ceil(W / s) x ceil(H / s), as for every scaled decode.
+ *   2. Component c takes a transform of size N_c (jdmaster.c; one size for both directions): N_c = m, doubled while N_c < 8,
+ *      (hmax m) mod (h_c N_c 2) == 0 and (vmax m) mod (v_c N_c 2) == 0; a one-component file has h = v = 1.  Its plane holds
+ *      ceil(W h_c N_c / (8 hmax)) x ceil(H v_c N_c / (8 vmax)) samples and is upsampled by rh = hmax m / (h_c N_c),
+ *      rv = vmax m / (v_c N_c).  (4:2:0 at 1/2: Y through the 4 x 4 transform, Cb and Cr through the full 8 x 8 one, nothing upsampled.)
+ *   3. d[v][u] = coef[v][u] q[v][u] as above, wrapping.
+ *   4. The transform (jidctred.c).  D(x, n) = (x + (1 << (n - 1))) >> n, arithmetic; FIX as above; everything wraps.
+ *      N = 8: the transform above.
+ *      N = 4: R4(d0 .. d7, n): t0 = d0 << 14, t2 = d2 FIX(1.847759065) - d6 FIX(0.765366865), t10 = t0 + t2, t12 = t0 - t2;
+ *        with z1 = d7, z2 = d5, z3 = d3, z4 = d1:
+ *        a = -z1 FIX(0.211164243) + z2 FIX(1.451774981) - z3 FIX(2.172734803) + z4 FIX(1.061594337),
+ *        b = -z1 FIX(0.509795579) - z2 FIX(0.601344887) + z3 FIX(0.899976223) + z4 FIX(2.562915447);
+ *        outputs D(t10 + b, n), D(t12 + a, n), D(t12 - a, n), D(t10 - b, n); d4 is never read.  Pass 1 runs R4(., 12) down every
+ *        column u != 4 over v, pass 2 R4(., 19) along each of the four rows over u.
+ *      N = 2: R2(d, n): t10 = d0 << 15, t0 = -d7 FIX(0.720959822) + d5 FIX(0.850430095) - d3 FIX(1.272758580) + d1 FIX(3.624509785);
+ *        outputs D(t10 + t0, n), D(t10 - t0, n).  Pass 1 runs R2(., 13) on columns 0, 1, 3, 5, 7, pass 2 R2(., 20) on the two rows.
+ *      N = 1: D(d[0][0], 3).
+ *      The sample is clamp(x + 128, 0, 255) as above.  mjx_idct_reduced_host runs exactly this on the CPU.
+ *   5. Upsampling.  At s = 2 and 4 the rules above on the scaled planes and the scaled ratios: the triangle filters for (2, 1), (1, 2)
+ *      and (2, 2), replication for a ratio of 4, and the narrow-plane rule on the SCALED plane's width.  At s = 8 every component is
+ *      replicated whatever its ratios (jdsample.c turns fancy upsampling off when min_DCT_scaled_size is 1).  Then jdcolor.c's colour
+ *      step; a one-component picture is its plane.
+ * Rectangles are in the coordinates of the scaled picture and are byte for byte its crop; output formats, caller memory, luminance,
+ * orientation, an explicit scale with a resize, mjx_batch_tile, mjx_decode and every input path compose.  A resize with auto_scale
+ * still picks scale 1 with MJX_PIXELS_LIBJPEG; scale_denom with MJX_PIXELS_LIBJPEG and the float transform, or without
+ * MJX_OPTS_EXACT_SCALE, stays MJX_ERR_INVALID_ARG. */
+#define MJX_OPTS_EXACT_SCALE_OFFSET 13
+#define MJX_OPTS_EXACT_SCALE(opts) (((uint8_t *)(opts))[MJX_OPTS_EXACT_SCALE_OFFSET])
 #define MJX_OPTS_IDCT_OFFSET 12
 #define MJX_OPTS_IDCT(opts) (((uint8_t *)(opts))[MJX_OPTS_IDCT_OFFSET])
 enum {
@@ -770,6 +806,15 @@ int mjx_upsample_luma_host(const uint8_t *plane, uint32_t cw, uint32_t ch, uint8
  * (idct_islow_inplace, mjx_kernels.h).  coef: the 64 coefficients, q: the 64 raw DQT entries, out: the 64 samples
  * clamp(x + 128, 0, 255), all three in natural (row-major, [v][u]) order. */
 int mjx_idct_islow_host(const int16_t coef[64], const uint16_t q[64], uint8_t out[64]);
+/* Host-only, from the planner itself: the geometry of MJX_IDCT_ISLOW's planes for this picture and these options -- per component the
+ * transform's size N_c (8 without MJX_OPTS_EXACT_SCALE and a scale), the plane's samples, the upsampling ratios, the row stride of the
+ * plane in the library's scratch and whether the component is replicated (the narrow-plane rule; every component at 1/8).  Any
+ * pointer may be NULL.  A picture without MJX_PIXELS_LIBJPEG and MJX_IDCT_ISLOW: MJX_ERR_INVALID_ARG; else the picture's status. */
+int mjx_plan_reduced(const mjx_scan_desc *desc, const mjx_opts *opts, uint32_t *ncomp, uint32_t size[3], uint32_t plane_w[3],
+                     uint32_t plane_h[3], uint32_t rh[3], uint32_t rv[3], uint32_t stride[3], uint32_t replicated[3]);
+/* ... and of its reduced siblings at scale_denom 2, 4, 8 (the lane routines stage B runs there): N = 8, 4, 2 or 1, the size of the
+ * component's transform; out holds the N x N samples, rows of N.  Any other N: MJX_ERR_INVALID_ARG. */
+int mjx_idct_reduced_host(const int16_t coef[64], const uint16_t q[64], uint32_t N, uint8_t *out);
 
 /* mjx_batch_create_resize with an orientation description (above); orient == NULL: mjx_batch_create_resize itself.  Descriptors
  * carry no file bytes: from_exif = 1 is MJX_ERR_INVALID_ARG for the call -- read the tag with mjx_exif_orientation and pass it in

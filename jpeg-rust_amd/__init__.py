@@ -95,6 +95,18 @@ Opts.IDCT_OFFSET = 12                   # MJX_OPTS_IDCT_OFFSET: the next padding
 Opts.idct = property(_opts_idct, _opts_set_idct)
 
 
+def _opts_exact_scale(self):
+    return ctypes.c_uint8.from_address(ctypes.addressof(self) + Opts.EXACT_SCALE_OFFSET).value
+
+
+def _opts_set_exact_scale(self, v):
+    ctypes.c_uint8.from_address(ctypes.addressof(self) + Opts.EXACT_SCALE_OFFSET).value = int(v)
+
+
+Opts.EXACT_SCALE_OFFSET = 13            # MJX_OPTS_EXACT_SCALE_OFFSET: the next padding byte
+Opts.exact_scale = property(_opts_exact_scale, _opts_set_exact_scale)
+
+
 class Dst(ctypes.Structure):
     """mjx_dst: caller-owned device memory for one picture; pitches in elements."""
     _fields_ = [("dev", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
@@ -281,6 +293,8 @@ SYMBOLS = {
                                        _P(Rect), _P(ctypes.c_uint8)]),
     "mjx_upsample_luma_host": (_int, [_P(ctypes.c_uint8), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8, _P(Rect), _P(ctypes.c_uint8)]),
     "mjx_idct_islow_host": (_int, [_P(ctypes.c_int16), _P(ctypes.c_uint16), _P(ctypes.c_uint8)]),
+    "mjx_plan_reduced": (_int, [_P(ScanDesc), _P(Opts), _P(ctypes.c_uint32)] + [_P(ctypes.c_uint32)] * 7),
+    "mjx_idct_reduced_host": (_int, [_P(ctypes.c_int16), _P(ctypes.c_uint16), ctypes.c_uint32, _P(ctypes.c_uint8)]),
     "mjx_exif_orientation": (_int, [ctypes.c_char_p, _sz, _P(ctypes.c_uint8)]),
     "mjx_orient_compose": (ctypes.c_uint8, [ctypes.c_uint8, ctypes.c_uint8]),
     "mjx_color_model": (_int, [ctypes.c_char_p, _sz, _P(ColorInfo)]),
@@ -396,8 +410,9 @@ def _pixels(pixels):
 
 
 def _idct(idct, pixels=None):
-    """None / "float" / IDCT_FLOAT, or "islow" / IDCT_ISLOW (mjx.h: MJX_OPTS_IDCT); None with pixels="libjpeg-exact" is "islow"."""
-    names = {None: IDCT_ISLOW if pixels == "libjpeg-exact" else IDCT_FLOAT, "float": IDCT_FLOAT, "islow": IDCT_ISLOW}
+    """None / "float" / IDCT_FLOAT, or "islow" / "islow-scaled" / IDCT_ISLOW (mjx.h: MJX_OPTS_IDCT); None with pixels="libjpeg-exact" is
+    "islow".  ("islow-scaled": "islow", and _opts sets MJX_OPTS_EXACT_SCALE with it.)"""
+    names = {None: IDCT_ISLOW if pixels == "libjpeg-exact" else IDCT_FLOAT, "float": IDCT_FLOAT, "islow": IDCT_ISLOW, "islow-scaled": IDCT_ISLOW}
     if idct is None or isinstance(idct, str):
         if idct not in names:
             raise MjxError(ERR_INVALID_ARG, "idct=%r" % (idct,))
@@ -425,7 +440,10 @@ def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_imag
     rois: see _rects (mjx.h: mjx_opts.rois, n_rois); the Opts returned keeps the array alive.
     pixels: see _pixels -- "libjpeg": rounded samples, fancy chroma upsampling and libjpeg's integer colour tables.
     idct: see _idct -- "islow": libjpeg's integer slow inverse DCT, with pixels="libjpeg" only: the picture is byte for byte libjpeg's
-    (mjx.h: MJX_OPTS_IDCT); pixels="libjpeg-exact" is shorthand for pixels="libjpeg", idct="islow".
+    (mjx.h: MJX_OPTS_IDCT); pixels="libjpeg-exact" is shorthand for pixels="libjpeg", idct="islow".  With pixels="libjpeg-exact" (and the
+    integer transform), or with idct="islow-scaled" beside pixels="libjpeg", scale=2, 4 or 8 is libjpeg's own reduced decode (mjx.h:
+    MJX_OPTS_EXACT_SCALE: its reduced integer transforms, a size per component), again byte for byte; pixels="libjpeg", idct="islow"
+    with a scale stays refused, as it was.
     color: see _color -- "file": the colour model comes from the file (RGB, CMYK and YCCK files decode to R,G,B).
     progressive: True -- progressive files (SOF2) are accepted (mjx.h: MJX_OPTS_PROGRESSIVE); an integer is passed through as it is."""
     dd = DESTUFF_AUTO if device_destuff is None else (DESTUFF_DEVICE if device_destuff else DESTUFF_HOST)
@@ -435,6 +453,7 @@ def _opts(strict_ref=False, layout=LAYOUT_STANDARD, keep_coefs=False, chunk_imag
     o = Opts(int(bool(strict_ref)), int(layout), int(bool(keep_coefs)), dd, int(chunk_images), _pixels(pixels), scale)
     o.color = _color(color)
     o.idct = _idct(idct, pixels)
+    o.exact_scale = int(o.idct == IDCT_ISLOW and (idct == "islow-scaled" or pixels == "libjpeg-exact"))      # (idct given as "islow" or IDCT_ISLOW alike)
     o.progressive = int(progressive) if not isinstance(progressive, bool) and 0 <= int(progressive) <= 255 else int(bool(progressive))
     arr = _rects(rois)
     if arr is not None:
@@ -686,6 +705,17 @@ def upsample_luma_host(plane, rh, rv, rect):
     return out[:h, :w]
 
 
+def idct_reduced_host(coef, q, n):
+    """mjx_idct_reduced_host (host only; the lane routines of the integer inverse DCT at a reduced scale): one block's 64 coefficients
+    (int16) and raw DQT entries (uint16), [8, 8] in natural order, and the transform's size n (8, 4, 2 or 1) -> ndarray [n, n] uint8."""
+    c = np.ascontiguousarray(coef, dtype=np.int16).reshape(64)
+    t = np.ascontiguousarray(q, dtype=np.uint16).reshape(64)
+    out = np.empty((int(n), int(n)), np.uint8)
+    _check(lib().mjx_idct_reduced_host(c.ctypes.data_as(_P(ctypes.c_int16)), t.ctypes.data_as(_P(ctypes.c_uint16)), int(n),
+                                       out.ctypes.data_as(_P(ctypes.c_uint8))), "mjx_idct_reduced_host")
+    return out
+
+
 def idct_islow_host(coef, q):
     """mjx_idct_islow_host (host only; the lane routine stage B's integer sink runs): one block's 64 coefficients (int16) and its 64
     raw DQT entries (uint16), both [8, 8] in natural order -> ndarray [8, 8] uint8, the samples of idct="islow"."""
@@ -731,6 +761,16 @@ class ParsedScan:
         rd, tot, t = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
         _check(lib().mjx_plan_tiles(ctypes.byref(self.desc), ctypes.byref(o), ctypes.byref(rd), ctypes.byref(tot), ctypes.byref(t)), "mjx_plan_tiles")
         return dict(tiles_read=rd.value, tiles_total=tot.value, tile_mcus=t.value)
+
+    def plan_reduced(self, scale=1, pixels="libjpeg-exact", idct=None, color=None, progressive=False):
+        """mjx_plan_reduced (host only) -> [dict(size, plane_w, plane_h, rh, rv, stride, replicated)] per component: the planner's geometry
+        of the exact pixels' planes at this scale -- the transform size libjpeg picks, the plane's samples, its upsampling ratios."""
+        o = _opts(scale=scale, pixels=pixels, idct=idct, color=color, progressive=progressive)
+        n = ctypes.c_uint32()
+        arr = [(ctypes.c_uint32 * 3)() for _ in range(7)]
+        _check(lib().mjx_plan_reduced(ctypes.byref(self.desc), ctypes.byref(o), ctypes.byref(n), *arr), "mjx_plan_reduced")
+        keys = ("size", "plane_w", "plane_h", "rh", "rv", "stride", "replicated")
+        return [{k: int(a[c]) for k, a in zip(keys, arr)} for c in range(n.value)]
 
     def output_layout(self, output=None, i=0, roi=None, scale=1, layout=LAYOUT_STANDARD, color=None, progressive=False):
         """mjx_output_layout (host only) -> dict(width, height, row_pitch, plane_pitch, bytes, dev): what a decode of this picture

@@ -165,6 +165,7 @@ enum PostPass : uint32_t {
     kPassUpsample,          // libjpeg's pixels: the chunk's component planes -> its pictures (or the intermediates of the passes below)
     kPassUpsampleLuma,      // ... luminance pictures: component 0's plane alone
     kPassUpsampleRep,       // ... the integer inverse DCT's pictures with a replicated component (DevImage::lj_rep), luminance or not
+    kPassUpsampleRed,       // ... the integer inverse DCT's pictures at a reduced scale (DevImage::lj_red), luminance or not
     kPassResize,            // resize on the device: the intermediates -> the target pictures (per filter kind)
     kPassOrient,            // orientation on the device: k_orient_out copies
     kPassResizeOrient,      // ... k_resize_orient resamples (per filter kind)
@@ -546,7 +547,7 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
     const StageBChoice sb = stage_b_choice(p);          // what stage B and the passes behind it do with the picture: decided there alone
     d.mode = sb.mode;
     d.rs_on = sb.rs_on; d.or_on = sb.or_on; d.out_ch = sb.out_ch;
-    d.lj_on = sb.lj_on; d.lj_luma = sb.lj_luma; d.lj_out = sb.lj_out; d.lj_rep = sb.lj_rep;
+    d.lj_on = sb.lj_on; d.lj_luma = sb.lj_luma; d.lj_out = sb.lj_out; d.lj_rep = sb.lj_rep; d.lj_red = sb.lj_red;
     d.scale = p.scale;
     d.out_w = p.out_w;
     d.out_h = p.out_h;
@@ -596,9 +597,11 @@ void fill_dev_image(const ImagePlan &p, DevImage &d)
     if (p.lj) {              // libjpeg's pixels: where stage B puts component c's plane in the chunk's scratch
         uint64_t off = 0;
         for (uint32_t c = 0; c < p.ncomp; c++) {
-            d.lj_stride[c] = p.mcux * 8 * p.h[c];
+            // (a reduced scale with the integer inverse DCT: N_c samples per block side, rows padded to the 8 bytes lj_strip8 reads by)
+            const uint32_t nc = d.lj_red ? lj_red_n(d.lj_red, c) : 8u;
+            d.lj_stride[c] = (p.mcux * nc * p.h[c] + 7u) & ~7u;
             d.lj_off[c] = off;
-            off += uint64_t(d.lj_stride[c]) * p.mcuy * 8 * p.v[c];
+            off += uint64_t(d.lj_stride[c]) * p.mcuy * nc * p.v[c];
         }
     }
     d.role = p.role;
@@ -744,10 +747,10 @@ void plan_chunks(mjx_batch *b)
                     c.plane_words += uint64_t(d.width) * d.height * d.ncomp;
                     c.max_pixel_wgs = std::max<uint32_t>(c.max_pixel_wgs, uint32_t((uint64_t(d.width) * d.height + 255) / 256));
                 }
-                if ((d.lj_on || d.lj_luma || d.lj_rep) && d.role != 1) {        // (the planes span the MCU grid: whole 64-byte block rows, so every plane starts on a multiple of 8)
+                if ((d.lj_on || d.lj_luma || d.lj_rep || d.lj_red) && d.role != 1) {        // (the planes span the MCU grid: whole 64-byte block rows, so every plane starts on a multiple of 8)
                     d.plane_off = c.lj_words;
-                    c.lj_words += (d.lj_off[d.ncomp - 1] + uint64_t(d.lj_stride[d.ncomp - 1]) * d.mcuy * 8 * d.cv[d.ncomp - 1]) / 8;
-                    pass(d.lj_rep ? kPassUpsampleRep : d.lj_luma ? kPassUpsampleLuma : kPassUpsample, 0, lj_tiles(d.roi_x, d.roi_w, d.roi_h));
+                    c.lj_words += (d.lj_off[d.ncomp - 1] + uint64_t(d.lj_stride[d.ncomp - 1]) * d.mcuy * (d.lj_red ? lj_red_n(d.lj_red, d.ncomp - 1) : 8u) * d.cv[d.ncomp - 1]) / 8;
+                    pass(d.lj_red ? kPassUpsampleRed : d.lj_rep ? kPassUpsampleRep : d.lj_luma ? kPassUpsampleLuma : kPassUpsample, 0, lj_tiles(d.roi_x, d.roi_w, d.roi_h));
                 }
                 c.max_segs = std::max<uint32_t>(c.max_segs, (d.nmcu + kDcSegMcus - 1) / kDcSegMcus);
             }
@@ -1089,6 +1092,9 @@ int run_chunk(mjx_batch *b, size_t ci, unsigned stages, int fix_passes, unsigned
                 case kPassUpsampleRep:
                     launch_upsample_rep(sp, tiles, nimg, imgs, reinterpret_cast<const uint8_t *>(SCR(d_planes)), b->d_rgb, b->d_img_flags);
                     break;
+                case kPassUpsampleRed:
+                    launch_upsample_red(sp, tiles, nimg, imgs, reinterpret_cast<const uint8_t *>(SCR(d_planes)), b->d_rgb, b->d_img_flags);
+                    break;
                 case kPassResize: launch_resize_out(sp, tiles, nimg, imgs, b->d_rgb, b->d_img_flags, f); break;
                 case kPassOrient: case kPassOrientLuma: launch_orient_out(sp, tiles, nimg, imgs, b->d_rgb, b->d_img_flags, k == kPassOrientLuma); break;
                 default: launch_resize_orient(sp, tiles, nimg, imgs, b->d_rgb, b->d_img_flags, k == kPassResizeLuma, f); break;
@@ -1353,7 +1359,7 @@ int build_batch(mjx_ctx *ctx, const std::vector<ImagePlan> &plans_in, const mjx_
         d.lut2_n = lut_n[k] - p.lut_plain_n;
         if (p.prog) d.lut_n = d.lut2_n = 0;      // (its tables are read where they lie, from lut_off on: no entropy workgroup stages them)
         d.qm_off = uint32_t(k * 192);
-        if (p.scale > 1) d.qm_off = uint32_t((nu + k) * 192);       // (the reduced transforms' multipliers: the second half of the pool)
+        if (p.scale > 1 && !p.islow) d.qm_off = uint32_t((nu + k) * 192);       // (the reduced transforms' multipliers: the second half of the pool; the integer ones take the raw entries)
         if (p.ncomp == 4) d.qm3_off = uint32_t(qm_tail[k] + (p.scale > 1 ? 64 : 0));      // (a fourth component's: behind both halves)
         inf.model = p.model;
         d.seg_off = seg_off[k];
@@ -2305,6 +2311,41 @@ extern "C" int mjx_plan_tiles(const mjx_scan_desc *desc, const mjx_opts *opts, u
     });
 }
 
+// Host-only: the planner's geometry of the integer inverse DCT at a reduced scale (MJX_OPTS_EXACT_SCALE) -- per component the
+// transform's size, the plane's samples, the upsampling ratios (red_plane, the planner's routine), the plane's row stride as
+// fill_dev_image lays it out and whether the component is replicated.  A picture planned without the reduced decode reports size 8,
+// its full-size planes and ratios, and no replication bits but the narrow-plane rule's.
+extern "C" int mjx_plan_reduced(const mjx_scan_desc *desc, const mjx_opts *opts, uint32_t *ncomp, uint32_t size[3], uint32_t plane_w[3],
+                                uint32_t plane_h[3], uint32_t rh[3], uint32_t rv[3], uint32_t stride[3], uint32_t replicated[3])
+{
+    return guarded([&]() -> int {
+    if (!desc) return MJX_ERR_INVALID_ARG;
+    mjx_opts o{};
+    if (opts) o = *opts;
+    if (!rois_fit(o, 1)) return MJX_ERR_INVALID_ARG;
+    std::vector<ImagePlan> plans;
+    plan_input(*desc, o, plans);
+    const ImagePlan &p = plans.back();
+    if (p.status != MJX_OK) return p.status;
+    if (!p.lj || !p.islow || p.ncomp > 3) return MJX_ERR_INVALID_ARG;
+    DevImage d;
+    fill_dev_image(p, d);
+    if (ncomp) *ncomp = p.ncomp;
+    for (uint32_t c = 0; c < p.ncomp; c++) {
+        const uint32_t n = d.lj_red ? lj_red_n(d.lj_red, c) : 8u;
+        const RedPlane g = red_plane(p.width, p.height, p.h[c], p.v[c], p.hmax, p.vmax, 8u / p.scale, n);
+        if (size) size[c] = n;
+        if (plane_w) plane_w[c] = g.cw;
+        if (plane_h) plane_h[c] = g.ch;
+        if (rh) rh[c] = g.rh;
+        if (rv) rv[c] = g.rv;
+        if (stride) stride[c] = d.lj_stride[c];
+        if (replicated) replicated[c] = d.lj_red ? lj_red_rep(d.lj_red, c) : (d.lj_rep >> c & 1u);
+    }
+    return MJX_OK;
+    });
+}
+
 // Host-only: what a decode of this picture as input i would write -- plan_output's own numbers.
 extern "C" int mjx_output_layout(const mjx_scan_desc *desc, const mjx_opts *opts, const mjx_output *fmt, size_t i, mjx_dst *layout,
                                  size_t *bytes)
@@ -2460,6 +2501,23 @@ extern "C" int mjx_upsample_color_host(const uint8_t *const *planes, const uint3
 }
 
 // Host-only: libjpeg's integer slow inverse DCT of one block -- the lane routine stage B's integer sink runs (idct_islow_inplace).
+// ... and its reduced siblings (idct_red4_inplace, idct_red2_inplace, idct_red1; N = 8: the full transform): out holds the N x N samples,
+// rows of N.  The block is a heap block of exactly 64 words, so that a read or a write outside it shows under a sanitizer.
+extern "C" int mjx_idct_reduced_host(const int16_t coef[64], const uint16_t q[64], uint32_t N, uint8_t *out)
+{
+    return guarded([&]() -> int {
+    if (!coef || !q || !out || (N != 1 && N != 2 && N != 4 && N != 8)) return MJX_ERR_INVALID_ARG;
+    uint32_t *blk = static_cast<uint32_t *>(std::aligned_alloc(16, 64 * sizeof(uint32_t)));
+    if (!blk) return MJX_ERR_NOMEM;
+    for (int k = 0; k < 64; k++) blk[k] = uint32_t(int32_t(coef[k])) * uint32_t(q[k]);
+    idct_reduced_inplace(blk, N);
+    for (uint32_t y = 0; y < N; y++)
+        for (uint32_t x = 0; x < N; x++) out[y * N + x] = uint8_t(islow_sample(blk[y * 8 + x]));
+    std::free(blk);
+    return MJX_OK;
+    });
+}
+
 extern "C" int mjx_idct_islow_host(const int16_t coef[64], const uint16_t q[64], uint8_t out[64])
 {
     return guarded([&]() -> int {
@@ -2556,9 +2614,13 @@ extern "C" int mjx_batch_tile(mjx_ctx *ctx, const mjx_batch *src, size_t times, 
         p.width = d.width; p.height = d.height; p.ncomp = d.ncomp; p.bpm = d.bpm; p.hmax = d.hmax; p.vmax = d.vmax;
         p.scale = d.scale ? d.scale : 1u; p.out_w = d.out_w; p.out_h = d.out_h;      // (the copies keep the source's scale)
         p.cropped = src->info[k].cropped;                                             // (... and its rectangle)
-        p.lj = src->himages[k].lj_on != 0 || src->himages[k].lj_luma != 0 || src->himages[k].lj_rep != 0;             // (... and its pixels)
-        p.islow = sink_of(src->himages[k].mode) == kSinkPlanesInt;                                                    // (... and its inverse DCT,
+        p.lj = src->himages[k].lj_on != 0 || src->himages[k].lj_luma != 0 || src->himages[k].lj_rep != 0 || src->himages[k].lj_red != 0;      // (... and its pixels)
+        p.islow = sink_of(src->himages[k].mode) == kSinkPlanesInt || sink_of(src->himages[k].mode) == kSinkPlanesRed; // (... and its inverse DCT,
         p.lj_rep = src->himages[k].lj_rep & 7u;                                                                       // whose replicated components keep their bits)
+        for (uint32_t c = 0; c < 3 && src->himages[k].lj_red; c++) {                                                  // (... and, at a reduced scale, their transform sizes)
+            p.red_n[c] = uint8_t(lj_red_n(src->himages[k].lj_red, c));
+            p.lj_rep |= lj_red_rep(src->himages[k].lj_red, c) << c;
+        }
         if (src->info[k].out_on) {                                                    // (... and its output format)
             const ImageInfo &fi = src->info[k];
             p.out_on = true;
@@ -3720,7 +3782,7 @@ extern "C" const char *mjx_version(void)
     static char v[200];
     static std::once_flag once;
     std::call_once(once, [] {
-        std::snprintf(v, sizeof v, "mjx 0.3 abi=%d gfx950 subseq_bits=%d..%d checkpoint_bits=%d lut_primary_bits=%d huff_wg_lanes=%d merge_wg_lanes=%d idct=float,islow",
+        std::snprintf(v, sizeof v, "mjx 0.3 abi=%d gfx950 subseq_bits=%d..%d checkpoint_bits=%d lut_primary_bits=%d huff_wg_lanes=%d merge_wg_lanes=%d idct=float,islow,islow-scaled",
                       MJX_ABI_VERSION, kSubseqBits, kSubseqBits * 5 / 4, kCpBits, kLutPrimaryBits, kHuffWg, kMergeWg);
     });
     return v;

@@ -4,7 +4,7 @@
 // fancy chroma upsampling and libjpeg's integer colour tables, mjx_opts.pixels = MJX_PIXELS_LIBJPEG; --color-from-file: the file says
 // what its components are, MJX_OPTS_COLOR = MJX_COLOR_FILE -- RGB, CMYK and YCCK files are written as R,G,B; --progressive: progressive
 // files (SOF2) are accepted, MJX_OPTS_PROGRESSIVE = 1; --islow: --libjpeg-pixels with libjpeg's integer inverse DCT, MJX_OPTS_IDCT =
-// MJX_IDCT_ISLOW -- byte for byte the picture libjpeg gives)
+// MJX_IDCT_ISLOW -- byte for byte the picture libjpeg gives, with --scale 2, 4 or 8 libjpeg's own reduced decode, MJX_OPTS_EXACT_SCALE = 1)
 // Writes the same ASCII P3 file ("P3\n{w} {h}\n255\n" then "r g b\n" per pixel, main.rs:35-39), buffered; --p6 writes
 // binary PPM instead.  --luma: the luminance picture (MJX_OUTPUT_CHANNELS = 1) through the batch API, written as binary PGM (P5); chroma
 // is never transformed.  --ycc: the component planes at their own sampling (mjx_planes), written back to back as one raw file -- Y,
@@ -104,7 +104,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--strict")) opts.strict_ref = 1;
         else if (!std::strcmp(argv[i], "--ref-compat")) opts.layout = MJX_LAYOUT_REF_COMPAT;
         else if (!std::strcmp(argv[i], "--libjpeg-pixels")) opts.pixels = MJX_PIXELS_LIBJPEG;
-        else if (!std::strcmp(argv[i], "--islow")) { opts.pixels = MJX_PIXELS_LIBJPEG; MJX_OPTS_IDCT(&opts) = MJX_IDCT_ISLOW; }      // (implies --libjpeg-pixels)
+        else if (!std::strcmp(argv[i], "--islow")) { opts.pixels = MJX_PIXELS_LIBJPEG; MJX_OPTS_IDCT(&opts) = MJX_IDCT_ISLOW; MJX_OPTS_EXACT_SCALE(&opts) = 1; }      // (implies --libjpeg-pixels)
         else if (!std::strcmp(argv[i], "--color-from-file")) MJX_OPTS_COLOR(&opts) = MJX_COLOR_FILE;
         else if (!std::strcmp(argv[i], "--progressive")) MJX_OPTS_PROGRESSIVE(&opts) = 1;
         else if (!std::strcmp(argv[i], "--scale")) {

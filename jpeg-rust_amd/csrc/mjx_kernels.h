@@ -169,8 +169,32 @@ struct DevImage {
     // kLjRepOn | bit c per replicated component | kLjRepLuma for a luminance picture.  Such a picture has lj_on = lj_luma = 0 and is
     // k_upsample_rep's; lj_out says where it leaves as for k_upsample_color.
     uint32_t lj_rep;
+    // ... at a reduced scale (scale 2, 4 or 8 with MJX_IDCT_ISLOW; kSinkPlanesRed): libjpeg picks a transform size N_c per component
+    // (jdmaster.c; red_size below), so component c's plane holds N_c samples per block side -- rows of lj_stride[c] bytes (mcux * N_c * ch[c]
+    // rounded up to 8), mcuy * N_c * cv[c] of them -- and is upsampled by (hmax m / (ch N_c), vmax m / (cv N_c)), m = 8 / scale.  lj_red != 0:
+    // kLjRedOn | kLjRedLuma for a luminance picture | per component c, from bit 4 c on: log2 N_c in two bits and the replicate bit (a
+    // narrow plane as lj_rep; every component at 1/8).  Such a picture has lj_on = lj_luma = lj_rep = 0 and is k_upsample_red's.
+    uint32_t lj_red;
 };
 constexpr uint32_t kLjRepOn = 16u, kLjRepLuma = 32u;
+constexpr uint32_t kLjRedOn = 1u << 31, kLjRedLuma = 1u << 30;
+MJX_HD constexpr uint32_t lj_red_n(uint32_t word, uint32_t c) { return 1u << (word >> (4u * c) & 3u); }
+MJX_HD constexpr uint32_t lj_red_rep(uint32_t word, uint32_t c) { return word >> (4u * c + 2u) & 1u; }
+// Component (hc, vc) of maxima (hmax, vmax) in a W x H picture at scale 8 / m with a transform of size n: its plane's samples and its
+// upsampling ratios.  The planner and mjx_plan_reduced run this routine; k_upsample_red states the same arithmetic on the descriptor.
+struct RedPlane { uint32_t cw, ch, rh, rv; };
+MJX_HD constexpr RedPlane red_plane(uint32_t W, uint32_t H, uint32_t hc, uint32_t vc, uint32_t hmax, uint32_t vmax, uint32_t m, uint32_t n)
+{
+    return RedPlane{(W * hc * n + hmax * 8u - 1u) / (hmax * 8u), (H * vc * n + vmax * 8u - 1u) / (vmax * 8u), hmax * m / (hc * n), vmax * m / (vc * n)};
+}
+// jdmaster.c's rule for the transform size of a component with factors (hc, vc) of maxima (hmax, vmax) at scale 8 / m: from m, doubled
+// while it stays below 8 and the doubled size still divides the MCU's scaled extent in BOTH directions -- one size for both.
+MJX_HD constexpr uint32_t red_size(uint32_t m, uint32_t hc, uint32_t vc, uint32_t hmax, uint32_t vmax)
+{
+    uint32_t n = m;
+    while (n < 8u && (hmax * m) % (hc * n * 2u) == 0u && (vmax * m) % (vc * n * 2u) == 0u) n *= 2u;
+    return n;
+}
 // DevImage::model
 enum ColorModel : uint32_t {
     kModelPositional = 0,   // grey, or Y, Cb, Cr by position: the pixel phase as it has always been
@@ -201,8 +225,9 @@ enum StageBSink : uint32_t {
     kSinkLuma = 4,          // luminance: component 0 alone, one element per pixel
     kSinkYcc = 5,           // YCbCr output: the component planes as the picture (4:2:0 takes kFormGeneric)
     kSinkPlanesInt = 6,     // libjpeg's pixels with its integer inverse DCT (MJX_IDCT_ISLOW): kSinkPlanes on an int32 tile, kFormGeneric only
+    kSinkPlanesRed = 7,     // ... at scale 2, 4 or 8: libjpeg's reduced integer transforms, a size per component (k_upsample_red follows), kFormGeneric only
 };
-constexpr uint32_t kStageBSinks = 7;
+constexpr uint32_t kStageBSinks = 8;
 MJX_HD constexpr uint32_t stage_b_mode(uint32_t form, uint32_t sink) { return form | sink << 3; }
 MJX_HD constexpr StageBForm form_of(uint32_t mode) { return StageBForm(mode & 7u); }
 MJX_HD constexpr StageBSink sink_of(uint32_t mode) { return StageBSink(mode >> 3); }
@@ -231,10 +256,13 @@ enum StageBDensity : uint32_t { kAnyDensity = 0, kSparse = 1, kDense = 2 };
 // The forms of the integer inverse DCT (MJX_IDCT_ISLOW): a list of their own behind the one above, which stays what it was -- the
 // modes stage_b_choice gave before the option existed.  MJX_STAGE_B_ALL is what configure_kernels and launch_idct_color are generated from.
 #define MJX_STAGE_B_KERNELS_ISLOW(X) MJX_STAGE_B_SOURCES(X, kFormGeneric, kSinkPlanesInt)
-#define MJX_STAGE_B_ALL(X) MJX_STAGE_B_KERNELS(X) MJX_STAGE_B_KERNELS_ISLOW(X)
+// ... and of its reduced transforms (MJX_IDCT_ISLOW with a scale): again a list of their own, so that neither count above moves.
+#define MJX_STAGE_B_KERNELS_ISLOW_RED(X) MJX_STAGE_B_SOURCES(X, kFormGeneric, kSinkPlanesRed)
+#define MJX_STAGE_B_ALL(X) MJX_STAGE_B_KERNELS(X) MJX_STAGE_B_KERNELS_ISLOW(X) MJX_STAGE_B_KERNELS_ISLOW_RED(X)
 #define MJX_STAGE_B_COUNT(F, S, PF, SRC, LAYOUT, DENSITY) +1
 static_assert(0 MJX_STAGE_B_KERNELS(MJX_STAGE_B_COUNT) == 64, "16 packed kernels + 48 of the other sinks (DESIGN.md s3.2)");
 static_assert(0 MJX_STAGE_B_KERNELS_ISLOW(MJX_STAGE_B_COUNT) == 3, "the integer inverse DCT: the generic form on the three stream sources");
+static_assert(0 MJX_STAGE_B_KERNELS_ISLOW_RED(MJX_STAGE_B_COUNT) == 3, "the reduced integer transforms: one form for 1/2, 1/4 and 1/8 on the three stream sources");
 #undef MJX_STAGE_B_COUNT
 
 // DevImage::or_on: the pass behind stage B that brings an oriented (or resized, one-channel) picture to the form it leaves in
@@ -581,6 +609,93 @@ MJX_UNROLL
         islow_st4(blk + v * 8u, r[0], r[1], r[2], r[3]);
         islow_st4(blk + v * 8u + 4u, r[4], r[5], r[6], r[7]);
     }
+}
+// ---- ... at reduced scales: jidctred.c's 4x4, 2x2 and 1x1 transforms (include/mjx.h states the contract) ------------------------
+// R4 of the contract: d[0 .. 7] of one column or row (d[4] is never read) -> four outputs in d[0 .. 3], descaled by n
+MJX_HD void islow_red4_pass(uint32_t d[8], uint32_t n)
+{
+    constexpr uint32_t F0_211 = 1730u, F0_509 = 4176u, F0_601 = 4926u, F0_765 = 6270u, F0_899 = 7373u, F1_061 = 8697u, F1_451 = 11893u,
+                       F1_847 = 15137u, F2_172 = 17799u, F2_562 = 20995u;
+    const uint32_t t0 = d[0] << (kIslowBits + 1u);
+    const uint32_t t2 = d[2] * F1_847 - d[6] * F0_765;
+    const uint32_t t10 = t0 + t2, t12 = t0 - t2;
+    const uint32_t z1 = d[7], z2 = d[5], z3 = d[3], z4 = d[1];
+    const uint32_t a = z2 * F1_451 - z1 * F0_211 - z3 * F2_172 + z4 * F1_061;
+    const uint32_t b = z3 * F0_899 - z1 * F0_509 - z2 * F0_601 + z4 * F2_562;
+    d[0] = islow_descale(t10 + b, n); d[3] = islow_descale(t10 - b, n);
+    d[1] = islow_descale(t12 + a, n); d[2] = islow_descale(t12 - a, n);
+}
+// R2: d[0], d[1], d[3], d[5], d[7] -> two outputs in d[0 .. 1]
+MJX_HD void islow_red2_pass(uint32_t d[8], uint32_t n)
+{
+    constexpr uint32_t F0_720 = 5906u, F0_850 = 6967u, F1_272 = 10426u, F3_624 = 29692u;
+    const uint32_t t10 = d[0] << (kIslowBits + 2u);
+    const uint32_t t0 = d[5] * F0_850 - d[7] * F0_720 - d[3] * F1_272 + d[1] * F3_624;
+    d[0] = islow_descale(t10 + t0, n); d[1] = islow_descale(t10 - t0, n);
+}
+// One lane = one block, in place as idct_islow_inplace: blk[v * 8 + u] = coef[v][u] q[v][u] on entry; on exit output (y, x), x, y < N,
+// lies at blk[y * 8 + x] (the sample is islow_sample of it) and the rest of the block holds leftovers.  16 bytes per access.
+// N = 4: pass 1 on every column but 4 over rows 0 .. 3, 5 .. 7 (four columns at a time; row 4 is not loaded), pass 2 on rows 0 .. 3.
+MJX_HD void idct_red4_inplace(uint32_t *blk)
+{
+MJX_UNROLL
+    for (uint32_t h = 0; h < 2u; h++) {
+        uint32_t c[4][8];
+MJX_UNROLL
+        for (uint32_t v = 0; v < 8u; v++) {
+            if (v == 4u) { c[0][v] = c[1][v] = c[2][v] = c[3][v] = 0u; continue; }
+            const IslowQuad t = islow_ld4(blk + v * 8u + h * 4u);
+            c[0][v] = t.x; c[1][v] = t.y; c[2][v] = t.z; c[3][v] = t.w;
+        }
+MJX_UNROLL
+        for (uint32_t k = 0; k < 4u; k++)
+            if (h * 4u + k != 4u) islow_red4_pass(c[k], kIslowBits - kIslowPass1 + 1u);        // (column 4: pass 2 never reads it)
+MJX_UNROLL
+        for (uint32_t v = 0; v < 4u; v++) islow_st4(blk + v * 8u + h * 4u, c[0][v], c[1][v], c[2][v], c[3][v]);
+    }
+MJX_UNROLL
+    for (uint32_t v = 0; v < 4u; v++) {
+        const IslowQuad lo = islow_ld4(blk + v * 8u), hi = islow_ld4(blk + v * 8u + 4u);
+        uint32_t r[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        islow_red4_pass(r, kIslowBits + kIslowPass1 + 3u + 1u);
+        islow_st4(blk + v * 8u, r[0], r[1], r[2], r[3]);
+    }
+}
+// N = 2: pass 1 on columns 0, 1, 3, 5, 7 over rows 0, 1, 3, 5, 7, pass 2 on rows 0 and 1.
+MJX_HD void idct_red2_inplace(uint32_t *blk)
+{
+MJX_UNROLL
+    for (uint32_t h = 0; h < 2u; h++) {
+        uint32_t c[4][8];
+MJX_UNROLL
+        for (uint32_t v = 0; v < 8u; v++) {
+            if (v != 0u && !(v & 1u)) { c[0][v] = c[1][v] = c[2][v] = c[3][v] = 0u; continue; }
+            const IslowQuad t = islow_ld4(blk + v * 8u + h * 4u);
+            c[0][v] = t.x; c[1][v] = t.y; c[2][v] = t.z; c[3][v] = t.w;
+        }
+MJX_UNROLL
+        for (uint32_t k = 0; k < 4u; k++)
+            if (h * 4u + k == 0u || ((h * 4u + k) & 1u)) islow_red2_pass(c[k], kIslowBits - kIslowPass1 + 2u);
+MJX_UNROLL
+        for (uint32_t v = 0; v < 2u; v++) islow_st4(blk + v * 8u + h * 4u, c[0][v], c[1][v], c[2][v], c[3][v]);
+    }
+MJX_UNROLL
+    for (uint32_t v = 0; v < 2u; v++) {
+        const IslowQuad lo = islow_ld4(blk + v * 8u), hi = islow_ld4(blk + v * 8u + 4u);
+        uint32_t r[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        islow_red2_pass(r, kIslowBits + kIslowPass1 + 3u + 2u);
+        islow_st4(blk + v * 8u, r[0], r[1], r[2], r[3]);
+    }
+}
+// N = 1: the DC term alone, descaled by 3
+MJX_HD void idct_red1(uint32_t *blk) { blk[0] = islow_descale(blk[0], 3u); }
+// the block's transform by its component's size N (8: the full one)
+MJX_HD void idct_reduced_inplace(uint32_t *blk, uint32_t N)
+{
+    if (N == 8u) idct_islow_inplace(blk);
+    else if (N == 4u) idct_red4_inplace(blk);
+    else if (N == 2u) idct_red2_inplace(blk);
+    else idct_red1(blk);
 }
 // the sample of pass 2's output x: clamp(x + 128, 0, 255) -- it saturates (|x| < 2^14 after the shift by 18: the sum cannot wrap)
 MJX_HD uint32_t islow_sample(uint32_t x)
@@ -1173,6 +1288,9 @@ void launch_upsample_color(hipStream_t st, uint32_t max_tiles, uint32_t nimg, co
                            const uint32_t *img_flags, bool luma = false /* k_upsample_luma: pictures with DevImage::lj_luma */);
 // ... k_upsample_rep: pictures with DevImage::lj_rep (the integer inverse DCT's planes of at most two columns, replicated)
 void launch_upsample_rep(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
+                         const uint32_t *img_flags);
+// ... k_upsample_red: pictures with DevImage::lj_red (the integer inverse DCT at a reduced scale)
+void launch_upsample_red(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
                          const uint32_t *img_flags);
 #endif
 

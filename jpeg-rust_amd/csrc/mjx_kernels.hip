@@ -3238,10 +3238,10 @@ __device__ __forceinline__ uint32_t comp_of_block(uint32_t b, const uint8_t *s_c
     return s_comp[b];
 }
 
-template <int MODE, int N, bool LUMA = false, bool INT = false>
+template <int MODE, int N, bool LUMA = false, int INT = 0>
 __device__ __forceinline__ void scatter_at(const uint32_t *ent, const uint32_t *b, uint32_t nblk, float *tile_f,
                                            const float *s_qm, const uint8_t *s_nat, const uint8_t *s_comp);
-template <int MODE, int N, bool LUMA = false, bool INT = false>
+template <int MODE, int N, bool LUMA = false, int INT = 0>
 __device__ __forceinline__ void scatter_batch(const uint32_t *ent, uint32_t first_lo, uint32_t nblk, float *tile_f,
                                               const float *s_qm, const uint8_t *s_nat, const uint8_t *s_comp)
 {
@@ -3252,7 +3252,7 @@ __device__ __forceinline__ void scatter_batch(const uint32_t *ent, uint32_t firs
 }
 // (b[k]: the block slot of entry k in the tile; anything >= nblk is dropped.  LUMA: so is an entry of a block that is not component 0's.
 // INT, the integer inverse DCT's tile: s_qm holds the raw DQT entries as uint32 and the word stored is coefficient x entry, wrapping)
-template <int MODE, int N, bool LUMA, bool INT>
+template <int MODE, int N, bool LUMA, int INT>
 __device__ __forceinline__ void scatter_at(const uint32_t *ent, const uint32_t *b, uint32_t nblk, float *tile_f,
                                            const float *s_qm, const uint8_t *s_nat, const uint8_t *s_comp)
 {
@@ -3427,7 +3427,7 @@ __device__ __forceinline__ uint32_t planar_block(uint32_t e, uint32_t how, uint3
     const uint32_t l = how >> 24, fm = jb >> l;                   // its MCU of the picture, counted from the piece's first
     return min(((how >> 8) & 0xffu) + ((how >> 16) & 0xffu) + fm * bpm + (jb - (fm << l)), 255u);
 }
-template <int MODE, int N, bool LUMA = false, bool INT = false>
+template <int MODE, int N, bool LUMA = false, int INT = 0>
 __device__ __forceinline__ void scatter_planar(const uint32_t *ent, const PlanarTile &t, uint32_t bpm, uint32_t nblk, float *tile_f,
                                                const float *s_qm, const uint8_t *s_nat, const uint8_t *s_comp)
 {
@@ -3886,6 +3886,46 @@ __device__ __forceinline__ void planes_store(const DevImage &im, const float *ti
     }
 }
 
+// ... of the reduced integer transforms (kSinkPlanesRed): the block of component c left N_c x N_c outputs, row y at words y * 8 .. y * 8 +
+// N_c - 1 of its tile row, and the plane holds N_c samples per block side at its own stride.  The lane-to-row map is planes_store's -- a
+// lane per row of a block, rows from N_c on idle --, the store is 8, 4, 2 or 1 byte wide.
+__device__ __forceinline__ void planes_store_red(const DevImage &im, const uint32_t *tile, uint32_t m0, uint32_t nblk, uint32_t bpm, uint32_t mcux,
+                                                 uint8_t *pl, uint32_t red)
+{
+    const uint32_t tid = threadIdx.x, r = tid & 7u;
+    const uint32_t t_inc = 32u / bpm, b_inc = 32u - t_inc * bpm;
+    const uint32_t my0 = m0 / mcux, mx0 = m0 - my0 * mcux;
+    uint32_t t = (tid >> 3) / bpm, b = (tid >> 3) - t * bpm;
+    for (uint32_t blk = tid >> 3; blk < nblk; blk += 32u, t += t_inc, b += b_inc) {
+        if (b >= bpm) { b -= bpm; t++; }
+        uint32_t mx = mx0 + t, my = my0;
+        if (mx >= mcux) {
+            mx -= mcux; my++;
+            if (mx >= mcux) { const uint32_t q = mx / mcux; my += q; mx -= q * mcux; }
+        }
+        const uint32_t c = im.blk_comp[b], n = lj_red_n(red, c);
+        if (r >= n) continue;
+        const uint32_t bx = mx * im.ch[c] + im.blk_bx[b], by = my * im.cv[c] + im.blk_by[b];
+        uint8_t *dst = pl + im.lj_off[c] + (size_t(by) * n + r) * im.lj_stride[c] + bx * n;
+        const uint32_t *src = tile + blk * kPixStride + r * 8;
+        if (n == 8u) {
+            const uint4 lo = *reinterpret_cast<const uint4 *>(src), hi = *reinterpret_cast<const uint4 *>(src + 4);
+            uint2 w;
+            w.x = islow_sample(lo.x) | islow_sample(lo.y) << 8 | islow_sample(lo.z) << 16 | islow_sample(lo.w) << 24;
+            w.y = islow_sample(hi.x) | islow_sample(hi.y) << 8 | islow_sample(hi.z) << 16 | islow_sample(hi.w) << 24;
+            *reinterpret_cast<uint2 *>(dst) = w;
+        } else if (n == 4u) {
+            const uint4 lo = *reinterpret_cast<const uint4 *>(src);
+            *reinterpret_cast<uint32_t *>(dst) = islow_sample(lo.x) | islow_sample(lo.y) << 8 | islow_sample(lo.z) << 16 | islow_sample(lo.w) << 24;
+        } else if (n == 2u) {
+            const uint2 lo = *reinterpret_cast<const uint2 *>(src);
+            *reinterpret_cast<uint16_t *>(dst) = uint16_t(islow_sample(lo.x) | islow_sample(lo.y) << 8);
+        } else {
+            *dst = uint8_t(islow_sample(src[0]));
+        }
+    }
+}
+
 // ---- YCbCr output (mjx_planes; k_idct_color's kSinkYcc forms; DevImage::ycc_*) -------------------------------------------------
 // One element of a plane: byte value `u` through the dtype's table (DT: MJX_DTYPE_*, a template argument -- chosen once per tile).
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -4303,6 +4343,9 @@ __device__ __forceinline__ void pixels_scaled_luma(const GenShape &g, const floa
 //   PLANESI  ... with libjpeg's integer slow inverse DCT (kSinkPlanesInt, MJX_IDCT_ISLOW): PLANES with the tile held as int32 at the same
 //        stride -- phase 1 scatters coefficient x raw DQT entry in natural order (the scatter routines' INT flag), the DC term is dc x
 //        entry with no level shift, phase 2 is idct_islow_inplace (mjx_kernels.h, the routine the host runs), phase 3 planes_store<true>
+//   PLANESR  ... at scale 2, 4 or 8 (kSinkPlanesRed): PLANESI's phases 0 and 1 as they are -- all 64 positions, the reduced transforms read
+//        rows and columns up to 7 --, phase 2 the block's transform by its component's size N_c (DevImage::lj_red; idct_reduced_inplace:
+//        one branch, the blocks of an MCU differ), phase 3 planes_store_red
 //   OUT  output formats (kSinkOut, the sink of a picture with an output description): the ROI form -- a picture without a
 //        rectangle is its own whole rectangle --, phase 3 writing the picture's format (store4_out, DevImage::out_*)
 //   YCC  YCbCr output (kSinkYcc, MODE 0, 3, 4; mjx_planes): the ROI form with one difference in phases 1-2 -- every
@@ -4326,7 +4369,10 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     constexpr bool YCC = SINK == kSinkYcc;                    // YCbCr output: the cropped form, phase 3 storing the component planes as the picture
     constexpr bool LUMA = SINK == kSinkLuma;                  // luminance output: the cropped form, component 0 alone
     constexpr bool PLANES = SINK == kSinkPlanes;              // libjpeg's pixels: the cropped form again, phase 3 storing component planes
-    constexpr bool PLANESI = SINK == kSinkPlanesInt;          // ... with libjpeg's integer inverse DCT: the tile holds int32, phases 1-3 in integers
+    constexpr bool PLANESR = SINK == kSinkPlanesRed;          // ... at a reduced scale: the transform's size by the block's component
+    constexpr bool PLANESI = SINK == kSinkPlanesInt || PLANESR;   // ... with libjpeg's integer inverse DCT: the tile holds int32, phases 1-3 in integers
+    constexpr int INTK = PLANESR ? 2 : PLANESI ? 1 : 0;       // the scatter routines' INT flag (2 is 1: instantiations of its own for the reduced form,
+                                                              // so that the existing kernels compile to what they were)
     constexpr bool OUT = SINK == kSinkOut;                    // output formats: the cropped form, the picture its own whole rectangle without one
     constexpr bool ROI = SINK != kSinkPacked;                 // every sink but the packed whole picture walks and writes a rectangle
     static_assert(uint32_t(MODE_) == stage_b_mode(MODE, SINK) && SINK < kStageBSinks && MODE <= int(kFormQuarter), "a mode of MJX_STAGE_B_ALL");
@@ -4480,6 +4526,9 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     // and the DC term is dc x entry alone: the level shift is islow_sample's)
     uint32_t my_dc_qi = 0u;
     if constexpr (PLANESI) my_dc_qi = reinterpret_cast<const uint32_t *>(qmult)[im.qm_off + my_comp * 64];
+    // (a reduced scale: the descriptor word and the size of the lane's own block's transform -- the same in every tile, as my_comp)
+    uint32_t red_word = 0u, my_red_n = 8u;
+    if constexpr (PLANESR) { red_word = im.lj_red; my_red_n = lj_red_n(red_word, my_comp); }
     float *tile_f = reinterpret_cast<float *>(smem_px);
     GenShape gshape{};
     if (MODE == 0 || SCALED) gshape = gen_shape(im);
@@ -4492,6 +4541,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
     // back edge.  Round 6: found in the ISA; it was a store drain per tile and wave right behind the pixel phase.)
     asm volatile("" : "+v"(my_dc_qm), "+v"(my_dc_add));
     if constexpr (PLANESI) asm volatile("" : "+v"(my_dc_qi));
+    if constexpr (PLANESR) asm volatile("" : "+v"(my_red_n));
     if (!M420) asm volatile("" :: "v"(gshape.width));
 
 #ifdef MJX_STAMP_B
@@ -4549,9 +4599,9 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             if constexpr (PLANAR) {
                 // as many rounds as the tile has -- a uniform choice between a few batch sizes, as for the linear stream below
                 const PlanarTile &pt = s_ptile[tile % 3u];
-                if (__builtin_amdgcn_readfirstlane(pt.rnd[4].cnt) == 0) scatter_planar<MODE, 4, LUMA, PLANESI>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
-                else if (__builtin_amdgcn_readfirstlane(pt.rnd[6].cnt) == 0) scatter_planar<MODE, 6, LUMA, PLANESI>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
-                else scatter_planar<MODE, 8, LUMA, PLANESI>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
+                if (__builtin_amdgcn_readfirstlane(pt.rnd[4].cnt) == 0) scatter_planar<MODE, 4, LUMA, INTK>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
+                else if (__builtin_amdgcn_readfirstlane(pt.rnd[6].cnt) == 0) scatter_planar<MODE, 6, LUMA, INTK>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
+                else scatter_planar<MODE, 8, LUMA, INTK>(cur.ent, pt, bpm, nblk, tile_f, s_qm, s_nat, s_comp);
                 // what the tile has beyond the prefetched rounds (dense streams)
                 for (uint32_t j = pt.rest_seg, r0 = pt.rest_rnd; j < kPlanarSegs; j++, r0 = 0) {
                     const uint32_t rel = s_kind[j >= nk ? j - nk : j].ent_rel + pt.start[j], len = pt.len[j], how = pt.how[j];
@@ -4559,7 +4609,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                         uint32_t e1[1], b1[1];
                         e1[0] = i0 + tid < len ? psrc[rel + i0 + tid] : 0u;
                         b1[0] = planar_block(e1[0], how, bpm);
-                        scatter_at<MODE, 1, LUMA, PLANESI>(e1, b1, nblk, tile_f, s_qm, s_nat, s_comp);
+                        scatter_at<MODE, 1, LUMA, INTK>(e1, b1, nblk, tile_f, s_qm, s_nat, s_comp);
                     }
                 }
             } else if constexpr (QUAD) {
@@ -4569,14 +4619,14 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                     if (cur.ncells > wave0 + LANES * r) {                                    // uniform over the wave
                         quad_mask(cur.ent[r], cur.k_lo[r], cur.k_hi[r]);
                         // (the labels of the group's entries + its subsequence's label offset = the blocks' indices in the picture, mod 256)
-                        scatter_batch<MODE, 8, LUMA, PLANESI>(cur.ent[r], first_lo - cur.lab[r], nblk, tile_f, s_qm, s_nat, s_comp);
+                        scatter_batch<MODE, 8, LUMA, INTK>(cur.ent[r], first_lo - cur.lab[r], nblk, tile_f, s_qm, s_nat, s_comp);
                     }
                 }
                 for (uint32_t h0 = LANES * QR; h0 < cur.ncells; h0 += LANES) {
                     uint32_t more[8], k_lo, k_hi, lab;
                     quad_load(src, qv, tile - tile0, h0 + tid, more, k_lo, k_hi, lab);
                     quad_mask(more, k_lo, k_hi);
-                    scatter_batch<MODE, 8, LUMA, PLANESI>(more, first_lo - lab, nblk, tile_f, s_qm, s_nat, s_comp);
+                    scatter_batch<MODE, 8, LUMA, INTK>(more, first_lo - lab, nblk, tile_f, s_qm, s_nat, s_comp);
                 }
             } else {
                 // The prefetched words the wave really has (a tile of the bench content holds ~1500 entries, 5.9 per lane; at quality
@@ -4585,10 +4635,10 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                 // fetched as 0: null entries.)
                 const uint32_t have = cur.e1 - cur.e0;
                 const uint32_t slots = have > wave0 ? (have - wave0 + LANES - 1) / LANES : 0u;      // uniform over the wave
-                if (slots <= 4) scatter_batch<MODE, 4, LUMA, PLANESI>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
-                else if (slots <= 6) scatter_batch<MODE, 6, LUMA, PLANESI>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
-                else if (slots <= 8 || PF == 8) scatter_batch<MODE, 8, LUMA, PLANESI>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
-                else if (PF > 8) scatter_batch<MODE, PF, LUMA, PLANESI>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                if (slots <= 4) scatter_batch<MODE, 4, LUMA, INTK>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                else if (slots <= 6) scatter_batch<MODE, 6, LUMA, INTK>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                else if (slots <= 8 || PF == 8) scatter_batch<MODE, 8, LUMA, INTK>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                else if (PF > 8) scatter_batch<MODE, PF, LUMA, INTK>(cur.ent, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
                 for (uint32_t i0 = cur.e0 + LANES * PF; i0 < cur.e1; i0 += LANES * 4) {     // what a dense tile has beyond the prefetched words
                     uint32_t more[4];
 #pragma unroll
@@ -4596,7 +4646,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
                         const uint32_t i = i0 + tid + LANES * k;
                         more[k] = i < cur.e1 ? src[i] : 0u;
                     }
-                    scatter_batch<MODE, 4, LUMA, PLANESI>(more, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
+                    scatter_batch<MODE, 4, LUMA, INTK>(more, first_lo, nblk, tile_f, s_qm, s_nat, s_comp);
                 }
             }
             // DC; luminance blocks also take the + 128 of decoder.rs:318-330 here (a constant on the DC term of the
@@ -4616,7 +4666,8 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
         if constexpr (SCALED) {
             if (tid < nblk && (!LUMA || my_comp == 0u)) idct_scaled_inplace<scaled_n<MODE>()>(tile_f + tid * kPixStride);
         } else if constexpr (PLANESI) {
-            if (tid < nblk) idct_islow_inplace(reinterpret_cast<uint32_t *>(tile_f) + tid * kPixStride);
+            if constexpr (PLANESR) { if (tid < nblk) idct_reduced_inplace(reinterpret_cast<uint32_t *>(tile_f) + tid * kPixStride, my_red_n); }
+            else if (tid < nblk) idct_islow_inplace(reinterpret_cast<uint32_t *>(tile_f) + tid * kPixStride);
         } else if (tid < nblk && (!LUMA || my_comp == 0u)) idct_row_inplace(tile_f + tid * kPixStride);
         MJX_SB(4);
         __syncthreads();
@@ -4661,6 +4712,7 @@ __global__ __launch_bounds__(256) void k_idct_color(const DevImage *__restrict__
             if constexpr (YCC) planes_out_store<8u>(ycc_pl, gshape.ncomp, log2T, tile_f, m0, nm, bpm, mcux);
             else if constexpr (LUMA) pixels_generic_luma(gshape, tile_f, m0, nm, roi, ofmt);
             else if constexpr (PLANES) planes_store(im, tile_f, m0, nblk, bpm, mcux, reinterpret_cast<uint8_t *>(planes + im.plane_off));
+            else if constexpr (PLANESR) planes_store_red(im, reinterpret_cast<const uint32_t *>(tile_f), m0, nblk, bpm, mcux, reinterpret_cast<uint8_t *>(planes + im.plane_off), red_word);
             else if constexpr (PLANESI) planes_store<true>(im, tile_f, m0, nblk, bpm, mcux, reinterpret_cast<uint8_t *>(planes + im.plane_off));
             else if constexpr (OUT) pixels_generic_out(gshape, tile_f, m0, nm, roi, ofmt);
             else if constexpr (ROI) pixels_generic_roi(gshape, tile_f, m0, nm, out_img, aligned, roi);
@@ -5517,6 +5569,55 @@ __global__ __launch_bounds__(256) void k_upsample_rep(const DevImage *__restrict
     }
 }
 
+// ... a picture of the integer inverse DCT at a reduced scale (DevImage::lj_red): k_upsample_rep's kernel on the scaled geometry -- the
+// picture is out_w x out_h, component k's plane holds ceil(W ch N_k / (8 hmax)) x ceil(H cv N_k / (8 vmax)) samples and is upsampled by
+// (hmax m / (ch N_k), vmax m / (cv N_k)), m = 8 / scale, replicated where its bit says so (every component at 1/8).
+__global__ __launch_bounds__(256) void k_upsample_red(const DevImage *__restrict__ images, const uint8_t *__restrict__ planes,
+                                                       uint8_t *__restrict__ rgb, const uint32_t *__restrict__ img_flags)
+{
+    const DevImage &im = images[blockIdx.y];
+    if (!im.valid || !im.lj_red || im.role == 1u || img_flags[im.status_idx]) return;
+    const Roi roi{im.roi_x, im.roi_y, im.roi_w, im.roi_h};
+    const uint32_t xb = roi.x & ~(kLjStrip - 1u), tiles_x = (roi.x - xb + roi.w + kLjTileW - 1u) / kLjTileW;
+    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    if (ty * kLjTileH >= roi.h) return;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t px = xb + tx * kLjTileW + (tid & 63u) * kLjStrip;
+    if (px >= roi.x + roi.w) return;
+    const uint32_t width = im.out_w, ncomp = im.ncomp, hmax = im.hmax, vmax = im.vmax, red = im.lj_red, m = 8u / im.scale;
+    const uint8_t *base = planes + im.plane_off * 8u;
+    LjPlane pl[3];
+#pragma unroll
+    for (uint32_t c = 0; c < 3; c++) {
+        const uint32_t k = c < ncomp ? c : 0u, n = lj_red_n(red, k);
+        pl[c] = LjPlane{base + im.lj_off[k], im.lj_stride[k], (im.width * im.ch[k] * n + hmax * 8u - 1u) / (hmax * 8u),
+                        (im.height * im.cv[k] * n + vmax * 8u - 1u) / (vmax * 8u), hmax * m / (im.ch[k] * n), vmax * m / (im.cv[k] * n),
+                        lj_red_rep(red, k)};
+    }
+    const bool luma = (red & kLjRedLuma) != 0u, fmt = im.lj_out != 0u;
+    OutFmt of{};
+    if (luma) of = luma_fmt(im, rgb);
+    else if (fmt) of = out_fmt(im, rgb);
+    uint8_t *out_img = rgb + im.rgb_off;
+    uint32_t w[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll 1
+    for (uint32_t it = 0; it < 2u * (kLjTileH / 4u); it++) {
+        const uint32_t py = roi.y + ty * kLjTileH + (tid >> 6) + 4u * (it >> 1), half = it & 1u;
+        if (py >= roi.y + roi.h) break;
+        if (!half) {
+            if (luma) lj_luma8(pl[0], px, py, w);
+            else lj_pixels8(pl, ncomp, px, py, w);
+        }
+        const uint32_t x4 = px + 4u * half;
+        if (x4 >= width) continue;
+        const uint32_t npix = min(4u, width - x4);
+        if (luma) { store4_luma(of, roi, x4, py, half ? w[1] : w[0], npix); continue; }
+        const Rgb4 v = half ? Rgb4{w[3], w[4], w[5]} : Rgb4{w[0], w[1], w[2]};
+        if (fmt) store4_out(of, roi, x4, py, v, npix);
+        else store4_roi(out_img, roi, x4, py, v, npix);
+    }
+}
+
 // ---- verification helper: byte-wise comparison of decoded pictures on the device ------------------------------
 // (mjx_batch_compare_rgb: the parity gate of bench.py and the batch-scale tests compare tens of gigabytes of output
 // without copying them to the host.)  One workgroup per 16 KiB of a pair; per pair the largest absolute byte
@@ -5860,6 +5961,13 @@ void launch_upsample_rep(hipStream_t st, uint32_t max_tiles, uint32_t nimg, cons
 {
     if (max_tiles == 0 || nimg == 0) return;
     hipLaunchKernelGGL(k_upsample_rep, dim3(max_tiles, nimg), dim3(256), 0, st, images, planes, rgb, img_flags);
+}
+
+void launch_upsample_red(hipStream_t st, uint32_t max_tiles, uint32_t nimg, const DevImage *images, const uint8_t *planes, uint8_t *rgb,
+                         const uint32_t *img_flags)
+{
+    if (max_tiles == 0 || nimg == 0) return;
+    hipLaunchKernelGGL(k_upsample_red, dim3(max_tiles, nimg), dim3(256), 0, st, images, planes, rgb, img_flags);
 }
 
 void launch_dc_color(hipStream_t st, uint32_t max_pixel_wgs, uint32_t nimg, const DevImage *images, const int32_t *dcbuf,

@@ -293,10 +293,15 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     if (scale != 1 && scale != 2 && scale != 4 && scale != 8) return fail(MJX_ERR_INVALID_ARG);
     if (scale != 1 && opts.layout == MJX_LAYOUT_REF_COMPAT) return fail(MJX_ERR_INVALID_ARG);    // (the reference has no scaled decode)
     p.scale = scale;
-    // libjpeg's pixels: STANDARD layout at full size only (a scan of a multi-scan file has no pixels: its picture's plan carries the option)
+    // libjpeg's pixels: STANDARD layout, at full size unless the inverse DCT is libjpeg's too and the call opts into its reduced transforms
+    // (MJX_OPTS_EXACT_SCALE: without that byte a scale stays refused, as before the byte existed; a scan of a multi-scan file has no
+    // pixels: its picture's plan carries the option)
     if (opts.pixels > MJX_PIXELS_LIBJPEG) return fail(MJX_ERR_INVALID_ARG);
     const bool lj = opts.pixels == MJX_PIXELS_LIBJPEG && !scan_part;
-    if (lj && (scale != 1 || opts.layout == MJX_LAYOUT_REF_COMPAT || opts.strict_ref)) return fail(MJX_ERR_INVALID_ARG);
+    if (MJX_OPTS_EXACT_SCALE(&opts) > 1) return fail(MJX_ERR_INVALID_ARG);
+    const bool exact_scale = MJX_OPTS_EXACT_SCALE(&opts) == 1;
+    if (exact_scale && (opts.pixels != MJX_PIXELS_LIBJPEG || MJX_OPTS_IDCT(&opts) != MJX_IDCT_ISLOW)) return fail(MJX_ERR_INVALID_ARG);
+    if (lj && ((scale != 1 && !exact_scale) || opts.layout == MJX_LAYOUT_REF_COMPAT || opts.strict_ref)) return fail(MJX_ERR_INVALID_ARG);
     // libjpeg's integer inverse DCT: with its pixels only
     if (MJX_OPTS_IDCT(&opts) > MJX_IDCT_ISLOW) return fail(MJX_ERR_INVALID_ARG);
     if (MJX_OPTS_IDCT(&opts) == MJX_IDCT_ISLOW && opts.pixels != MJX_PIXELS_LIBJPEG) return fail(MJX_ERR_INVALID_ARG);
@@ -397,19 +402,31 @@ int plan_image(const mjx_scan_desc &d, const mjx_opts &opts, ImagePlan &p, bool 
     }
     {
         const uint32_t pw = 8 / scale * p.hmax, ph = 8 / scale * p.vmax;      // an MCU's patch of the output picture
-        // (libjpeg's pixels: the rectangle grown by the filter's reach -- a pixel's chroma neighbours lie up to hmax x vmax pixels away)
-        const uint32_t gx = lj && p.hmax > 1 ? p.hmax : 0u, gy = lj && p.vmax > 1 ? p.vmax : 0u;
+        p.lj = lj;
+        p.islow = islow;
+        // (jdsample.c takes its triangle filters for downsampled_width > 2 only: a narrower plane of ratios (2, 1) or (2, 2) is replicated)
+        for (uint32_t c = 0; islow && scale == 1 && c < p.ncomp; c++) {
+            const uint32_t cw = (p.width * p.h[c] + p.hmax - 1) / p.hmax, rh = p.hmax / p.h[c], rv = p.vmax / p.v[c];
+            if (cw <= 2 && rh == 2 && (rv == 1 || rv == 2)) p.lj_rep |= 1u << c;
+        }
+        // (... at a reduced scale: libjpeg's transform size per component, the same rule on the scaled plane and the scaled ratios, and
+        // at 1/8 no filter at all -- jdsample.c turns fancy upsampling off when min_DCT_scaled_size is 1)
+        uint32_t red_gx = 0, red_gy = 0;
+        for (uint32_t c = 0; islow && scale != 1 && c < p.ncomp; c++) {
+            const uint32_t m = 8 / scale, nc = red_size(m, p.h[c], p.v[c], p.hmax, p.vmax);
+            const RedPlane g = red_plane(p.width, p.height, p.h[c], p.v[c], p.hmax, p.vmax, m, nc);
+            const uint32_t cw = g.cw, rh = g.rh, rv = g.rv;
+            p.red_n[c] = uint8_t(nc);
+            if (scale == 8 || (cw <= 2 && rh == 2 && (rv == 1 || rv == 2))) p.lj_rep |= 1u << c;
+            else { red_gx = std::max(red_gx, rh > 1 ? rh : 0u); red_gy = std::max(red_gy, rv > 1 ? rv : 0u); }
+        }
+        // (libjpeg's pixels: the rectangle grown by the filter's reach -- a pixel's chroma neighbours lie up to hmax x vmax pixels away;
+        // at a reduced scale one sample of the filtered component with the largest scaled ratio)
+        const uint32_t gx = islow && scale != 1 ? red_gx : lj && p.hmax > 1 ? p.hmax : 0u, gy = islow && scale != 1 ? red_gy : lj && p.vmax > 1 ? p.vmax : 0u;
         const uint32_t x0 = p.roi_x > gx ? p.roi_x - gx : 0u, x1 = std::min(p.out_w - 1, p.roi_x + p.roi_w - 1 + gx);
         const uint32_t y0 = p.roi_y > gy ? p.roi_y - gy : 0u, y1 = std::min(p.out_h - 1, p.roi_y + p.roi_h - 1 + gy);
         p.roi_mc0 = x0 / pw; p.roi_mc1 = x1 / pw;
         p.roi_mr0 = y0 / ph; p.roi_mr1 = y1 / ph;
-        p.lj = lj;
-        p.islow = islow;
-        // (jdsample.c takes its triangle filters for downsampled_width > 2 only: a narrower plane of ratios (2, 1) or (2, 2) is replicated)
-        for (uint32_t c = 0; islow && c < p.ncomp; c++) {
-            const uint32_t cw = (p.width * p.h[c] + p.hmax - 1) / p.hmax, rh = p.hmax / p.h[c], rv = p.vmax / p.v[c];
-            if (cw <= 2 && rh == 2 && (rv == 1 || rv == 2)) p.lj_rep |= 1u << c;
-        }
     }
     if (p.layout == MJX_LAYOUT_REF_COMPAT) {
         const uint64_t nb = uint64_t((p.width + 7) / 8) * ((p.height + 7) / 8);    // decoder.rs:164-166
@@ -623,7 +640,8 @@ StageBChoice stage_b_choice(const ImagePlan &p)
     // description with no resize behind it -- a resized picture's description is the resize's, stage B writes the packed
     // intermediate; (5) a rectangle; (6) the packed whole picture.  (This is the order in which the features' overwrites of the
     // mode used to follow one another, last writer first; tests/golden/stage_b_choice.npz holds what those gave.)
-    const StageBSink sink = p.lj ? (p.islow ? kSinkPlanesInt : kSinkPlanes) : p.ycc_on ? kSinkYcc : luma ? kSinkLuma : p.out_on && !p.rs_on ? kSinkOut
+    const bool red = p.lj && p.islow && p.scale > 1;     // (the integer inverse DCT at a reduced scale: a sink, a pass and a descriptor word of its own)
+    const StageBSink sink = p.lj ? (red ? kSinkPlanesRed : p.islow ? kSinkPlanesInt : kSinkPlanes) : p.ycc_on ? kSinkYcc : luma ? kSinkLuma : p.out_on && !p.rs_on ? kSinkOut
                           : p.cropped ? kSinkCropped : kSinkPacked;
     StageBChoice c;
     // (0) ahead of them all: a scan of a multi-scan file has no stage B.  Its tile geometry is still that of `form`.
@@ -638,10 +656,17 @@ StageBChoice stage_b_choice(const ImagePlan &p)
     c.out_ch = luma ? 1u : 0u;
     // (the integer inverse DCT's pictures with a replicated component are k_upsample_rep's, luminance or not.  A luminance picture
     // reads component 0 alone: only its own bit counts)
-    const uint32_t rep = !p.lj ? 0u : luma ? p.lj_rep & 1u : p.lj_rep;
+    const uint32_t rep = !p.lj || red ? 0u : luma ? p.lj_rep & 1u : p.lj_rep;
     c.lj_rep = rep ? kLjRepOn | rep | (luma ? kLjRepLuma : 0u) : 0u;
-    c.lj_luma = p.lj && luma && !rep ? 1u : 0u;              // (a luminance picture is k_upsample_luma's: component 0's plane alone)
-    c.lj_on = p.lj && !luma && !rep ? 1u : 0u;
+    c.lj_luma = p.lj && luma && !rep && !red ? 1u : 0u;      // (a luminance picture is k_upsample_luma's: component 0's plane alone)
+    c.lj_on = p.lj && !luma && !rep && !red ? 1u : 0u;
+    // (... at a reduced scale k_upsample_red's, luminance or not: every component's transform size and replicate bit, DevImage::lj_red)
+    c.lj_red = 0u;
+    for (uint32_t k = 0; red && k < 3u; k++) {
+        const uint32_t n = k < p.ncomp ? p.red_n[k] : 8u;
+        c.lj_red |= ((n >= 8u ? 3u : n >= 4u ? 2u : n >= 2u ? 1u : 0u) | (p.lj_rep >> k & 1u) << 2) << (4u * k);
+    }
+    if (red) c.lj_red |= kLjRedOn | (luma ? kLjRedLuma : 0u);
     c.lj_out = p.lj && p.out_on && !p.rs_on ? 1u : 0u;
     return c;
 }

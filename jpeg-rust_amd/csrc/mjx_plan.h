@@ -117,8 +117,12 @@ struct ImagePlan {
     // entries, zig-zag order, the table stage B multiplies by in place of qmult.  lj_rep: bit c -- component c's plane has at most two
     // columns and ratios (2, 1) or (2, 2), so jdsample.c replicates it (its downsampled_width > 2 condition); such a picture is
     // k_upsample_rep's.  Without the option both stay 0.
+    // ... and a scale of 2, 4 or 8 (kSinkPlanesRed): red_n[c] is the size N_c of the transform libjpeg picks for component c (red_size,
+    // mjx_kernels.h; 8 without a scale), its plane holds N_c samples per block side, and lj_rep is the same rule on the scaled plane and
+    // the scaled ratios -- every component at 1/8.  Such a picture is k_upsample_red's.
     bool islow = false;
     uint32_t lj_rep = 0;
+    uint8_t red_n[4] = {8, 8, 8, 8};
     uint32_t qint[4][64] = {};
     const uint8_t *scan = nullptr;
     size_t scan_len = 0;
@@ -159,7 +163,7 @@ struct ImagePlan {
 // What stage B and the passes behind it do with a planned picture: DevImage's fields of the same names (mjx_kernels.h), decided
 // here and nowhere else.  tile_420: the picture's tile is the 4:2:0 kernel's (tile_mcus_420) and not the generic power of two.
 struct StageBChoice {
-    uint32_t mode, rs_on, or_on, out_ch, lj_on, lj_luma, lj_out, lj_rep;
+    uint32_t mode, rs_on, or_on, out_ch, lj_on, lj_luma, lj_out, lj_rep, lj_red;
     bool tile_420;
 };
 StageBChoice stage_b_choice(const ImagePlan &p);
